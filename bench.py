@@ -2,15 +2,17 @@
 """bench.py — edges/sec of one GATv2 forward+backward step (hot path of GATv2_edge_based.cu) on
 N MI355X, on the OGBN-Products-shape synthetic power-law graph BASELINE.json quotes the metric on.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 A step = forward over all layers + output head + loss (scalars read back) + backward over all
 layers; optimizer / zero-grad excluded.  Inputs are resident in HBM before the timed
-region.  Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel class, timed live with
-HIP events on the context's stream inside the timed steps; `cpu_baseline` is the literal CPU
-restatement of the reference's algorithm (oracle/) on a bounded sample of the same graph law.
+region.  Rank 0 prints ONE JSON line.  A plain run measures only the headline (wall-clock time of the
+timed steps); `--full` adds the rest: per-step and per-kernel HIP-event timing inside the timed steps,
+`roofline` (the dominant kernel class) and `step_roofline`, and the CPU lines — `cpu_baseline` is the
+literal CPU restatement of the reference's algorithm (oracle/) on a bounded sample of the same graph law.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -44,7 +46,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="products", choices=sorted(PRESETS))
     ap.add_argument("--scale", type=float, default=1.0, help="shrink nodes and edges (debug only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-step / per-kernel HIP-event timing, the roofline "
+                         "objects and (N=1, unless --no-cpu-baseline) the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results (loss sum, #correct, parameter gradients) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU lines")
     ap.add_argument("--exchange-layer0", action="store_true",
                     help="N>1: do not replicate the input features; all-gather / reduce-scatter layer 0 too (A/B)")
     ap.add_argument("--cpu-sample-scale", type=float, default=0.0, help="0 = auto (~15 s of CPU work)")
@@ -198,6 +206,25 @@ def measured_traffic_src(args, world, kernel):
     return best, src
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(ctx, A, loss, correct, out_dir):
+    """What a caller of the timed path receives after its last step: the loss sum and #correct that step() returned, and
+    the parameter-gradient buffer (grads accumulate from the zero_grad before the timed steps, so it holds the sum over the
+    timed steps).  float64 scalars, float32 gradients; an array beyond its share of the 64 MB budget is written as a fixed
+    seeded sample of its elements (same indices on every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss_sum": np.array([loss], np.float64), "n_correct": np.array([correct], np.float64),
+              "grad_W": ctx.grads_get(A.PARAM_W), "grad_a": ctx.grads_get(A.PARAM_A), "grad_Wo": ctx.grads_get(A.PARAM_WO)}
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
     # native libraries (RCCL's version banner) write to fd 1: keep stdout for the one JSON line
@@ -238,7 +265,7 @@ def main():
     with torch.cuda.stream(stream):
         use_graph = args.graph and world == 1 and os.environ.get("GAT_FORCE_SHARDED") != "1"
         ctx = pkg.GatContext(heads, outdims, f, c, device=local_rank, stream=stream.cuda_stream,
-                             collect_timing=not use_graph, dtype=args.dtype)
+                             collect_timing=args.full and not use_graph, dtype=args.dtype)
         force_sharded = os.environ.get("GAT_FORCE_SHARDED") == "1"     # rehearse the N>1 code path on one GPU
         if world == 1 and force_sharded:
             import torch.distributed as dist
@@ -320,58 +347,71 @@ def main():
                 dist.barrier()
                 torch.cuda.synchronize(dev)
 
-        # per-step HIP events on the context's stream (median of the timed steps); recorded without a
+        # --full: per-step HIP events on the context's stream (median of the timed steps); recorded without a
         # host sync, read after the closing fence.  `value` stays the wall-clock total of the bracketed region.
-        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if args.full else None
         fence()
         t0 = time.perf_counter()
-        for i in range(args.steps):
-            ev[i][0].record(stream)
-            loss, correct = step()
-            ev[i][1].record(stream)
+        if args.full:
+            for i in range(args.steps):
+                ev[i][0].record(stream)
+                loss, correct = step()
+                ev[i][1].record(stream)
+        else:
+            for _ in range(args.steps):
+                loss, correct = step()
         fence()
         dt = time.perf_counter() - t0
-        step_ms = sorted(a.elapsed_time(b) for a, b in ev)
-        median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
-        stats = ctx.kernel_stats()
-        bytes_step, bytes_k = ctx.algorithmic_bytes()
+        if args.full:
+            step_ms = sorted(a.elapsed_time(b) for a, b in ev)
+            median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
+            stats = ctx.kernel_stats()
+            bytes_step, bytes_k = ctx.algorithmic_bytes()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(ctx, A, loss, correct, args.dump_outputs)
 
     if dist is not None:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-        bt = torch.tensor([bytes_step], dtype=torch.float64, device=dev)
-        dist.all_reduce(bt)
-        bytes_step_all = float(bt.item())
-    else:
+        if args.full:
+            bt = torch.tensor([bytes_step], dtype=torch.float64, device=dev)
+            dist.all_reduce(bt)
+            bytes_step_all = float(bt.item())
+    elif args.full:
         bytes_step_all = bytes_step
 
     if rank == 0:
         ms = dt / args.steps * 1e3
-        step_traffic = measured_traffic(args, world, None)
-        req_bytes_step = A.request_bytes_shape(heads, outdims, f, c, n, e, dtype=args.dtype)[0] if world == 1 and args.scale == 1.0 else None
-        timed = [k for k in stats if stats[k][0] > 0 and k not in ("misc", "exchange")]
-        if timed:
-            dom = max(timed, key=lambda k: stats[k][1])
-            launches, tot_ms = stats[dom]
-            per_launch_bytes = bytes_k[dom] * args.steps / launches
-            avg_ms = tot_ms / launches
-            achieved = per_launch_bytes / (avg_ms * 1e-3) / 1e9
-        # SURVEY 8d's byte count prices an attn_coeff write (forward) and read (backward) of E*H elements per layer that the
-        # training path never performs (alpha is recomputed from the per-row softmax statistics): the same quotients on the
-        # bytes this path's algorithm really needs are reported beside the contract's `frac` — never instead of it
-        b_store = 4 if args.dtype == "f32" else 2
-        alpha_dir = float(sum(e * h * b_store for h in heads)) if runner is None else 0.0
-        tp_bytes_step = bytes_step_all - 2.0 * alpha_dir if runner is None else None
-        pmc_note = ("traffic = L2-to-fabric request bytes (TCC_EA_RDREQ / WRREQ, rocprofv3 PMC): Infinity-Cache hits are counted in it "
-                    "(MI355X_MICROARCH.md, HBM), so it is an upper bound of DRAM bytes, and `frac` / `achieved` are fractions of SURVEY 8d's "
-                    "byte model (which assumes every gathered row misses), not a measured DRAM utilisation")
+        if args.full:
+            step_traffic = measured_traffic(args, world, None)
+            req_bytes_step = A.request_bytes_shape(heads, outdims, f, c, n, e, dtype=args.dtype)[0] if world == 1 and args.scale == 1.0 else None
+            timed = [k for k in stats if stats[k][0] > 0 and k not in ("misc", "exchange")]
+            if timed:
+                dom = max(timed, key=lambda k: stats[k][1])
+                launches, tot_ms = stats[dom]
+                per_launch_bytes = bytes_k[dom] * args.steps / launches
+                avg_ms = tot_ms / launches
+                achieved = per_launch_bytes / (avg_ms * 1e-3) / 1e9
+            # SURVEY 8d's byte count prices an attn_coeff write (forward) and read (backward) of E*H elements per layer that the
+            # training path never performs (alpha is recomputed from the per-row softmax statistics): the same quotients on the
+            # bytes this path's algorithm really needs are reported beside the contract's `frac` — never instead of it
+            b_store = 4 if args.dtype == "f32" else 2
+            alpha_dir = float(sum(e * h * b_store for h in heads)) if runner is None else 0.0
+            tp_bytes_step = bytes_step_all - 2.0 * alpha_dir if runner is None else None
+            pmc_note = ("traffic = L2-to-fabric request bytes (TCC_EA_RDREQ / WRREQ, rocprofv3 PMC): Infinity-Cache hits are counted in it "
+                        "(MI355X_MICROARCH.md, HBM), so it is an upper bound of DRAM bytes, and `frac` / `achieved` are fractions of SURVEY 8d's "
+                        "byte model (which assumes every gathered row misses), not a measured DRAM utilisation")
         line = {
             "metric": "edges/sec (fwd+bwd, 2-layer 8-head GATv2)" if len(heads) == 2 else
                       f"edges/sec (fwd+bwd, {len(heads)}-layer 8-head GATv2)",
             "value": e / (dt / args.steps), "unit": "edges/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms, "ms_per_step_median_hipevents": median_ms,
-            "ms_per_step_min_max_hipevents": [step_ms[0], step_ms[-1]], "higher_is_better": True, "scaling": "strong",
+            "warmup": args.warmup, "ms_per_step": ms,
+        }
+        if args.full:
+            line.update({"ms_per_step_median_hipevents": median_ms, "ms_per_step_min_max_hipevents": [step_ms[0], step_ms[-1]]})
+        line.update({
+            "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": "f32" if args.dtype == "f32" else "f32 arithmetic, bf16 PL/message storage",
             "data": "synthetic",
             "config": {
@@ -388,36 +428,39 @@ def main():
                 "loss_per_node": loss / n, "setup_s": round(t_gen, 1), "index_s": round(t_up, 2),
                 "generator": "device (csrc/gat_synth.hip), bit-for-bit synth.py" + (" — EXPERIMENT: sources sorted by popularity" if args.sorted_sources else ""),
             },
-            "step_roofline": {"algorithmic_GB_per_step": bytes_step_all / 1e9,
-                              "achieved_GBps": bytes_step_all / (dt / args.steps) / 1e9 / world,
-                              "frac_of_8TBps_per_gpu": bytes_step_all / (dt / args.steps) / 1e9 / world / HBM_PEAK_GBS,
-                              # HBM bytes the step really moves (sum of the PMC passes over all its kernels), and its
-                              # ratio to the algorithmic bytes: > 1 = traffic the algorithm does not need
-                              "traffic": step_traffic, "traffic_source": measured_traffic_src(args, world, None)[1],
-                              "traffic_over_algorithmic": (step_traffic / bytes_step_all) if step_traffic else None,
-                              # the same model with every per-edge gathered / scattered row rounded up to whole 128-byte fabric requests
-                              # (gat_request_bytes_shape): what the memory system can serve — differs from the figure above for bf16 rows at
-                              # H*D < 64 (config 5: 64-byte rows cost a line each); single GPU only
-                              "request_granular_GB_per_step": (req_bytes_step / 1e9) if req_bytes_step else None,
-                              "frac_request_granular": (req_bytes_step / (dt / args.steps) / 1e9 / HBM_PEAK_GBS) if req_bytes_step else None,
-                              "training_path_GB_per_step": (tp_bytes_step / 1e9) if tp_bytes_step else None,
-                              "frac_training_path": (tp_bytes_step / (dt / args.steps) / 1e9 / HBM_PEAK_GBS) if tp_bytes_step else None,
-                              "note": pmc_note},
-            "roofline": {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": measured_traffic(args, world, dom),
-                         "traffic_source": measured_traffic_src(args, world, dom)[1],
-                         "avg_launch_ms": avg_ms, "algorithmic_bytes_per_launch": per_launch_bytes,
-                         # the kernel's REAL HBM rate (PMC bytes / measured time): what the memory system delivers to it,
-                         # whatever share of those bytes the algorithm needs
-                         "achieved_traffic_GBps": (measured_traffic(args, world, dom) / (avg_ms * 1e-3) / 1e9)
-                                                  if measured_traffic(args, world, dom) else None,
-                         # the same kernel on the bytes the training path needs (no attn_coeff read / write: see above)
-                         "frac_training_path": ((per_launch_bytes - alpha_dir * args.steps / launches) / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
-                                               if (runner is None and dom in ("edge_forward", "edge_backward")) else None,
-                         "note": pmc_note} if timed else None,
-            "kernels_ms_per_step": {k: round(v[1] / args.steps, 4) for k, v in stats.items() if v[0] > 0},
-        }
-        if not args.no_cpu_baseline and world == 1:      # CPU lines: rank 0 at N = 1 only (the other ranks would wait in the barrier)
+        })
+        if args.full:
+            line.update({
+                "step_roofline": {"algorithmic_GB_per_step": bytes_step_all / 1e9,
+                                  "achieved_GBps": bytes_step_all / (dt / args.steps) / 1e9 / world,
+                                  "frac_of_8TBps_per_gpu": bytes_step_all / (dt / args.steps) / 1e9 / world / HBM_PEAK_GBS,
+                                  # HBM bytes the step really moves (sum of the PMC passes over all its kernels), and its
+                                  # ratio to the algorithmic bytes: > 1 = traffic the algorithm does not need
+                                  "traffic": step_traffic, "traffic_source": measured_traffic_src(args, world, None)[1],
+                                  "traffic_over_algorithmic": (step_traffic / bytes_step_all) if step_traffic else None,
+                                  # the same model with every per-edge gathered / scattered row rounded up to whole 128-byte fabric requests
+                                  # (gat_request_bytes_shape): what the memory system can serve — differs from the figure above for bf16 rows at
+                                  # H*D < 64 (config 5: 64-byte rows cost a line each); single GPU only
+                                  "request_granular_GB_per_step": (req_bytes_step / 1e9) if req_bytes_step else None,
+                                  "frac_request_granular": (req_bytes_step / (dt / args.steps) / 1e9 / HBM_PEAK_GBS) if req_bytes_step else None,
+                                  "training_path_GB_per_step": (tp_bytes_step / 1e9) if tp_bytes_step else None,
+                                  "frac_training_path": (tp_bytes_step / (dt / args.steps) / 1e9 / HBM_PEAK_GBS) if tp_bytes_step else None,
+                                  "note": pmc_note},
+                "roofline": {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": measured_traffic(args, world, dom),
+                             "traffic_source": measured_traffic_src(args, world, dom)[1],
+                             "avg_launch_ms": avg_ms, "algorithmic_bytes_per_launch": per_launch_bytes,
+                             # the kernel's REAL HBM rate (PMC bytes / measured time): what the memory system delivers to it,
+                             # whatever share of those bytes the algorithm needs
+                             "achieved_traffic_GBps": (measured_traffic(args, world, dom) / (avg_ms * 1e-3) / 1e9)
+                                                      if measured_traffic(args, world, dom) else None,
+                             # the same kernel on the bytes the training path needs (no attn_coeff read / write: see above)
+                             "frac_training_path": ((per_launch_bytes - alpha_dir * args.steps / launches) / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
+                                                   if (runner is None and dom in ("edge_forward", "edge_backward")) else None,
+                             "note": pmc_note} if timed else None,
+                "kernels_ms_per_step": {k: round(v[1] / args.steps, 4) for k, v in stats.items() if v[0] > 0},
+            })
+        if args.full and not args.no_cpu_baseline and world == 1:      # CPU lines: rank 0 at N = 1 only (the other ranks would wait in the barrier)
             line["cpu_baseline"] = cpu_baseline(pkg, args.workload, heads, outdims, args.cpu_sample_scale)
             line["cpu_baseline_restructured"] = cpu_baseline_restructured(pkg, args.workload, heads, outdims)
             line["cpu_baseline_cora_shape"] = cpu_baseline_cora_shape(pkg)          # "Cora-shape always"

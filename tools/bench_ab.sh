@@ -9,7 +9,7 @@ for e in "$@"; do
   echo "$i: $e" >> "$out/ab_index.txt"
   # GAT_DBG (timing-only / wrong-result experiments) exists only in the experiment library
   case "$e" in *GAT_DBG*) e="$e GATV2_LIB=$root/graph-attention-network-gatv2-_amd/libgatv2_hip_exp.so";; esac
-  env $e timeout -k 10 300 python bench.py --workload "$wl" --dtype "$dt" --no-cpu-baseline --steps ${STEPS:-10} --warmup 3 > "$out/ab_$i.json" 2> "$out/ab_$i.err" || { echo "run $i failed"; tail -5 "$out/ab_$i.err"; exit 1; }
+  env $e timeout -k 10 300 python bench.py --workload "$wl" --dtype "$dt" --full --no-cpu-baseline --steps ${STEPS:-10} --warmup 3 > "$out/ab_$i.json" 2> "$out/ab_$i.err" || { echo "run $i failed"; tail -5 "$out/ab_$i.err"; exit 1; }
   python - "$out/ab_$i.json" "$e" <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1]))
