@@ -53,6 +53,7 @@ COMM_PIPELINE = 2
 COMM_HALO = 3
 (TAP_SRC, TAP_DST, TAP_ALPHA, TAP_HPRE, TAP_HOUT, TAP_Y, TAP_G, TAP_GE, TAP_MAX, TAP_SUM, TAP_PL,
  TAP_PR, TAP_SCORE, TAP_GALPHA, TAP_GX) = range(15)
+TAP_ATTN_KEEP, TAP_FEAT_KEEP = 15, 16       # dropout factors (0 or 1/(1-p)) for the step the counter holds
 (K_PROJECT, K_EDGE_FWD, K_HEAD_FWD, K_HEAD_BWD, K_EDGE_BWD, K_GPL_SUM, K_GRAD_W, K_GRAD_X, K_MISC,
  K_EXCHANGE, K_EDGE_FUSED, K_COUNT) = range(12)
 COMM_ID_BYTES = 128
@@ -189,6 +190,10 @@ def _declare(lib: C.CDLL) -> None:
         "gat_synth_features_device": [C.c_uint64, i64, i64, i32, i32, vp, vp],
         "gat_synth_labels_device": [C.c_uint64, i64, i64, i32, vp, vp],
         "gat_synth_argsort_u64": [vp, i64, vp, vp],
+        "gat_set_dropout": [vp, f32, f32, C.c_uint64, C.c_uint64],
+        "gat_set_training": [vp, i32],
+        "gat_dropout_step": [vp, P(C.c_uint64)],
+        "gat_set_shard_bounds": [vp, i32, vp],
     }
     for name, argt in sigs.items():
         fn = getattr(lib, name)          # AttributeError here == symbol missing from the .so
@@ -364,6 +369,25 @@ class GatContext:
     def n_params(self) -> int:
         return self.param_count(PARAM_W) + self.param_count(PARAM_A) + self.param_count(PARAM_WO)
 
+    # -- dropout (gatv2_abi.h "dropout")
+    def set_dropout(self, feat_p: float = 0.0, attn_p: float = 0.0, seed: int = 0, first_step: int = 0):
+        """Inverted feature / attention dropout in training mode; p in [0, 1).  The mask counter starts at first_step."""
+        _chk(self.lib.gat_set_dropout(self._ctx, float(feat_p), float(attn_p), int(seed) & (2 ** 64 - 1), int(first_step)))
+
+    def set_training(self, training: bool = True):
+        """False: eval mode (no dropout, the counter does not advance)."""
+        _chk(self.lib.gat_set_training(self._ctx, int(bool(training))))
+
+    def dropout_step(self) -> int:
+        st = C.c_uint64()
+        _chk(self.lib.gat_dropout_step(self._ctx, C.byref(st)))
+        return st.value
+
+    def set_shard_bounds(self, bounds):
+        """Global row boundaries [world+1] of the shard plan: the masks use unsharded node ids."""
+        b = np.ascontiguousarray(bounds, np.int64)
+        _chk(self.lib.gat_set_shard_bounds(self._ctx, len(b) - 1, _np_ptr(b)))
+
     # -- step
     def forward(self, want_loss: bool = True):
         if not want_loss:
@@ -486,6 +510,7 @@ class GatContext:
             TAP_PL: ((self.n_table, H * D), np.float32), TAP_PR: ((N, H * D), np.float32),
             TAP_SCORE: ((H, E), np.float32), TAP_GALPHA: ((H, E), np.float32),
             TAP_GX: ((N, self.heads[l - 1] * self.outdims[l - 1] if l > 0 else 0), np.float32),
+            TAP_ATTN_KEEP: ((H, E), np.float32), TAP_FEAT_KEEP: ((N, self.in_dims[l]), np.float32),
         }
         shape, dt = shapes[tensor]
         out = np.empty(shape, dt)

@@ -176,6 +176,14 @@ struct gat_ctx {
     float* gfull = nullptr;                         // [n_rows][HDmax] dL/dh_pre incl. LReLU' (stash path: gathered by the pull pass)
     uint8_t* hbits = nullptr;                       // [n_rows][HD_last/N] LReLU'(h_pre) decisions of the last layer (EdgeBwdArgs::hbits)
     int32_t dbg = 0;                                // GAT_DBG timing experiments (0 = product behaviour)
+    // dropout (gatv2_abi.h "dropout"): probabilities, seed, mode, the device step counter, the unsharded node ids of a shard
+    float drop_pf = 0.f, drop_pa = 0.f;
+    uint64_t drop_seed = 0;
+    bool training = true;
+    uint64_t* drop_step = nullptr;                  // [1] device: advanced by the layer-0 projection of a training forward
+    int64_t* drop_bounds = nullptr; int64_t drop_max_rows = 0;    // gat_set_shard_bounds (null: node id = table row)
+    std::vector<float*> xdrop;                      // [L] layer inputs after feature dropout (rows as Xin_of), allocated with p_f > 0
+    float* xdrop_tab = nullptr;                     // the replicated layer-0 input after feature dropout
     gat::WorkList work;                             // host copy of the item list
     int4* items = nullptr; int4* slot_info = nullptr;
     float* part_acc = nullptr; float* part_mz = nullptr;
@@ -262,7 +270,24 @@ static float* Wo_of(gat_ctx* c) { return c->params + c->nW + c->nA; }
 static float* gW_of(gat_ctx* c, int l) { return c->grads + c->layers[l].w_off; }
 static float* ga_of(gat_ctx* c, int l) { return c->grads + c->nW + c->layers[l].a_off; }
 static float* gWo_of(gat_ctx* c) { return c->grads + c->nW + c->nA; }
-static const float* Xin_of(gat_ctx* c, int l) { return l == 0 ? c->X0 : c->layers[l - 1].hout; }
+static bool feat_drop_on(const gat_ctx* c) { return c->training && c->drop_pf > 0.f; }
+static bool attn_drop_on(const gat_ctx* c) { return c->training && c->drop_pa > 0.f; }
+static bool drop_on(const gat_ctx* c) { return feat_drop_on(c) || attn_drop_on(c); }
+// what layer l reads as its input: x_l, or x_l with the feature-dropout mask applied (projection and grad_W alike)
+static const float* Xin_raw(gat_ctx* c, int l) { return l == 0 ? c->X0 : c->layers[l - 1].hout; }
+static const float* Xin_of(gat_ctx* c, int l) { return feat_drop_on(c) && (size_t)l < c->xdrop.size() && c->xdrop[(size_t)l] ? c->xdrop[(size_t)l] : Xin_raw(c, l); }
+static const float* Xtab_of(gat_ctx* c) { return feat_drop_on(c) && c->xdrop_tab ? c->xdrop_tab : c->Xtab; }
+static DropArgs drop_args(gat_ctx* c, int32_t kind, int32_t l) {
+    const double p = kind == kDropAttn ? c->drop_pa : c->drop_pf;
+    DropArgs d{};
+    d.step = c->drop_step; d.bounds = c->drop_bounds; d.max_rows = c->drop_max_rows; d.row0 = c->table_row0;
+    d.seed_lo = (uint32_t)c->drop_seed; d.seed_hi = (uint32_t)(c->drop_seed >> 32);
+    d.T = (uint32_t)std::min<double>(16777216.0, std::floor(p * 16777216.0 + 0.5));
+    d.scale = (float)(1.0 / (1.0 - p));
+    d.layer = l;
+    d.on = 1;
+    return d;
+}
 static int32_t ldX_of(gat_ctx* c, int l) { return l == 0 ? c->ld0 : c->layers[l].F; }
 // rows of in_dim floats -> rows of ld0 floats with zeros behind column in_dim
 static int upload_rows_padded(gat_ctx* c, float* dst, const float* src, int64_t n_rows, int32_t in_dim, hipMemcpyKind kind) {
@@ -277,6 +302,17 @@ static int upload_rows_padded(gat_ctx* c, float* dst, const float* src, int64_t 
 static float* gPL_of(gat_ctx* c, int l) { return (c->ov_active && (l & 1)) ? c->gPL_alt : c->gPL; }
 static float* gPR_of(gat_ctx* c, int l) { return (c->ov_active && (l & 1)) ? c->gPR_alt : c->gPR; }
 
+// feature-dropout copies of the layer inputs (only once p_f > 0 was set on a complete context)
+static int ensure_drop_buffers(gat_ctx* c) {
+    if (!c->buffers_ready || c->drop_pf <= 0.f) return 0;
+    const int L = c->cfg.num_layers;
+    if (c->xdrop.empty()) {
+        c->xdrop.assign((size_t)L, nullptr);
+        for (int l = 0; l < L; ++l) GAT_TRY(dalloc(c, &c->xdrop[(size_t)l], c->n_rows * (l == 0 ? c->ld0 : c->layers[l].F)));
+    }
+    if (c->Xtab && !c->xdrop_tab) GAT_TRY(dalloc(c, &c->xdrop_tab, c->n_table * c->ld0));
+    return 0;
+}
 // (re)allocate everything that depends on the graph size
 static int ensure_buffers(gat_ctx* c) {
     if (c->buffers_ready) return 0;
@@ -430,6 +466,7 @@ static int ensure_buffers(gat_ctx* c) {
     GAT_TRY(dalloc(c, &c->correct_out, 1));
     GAT_TRY(dalloc(c, &c->y, N * C));
     c->buffers_ready = true;
+    GAT_TRY(ensure_drop_buffers(c));
     // The cliff of gatv2_abi.h "Limits": a layer whose SHAPE has wave-per-row kernels but whose gathered table is 4 GiB or
     // more drops to the generic float-atomic kernels.  Not an error (same results) — but never silent: the call that
     // completed the context returns 0 with this text in gat_last_error(), and gat_layer_path() reports it per layer.
@@ -798,24 +835,43 @@ int gat_params_init(gat_ctx* c, uint64_t seed) {
 }
 
 // ---- phases --------------------------------------------------------------------------------------------------
+// Training forward with dropout: layer 0 advances the step counter first (one lane, captured like any other kernel), then every
+// layer with p_f > 0 writes its masked input x' = x (.) kappa s_f, which the projection and grad_W read instead of x.
+static int drop_prepare_input(gat_ctx* c, int32_t l) {
+    if (!drop_on(c)) return 0;
+    if (l == 0) GAT_TRY(launch_drop_advance(c->drop_step, c->stream));
+    if (!feat_drop_on(c)) return 0;
+    if (c->xdrop.empty() || (c->Xtab && !c->xdrop_tab)) GAT_TRY(ensure_drop_buffers(c));
+    const Layer& y = c->layers[l];
+    DropArgs d = drop_args(c, kDropFeat, l);
+    GAT_TRY(launch_feat_drop_fwd(Xin_raw(c, l), c->xdrop[(size_t)l], c->n_rows, y.F, ldX_of(c, l), d, c->stream));
+    if (l == 0 && c->Xtab) {      // the replicated table: its rows are table rows, the same node ids
+        d.row0 = 0;
+        GAT_TRY(launch_feat_drop_fwd(c->Xtab, c->xdrop_tab, c->n_table, y.F, c->ld0, d, c->stream));
+    }
+    return 0;
+}
 int gat_layer_project(gat_ctx* c, int32_t l) {
     GAT_TRY(check_layer(c, l));
     Layer& y = c->layers[l];
     Scope t(c, GAT_K_PROJECT);
+    GAT_TRY(drop_prepare_input(c, l));
     if (l == 0 && c->Xtab) {      // replicated input: whole PL table from the table rows, PR from the shard's rows
-        GAT_TRY(launch_project(c->Xtab, W_of(c, l), y.PL, nullptr, c->n_table, y.F, y.HD, kPartLeft, bf16(c), c->gw_scratch, c->gw_scratch_floats, c->stream, c->ld0));
-        return launch_project(c->X0, W_of(c, l), nullptr, y.PR, c->n_rows, y.F, y.HD, kPartRight, bf16(c), c->gw_scratch, c->gw_scratch_floats, c->stream, c->ld0);
+        GAT_TRY(launch_project(Xtab_of(c), W_of(c, l), y.PL, nullptr, c->n_table, y.F, y.HD, kPartLeft, bf16(c), c->gw_scratch, c->gw_scratch_floats, c->stream, c->ld0));
+        return launch_project(Xin_of(c, 0), W_of(c, l), nullptr, y.PR, c->n_rows, y.F, y.HD, kPartRight, bf16(c), c->gw_scratch, c->gw_scratch_floats, c->stream, c->ld0);
     }
     float* own_rows = reinterpret_cast<float*>(reinterpret_cast<char*>(y.PL) + c->table_row0 * y.HD * st_bytes(c));
     return launch_project(Xin_of(c, l), W_of(c, l), own_rows, y.PR, c->n_rows, y.F, y.HD, kPartBoth, bf16(c), c->gw_scratch, c->gw_scratch_floats, c->stream, ldX_of(c, l));
 }
 
 static EdgeFwdArgs plan_forward_edges(gat_ctx* c, int32_t l);
+static DropArgs attn_drop_args(gat_ctx* c, int32_t l) { return attn_drop_on(c) ? drop_args(c, kDropAttn, l) : DropArgs{}; }
 int gat_layer_forward_edges(gat_ctx* c, int32_t l) {
     GAT_TRY(check_layer(c, l));
     const EdgeFwdArgs a = plan_forward_edges(c, l);
+    const DropArgs d = attn_drop_args(c, l);
     Scope t(c, GAT_K_EDGE_FWD);
-    return launch_edge_forward(a, c->stream);
+    return launch_edge_forward(a, c->stream, &d);
 }
 static EdgeFwdArgs plan_forward_edges(gat_ctx* c, int32_t l) {
     Layer& y = c->layers[l];
@@ -865,7 +921,7 @@ int gat_head_backward(gat_ctx* c) {
 }
 
 // Arguments of layer l's edge backward (shared by gat_layer_backward_edges and the fused last layer of gat_step).
-struct BwdPlan { EdgeBwdArgs a; bool store, stash, last_g; };
+struct BwdPlan { EdgeBwdArgs a; bool store, stash, last_g; DropArgs drop; };
 static int plan_backward_edges(gat_ctx* c, int32_t l, BwdPlan* P) {
     Layer& y = c->layers[l];
     const bool store = c->msg != nullptr && edge_fast_path(y.H, y.D, c->n_table);
@@ -893,7 +949,8 @@ static int plan_backward_edges(gat_ctx* c, int32_t l, BwdPlan* P) {
     a.part_acc = c->part_acc;
     a.dbg = c->dbg;
     a.ga_partial = c->ga_partial + (int64_t)l * 2048 * c->HDmax; a.n_rows = c->n_rows; a.n_table = c->n_table; a.bf16 = bf16(c); a.H = y.H; a.D = y.D;
-    a.ga_blocks = edge_fast_path(y.H, y.D, c->n_table) ? edge_backward_blocks(c->work.n_items, y.H, y.D, store, y.ge != nullptr, bf16(c), stash)
+    P->drop = attn_drop_args(c, l);
+    a.ga_blocks = edge_fast_path(y.H, y.D, c->n_table) ? edge_backward_blocks(c->work.n_items, y.H, y.D, store, y.ge != nullptr, bf16(c), stash, P->drop.on != 0)
                                            : edge_backward_blocks(c->n_rows * 4, y.H, y.D, false, false, false);
     a.slope = c->cfg.negative_slope;
     P->a = a; P->store = store; P->stash = stash; P->last_g = last_g;
@@ -927,7 +984,7 @@ int gat_layer_backward_edges(gat_ctx* c, int32_t l) {
     }
     {
         Scope t(c, GAT_K_EDGE_BWD);
-        GAT_TRY(launch_edge_backward(P.a, c->stream));
+        GAT_TRY(launch_edge_backward(P.a, c->stream, &P.drop));
     }
     GAT_TRY(sum_backward_edges(c, l, P));
     Scope t(c, GAT_K_MISC);
@@ -940,8 +997,8 @@ static int backward_grad_w(gat_ctx* c, int32_t l, hipStream_t st) {
     const float* gPL_rows = gPL_of(c, l) + c->table_row0 * y.HD;
     Scope t(c, GAT_K_GRAD_W, st);
     if (l == 0 && c->Xtab) {  // partial gPL over the whole table x replicated input; the gradient all-reduce sums shards
-        GAT_TRY(launch_grad_w(gPL_of(c, l), nullptr, c->Xtab, gW_of(c, l), c->gw_scratch, c->n_table, y.F, y.HD, kPartLeft, st, c->ld0));
-        return launch_grad_w(nullptr, gPR_of(c, l), c->X0, gW_of(c, l), c->gw_scratch, c->n_rows, y.F, y.HD, kPartRight, st, c->ld0);
+        GAT_TRY(launch_grad_w(gPL_of(c, l), nullptr, Xtab_of(c), gW_of(c, l), c->gw_scratch, c->n_table, y.F, y.HD, kPartLeft, st, c->ld0));
+        return launch_grad_w(nullptr, gPR_of(c, l), Xin_of(c, 0), gW_of(c, l), c->gw_scratch, c->n_rows, y.F, y.HD, kPartRight, st, c->ld0);
     }
     return launch_grad_w(gPL_rows, gPR_of(c, l), Xin_of(c, l), gW_of(c, l), c->gw_scratch + c->gw_off[(size_t)l], c->n_rows, y.F, y.HD, kPartBoth, st, ldX_of(c, l));
 }
@@ -952,8 +1009,11 @@ static int backward_grad_x(gat_ctx* c, int32_t l) {
     Scope t(c, GAT_K_GRAD_X);
     // plain dL/d(input) of this layer: the LReLU'(h_pre) factor of E:888-892 is applied by the edge backward
     // of layer l-1, which reads h_pre anyway (the epilogue's extra read of h_pre cost 0.45 of 1.03 ms)
-    return launch_grad_x(gPL_rows, gPR_of(c, l), W_of(c, l), nullptr, c->layers[l - 1].g, c->n_rows, y.F, y.HD,
-                         c->cfg.negative_slope, c->stream);
+    GAT_TRY(launch_grad_x(gPL_rows, gPR_of(c, l), W_of(c, l), nullptr, c->layers[l - 1].g, c->n_rows, y.F, y.HD,
+                          c->cfg.negative_slope, c->stream));
+    // feature dropout: dL/dx_l = dL/dx'_l (.) kappa s_f, before the LReLU' factor of layer l-1 (applied by its edge backward)
+    if (feat_drop_on(c)) return launch_feat_drop_bwd(c->layers[l - 1].g, c->n_rows, y.F, drop_args(c, kDropFeat, l), c->stream);
+    return 0;
 }
 int gat_layer_backward_dense(gat_ctx* c, int32_t l) {
     GAT_TRY(check_layer(c, l));
@@ -993,6 +1053,7 @@ static int forward_exchange_pipelined(gat_ctx* c, int l) {
     const int64_t rowf = y.HD * st_bytes(c) / 4;                           // floats per PL row (bf16 rows: half)
     char* own_rows = reinterpret_cast<char*>(y.PL) + c->table_row0 * y.HD * st_bytes(c);
     Scope t(c, GAT_K_EXCHANGE);                                            // timed as a whole: projection chunks + their exchanges
+    GAT_TRY(drop_prepare_input(c, l));
     for (int k = 0; k < K; ++k) {
         const int64_t r0 = (int64_t)k * rpc, r1s = std::min<int64_t>(r0 + rpc, max_rows), r1 = std::min<int64_t>(r1s, c->n_rows);
         if (r0 >= max_rows) break;
@@ -1064,7 +1125,7 @@ static bool fused_last(gat_ctx* c) {
     if (!fused_head(c) || bf16(c) || c->comm || c->n_table != c->n_rows || c->cfg.flat_lrelu_index) return false;
     const Layer& y = c->layers.back();
     if (!edge_fast_path(y.H, y.D, c->n_table) || !y.stash || c->stash == nullptr || c->gH == nullptr) return false;
-    if (!edge_last_fused_supported(y.H, y.D, c->cfg.num_classes) || c->dbg != 0) return false;
+    if (!edge_last_fused_supported(y.H, y.D, c->cfg.num_classes) || c->dbg != 0 || drop_on(c)) return false;   // no dropout form
     // MEASURED, NOT THE DEFAULT (DESIGN §4 "Round 3"): on the Products shape the fused launch takes 5.0 ms for the 76 % of the edges
     // that sit in unsplit rows — what the separate forward + backward take for them — and the split rows' segments, launched on
     // their own, lose what they used to hide behind the bulk: 20.95 vs 20.78 ms per step.  GAT_FUSE_LAST=1 enables.
@@ -1344,6 +1405,61 @@ int gat_step_graph(gat_ctx* c, int32_t enable) {
     c->graph_state = enable ? 1 : 0;
     return 0;
 }
+// ---- dropout ---------------------------------------------------------------------------------------------------
+int gat_set_dropout(gat_ctx* c, float feat_p, float attn_p, uint64_t seed, uint64_t first_step) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (!(feat_p >= 0.f && feat_p < 1.f)) return fail(GAT_E_INVALID, "gat_set_dropout: feat_p must be in [0, 1)");
+    if (!(attn_p >= 0.f && attn_p < 1.f)) return fail(GAT_E_INVALID, "gat_set_dropout: attn_p must be in [0, 1)");
+#ifdef GAT_EXPERIMENTS                               // (the release library does not know the switch's name)
+    if (c->dbg != 0 && (feat_p > 0.f || attn_p > 0.f))
+        return fail(GAT_E_UNSUPPORTED, "gat_set_dropout: not with a GAT_DBG timing experiment (those kernels have no dropout form)");
+#endif
+    if (!c->drop_step) GAT_TRY(dalloc(c, &c->drop_step, 1));
+    GAT_HIP(hipMemcpyAsync(c->drop_step, &first_step, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    graph_drop(c);                                       // a captured step holds the other kernel sequence
+    c->drop_pf = feat_p; c->drop_pa = attn_p; c->drop_seed = seed;
+    return ensure_drop_buffers(c);
+}
+int gat_set_training(gat_ctx* c, int32_t training) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (training != 0 && training != 1) return fail(GAT_E_INVALID, "gat_set_training: 0 (eval) or 1 (training)");
+    if (c->training != (training == 1)) graph_drop(c);
+    c->training = training == 1;
+    return 0;
+}
+int gat_dropout_step(gat_ctx* c, uint64_t* step) {
+    if (!c || !step) return fail(GAT_E_INVALID, "null argument");
+    *step = 0;
+    if (!c->drop_step) return 0;
+    GAT_HIP(hipMemcpyAsync(step, c->drop_step, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+int gat_set_shard_bounds(gat_ctx* c, int32_t world, const int64_t* bounds) {
+    if (!c || !bounds) return fail(GAT_E_INVALID, "null argument");
+    if (!c->have_graph) return fail(GAT_E_STATE, "gat_set_shard_bounds: set the graph first");
+    if (world < 1 || c->n_table % world != 0) return fail(GAT_E_INVALID, "gat_set_shard_bounds: n_table is not world slices of equal size");
+    const int64_t max_rows = c->n_table / world;
+    if (bounds[0] != 0) return fail(GAT_E_INVALID, "gat_set_shard_bounds: bounds[0] must be 0");
+    for (int32_t r = 0; r < world; ++r)
+        if (bounds[r + 1] < bounds[r] || bounds[r + 1] - bounds[r] > max_rows)
+            return fail(GAT_E_INVALID, "gat_set_shard_bounds: every rank's row range must be ascending and fit its table slice");
+    const int64_t rank = c->table_row0 / max_rows;
+    if (c->table_row0 % max_rows != 0 || rank >= world || bounds[rank + 1] - bounds[rank] != c->n_rows)
+        return fail(GAT_E_INVALID, "gat_set_shard_bounds: bounds do not match this shard's table_row0 / n_rows");
+    if (!c->drop_bounds) GAT_TRY(dalloc(c, &c->drop_bounds, (int64_t)world + 1));
+    else if (c->drop_max_rows != max_rows) {
+        dfree(c, c->drop_bounds);
+        GAT_TRY(dalloc(c, &c->drop_bounds, (int64_t)world + 1));
+    }
+    GAT_HIP(hipMemcpyAsync(c->drop_bounds, bounds, ((size_t)world + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    graph_drop(c);
+    c->drop_max_rows = max_rows;
+    return 0;
+}
+
 int gat_step(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
     GAT_TRY(check_step(c, "gat_step"));
     if (c->graph_state != 0) return step_graph(c, loss_sum, n_correct);
@@ -1570,6 +1686,20 @@ int gat_tap(gat_ctx* c, int tensor, int32_t l, void* host, int64_t count) {
             return 0;
         }
         case GAT_TAP_PR: GAT_TRY(need(N * y.HD)); return d2h(c, host, y.PR, N * y.HD * sizeof(float));
+        case GAT_TAP_ATTN_KEEP:
+        case GAT_TAP_FEAT_KEEP: {                      // the masks for the step the counter holds, from the kernels' own device functions
+            const bool attn = tensor == GAT_TAP_ATTN_KEEP;
+            const int64_t n = attn ? E * y.H : N * y.F;
+            GAT_TRY(need(n));
+            if (!c->drop_step) return fail(GAT_E_STATE, "gat_tap: dropout was never set (gat_set_dropout)");
+            float* tmp = nullptr;
+            GAT_HIP(hipMalloc((void**)&tmp, (size_t)std::max<int64_t>(n, 1) * sizeof(float)));
+            const DropArgs d = drop_args(c, attn ? kDropAttn : kDropFeat, l);
+            int rc = attn ? launch_attn_keep_tap(c->row_ptr, N, E, y.H, d, tmp, c->stream) : launch_feat_keep_tap(N, y.F, d, tmp, c->stream);
+            if (rc == 0) rc = d2h(c, host, tmp, (size_t)n * sizeof(float));
+            (void)hipFree(tmp);
+            return rc;
+        }
         default: return fail(GAT_E_INVALID, "gat_tap: unknown tensor id");
     }
 }

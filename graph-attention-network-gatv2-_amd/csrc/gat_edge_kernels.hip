@@ -36,6 +36,17 @@ constexpr float kLn2 = 0.6931471805599453f;
 
 __device__ __forceinline__ float lrelu(float v, float s) { return v > 0.f ? v : v * s; }
 __device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }   // v_exp_f32
+// attention dropout (gatv2_abi.h "dropout"): kappa * s_a of edge k of a row (kd = mix(K(1, l), node(dst))) and head h
+__device__ __forceinline__ float attn_keep(const DropArgs& d, uint32_t kd, int k, int h) {
+    return drop_factor(d, drop_mix(drop_mix(kd, (uint32_t)k), (uint32_t)h));
+}
+// kernel argument of the DROP instantiations: the plain struct + the mask parameters (the default ones keep the plain struct)
+template <bool DROP> struct FwdArgsOf { typedef EdgeFwdArgs T; };
+template <> struct FwdArgsOf<true> { typedef EdgeFwdDropArgs T; };
+template <bool DROP> struct BwdArgsOf { typedef EdgeBwdArgs T; };
+template <> struct BwdArgsOf<true> { typedef EdgeBwdDropArgs T; };
+template <bool DROP> using FwdArgsT = typename FwdArgsOf<DROP>::T;
+template <bool DROP> using BwdArgsT = typename BwdArgsOf<DROP>::T;
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {
@@ -220,10 +231,10 @@ __device__ __forceinline__ void store_row(float* __restrict__ msg, int slot, int
 
 // One chunk of UU slots per edge group: UU independent gathers issued back to back (indices
 // clamped into the item, so loads need no predicate), then scores, then the online-softmax update.
-template <int HD, int D, int UU, int USC, bool ALPHA, bool BF>
-__device__ __forceinline__ void fwd_chunk(const EdgeFwdArgs& A, int e0, int e_end, int e_end_v, int c, int gidx,
+template <int HD, int D, int UU, int USC, bool ALPHA, bool BF, bool DROP = false, class AT = EdgeFwdArgs>
+__device__ __forceinline__ void fwd_chunk(const AT& A, int e0, int e_end, int e_end_v, int c, int gidx,
                                           float pr, float ac2, bool multi, float (&sc)[USC], float& m, float& Z,
-                                          float& acc) {
+                                          float& acc, uint32_t kd = 0, int rb = 0) {
     constexpr int G = 64 / HD;
     constexpr int H = HD / D;
     float v[UU];
@@ -257,7 +268,8 @@ __device__ __forceinline__ void fwd_chunk(const EdgeFwdArgs& A, int e0, int e_en
     for (int u = 0; u < UU; ++u) {
         const float p = exp2_fast(sc[u] - mn);       // 0 for padded slots
         Z += p;
-        acc = fmaf(p, v[u], acc);
+        if constexpr (DROP) acc = fmaf(p * attn_keep(A.drop, kd, e0 + u * G + gidx - rb, c / D), v[u], acc);   // the term, not Z
+        else acc = fmaf(p, v[u], acc);
     }
     m = mn;
     if (ALPHA && multi) {                            // park raw scores; normalised later
@@ -271,8 +283,8 @@ __device__ __forceinline__ void fwd_chunk(const EdgeFwdArgs& A, int e0, int e_en
 }
 
 // ALPHA: also materialise attn_coeff [E][H] (parity taps only; the training path never needs it).
-template <int HD, int D, bool ALPHA, bool BF = false>
-__global__ __launch_bounds__(256) void edge_fwd_kernel(EdgeFwdArgs A) {
+template <int HD, int D, bool ALPHA, bool BF = false, bool DROP = false>
+__global__ __launch_bounds__(256) void edge_fwd_kernel(FwdArgsT<DROP> A) {
     constexpr int G = 64 / HD;      // edges per wave-instruction
     constexpr int U = 16 / G;       // gathers in flight per group
     constexpr int CH = 16;          // edges per chunk (= U*G)
@@ -294,13 +306,16 @@ __global__ __launch_bounds__(256) void edge_fwd_kernel(EdgeFwdArgs A) {
     float sc[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) sc[u] = -INFINITY;
+    uint32_t kd = 0;
+    int rb = 0;
+    if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; }
 
     for (int e0 = b; e0 < e_end; e0 += CH) {
         if constexpr (U >= 2) {
-            if (e_end - e0 <= CH / 2) fwd_chunk<HD, D, U / 2, U, ALPHA, BF>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc);
-            else fwd_chunk<HD, D, U, U, ALPHA, BF>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc);
+            if (e_end - e0 <= CH / 2) fwd_chunk<HD, D, U / 2, U, ALPHA, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, kd, rb);
+            else fwd_chunk<HD, D, U, U, ALPHA, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, kd, rb);
         } else {
-            fwd_chunk<HD, D, U, U, ALPHA, BF>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc);
+            fwd_chunk<HD, D, U, U, ALPHA, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, kd, rb);
         }
     }
 
@@ -399,10 +414,10 @@ __global__ __launch_bounds__(256) void edge_fwd_fix_kernel(EdgeFwdArgs A) {
 //   grad_a += ge LReLU(s)   gPR[dst] += gs   gPL[src] += g alpha + gs   (E:769-782, 859-869)
 // STORE: message row -> its CSC slot (summed per source by gpl_sum_kernel); else float atomics.
 // ------------------------------------------------------------------------------------------------
-template <int HD, int D, int UU, bool STORE, bool TAPS, int DBG, bool BF>
-__device__ __forceinline__ void bwd_chunk(const EdgeBwdArgs& A, int e0, int e_end, int e_end_v, int c, int gidx,
+template <int HD, int D, int UU, bool STORE, bool TAPS, int DBG, bool BF, bool DROP = false, class AT = EdgeBwdArgs>
+__device__ __forceinline__ void bwd_chunk(const AT& A, int e0, int e_end, int e_end_v, int c, int gidx,
                                           float g, float pr, float dot, float ac, float ac2, float m2, float inv,
-                                          float& ga, float& gpr) {
+                                          float& ga, float& gpr, uint32_t kd = 0, int rb = 0) {
     constexpr int G = 64 / HD;
     constexpr int H = HD / D;
     float v[UU];
@@ -429,6 +444,11 @@ __device__ __forceinline__ void bwd_chunk(const EdgeBwdArgs& A, int e0, int e_en
 #pragma unroll
         for (int q = 0; q < P; ++q) { al[q] = exp2_fast(al[q] - m2) * inv; ga_[q] = g * v[p0 + q]; }
         group_sum_n<D, P>(ga_);                                  // galpha, slot-interleaved DPP stages
+        [[maybe_unused]] float kf[P];
+        if constexpr (DROP) {                                    // galpha = kappa s_a <g, PL[src]>; the message carries kappa s_a alpha
+#pragma unroll
+            for (int q = 0; q < P; ++q) { kf[q] = attn_keep(A.drop, kd, e0 + (p0 + q) * G + gidx - rb, c / D); ga_[q] *= kf[q]; }
+        }
 #pragma unroll
         for (int q = 0; q < P; ++q) {
             const int u = p0 + q;
@@ -440,7 +460,7 @@ __device__ __forceinline__ void bwd_chunk(const EdgeBwdArgs& A, int e0, int e_en
             const float gs = ge * ac * (pos ? 1.0f : A.slope);
             ga = fmaf(ge, fmaxf(s, s * A.slope), ga);
             gpr += gs;
-            const float msg = fmaf(g, al[q], gs);                // d/dPL[src] from this edge
+            const float msg = fmaf(g, DROP ? al[q] * kf[q] : al[q], gs);   // d/dPL[src] from this edge
             if (valid && DBG != 1) {
                 if constexpr (STORE) store_row<HD, G == 1, BF>(A.msg, sid[u], c, msg);
                 else unsafeAtomicAdd(A.gPL + (int64_t)sid[u] * HD + c, msg);
@@ -455,8 +475,8 @@ __device__ __forceinline__ void bwd_chunk(const EdgeBwdArgs& A, int e0, int e_en
     }
 }
 
-template <int HD, int D, bool STORE, bool TAPS, int DBG = 0, bool BF = false>
-__global__ __launch_bounds__(256) void edge_bwd_kernel(EdgeBwdArgs A) {
+template <int HD, int D, bool STORE, bool TAPS, int DBG = 0, bool BF = false, bool DROP = false>
+__global__ __launch_bounds__(256) void edge_bwd_kernel(BwdArgsT<DROP> A) {
     constexpr int G = 64 / HD;
     constexpr int U = 16 / G;
     constexpr int CH = 16;
@@ -486,12 +506,15 @@ __global__ __launch_bounds__(256) void edge_bwd_kernel(EdgeBwdArgs A) {
         const float m2 = A.mstat[row * (HD / D) + c / D];
         const float inv = __builtin_amdgcn_rcpf(A.zstat[row * (HD / D) + c / D] + 1e-8f);
         float gpr = 0.f;
+        uint32_t kd = 0;
+        int rb = 0;
+        if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; }
         for (int e0 = b; e0 < e_end; e0 += CH) {
             if constexpr (U >= 2) {
-                if (e_end - e0 <= CH / 2) bwd_chunk<HD, D, U / 2, STORE, TAPS, DBG, BF>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr);
-                else bwd_chunk<HD, D, U, STORE, TAPS, DBG, BF>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr);
+                if (e_end - e0 <= CH / 2) bwd_chunk<HD, D, U / 2, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, kd, rb);
+                else bwd_chunk<HD, D, U, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, kd, rb);
             } else {
-                bwd_chunk<HD, D, U, STORE, TAPS, DBG, BF>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr);
+                bwd_chunk<HD, D, U, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, kd, rb);
             }
         }
 #pragma unroll
@@ -606,9 +629,9 @@ __device__ __forceinline__ void store_row_n(float* __restrict__ msg, int slot, i
 // Forward edge pass in the packed layout (training path: alpha not materialised).  Same online softmax as
 // fwd_chunk; partials of split rows go to the same [slot][HD] / [slot][2H] arrays, so edge_fwd_fix_kernel
 // finishes them unchanged.
-template <int HD, int D, int N, int UU, bool BF>
-__device__ __forceinline__ void fwd2_chunk(const EdgeFwdArgs& A, int e0, int e_end_v, int cp, int gidx, int srcv,
-                                           vnf<N> pr, vnf<N> ac2, float& m, float& Z, vnf<N>& acc) {
+template <int HD, int D, int N, int UU, bool BF, bool DROP = false, class AT = EdgeFwdArgs>
+__device__ __forceinline__ void fwd2_chunk(const AT& A, int e0, int e_end_v, int cp, int gidx, int srcv,
+                                           vnf<N> pr, vnf<N> ac2, float& m, float& Z, vnf<N>& acc, uint32_t kd = 0, int rb = 0) {
     constexpr int LPE = HD / N, G = 64 / LPE, DL = D / N;
     vnf<N> v[UU];
 #pragma unroll
@@ -632,13 +655,14 @@ __device__ __forceinline__ void fwd2_chunk(const EdgeFwdArgs& A, int e0, int e_e
     for (int u = 0; u < UU; ++u) {
         const float p = exp2_fast(t[u] - mn);        // 0 for padded slots
         Z += p;
-        acc += p * v[u];
+        if constexpr (DROP) acc += (p * attn_keep(A.drop, kd, e0 + u * G + gidx - rb, (N * cp) / D)) * v[u];
+        else acc += p * v[u];
     }
     m = mn;
 }
 
-template <int HD, int D, int N, bool BF = false>
-__global__ __launch_bounds__(256) void edge_fwd2_kernel(EdgeFwdArgs A) {
+template <int HD, int D, int N, bool BF = false, bool DROP = false>
+__global__ __launch_bounds__(256) void edge_fwd2_kernel(FwdArgsT<DROP> A) {
     constexpr int LPE = HD / N, G = 64 / LPE, DL = D / N, H = HD / D;
     constexpr int CH = 16;
     constexpr int U = CH / G;
@@ -663,13 +687,16 @@ __global__ __launch_bounds__(256) void edge_fwd2_kernel(EdgeFwdArgs A) {
     };
     int srcv = 0;
     if (b < e_end) srcv = load_idx(b);               // empty item (zero in-degree row): e_end - 1 would be b - 1, i.e. -1 for row 0
+    uint32_t kd = 0;
+    int rb = 0;
+    if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; }
     for (int e0 = b; e0 < e_end; e0 += CH) {
         const int srcn = (e0 + CH < e_end) ? load_idx(e0 + CH) : 0;
         if constexpr (U >= 2) {
-            if (e_end - e0 <= CH / 2) fwd2_chunk<HD, D, N, U / 2, BF>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc);
-            else fwd2_chunk<HD, D, N, U, BF>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc);
+            if (e_end - e0 <= CH / 2) fwd2_chunk<HD, D, N, U / 2, BF, DROP>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, kd, rb);
+            else fwd2_chunk<HD, D, N, U, BF, DROP>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, kd, rb);
         } else {
-            fwd2_chunk<HD, D, N, U, BF>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc);
+            fwd2_chunk<HD, D, N, U, BF, DROP>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, kd, rb);
         }
         srcv = srcn;
     }
@@ -728,8 +755,8 @@ __device__ __forceinline__ int wave_max_over_groups(int v) {
     return __builtin_amdgcn_readfirstlane(v);
 }
 
-template <int HD, int D, int N, bool BF = false>
-__global__ __launch_bounds__(256) void edge_fwd3_kernel(EdgeFwdArgs A) {
+template <int HD, int D, int N, bool BF = false, bool DROP = false>
+__global__ __launch_bounds__(256) void edge_fwd3_kernel(FwdArgsT<DROP> A) {
     constexpr int LPE = HD / N, G = 64 / LPE, DL = D / N, H = HD / D;
     constexpr int U = 4;                             // edges per group and step: G*U gathers in flight per wave
     static_assert(D % N == 0 && LPE >= U, "lane layout");
@@ -754,6 +781,9 @@ __global__ __launch_bounds__(256) void edge_fwd3_kernel(EdgeFwdArgs A) {
         return A.col_idx[j > 0 ? j : 0];
     };
     int srcv = load_idx(0);
+    [[maybe_unused]] uint32_t kd = 0;
+    [[maybe_unused]] int rb = 0;
+    if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, rowc)); rb = A.row_ptr[rowc]; }
     for (int st = 0; st < nst; ++st) {
         const int srcn = load_idx(st + 1);           // next step's indices: in flight during this one
         vnf<N> v[U];
@@ -777,7 +807,8 @@ __global__ __launch_bounds__(256) void edge_fwd3_kernel(EdgeFwdArgs A) {
         for (int u = 0; u < U; ++u) {
             const float p = exp2_fast(t[u] - mn);    // 0 for padded slots
             Z += p;
-            acc += p * v[u];
+            if constexpr (DROP) acc += (p * attn_keep(A.drop, kd, b + st * U + u - rb, c / D)) * v[u];   // the term, not Z
+            else acc += p * v[u];
         }
         m = mn;
         srcv = srcn;
@@ -808,10 +839,10 @@ __global__ __launch_bounds__(256) void edge_fwd3_kernel(EdgeFwdArgs A) {
 // STASH (see edge_bwd2_kernel): instead of the H*D-float message row an edge leaves a record of H*D/N words in its
 // source-major slot — per head alpha and grad_attn_score, with the N LeakyReLU' decisions of the lane's channels in
 // the N low mantissa bits of the word (value rounded to nearest at that precision: relative 2^-(24-N)).
-template <int HD, int D, int N, int UU, int DBG, bool BF, bool STASH>
-__device__ __forceinline__ void bwd2_chunk(const EdgeBwdArgs& A, int e0, int e_end, int e_end_v, int cp, int gidx,
+template <int HD, int D, int N, int UU, int DBG, bool BF, bool STASH, bool DROP = false, class AT = EdgeBwdArgs>
+__device__ __forceinline__ void bwd2_chunk(const AT& A, int e0, int e_end, int e_end_v, int cp, int gidx,
                                            int srcv, int posv, vnf<N> g, vnf<N> pr, float dot, vnf<N> ac, vnf<N> acs,
-                                           vnf<N> ac2, float m2, float inv, vnf<N>& ga, vnf<N>& gpr) {
+                                           vnf<N> ac2, float m2, float inv, vnf<N>& ga, vnf<N>& gpr, uint32_t kd = 0, int rb = 0) {
     constexpr int LPE = HD / N;         // lanes per edge
     constexpr int G = 64 / LPE;         // edges per wave-instruction
     constexpr int DL = D / N;           // lanes per head
@@ -844,6 +875,11 @@ __device__ __forceinline__ void bwd2_chunk(const EdgeBwdArgs& A, int e0, int e_e
             ga_[q] = hsum<N>(g * v[p0 + q]);
         }
         group_sum_n<DL, P>(ga_);
+        [[maybe_unused]] float kf[P];
+        if constexpr (DROP) {                                    // galpha = kappa s_a <g, PL[src]>; records / messages carry kappa s_a alpha
+#pragma unroll
+            for (int q = 0; q < P; ++q) { kf[q] = attn_keep(A.drop, kd, e0 + (p0 + q) * G + gidx - rb, (N * cp) / D); ga_[q] *= kf[q]; }
+        }
 #pragma unroll
         for (int q = 0; q < P; ++q) {
             const int u = p0 + q;
@@ -854,6 +890,7 @@ __device__ __forceinline__ void bwd2_chunk(const EdgeBwdArgs& A, int e0, int e_e
             const vnf<N> gs = ge * select_pos<N>(s, ac, acs);        // ge * a * LReLU'(s)
             ga += ge * lrelu_n<N>(s, A.slope);
             gpr += gs;
+            if constexpr (DROP) al[q] *= kf[q];
             if constexpr (STASH) {
                 static_assert(D / N == 2, "stash records: two lanes per head (one carries alpha, the other ge)");
                 uint32_t bits = 0;
@@ -877,8 +914,8 @@ __device__ __forceinline__ void bwd2_chunk(const EdgeBwdArgs& A, int e0, int e_e
 // per-edge record is H*D/N words (64 B at H*D = 64) instead of the H*D*4-byte message row, and gpl_pull_kernel
 // (gat_csc.hip) rebuilds each message from the record and ONE gathered row of g[dst] while it sums per source.
 // This kernel then also writes g[row] (dL/dh_pre with the LeakyReLU' factor applied) for that gather.
-template <int HD, int D, int N, int DBG, bool BF, bool STASH>
-__device__ __forceinline__ void edge_bwd2_body(const EdgeBwdArgs& A) {
+template <int HD, int D, int N, int DBG, bool BF, bool STASH, bool DROP = false, class AT = EdgeBwdArgs>
+__device__ __forceinline__ void edge_bwd2_body(const AT& A) {
     constexpr int LPE = HD / N, G = 64 / LPE, DL = D / N, H = HD / D;
     constexpr int U = 16 / G;
     constexpr int CH = 16;
@@ -936,14 +973,17 @@ __device__ __forceinline__ void edge_bwd2_body(const EdgeBwdArgs& A) {
         };
         int srcv = 0, posv = 0;
         if (b < e_end) load_idx(b, srcv, posv);                      // empty item: nothing to prefetch (e_end - 1 < b)
+        uint32_t kd = 0;
+        int rb = 0;
+        if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; }
         for (int e0 = b; e0 < e_end; e0 += CH) {
             int srcn = 0, posn = 0;
             if (e0 + CH < e_end) load_idx(e0 + CH, srcn, posn);      // next chunk's indices: in flight during this one
             if constexpr (U >= 2) {
-                if (e_end - e0 <= CH / 2) bwd2_chunk<HD, D, N, U / 2, DBG, BF, STASH>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr);
-                else bwd2_chunk<HD, D, N, U, DBG, BF, STASH>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr);
+                if (e_end - e0 <= CH / 2) bwd2_chunk<HD, D, N, U / 2, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, kd, rb);
+                else bwd2_chunk<HD, D, N, U, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, kd, rb);
             } else {
-                bwd2_chunk<HD, D, N, U, DBG, BF, STASH>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr);
+                bwd2_chunk<HD, D, N, U, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, kd, rb);
             }
             srcv = srcn; posv = posn;
         }
@@ -966,8 +1006,8 @@ __device__ __forceinline__ void edge_bwd2_body(const EdgeBwdArgs& A) {
             (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
-template <int HD, int D, int N, int DBG = 0, bool BF = false, bool STASH = false>
-__global__ __launch_bounds__(256) void edge_bwd2_kernel(EdgeBwdArgs A) { edge_bwd2_body<HD, D, N, DBG, BF, STASH>(A); }
+template <int HD, int D, int N, int DBG = 0, bool BF = false, bool STASH = false, bool DROP = false>
+__global__ __launch_bounds__(256) void edge_bwd2_kernel(BwdArgsT<DROP> A) { edge_bwd2_body<HD, D, N, DBG, BF, STASH, DROP>(A); }
 // The stash variant sits a few registers above 128 VGPRs when left alone (3 waves/SIMD); it is told to fit 4 waves.
 template <int HD, int D, int N, int DBG = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void edge_bwd2s_kernel(EdgeBwdArgs A) {
@@ -979,8 +1019,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 // MSG = true: the same walk for the layers WITHOUT a record path (bf16 storage at H*D < 64: BASELINE config 5; GAT_BWD_STASH=0):
 // an edge leaves its H*D-element message row g*alpha + ge*a*LReLU' in its source-major slot (summed by launch_gpl_sum) instead
 // of a record, nothing is written for the pull pass (no gfull / decision bytes), any D/N lanes per head.
-template <int HD, int D, int N, int DBG = 0, bool BF = false, bool MSG = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void edge_bwd3_kernel(EdgeBwdArgs A) {
+// DROP: the mask hash does not fit the 128-VGPR budget of 4 waves / SIMD without spilling (measured: 36-80 B/lane of scratch at
+// N = 4); the attention-dropout instantiations are allowed 3 waves / SIMD instead.
+template <int HD, int D, int N, int DBG = 0, bool BF = false, bool MSG = false, bool DROP = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DROP ? 3 : 4, 8))) void edge_bwd3_kernel(BwdArgsT<DROP> A) {
     constexpr int LPE = HD / N, G = 64 / LPE, DL = D / N, H = HD / D;
     constexpr int U = 4;
     static_assert((MSG || DL == 2) && LPE >= U, "records: two lanes per head (one carries alpha, the other ge)");
@@ -995,6 +1037,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     const int64_t nquads = (A.n_items + G - 1) / G;
     const int64_t nwaves = (int64_t)gridDim.x * 4;
     vnf<N> ga = vzero<N>();
+    [[maybe_unused]] uint32_t k1 = 0;
+    if constexpr (DROP) k1 = drop_key(A.drop, kDropAttn);
 
     for (int64_t q = (int64_t)blockIdx.x * 4 + wave; q < nquads; q += nwaves) {
         const int64_t it = q * G + gidx;
@@ -1049,6 +1093,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         const float dot = group_sum<DL>(hsum<N>(g * hp));
         const float m2 = A.mstat[rowc * H + c / D];
         const float inv = __builtin_amdgcn_rcpf(A.zstat[rowc * H + c / D] + 1e-8f);
+        [[maybe_unused]] uint32_t kd = 0;
+        [[maybe_unused]] int kb = 0;                 // in-row position of the item's first edge (segments of a split row)
+        if constexpr (DROP) { kd = drop_mix(k1, drop_node(A.drop, rowc)); kb = b - A.row_ptr[rowc]; }
         if (!MSG && row >= 0 && (slot < 0 || b == A.row_ptr[rowc])) {    // one writer per row: whole rows, or a split row's first segment
             if (A.hbits != nullptr) {                                // last layer: the decisions only (g = gh * LReLU'(h_pre) / H is rebuilt by the pull pass)
                 uint32_t nib = 0;
@@ -1125,6 +1172,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
                 ga_[u] = hsum<N>(g * v[u]);
             }
             group_sum_n<DL, U>(ga_);
+            // galpha = kappa s_a <g, PL[src]>; records / messages carry kappa s_a alpha.  The keep decisions are lane masks (SGPR
+            // pairs), not factors in VGPRs: this kernel sits at its 128-VGPR budget
+            [[maybe_unused]] bool kp[U];
+            if constexpr (DROP) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    kp[u] = (drop_mix(drop_mix(kd, (uint32_t)(kb + st * U + u)), (uint32_t)(c / D)) >> 8) >= A.drop.T;
+                    ga_[u] = kp[u] ? ga_[u] * A.drop.scale : 0.f;
+                }
+            }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const bool valid = b + st * U + u < e;
@@ -1133,6 +1190,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
                 const vnf<N> gs = ge * select_pos<N>(s, ac, acs);        // ge * a * LReLU'(s)
                 ga += ge * lrelu_n<N>(s, A.slope);
                 gpr += gs;
+                if constexpr (DROP) al[u] = kp[u] ? al[u] * A.drop.scale : 0.f;
                 if constexpr (MSG) {
                     pend_m[u] = g * al[u] + gs;                          // d/dPL[src] from this edge (E:859-869)
                 } else {
@@ -1664,13 +1722,15 @@ __global__ __launch_bounds__(256) void edge_bwd_fix_kernel(const int4* __restric
 // fast path; same math, literal alpha-weighted sums in ascending edge order.
 // dynamic LDS: forward  act[HD];  backward dot[H] ge[H] al[H] ga[HD] gpr[HD]
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void edge_fwd_generic(EdgeFwdArgs A) {
+__global__ __launch_bounds__(64) void edge_fwd_generic(EdgeFwdArgs A, DropArgs dr) {
     extern __shared__ float lds[];
     const int H = A.H, D = A.D, HD = H * D;
     const int lane = threadIdx.x;
     const float slope = A.slope;
+    const uint32_t k1 = dr.on ? drop_key(dr, kDropAttn) : 0u;
     for (int64_t row = blockIdx.x; row < A.n_rows; row += gridDim.x) {
         const int b = A.row_ptr[row], e_end = A.row_ptr[row + 1];
+        const uint32_t kd = dr.on ? drop_mix(k1, drop_node(dr, row)) : 0u;
         for (int h = lane; h < H; h += 64) {
             float m = -1e9f;
             for (int e = b; e < e_end; ++e) {
@@ -1698,7 +1758,9 @@ __global__ __launch_bounds__(64) void edge_fwd_generic(EdgeFwdArgs A) {
             float acc = 0.f;
             for (int e = b; e < e_end; ++e) {
                 const int64_t sid = A.col_idx[e];
-                acc += A.alpha[(int64_t)e * H + ch / D] * A.PL[sid * HD + ch];
+                float w = A.alpha[(int64_t)e * H + ch / D];
+                if (dr.on) w *= attn_keep(dr, kd, e - b, ch / D);   // attention dropout: the term, not alpha
+                acc += w * A.PL[sid * HD + ch];
             }
             A.hpre[row * HD + ch] = acc;
             const float act = lrelu(acc, slope);
@@ -1716,7 +1778,7 @@ __global__ __launch_bounds__(64) void edge_fwd_generic(EdgeFwdArgs A) {
     }
 }
 
-__global__ __launch_bounds__(64) void edge_bwd_generic(EdgeBwdArgs A) {
+__global__ __launch_bounds__(64) void edge_bwd_generic(EdgeBwdArgs A, DropArgs dr) {
     extern __shared__ float lds[];
     const int H = A.H, D = A.D, HD = H * D;
     float* s_dot = lds;
@@ -1732,8 +1794,10 @@ __global__ __launch_bounds__(64) void edge_bwd_generic(EdgeBwdArgs A) {
         const float gv = A.g[i];
         return A.g_raw ? gv * (A.hpre[i] > 0.f ? 1.0f : slope) : gv;
     };
+    const uint32_t k1 = dr.on ? drop_key(dr, kDropAttn) : 0u;
     for (int64_t row = blockIdx.x; row < A.n_rows; row += gridDim.x) {
         const int b = A.row_ptr[row], e_end = A.row_ptr[row + 1];
+        const uint32_t kd = dr.on ? drop_mix(k1, drop_node(dr, row)) : 0u;
         for (int h = lane; h < H; h += 64) {
             float t = 0.f;
             for (int k = 0; k < D; ++k) t += gval(row * HD + h * D + k) * A.hpre[row * HD + h * D + k];
@@ -1746,10 +1810,12 @@ __global__ __launch_bounds__(64) void edge_bwd_generic(EdgeBwdArgs A) {
             for (int h = lane; h < H; h += 64) {
                 float t = 0.f;
                 for (int k = 0; k < D; ++k) t += gval(row * HD + h * D + k) * A.PL[sid * HD + h * D + k];
-                const float al = A.alpha[(int64_t)e * H + h];
+                const float al = A.alpha[(int64_t)e * H + h];     // the softmax alpha (dropout is applied here, not stored)
+                const float kf = dr.on ? attn_keep(dr, kd, e - b, h) : 1.0f;
+                t *= kf;                                          // dL/dalpha = kappa s_a <g, PL[src]>
                 const float ge = al * (t - s_dot[h]);
                 s_ge[h] = ge;
-                s_al[h] = al;
+                s_al[h] = al * kf;
                 if (A.ge != nullptr) A.ge[(int64_t)e * H + h] = ge;
                 if (A.galpha != nullptr) A.galpha[(int64_t)e * H + h] = t;
             }
@@ -1799,6 +1865,39 @@ static bool packed_layout() {
 static int lane_channels() {
     static const int v = [] { const char* e = choice_env("GAT_CPL"); return (e && e[0] == '2') ? 2 : 4; }();
     return v;
+}
+
+// Attention dropout (a.drop.on): the DROP instantiation of the kernel the default settings pick — the group-per-row kernel where
+// the shape has one, else the packed wave-per-row kernel; the parity-tap form with alpha.  The A/B switches of the default path
+// (GAT_ROWGROUP, GAT_PACKED, GAT_CPL, GAT_FWD_WAVES, GAT_GROUP_MSG) do not apply: only these instantiations exist.
+template <int HD, int D>
+int run_fwd_drop(const EdgeFwdDropArgs& a, hipStream_t s) {
+    if (a.items == nullptr) return fail(GAT_E_INVALID, "edge_forward: work-item list missing");
+    if (a.mstat == nullptr || a.zstat == nullptr) return fail(GAT_E_INVALID, "edge_forward: stats buffers missing");
+    const EdgeFwdArgs& p = a;                        // what the fix-up kernel takes
+    const dim3 block(256);
+    const dim3 fgrid((unsigned)(((a.alpha != nullptr ? a.n_slots : a.n_split) + 3) / 4));
+    if (a.alpha != nullptr) {
+        const dim3 grid((unsigned)((a.n_items + 3) / 4));
+        if (a.bf16) hipLaunchKernelGGL((edge_fwd_kernel<HD, D, true, true, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((edge_fwd_kernel<HD, D, true, false, true>), grid, block, 0, s, a);
+        if (a.n_slots > 0) hipLaunchKernelGGL((edge_fwd_fix_kernel<HD, D, true>), fgrid, block, 0, s, p);
+    } else if constexpr (stash_n<HD, D>() != 0) {
+        constexpr int NN = stash_n<HD, D>(), GG = 64 / (HD / NN);
+        const dim3 g3((unsigned)((a.n_items + GG - 1) / GG));
+        if (a.bf16) hipLaunchKernelGGL((edge_fwd3_kernel<HD, D, NN, true, true>), g3, dim3(64), 0, s, a);
+        else hipLaunchKernelGGL((edge_fwd3_kernel<HD, D, NN, false, true>), g3, dim3(64), 0, s, a);
+        if (a.n_slots > 0) hipLaunchKernelGGL((edge_fwd_fix_kernel<HD, D, false>), fgrid, block, 0, s, p);
+    } else {
+        static_assert(D % 2 == 0, "every fast-path shape has an even D");
+        constexpr int NN = (HD >= 32 && D % 4 == 0) ? 4 : 2;
+        const dim3 grid((unsigned)a.n_items);
+        if (a.bf16) hipLaunchKernelGGL((edge_fwd2_kernel<HD, D, NN, true, true>), grid, dim3(64), 0, s, a);
+        else hipLaunchKernelGGL((edge_fwd2_kernel<HD, D, NN, false, true>), grid, dim3(64), 0, s, a);
+        if (a.n_slots > 0) hipLaunchKernelGGL((edge_fwd_fix_kernel<HD, D, false>), fgrid, block, 0, s, p);
+    }
+    GAT_HIP(hipGetLastError());
+    return 0;
 }
 
 template <int HD, int D>
@@ -1878,7 +1977,7 @@ static bool group_msg() {
     static const bool v = [] { const char* e = choice_env("GAT_GROUP_MSG"); return !(e && e[0] == '0'); }();
     return v;
 }
-struct BwdSel { bool store, taps, bf16, stash; };
+struct BwdSel { bool store, taps, bf16, stash, drop; };
 template <int HD, int D, bool BF>
 const void* bwd_variant(bool store, bool taps, bool stash = false) {
     if constexpr (stash_n<HD, D>() != 0) {
@@ -1901,9 +2000,44 @@ const void* bwd_variant(bool store, bool taps, bool stash = false) {
     return store ? (taps ? (const void*)edge_bwd_kernel<HD, D, true, true, 0, BF> : (const void*)edge_bwd_kernel<HD, D, true, false, 0, BF>)
                  : (taps ? (const void*)edge_bwd_kernel<HD, D, false, true, 0, BF> : (const void*)edge_bwd_kernel<HD, D, false, false, 0, BF>);
 }
+// the attention-dropout kernel run_bwd_drop launches for this selection (null: none)
+template <int HD, int D, bool BF>
+const void* bwd_variant_drop(bool store, bool taps, bool stash) {
+    if (taps) return store ? (const void*)edge_bwd_kernel<HD, D, true, true, 0, BF, true> : nullptr;
+    if (!store) return nullptr;
+    if constexpr (stash_n<HD, D>() != 0) {
+        if (stash) return (const void*)edge_bwd3_kernel<HD, D, stash_n<HD, D>(), 0, BF, false, true>;
+        return (const void*)edge_bwd3_kernel<HD, D, stash_n<HD, D>(), 0, BF, true, true>;
+    } else {
+        return (const void*)edge_bwd2_kernel<HD, D, (HD >= 32 && D % 4 == 0) ? 4 : 2, 0, BF, false, true>;
+    }
+}
 template <int HD, int D>
 int bwd_resident(const BwdSel& sel, hipStream_t) {
+    if (sel.drop) {
+        const void* fn = sel.bf16 ? bwd_variant_drop<HD, D, true>(sel.store, sel.taps, sel.stash) : bwd_variant_drop<HD, D, false>(sel.store, sel.taps, sel.stash);
+        if (fn != nullptr) return resident_blocks(fn);
+    }
     return resident_blocks(sel.bf16 ? bwd_variant<HD, D, true>(sel.store, sel.taps, sel.stash) : bwd_variant<HD, D, false>(sel.store, sel.taps, sel.stash));
+}
+
+template <int HD, int D>
+int run_bwd_drop(const EdgeBwdDropArgs& a, hipStream_t s) {
+    if (a.items == nullptr) return fail(GAT_E_INVALID, "edge_backward: work-item list missing");
+    const bool store = a.pos != nullptr && a.msg != nullptr, taps = a.ge != nullptr, stash = a.stash != nullptr && !taps;
+    if (stash && (a.gfull == nullptr || a.pos == nullptr)) return fail(GAT_E_INVALID, "edge_backward: stash path needs gfull and pos");
+    const void* fn = a.bf16 ? bwd_variant_drop<HD, D, true>(store, taps, stash) : bwd_variant_drop<HD, D, false>(store, taps, stash);
+    if (fn == nullptr)
+        return fail(GAT_E_UNSUPPORTED, "edge_backward: attention dropout needs the store path (not with GAT_BWD_ATOMICS=1 or without the message scratch)");
+    void* args[] = {const_cast<EdgeBwdDropArgs*>(&a)};
+    GAT_HIP(hipLaunchKernel(fn, dim3((unsigned)a.ga_blocks), dim3(256), args, 0, s));
+    if (a.n_slots > 0) {
+        const int64_t threads = (int64_t)a.n_split * HD;
+        hipLaunchKernelGGL(edge_bwd_fix_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s,
+                           a.slot_info, a.n_slots, a.n_split, a.part_acc, a.gPR, HD);
+        GAT_HIP(hipGetLastError());
+    }
+    return 0;
 }
 
 template <int HD, int D>
@@ -2035,12 +2169,22 @@ constexpr int kGenericBlocks = 4096;
         default: break;                                                           \
     }
 
-int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s) {
+int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const DropArgs* drop) {
     if (a.n_rows <= 0) return 0;
     const int HD = a.H * a.D, D = a.D;
-    if (edge_fast_path(a.H, a.D, a.n_table)) { GAT_DISPATCH_HD_D(run_fwd, a, s) }
+    const DropArgs dr = drop != nullptr ? *drop : DropArgs{};
+    if (edge_fast_path(a.H, a.D, a.n_table)) {
+        if (dr.on) {
+            EdgeFwdDropArgs ad;
+            static_cast<EdgeFwdArgs&>(ad) = a;
+            ad.drop = dr;
+            GAT_DISPATCH_HD_D(run_fwd_drop, ad, s)
+        } else {
+            GAT_DISPATCH_HD_D(run_fwd, a, s)
+        }
+    }
     const int64_t blocks = a.n_rows < kGenericBlocks * 8 ? a.n_rows : kGenericBlocks * 8;
-    hipLaunchKernelGGL(edge_fwd_generic, dim3((unsigned)blocks), dim3(64), (size_t)HD * sizeof(float), s, a);
+    hipLaunchKernelGGL(edge_fwd_generic, dim3((unsigned)blocks), dim3(64), (size_t)HD * sizeof(float), s, a, dr);
     GAT_HIP(hipGetLastError());
     return 0;
 }
@@ -2057,11 +2201,11 @@ int edge_stash_words(int32_t H, int32_t D_) {
     return probe();
 }
 
-int edge_backward_blocks(int64_t n_items, int32_t H, int32_t D_, bool store, bool taps, bool bf16, bool stash) {
+int edge_backward_blocks(int64_t n_items, int32_t H, int32_t D_, bool store, bool taps, bool bf16, bool stash, bool drop) {
     int64_t want = (n_items + 3) / 4;
     if (want < 1) want = 1;
     const int HD = H * D_, D = D_;
-    const BwdSel sel{store, taps, bf16, stash};
+    const BwdSel sel{store, taps, bf16, stash, drop};
     auto cap = [&]() -> int {
         GAT_DISPATCH_HD_D(bwd_resident, sel, nullptr)
         return 2048;                                  // generic path: one wave per block
@@ -2090,14 +2234,24 @@ bool edge_fast_path(int32_t H, int32_t D_, int64_t n_table) {
     return probe() == 1;
 }
 
-int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s) {
+int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s, const DropArgs* drop) {
     const int HD = a.H * a.D, D = a.D;
     if (a.ga_blocks < 1) return fail(GAT_E_INVALID, "edge_backward: ga_blocks must come from edge_backward_blocks()");
-    if (edge_fast_path(a.H, a.D, a.n_table)) { GAT_DISPATCH_HD_D(run_bwd, a, s) }
+    const DropArgs dr = drop != nullptr ? *drop : DropArgs{};
+    if (edge_fast_path(a.H, a.D, a.n_table)) {
+        if (dr.on) {
+            EdgeBwdDropArgs ad;
+            static_cast<EdgeBwdArgs&>(ad) = a;
+            ad.drop = dr;
+            GAT_DISPATCH_HD_D(run_bwd_drop, ad, s)
+        } else {
+            GAT_DISPATCH_HD_D(run_bwd, a, s)
+        }
+    }
     if (a.pos != nullptr) return fail(GAT_E_INVALID, "edge_backward: the generic path has no store mode");
     const size_t lds = (size_t)(3 * a.H + 2 * HD) * sizeof(float);
     if (lds > 64 * 1024) return fail(GAT_E_UNSUPPORTED, "edge_backward: H*D too large for the generic path");
-    hipLaunchKernelGGL(edge_bwd_generic, dim3((unsigned)a.ga_blocks), dim3(64), lds, s, a);
+    hipLaunchKernelGGL(edge_bwd_generic, dim3((unsigned)a.ga_blocks), dim3(64), lds, s, a, dr);
     GAT_HIP(hipGetLastError());
     return 0;
 }

@@ -32,6 +32,53 @@ const char* choice_env(const char* name);
         if (rc__ != 0) return rc__;   \
     } while (0)
 
+// ---- dropout masks (gat_dropout.hip; the contract is in gatv2_abi.h "dropout") -------------------------
+// Stateless, counter-based: every keep decision is a hash of (seed, step, layer, kind, node, position), so a shard, a replay and
+// the backward draw the same masks as the forward without storing them.  `step` lives on the device (advanced by the layer-0
+// projection of a training forward), so a captured graph replays with fresh masks.
+struct DropArgs {
+    const uint64_t* step = nullptr;   // device counter
+    const int64_t* bounds = nullptr;  // [world+1] device, or null: the node id of table row t is t
+    int64_t max_rows = 0;             // rows per rank slice of the source table (with bounds)
+    int64_t row0 = 0;                 // table row of local row 0
+    uint32_t seed_lo = 0, seed_hi = 0;
+    uint32_t T = 0;                   // drop threshold on the 24-bit draw: keep <=> (r >> 8) >= T
+    float scale = 1.f;                // 1 / (1 - p)
+    int32_t layer = 0;
+    int32_t on = 0;                   // generic kernels: runtime switch (the wave-per-row kernels take a template flag)
+};
+enum : int32_t { kDropFeat = 0, kDropAttn = 1 };
+__host__ __device__ __forceinline__ uint32_t drop_fmix32(uint32_t h) {
+    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+    return h;
+}
+__host__ __device__ __forceinline__ uint32_t drop_mix(uint32_t k, uint32_t v) { return drop_fmix32(k ^ (v * 0x9E3779B9u + 0x7F4A7C15u)); }
+// K(kind, l) for the step the counter holds
+__device__ __forceinline__ uint32_t drop_key(const DropArgs& d, int32_t kind) {
+    const uint64_t st = *d.step;
+    uint32_t k = drop_mix(d.seed_lo, d.seed_hi);
+    k = drop_mix(k, (uint32_t)st);
+    k = drop_mix(k, (uint32_t)(st >> 32));
+    return drop_mix(k, (uint32_t)(2 * d.layer + kind));
+}
+// id in the unsharded graph of local row r (padding rows of a shard get some id: their features are zero)
+__device__ __forceinline__ uint32_t drop_node(const DropArgs& d, int64_t r) {
+    const int64_t t = d.row0 + r;
+    if (d.bounds == nullptr) return (uint32_t)t;
+    return (uint32_t)(d.bounds[t / d.max_rows] + t % d.max_rows);
+}
+// 0 or 1/(1-p)
+__device__ __forceinline__ float drop_factor(const DropArgs& d, uint32_t r) { return (r >> 8) >= d.T ? d.scale : 0.f; }
+
+int launch_drop_advance(uint64_t* step, hipStream_t s);
+// xo[r][f] = x[r][f] * kappa * s_f for f < F, 0 for F <= f < ld (rows of `ld` floats)
+int launch_feat_drop_fwd(const float* x, float* xo, int64_t rows, int32_t F, int32_t ld, const DropArgs& d, hipStream_t s);
+// g[r][f] *= kappa * s_f   (rows of F floats)
+int launch_feat_drop_bwd(float* g, int64_t rows, int32_t F, const DropArgs& d, hipStream_t s);
+// taps: out [H][E] = 0 or s_a per (head, CSR edge); out [rows][F] = 0 or s_f
+int launch_attn_keep_tap(const int32_t* row_ptr, int64_t n_rows, int64_t n_edges, int32_t H, const DropArgs& d, float* out, hipStream_t s);
+int launch_feat_keep_tap(int64_t rows, int32_t F, const DropArgs& d, float* out, hipStream_t s);
+
 // ---- edge-centric kernels (gat_edge_kernels.hip) ------------------------------------------------
 struct EdgeFwdArgs {
     const int32_t* row_ptr;   // [n_rows+1]
@@ -73,7 +120,10 @@ struct WorkList {
     int32_t n_split = 0;              // rows cut into segments (entries n_slots .. n_slots+n_split-1 of slot_info)
 };
 void build_worklist(const int32_t* row_ptr, int64_t n_rows, WorkList& w);
-int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s);
+// drop (optional): attention dropout; drop->on selects the DROP instantiations, whose kernel argument is the struct below.  The
+// default kernels keep the plain argument struct (same layout, same machine code as without the feature).
+int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const DropArgs* drop = nullptr);
+struct EdgeFwdDropArgs : EdgeFwdArgs { DropArgs drop; };
 
 struct EdgeBwdArgs {
     const int32_t* row_ptr;
@@ -119,7 +169,9 @@ struct EdgeBwdArgs {
     float* part_acc;          // [n_slots][HD]  per-segment gPR partials of split rows
     int32_t dbg;
 };
-int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s);
+// drop: the attention dropout of the forward this backward follows (same masks)
+int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s, const DropArgs* drop = nullptr);
+struct EdgeBwdDropArgs : EdgeBwdArgs { DropArgs drop; };
 // Last layer, fused per row (gat_step): forward edge pass + output head + backward edge pass of every WHOLE row in one kernel
 // (edge_last_fused_kernel); f / b as for the separate passes (f.items / f.n_items: the whole-row items only; b.ga_partial /
 // b.ga_blocks from edge_last_fused_blocks), gh_out = the [n_rows][gh_stride] node records the pull pass reads.
@@ -141,7 +193,7 @@ int launch_head_rows(const int4* slot_info, int32_t n_slots, int32_t n_split, co
 // path is used): two lanes per head are needed (D = 8 with four channels per lane, D = 4 with two).
 int edge_stash_words(int32_t H, int32_t D);
 // Grid size (== rows of ga_partial) for the backward of an (H, D) layer over n_items work items.
-int edge_backward_blocks(int64_t n_items, int32_t H, int32_t D, bool store, bool taps, bool bf16, bool stash = false);
+int edge_backward_blocks(int64_t n_items, int32_t H, int32_t D, bool store, bool taps, bool bf16, bool stash = false, bool drop = false);
 // wave-per-row templates cover this (H, D), and the gathered table is < 4 GiB (they address it as
 // uniform base + 32-bit byte offset); anything else runs the generic kernels
 bool edge_fast_path(int32_t H, int32_t D, int64_t n_table);

@@ -18,6 +18,9 @@
 // GAT_COMM_HALO; 2 = only where fewer than half of the rows would travel).  Same numbers as the full exchange.
 // --dtype f32|bf16: storage type of the gathered / exchanged source table and the per-edge message
 // rows (arithmetic stays fp32).
+// --dropout P / --attn-dropout P (default 0): inverted dropout on every layer's input features / on the attention
+// coefficients during training (gatv2_abi.h "dropout"), masks keyed by --seed.  With --val-mask the validation line
+// then comes from an eval-mode forward (no dropout) after the optimizer step.  Both 0: the output is the reference's.
 #include <algorithm>
 #include <chrono>
 #include <cstdint>
@@ -63,6 +66,7 @@ struct Options {
     int halo = 0;
     std::string dtype = "f32";
     std::string train_mask, val_mask;     // text files of N 0/1 values (beyond the reference: README R:134 "later")
+    float dropout = 0.f, attn_dropout = 0.f;
 };
 
 struct RankEnv {                      // one forked process per GPU
@@ -134,7 +138,9 @@ Options parse_args(int argc, char** argv) {
         } else if (a == "--halo" && has_val) {
             o.halo = std::stoi(argv[++i]);
             if (o.halo < 0 || o.halo > 2) die("Invalid halo choice. Use 0, 1 or 2\n");
-        } else if (a == "--transport" && has_val) {
+        } else if (a == "--dropout" && has_val) o.dropout = std::strtof(argv[++i], nullptr);
+        else if (a == "--attn-dropout" && has_val) o.attn_dropout = std::strtof(argv[++i], nullptr);
+        else if (a == "--transport" && has_val) {
             o.transport = argv[++i];
             if (o.transport != "rccl" && o.transport != "host") die("Invalid transport choice. Use 'rccl' or 'host'\n");
         }
@@ -370,6 +376,7 @@ int run(const Options& o, const RankEnv& env) {
             check(gat_set_source_features(ctx, xt.data(), plan.n_table(), F0), "gat_set_source_features");
         }
         check(gat_set_labels(ctx, labels.data() + plan.row0(), plan.n_rows()), "gat_set_labels");
+        check(gat_set_shard_bounds(ctx, env.world, plan.bounds.data()), "gat_set_shard_bounds");     // dropout masks: unsharded node ids
         if (o.transport == "rccl") {
             if (env.rank == 0) {
                 check(gat_comm_unique_id(env.shared->id), "gat_comm_unique_id");
@@ -423,6 +430,8 @@ int run(const Options& o, const RankEnv& env) {
         if (env.world != 1) die("Error: --val-mask needs --ranks 1\n");
         load_mask(o.val_mask, val_m, "val mask");
     }
+    const bool dropout = o.dropout > 0.f || o.attn_dropout > 0.f;
+    if (dropout) check(gat_set_dropout(ctx, o.dropout, o.attn_dropout, o.seed, 0), "gat_set_dropout");
     check(gat_params_init(ctx, o.seed), "xavier_init_kernel");
     if (!o.load_params.empty()) {
         std::vector<float> p(nW + nA + nWo);
@@ -447,7 +456,7 @@ int run(const Options& o, const RankEnv& env) {
         float loss_sum = 0.f; int32_t n_correct = 0;
         check(gat_forward(ctx, &loss_sum, &n_correct), "gatv2 forward");
         std::printf("\nAvg Loss: %f, Accuracy: %.2f%%\n", loss_sum / n_train, 100.0f * (static_cast<float>(n_correct) / n_train));
-        if (!val_m.empty()) {
+        if (!val_m.empty() && !dropout) {
             double vl = 0.0; int32_t vc = 0, vn = 0;
             check(gat_eval_mask(ctx, val_m.data(), N, &vl, &vc, &vn), "gat_eval_mask");
             std::printf("Val Loss: %f, Val Accuracy: %.2f%%\n", vn ? vl / vn : 0.0, vn ? 100.0f * (static_cast<float>(vc) / vn) : 0.0f);
@@ -457,6 +466,14 @@ int run(const Options& o, const RankEnv& env) {
         if (o.optimizer == "adam") check(gat_step_adam(ctx, o.lr, o.beta1, o.beta2, 1e-8f, epoch), "adam_update_kernel");
         else check(gat_step_sgd(ctx, o.lr), "sgd_update_kernel");
         check(gat_zero_grad(ctx), "gat_zero_grad");
+        if (!val_m.empty() && dropout) {          // validation of the updated model, without dropout
+            double vl = 0.0; int32_t vc = 0, vn = 0;
+            check(gat_set_training(ctx, 0), "gat_set_training");
+            check(gat_forward(ctx, nullptr, nullptr), "gatv2 forward");
+            check(gat_eval_mask(ctx, val_m.data(), N, &vl, &vc, &vn), "gat_eval_mask");
+            check(gat_set_training(ctx, 1), "gat_set_training");
+            std::printf("Val Loss: %f, Val Accuracy: %.2f%%\n", vn ? vl / vn : 0.0, vn ? 100.0f * (static_cast<float>(vc) / vn) : 0.0f);
+        }
         check(gat_sync(ctx), "gat_sync");
         const std::chrono::duration<double, std::milli> elapsed = std::chrono::high_resolution_clock::now() - start;
         std::cout << " total time: " << elapsed.count() << " ms" << std::endl;
@@ -480,6 +497,14 @@ int main(int argc, char** argv) {
     bool multi = false;                                    // --ranks P > 1: see print_memory_tracker_before
     for (int i = 1; i + 1 < argc; ++i)
         if (std::string(argv[i]) == "--ranks" && std::atoi(argv[i + 1]) > 1) multi = true;
+    // dropout probabilities are checked before anything touches the GPU (NaN and trailing garbage included)
+    for (int i = 1; i + 1 < argc; ++i) {
+        const std::string a = argv[i];
+        if (a != "--dropout" && a != "--attn-dropout") continue;
+        char* end = nullptr;
+        const float p = std::strtof(argv[i + 1], &end);
+        if (end == argv[i + 1] || *end != '\0' || !(p >= 0.f && p < 1.f)) die("Error: " + a + " must be in [0, 1)\n");
+    }
     if (!multi) print_memory_tracker_before();
     Options o = parse_args(argc, argv);
     if (!o.seed_given) { o.seed = (uint64_t)time(nullptr); o.seed_given = true; }     // E:1305; one seed for all ranks

@@ -234,8 +234,14 @@ class ShardedGat:
     ``tables`` maps (which, layer) -> flat torch tensor bound to the context."""
 
     def __init__(self, ctx, plan: ShardPlan, comm, heads: Sequence[int], outdims: Sequence[int],
-                 alloc: Callable[[int], "object"], halo: bool = False):
+                 alloc: Callable[[int], "object"], halo: bool = False, dropout: Optional[Sequence[float]] = None):
         self.ctx, self.plan, self.comm = ctx, plan, comm
+        # dropout masks are drawn per unsharded node id: every rank gets the plan's bounds, so that the masks (and the
+        # results) equal a single GPU's.  dropout = (feat_p, attn_p, seed[, first_step]), or None: the context's setting stays
+        if hasattr(ctx, "set_shard_bounds"):
+            ctx.set_shard_bounds(plan.bounds)
+        if dropout is not None:
+            ctx.set_dropout(*dropout)
         self.halo = bool(halo)                         # comm.halo_setup(plan, col_idx_local) must have run (collective)
         self.hd = [int(h) * int(d) for h, d in zip(heads, outdims)]
         self.L = len(self.hd)

@@ -244,10 +244,56 @@ enum {
     GAT_TAP_PR = 11,        /* [N][H*D]              W_right·x */
     GAT_TAP_SCORE = 12,     /* [H][E]                attn_score[l] (E:323), keep_taps */
     GAT_TAP_GALPHA = 13,    /* [H][E]                grad_attn_coeff (E:646), keep_taps */
-    GAT_TAP_GX = 14         /* [N][F_l], l >= 1      input_gradients[l-1] as compute_features_input_gradients leaves
-                                                      it (E:868-869), BEFORE the LReLU'(h_pre_{l-1}) factor of E:888-892 */
+    GAT_TAP_GX = 14,        /* [N][F_l], l >= 1      input_gradients[l-1] as compute_features_input_gradients leaves
+                                                      it (E:868-869), BEFORE the LReLU'(h_pre_{l-1}) factor of E:888-892
+                                                      (with feature dropout: wrt the undropped x_l, i.e. incl. kappa*s_f) */
+    GAT_TAP_ATTN_KEEP = 15, /* [H][E]                attention-dropout factor kappa*s_a (0 or s_a) of layer l for the step the
+                                                      counter holds (after a training forward: the masks that forward used) */
+    GAT_TAP_FEAT_KEEP = 16  /* [N][F_l]              feature-dropout factor kappa*s_f (0 or s_f) of layer l's input, likewise */
 };
 int gat_tap(gat_ctx* ctx, int tensor, int32_t layer, void* host_dst, int64_t count);
+
+/* ---- dropout (beyond the reference, which has none; the GAT / GATv2 papers' regulariser) ----------------------------
+ * Inverted dropout: a kept value is multiplied by s = 1/(1-p), a dropped one by 0.  Training mode only.
+ *   Attention, p_a, every layer.  With kappa[e,h] in {0,1}:
+ *       h_pre[n,h,:] = sum_{e->n} kappa[e,h] * s_a * alpha[h,e] * PL[src_e]
+ *     The softmax statistics (max, sum) and alpha are unchanged.  Backward: ge = alpha * (galpha - sum alpha*galpha) with
+ *     galpha[e,h] = kappa * s_a * <g, PL[src_e]>, and sum_e alpha*galpha is still <g, h_pre>; the source-side message is
+ *     g * (kappa*s_a*alpha) + ge * a * LReLU'(s).  The per-edge records / message rows carry kappa*s_a*alpha in place of alpha,
+ *     so the source-major pass is unchanged.
+ *   Features, p_f, the input of every layer (layer 0 included): x'_l = x_l (.) kappa*s_f.  Both projections read x'_l and
+ *     grad_W is formed from x'_l; the gradient passed to x_l is gx' (.) kappa*s_f, before the LReLU' factor of the layer below.
+ *   The output head (W_o) has no dropout.  DropEdge (dropping edges before the softmax) is a different regulariser, not this.
+ * Masks are stateless and counter-based (no mask is stored; the backward recomputes the forward's).  uint32 arithmetic, wrapping:
+ *   fmix32(h): h ^= h>>16; h *= 0x85EBCA6B; h ^= h>>13; h *= 0xC2B2AE35; h ^= h>>16
+ *   mix(k, v)  = fmix32(k ^ (v * 0x9E3779B9 + 0x7F4A7C15))
+ *   K(kind, l) = mix(mix(mix(mix(lo32(seed), hi32(seed)), lo32(step)), hi32(step)), 2*l + kind)    kind 0 = feature, 1 = attention
+ *   attention: r = mix(mix(mix(K(1,l), node(dst)), k), h)   k = j - row_ptr[dst], the edge's position in its CSR row (the same
+ *              when a hub row is processed as 256-edge segments)
+ *   feature:   r = mix(mix(K(0,l), node(row)), column)
+ *   keep <=> (r >> 8) >= T,  T = min(2^24, floor(p * 2^24 + 0.5));  s = (float)(1.0 / (1.0 - (double)p))
+ * node(.) is the row's id in the UNSHARDED graph: the row index on one GPU; on a destination-range shard table row t maps to
+ * bounds[t / max_rows] + t % max_rows with the bounds given to gat_set_shard_bounds (without them: t).  Every rank then draws
+ * the masks of a single GPU (padding rows take some id; their features are zero).
+ * step is a 64-bit counter on the device.  A TRAINING forward advances it by one at its start, inside the layer-0 projection (a
+ * one-lane kernel): gat_forward, gat_step, a gat_step_graph replay (the advance is part of the captured graph) and the phase API
+ * (gat_layer_project(0)) alike.  The backward reads it without advancing, so it uses the masks of the forward before it.
+ * Eval mode (gat_set_training(ctx, 0)): the model is the identity with respect to dropout and nothing advances.
+ * p_a = p_f = 0 (the default, also when set explicitly) runs exactly the kernels of a context without dropout.  With dropout on,
+ * each edge pass runs the attention-dropout instantiation of the kernel the default settings select, so the A/B switches of the
+ * default path (GAT_ROWGROUP, GAT_PACKED, GAT_CPL, GAT_FWD_WAVES, GAT_GROUP_MSG, GAT_FUSE_LAST) do not apply; GAT_BWD_ATOMICS=1
+ * (no store path) is refused with GAT_E_UNSUPPORTED at the backward, and so is dropout in the experiment library with GAT_DBG set.
+ * keep_taps = 1: GAT_TAP_ALPHA stays the softmax alpha, GAT_TAP_GALPHA is dL/dalpha (incl. kappa*s_a).  bf16 storage: the
+ * masks and their factors are the same; PL rows are bf16 as without dropout.  Transports (host, RCCL, halo) are unaffected:
+ * masks are drawn where the rows live, never exchanged. */
+/* feat_p, attn_p in [0, 1) (else GAT_E_INVALID, NaN included); seed keys every mask; the counter is set to first_step (a run that
+ * starts from step 5 repeats steps 5, 6, ... of a run that started from 0).  Allowed before the graph is set. */
+int gat_set_dropout(gat_ctx* ctx, float feat_p, float attn_p, uint64_t seed, uint64_t first_step);
+int gat_set_training(gat_ctx* ctx, int32_t training);           /* 1 = training (default), 0 = eval */
+int gat_dropout_step(gat_ctx* ctx, uint64_t* step);             /* the counter's value (synchronises; 0 before gat_set_dropout) */
+/* Shard bounds [world+1] (global row boundaries, bounds[0] = 0): node ids of the table rows for the masks.  Checked against
+ * n_table (= world slices of max_rows), table_row0 and n_rows; call after the graph is set. */
+int gat_set_shard_bounds(gat_ctx* ctx, int32_t world, const int64_t* bounds);
 
 /* ---- op-level entry points, whole layers: caller-provided DEVICE pointers in the reference layouts
  *      (unit parity).  `stream` may be NULL (default stream).  One entry point per reference KERNEL: below. ---- */
