@@ -58,6 +58,8 @@ TAP_ATTN_KEEP, TAP_FEAT_KEEP = 15, 16       # dropout factors (0 or 1/(1-p)) for
  K_EXCHANGE, K_EDGE_FUSED, K_COUNT) = range(12)
 COMM_ID_BYTES = 128
 PATH_GENERIC_SHAPE, PATH_FAST, PATH_GENERIC_SIZE = 0, 1, 2
+GRAPH_SELF_LOOPS, GRAPH_SYMMETRIZE, GRAPH_COALESCE = 1, 2, 4      # flags of the graph builder (graph_from_coo, set_graph_coo)
+CSR_OK, CSR_BAD_START, CSR_BAD_END, CSR_NOT_MONOTONE, CSR_COL_RANGE = range(5)   # graph_check_device
 
 _lib: Optional[C.CDLL] = None
 
@@ -194,6 +196,13 @@ def _declare(lib: C.CDLL) -> None:
         "gat_set_training": [vp, i32],
         "gat_dropout_step": [vp, P(C.c_uint64)],
         "gat_set_shard_bounds": [vp, i32, vp],
+        "gat_graph_from_coo_device": [vp, vp, i64, i64, i64, i64, i32, vp, vp, i64, P(i64), vp],
+        "gat_graph_from_coo": [vp, vp, i64, i64, i64, i64, i32, vp, vp, i64, P(i64), i32],
+        "gat_set_graph_coo": [vp, vp, vp, i64, i64, i64, i64, i32],
+        "gat_set_graph_coo_device": [vp, vp, vp, i64, i64, i64, i64, i32],
+        "gat_graph_size": [vp, P(i64), P(i64), P(i64)],
+        "gat_graph_get": [vp, vp, vp],
+        "gat_graph_check_device": [vp, vp, i64, i64, i64, P(i32), P(i64), vp],
     }
     for name, argt in sigs.items():
         fn = getattr(lib, name)          # AttributeError here == symbol missing from the .so
@@ -294,6 +303,33 @@ class GatContext:
         _chk(self.lib.gat_set_graph_device(self._ctx, C.c_void_p(d_row_ptr), C.c_void_p(d_col_idx), n_rows,
                                            n_edges, nt, table_row0))
         self.n_rows, self.n_edges, self.n_table, self.table_row0 = n_rows, n_edges, nt, table_row0
+
+    def set_graph_coo(self, src, dst, n_rows: int, n_table: Optional[int] = None, table_row0: int = 0, flags: int = 0):
+        """Build the CSR from the edge list (host arrays) on the device and train on it; see graph_from_coo."""
+        s, d, nt = _coo_args(src, dst, n_rows, n_table, flags)
+        _chk(self.lib.gat_set_graph_coo(self._ctx, _np_ptr(s), _np_ptr(d), len(s), n_rows, nt, table_row0, flags))
+        self.n_rows, self.n_edges, self.n_table = self.graph_size()
+        self.table_row0 = table_row0
+
+    def set_graph_coo_device(self, d_src: int, d_dst: int, n_in: int, n_rows: int, n_table: Optional[int] = None,
+                             table_row0: int = 0, flags: int = 0):
+        nt = _coo_sizes(n_in, n_rows, n_table, flags)
+        _chk(self.lib.gat_set_graph_coo_device(self._ctx, C.c_void_p(d_src), C.c_void_p(d_dst), n_in, n_rows, nt, table_row0, flags))
+        self.n_rows, self.n_edges, self.n_table = self.graph_size()
+        self.table_row0 = table_row0
+
+    def graph_size(self):
+        """(n_rows, n_edges, n_table) of the CSR the context trains on."""
+        n, e, t = C.c_int64(), C.c_int64(), C.c_int64()
+        _chk(self.lib.gat_graph_size(self._ctx, C.byref(n), C.byref(e), C.byref(t)))
+        return n.value, e.value, t.value
+
+    def graph(self):
+        """(row_ptr, col_idx) of the CSR the context trains on, as host int32 arrays."""
+        n, e, _ = self.graph_size()
+        rp, ci = np.empty(n + 1, np.int32), np.empty(e, np.int32)
+        _chk(self.lib.gat_graph_get(self._ctx, _np_ptr(rp), _np_ptr(ci)))
+        return rp, ci
 
     def set_features(self, x):
         x = np.ascontiguousarray(x, np.float32)
@@ -570,6 +606,70 @@ def request_bytes_shape(heads: Sequence[int], outdims: Sequence[int], in_dim: in
     _chk(lib.gat_request_bytes_shape(C.byref(cfg), n_rows, n_edges, n_rows if n_table is None else n_table,
                                      int(replicated_input), C.byref(tot), per))
     return tot.value, {lib.gat_kernel_name(k).decode(): per[k] for k in range(K_COUNT)}
+
+
+def _coo_sizes(n_in: int, n_rows: int, n_table: Optional[int], flags: int) -> int:
+    if int(n_in) < 0 or int(n_rows) <= 0:
+        raise ValueError(f"edge list: bad sizes (n_in={n_in}, n_rows={n_rows})")
+    if not isinstance(flags, (int, np.integer)) or flags < 0:
+        raise TypeError("flags must be a non-negative int (GRAPH_SELF_LOOPS | GRAPH_SYMMETRIZE | GRAPH_COALESCE)")
+    return int(n_rows) if n_table is None else int(n_table)
+
+
+def _coo_args(src, dst, n_rows: int, n_table: Optional[int], flags: int):
+    """Argument checks of the host edge-list entry points: raise before any library call."""
+    s, d = np.asarray(src), np.asarray(dst)
+    for name, a in (("src", s), ("dst", d)):
+        if a.ndim != 1:
+            raise ValueError(f"{name} must be one-dimensional, got shape {a.shape}")
+        if a.size and a.dtype.kind not in "iu":
+            raise TypeError(f"{name} must hold integers, got {a.dtype}")
+        if a.size and (int(a.max()) > 0x7fffffff or int(a.min()) < -0x80000000):
+            raise ValueError(f"{name} does not fit int32")
+    if len(s) != len(d):
+        raise ValueError(f"src and dst differ in length ({len(s)} vs {len(d)})")
+    nt = _coo_sizes(len(s), n_rows, n_table, flags)
+    return np.ascontiguousarray(s, np.int32), np.ascontiguousarray(d, np.int32), nt
+
+
+def graph_from_coo(src, dst, n_rows: int, n_table: Optional[int] = None, table_row0: int = 0, flags: int = 0, device: int = 0):
+    """Edge list (host arrays; a message flows src -> dst) -> (row_ptr, col_idx) int32, built on the device: rows are
+    destinations, sources ascending inside a row.  flags: GRAPH_SELF_LOOPS | GRAPH_SYMMETRIZE | GRAPH_COALESCE, applied
+    in that order (gatv2_abi.h "graph construction").  Does the count-then-fill pair of calls."""
+    s, d, nt = _coo_args(src, dst, n_rows, n_table, flags)
+    lib = load_library()
+    m = C.c_int64()
+    _chk(lib.gat_graph_from_coo(_np_ptr(s), _np_ptr(d), len(s), n_rows, nt, table_row0, flags, None, None, 0, C.byref(m), device))
+    rp, ci = np.empty(n_rows + 1, np.int32), np.empty(m.value, np.int32)
+    _chk(lib.gat_graph_from_coo(_np_ptr(s), _np_ptr(d), len(s), n_rows, nt, table_row0, flags, _np_ptr(rp), _np_ptr(ci), m.value,
+                                C.byref(m), device))
+    return rp, ci
+
+
+def graph_from_coo_device(d_src: int, d_dst: int, n_in: int, n_rows: int, n_table: Optional[int] = None, table_row0: int = 0,
+                          flags: int = 0, d_row_ptr: int = 0, d_col_idx: int = 0, col_capacity: int = 0, stream: int = 0) -> int:
+    """The stateless builder on device pointers (current device).  Returns the edge count of the result; with d_col_idx == 0
+    that is all it does, otherwise d_row_ptr [n_rows+1] and d_col_idx [col_capacity] are filled (too small: GatError, and the
+    needed count is in its `needed` attribute)."""
+    nt = _coo_sizes(n_in, n_rows, n_table, flags)
+    m = C.c_int64(-1)
+    rc = load_library().gat_graph_from_coo_device(C.c_void_p(d_src or None), C.c_void_p(d_dst or None), n_in, n_rows, nt, table_row0,
+                                                  flags, C.c_void_p(d_row_ptr or None), C.c_void_p(d_col_idx or None), col_capacity,
+                                                  C.byref(m), C.c_void_p(stream or None))
+    if rc != 0:
+        err = GatError(rc, load_library().gat_last_error().decode("utf-8", "replace"))
+        err.needed = m.value if m.value >= 0 else None
+        raise err
+    return m.value
+
+
+def graph_check_device(d_row_ptr: int, d_col_idx: int, n_rows: int, n_edges: int, n_table: Optional[int] = None, stream: int = 0):
+    """One pass over a device CSR: (problem, where) — (CSR_OK, -1) or the first broken rule and the lowest offending index."""
+    nt = int(n_rows) if n_table is None else int(n_table)
+    prob, where = C.c_int32(), C.c_int64()
+    _chk(load_library().gat_graph_check_device(C.c_void_p(d_row_ptr or None), C.c_void_p(d_col_idx or None), n_rows, n_edges, nt,
+                                               C.byref(prob), C.byref(where), C.c_void_p(stream or None)))
+    return prob.value, where.value
 
 
 def mem_info():

@@ -586,6 +586,18 @@ int gat_sync(gat_ctx* c) {
 }
 
 // ---- data -------------------------------------------------------------------------------------------------
+// c->row_ptr / c->col_idx are in place: the work list (from the host's row_ptr, or a copy fetched here), then the buffers
+static int finish_graph(gat_ctx* c, const int32_t* host_row_ptr) {
+    if (host_row_ptr) {
+        build_worklist(host_row_ptr, c->n_rows, c->work);
+    } else {
+        std::vector<int32_t> h(c->n_rows + 1);
+        GAT_HIP(hipMemcpy(h.data(), c->row_ptr, (c->n_rows + 1) * sizeof(int32_t), hipMemcpyDeviceToHost));
+        build_worklist(h.data(), c->n_rows, c->work);
+    }
+    c->have_graph = true;
+    return ensure_buffers(c);
+}
 static int set_graph_common(gat_ctx* c, const int32_t* row_ptr, const int32_t* col_idx, int64_t n_rows,
                             int64_t n_edges, int64_t n_table, int64_t table_row0, hipMemcpyKind kind) {
     if (!c || !row_ptr || (!col_idx && n_edges > 0)) return fail(GAT_E_INVALID, "gat_set_graph: null argument");
@@ -601,6 +613,10 @@ static int set_graph_common(gat_ctx* c, const int32_t* row_ptr, const int32_t* c
             if (row_ptr[i + 1] < row_ptr[i]) return fail(GAT_E_INVALID, "Invalid row_ptr: not monotone");
         for (int64_t e = 0; e < n_edges; ++e)
             if (col_idx[e] < 0 || (int64_t)col_idx[e] >= n_table) return fail(GAT_E_INVALID, "col_idx entry outside the node table");
+    } else {    // the same rules on the caller's device arrays, before anything walks them (one pass, gat_graph.hip)
+        int32_t problem = 0; int64_t where = -1;
+        GAT_TRY(csr_check_device(row_ptr, col_idx, n_rows, n_edges, n_table, &problem, &where, c->stream));
+        if (problem) return fail(GAT_E_INVALID, csr_problem_text(problem));
     }
     c->n_rows = n_rows; c->n_edges = n_edges; c->n_table = n_table; c->table_row0 = table_row0;
     GAT_TRY(dalloc(c, &c->row_ptr, n_rows + 1));
@@ -608,15 +624,7 @@ static int set_graph_common(gat_ctx* c, const int32_t* row_ptr, const int32_t* c
     GAT_HIP(hipMemcpyAsync(c->row_ptr, row_ptr, (n_rows + 1) * sizeof(int32_t), kind, c->stream));
     if (n_edges > 0) GAT_HIP(hipMemcpyAsync(c->col_idx, col_idx, n_edges * sizeof(int32_t), kind, c->stream));
     GAT_HIP(hipStreamSynchronize(c->stream));
-    if (kind == hipMemcpyHostToDevice) {
-        build_worklist(row_ptr, n_rows, c->work);
-    } else {
-        std::vector<int32_t> h(n_rows + 1);
-        GAT_HIP(hipMemcpy(h.data(), c->row_ptr, (n_rows + 1) * sizeof(int32_t), hipMemcpyDeviceToHost));
-        build_worklist(h.data(), n_rows, c->work);
-    }
-    c->have_graph = true;
-    return ensure_buffers(c);
+    return finish_graph(c, kind == hipMemcpyHostToDevice ? row_ptr : nullptr);
 }
 int gat_set_graph(gat_ctx* c, const int32_t* row_ptr, const int32_t* col_idx, int64_t n_rows, int64_t n_edges,
                   int64_t n_table, int64_t table_row0) {
@@ -625,6 +633,62 @@ int gat_set_graph(gat_ctx* c, const int32_t* row_ptr, const int32_t* col_idx, in
 int gat_set_graph_device(gat_ctx* c, const int32_t* row_ptr, const int32_t* col_idx, int64_t n_rows,
                          int64_t n_edges, int64_t n_table, int64_t table_row0) {
     return set_graph_common(c, row_ptr, col_idx, n_rows, n_edges, n_table, table_row0, hipMemcpyDeviceToDevice);
+}
+
+// Build the CSR from an edge list on the device (gat_graph.hip) straight into the context's arrays, then as above.
+static int set_graph_coo_common(gat_ctx* c, const int32_t* src, const int32_t* dst, int64_t n_in, int64_t n_rows, int64_t n_table,
+                                int64_t table_row0, int32_t flags, bool on_host) {
+    if (!c || ((!src || !dst) && n_in > 0)) return fail(GAT_E_INVALID, "gat_set_graph_coo: null argument");
+    if (c->have_graph) return fail(GAT_E_STATE, "gat_set_graph: graph already set (create a new context)");
+    if (n_in < 0 || n_in > 0x7fffffffLL) return fail(n_in < 0 ? GAT_E_INVALID : GAT_E_UNSUPPORTED, "gat_set_graph_coo: edge count outside the 32-bit count of the sort");
+    int32_t *d_src = nullptr, *d_dst = nullptr;
+    if (on_host && n_in > 0) {
+        GAT_TRY(dalloc(c, &d_src, n_in));
+        if (int rc = dalloc(c, &d_dst, n_in)) { dfree(c, d_src); return rc; }
+        hipError_t e = hipMemcpyAsync(d_src, src, n_in * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_dst, dst, n_in * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { dfree(c, d_src); dfree(c, d_dst); return fail((int)e, std::string("gat_set_graph_coo: upload: ") + hipGetErrorString(e)); }
+        src = d_src; dst = d_dst;
+    }
+    CooBuild b;
+    int rc = coo_sort(src, dst, n_in, n_rows, n_table, table_row0, flags, c->stream, &b);
+    dfree(c, d_src); dfree(c, d_dst);
+    if (rc) return rc;
+    int32_t *rp = nullptr, *ci = nullptr;
+    const int64_t m = b.m;
+    rc = dalloc(c, &rp, n_rows + 1);
+    if (!rc) rc = dalloc(c, &ci, m);
+    if (!rc) rc = coo_fill(&b, n_rows, rp, ci, c->stream);
+    coo_free(&b);
+    if (rc) { dfree(c, rp); dfree(c, ci); return rc; }
+    c->n_rows = n_rows; c->n_edges = m; c->n_table = n_table; c->table_row0 = table_row0;
+    c->row_ptr = rp; c->col_idx = ci;
+    return finish_graph(c, nullptr);
+}
+int gat_set_graph_coo(gat_ctx* c, const int32_t* src, const int32_t* dst, int64_t n_in, int64_t n_rows, int64_t n_table,
+                      int64_t table_row0, int32_t flags) {
+    return set_graph_coo_common(c, src, dst, n_in, n_rows, n_table, table_row0, flags, true);
+}
+int gat_set_graph_coo_device(gat_ctx* c, const int32_t* d_src, const int32_t* d_dst, int64_t n_in, int64_t n_rows, int64_t n_table,
+                             int64_t table_row0, int32_t flags) {
+    return set_graph_coo_common(c, d_src, d_dst, n_in, n_rows, n_table, table_row0, flags, false);
+}
+int gat_graph_size(gat_ctx* c, int64_t* n_rows, int64_t* n_edges, int64_t* n_table) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (!c->have_graph) return fail(GAT_E_STATE, "gat_graph_size: no graph set");
+    if (n_rows) *n_rows = c->n_rows;
+    if (n_edges) *n_edges = c->n_edges;
+    if (n_table) *n_table = c->n_table;
+    return 0;
+}
+int gat_graph_get(gat_ctx* c, int32_t* row_ptr_host, int32_t* col_idx_host) {
+    if (!c || !row_ptr_host || (!col_idx_host && c->have_graph && c->n_edges > 0)) return fail(GAT_E_INVALID, "gat_graph_get: null argument");
+    if (!c->have_graph) return fail(GAT_E_STATE, "gat_graph_get: no graph set");
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    GAT_HIP(hipMemcpy(row_ptr_host, c->row_ptr, (c->n_rows + 1) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (c->n_edges > 0) GAT_HIP(hipMemcpy(col_idx_host, c->col_idx, c->n_edges * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 static int set_features_common(gat_ctx* c, const float* x, int64_t n_rows, int32_t in_dim, hipMemcpyKind kind) {

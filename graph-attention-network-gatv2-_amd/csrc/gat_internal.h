@@ -396,4 +396,23 @@ int launch_adam(float* p, const float* g, float* m, float* v, float lr, int64_t 
 // per-group clip (E:250-278) with the norm kept on the device; scratch >= 1 float
 int launch_clip(float* g, int64_t n, float thresh, float* scratch, hipStream_t s);
 
+// ---- graph construction (gat_graph.hip; the contract is in gatv2_abi.h "graph construction") ---------------------------
+// coo_sort: range check + packing + sort (+ unique) of the edge keys; afterwards b->m is the edge count of the result and
+// coo_fill writes row_ptr [n_rows+1] / col_idx [m].  coo_free releases the temporaries (also after a failure).
+struct CooBuild {
+    uint64_t* k0 = nullptr; uint64_t* k1 = nullptr; uint64_t* sorted = nullptr;   // sorted: k0 or k1
+    void* temp = nullptr; size_t temp_bytes = 0;
+    unsigned long long* status = nullptr;
+    int64_t slots = 0, m = 0;
+    int sbits = 0;
+};
+int coo_sort(const int32_t* d_src, const int32_t* d_dst, int64_t n_in, int64_t n_rows, int64_t n_table, int64_t table_row0,
+             int32_t flags, hipStream_t s, CooBuild* b);
+int coo_fill(CooBuild* b, int64_t n_rows, int32_t* d_row_ptr, int32_t* d_col_idx, hipStream_t s);
+void coo_free(CooBuild* b);
+// one pass over a device CSR: *problem = 0 or GAT_CSR_*, *where = lowest offending index (-1: none); synchronises s
+int csr_check_device(const int32_t* d_row_ptr, const int32_t* d_col_idx, int64_t n_rows, int64_t n_edges, int64_t n_table,
+                     int32_t* problem, int64_t* where, hipStream_t s);
+const char* csr_problem_text(int32_t problem);     // the text gat_set_graph fails with for this rule
+
 }  // namespace gat

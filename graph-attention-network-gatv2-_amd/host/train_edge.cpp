@@ -21,6 +21,13 @@
 // --dropout P / --attn-dropout P (default 0): inverted dropout on every layer's input features / on the attention
 // coefficients during training (gatv2_abi.h "dropout"), masks keyed by --seed.  With --val-mask the validation line
 // then comes from an eval-mode forward (no dropout) after the optimizer step.  Both 0: the output is the reference's.
+// --add-self-loops / --undirected / --coalesce: the graph is rebuilt on the device before training (gat_graph_from_coo:
+// GAT_GRAPH_SELF_LOOPS / SYMMETRIZE / COALESCE, applied in that order); a CSR dataset is expanded to an edge list first.
+// Edge-list dataset: a folder with edges.txt (one "src dst" pair per line, a message flows src -> dst) instead of
+// row_ptr.txt / col_idx.txt is read and built the same way.  The flags and the resulting edge count are printed once.
+// With --ranks P > 1 the build runs in one short-lived forked child (the parent never touches the HIP runtime) that hands
+// the CSR back through shared memory.  --cache applies to CSR datasets (the files as read; the flags apply after loading).
+// --help prints the usage text.
 #include <algorithm>
 #include <chrono>
 #include <cstdint>
@@ -67,12 +74,30 @@ struct Options {
     std::string dtype = "f32";
     std::string train_mask, val_mask;     // text files of N 0/1 values (beyond the reference: README R:134 "later")
     float dropout = 0.f, attn_dropout = 0.f;
+    int graph_flags = 0;                  // GAT_GRAPH_*: --add-self-loops, --undirected, --coalesce
 };
+
+// A CSR built before the ranks were forked (main): row_ptr [n + 1] then col_idx [e] in shared memory.
+struct Prebuilt { const int32_t* row_ptr = nullptr; const int32_t* col_idx = nullptr; int64_t n = 0, e = 0, n_in = 0; };
+
+const char* kUsage =
+    "Usage: train_edge --heads H1,..,HL --outdims D1,..,DL [--num-layers L] [--epochs N] [--optimizer sgd|adam] [--lr X]\n"
+    "                  [--beta1 X] [--beta2 X] [--clip] [--dataset NAME] [--data-root DIR]\n"
+    "  dataset folder: features.txt, labels.txt and either row_ptr.txt + col_idx.txt (CSR, rows = destinations)\n"
+    "                  or edges.txt (one \"src dst\" pair per line)\n"
+    "  graph:    --add-self-loops   every node ends with exactly one self-loop (existing ones are replaced)\n"
+    "            --undirected       add the reverse of every edge\n"
+    "            --coalesce         reduce duplicate edges to one\n"
+    "            (applied in this order, on the device, before training; with --ranks to the whole graph)\n"
+    "  additive: --seed N --load-params FILE --dump-params FILE --device N --cache --dtype f32|bf16\n"
+    "            --train-mask FILE --val-mask FILE --dropout P --attn-dropout P\n"
+    "            --ranks P [--transport rccl|host] [--halo 0|1|2]\n";
 
 struct RankEnv {                      // one forked process per GPU
     int world = 1, rank = 0;
     struct Shared { volatile int id_ready; char id[GAT_COMM_ID_BYTES]; }* shared = nullptr;
     std::string shm_name;
+    Prebuilt graph;                   // world > 1 with an edge-list dataset or graph flags
 };
 
 [[noreturn]] void die(const std::string& msg) {
@@ -129,6 +154,9 @@ Options parse_args(int argc, char** argv) {
         else if (a == "--dump-params" && has_val) o.dump_params = argv[++i];
         else if (a == "--device" && has_val) o.device = std::stoi(argv[++i]);
         else if (a == "--cache") o.cache = true;
+        else if (a == "--add-self-loops") o.graph_flags |= GAT_GRAPH_SELF_LOOPS;
+        else if (a == "--undirected") o.graph_flags |= GAT_GRAPH_SYMMETRIZE;
+        else if (a == "--coalesce") o.graph_flags |= GAT_GRAPH_COALESCE;
         else if (a == "--ranks" && has_val) {
             o.ranks = std::stoi(argv[++i]);
             if (o.ranks < 1) die("Error: --ranks must be >= 1\n");
@@ -212,6 +240,43 @@ void load_ints(const std::string& path, std::vector<int32_t>& v) {
         v.push_back((int32_t)val);
         p = next;
     }
+}
+
+bool file_exists(const std::string& p) { struct stat s{}; return stat(p.c_str(), &s) == 0; }
+// edges.txt takes the place of row_ptr.txt / col_idx.txt when those are absent
+bool edge_list_dataset(const std::string& dir) { return file_exists(dir + "edges.txt") && !file_exists(dir + "row_ptr.txt"); }
+
+bool load_edges(const std::string& path, std::vector<int32_t>& src, std::vector<int32_t>& dst) {
+    std::vector<int32_t> v;
+    load_ints(path, v);
+    if (v.size() % 2 != 0) { std::cerr << "Invalid edges.txt: odd number of values\n"; return false; }
+    src.resize(v.size() / 2); dst.resize(v.size() / 2);
+    for (size_t i = 0; i < src.size(); ++i) { src[i] = v[2 * i]; dst[i] = v[2 * i + 1]; }
+    return true;
+}
+// rows = destinations, columns = sources (E:74-82)
+bool csr_to_edges(const std::vector<int32_t>& rp, const std::vector<int32_t>& ci, int64_t n, std::vector<int32_t>& src,
+                  std::vector<int32_t>& dst) {
+    if (rp[0] != 0 || (int64_t)rp[n] != (int64_t)ci.size()) { std::cerr << "Invalid row_ptr: must start at 0 and end at the edge count\n"; return false; }
+    for (int64_t i = 0; i < n; ++i) if (rp[i + 1] < rp[i]) { std::cerr << "Invalid row_ptr: not monotone\n"; return false; }
+    src = ci; dst.resize(ci.size());
+    for (int64_t i = 0; i < n; ++i) for (int32_t e = rp[i]; e < rp[i + 1]; ++e) dst[e] = (int32_t)i;
+    return true;
+}
+// count, then fill (gat_graph_from_coo): rp [n + 1] and ci are sized by `room`, which gets the edge count
+bool build_graph(const std::vector<int32_t>& src, const std::vector<int32_t>& dst, int64_t n, int flags, int device,
+                 int32_t* (*room)(void*, int64_t), void* arg, int32_t* rp, int64_t* e_out) {
+    int64_t e = 0;
+    if (gat_graph_from_coo(src.data(), dst.data(), (int64_t)src.size(), n, n, 0, flags, nullptr, nullptr, 0, &e, device) != 0) return false;
+    int32_t* ci = room(arg, e);
+    if (!ci) return false;
+    *e_out = e;
+    return gat_graph_from_coo(src.data(), dst.data(), (int64_t)src.size(), n, n, 0, flags, rp, ci, e, &e, device) == 0;
+}
+void print_graph_build(int flags, int64_t n_in, int64_t e) {
+    std::cout << "Graph build: add-self-loops=" << ((flags & GAT_GRAPH_SELF_LOOPS) ? 1 : 0) << " undirected="
+              << ((flags & GAT_GRAPH_SYMMETRIZE) ? 1 : 0) << " coalesce=" << ((flags & GAT_GRAPH_COALESCE) ? 1 : 0) << ": " << n_in
+              << " input edges -> " << e << " edges" << std::endl;
 }
 
 // ---- binary cache: magic, N, F, E, then the four arrays as raw little-endian data ----------------
@@ -298,7 +363,14 @@ int run(const Options& o, const RankEnv& env) {
     // start-up bottleneck at Products scale (~2 GB of text); the cache is rewritten whenever a text
     // file is newer than it.
     const std::string cache = path + "gatv2_cache.bin";
-    if (!(o.cache && load_cache(cache, path, x, N, F0, row_ptr, col_idx, labels))) {
+    const bool edge_list = edge_list_dataset(path);
+    std::vector<int32_t> e_src, e_dst;
+    if (edge_list) {
+        load_features(path + "features.txt", x, N, F0);
+        if (!env.graph.row_ptr && !load_edges(path + "edges.txt", e_src, e_dst)) return 1;
+        load_ints(path + "labels.txt", labels);
+        if ((int64_t)labels.size() != N) { std::cerr << "Invalid labels length\n"; return 1; }
+    } else if (!(o.cache && load_cache(cache, path, x, N, F0, row_ptr, col_idx, labels))) {
         load_features(path + "features.txt", x, N, F0);
         load_ints(path + "row_ptr.txt", row_ptr);
         if ((int64_t)row_ptr.size() != N + 1) { std::cerr << "Invalid row_ptr length\n"; return 1; }
@@ -306,6 +378,23 @@ int run(const Options& o, const RankEnv& env) {
         load_ints(path + "labels.txt", labels);
         if ((int64_t)labels.size() != N) { std::cerr << "Invalid labels length\n"; return 1; }
         if (o.cache) save_cache(cache, x, N, F0, row_ptr, col_idx, labels);
+    }
+    if (env.graph.row_ptr) {                    // built before the ranks were forked
+        if (env.graph.n != N) { std::cerr << "Invalid labels length\n"; return 1; }
+        row_ptr.assign(env.graph.row_ptr, env.graph.row_ptr + N + 1);
+        col_idx.assign(env.graph.col_idx, env.graph.col_idx + env.graph.e);
+        print_graph_build(o.graph_flags, env.graph.n_in, env.graph.e);
+    } else if (edge_list || o.graph_flags) {
+        if (!edge_list && !csr_to_edges(row_ptr, col_idx, N, e_src, e_dst)) return 1;
+        if (N <= 0) { std::cerr << "Invalid labels length\n"; return 1; }
+        row_ptr.assign(N + 1, 0);
+        int64_t e_built = 0;
+        auto room = [](void* v, int64_t e) { auto* c = static_cast<std::vector<int32_t>*>(v); c->assign((size_t)std::max<int64_t>(e, 1), 0); return c->data(); };
+        const bool ok = build_graph(e_src, e_dst, N, o.graph_flags, o.device, room, &col_idx, row_ptr.data(), &e_built);
+        if (!ok) check(1, "gat_graph_from_coo");
+        col_idx.resize((size_t)e_built);
+        print_graph_build(o.graph_flags, (int64_t)e_src.size(), e_built);
+        std::vector<int32_t>().swap(e_src); std::vector<int32_t>().swap(e_dst);
     }
     const int64_t E = (int64_t)col_idx.size();
 
@@ -505,6 +594,27 @@ int main(int argc, char** argv) {
         const float p = std::strtof(argv[i + 1], &end);
         if (end == argv[i + 1] || *end != '\0' || !(p >= 0.f && p < 1.f)) die("Error: " + a + " must be in [0, 1)\n");
     }
+    // --help, and graph flags without a graph to apply them to, end here: before anything touches the GPU
+    bool graph_flag = false;
+    for (int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--help") { std::cout << kUsage; return 0; }
+        if (a == "--add-self-loops" || a == "--undirected" || a == "--coalesce") graph_flag = true;
+    }
+    if (graph_flag) {
+        std::string root = "./data", name = "pubmed";
+        bool root_given = false;
+        for (int i = 1; i + 1 < argc; ++i) {
+            if (std::string(argv[i]) == "--data-root") { root = argv[i + 1]; root_given = true; }
+            if (std::string(argv[i]) == "--dataset") name = argv[i + 1];
+        }
+        const char* env_root = std::getenv("DATA_ROOT");
+        if (env_root && !root_given) root = env_root;
+        if (!root.empty() && root.back() != '/' && root.back() != '\\') root += '/';
+        const std::string dir = root + name + "/";
+        if (!file_exists(dir + "edges.txt") && !(file_exists(dir + "row_ptr.txt") && file_exists(dir + "col_idx.txt")))
+            die("Error: --add-self-loops / --undirected / --coalesce need a graph: no edges.txt and no row_ptr.txt + col_idx.txt in " + dir + "\n");
+    }
     if (!multi) print_memory_tracker_before();
     Options o = parse_args(argc, argv);
     if (!o.seed_given) { o.seed = (uint64_t)time(nullptr); o.seed_given = true; }     // E:1305; one seed for all ranks
@@ -517,6 +627,46 @@ int main(int argc, char** argv) {
     env.world = o.ranks;
     env.shared = static_cast<RankEnv::Shared*>(mem);
     env.shm_name = "/gatv2_" + std::to_string((long)getpid());
+    // Edge-list dataset or graph flags: the whole graph is built ONCE, in a short-lived child (this process must not
+    // touch the HIP runtime before it forks its ranks); the CSR comes back in anonymous shared memory the ranks inherit.
+    const std::string dir = o.data_root + o.dataset + "/";
+    if (edge_list_dataset(dir) || o.graph_flags) {
+        std::vector<int32_t> src, dst, labels;
+        load_ints(dir + "labels.txt", labels);
+        const int64_t N = (int64_t)labels.size();
+        if (N <= 0) die("Invalid labels length\n");
+        if (edge_list_dataset(dir)) {
+            if (!load_edges(dir + "edges.txt", src, dst)) return 1;
+        } else {
+            std::vector<int32_t> rp, ci;
+            load_ints(dir + "row_ptr.txt", rp);
+            if ((int64_t)rp.size() != N + 1) die("Invalid row_ptr length\n");
+            load_ints(dir + "col_idx.txt", ci);
+            if (!csr_to_edges(rp, ci, N, src, dst)) return 1;
+        }
+        const int64_t n_in = (int64_t)src.size();
+        const int64_t cap = n_in * ((o.graph_flags & GAT_GRAPH_SYMMETRIZE) ? 2 : 1) + ((o.graph_flags & GAT_GRAPH_SELF_LOOPS) ? N : 0);
+        const size_t bytes = (size_t)(4 + N + 1 + std::max<int64_t>(cap, 1)) * sizeof(int32_t);
+        void* g = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
+        if (g == MAP_FAILED) die("Error: mmap failed\n");
+        int64_t* e_out = static_cast<int64_t*>(g);                 // [0]: edge count, written by the child
+        int32_t* rp_out = static_cast<int32_t*>(g) + 4;
+        int32_t* ci_out = rp_out + N + 1;
+        std::fflush(nullptr);
+        const pid_t pid = fork();
+        if (pid < 0) die("Error: fork failed\n");
+        if (pid == 0) {
+            struct Room { int32_t* ci; int64_t cap; } room{ci_out, cap};
+            auto give = [](void* v, int64_t e) { auto* r = static_cast<Room*>(v); return e <= r->cap ? r->ci : nullptr; };
+            const bool ok = build_graph(src, dst, N, o.graph_flags, o.device, give, &room, rp_out, e_out);
+            if (!ok) std::fprintf(stderr, "Error launching gat_graph_from_coo: %s\n", gat_last_error());
+            std::fflush(nullptr);
+            std::_Exit(ok ? 0 : 1);
+        }
+        int status = 0;
+        if (waitpid(pid, &status, 0) < 0 || !WIFEXITED(status) || WEXITSTATUS(status) != 0) return 1;
+        env.graph.row_ptr = rp_out; env.graph.col_idx = ci_out; env.graph.n = N; env.graph.e = *e_out; env.graph.n_in = n_in;
+    }
     std::fflush(nullptr);
     std::vector<pid_t> kids;
     for (int r = 0; r < o.ranks; ++r) {

@@ -104,6 +104,17 @@ def local_csr(plan: ShardPlan, row_ptr: np.ndarray, col_idx: np.ndarray):
     return rp, ci
 
 
+def plan_from_coo(src, dst, n_nodes: int, world: int, rank: int, flags: int = 0, device: int = 0):
+    """Edge-list input for a sharded run: the GLOBAL CSR is built on the device with the builder's flags
+    (abi.graph_from_coo: self-loops / symmetrize / coalesce apply to the whole graph, before it is cut), then planned and cut
+    as for a CSR input.  -> (plan, row_ptr_local, col_idx_local, row_ptr, col_idx)"""
+    from . import abi
+    row_ptr, col_idx = abi.graph_from_coo(src, dst, n_nodes, flags=flags, device=device)
+    plan = make_plan(row_ptr, world, rank)
+    rp, ci = local_csr(plan, row_ptr, col_idx)
+    return plan, rp, ci, row_ptr, col_idx
+
+
 class TorchComm:
     """The three exchanges over torch.distributed.  backend "nccl" (= RCCL over xGMI): in place on
     device tensors.  Any other backend (gloo, used by the CPU tests and the 2-ranks-on-one-GPU

@@ -131,6 +131,53 @@ int gat_set_labels_device(gat_ctx* ctx, const int32_t* d_labels, int64_t n_rows)
 int gat_set_source_features(gat_ctx* ctx, const float* x_table, int64_t n_table, int32_t in_dim);
 int gat_set_source_features_device(gat_ctx* ctx, const float* d_x_table, int64_t n_table, int32_t in_dim);
 
+/* ---- graph construction (beyond the reference, which reads a finished CSR only: README "Graph Data Handling") ----------
+ * The training graph built ON the device from an edge list (COO / `edge_index`): n_in edges (src[i], dst[i]), a message
+ * flows src -> dst.  dst is a row of the context, 0 <= dst < n_rows; src is a row of the source table, 0 <= src < n_table
+ * (single GPU: n_table == n_rows, table_row0 == 0; a destination-range shard as in gat_set_graph).
+ *   GAT_GRAPH_SELF_LOOPS  every row r ends with EXACTLY one edge from table row table_row0 + r: self-loops already present
+ *                         (any multiplicity) are dropped, one is added
+ *   GAT_GRAPH_SYMMETRIZE  for every input edge with src != dst the edge (dst, src) is added as well; needs n_table == n_rows
+ *                         and table_row0 == 0, else GAT_E_UNSUPPORTED (shards: symmetrize the whole graph, then shard)
+ *   GAT_GRAPH_COALESCE    edges with equal (src, dst) are reduced to one
+ * Applied in this order: symmetrize, self-loops, coalesce.  Without COALESCE multiplicities are kept.  flags == 0 is the
+ * plain COO -> CSR conversion; any other bit: GAT_E_INVALID.  Result: CSR with rows = destinations and, inside every row,
+ * the sources ascending — fully determined by the input multiset and the flags.
+ * Errors: a src or dst out of range gives GAT_E_INVALID and a text naming the lowest offending edge index and its value;
+ * more than 2^31-1 intermediate edges (n_in, doubled by SYMMETRIZE, plus n_rows with SELF_LOOPS: the count the 32-bit
+ * radix sort takes) gives GAT_E_UNSUPPORTED, never a truncated graph.  n_in == 0 is legal.
+ * Temporary device memory: 16 B x the intermediate edge count (two buffers of 64-bit keys) plus a few MB of sort scratch
+ * — 0.99 GB for 61.9 M edges, 2.0 GB with SYMMETRIZE — freed before return.  Inputs are never modified. */
+enum { GAT_GRAPH_SELF_LOOPS = 1, GAT_GRAPH_SYMMETRIZE = 2, GAT_GRAPH_COALESCE = 4 };
+/* Stateless, device pointers (current device).  Count-then-fill: with d_col_idx == NULL only *n_edges_out is written; with
+ * col_capacity < *n_edges_out the call returns GAT_E_INVALID and still sets *n_edges_out.  d_row_ptr: n_rows + 1 entries.
+ * Both phases run the whole sort (the count of a COALESCE build is not known earlier).  Synchronises `stream` (may be NULL). */
+int gat_graph_from_coo_device(const int32_t* d_src, const int32_t* d_dst, int64_t n_in, int64_t n_rows, int64_t n_table,
+                              int64_t table_row0, int32_t flags, int32_t* d_row_ptr, int32_t* d_col_idx, int64_t col_capacity,
+                              int64_t* n_edges_out, void* stream);
+/* The same with HOST arrays in and out, staged by the library on `device` (callers without a device allocator). */
+int gat_graph_from_coo(const int32_t* src, const int32_t* dst, int64_t n_in, int64_t n_rows, int64_t n_table, int64_t table_row0,
+                       int32_t flags, int32_t* row_ptr_out, int32_t* col_idx_out, int64_t col_capacity, int64_t* n_edges_out,
+                       int32_t device);
+/* Build on the context's device, then continue exactly as gat_set_graph_device (work list, source-major index).  State
+ * rules of gat_set_graph (graph already set: GAT_E_STATE).  Host arrays / device pointers. */
+int gat_set_graph_coo(gat_ctx* ctx, const int32_t* src, const int32_t* dst, int64_t n_in, int64_t n_rows, int64_t n_table,
+                      int64_t table_row0, int32_t flags);
+int gat_set_graph_coo_device(gat_ctx* ctx, const int32_t* d_src, const int32_t* d_dst, int64_t n_in, int64_t n_rows,
+                             int64_t n_table, int64_t table_row0, int32_t flags);
+/* The CSR the context trains on (after a build the caller does not know the edge count).  Any pointer of gat_graph_size may
+ * be NULL; gat_graph_get copies n_rows + 1 and n_edges int32 to the host. */
+int gat_graph_size(gat_ctx* ctx, int64_t* n_rows, int64_t* n_edges, int64_t* n_table);
+int gat_graph_get(gat_ctx* ctx, int32_t* row_ptr_host, int32_t* col_idx_host);
+/* One pass over a DEVICE CSR (reads 4(n_rows+1) + 4 n_edges bytes).  *problem = 0 when the CSR is fine, else the first rule
+ * broken in the order gat_set_graph checks them; *where (may be NULL) = the lowest offending index (0, n_rows, the row i with
+ * row_ptr[i+1] < row_ptr[i], the edge e with col_idx[e] outside [0, n_table)), -1 when fine.  The call returns 0 when it could
+ * check: a bad graph is a result, not a failure.  gat_set_graph_device runs this check on its arguments before anything
+ * consumes them and fails with gat_set_graph's codes and texts, leaving the context without a graph. */
+enum { GAT_CSR_OK = 0, GAT_CSR_BAD_START = 1, GAT_CSR_BAD_END = 2, GAT_CSR_NOT_MONOTONE = 3, GAT_CSR_COL_RANGE = 4 };
+int gat_graph_check_device(const int32_t* d_row_ptr, const int32_t* d_col_idx, int64_t n_rows, int64_t n_edges, int64_t n_table,
+                           int32_t* problem, int64_t* where, void* stream);
+
 /* ---- parameters (Xavier init E:186-248; flat layouts E:1242-1258) --------------------------- */
 enum { GAT_PARAM_W = 0, GAT_PARAM_A = 1, GAT_PARAM_WO = 2 };
 int gat_param_count(gat_ctx* ctx, int group, int64_t* count);
