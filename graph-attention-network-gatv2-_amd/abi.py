@@ -54,6 +54,8 @@ COMM_HALO = 3
 (TAP_SRC, TAP_DST, TAP_ALPHA, TAP_HPRE, TAP_HOUT, TAP_Y, TAP_G, TAP_GE, TAP_MAX, TAP_SUM, TAP_PL,
  TAP_PR, TAP_SCORE, TAP_GALPHA, TAP_GX) = range(15)
 TAP_ATTN_KEEP, TAP_FEAT_KEEP = 15, 16       # dropout factors (0 or 1/(1-p)) for the step the counter holds
+TAP_EDGE_KEEP = 17                          # DropEdge: 1 = edge kept, 0 = dropped, [E], likewise
+DROPEDGE_KEEP_SELF, DROPEDGE_SHARED_LAYERS = 1, 2
 (K_PROJECT, K_EDGE_FWD, K_HEAD_FWD, K_HEAD_BWD, K_EDGE_BWD, K_GPL_SUM, K_GRAD_W, K_GRAD_X, K_MISC,
  K_EXCHANGE, K_EDGE_FUSED, K_COUNT) = range(12)
 COMM_ID_BYTES = 128
@@ -193,6 +195,7 @@ def _declare(lib: C.CDLL) -> None:
         "gat_synth_labels_device": [C.c_uint64, i64, i64, i32, vp, vp],
         "gat_synth_argsort_u64": [vp, i64, vp, vp],
         "gat_set_dropout": [vp, f32, f32, C.c_uint64, C.c_uint64],
+        "gat_set_dropedge": [vp, f32, i32],
         "gat_set_training": [vp, i32],
         "gat_dropout_step": [vp, P(C.c_uint64)],
         "gat_set_shard_bounds": [vp, i32, vp],
@@ -410,6 +413,13 @@ class GatContext:
         """Inverted feature / attention dropout in training mode; p in [0, 1).  The mask counter starts at first_step."""
         _chk(self.lib.gat_set_dropout(self._ctx, float(feat_p), float(attn_p), int(seed) & (2 ** 64 - 1), int(first_step)))
 
+    def set_dropedge(self, p: float = 0.0, keep_self: bool = False, shared_layers: bool = False, flags: int = 0):
+        """DropEdge in training mode (gatv2_abi.h "DropEdge"): every step drops each edge with probability p in [0, 1) before
+        the softmax.  keep_self: self-loops are never dropped; shared_layers: one mask per step for all layers.  Seed and
+        counter are those of set_dropout.  ``flags``: extra raw GAT_DROPEDGE_* bits (or-ed in)."""
+        f = int(flags) | (DROPEDGE_KEEP_SELF if keep_self else 0) | (DROPEDGE_SHARED_LAYERS if shared_layers else 0)
+        _chk(self.lib.gat_set_dropedge(self._ctx, float(p), f))
+
     def set_training(self, training: bool = True):
         """False: eval mode (no dropout, the counter does not advance)."""
         _chk(self.lib.gat_set_training(self._ctx, int(bool(training))))
@@ -547,6 +557,7 @@ class GatContext:
             TAP_SCORE: ((H, E), np.float32), TAP_GALPHA: ((H, E), np.float32),
             TAP_GX: ((N, self.heads[l - 1] * self.outdims[l - 1] if l > 0 else 0), np.float32),
             TAP_ATTN_KEEP: ((H, E), np.float32), TAP_FEAT_KEEP: ((N, self.in_dims[l]), np.float32),
+            TAP_EDGE_KEEP: ((E,), np.float32),
         }
         shape, dt = shapes[tensor]
         out = np.empty(shape, dt)

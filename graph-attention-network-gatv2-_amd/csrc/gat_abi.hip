@@ -178,6 +178,7 @@ struct gat_ctx {
     int32_t dbg = 0;                                // GAT_DBG timing experiments (0 = product behaviour)
     // dropout (gatv2_abi.h "dropout"): probabilities, seed, mode, the device step counter, the unsharded node ids of a shard
     float drop_pf = 0.f, drop_pa = 0.f;
+    float edge_p = 0.f; int32_t edge_flags = 0;     // DropEdge (gat_set_dropedge); seed and counter are the dropout ones
     uint64_t drop_seed = 0;
     bool training = true;
     uint64_t* drop_step = nullptr;                  // [1] device: advanced by the layer-0 projection of a training forward
@@ -272,17 +273,19 @@ static float* ga_of(gat_ctx* c, int l) { return c->grads + c->nW + c->layers[l].
 static float* gWo_of(gat_ctx* c) { return c->grads + c->nW + c->nA; }
 static bool feat_drop_on(const gat_ctx* c) { return c->training && c->drop_pf > 0.f; }
 static bool attn_drop_on(const gat_ctx* c) { return c->training && c->drop_pa > 0.f; }
-static bool drop_on(const gat_ctx* c) { return feat_drop_on(c) || attn_drop_on(c); }
+static bool edge_drop_on(const gat_ctx* c) { return c->training && c->edge_p > 0.f; }
+static bool drop_on(const gat_ctx* c) { return feat_drop_on(c) || attn_drop_on(c) || edge_drop_on(c); }
 // what layer l reads as its input: x_l, or x_l with the feature-dropout mask applied (projection and grad_W alike)
 static const float* Xin_raw(gat_ctx* c, int l) { return l == 0 ? c->X0 : c->layers[l - 1].hout; }
 static const float* Xin_of(gat_ctx* c, int l) { return feat_drop_on(c) && (size_t)l < c->xdrop.size() && c->xdrop[(size_t)l] ? c->xdrop[(size_t)l] : Xin_raw(c, l); }
 static const float* Xtab_of(gat_ctx* c) { return feat_drop_on(c) && c->xdrop_tab ? c->xdrop_tab : c->Xtab; }
+static uint32_t drop_threshold(double p) { return (uint32_t)std::min<double>(16777216.0, std::floor(p * 16777216.0 + 0.5)); }
 static DropArgs drop_args(gat_ctx* c, int32_t kind, int32_t l) {
     const double p = kind == kDropAttn ? c->drop_pa : c->drop_pf;
     DropArgs d{};
     d.step = c->drop_step; d.bounds = c->drop_bounds; d.max_rows = c->drop_max_rows; d.row0 = c->table_row0;
     d.seed_lo = (uint32_t)c->drop_seed; d.seed_hi = (uint32_t)(c->drop_seed >> 32);
-    d.T = (uint32_t)std::min<double>(16777216.0, std::floor(p * 16777216.0 + 0.5));
+    d.T = drop_threshold(p);
     d.scale = (float)(1.0 / (1.0 - p));
     d.layer = l;
     d.on = 1;
@@ -929,7 +932,16 @@ int gat_layer_project(gat_ctx* c, int32_t l) {
 }
 
 static EdgeFwdArgs plan_forward_edges(gat_ctx* c, int32_t l);
-static DropArgs attn_drop_args(gat_ctx* c, int32_t l) { return attn_drop_on(c) ? drop_args(c, kDropAttn, l) : DropArgs{}; }
+// the DropEdge part of the mask parameters, from the context's setting whatever the mode (the tap; the passes ask edge_drop_on first)
+static void set_edge_drop(const gat_ctx* c, DropArgs* d) { d->Te = drop_threshold(c->edge_p); d->eflags = c->edge_flags; }
+// what the edge passes of layer l take: attention dropout and / or DropEdge (either one selects the DROP instantiations)
+static DropArgs attn_drop_args(gat_ctx* c, int32_t l) {
+    if (!attn_drop_on(c) && !edge_drop_on(c)) return DropArgs{};
+    DropArgs d = drop_args(c, kDropAttn, l);
+    if (!attn_drop_on(c)) { d.T = 0; d.scale = 1.f; }
+    if (edge_drop_on(c)) set_edge_drop(c, &d);
+    return d;
+}
 int gat_layer_forward_edges(gat_ctx* c, int32_t l) {
     GAT_TRY(check_layer(c, l));
     const EdgeFwdArgs a = plan_forward_edges(c, l);
@@ -1485,6 +1497,23 @@ int gat_set_dropout(gat_ctx* c, float feat_p, float attn_p, uint64_t seed, uint6
     c->drop_pf = feat_p; c->drop_pa = attn_p; c->drop_seed = seed;
     return ensure_drop_buffers(c);
 }
+int gat_set_dropedge(gat_ctx* c, float edge_p, int32_t flags) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (!(edge_p >= 0.f && edge_p < 1.f)) return fail(GAT_E_INVALID, "gat_set_dropedge: edge_p must be in [0, 1)");
+    if (flags & ~(GAT_DROPEDGE_KEEP_SELF | GAT_DROPEDGE_SHARED_LAYERS)) return fail(GAT_E_INVALID, "gat_set_dropedge: unknown flag bits");
+#ifdef GAT_EXPERIMENTS                               // (the release library does not know the switch's name)
+    if (c->dbg != 0 && edge_p > 0.f)
+        return fail(GAT_E_UNSUPPORTED, "gat_set_dropedge: not with a GAT_DBG timing experiment (those kernels have no dropout form)");
+#endif
+    if (!c->drop_step) {                                 // gat_set_dropout was never called: seed 0, counter 0
+        GAT_TRY(dalloc(c, &c->drop_step, 1));
+        GAT_HIP(hipMemsetAsync(c->drop_step, 0, sizeof(uint64_t), c->stream));
+        GAT_HIP(hipStreamSynchronize(c->stream));
+    }
+    graph_drop(c);                                       // a captured step holds the other kernel sequence
+    c->edge_p = edge_p; c->edge_flags = flags;
+    return 0;
+}
 int gat_set_training(gat_ctx* c, int32_t training) {
     if (!c) return fail(GAT_E_INVALID, "null context");
     if (training != 0 && training != 1) return fail(GAT_E_INVALID, "gat_set_training: 0 (eval) or 1 (training)");
@@ -1761,6 +1790,18 @@ int gat_tap(gat_ctx* c, int tensor, int32_t l, void* host, int64_t count) {
             const DropArgs d = drop_args(c, attn ? kDropAttn : kDropFeat, l);
             int rc = attn ? launch_attn_keep_tap(c->row_ptr, N, E, y.H, d, tmp, c->stream) : launch_feat_keep_tap(N, y.F, d, tmp, c->stream);
             if (rc == 0) rc = d2h(c, host, tmp, (size_t)n * sizeof(float));
+            (void)hipFree(tmp);
+            return rc;
+        }
+        case GAT_TAP_EDGE_KEEP: {                      // DropEdge's mask for the step the counter holds (0 / 1 per CSR edge)
+            GAT_TRY(need(E));
+            if (!c->drop_step) return fail(GAT_E_STATE, "gat_tap: DropEdge was never set (gat_set_dropedge)");
+            float* tmp = nullptr;
+            GAT_HIP(hipMalloc((void**)&tmp, (size_t)std::max<int64_t>(E, 1) * sizeof(float)));
+            DropArgs d = drop_args(c, kDropAttn, l);
+            set_edge_drop(c, &d);
+            int rc = launch_edge_keep_tap(c->row_ptr, c->col_idx, N, E, d, tmp, c->stream);
+            if (rc == 0) rc = d2h(c, host, tmp, (size_t)E * sizeof(float));
             (void)hipFree(tmp);
             return rc;
         }

@@ -1,5 +1,5 @@
 // gat_dropout.hip — the dense side of dropout (include/gatv2_abi.h "dropout"): the step counter, the feature-dropout
-// copy of a layer's input and its backward, and the two mask taps.  Attention dropout lives inside the edge kernels
+// copy of a layer's input and its backward, and the mask taps (DropEdge's included).  Attention dropout lives inside the edge kernels
 // (gat_edge_kernels.hip, DROP instantiations).  Every kernel evaluates the masks with the same device functions
 // (gat_internal.h drop_*), so the taps show exactly what the passes used.
 #include "gat_internal.h"
@@ -61,6 +61,21 @@ __global__ __launch_bounds__(256) void attn_keep_tap_kernel(const int32_t* __res
     }
 }
 
+// out[e] = 1 if CSR edge e is kept by DropEdge, else 0 (row by binary search, as above)
+__global__ __launch_bounds__(256) void edge_keep_tap_kernel(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col_idx,
+                                                            int64_t n_rows, int64_t n_edges, DropArgs d, float* __restrict__ out) {
+    const uint32_t K = drop_edge_key(d);
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_edges; e += stride) {
+        int64_t lo = 0, hi = n_rows;                 // row_ptr[lo] <= e < row_ptr[hi]
+        while (hi - lo > 1) {
+            const int64_t mid = (lo + hi) >> 1;
+            if ((int64_t)row_ptr[mid] <= e) lo = mid; else hi = mid;
+        }
+        out[e] = drop_edge_kept(d, drop_mix(K, drop_node(d, lo)), (int)(e - row_ptr[lo]), col_idx[e], lo) ? 1.f : 0.f;
+    }
+}
+
 unsigned grid_for(int64_t n) {
     const int64_t b = (n + 255) / 256;
     return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
@@ -88,6 +103,12 @@ int launch_feat_drop_bwd(float* g, int64_t rows, int32_t F, const DropArgs& d, h
 int launch_attn_keep_tap(const int32_t* row_ptr, int64_t n_rows, int64_t n_edges, int32_t H, const DropArgs& d, float* out, hipStream_t s) {
     if (n_edges <= 0 || n_rows <= 0) return 0;
     hipLaunchKernelGGL(attn_keep_tap_kernel, dim3(grid_for(n_edges)), dim3(256), 0, s, row_ptr, n_rows, n_edges, H, d, out);
+    GAT_HIP(hipGetLastError());
+    return 0;
+}
+int launch_edge_keep_tap(const int32_t* row_ptr, const int32_t* col_idx, int64_t n_rows, int64_t n_edges, const DropArgs& d, float* out, hipStream_t s) {
+    if (n_edges <= 0 || n_rows <= 0) return 0;
+    hipLaunchKernelGGL(edge_keep_tap_kernel, dim3(grid_for(n_edges)), dim3(256), 0, s, row_ptr, col_idx, n_rows, n_edges, d, out);
     GAT_HIP(hipGetLastError());
     return 0;
 }

@@ -40,6 +40,10 @@ __device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_ex
 __device__ __forceinline__ float attn_keep(const DropArgs& d, uint32_t kd, int k, int h) {
     return drop_factor(d, drop_mix(drop_mix(kd, (uint32_t)k), (uint32_t)h));
 }
+// DropEdge (gatv2_abi.h "DropEdge"): ke = mix(K_e(l), node(dst)) of a row; the per-edge draw is drop_edge_kept (gat_internal.h).
+// A dropped edge is handled like a padded slot of a chunk: its score is replaced by -inf BY PREDICATE before the max (p = exp2(-inf) = 0
+// exactly, it never enters m or Z), and the backward selects ge = alpha = 0 for it — so its record / message row is all zero.
+__device__ __forceinline__ uint32_t edge_row_key(const DropArgs& d, int64_t row) { return drop_mix(drop_edge_key(d), drop_node(d, row)); }
 // kernel argument of the DROP instantiations: the plain struct + the mask parameters (the default ones keep the plain struct)
 template <bool DROP> struct FwdArgsOf { typedef EdgeFwdArgs T; };
 template <> struct FwdArgsOf<true> { typedef EdgeFwdDropArgs T; };
@@ -234,15 +238,18 @@ __device__ __forceinline__ void store_row(float* __restrict__ msg, int slot, int
 template <int HD, int D, int UU, int USC, bool ALPHA, bool BF, bool DROP = false, class AT = EdgeFwdArgs>
 __device__ __forceinline__ void fwd_chunk(const AT& A, int e0, int e_end, int e_end_v, int c, int gidx,
                                           float pr, float ac2, bool multi, float (&sc)[USC], float& m, float& Z,
-                                          float& acc, uint32_t kd = 0, int rb = 0) {
+                                          float& acc, uint32_t kd = 0, int rb = 0, uint32_t ke = 0, int64_t row = 0) {
     constexpr int G = 64 / HD;
     constexpr int H = HD / D;
     float v[UU];
+    [[maybe_unused]] bool ek[UU];                    // DropEdge: the edge is kept (one draw per edge, all heads)
 #pragma unroll
     for (int u = 0; u < UU; ++u) {
         const int j = e0 + u * G + gidx;
         const int jc = j < e_end ? j : e_end - 1;
-        v[u] = gather_row<HD, BF>(A.PL, A.col_idx[jc], c);
+        const int src = A.col_idx[jc];
+        v[u] = gather_row<HD, BF>(A.PL, src, c);
+        if constexpr (DROP) ek[u] = drop_edge_kept(A.drop, ke, jc - rb, src, row);
     }
     // scores: the cross-lane stages run slot-interleaved (UU independent DPP chains), so that no
     // stage waits on the VALU->DPP hazard of its own predecessor
@@ -254,7 +261,9 @@ __device__ __forceinline__ void fwd_chunk(const AT& A, int e0, int e_end, int e_
 #pragma unroll
     for (int u = 0; u < UU; ++u) {
         const int j = e0 + u * G + gidx;
-        sc[u] = (j < e_end_v) ? t[u] : -INFINITY;
+        bool in = j < e_end_v;
+        if constexpr (DROP) in = in && ek[u];        // a dropped edge: out of the max, Z and the sum, alpha exactly 0
+        sc[u] = in ? t[u] : -INFINITY;
         cm = fmaxf(cm, sc[u]);
         if constexpr (ALPHA) {                       // tap: the reference's attn_score (natural-log domain, E:323)
             if (A.score != nullptr && (c % D) == 0 && j < e_end_v) A.score[(int64_t)j * H + c / D] = t[u] * kLn2;
@@ -308,14 +317,15 @@ __global__ __launch_bounds__(256) void edge_fwd_kernel(FwdArgsT<DROP> A) {
     for (int u = 0; u < U; ++u) sc[u] = -INFINITY;
     uint32_t kd = 0;
     int rb = 0;
-    if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; }
+    uint32_t ke = 0;
+    if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; ke = edge_row_key(A.drop, row); }
 
     for (int e0 = b; e0 < e_end; e0 += CH) {
         if constexpr (U >= 2) {
-            if (e_end - e0 <= CH / 2) fwd_chunk<HD, D, U / 2, U, ALPHA, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, kd, rb);
-            else fwd_chunk<HD, D, U, U, ALPHA, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, kd, rb);
+            if (e_end - e0 <= CH / 2) fwd_chunk<HD, D, U / 2, U, ALPHA, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, kd, rb, ke, row);
+            else fwd_chunk<HD, D, U, U, ALPHA, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, kd, rb, ke, row);
         } else {
-            fwd_chunk<HD, D, U, U, ALPHA, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, kd, rb);
+            fwd_chunk<HD, D, U, U, ALPHA, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, kd, rb, ke, row);
         }
     }
 
@@ -417,17 +427,19 @@ __global__ __launch_bounds__(256) void edge_fwd_fix_kernel(EdgeFwdArgs A) {
 template <int HD, int D, int UU, bool STORE, bool TAPS, int DBG, bool BF, bool DROP = false, class AT = EdgeBwdArgs>
 __device__ __forceinline__ void bwd_chunk(const AT& A, int e0, int e_end, int e_end_v, int c, int gidx,
                                           float g, float pr, float dot, float ac, float ac2, float m2, float inv,
-                                          float& ga, float& gpr, uint32_t kd = 0, int rb = 0) {
+                                          float& ga, float& gpr, uint32_t kd = 0, int rb = 0, uint32_t ke = 0, int64_t row = 0) {
     constexpr int G = 64 / HD;
     constexpr int H = HD / D;
     float v[UU];
     int sid[UU];            // gPL row (atomics path) or message slot (store path)
+    [[maybe_unused]] bool ek[UU];                                // DropEdge: the edge is kept
 #pragma unroll
     for (int u = 0; u < UU; ++u) {
         const int j = e0 + u * G + gidx;
         const int jc = j < e_end ? j : e_end - 1;                // clamped: loads need no predicate
         const int src = A.col_idx[jc];
         v[u] = gather_row<HD, BF>(A.PL, src, c);
+        if constexpr (DROP) ek[u] = drop_edge_kept(A.drop, ke, jc - rb, src, row);
         if constexpr (STORE) sid[u] = (DBG == 2) ? jc : A.pos[jc]; else sid[u] = src;
     }
     // Compute in passes of P <= 8 slots (bounds the live registers; the first pass starts as soon as
@@ -453,22 +465,26 @@ __device__ __forceinline__ void bwd_chunk(const AT& A, int e0, int e_end, int e_
         for (int q = 0; q < P; ++q) {
             const int u = p0 + q;
             const int j = e0 + u * G + gidx;
-            const bool valid = j < e_end_v;
+            const bool inr = j < e_end_v;
+            bool valid = inr;
+            if constexpr (DROP) valid = inr && ek[u];                // a dropped edge: ge = alpha = 0 by selection, a zero message row
             const float ge = valid ? al[q] * (ga_[q] - dot) : 0.f;   // padded slots contribute nothing
             const float s = v[u] + pr;
             const bool pos = s > 0.f;
             const float gs = ge * ac * (pos ? 1.0f : A.slope);
             ga = fmaf(ge, fmaxf(s, s * A.slope), ga);
             gpr += gs;
-            const float msg = fmaf(g, DROP ? al[q] * kf[q] : al[q], gs);   // d/dPL[src] from this edge
-            if (valid && DBG != 1) {
+            float alm = al[q];
+            if constexpr (DROP) alm = valid ? al[q] * kf[q] : 0.f;
+            const float msg = fmaf(g, alm, gs);                      // d/dPL[src] from this edge
+            if (inr && DBG != 1) {
                 if constexpr (STORE) store_row<HD, G == 1, BF>(A.msg, sid[u], c, msg);
-                else unsafeAtomicAdd(A.gPL + (int64_t)sid[u] * HD + c, msg);
+                else if (valid) unsafeAtomicAdd(A.gPL + (int64_t)sid[u] * HD + c, msg);
             }
             if constexpr (TAPS) {
-                if (valid && (c % D) == 0) {
+                if (inr && (c % D) == 0) {
                     A.ge[(int64_t)j * H + c / D] = ge;
-                    if (A.galpha != nullptr) A.galpha[(int64_t)j * H + c / D] = ga_[q];
+                    if (A.galpha != nullptr) A.galpha[(int64_t)j * H + c / D] = valid ? ga_[q] : 0.f;
                 }
             }
         }
@@ -508,13 +524,14 @@ __global__ __launch_bounds__(256) void edge_bwd_kernel(BwdArgsT<DROP> A) {
         float gpr = 0.f;
         uint32_t kd = 0;
         int rb = 0;
-        if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; }
+        uint32_t ke = 0;
+        if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; ke = edge_row_key(A.drop, row); }
         for (int e0 = b; e0 < e_end; e0 += CH) {
             if constexpr (U >= 2) {
-                if (e_end - e0 <= CH / 2) bwd_chunk<HD, D, U / 2, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, kd, rb);
-                else bwd_chunk<HD, D, U, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, kd, rb);
+                if (e_end - e0 <= CH / 2) bwd_chunk<HD, D, U / 2, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, kd, rb, ke, row);
+                else bwd_chunk<HD, D, U, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, kd, rb, ke, row);
             } else {
-                bwd_chunk<HD, D, U, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, kd, rb);
+                bwd_chunk<HD, D, U, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, kd, rb, ke, row);
             }
         }
 #pragma unroll
@@ -631,11 +648,17 @@ __device__ __forceinline__ void store_row_n(float* __restrict__ msg, int slot, i
 // finishes them unchanged.
 template <int HD, int D, int N, int UU, bool BF, bool DROP = false, class AT = EdgeFwdArgs>
 __device__ __forceinline__ void fwd2_chunk(const AT& A, int e0, int e_end_v, int cp, int gidx, int srcv,
-                                           vnf<N> pr, vnf<N> ac2, float& m, float& Z, vnf<N>& acc, uint32_t kd = 0, int rb = 0) {
+                                           vnf<N> pr, vnf<N> ac2, float& m, float& Z, vnf<N>& acc, uint32_t kd = 0, int rb = 0,
+                                           uint32_t ke = 0, int64_t row = 0) {
     constexpr int LPE = HD / N, G = 64 / LPE, DL = D / N;
     vnf<N> v[UU];
+    [[maybe_unused]] bool ek[UU];                    // DropEdge: the edge is kept
 #pragma unroll
-    for (int u = 0; u < UU; ++u) v[u] = gather_row_n<HD, N, BF>(A.PL, __shfl(srcv, u * G + gidx), cp);
+    for (int u = 0; u < UU; ++u) {
+        const int src = __shfl(srcv, u * G + gidx);
+        v[u] = gather_row_n<HD, N, BF>(A.PL, src, cp);
+        if constexpr (DROP) ek[u] = drop_edge_kept(A.drop, ke, e0 + u * G + gidx - rb, src, row);
+    }
     float t[UU];
 #pragma unroll
     for (int u = 0; u < UU; ++u) t[u] = hsum<N>(ac2 * lrelu_n<N>(v[u] + pr, A.slope));
@@ -644,7 +667,9 @@ __device__ __forceinline__ void fwd2_chunk(const AT& A, int e0, int e_end_v, int
 #pragma unroll
     for (int u = 0; u < UU; ++u) {
         const int j = e0 + u * G + gidx;
-        t[u] = (j < e_end_v) ? t[u] : -INFINITY;
+        bool in = j < e_end_v;
+        if constexpr (DROP) in = in && ek[u];        // a dropped edge: out of the max, Z and the sum
+        t[u] = in ? t[u] : -INFINITY;
         cm = fmaxf(cm, t[u]);
     }
     const float mn = fmaxf(m, cm);
@@ -689,14 +714,15 @@ __global__ __launch_bounds__(256) void edge_fwd2_kernel(FwdArgsT<DROP> A) {
     if (b < e_end) srcv = load_idx(b);               // empty item (zero in-degree row): e_end - 1 would be b - 1, i.e. -1 for row 0
     uint32_t kd = 0;
     int rb = 0;
-    if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; }
+    uint32_t ke = 0;
+    if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; ke = edge_row_key(A.drop, row); }
     for (int e0 = b; e0 < e_end; e0 += CH) {
         const int srcn = (e0 + CH < e_end) ? load_idx(e0 + CH) : 0;
         if constexpr (U >= 2) {
-            if (e_end - e0 <= CH / 2) fwd2_chunk<HD, D, N, U / 2, BF, DROP>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, kd, rb);
-            else fwd2_chunk<HD, D, N, U, BF, DROP>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, kd, rb);
+            if (e_end - e0 <= CH / 2) fwd2_chunk<HD, D, N, U / 2, BF, DROP>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, kd, rb, ke, row);
+            else fwd2_chunk<HD, D, N, U, BF, DROP>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, kd, rb, ke, row);
         } else {
-            fwd2_chunk<HD, D, N, U, BF, DROP>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, kd, rb);
+            fwd2_chunk<HD, D, N, U, BF, DROP>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, kd, rb, ke, row);
         }
         srcv = srcn;
     }
@@ -783,12 +809,18 @@ __global__ __launch_bounds__(256) void edge_fwd3_kernel(FwdArgsT<DROP> A) {
     int srcv = load_idx(0);
     [[maybe_unused]] uint32_t kd = 0;
     [[maybe_unused]] int rb = 0;
-    if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, rowc)); rb = A.row_ptr[rowc]; }
+    [[maybe_unused]] uint32_t ke = 0;
+    if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, rowc)); rb = A.row_ptr[rowc]; ke = edge_row_key(A.drop, rowc); }
     for (int st = 0; st < nst; ++st) {
         const int srcn = load_idx(st + 1);           // next step's indices: in flight during this one
         vnf<N> v[U];
+        [[maybe_unused]] bool ek[U];                 // DropEdge: the edge is kept (lane masks; the hash runs under the gathers' latency)
 #pragma unroll
-        for (int u = 0; u < U; ++u) v[u] = gather_row_n<HD, N, BF>(A.PL, __shfl(srcv, gidx * LPE + u), cp);
+        for (int u = 0; u < U; ++u) {
+            const int src = __shfl(srcv, gidx * LPE + u);
+            v[u] = gather_row_n<HD, N, BF>(A.PL, src, cp);
+            if constexpr (DROP) ek[u] = drop_edge_kept(A.drop, ke, b + st * U + u - rb, src, rowc);
+        }
         float t[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) t[u] = hsum<N>(ac2 * lrelu_n<N>(v[u] + pr, A.slope));
@@ -796,7 +828,9 @@ __global__ __launch_bounds__(256) void edge_fwd3_kernel(FwdArgsT<DROP> A) {
         float cm = -INFINITY;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            t[u] = (b + st * U + u < e) ? t[u] : -INFINITY;
+            bool in = b + st * U + u < e;
+            if constexpr (DROP) in = in && ek[u];    // a dropped edge: out of the max, Z and the sum
+            t[u] = in ? t[u] : -INFINITY;
             cm = fmaxf(cm, t[u]);
         }
         const float mn = fmaxf(m, cm);
@@ -842,7 +876,8 @@ __global__ __launch_bounds__(256) void edge_fwd3_kernel(FwdArgsT<DROP> A) {
 template <int HD, int D, int N, int UU, int DBG, bool BF, bool STASH, bool DROP = false, class AT = EdgeBwdArgs>
 __device__ __forceinline__ void bwd2_chunk(const AT& A, int e0, int e_end, int e_end_v, int cp, int gidx,
                                            int srcv, int posv, vnf<N> g, vnf<N> pr, float dot, vnf<N> ac, vnf<N> acs,
-                                           vnf<N> ac2, float m2, float inv, vnf<N>& ga, vnf<N>& gpr, uint32_t kd = 0, int rb = 0) {
+                                           vnf<N> ac2, float m2, float inv, vnf<N>& ga, vnf<N>& gpr, uint32_t kd = 0, int rb = 0,
+                                           uint32_t ke = 0, int64_t row = 0) {
     constexpr int LPE = HD / N;         // lanes per edge
     constexpr int G = 64 / LPE;         // edges per wave-instruction
     constexpr int DL = D / N;           // lanes per head
@@ -851,9 +886,12 @@ __device__ __forceinline__ void bwd2_chunk(const AT& A, int e0, int e_end, int e
     // srcv / posv: the chunk's <= 16 edge indices, lane k holding edge e0+k (loaded by the caller one chunk ahead,
     // with ONE coalesced load each), handed to the owning lanes through the LDS crossbar: per-lane index loads
     // would put a second memory latency in front of every gather
+    [[maybe_unused]] bool ek[UU];       // DropEdge: the edge is kept
 #pragma unroll
     for (int u = 0; u < UU; ++u) {
-        v[u] = gather_row_n<HD, N, BF>(A.PL, __shfl(srcv, u * G + gidx), cp);
+        const int src = __shfl(srcv, u * G + gidx);
+        v[u] = gather_row_n<HD, N, BF>(A.PL, src, cp);
+        if constexpr (DROP) ek[u] = drop_edge_kept(A.drop, ke, e0 + u * G + gidx - rb, src, row);
         if constexpr (!STASH) sid[u] = __shfl(posv, u * G + gidx);     // STASH: fetched at the store (16 fewer live VGPRs: 4 waves/SIMD)
     }
     constexpr int PMAX = STASH ? 4 : 8;      // slots per compute pass (STASH: 4 keeps the kernel at 128 VGPRs = 4 waves/SIMD)
@@ -884,13 +922,15 @@ __device__ __forceinline__ void bwd2_chunk(const AT& A, int e0, int e_end, int e
         for (int q = 0; q < P; ++q) {
             const int u = p0 + q;
             const int j = e0 + u * G + gidx;
-            const bool valid = j < e_end_v;
+            const bool inr = j < e_end_v;
+            bool valid = inr;
+            if constexpr (DROP) valid = inr && ek[u];                // a dropped edge: ge = alpha = 0 by selection, a zero record / row
             const float ge = valid ? al[q] * (ga_[q] - dot) : 0.f;   // padded slots contribute nothing
             const vnf<N> s = v[u] + pr;
             const vnf<N> gs = ge * select_pos<N>(s, ac, acs);        // ge * a * LReLU'(s)
             ga += ge * lrelu_n<N>(s, A.slope);
             gpr += gs;
-            if constexpr (DROP) al[q] *= kf[q];
+            if constexpr (DROP) al[q] = valid ? al[q] * kf[q] : 0.f;
             if constexpr (STASH) {
                 static_assert(D / N == 2, "stash records: two lanes per head (one carries alpha, the other ge)");
                 uint32_t bits = 0;
@@ -900,11 +940,11 @@ __device__ __forceinline__ void bwd2_chunk(const AT& A, int e0, int e_end, int e
                 const uint32_t word = ((w + (1u << (N - 1))) & ~((1u << N) - 1u)) | bits;
                 // straight-line: padded lanes write the spare record behind the last slot instead of being masked off
                 // (an exec-masked store is a branch, and hipcc drains the memory counters at its join point)
-                const uint32_t slot = valid ? slots[q] : A.stash_spare;
+                const uint32_t slot = inr ? slots[q] : A.stash_spare;
                 if constexpr (DBG != 1) A.stash[(uint64_t)slot * LPE + cp] = word;
             } else {
                 const vnf<N> msg = g * al[q] + gs;                   // d/dPL[src] from this edge
-                if (valid && DBG != 1) store_row_n<HD, N, BF>(A.msg, sid[u], cp, msg);
+                if (inr && DBG != 1) store_row_n<HD, N, BF>(A.msg, sid[u], cp, msg);
             }
         }
     }
@@ -975,15 +1015,16 @@ __device__ __forceinline__ void edge_bwd2_body(const AT& A) {
         if (b < e_end) load_idx(b, srcv, posv);                      // empty item: nothing to prefetch (e_end - 1 < b)
         uint32_t kd = 0;
         int rb = 0;
-        if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; }
+        uint32_t ke = 0;
+        if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; ke = edge_row_key(A.drop, row); }
         for (int e0 = b; e0 < e_end; e0 += CH) {
             int srcn = 0, posn = 0;
             if (e0 + CH < e_end) load_idx(e0 + CH, srcn, posn);      // next chunk's indices: in flight during this one
             if constexpr (U >= 2) {
-                if (e_end - e0 <= CH / 2) bwd2_chunk<HD, D, N, U / 2, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, kd, rb);
-                else bwd2_chunk<HD, D, N, U, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, kd, rb);
+                if (e_end - e0 <= CH / 2) bwd2_chunk<HD, D, N, U / 2, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, kd, rb, ke, row);
+                else bwd2_chunk<HD, D, N, U, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, kd, rb, ke, row);
             } else {
-                bwd2_chunk<HD, D, N, U, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, kd, rb);
+                bwd2_chunk<HD, D, N, U, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, kd, rb, ke, row);
             }
             srcv = srcn; posv = posn;
         }
@@ -1038,7 +1079,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DROP ? 3 : 
     const int64_t nwaves = (int64_t)gridDim.x * 4;
     vnf<N> ga = vzero<N>();
     [[maybe_unused]] uint32_t k1 = 0;
-    if constexpr (DROP) k1 = drop_key(A.drop, kDropAttn);
+    [[maybe_unused]] uint32_t k1e = 0;
+    if constexpr (DROP) { k1 = drop_key(A.drop, kDropAttn); k1e = drop_edge_key(A.drop); }
 
     for (int64_t q = (int64_t)blockIdx.x * 4 + wave; q < nquads; q += nwaves) {
         const int64_t it = q * G + gidx;
@@ -1095,7 +1137,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DROP ? 3 : 
         const float inv = __builtin_amdgcn_rcpf(A.zstat[rowc * H + c / D] + 1e-8f);
         [[maybe_unused]] uint32_t kd = 0;
         [[maybe_unused]] int kb = 0;                 // in-row position of the item's first edge (segments of a split row)
-        if constexpr (DROP) { kd = drop_mix(k1, drop_node(A.drop, rowc)); kb = b - A.row_ptr[rowc]; }
+        [[maybe_unused]] uint32_t ke = 0;
+        if constexpr (DROP) { const uint32_t nd = drop_node(A.drop, rowc); kd = drop_mix(k1, nd); ke = drop_mix(k1e, nd); kb = b - A.row_ptr[rowc]; }
         if (!MSG && row >= 0 && (slot < 0 || b == A.row_ptr[rowc])) {    // one writer per row: whole rows, or a split row's first segment
             if (A.hbits != nullptr) {                                // last layer: the decisions only (g = gh * LReLU'(h_pre) / H is rebuilt by the pull pass)
                 uint32_t nib = 0;
@@ -1145,6 +1188,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DROP ? 3 : 
             vnf<N> v[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) v[u] = gather_row_n<HD, N, BF>(A.PL, src[u], cp);
+            // DropEdge: the step's keep decisions (lane masks), drawn under the gathers' latency and before src[] moves on
+            [[maybe_unused]] bool ek[U];
+            if constexpr (DROP) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) ek[u] = drop_edge_kept(A.drop, ke, kb + st * U + u, src[u], rowc);
+            }
             if constexpr (MSG) {                     // the previous step's message rows (spare row E for padded lanes)
                 if constexpr (DBG != 1) {            // (experiment library, GAT_DBG=1: the walk without its row stores — attribution of the reads)
 #pragma unroll
@@ -1178,19 +1227,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DROP ? 3 : 
             if constexpr (DROP) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    kp[u] = (drop_mix(drop_mix(kd, (uint32_t)(kb + st * U + u)), (uint32_t)(c / D)) >> 8) >= A.drop.T;
+                    kp[u] = ek[u] && (drop_mix(drop_mix(kd, (uint32_t)(kb + st * U + u)), (uint32_t)(c / D)) >> 8) >= A.drop.T;
                     ga_[u] = kp[u] ? ga_[u] * A.drop.scale : 0.f;
                 }
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const bool valid = b + st * U + u < e;
+                bool valid = b + st * U + u < e;
+                if constexpr (DROP) valid = valid && ek[u];              // a dropped edge: ge = alpha = 0 by selection, a zero record / row
                 const float ge = valid ? al[u] * (ga_[u] - dot) : 0.f;   // padded slots contribute nothing
                 const vnf<N> s = v[u] + pr;
                 const vnf<N> gs = ge * select_pos<N>(s, ac, acs);        // ge * a * LReLU'(s)
                 ga += ge * lrelu_n<N>(s, A.slope);
                 gpr += gs;
-                if constexpr (DROP) al[u] = kp[u] ? al[u] * A.drop.scale : 0.f;
+                if constexpr (DROP) al[u] = kp[u] ? al[u] * A.drop.scale : 0.f;   // kp includes the edge's own keep
                 if constexpr (MSG) {
                     pend_m[u] = g * al[u] + gs;                          // d/dPL[src] from this edge (E:859-869)
                 } else {
@@ -1728,13 +1778,20 @@ __global__ __launch_bounds__(64) void edge_fwd_generic(EdgeFwdArgs A, DropArgs d
     const int lane = threadIdx.x;
     const float slope = A.slope;
     const uint32_t k1 = dr.on ? drop_key(dr, kDropAttn) : 0u;
+    const uint32_t k1e = dr.on ? drop_edge_key(dr) : 0u;
     for (int64_t row = blockIdx.x; row < A.n_rows; row += gridDim.x) {
         const int b = A.row_ptr[row], e_end = A.row_ptr[row + 1];
         const uint32_t kd = dr.on ? drop_mix(k1, drop_node(dr, row)) : 0u;
+        const uint32_t ke = dr.on ? drop_mix(k1e, drop_node(dr, row)) : 0u;
         for (int h = lane; h < H; h += 64) {
             float m = -1e9f;
             for (int e = b; e < e_end; ++e) {
                 const int64_t sid = A.col_idx[e];
+                if (dr.on && !drop_edge_kept(dr, ke, e - b, (int)sid, row)) {   // DropEdge: outside the max; parked as -inf, so that
+                    A.alpha[(int64_t)e * H + h] = -INFINITY;                    // the two passes below give exp(-inf - m) = 0 exactly
+                    if (A.score != nullptr) A.score[(int64_t)e * H + h] = 0.f;
+                    continue;
+                }
                 float s = 0.f;
                 for (int k = 0; k < D; ++k) {
                     const int ch = h * D + k;
@@ -1795,9 +1852,11 @@ __global__ __launch_bounds__(64) void edge_bwd_generic(EdgeBwdArgs A, DropArgs d
         return A.g_raw ? gv * (A.hpre[i] > 0.f ? 1.0f : slope) : gv;
     };
     const uint32_t k1 = dr.on ? drop_key(dr, kDropAttn) : 0u;
+    const uint32_t k1e = dr.on ? drop_edge_key(dr) : 0u;
     for (int64_t row = blockIdx.x; row < A.n_rows; row += gridDim.x) {
         const int b = A.row_ptr[row], e_end = A.row_ptr[row + 1];
         const uint32_t kd = dr.on ? drop_mix(k1, drop_node(dr, row)) : 0u;
+        const uint32_t ke = dr.on ? drop_mix(k1e, drop_node(dr, row)) : 0u;
         for (int h = lane; h < H; h += 64) {
             float t = 0.f;
             for (int k = 0; k < D; ++k) t += gval(row * HD + h * D + k) * A.hpre[row * HD + h * D + k];
@@ -1807,6 +1866,13 @@ __global__ __launch_bounds__(64) void edge_bwd_generic(EdgeBwdArgs A, DropArgs d
         __syncthreads();
         for (int e = b; e < e_end; ++e) {
             const int64_t sid = A.col_idx[e];
+            if (dr.on && !drop_edge_kept(dr, ke, e - b, (int)sid, row)) {   // DropEdge (block-uniform): no gradient anywhere, zero taps
+                for (int h = lane; h < H; h += 64) {
+                    if (A.ge != nullptr) A.ge[(int64_t)e * H + h] = 0.f;
+                    if (A.galpha != nullptr) A.galpha[(int64_t)e * H + h] = 0.f;
+                }
+                continue;
+            }
             for (int h = lane; h < H; h += 64) {
                 float t = 0.f;
                 for (int k = 0; k < D; ++k) t += gval(row * HD + h * D + k) * A.PL[sid * HD + h * D + k];
@@ -2028,7 +2094,7 @@ int run_bwd_drop(const EdgeBwdDropArgs& a, hipStream_t s) {
     if (stash && (a.gfull == nullptr || a.pos == nullptr)) return fail(GAT_E_INVALID, "edge_backward: stash path needs gfull and pos");
     const void* fn = a.bf16 ? bwd_variant_drop<HD, D, true>(store, taps, stash) : bwd_variant_drop<HD, D, false>(store, taps, stash);
     if (fn == nullptr)
-        return fail(GAT_E_UNSUPPORTED, "edge_backward: attention dropout needs the store path (not with GAT_BWD_ATOMICS=1 or without the message scratch)");
+        return fail(GAT_E_UNSUPPORTED, "edge_backward: attention dropout / DropEdge need the store path (not with GAT_BWD_ATOMICS=1 or without the message scratch)");
     void* args[] = {const_cast<EdgeBwdDropArgs*>(&a)};
     GAT_HIP(hipLaunchKernel(fn, dim3((unsigned)a.ga_blocks), dim3(256), args, 0, s));
     if (a.n_slots > 0) {

@@ -46,8 +46,11 @@ struct DropArgs {
     float scale = 1.f;                // 1 / (1 - p)
     int32_t layer = 0;
     int32_t on = 0;                   // generic kernels: runtime switch (the wave-per-row kernels take a template flag)
+    uint32_t Te = 0;                  // DropEdge threshold (gatv2_abi.h "DropEdge"): edge kept <=> (r >> 8) >= Te; 0 = every edge kept
+    int32_t eflags = 0;               // GAT_DROPEDGE_* bits
 };
 enum : int32_t { kDropFeat = 0, kDropAttn = 1 };
+constexpr uint32_t kDropEdgeKey = 0x40000000u;   // last word of K_e: never reached by 2*l + kind
 __host__ __device__ __forceinline__ uint32_t drop_fmix32(uint32_t h) {
     h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
     return h;
@@ -61,6 +64,14 @@ __device__ __forceinline__ uint32_t drop_key(const DropArgs& d, int32_t kind) {
     k = drop_mix(k, (uint32_t)(st >> 32));
     return drop_mix(k, (uint32_t)(2 * d.layer + kind));
 }
+// K_e(l) for the step the counter holds: the same chain, last word 0x40000000 + l (l = 0 with GAT_DROPEDGE_SHARED_LAYERS)
+__device__ __forceinline__ uint32_t drop_edge_key(const DropArgs& d) {
+    const uint64_t st = *d.step;
+    uint32_t k = drop_mix(d.seed_lo, d.seed_hi);
+    k = drop_mix(k, (uint32_t)st);
+    k = drop_mix(k, (uint32_t)(st >> 32));
+    return drop_mix(k, kDropEdgeKey + (uint32_t)((d.eflags & GAT_DROPEDGE_SHARED_LAYERS) ? 0 : d.layer));
+}
 // id in the unsharded graph of local row r (padding rows of a shard get some id: their features are zero)
 __device__ __forceinline__ uint32_t drop_node(const DropArgs& d, int64_t r) {
     const int64_t t = d.row0 + r;
@@ -69,6 +80,11 @@ __device__ __forceinline__ uint32_t drop_node(const DropArgs& d, int64_t r) {
 }
 // 0 or 1/(1-p)
 __device__ __forceinline__ float drop_factor(const DropArgs& d, uint32_t r) { return (r >> 8) >= d.T ? d.scale : 0.f; }
+// DropEdge: is edge k (position in its full CSR row) of local row `row` kept?  ke = mix(K_e(l), node(row)); src = its col_idx entry.
+// One draw per edge, shared by all heads.
+__device__ __forceinline__ bool drop_edge_kept(const DropArgs& d, uint32_t ke, int k, int src, int64_t row) {
+    return (drop_mix(ke, (uint32_t)k) >> 8) >= d.Te || ((d.eflags & GAT_DROPEDGE_KEEP_SELF) && (int64_t)src == d.row0 + row);
+}
 
 int launch_drop_advance(uint64_t* step, hipStream_t s);
 // xo[r][f] = x[r][f] * kappa * s_f for f < F, 0 for F <= f < ld (rows of `ld` floats)
@@ -78,6 +94,8 @@ int launch_feat_drop_bwd(float* g, int64_t rows, int32_t F, const DropArgs& d, h
 // taps: out [H][E] = 0 or s_a per (head, CSR edge); out [rows][F] = 0 or s_f
 int launch_attn_keep_tap(const int32_t* row_ptr, int64_t n_rows, int64_t n_edges, int32_t H, const DropArgs& d, float* out, hipStream_t s);
 int launch_feat_keep_tap(int64_t rows, int32_t F, const DropArgs& d, float* out, hipStream_t s);
+// out [E] = 0 or 1 per CSR edge (DropEdge)
+int launch_edge_keep_tap(const int32_t* row_ptr, const int32_t* col_idx, int64_t n_rows, int64_t n_edges, const DropArgs& d, float* out, hipStream_t s);
 
 // ---- edge-centric kernels (gat_edge_kernels.hip) ------------------------------------------------
 struct EdgeFwdArgs {

@@ -21,6 +21,9 @@
 // --dropout P / --attn-dropout P (default 0): inverted dropout on every layer's input features / on the attention
 // coefficients during training (gatv2_abi.h "dropout"), masks keyed by --seed.  With --val-mask the validation line
 // then comes from an eval-mode forward (no dropout) after the optimizer step.  Both 0: the output is the reference's.
+// --drop-edge P (default 0): DropEdge (gatv2_abi.h "DropEdge"): every training step drops each edge with probability P BEFORE the
+// softmax, masks keyed by --seed; --drop-edge-keep-self never drops self-loops, --drop-edge-shared draws one mask per step for all
+// layers.  Validation (--val-mask) then comes from an eval-mode forward, as with dropout.
 // --add-self-loops / --undirected / --coalesce: the graph is rebuilt on the device before training (gat_graph_from_coo:
 // GAT_GRAPH_SELF_LOOPS / SYMMETRIZE / COALESCE, applied in that order); a CSR dataset is expanded to an edge list first.
 // Edge-list dataset: a folder with edges.txt (one "src dst" pair per line, a message flows src -> dst) instead of
@@ -74,6 +77,7 @@ struct Options {
     std::string dtype = "f32";
     std::string train_mask, val_mask;     // text files of N 0/1 values (beyond the reference: README R:134 "later")
     float dropout = 0.f, attn_dropout = 0.f;
+    float drop_edge = 0.f; int drop_edge_flags = 0;   // GAT_DROPEDGE_*: --drop-edge-keep-self, --drop-edge-shared
     int graph_flags = 0;                  // GAT_GRAPH_*: --add-self-loops, --undirected, --coalesce
 };
 
@@ -91,6 +95,8 @@ const char* kUsage =
     "            (applied in this order, on the device, before training; with --ranks to the whole graph)\n"
     "  additive: --seed N --load-params FILE --dump-params FILE --device N --cache --dtype f32|bf16\n"
     "            --train-mask FILE --val-mask FILE --dropout P --attn-dropout P\n"
+    "            --drop-edge P [--drop-edge-keep-self] [--drop-edge-shared]   DropEdge: each training step drops every edge with\n"
+    "                          probability P before the softmax (never a self-loop / one mask for all layers instead of one per layer)\n"
     "            --ranks P [--transport rccl|host] [--halo 0|1|2]\n";
 
 struct RankEnv {                      // one forked process per GPU
@@ -168,6 +174,9 @@ Options parse_args(int argc, char** argv) {
             if (o.halo < 0 || o.halo > 2) die("Invalid halo choice. Use 0, 1 or 2\n");
         } else if (a == "--dropout" && has_val) o.dropout = std::strtof(argv[++i], nullptr);
         else if (a == "--attn-dropout" && has_val) o.attn_dropout = std::strtof(argv[++i], nullptr);
+        else if (a == "--drop-edge" && has_val) o.drop_edge = std::strtof(argv[++i], nullptr);
+        else if (a == "--drop-edge-keep-self") o.drop_edge_flags |= GAT_DROPEDGE_KEEP_SELF;
+        else if (a == "--drop-edge-shared") o.drop_edge_flags |= GAT_DROPEDGE_SHARED_LAYERS;
         else if (a == "--transport" && has_val) {
             o.transport = argv[++i];
             if (o.transport != "rccl" && o.transport != "host") die("Invalid transport choice. Use 'rccl' or 'host'\n");
@@ -519,8 +528,9 @@ int run(const Options& o, const RankEnv& env) {
         if (env.world != 1) die("Error: --val-mask needs --ranks 1\n");
         load_mask(o.val_mask, val_m, "val mask");
     }
-    const bool dropout = o.dropout > 0.f || o.attn_dropout > 0.f;
-    if (dropout) check(gat_set_dropout(ctx, o.dropout, o.attn_dropout, o.seed, 0), "gat_set_dropout");
+    const bool dropout = o.dropout > 0.f || o.attn_dropout > 0.f || o.drop_edge > 0.f;
+    if (dropout) check(gat_set_dropout(ctx, o.dropout, o.attn_dropout, o.seed, 0), "gat_set_dropout");   // also seeds DropEdge
+    if (o.drop_edge > 0.f) check(gat_set_dropedge(ctx, o.drop_edge, o.drop_edge_flags), "gat_set_dropedge");
     check(gat_params_init(ctx, o.seed), "xavier_init_kernel");
     if (!o.load_params.empty()) {
         std::vector<float> p(nW + nA + nWo);
@@ -586,10 +596,10 @@ int main(int argc, char** argv) {
     bool multi = false;                                    // --ranks P > 1: see print_memory_tracker_before
     for (int i = 1; i + 1 < argc; ++i)
         if (std::string(argv[i]) == "--ranks" && std::atoi(argv[i + 1]) > 1) multi = true;
-    // dropout probabilities are checked before anything touches the GPU (NaN and trailing garbage included)
+    // dropout / DropEdge probabilities are checked before anything touches the GPU (NaN and trailing garbage included)
     for (int i = 1; i + 1 < argc; ++i) {
         const std::string a = argv[i];
-        if (a != "--dropout" && a != "--attn-dropout") continue;
+        if (a != "--dropout" && a != "--attn-dropout" && a != "--drop-edge") continue;
         char* end = nullptr;
         const float p = std::strtof(argv[i + 1], &end);
         if (end == argv[i + 1] || *end != '\0' || !(p >= 0.f && p < 1.f)) die("Error: " + a + " must be in [0, 1)\n");

@@ -245,7 +245,8 @@ class ShardedGat:
     ``tables`` maps (which, layer) -> flat torch tensor bound to the context."""
 
     def __init__(self, ctx, plan: ShardPlan, comm, heads: Sequence[int], outdims: Sequence[int],
-                 alloc: Callable[[int], "object"], halo: bool = False, dropout: Optional[Sequence[float]] = None):
+                 alloc: Callable[[int], "object"], halo: bool = False, dropout: Optional[Sequence[float]] = None,
+                 dropedge: Optional[Sequence] = None):
         self.ctx, self.plan, self.comm = ctx, plan, comm
         # dropout masks are drawn per unsharded node id: every rank gets the plan's bounds, so that the masks (and the
         # results) equal a single GPU's.  dropout = (feat_p, attn_p, seed[, first_step]), or None: the context's setting stays
@@ -253,6 +254,10 @@ class ShardedGat:
             ctx.set_shard_bounds(plan.bounds)
         if dropout is not None:
             ctx.set_dropout(*dropout)
+        # DropEdge = (p[, keep_self[, shared_layers]]): destination-range shards own whole rows and the mask is keyed by the
+        # unsharded node id and the position in the row, so every rank draws the single-GPU masks of its rows
+        if dropedge is not None:
+            ctx.set_dropedge(*dropedge)
         self.halo = bool(halo)                         # comm.halo_setup(plan, col_idx_local) must have run (collective)
         self.hd = [int(h) * int(d) for h, d in zip(heads, outdims)]
         self.L = len(self.hd)

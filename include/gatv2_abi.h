@@ -296,7 +296,11 @@ enum {
                                                       (with feature dropout: wrt the undropped x_l, i.e. incl. kappa*s_f) */
     GAT_TAP_ATTN_KEEP = 15, /* [H][E]                attention-dropout factor kappa*s_a (0 or s_a) of layer l for the step the
                                                       counter holds (after a training forward: the masks that forward used) */
-    GAT_TAP_FEAT_KEEP = 16  /* [N][F_l]              feature-dropout factor kappa*s_f (0 or s_f) of layer l's input, likewise */
+    GAT_TAP_FEAT_KEEP = 16, /* [N][F_l]              feature-dropout factor kappa*s_f (0 or s_f) of layer l's input, likewise */
+    GAT_TAP_EDGE_KEEP = 17  /* [E]                   DropEdge: 1 = CSR edge kept, 0 = dropped, for layer l and the step the counter
+                                                      holds, likewise (all 1 at edge_p = 0; needs gat_set_dropedge or gat_set_dropout).  Like the two
+                                                      taps above it reports the mask of the SETTING, whatever the mode: in eval mode the passes drop
+                                                      nothing, the tap still shows what a training forward at that counter value draws */
 };
 int gat_tap(gat_ctx* ctx, int tensor, int32_t layer, void* host_dst, int64_t count);
 
@@ -310,7 +314,8 @@ int gat_tap(gat_ctx* ctx, int tensor, int32_t layer, void* host_dst, int64_t cou
  *     so the source-major pass is unchanged.
  *   Features, p_f, the input of every layer (layer 0 included): x'_l = x_l (.) kappa*s_f.  Both projections read x'_l and
  *     grad_W is formed from x'_l; the gradient passed to x_l is gx' (.) kappa*s_f, before the LReLU' factor of the layer below.
- *   The output head (W_o) has no dropout.  DropEdge (dropping edges before the softmax) is a different regulariser, not this.
+ *   The output head (W_o) has no dropout.  DropEdge (dropping edges before the softmax) is a different regulariser, not this:
+ *   see "DropEdge" below.
  * Masks are stateless and counter-based (no mask is stored; the backward recomputes the forward's).  uint32 arithmetic, wrapping:
  *   fmix32(h): h ^= h>>16; h *= 0x85EBCA6B; h ^= h>>13; h *= 0xC2B2AE35; h ^= h>>16
  *   mix(k, v)  = fmix32(k ^ (v * 0x9E3779B9 + 0x7F4A7C15))
@@ -341,6 +346,45 @@ int gat_dropout_step(gat_ctx* ctx, uint64_t* step);             /* the counter's
 /* Shard bounds [world+1] (global row boundaries, bounds[0] = 0): node ids of the table rows for the masks.  Checked against
  * n_table (= world slices of max_rows), table_row0 and n_rows; call after the graph is set. */
 int gat_set_shard_bounds(gat_ctx* ctx, int32_t world, const int64_t* bounds);
+
+/* ---- DropEdge (Rong et al., ICLR 2020; beyond the reference): whole edges leave the neighbourhood, per step ------------------
+ * Training mode only.  For layer l every CSR edge j of destination row dst is kept or dropped AS A WHOLE (all heads at once).
+ * A dropped edge takes no part in the row's max, in Z, in alpha, in the aggregation or in any gradient: its alpha is exactly 0,
+ * and it sends nothing to PL[src], to PR[dst] or to a.  The surviving edges renormalise among themselves (attention dropout
+ * zeroes a term AFTER the softmax and leaves alpha alone; an attention mask cannot emulate this, because Z would keep the
+ * dropped terms).  No rescaling: the softmax over the survivors normalises itself.  A row whose edges are all dropped is, for
+ * that step, a zero in-degree row: max = -1e9f, sum = 0, h_pre = 0 (E:336).  In other words the layer computes exactly what it
+ * computes on the CSR with the dropped edges removed.
+ * Composes with feature dropout (unchanged) and with attention dropout, which still keys its draw by the edge's position k in
+ * the FULL CSR row (its masks do not depend on edge_p).
+ * Mask: the hash of the dropout section, bit for bit.  With base = mix(mix(mix(lo32(seed), hi32(seed)), lo32(step)), hi32(step))
+ * (the chain K(kind, l) starts with):
+ *   K_e(l) = mix(base, 0x40000000 + l')     l' = l, or 0 for every layer with GAT_DROPEDGE_SHARED_LAYERS
+ *   r      = mix(mix(K_e(l), node(dst)), k)  k = j - row_ptr[dst] (position in the whole row, also when a hub row is processed as
+ *                                            256-edge segments); node(.) as for dropout (shard bounds respected)
+ *   keep <=> (r >> 8) >= T(edge_p)           T(p) = min(2^24, floor(p * 2^24 + 0.5)), as for dropout
+ * 2*l + kind never reaches 0x40000000 (l < 2^29), so K_e cannot collide with a feature or attention key.  One draw per edge,
+ * not per head.  Destination-range shards own whole rows, so every rank draws the masks of a single GPU.
+ *   GAT_DROPEDGE_KEEP_SELF      an edge whose col_idx equals table_row0 + row (a self-loop) is never dropped: with a self-looped
+ *                               graph no row can go empty.  (The draw is still made; only its outcome is overridden.)
+ *   GAT_DROPEDGE_SHARED_LAYERS  one mask per step for all layers (the DropEdge paper's default); without it the layers draw
+ *                               independently.
+ * edge_p in [0, 1), else GAT_E_INVALID (NaN included); unknown flag bits: GAT_E_INVALID.  Allowed before the graph is set.  Seed
+ * and step counter are those of gat_set_dropout (call it with both p = 0 to seed only; without it the seed is 0 and the counter
+ * starts at 0); gat_set_dropedge does not touch the counter.  With edge_p > 0 a training forward advances the counter exactly as
+ * dropout does (same one-lane kernel, same place, part of a captured graph) — ONCE per forward, whichever of the three
+ * regularisers are on.  Eval mode (gat_set_training(ctx, 0)) drops nothing and advances nothing.
+ * edge_p = 0 (the default, also when set explicitly) runs exactly the kernels a context without DropEdge runs.  Otherwise the
+ * edge passes run their DROP instantiations (the same ones attention dropout selects), with their rules: the A/B switches of the
+ * default path do not apply, GAT_BWD_ATOMICS=1 gives GAT_E_UNSUPPORTED at the backward, and so does the experiment library with
+ * GAT_DBG set.  In the backward a dropped edge leaves an all-zero record / message row in its source-major slot, so the
+ * source-major passes (list, slot-parallel, halo) are unchanged.
+ * Taps (keep_taps = 1): GAT_TAP_ALPHA, GAT_TAP_GE and GAT_TAP_GALPHA are exactly 0 at dropped edges; GAT_TAP_SCORE may hold
+ * anything there.  GAT_TAP_MAX / GAT_TAP_SUM are those of the surviving edges.
+ * gat_algorithmic_bytes* keep pricing the FULL graph (every edge's index is read, every slot is written; the gathers a dropped
+ * edge would not need are not subtracted). */
+enum { GAT_DROPEDGE_KEEP_SELF = 1, GAT_DROPEDGE_SHARED_LAYERS = 2 };
+int gat_set_dropedge(gat_ctx* ctx, float edge_p, int32_t flags);
 
 /* ---- op-level entry points, whole layers: caller-provided DEVICE pointers in the reference layouts
  *      (unit parity).  `stream` may be NULL (default stream).  One entry point per reference KERNEL: below. ---- */

@@ -1,0 +1,146 @@
+"""DropEdge without a GPU: the edge mask of include/gatv2_abi.h ("DropEdge") restated in numpy, the new ABI symbols, the
+reduced-graph model, and the train_edge flag's argument errors."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import dropedge_ref as E
+import dropout_ref as R
+from conftest import small_graph
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "graph-attention-network-gatv2-_amd", "train_edge")
+
+
+def test_symbols_declared_and_exported(pkg):
+    A = pkg.abi
+    assert "gat_set_dropedge" in A.declared_symbols()
+    assert hasattr(ctypes.CDLL(A.LIB_PATH), "gat_set_dropedge")
+    assert A.TAP_EDGE_KEEP == 17
+    assert (A.DROPEDGE_KEEP_SELF, A.DROPEDGE_SHARED_LAYERS) == (1, 2)
+    assert A.load_library().gat_abi_version() == 6
+    hdr = open(os.path.join(ROOT, "include", "gatv2_abi.h")).read()
+    assert "GAT_TAP_EDGE_KEEP = 17" in hdr and "GAT_DROPEDGE_KEEP_SELF = 1, GAT_DROPEDGE_SHARED_LAYERS = 2" in hdr
+    assert hasattr(pkg.GatContext, "set_dropedge")
+
+
+@pytest.mark.parametrize("p", [0.1, 0.5, 0.9])
+def test_keep_rate_within_5_sigma(p):
+    n = 1_000_000
+    rp = np.arange(0, n + 1, 100)                            # 10,000 rows of 100 edges
+    keep = E.edge_keep(11, 3, 0, rp, np.zeros(n, np.int32), p)
+    want = 1.0 - R.threshold(p) / 2.0 ** 24
+    sigma = np.sqrt(want * (1 - want) / n)
+    assert abs(keep.mean() - want) < 5 * sigma, (keep.mean(), want, sigma)
+
+
+def test_mask_differs_across_seed_step_layer_and_is_shared_on_request():
+    rp = np.array([0, 40, 90, 200], np.int64)
+    ci = np.zeros(200, np.int32)
+    base = E.edge_keep(1, 0, 0, rp, ci, 0.5)
+    assert not np.array_equal(base, E.edge_keep(2, 0, 0, rp, ci, 0.5))             # seed
+    assert not np.array_equal(base, E.edge_keep(1 + (1 << 32), 0, 0, rp, ci, 0.5))  # its high word
+    assert not np.array_equal(base, E.edge_keep(1, 1, 0, rp, ci, 0.5))             # step
+    assert not np.array_equal(base, E.edge_keep(1, 1 << 32, 0, rp, ci, 0.5))
+    assert not np.array_equal(base, E.edge_keep(1, 0, 1, rp, ci, 0.5))             # layer
+    sh = [E.edge_keep(1, 0, l, rp, ci, 0.5, shared=True) for l in range(3)]
+    assert np.array_equal(sh[0], sh[1]) and np.array_equal(sh[0], sh[2])
+    assert np.array_equal(sh[0], base)                       # shared = layer 0's key
+    assert E.edge_keep(1, 0, 0, rp, ci, 0.0).all()           # p = 0 keeps everything
+
+
+def test_key_differs_from_the_dropout_keys():
+    for seed, step in ((0, 0), (5, 7), (1 << 40, 1 << 33)):
+        for l in range(64):
+            ke = int(E.edge_key(seed, step, l))
+            assert ke != int(R.key(seed, step, l, 0)) and ke != int(R.key(seed, step, l, 1))
+    # the last word of the chain is out of the range 2*l + kind can reach
+    assert E.EDGE_KEY == 0x40000000 and 2 * 63 + 1 < E.EDGE_KEY
+    # and the edge draw is not the attention draw of any head's predecessor
+    rp = np.array([0, 500], np.int64)
+    assert not np.array_equal(E.edge_keep(3, 1, 0, rp, np.zeros(500, np.int32), 0.5), R.attn_factor(3, 1, 0, rp, 1, 0.5)[0] != 0)
+
+
+def test_shard_slice_equals_the_rows_of_the_whole_mask():
+    rng = np.random.default_rng(0)
+    n = 50
+    rp, ci = small_graph(rng, n, 700)
+    ci = ci.copy()
+    ci[rp[:-1][np.diff(rp) > 0]] = np.arange(n)[np.diff(rp) > 0]      # a self-loop first in every non-empty row
+    for keep_self in (False, True):
+        whole = E.edge_keep(5, 2, 1, rp, ci, 0.6, keep_self=keep_self)
+        lo, hi = 17, 41
+        # a destination-range shard: local rows 0..hi-lo, col_idx holds table rows; here the table is the unsharded graph
+        # shifted so that local row 0 sits at table row table_row0
+        t0 = 64
+        part = E.edge_keep(5, 2, 1, rp[lo:hi + 1] - rp[lo], ci[rp[lo]:rp[hi]] - lo + t0, 0.6, keep_self=keep_self,
+                           nodes=np.arange(lo, hi), table_row0=t0)
+        assert np.array_equal(part, whole[rp[lo]:rp[hi]])
+
+
+def test_keep_self_leaves_no_row_empty():
+    rng = np.random.default_rng(1)
+    n = 400
+    rp0, ci0 = small_graph(rng, n, 3000, empty=(3,))
+    # add one self-loop per row
+    rows = np.repeat(np.arange(n), np.diff(rp0))
+    src = np.concatenate([ci0, np.arange(n, dtype=np.int32)])
+    dst = np.concatenate([rows, np.arange(n)])
+    order = np.lexsort((src, dst))
+    ci = src[order].astype(np.int32)
+    rp = np.zeros(n + 1, np.int32)
+    rp[1:] = np.cumsum(np.bincount(dst, minlength=n))
+    keep = E.edge_keep(9, 1, 0, rp, ci, 0.9, keep_self=True)
+    rr, _ = E.reduce_graph(rp, ci, keep)
+    assert (np.diff(rr) >= 1).all()
+    # without the flag rows do go empty at p = 0.9
+    rr2, _ = E.reduce_graph(rp, ci, E.edge_keep(9, 1, 0, rp, ci, 0.9))
+    assert (np.diff(rr2) == 0).any()
+    assert keep.mean() < 0.25                                # the flag spares the self-loops only
+
+
+def test_reduce_graph():
+    rp = np.array([0, 3, 3, 5], np.int32)
+    ci = np.array([4, 5, 6, 7, 8], np.int32)
+    r, c = E.reduce_graph(rp, ci, np.array([1, 0, 1, 0, 0], bool))
+    assert r.tolist() == [0, 2, 2, 2] and c.tolist() == [4, 6]
+    r, c = E.reduce_graph(rp, ci, np.ones(5, bool))
+    assert r.tolist() == rp.tolist() and c.tolist() == ci.tolist()
+
+
+def test_layered_model_equals_the_reduced_graph_model(orc):
+    """forward_layers with one mask for all layers is dropout_ref.forward on the reduced graph."""
+    rng = np.random.default_rng(2)
+    n, F, C = 60, 12, 4
+    rp, ci = small_graph(rng, n, 400, empty=(3,))
+    x = rng.standard_normal((n, F)).astype(np.float32)
+    lab = rng.integers(0, C, n).astype(np.int32)
+    cfg = orc.Config([2, 2], [4, 4], F, C)
+    P = orc.xavier_params(cfg, 1)
+    keep = E.edge_keep(4, 1, 0, rp, ci, 0.4, shared=True)
+    attn = [R.attn_factor(4, 1, l, rp, 2, 0.3) for l in range(2)]
+    a = E.forward(cfg, rp, ci, lab, x, *P, keep=keep, attn=attn)
+    b = E.forward_layers(cfg, rp, ci, lab, x, *P, keeps=[keep, keep], attn=attn)
+    assert abs(a["loss"].item() - b["loss"].item()) < 1e-12 * abs(a["loss"].item())
+    for u, v in zip(a["hpre"], b["hpre"]):
+        assert np.allclose(u.detach().numpy(), v.detach().numpy(), rtol=0, atol=1e-13)
+
+
+@pytest.mark.parametrize("value", ["1.0", "-0.1", "nan", "x", "0.5x"])
+def test_train_edge_refuses_bad_drop_edge(value):
+    e = dict(os.environ)
+    e.pop("DATA_ROOT", None)
+    r = subprocess.run([BIN, "--heads", "8,8", "--outdims", "8,8", "--drop-edge", value], capture_output=True, text=True, env=e, timeout=120)
+    assert r.returncode == 1
+    assert r.stderr.endswith("Error: --drop-edge must be in [0, 1)\n"), r.stderr
+    assert "[Memory Tracker]" not in r.stdout                # refused before anything touches the GPU
+
+
+def test_train_edge_help_names_the_flags():
+    r = subprocess.run([BIN, "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0
+    for f in ("--drop-edge P", "--drop-edge-keep-self", "--drop-edge-shared"):
+        assert f in r.stdout
