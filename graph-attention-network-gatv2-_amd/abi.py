@@ -390,6 +390,11 @@ class GatContext:
         _chk(self.lib.gat_grads_get(self._ctx, group, _np_ptr(a), a.size))
         return a
 
+    def grads_set(self, group: int, arr):
+        """Overwrite one group of the gradient buffer (clip / optimizer without a model run)."""
+        a = np.ascontiguousarray(arr, np.float32).reshape(-1)
+        _chk(self.lib.gat_grads_set(self._ctx, group, _np_ptr(a), a.size))
+
     def grads_device(self):
         p, n = C.c_void_p(), C.c_int64()
         _chk(self.lib.gat_grads_device(self._ctx, C.byref(p), C.byref(n)))
