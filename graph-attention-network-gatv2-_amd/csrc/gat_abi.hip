@@ -447,7 +447,7 @@ static int ensure_buffers(gat_ctx* c) {
     }
     // one region per layer (grad_a block partials, grad_w slabs): their reductions are queued until the end of the
     // backward and run as one launch (reduce_batch_flush), so a later layer must not overwrite an earlier layer's slabs
-    GAT_TRY(dalloc(c, &c->ga_partial, (int64_t)L * 2048 * c->HDmax));  // per layer >= any edge_backward_blocks()
+    GAT_TRY(dalloc(c, &c->ga_partial, (int64_t)L * kGaPartialRows * c->HDmax));  // per layer >= any edge_backward_blocks()
     int64_t gw = 0;
     c->gw_off.assign((size_t)L, 0);
     for (int l = 0; l < L; ++l) { c->gw_off[(size_t)l] = gw; gw += grad_w_scratch_floats(N, c->layers[l].F, c->layers[l].HD); }
@@ -1024,11 +1024,10 @@ static int plan_backward_edges(gat_ctx* c, int32_t l, BwdPlan* P) {
     a.items = c->items; a.n_items = c->work.n_items; a.slot_info = c->slot_info; a.n_slots = c->work.n_slots; a.n_split = c->work.n_split;
     a.part_acc = c->part_acc;
     a.dbg = c->dbg;
-    a.ga_partial = c->ga_partial + (int64_t)l * 2048 * c->HDmax; a.n_rows = c->n_rows; a.n_table = c->n_table; a.bf16 = bf16(c); a.H = y.H; a.D = y.D;
-    P->drop = attn_drop_args(c, l);
-    a.ga_blocks = edge_fast_path(y.H, y.D, c->n_table) ? edge_backward_blocks(c->work.n_items, y.H, y.D, store, y.ge != nullptr, bf16(c), stash, P->drop.on != 0)
-                                           : edge_backward_blocks(c->n_rows * 4, y.H, y.D, false, false, false);
+    a.ga_partial = c->ga_partial + (int64_t)l * kGaPartialRows * c->HDmax; a.n_rows = c->n_rows; a.n_table = c->n_table; a.bf16 = bf16(c); a.H = y.H; a.D = y.D;
     a.slope = c->cfg.negative_slope;
+    P->drop = attn_drop_args(c, l);
+    a.ga_blocks = edge_backward_blocks(a, &P->drop);
     P->a = a; P->store = store; P->stash = stash; P->last_g = last_g;
     return 0;
 }
@@ -1215,7 +1214,7 @@ static int last_layer_fused(gat_ctx* c) {
     GAT_TRY(plan_backward_edges(c, l, &P));
     const EdgeFwdArgs f = plan_forward_edges(c, l);
     const int32_t n_seg = c->work.n_slots;          // the segments of split rows come first in the work list
-    float* ga_a = P.a.ga_partial;                   // this layer's region (2048 rows): the segments' launch, then the fused one,
+    float* ga_a = P.a.ga_partial;                   // this layer's region (kGaPartialRows rows): the segments' launch, then the fused one,
     int blocks_a = 0;                               // back to back — ONE reduction job (two jobs into one output would race)
     if (n_seg > 0) {                                // split rows: forward segments + fix-up, their gH, backward segments + fix-up
         EdgeFwdArgs fs = f;
@@ -1232,14 +1231,14 @@ static int last_layer_fused(gat_ctx* c) {
         EdgeBwdArgs bs = P.a;
         bs.n_items = n_seg;
         bs.ga_partial = ga_a;
-        bs.ga_blocks = blocks_a = std::min(1024, edge_backward_blocks(n_seg, y.H, y.D, P.store, false, false, P.stash));
+        bs.ga_blocks = blocks_a = std::min(kGaPartialRows / 2, edge_backward_blocks(bs));
         Scope t(c, GAT_K_EDGE_BWD);
         GAT_TRY(launch_edge_backward(bs, c->stream));
     }
     EdgeLastArgs a{};
     a.f = f; a.f.items = c->items + n_seg; a.f.n_items = c->work.n_items - n_seg;
     float* ga_b = ga_a + (int64_t)blocks_a * y.HD;
-    a.b = P.a; a.b.ga_partial = ga_b; a.b.ga_blocks = a.f.n_items > 0 ? std::min(edge_last_fused_blocks(a.f.n_items), 2048 - blocks_a) : 0;    // the layer's region holds 2048 partial rows
+    a.b = P.a; a.b.ga_partial = ga_b; a.b.ga_blocks = a.f.n_items > 0 ? std::min(edge_last_fused_blocks(a.f.n_items), kGaPartialRows - blocks_a) : 0;    // what is left of the layer's region
     a.Wo = Wo_of(c); a.labels = c->labels_eff ? c->labels_eff : c->labels; a.gh_out = c->gH; a.C = c->cfg.num_classes;
     {
         Scope t(c, GAT_K_EDGE_FUSED);
@@ -1887,9 +1886,8 @@ int gat_op_layer_backward(const int32_t* d_row_ptr, const int32_t* d_col_idx, co
         d_col_idx = reinterpret_cast<const int32_t*>(dummy);
     }
     float *PL, *PR, *alpha, *gPL, *gPR, *gap, *scr;
-    const int blocks = 2048;      // capacity; the grid actually used is computed below
     GAT_TRY(t.get(&PL, n * HD)); GAT_TRY(t.get(&PR, n * HD)); GAT_TRY(t.get(&alpha, e * h));
-    GAT_TRY(t.get(&gPL, n * HD)); GAT_TRY(t.get(&gPR, n * HD)); GAT_TRY(t.get(&gap, (int64_t)blocks * HD));
+    GAT_TRY(t.get(&gPL, n * HD)); GAT_TRY(t.get(&gPR, n * HD)); GAT_TRY(t.get(&gap, (int64_t)kGaPartialRows * HD));    // capacity: >= any edge_backward_blocks()
     GAT_TRY(t.get(&scr, grad_w_scratch_floats(n, f, HD)));
     GAT_TRY(launch_project(d_x, d_w, PL, PR, n, f, HD, kPartBoth, false, nullptr, 0, s));
     GAT_TRY(launch_transpose_he_to_eh(d_attn_coeff, alpha, e, h, s));
@@ -1912,11 +1910,10 @@ int gat_op_layer_backward(const int32_t* d_row_ptr, const int32_t* d_col_idx, co
     a.mstat = ms; a.zstat = zs;
     a.row_ptr = d_row_ptr; a.col_idx = d_col_idx; a.PL = PL; a.PR = PR; a.a = d_a; a.alpha = alpha;
     a.hpre = d_hpre; a.g = d_g; a.gPL = gPL; a.gPR = gPR; a.ge = nullptr; a.ga_partial = gap;
-    a.ga_blocks = edge_fast_path(h, d, n) ? edge_backward_blocks(t.w.n_items, h, d, false, false, false)
-                                       : edge_backward_blocks(n * 4, h, d, false, false, false);
     a.n_rows = n; a.n_table = n; a.H = h; a.D = d; a.slope = slope;
     a.items = t.items; a.n_items = t.w.n_items; a.slot_info = t.slot_info; a.n_slots = t.w.n_slots; a.n_split = t.w.n_split;
     a.part_acc = t.part_acc;
+    a.ga_blocks = edge_backward_blocks(a);
     GAT_TRY(launch_edge_backward(a, s));
     GAT_TRY(launch_reduce_partials_add(gap, a.ga_blocks, HD, d_grad_a, s));
     GAT_TRY(launch_grad_w(gPL, gPR, d_x, d_grad_w, scr, n, f, HD, kPartBoth, s));

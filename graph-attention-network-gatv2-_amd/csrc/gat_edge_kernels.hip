@@ -25,8 +25,10 @@
 // inside windows of 4,096 rows.
 #include "gat_internal.h"
 
+#include <algorithm>
 #include <map>
 #include <mutex>
+#include <utility>
 
 namespace gat {
 namespace {
@@ -1915,14 +1917,30 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
     }
 }
 
+// ---- host side: which kernel runs -----------------------------------------------------------------------------------
+// The (H*D, D) shapes the wave-per-row kernels are instantiated for; any other shape runs the generic kernels.  This one
+// list feeds edge_fast_path(), edge_stash_words() and the switch that enters the templates (GAT_DISPATCH_HD_D below).
+#define GAT_EDGE_SHAPES(X, ...)                                                                                          \
+    X(64, 8, __VA_ARGS__) X(64, 4, __VA_ARGS__) X(64, 16, __VA_ARGS__) X(64, 32, __VA_ARGS__) X(64, 64, __VA_ARGS__)    \
+    X(32, 8, __VA_ARGS__) X(32, 4, __VA_ARGS__) X(32, 16, __VA_ARGS__) X(32, 32, __VA_ARGS__)                           \
+    X(16, 4, __VA_ARGS__) X(16, 8, __VA_ARGS__) X(16, 16, __VA_ARGS__) X(8, 4, __VA_ARGS__) X(8, 8, __VA_ARGS__)
+#define GAT_SHAPE_ENTRY(hd, d, ...) {hd, d},
+constexpr struct { int HD, D; } kEdgeShapes[] = {GAT_EDGE_SHAPES(GAT_SHAPE_ENTRY)};
+static_assert(sizeof(kEdgeShapes) / sizeof(kEdgeShapes[0]) == 14, "the wave-per-row kernels cover 14 shapes");
+static bool edge_shape_listed(int HD, int D) {
+    for (const auto& sh : kEdgeShapes) if (sh.HD == HD && sh.D == D) return true;
+    return false;
+}
 // channels per lane of the two-lanes-per-head kernels (stash backward, group-per-row kernels) for this shape, 0 = none
-template <int HD, int D> constexpr int stash_n() { return (D == 8 && HD >= 32) ? 4 : (D == 4 ? 2 : 0); }
+constexpr int stash_n(int HD, int D) { return (D == 8 && HD >= 32) ? 4 : (D == 4 ? 2 : 0); }
+template <int HD, int D> constexpr int stash_n() { return stash_n(HD, D); }
+
 // GAT_ROWGROUP=0: one wave per row (chunked kernels) instead of one lane group per row (A/B)
 static bool row_groups() {
     static const bool v = [] { const char* e = choice_env("GAT_ROWGROUP"); return !(e && e[0] == '0'); }();
     return v;
 }
-// GAT_PACKED=0 keeps the one-channel-per-lane kernels on the training path too (A/B)
+// GAT_PACKED=0 keeps the one-channel-per-lane kernels on the training path too (A/B), forward and backward
 static bool packed_layout() {
     static const bool v = [] { const char* e = choice_env("GAT_PACKED"); return !(e && e[0] == '0'); }();
     return v;
@@ -1932,283 +1950,176 @@ static int lane_channels() {
     static const int v = [] { const char* e = choice_env("GAT_CPL"); return (e && e[0] == '2') ? 2 : 4; }();
     return v;
 }
-
-// Attention dropout (a.drop.on): the DROP instantiation of the kernel the default settings pick — the group-per-row kernel where
-// the shape has one, else the packed wave-per-row kernel; the parity-tap form with alpha.  The A/B switches of the default path
-// (GAT_ROWGROUP, GAT_PACKED, GAT_CPL, GAT_FWD_WAVES, GAT_GROUP_MSG) do not apply: only these instantiations exist.
-template <int HD, int D>
-int run_fwd_drop(const EdgeFwdDropArgs& a, hipStream_t s) {
-    if (a.items == nullptr) return fail(GAT_E_INVALID, "edge_forward: work-item list missing");
-    if (a.mstat == nullptr || a.zstat == nullptr) return fail(GAT_E_INVALID, "edge_forward: stats buffers missing");
-    const EdgeFwdArgs& p = a;                        // what the fix-up kernel takes
-    const dim3 block(256);
-    const dim3 fgrid((unsigned)(((a.alpha != nullptr ? a.n_slots : a.n_split) + 3) / 4));
-    if (a.alpha != nullptr) {
-        const dim3 grid((unsigned)((a.n_items + 3) / 4));
-        if (a.bf16) hipLaunchKernelGGL((edge_fwd_kernel<HD, D, true, true, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((edge_fwd_kernel<HD, D, true, false, true>), grid, block, 0, s, a);
-        if (a.n_slots > 0) hipLaunchKernelGGL((edge_fwd_fix_kernel<HD, D, true>), fgrid, block, 0, s, p);
-    } else if constexpr (stash_n<HD, D>() != 0) {
-        constexpr int NN = stash_n<HD, D>(), GG = 64 / (HD / NN);
-        const dim3 g3((unsigned)((a.n_items + GG - 1) / GG));
-        if (a.bf16) hipLaunchKernelGGL((edge_fwd3_kernel<HD, D, NN, true, true>), g3, dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((edge_fwd3_kernel<HD, D, NN, false, true>), g3, dim3(64), 0, s, a);
-        if (a.n_slots > 0) hipLaunchKernelGGL((edge_fwd_fix_kernel<HD, D, false>), fgrid, block, 0, s, p);
-    } else {
-        static_assert(D % 2 == 0, "every fast-path shape has an even D");
-        constexpr int NN = (HD >= 32 && D % 4 == 0) ? 4 : 2;
-        const dim3 grid((unsigned)a.n_items);
-        if (a.bf16) hipLaunchKernelGGL((edge_fwd2_kernel<HD, D, NN, true, true>), grid, dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((edge_fwd2_kernel<HD, D, NN, false, true>), grid, dim3(64), 0, s, a);
-        if (a.n_slots > 0) hipLaunchKernelGGL((edge_fwd_fix_kernel<HD, D, false>), fgrid, block, 0, s, p);
-    }
-    GAT_HIP(hipGetLastError());
-    return 0;
+// waves per block of the packed forward kernels, GAT_FWD_WAVES=1|2|4 (A/B).  One wave per block: a 4-wave block lives as long as its
+// longest item (a 256-edge segment next to 10-edge rows) and pins the other three wave slots meanwhile — 5.51 -> 5.02 ms per step
+static int fwd_waves() {
+    static const int v = [] { const char* e = choice_env("GAT_FWD_WAVES"); const int w = e ? atoi(e) : 1; return (w == 1 || w == 2 || w == 4) ? w : 1; }();
+    return v;
 }
-
-template <int HD, int D>
-int run_fwd(const EdgeFwdArgs& a, hipStream_t s) {
-    if (a.items == nullptr) return fail(GAT_E_INVALID, "edge_forward: work-item list missing");
-    const int64_t blocks = (a.n_items + 3) / 4;
-    if (a.mstat == nullptr || a.zstat == nullptr) return fail(GAT_E_INVALID, "edge_forward: stats buffers missing");
-    const dim3 grid((unsigned)blocks), block(256);
-    const dim3 fgrid((unsigned)(((a.alpha != nullptr ? a.n_slots : a.n_split) + 3) / 4));
-    if (a.alpha != nullptr) {
-        if (a.bf16) hipLaunchKernelGGL((edge_fwd_kernel<HD, D, true, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((edge_fwd_kernel<HD, D, true, false>), grid, block, 0, s, a);
-        if (a.n_slots > 0) hipLaunchKernelGGL((edge_fwd_fix_kernel<HD, D, true>), fgrid, block, 0, s, a);
-    } else {
-        bool launched = false;
-        if constexpr (D % 2 == 0) {
-            if (packed_layout()) {                   // two or four channels per lane (see edge_fwd2_kernel)
-                // one wave per block: a 4-wave block lives as long as its longest item (a 256-edge segment next to
-                // 10-edge rows) and pins the other three wave slots meanwhile — 5.51 -> 5.02 ms per step
-                static const int wpb = [] { const char* e = choice_env("GAT_FWD_WAVES"); const int v = e ? atoi(e) : 1; return (v == 1 || v == 2 || v == 4) ? v : 1; }();
-                const dim3 grid((unsigned)((a.n_items + wpb - 1) / wpb)), block(64 * wpb);
-                if constexpr (stash_n<HD, D>() != 0) {        // group-per-row kernel (GAT_ROWGROUP=0: the chunked one, A/B)
-                    if (row_groups()) {
-                        constexpr int NN = stash_n<HD, D>(), GG = 64 / (HD / NN);
-                        const dim3 g3((unsigned)((a.n_items + (int64_t)GG * wpb - 1) / ((int64_t)GG * wpb)));
-                        if (a.bf16) hipLaunchKernelGGL((edge_fwd3_kernel<HD, D, NN, true>), g3, block, 0, s, a);
-                        else hipLaunchKernelGGL((edge_fwd3_kernel<HD, D, NN, false>), g3, block, 0, s, a);
-                        if (a.n_slots > 0) hipLaunchKernelGGL((edge_fwd_fix_kernel<HD, D, false>), fgrid, dim3(256), 0, s, a);
-                        GAT_HIP(hipGetLastError());
-                        return 0;
-                    }
-                }
-                bool four = false;
-                if constexpr (HD >= 32 && D % 4 == 0) {
-                    if (lane_channels() == 4) {
-                        if (a.bf16) hipLaunchKernelGGL((edge_fwd2_kernel<HD, D, 4, true>), grid, block, 0, s, a);
-                        else hipLaunchKernelGGL((edge_fwd2_kernel<HD, D, 4, false>), grid, block, 0, s, a);
-                        four = true;
-                    }
-                }
-                if (!four) {
-                    if (a.bf16) hipLaunchKernelGGL((edge_fwd2_kernel<HD, D, 2, true>), grid, block, 0, s, a);
-                    else hipLaunchKernelGGL((edge_fwd2_kernel<HD, D, 2, false>), grid, block, 0, s, a);
-                }
-                launched = true;
-            }
-        }
-        if (!launched) {
-            if (a.bf16) hipLaunchKernelGGL((edge_fwd_kernel<HD, D, false, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((edge_fwd_kernel<HD, D, false, false>), grid, block, 0, s, a);
-        }
-        if (a.n_slots > 0) hipLaunchKernelGGL((edge_fwd_fix_kernel<HD, D, false>), fgrid, block, 0, s, a);
-    }
-    GAT_HIP(hipGetLastError());
-    return 0;
-}
-// Blocks of `fn` (256 threads, no dynamic LDS) that are resident on the whole chip at once, from the
-// occupancy API (cached per kernel).  The backward grid is exactly this size: its items are dealt
-// statically, so a second, partially filled round of blocks would be pure tail.
-static int resident_blocks(const void* fn) {
-    static std::mutex mu;
-    static std::map<const void*, int> cache;
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(fn);
-    if (it != cache.end()) return it->second;
-    int per_cu = 0, dev = 0, cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0) != hipSuccess || per_cu < 1) per_cu = 4;
-    if (per_cu > 8) per_cu = 8;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipGetLastError();
-    return cache[fn] = per_cu * (cus > 0 ? cus : 256);
-}
-static bool packed_backward() { return packed_layout(); }
 // GAT_GROUP_MSG=0: message-row layers on the wave-per-row kernel (edge_bwd2_kernel) instead of the group-per-row one (A/B)
 static bool group_msg() {
     static const bool v = [] { const char* e = choice_env("GAT_GROUP_MSG"); return !(e && e[0] == '0'); }();
     return v;
 }
-struct BwdSel { bool store, taps, bf16, stash, drop; };
+
+// The kernel of one edge pass and what its launch needs.  pick_fwd / pick_bwd below are the only places that name an
+// instantiation: the launchers run what they return, and edge_backward_blocks() sizes the persistent backward grid from
+// the same answer, so the two cannot disagree.
+struct EdgePick {
+    const void* fn = nullptr;       // null: no kernel for this selection
+    unsigned block = 256;           // threads per block
+    int per_block = 4;              // forward: work items per block (the backward grid is edge_backward_blocks())
+    const void* fix = nullptr;      // forward: the fix-up kernel of the split rows
+    int grid_div = 1;               // backward: blocks this many times the size of the product kernel's (experiments)
+};
+#define GAT_K(...) ((const void*)(__VA_ARGS__))
+
+// Forward.  Attention dropout / DropEdge (drop): the DROP instantiation of the kernel the default settings pick, one wave per
+// block — the parity-tap form with alpha, else the group-per-row kernel where the shape has one, else the packed wave-per-row
+// kernel.  The A/B switches of the default path (GAT_ROWGROUP, GAT_PACKED, GAT_CPL, GAT_FWD_WAVES) do not apply to it: only these
+// instantiations exist.
 template <int HD, int D, bool BF>
-const void* bwd_variant(bool store, bool taps, bool stash = false) {
-    if constexpr (stash_n<HD, D>() != 0) {
-        if (stash && !taps) {
-            if (BF) return (const void*)edge_bwd3_kernel<HD, D, stash_n<HD, D>(), 0, true>;
-            return row_groups() ? (const void*)edge_bwd3_kernel<HD, D, stash_n<HD, D>()> : (const void*)edge_bwd2s_kernel<HD, D, stash_n<HD, D>()>;
-        }
+EdgePick pick_fwd(const EdgeFwdArgs& a, bool drop) {
+    static_assert(D % 2 == 0, "every fast-path shape has an even D");
+    constexpr int N3 = stash_n<HD, D>(), N2 = (HD >= 32 && D % 4 == 0) ? 4 : 2;
+    constexpr int G3 = N3 != 0 ? 64 / (HD / (N3 != 0 ? N3 : 1)) : 1;             // rows per wave of the group-per-row kernel
+    if (a.alpha != nullptr) {                                                     // parity-tap form: alpha (and scores) materialised
+        const void* fix = GAT_K(edge_fwd_fix_kernel<HD, D, true>);
+        return {drop ? GAT_K(edge_fwd_kernel<HD, D, true, BF, true>) : GAT_K(edge_fwd_kernel<HD, D, true, BF>), 256, 4, fix};
     }
-    if constexpr (stash_n<HD, D>() != 0) {        // message rows from the group-per-row kernel
-        if (store && !taps && packed_backward() && row_groups() && group_msg()) return (const void*)edge_bwd3_kernel<HD, D, stash_n<HD, D>(), 0, BF, true>;
+    const void* fix = GAT_K(edge_fwd_fix_kernel<HD, D, false>);
+    if (drop) {
+        if constexpr (N3 != 0) return {GAT_K(edge_fwd3_kernel<HD, D, N3, BF, true>), 64, G3, fix};
+        else return {GAT_K(edge_fwd2_kernel<HD, D, N2, BF, true>), 64, 1, fix};
     }
-    if constexpr (D % 2 == 0) {
-        if (store && !taps && packed_backward()) {
-            if constexpr (HD >= 32 && D % 4 == 0) {
-                if (lane_channels() == 4) return (const void*)edge_bwd2_kernel<HD, D, 4, 0, BF>;
-            }
-            return (const void*)edge_bwd2_kernel<HD, D, 2, 0, BF>;
-        }
+    if (!packed_layout()) return {GAT_K(edge_fwd_kernel<HD, D, false, BF>), 256, 4, fix};
+    const int wpb = fwd_waves();                                                  // two or four channels per lane (see edge_fwd2_kernel)
+    if constexpr (N3 != 0) {                                                      // group-per-row kernel (GAT_ROWGROUP=0: the chunked one, A/B)
+        if (row_groups()) return {GAT_K(edge_fwd3_kernel<HD, D, N3, BF>), 64u * wpb, G3 * wpb, fix};
     }
-    return store ? (taps ? (const void*)edge_bwd_kernel<HD, D, true, true, 0, BF> : (const void*)edge_bwd_kernel<HD, D, true, false, 0, BF>)
-                 : (taps ? (const void*)edge_bwd_kernel<HD, D, false, true, 0, BF> : (const void*)edge_bwd_kernel<HD, D, false, false, 0, BF>);
-}
-// the attention-dropout kernel run_bwd_drop launches for this selection (null: none)
-template <int HD, int D, bool BF>
-const void* bwd_variant_drop(bool store, bool taps, bool stash) {
-    if (taps) return store ? (const void*)edge_bwd_kernel<HD, D, true, true, 0, BF, true> : nullptr;
-    if (!store) return nullptr;
-    if constexpr (stash_n<HD, D>() != 0) {
-        if (stash) return (const void*)edge_bwd3_kernel<HD, D, stash_n<HD, D>(), 0, BF, false, true>;
-        return (const void*)edge_bwd3_kernel<HD, D, stash_n<HD, D>(), 0, BF, true, true>;
-    } else {
-        return (const void*)edge_bwd2_kernel<HD, D, (HD >= 32 && D % 4 == 0) ? 4 : 2, 0, BF, false, true>;
+    if constexpr (N2 == 4) {
+        if (lane_channels() == 4) return {GAT_K(edge_fwd2_kernel<HD, D, 4, BF>), 64u * wpb, wpb, fix};
     }
-}
-template <int HD, int D>
-int bwd_resident(const BwdSel& sel, hipStream_t) {
-    if (sel.drop) {
-        const void* fn = sel.bf16 ? bwd_variant_drop<HD, D, true>(sel.store, sel.taps, sel.stash) : bwd_variant_drop<HD, D, false>(sel.store, sel.taps, sel.stash);
-        if (fn != nullptr) return resident_blocks(fn);
-    }
-    return resident_blocks(sel.bf16 ? bwd_variant<HD, D, true>(sel.store, sel.taps, sel.stash) : bwd_variant<HD, D, false>(sel.store, sel.taps, sel.stash));
+    return {GAT_K(edge_fwd2_kernel<HD, D, 2, BF>), 64u * wpb, wpb, fix};
 }
 
-template <int HD, int D>
-int run_bwd_drop(const EdgeBwdDropArgs& a, hipStream_t s) {
-    if (a.items == nullptr) return fail(GAT_E_INVALID, "edge_backward: work-item list missing");
+#ifdef GAT_EXPERIMENTS
+// the record-path timing variants of the group-per-row backward at H*D = 64, D = 8 that differ in nothing but DBG
+template <int... DBG>
+const void* bwd3_dbg(int dbg) {
+    const void* fn = nullptr;
+    ((dbg == DBG ? (void)(fn = GAT_K(edge_bwd3_kernel<64, 8, 4, DBG>)) : (void)0), ...);
+    return fn;
+}
+#endif
+
+// Backward.  store: message rows or records by CSC slot (else atomics into gPL); taps: the parity form that also writes ge / galpha;
+// stash: per-edge records + pull pass instead of message rows.  Attention dropout / DropEdge (drop) exist for the store path only,
+// as the DROP instantiation of the kernel the default settings pick; the A/B switches do not apply to them.
+// dbg (experiment library only, GAT_DBG): timing variants, most with WRONG results; 0 = the product kernel of the selection.
+template <int HD, int D, bool BF>
+EdgePick pick_bwd(const EdgeBwdArgs& a, bool drop, int dbg) {
+    constexpr int N3 = stash_n<HD, D>(), N2 = (HD >= 32 && D % 4 == 0) ? 4 : 2;
     const bool store = a.pos != nullptr && a.msg != nullptr, taps = a.ge != nullptr, stash = a.stash != nullptr && !taps;
-    if (stash && (a.gfull == nullptr || a.pos == nullptr)) return fail(GAT_E_INVALID, "edge_backward: stash path needs gfull and pos");
-    const void* fn = a.bf16 ? bwd_variant_drop<HD, D, true>(store, taps, stash) : bwd_variant_drop<HD, D, false>(store, taps, stash);
-    if (fn == nullptr)
-        return fail(GAT_E_UNSUPPORTED, "edge_backward: attention dropout / DropEdge need the store path (not with GAT_BWD_ATOMICS=1 or without the message scratch)");
-    void* args[] = {const_cast<EdgeBwdDropArgs*>(&a)};
-    GAT_HIP(hipLaunchKernel(fn, dim3((unsigned)a.ga_blocks), dim3(256), args, 0, s));
-    if (a.n_slots > 0) {
-        const int64_t threads = (int64_t)a.n_split * HD;
-        hipLaunchKernelGGL(edge_bwd_fix_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s,
-                           a.slot_info, a.n_slots, a.n_split, a.part_acc, a.gPR, HD);
-        GAT_HIP(hipGetLastError());
+    if (drop) {
+        if (!store) return {};
+        if (taps) return {GAT_K(edge_bwd_kernel<HD, D, true, true, 0, BF, true>)};
+        if constexpr (N3 != 0) return {stash ? GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, false, true>) : GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, true, true>)};
+        else return {GAT_K(edge_bwd2_kernel<HD, D, N2, 0, BF, false, true>)};
     }
+    const bool msg_rows = store && !taps && packed_layout();                      // packed message-row kernels
+#ifdef GAT_EXPERIMENTS
+    if constexpr (HD == 64 && D == 8) {
+        if (store && !taps && !stash) {                                           // GAT_DBG=1: no message store, 2: sequential slots
+            if (dbg == 1) return {GAT_K(edge_bwd_kernel<HD, D, true, false, 1>)};
+            if (dbg == 2) return {GAT_K(edge_bwd_kernel<HD, D, true, false, 2>)};
+        }
+        if (stash && !BF && row_groups()) {
+            // GAT_DBG=1: no record store, 2: records in CSR order, 3; 9: double walk; scatter folded into 64 MiB (10), 16 MiB, 4 MiB,
+            // 1 MiB (13), 1 GiB (14); 64 (15), 512, 4,096, 32,768 (18) sequential write fronts
+            if (const void* fn = bwd3_dbg<1, 2, 3, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18>(dbg)) return {fn};
+            // wave-specialised stores.  4: 7 + 1 waves, 512-thread blocks — half as many are resident as of the 256-thread product
+            // kernel the grid is sized from, so half its grid
+            if (dbg == 4) return {GAT_K(edge_bwd4_kernel<7, 4>), 512, 4, nullptr, 2};
+            if (dbg == 5) return {GAT_K(edge_bwd4_kernel<3, 4>)};                 // 3 + 1 waves
+            if (dbg == 6) return {GAT_K(edge_bwd4_kernel<3, 4, 1>)};              // 3 + 1 waves, sc1 stores
+            if (dbg == 7) return {GAT_K(edge_bwd4_kernel<3, 4, 2>)};              // sc0 sc1
+            if (dbg == 8) return {GAT_K(edge_bwd4_kernel<3, 4, 3>)};              // nt
+        } else if (stash && !BF) {
+            if (dbg == 1) return {GAT_K(edge_bwd2s_kernel<64, 8, 4, 1>)};
+            if (dbg == 2) return {GAT_K(edge_bwd2s_kernel<64, 8, 4, 2>)};
+        }
+    }
+#endif
+    if constexpr (N3 != 0) {
+        // records; bf16 storage: always the group-per-row kernel (GAT_ROWGROUP=0 has no bf16 form)
+        if (stash) return {(BF || row_groups()) ? GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF>) : GAT_K(edge_bwd2s_kernel<HD, D, N3>)};
+        if (msg_rows && row_groups() && group_msg()) {                            // message rows from the group-per-row kernel
+#ifdef GAT_EXPERIMENTS      // GAT_DBG=1 on a message-row layer (BASELINE config 5): the walk without its message-row stores — WRONG RESULTS, timing / PMC
+            if constexpr (HD == 32 && D == 8 && BF) {     // attribution only (DESIGN §4 "Round 4": how much of the backward's reads is fill for its 64-byte row writes)
+                if (dbg == 1) return {GAT_K(edge_bwd3_kernel<HD, D, N3, 1, true, true>)};
+            }
+#endif
+            return {GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, true>)};
+        }
+    }
+    if (msg_rows) {
+        if constexpr (N2 == 4) {
+            if (lane_channels() == 4) return {GAT_K(edge_bwd2_kernel<HD, D, 4, 0, BF>)};
+        }
+        return {GAT_K(edge_bwd2_kernel<HD, D, 2, 0, BF>)};
+    }
+    return {store ? (taps ? GAT_K(edge_bwd_kernel<HD, D, true, true, 0, BF>) : GAT_K(edge_bwd_kernel<HD, D, true, false, 0, BF>))
+                  : (taps ? GAT_K(edge_bwd_kernel<HD, D, false, true, 0, BF>) : GAT_K(edge_bwd_kernel<HD, D, false, false, 0, BF>))};
+}
+
+// the templates' entry: FN<H*D, D, bf16 storage>(...) for a listed shape (returns from the enclosing function), nothing otherwise
+#define GAT_SHAPE_CASE(hd, d, FN, BF, ...) case hd * 1000 + d: return (BF) ? FN<hd, d, true>(__VA_ARGS__) : FN<hd, d, false>(__VA_ARGS__);
+#define GAT_DISPATCH_HD_D(HD, D, FN, BF, ...) \
+    switch ((HD) * 1000 + (D)) { GAT_EDGE_SHAPES(GAT_SHAPE_CASE, FN, BF, __VA_ARGS__) default: break; }
+static EdgePick pick_forward(const EdgeFwdArgs& a, bool drop) {
+    GAT_DISPATCH_HD_D(a.H * a.D, a.D, pick_fwd, a.bf16 != 0, a, drop)
+    return {};
+}
+static EdgePick pick_backward(const EdgeBwdArgs& a, bool drop, int dbg) {
+    GAT_DISPATCH_HD_D(a.H * a.D, a.D, pick_bwd, a.bf16 != 0, a, drop, dbg)
+    return {};
+}
+
+// Blocks of `fn` (`block` threads, no dynamic LDS) that are resident on the whole chip at once, from the
+// occupancy API (cached per kernel).  The backward grid is exactly this size: its items are dealt
+// statically, so a second, partially filled round of blocks would be pure tail.
+static int resident_blocks(const void* fn, unsigned block) {
+    static std::mutex mu;
+    static std::map<std::pair<const void*, unsigned>, int> cache;
+    std::lock_guard<std::mutex> lock(mu);
+    const auto key = std::make_pair(fn, block);
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+    int per_cu = 0, dev = 0, cus = 256;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, (int)block, 0) != hipSuccess || per_cu < 1) per_cu = 4;
+    if (per_cu > 8) per_cu = 8;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    (void)hipGetLastError();
+    return cache[key] = per_cu * (cus > 0 ? cus : 256);
+}
+
+// the split rows' partial sums -> their rows (after either forward kernel)
+static int launch_fwd_fix(const EdgePick& p, const EdgeFwdArgs& a, hipStream_t s) {
+    if (a.n_slots <= 0) return 0;
+    const int64_t n = a.alpha != nullptr ? a.n_slots : a.n_split;                 // per segment with alpha, else per split row
+    void* args[] = {const_cast<EdgeFwdArgs*>(&a)};
+    GAT_HIP(hipLaunchKernel(p.fix, dim3((unsigned)((n + 3) / 4)), dim3(256), args, 0, s));
     return 0;
 }
-
-template <int HD, int D>
-int run_bwd(const EdgeBwdArgs& a, hipStream_t s) {
-    if (a.items == nullptr) return fail(GAT_E_INVALID, "edge_backward: work-item list missing");
-    const dim3 grid((unsigned)a.ga_blocks), block(256);
-    const bool store = a.pos != nullptr && a.msg != nullptr, taps = a.ge != nullptr;
-#ifdef GAT_EXPERIMENTS
-    if constexpr (HD == 64 && D == 8) {          // timing experiments (GAT_DBG=1: no message store, 2: sequential slots) — WRONG RESULTS
-        if (store && !taps && a.stash == nullptr && a.dbg == 1) { hipLaunchKernelGGL((edge_bwd_kernel<HD, D, true, false, 1>), grid, block, 0, s, a); return 0; }
-        if (store && !taps && a.stash == nullptr && a.dbg == 2) { hipLaunchKernelGGL((edge_bwd_kernel<HD, D, true, false, 2>), grid, block, 0, s, a); return 0; }
-    }
-#endif
-    bool launched = false;
-    if constexpr (stash_n<HD, D>() != 0) {
-        if (a.stash != nullptr && !taps && a.bf16) {                // bf16 storage: always the group-per-row kernel
-            if (a.gfull == nullptr || a.pos == nullptr) return fail(GAT_E_INVALID, "edge_backward: stash path needs gfull and pos");
-            hipLaunchKernelGGL((edge_bwd3_kernel<HD, D, stash_n<HD, D>(), 0, true>), grid, block, 0, s, a);
-            launched = true;
-        }
-        if (a.stash != nullptr && !taps && !a.bf16) {
-            if (a.gfull == nullptr || a.pos == nullptr) return fail(GAT_E_INVALID, "edge_backward: stash path needs gfull and pos");
-            bool dbg_done = false;
-#ifdef GAT_EXPERIMENTS                               // GAT_DBG exists in the experiment library only (make experiments): most values give WRONG results
-            if constexpr (HD == 64 && D == 8) {      // timing experiments (GAT_DBG=1: no record store, 2: records in CSR order)
-                if (a.dbg == 9 && row_groups()) { hipLaunchKernelGGL((edge_bwd3_kernel<64, 8, 4, 9>), grid, block, 0, s, a); dbg_done = true; }   // double walk
-                else if (a.dbg == 10 && row_groups()) { hipLaunchKernelGGL((edge_bwd3_kernel<64, 8, 4, 10>), grid, block, 0, s, a); dbg_done = true; }   // scatter folded into 64 MiB
-                else if (a.dbg == 11 && row_groups()) { hipLaunchKernelGGL((edge_bwd3_kernel<64, 8, 4, 11>), grid, block, 0, s, a); dbg_done = true; }   // 16 MiB
-                else if (a.dbg == 12 && row_groups()) { hipLaunchKernelGGL((edge_bwd3_kernel<64, 8, 4, 12>), grid, block, 0, s, a); dbg_done = true; }   // 4 MiB
-                else if (a.dbg == 13 && row_groups()) { hipLaunchKernelGGL((edge_bwd3_kernel<64, 8, 4, 13>), grid, block, 0, s, a); dbg_done = true; }   // 1 MiB
-                else if (a.dbg == 15 && row_groups()) { hipLaunchKernelGGL((edge_bwd3_kernel<64, 8, 4, 15>), grid, block, 0, s, a); dbg_done = true; }   // 64 sequential write fronts
-                else if (a.dbg == 16 && row_groups()) { hipLaunchKernelGGL((edge_bwd3_kernel<64, 8, 4, 16>), grid, block, 0, s, a); dbg_done = true; }   // 512
-                else if (a.dbg == 17 && row_groups()) { hipLaunchKernelGGL((edge_bwd3_kernel<64, 8, 4, 17>), grid, block, 0, s, a); dbg_done = true; }   // 4,096
-                else if (a.dbg == 18 && row_groups()) { hipLaunchKernelGGL((edge_bwd3_kernel<64, 8, 4, 18>), grid, block, 0, s, a); dbg_done = true; }   // 32,768
-                else if (a.dbg == 14 && row_groups()) { hipLaunchKernelGGL((edge_bwd3_kernel<64, 8, 4, 14>), grid, block, 0, s, a); dbg_done = true; }   // 1 GiB
-                else if (a.dbg == 4 && row_groups()) { hipLaunchKernelGGL((edge_bwd4_kernel<7, 4>), grid, dim3(512), 0, s, a); dbg_done = true; }   // wave-specialised stores: 7 + 1 waves
-                else if (a.dbg == 6 && row_groups()) { hipLaunchKernelGGL((edge_bwd4_kernel<3, 4, 1>), grid, dim3(256), 0, s, a); dbg_done = true; }   // 3 + 1 waves, sc1 stores
-                else if (a.dbg == 7 && row_groups()) { hipLaunchKernelGGL((edge_bwd4_kernel<3, 4, 2>), grid, dim3(256), 0, s, a); dbg_done = true; }   // sc0 sc1
-                else if (a.dbg == 8 && row_groups()) { hipLaunchKernelGGL((edge_bwd4_kernel<3, 4, 3>), grid, dim3(256), 0, s, a); dbg_done = true; }   // nt
-                else if (a.dbg == 5 && row_groups()) { hipLaunchKernelGGL((edge_bwd4_kernel<3, 4>), grid, dim3(256), 0, s, a); dbg_done = true; }   // 3 + 1 waves
-                else if (a.dbg == 3 && row_groups()) { hipLaunchKernelGGL((edge_bwd3_kernel<64, 8, 4, 3>), grid, block, 0, s, a); dbg_done = true; }
-                else if (a.dbg == 1 && row_groups()) { hipLaunchKernelGGL((edge_bwd3_kernel<64, 8, 4, 1>), grid, block, 0, s, a); dbg_done = true; }
-                else if (a.dbg == 2 && row_groups()) { hipLaunchKernelGGL((edge_bwd3_kernel<64, 8, 4, 2>), grid, block, 0, s, a); dbg_done = true; }
-                else if (a.dbg == 1) { hipLaunchKernelGGL((edge_bwd2s_kernel<64, 8, 4, 1>), grid, block, 0, s, a); dbg_done = true; }
-                else if (a.dbg == 2) { hipLaunchKernelGGL((edge_bwd2s_kernel<64, 8, 4, 2>), grid, block, 0, s, a); dbg_done = true; }
-            }
-#endif
-            if (!dbg_done) {
-                if (row_groups()) hipLaunchKernelGGL((edge_bwd3_kernel<HD, D, stash_n<HD, D>()>), grid, block, 0, s, a);
-                else hipLaunchKernelGGL((edge_bwd2s_kernel<HD, D, stash_n<HD, D>()>), grid, block, 0, s, a);
-            }
-            launched = true;
-        }
-    }
-    if constexpr (stash_n<HD, D>() != 0) {
-#ifdef GAT_EXPERIMENTS       // GAT_DBG=1 on a message-row layer (BASELINE config 5): the walk without its message-row stores — WRONG RESULTS, timing / PMC
-        if constexpr (HD == 32 && D == 8) {           // attribution only (DESIGN §4 "Round 4": how much of the backward's reads is fill for its 64-byte row writes)
-            if (!launched && store && !taps && packed_backward() && row_groups() && group_msg() && a.bf16 && a.dbg == 1) {
-                hipLaunchKernelGGL((edge_bwd3_kernel<HD, D, stash_n<HD, D>(), 1, true, true>), grid, block, 0, s, a);
-                launched = true;
-            }
-        }
-#endif
-        if (!launched && store && !taps && packed_backward() && row_groups() && group_msg()) {
-            if (a.bf16) hipLaunchKernelGGL((edge_bwd3_kernel<HD, D, stash_n<HD, D>(), 0, true, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((edge_bwd3_kernel<HD, D, stash_n<HD, D>(), 0, false, true>), grid, block, 0, s, a);
-            launched = true;
-        }
-    }
-    if constexpr (D % 2 == 0) {
-        if (!launched && store && !taps && packed_backward()) {
-            bool four = false;
-            if constexpr (HD >= 32 && D % 4 == 0) {
-                if (lane_channels() == 4) {
-                    if (a.bf16) hipLaunchKernelGGL((edge_bwd2_kernel<HD, D, 4, 0, true>), grid, block, 0, s, a);
-                    else hipLaunchKernelGGL((edge_bwd2_kernel<HD, D, 4, 0, false>), grid, block, 0, s, a);
-                    four = true;
-                }
-            }
-            if (!four) {
-                if (a.bf16) hipLaunchKernelGGL((edge_bwd2_kernel<HD, D, 2, 0, true>), grid, block, 0, s, a);
-                else hipLaunchKernelGGL((edge_bwd2_kernel<HD, D, 2, 0, false>), grid, block, 0, s, a);
-            }
-            launched = true;
-        }
-    }
-    if (launched) {
-    } else if (a.bf16) {
-        if (store && taps) hipLaunchKernelGGL((edge_bwd_kernel<HD, D, true, true, 0, true>), grid, block, 0, s, a);
-        else if (store) hipLaunchKernelGGL((edge_bwd_kernel<HD, D, true, false, 0, true>), grid, block, 0, s, a);
-        else if (taps) hipLaunchKernelGGL((edge_bwd_kernel<HD, D, false, true, 0, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((edge_bwd_kernel<HD, D, false, false, 0, true>), grid, block, 0, s, a);
-    } else {
-        if (store && taps) hipLaunchKernelGGL((edge_bwd_kernel<HD, D, true, true>), grid, block, 0, s, a);
-        else if (store) hipLaunchKernelGGL((edge_bwd_kernel<HD, D, true, false>), grid, block, 0, s, a);
-        else if (taps) hipLaunchKernelGGL((edge_bwd_kernel<HD, D, false, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((edge_bwd_kernel<HD, D, false, false>), grid, block, 0, s, a);
-    }
+static int launch_bwd_fix(const EdgeBwdArgs& a, hipStream_t s) {
+    if (a.n_slots <= 0) return 0;
+    const int HD = a.H * a.D;
+    const int64_t threads = (int64_t)a.n_split * HD;
+    hipLaunchKernelGGL(edge_bwd_fix_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s,
+                       a.slot_info, a.n_slots, a.n_split, a.part_acc, a.gPR, HD);
     GAT_HIP(hipGetLastError());
-    if (a.n_slots > 0) {
-        const int64_t threads = (int64_t)a.n_split * HD;
-        hipLaunchKernelGGL(edge_bwd_fix_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s,
-                           a.slot_info, a.n_slots, a.n_split, a.part_acc, a.gPR, HD);
-        GAT_HIP(hipGetLastError());
-    }
     return 0;
 }
 
@@ -2216,105 +2127,66 @@ constexpr int kGenericBlocks = 4096;
 
 }  // namespace
 
-#define GAT_DISPATCH_HD_D(FN, ARGS, S)                                            \
-    switch (HD * 1000 + D) {                                                      \
-        case 64008: return FN<64, 8>(ARGS, S);                                    \
-        case 64004: return FN<64, 4>(ARGS, S);                                    \
-        case 64016: return FN<64, 16>(ARGS, S);                                   \
-        case 64032: return FN<64, 32>(ARGS, S);                                   \
-        case 64064: return FN<64, 64>(ARGS, S);                                   \
-        case 32008: return FN<32, 8>(ARGS, S);                                    \
-        case 32004: return FN<32, 4>(ARGS, S);                                    \
-        case 32016: return FN<32, 16>(ARGS, S);                                   \
-        case 32032: return FN<32, 32>(ARGS, S);                                   \
-        case 16004: return FN<16, 4>(ARGS, S);                                    \
-        case 16008: return FN<16, 8>(ARGS, S);                                    \
-        case 16016: return FN<16, 16>(ARGS, S);                                   \
-        case 8004: return FN<8, 4>(ARGS, S);                                      \
-        case 8008: return FN<8, 8>(ARGS, S);                                      \
-        default: break;                                                           \
-    }
+bool edge_fast_path(int32_t H, int32_t D, int64_t n_table) {
+    return n_table * H * D * (int64_t)sizeof(float) < ((int64_t)1 << 32) && edge_shape_listed(H * D, D);
+}
+int edge_stash_words(int32_t H, int32_t D) {
+    const int n = edge_shape_listed(H * D, D) ? stash_n(H * D, D) : 0;
+    return n ? H * D / n : 0;
+}
 
 int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const DropArgs* drop) {
     if (a.n_rows <= 0) return 0;
-    const int HD = a.H * a.D, D = a.D;
     const DropArgs dr = drop != nullptr ? *drop : DropArgs{};
     if (edge_fast_path(a.H, a.D, a.n_table)) {
-        if (dr.on) {
-            EdgeFwdDropArgs ad;
-            static_cast<EdgeFwdArgs&>(ad) = a;
-            ad.drop = dr;
-            GAT_DISPATCH_HD_D(run_fwd_drop, ad, s)
-        } else {
-            GAT_DISPATCH_HD_D(run_fwd, a, s)
-        }
+        if (a.items == nullptr) return fail(GAT_E_INVALID, "edge_forward: work-item list missing");
+        if (a.mstat == nullptr || a.zstat == nullptr) return fail(GAT_E_INVALID, "edge_forward: stats buffers missing");
+        const EdgePick p = pick_forward(a, dr.on != 0);
+        EdgeFwdDropArgs ad;                              // the argument struct of the DROP instantiations
+        if (dr.on) { static_cast<EdgeFwdArgs&>(ad) = a; ad.drop = dr; }
+        void* args[] = {dr.on ? (void*)&ad : (void*)const_cast<EdgeFwdArgs*>(&a)};
+        GAT_HIP(hipLaunchKernel(p.fn, dim3((unsigned)((a.n_items + p.per_block - 1) / p.per_block)), dim3(p.block), args, 0, s));
+        return launch_fwd_fix(p, a, s);
     }
+    const int HD = a.H * a.D;
     const int64_t blocks = a.n_rows < kGenericBlocks * 8 ? a.n_rows : kGenericBlocks * 8;
     hipLaunchKernelGGL(edge_fwd_generic, dim3((unsigned)blocks), dim3(64), (size_t)HD * sizeof(float), s, a, dr);
     GAT_HIP(hipGetLastError());
     return 0;
 }
 
-template <int HD, int D>
-int stash_words_t(const int&, hipStream_t) { return stash_n<HD, D>() ? HD / stash_n<HD, D>() : 0; }
-int edge_stash_words(int32_t H, int32_t D_) {
-    const int HD = H * D_, D = D_;
-    const int dummy = 0;
-    auto probe = [&]() -> int {
-        GAT_DISPATCH_HD_D(stash_words_t, dummy, nullptr)
-        return 0;
-    };
-    return probe();
-}
-
-int edge_backward_blocks(int64_t n_items, int32_t H, int32_t D_, bool store, bool taps, bool bf16, bool stash, bool drop) {
-    int64_t want = (n_items + 3) / 4;
-    if (want < 1) want = 1;
-    const int HD = H * D_, D = D_;
-    const BwdSel sel{store, taps, bf16, stash, drop};
-    auto cap = [&]() -> int {
-        GAT_DISPATCH_HD_D(bwd_resident, sel, nullptr)
-        return 2048;                                  // generic path: one wave per block
-    };
-    int c = cap();
-    // experiment library, GAT_DBG=4: 512-thread blocks of edge_bwd4_kernel — two resident per CU instead of four
+int edge_backward_blocks(const EdgeBwdArgs& a, const DropArgs* drop) {
+    if (!edge_fast_path(a.H, a.D, a.n_table))            // generic path: one wave per block, a row at a time
+        return (int)std::min<int64_t>(std::max<int64_t>(a.n_rows, 1), kGaPartialRows);
+    const bool on = drop != nullptr && drop->on != 0;
+    // the experiment kernels (dbg) run on the grid of the product kernel of their selection
+    EdgePick p = pick_backward(a, on, 0);
+    if (p.fn == nullptr) p = pick_backward(a, false, 0);  // no dropout form: launch_edge_backward reports it
+    int64_t cap = resident_blocks(p.fn, p.block);
 #ifdef GAT_EXPERIMENTS
-    static const int dbg = [] { const char* e = getenv("GAT_DBG"); return e ? atoi(e) : 0; }();
-    if (dbg == 4 && HD == 64 && D == 8 && stash && !bf16 && !taps) c = c / 2;
+    cap /= pick_backward(a, on, a.dbg).grid_div;
 #endif
-    return (int)(want < c ? want : c);
-}
-
-static int fast_probe(const int&, hipStream_t) { return 1; }
-template <int HD, int D>
-int fast_probe_t(const int& x, hipStream_t s) { return fast_probe(x, s); }
-
-bool edge_fast_path(int32_t H, int32_t D_, int64_t n_table) {
-    const int HD = H * D_, D = D_;
-    if (n_table * HD * (int64_t)sizeof(float) >= ((int64_t)1 << 32)) return false;
-    const int dummy = 0;
-    auto probe = [&]() -> int {
-        GAT_DISPATCH_HD_D(fast_probe_t, dummy, nullptr)
-        return 0;
-    };
-    return probe() == 1;
+    return (int)std::min({std::max<int64_t>((a.n_items + 3) / 4, 1), cap, (int64_t)kGaPartialRows});
 }
 
 int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s, const DropArgs* drop) {
-    const int HD = a.H * a.D, D = a.D;
     if (a.ga_blocks < 1) return fail(GAT_E_INVALID, "edge_backward: ga_blocks must come from edge_backward_blocks()");
     const DropArgs dr = drop != nullptr ? *drop : DropArgs{};
     if (edge_fast_path(a.H, a.D, a.n_table)) {
-        if (dr.on) {
-            EdgeBwdDropArgs ad;
-            static_cast<EdgeBwdArgs&>(ad) = a;
-            ad.drop = dr;
-            GAT_DISPATCH_HD_D(run_bwd_drop, ad, s)
-        } else {
-            GAT_DISPATCH_HD_D(run_bwd, a, s)
-        }
+        if (a.items == nullptr) return fail(GAT_E_INVALID, "edge_backward: work-item list missing");
+        if (a.stash != nullptr && a.ge == nullptr && (a.gfull == nullptr || a.pos == nullptr))
+            return fail(GAT_E_INVALID, "edge_backward: stash path needs gfull and pos");
+        const EdgePick p = pick_backward(a, dr.on != 0, a.dbg);
+        if (p.fn == nullptr)
+            return fail(GAT_E_UNSUPPORTED, "edge_backward: attention dropout / DropEdge need the store path (not with GAT_BWD_ATOMICS=1 or without the message scratch)");
+        EdgeBwdDropArgs ad;
+        if (dr.on) { static_cast<EdgeBwdArgs&>(ad) = a; ad.drop = dr; }
+        void* args[] = {dr.on ? (void*)&ad : (void*)const_cast<EdgeBwdArgs*>(&a)};
+        GAT_HIP(hipLaunchKernel(p.fn, dim3((unsigned)a.ga_blocks), dim3(p.block), args, 0, s));
+        return launch_bwd_fix(a, s);
     }
     if (a.pos != nullptr) return fail(GAT_E_INVALID, "edge_backward: the generic path has no store mode");
+    const int HD = a.H * a.D;
     const size_t lds = (size_t)(3 * a.H + 2 * HD) * sizeof(float);
     if (lds > 64 * 1024) return fail(GAT_E_UNSUPPORTED, "edge_backward: H*D too large for the generic path");
     hipLaunchKernelGGL(edge_bwd_generic, dim3((unsigned)a.ga_blocks), dim3(64), lds, s, a, dr);
@@ -2325,7 +2197,7 @@ int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s, const DropArgs* dr
 bool edge_last_fused_supported(int32_t H, int32_t D, int32_t C) { return H * D == 64 && D == 8 && C >= 1 && C <= 64; }
 int edge_last_fused_blocks(int64_t n_items) {
     const int64_t want = std::max<int64_t>(1, ((n_items + 3) / 4 + 3) / 4);        // 4 rows per wave, 4 waves per block
-    const int cap = resident_blocks((const void*)edge_last_fused_kernel<64, 8, 4>);
+    const int cap = std::min(resident_blocks((const void*)edge_last_fused_kernel<64, 8, 4>, 256u), kGaPartialRows);
     return (int)std::min<int64_t>(want, cap);
 }
 int launch_edge_last_fused(const EdgeLastArgs& a, hipStream_t s) {

@@ -210,8 +210,11 @@ int launch_head_rows(const int4* slot_info, int32_t n_slots, int32_t n_split, co
 // Words per edge record of the stash path for an (H, D) layer, 0 = that shape has no stash path (the message-row
 // path is used): two lanes per head are needed (D = 8 with four channels per lane, D = 4 with two).
 int edge_stash_words(int32_t H, int32_t D);
-// Grid size (== rows of ga_partial) for the backward of an (H, D) layer over n_items work items.
-int edge_backward_blocks(int64_t n_items, int32_t H, int32_t D, bool store, bool taps, bool bf16, bool stash = false, bool drop = false);
+// Rows of ga_partial a layer's backward may write: the cap of every grid that writes one row per block
+constexpr int kGaPartialRows = 2048;
+// Grid size (== rows of ga_partial, <= kGaPartialRows) for the backward launch_edge_backward(a, s, drop) will run: sized for the
+// kernel those arguments select (a.ga_blocks is not read)
+int edge_backward_blocks(const EdgeBwdArgs& a, const DropArgs* drop = nullptr);
 // wave-per-row templates cover this (H, D), and the gathered table is < 4 GiB (they address it as
 // uniform base + 32-bit byte offset); anything else runs the generic kernels
 bool edge_fast_path(int32_t H, int32_t D, int64_t n_table);
