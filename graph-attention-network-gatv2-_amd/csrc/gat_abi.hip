@@ -43,6 +43,8 @@ static std::string choices_text() {
 struct Layer {
     int32_t H = 0, D = 0, F = 0, HD = 0;
     int64_t w_off = 0, a_off = 0;
+    int64_t wres_off = 0, b_off = 0;                // inside the Wres / b groups (gat_set_residual)
+    float* R = nullptr;       // [n_rows][HD]  x' Wres^T of the shard's own rows (GAT_RES_LINEAR)
     float* PL = nullptr;      // [n_table][HD]  (table; may be caller-owned)
     bool PL_bound = false;
     float* PR = nullptr;      // [n_rows][HD]
@@ -136,8 +138,14 @@ struct gat_ctx {
                                                     // column in_dim), so that an odd in_dim — Cora's 1,433 — still gets 16-byte loads
     float* Xtab = nullptr;                          // [n_table][in_dim] replicated layer-0 input (gat_set_source_features)
     int64_t nW = 0, nA = 0, nWo = 0;
-    float* params = nullptr;   // [W | a | Wo]
-    float* grads = nullptr;    // [gradW | grada | gradWo] + 4 floats of tail: [loss, correct lo, correct hi, -]
+    int64_t nWres = 0, nB = 0;                      // 0 unless gat_set_residual switched the group on
+    int32_t res_flags = 0;                          // GAT_RES_* (gat_set_residual)
+    bool params_touched = false;                    // a gat_params_* / gat_grads_* / gat_set_graph* call was made: the packed buffers keep their size
+    float* resG = nullptr; float* res_agg = nullptr;   // [n_rows][HDmax] dL/dh_pre and h_pre - (R + b) of the layer whose backward runs
+    float* res_partial = nullptr;                   // [L][kResPartialRows][HDmax] block column sums of G (grad_b), one region per layer
+    float* res_gw_scratch = nullptr; std::vector<int64_t> res_gw_off;     // slabs of gradWres, one region per layer
+    float* params = nullptr;   // [W | a | Wo | Wres | b]
+    float* grads = nullptr;    // [gradW | grada | gradWo | gradWres | gradb] + 4 floats of tail: [loss, correct lo, correct hi, -]
     std::unique_ptr<gat::Comm> comm;                // exchange transport of a shard (gat_comm_init_*)
     int32_t comm_chunks = 1;                        // gat_comm_option(GAT_COMM_PIPELINE): row chunks of the pipelined forward exchange
     hipStream_t comm_stream = nullptr;              // second stream of the pipelined exchange (created on first use)
@@ -271,6 +279,13 @@ static float* Wo_of(gat_ctx* c) { return c->params + c->nW + c->nA; }
 static float* gW_of(gat_ctx* c, int l) { return c->grads + c->layers[l].w_off; }
 static float* ga_of(gat_ctx* c, int l) { return c->grads + c->nW + c->layers[l].a_off; }
 static float* gWo_of(gat_ctx* c) { return c->grads + c->nW + c->nA; }
+static int64_t n_params(const gat_ctx* c) { return c->nW + c->nA + c->nWo + c->nWres + c->nB; }
+static bool res_on(const gat_ctx* c) { return c->res_flags != 0; }
+// null while the group is off
+static float* Wres_of(gat_ctx* c, int l) { return c->nWres ? c->params + c->nW + c->nA + c->nWo + c->layers[l].wres_off : nullptr; }
+static float* b_of(gat_ctx* c, int l) { return c->nB ? c->params + c->nW + c->nA + c->nWo + c->nWres + c->layers[l].b_off : nullptr; }
+static float* gWres_of(gat_ctx* c, int l) { return c->grads + c->nW + c->nA + c->nWo + c->layers[l].wres_off; }
+static float* gb_of(gat_ctx* c, int l) { return c->grads + c->nW + c->nA + c->nWo + c->nWres + c->layers[l].b_off; }
 static bool feat_drop_on(const gat_ctx* c) { return c->training && c->drop_pf > 0.f; }
 static bool attn_drop_on(const gat_ctx* c) { return c->training && c->drop_pa > 0.f; }
 static bool edge_drop_on(const gat_ctx* c) { return c->training && c->edge_p > 0.f; }
@@ -468,6 +483,26 @@ static int ensure_buffers(gat_ctx* c) {
     GAT_TRY(dalloc(c, &c->loss_out, 1));
     GAT_TRY(dalloc(c, &c->correct_out, 1));
     GAT_TRY(dalloc(c, &c->y, N * C));
+    if (res_on(c)) {                                 // gatv2_abi.h "residual"
+        GAT_TRY(dalloc(c, &c->resG, N * c->HDmax));
+        GAT_TRY(dalloc(c, &c->res_agg, N * c->HDmax));
+        GAT_TRY(dalloc(c, &c->res_partial, (int64_t)L * kResPartialRows * c->HDmax));
+        if (c->nWres) {
+            int64_t rg = 0;
+            c->res_gw_off.assign((size_t)L, 0);
+            for (int l = 0; l < L; ++l) {
+                GAT_TRY(dalloc(c, &c->layers[l].R, N * c->layers[l].HD));
+                c->res_gw_off[(size_t)l] = rg;
+                rg += grad_w_scratch_floats(N, c->layers[l].F, c->layers[l].HD);
+            }
+            GAT_TRY(dalloc(c, &c->res_gw_scratch, std::max<int64_t>(rg, 1)));
+        }
+        if (!c->drop_step) {                         // the forward's DROP instantiations read the step counter (nothing is dropped)
+            GAT_TRY(dalloc(c, &c->drop_step, 1));
+            GAT_HIP(hipMemsetAsync(c->drop_step, 0, sizeof(uint64_t), c->stream));
+            GAT_HIP(hipStreamSynchronize(c->stream));
+        }
+    }
     c->buffers_ready = true;
     GAT_TRY(ensure_drop_buffers(c));
     // The cliff of gatv2_abi.h "Limits": a layer whose SHAPE has wave-per-row kernels but whose gathered table is 4 GiB or
@@ -554,7 +589,7 @@ int gat_create(const gat_config* cfg, gat_ctx** out) {
     const int64_t np = c->nW + c->nA + c->nWo;
     GAT_TRY(dalloc(p, &p->params, np));
     GAT_TRY(dalloc(p, &p->grads, np + 4));
-    GAT_TRY(dalloc(p, &p->clip_scratch, 4));
+    GAT_TRY(dalloc(p, &p->clip_scratch, 8));
     GAT_HIP(hipMemsetAsync(p->params, 0, np * sizeof(float), p->stream));
     GAT_HIP(hipMemsetAsync(p->grads, 0, np * sizeof(float), p->stream));
     *out = c.release();
@@ -605,6 +640,7 @@ static int set_graph_common(gat_ctx* c, const int32_t* row_ptr, const int32_t* c
                             int64_t n_edges, int64_t n_table, int64_t table_row0, hipMemcpyKind kind) {
     if (!c || !row_ptr || (!col_idx && n_edges > 0)) return fail(GAT_E_INVALID, "gat_set_graph: null argument");
     if (c->have_graph) return fail(GAT_E_STATE, "gat_set_graph: graph already set (create a new context)");
+    c->params_touched = true;                        // from here on gat_set_residual is refused
     if (n_rows <= 0 || n_edges < 0) return fail(GAT_E_INVALID, "gat_set_graph: bad sizes");
     if (n_edges > 0x7fffffffLL || n_rows >= 0x7fffffffLL || n_table > 0x7fffffffLL)
         return fail(GAT_E_UNSUPPORTED, "gat_set_graph: int32 CSR limits (E:1045-1046) exceeded");
@@ -643,6 +679,7 @@ static int set_graph_coo_common(gat_ctx* c, const int32_t* src, const int32_t* d
                                 int64_t table_row0, int32_t flags, bool on_host) {
     if (!c || ((!src || !dst) && n_in > 0)) return fail(GAT_E_INVALID, "gat_set_graph_coo: null argument");
     if (c->have_graph) return fail(GAT_E_STATE, "gat_set_graph: graph already set (create a new context)");
+    c->params_touched = true;                        // from here on gat_set_residual is refused
     if (n_in < 0 || n_in > 0x7fffffffLL) return fail(n_in < 0 ? GAT_E_INVALID : GAT_E_UNSUPPORTED, "gat_set_graph_coo: edge count outside the 32-bit count of the sort");
     int32_t *d_src = nullptr, *d_dst = nullptr;
     if (on_host && n_in > 0) {
@@ -823,6 +860,8 @@ static int group_span(gat_ctx* c, int group, int64_t* off, int64_t* cnt) {
         case GAT_PARAM_W: *off = 0; *cnt = c->nW; return 0;
         case GAT_PARAM_A: *off = c->nW; *cnt = c->nA; return 0;
         case GAT_PARAM_WO: *off = c->nW + c->nA; *cnt = c->nWo; return 0;
+        case GAT_PARAM_WRES: *off = c->nW + c->nA + c->nWo; *cnt = c->nWres; return 0;
+        case GAT_PARAM_B: *off = c->nW + c->nA + c->nWo + c->nWres; *cnt = c->nB; return 0;
         default: return fail(GAT_E_INVALID, "unknown parameter group");
     }
 }
@@ -833,7 +872,9 @@ int gat_param_count(gat_ctx* c, int group, int64_t* count) {
 static int copy_group(gat_ctx* c, float* base, int group, float* host, int64_t count, bool to_device) {
     int64_t off, cnt;
     GAT_TRY(group_span(c, group, &off, &cnt));
-    if (count != cnt || !host) return fail(GAT_E_INVALID, "parameter group size mismatch");
+    c->params_touched = true;
+    if (count != cnt || (!host && cnt > 0)) return fail(GAT_E_INVALID, "parameter group size mismatch");
+    if (cnt == 0) return 0;                          // a residual group that is off
     if (to_device) GAT_HIP(hipMemcpyAsync(base + off, host, cnt * sizeof(float), hipMemcpyHostToDevice, c->stream));
     else GAT_HIP(hipMemcpyAsync(host, base + off, cnt * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     GAT_HIP(hipStreamSynchronize(c->stream));
@@ -857,13 +898,15 @@ int gat_grads_set(gat_ctx* c, int group, const float* host, int64_t count) {
 }
 int gat_grads_device(gat_ctx* c, void** d_ptr, int64_t* count) {
     if (!c || !d_ptr || !count) return fail(GAT_E_INVALID, "null argument");
-    *d_ptr = c->grads; *count = c->nW + c->nA + c->nWo;
+    c->params_touched = true;
+    *d_ptr = c->grads; *count = n_params(c);
     return 0;
 }
 
 int gat_grads_export(gat_ctx* c, void* d_dst, int64_t count) {
     if (!c || !d_dst) return fail(GAT_E_INVALID, "null argument");
-    if (count != c->nW + c->nA + c->nWo) return fail(GAT_E_INVALID, "packed gradient size mismatch");
+    c->params_touched = true;
+    if (count != n_params(c)) return fail(GAT_E_INVALID, "packed gradient size mismatch");
     GAT_HIP(hipMemcpyAsync(d_dst, c->grads, count * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     return 0;
 }
@@ -874,13 +917,15 @@ int gat_result_export(gat_ctx* c, void* d_dst3) {
 }
 int gat_grads_import(gat_ctx* c, const void* d_src, int64_t count) {
     if (!c || !d_src) return fail(GAT_E_INVALID, "null argument");
-    if (count != c->nW + c->nA + c->nWo) return fail(GAT_E_INVALID, "packed gradient size mismatch");
+    c->params_touched = true;
+    if (count != n_params(c)) return fail(GAT_E_INVALID, "packed gradient size mismatch");
     GAT_HIP(hipMemcpyAsync(c->grads, d_src, count * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     return 0;
 }
 
 int gat_params_init(gat_ctx* c, uint64_t seed) {
     if (!c) return fail(GAT_E_INVALID, "null context");
+    c->params_touched = true;
     // Same distribution as xavier_init_kernel_curand (E:205-242): U(-lim, lim] with lim = sqrt(6/(2F+D)) for the W rows
     // and a of a layer, sqrt(6/(C+D_L)) for W_o; own counter-based stream ON THE DEVICE, since the reference's cuRAND
     // XORWOW stream is seeded with time(NULL) (E:1305) and unreproducible.  Draw order: per layer W then a, then W_o.
@@ -897,6 +942,16 @@ int gat_params_init(gat_ctx* c, uint64_t seed) {
     }
     const float limo = sqrtf(6.0f / (float)(c->cfg.num_classes + c->layers.back().D));
     GAT_TRY(launch_xavier_init(c->params + c->nW + c->nA, c->nWo, s0, draw, limo, c->stream));
+    draw += (uint64_t)c->nWo;
+    if (c->nWres) {                                  // after every existing draw: W, a and Wo of a seed do not depend on the flag
+        for (int l = 0; l < c->cfg.num_layers; ++l) {
+            const Layer& y = c->layers[l];
+            const int64_t nr = (int64_t)y.HD * y.F;
+            GAT_TRY(launch_xavier_init(Wres_of(c, l), nr, s0, draw, sqrtf(6.0f / (float)(y.F + y.HD)), c->stream));
+            draw += (uint64_t)nr;
+        }
+    }
+    if (c->nB) GAT_HIP(hipMemsetAsync(b_of(c, 0), 0, (size_t)c->nB * sizeof(float), c->stream));
     GAT_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -923,6 +978,8 @@ int gat_layer_project(gat_ctx* c, int32_t l) {
     Layer& y = c->layers[l];
     Scope t(c, GAT_K_PROJECT);
     GAT_TRY(drop_prepare_input(c, l));
+    // residual: R = x' Wres^T over the shard's own rows (with replicated input: its own rows of the table) — the third projection
+    if (y.R != nullptr) GAT_TRY(launch_project_res(Xin_of(c, l), Wres_of(c, l), y.R, c->n_rows, y.F, y.HD, c->stream, ldX_of(c, l)));
     if (l == 0 && c->Xtab) {      // replicated input: whole PL table from the table rows, PR from the shard's rows
         GAT_TRY(launch_project(Xtab_of(c), W_of(c, l), y.PL, nullptr, c->n_table, y.F, y.HD, kPartLeft, bf16(c), c->gw_scratch, c->gw_scratch_floats, c->stream, c->ld0));
         return launch_project(Xin_of(c, 0), W_of(c, l), nullptr, y.PR, c->n_rows, y.F, y.HD, kPartRight, bf16(c), c->gw_scratch, c->gw_scratch_floats, c->stream, c->ld0);
@@ -945,9 +1002,13 @@ static DropArgs attn_drop_args(gat_ctx* c, int32_t l) {
 int gat_layer_forward_edges(gat_ctx* c, int32_t l) {
     GAT_TRY(check_layer(c, l));
     const EdgeFwdArgs a = plan_forward_edges(c, l);
-    const DropArgs d = attn_drop_args(c, l);
+    DropArgs d = attn_drop_args(c, l);
+    if (res_on(c) && !d.on) {                         // residual without a mask: the DROP instantiations with nothing dropped
+        d = drop_args(c, kDropAttn, l);
+        d.T = 0; d.scale = 1.f; d.on = 0;
+    }
     Scope t(c, GAT_K_EDGE_FWD);
-    return launch_edge_forward(a, c->stream, &d);
+    return launch_edge_forward(a, c->stream, &d, c->layers[l].R, b_of(c, l));
 }
 static EdgeFwdArgs plan_forward_edges(gat_ctx* c, int32_t l) {
     Layer& y = c->layers[l];
@@ -1008,6 +1069,9 @@ static int plan_backward_edges(gat_ctx* c, int32_t l, BwdPlan* P) {
     a.hpre = y.hpre; a.g = y.g; a.gPL = gPL_of(c, l); a.gPR = gPR_of(c, l); a.ge = y.ge; a.galpha = y.galpha;
     a.g_raw = l < c->cfg.num_layers - 1;           // hidden layers: written by launch_grad_x without the LReLU' factor
     a.gh = (l == c->cfg.num_layers - 1) ? c->gH : nullptr; a.gh_stride = c->gh_stride; a.hb_stride = 64;
+    if (res_on(c)) {                                // residual: G (complete) and the aggregate h_pre - (R + b), from res_backward_layer
+        a.g = c->resG; a.g_raw = 0; a.gh = nullptr; a.hpre = c->res_agg;
+    }
     a.pos = store ? c->csc_pos : nullptr; a.msg = store ? c->msg : nullptr;
     a.stash = stash ? c->stash : nullptr; a.gfull = stash ? c->gfull : nullptr; a.stash_spare = (uint32_t)c->n_edges;
     // last layer: the pull pass rebuilds g from gH and the decision bytes (GAT_PULL_LAST=0: gathers gfull like a hidden layer, A/B)
@@ -1048,11 +1112,28 @@ static int sum_backward_edges(gat_ctx* c, int32_t l, const BwdPlan& P) {
     }
     return 0;
 }
+// Residual layer, before its edge backward: G = dL/dh_pre and agg = h_pre - (R + b) into the context's two N-sized buffers, the
+// block column sums of G into the layer's region, and their fixed-order reduction into grad_b (queued in a ReduceBatch)
+static int res_backward_layer(gat_ctx* c, int32_t l) {
+    Layer& y = c->layers[l];
+    const bool last = l == c->cfg.num_layers - 1;
+    ResBwdArgs r{};
+    r.hpre = y.hpre; r.g = y.g; r.gh = (last && c->gH != nullptr) ? c->gH : nullptr; r.res = y.R; r.bias = b_of(c, l);
+    r.G = c->resG; r.agg = c->res_agg;
+    r.partial = c->nB ? c->res_partial + (int64_t)l * kResPartialRows * c->HDmax : nullptr;
+    r.n_rows = c->n_rows; r.H = y.H; r.D = y.D; r.gh_stride = c->gh_stride; r.g_raw = last ? 0 : 1;
+    r.blocks = res_backward_blocks(c->n_rows, y.HD); r.slope = c->cfg.negative_slope;
+    Scope t(c, GAT_K_MISC);
+    GAT_TRY(launch_res_backward(r, c->stream));
+    if (r.partial != nullptr) return launch_reduce_partials_add(r.partial, r.blocks, y.HD, gb_of(c, l), c->stream);
+    return 0;
+}
 int gat_layer_backward_edges(gat_ctx* c, int32_t l) {
     GAT_TRY(check_layer(c, l));
     Layer& y = c->layers[l];
     BwdPlan P;
     GAT_TRY(plan_backward_edges(c, l, &P));
+    if (res_on(c)) GAT_TRY(res_backward_layer(c, l));
     if (!P.store) {
         Scope t(c, GAT_K_MISC);
         GAT_HIP(hipMemsetAsync(gPL_of(c, l), 0, (size_t)c->n_table * y.HD * sizeof(float), c->stream));
@@ -1071,6 +1152,10 @@ static int backward_grad_w(gat_ctx* c, int32_t l, hipStream_t st) {
     Layer& y = c->layers[l];
     const float* gPL_rows = gPL_of(c, l) + c->table_row0 * y.HD;
     Scope t(c, GAT_K_GRAD_W, st);
+    // residual: gradWres += G^T x' over the shard's own rows (G: this layer's, still in place — the next res_backward_layer runs later
+    // on the same stream; the side stream of GAT_OVERLAP is not used with a residual context)
+    if (y.R != nullptr)
+        GAT_TRY(launch_grad_wres(c->resG, Xin_of(c, l), gWres_of(c, l), c->res_gw_scratch + c->res_gw_off[(size_t)l], c->n_rows, y.F, y.HD, st, ldX_of(c, l)));
     if (l == 0 && c->Xtab) {  // partial gPL over the whole table x replicated input; the gradient all-reduce sums shards
         GAT_TRY(launch_grad_w(gPL_of(c, l), nullptr, Xtab_of(c), gW_of(c, l), c->gw_scratch, c->n_table, y.F, y.HD, kPartLeft, st, c->ld0));
         return launch_grad_w(nullptr, gPR_of(c, l), Xin_of(c, 0), gW_of(c, l), c->gw_scratch, c->n_rows, y.F, y.HD, kPartRight, st, c->ld0);
@@ -1086,6 +1171,8 @@ static int backward_grad_x(gat_ctx* c, int32_t l) {
     // of layer l-1, which reads h_pre anyway (the epilogue's extra read of h_pre cost 0.45 of 1.03 ms)
     GAT_TRY(launch_grad_x(gPL_rows, gPR_of(c, l), W_of(c, l), nullptr, c->layers[l - 1].g, c->n_rows, y.F, y.HD,
                           c->cfg.negative_slope, c->stream));
+    // residual: + G Wres, before the feature-dropout factor and before the LReLU' factor of the layer below
+    if (y.R != nullptr) GAT_TRY(launch_grad_x_res(c->resG, Wres_of(c, l), c->layers[l - 1].g, c->n_rows, y.F, y.HD, c->stream));
     // feature dropout: dL/dx_l = dL/dx'_l (.) kappa s_f, before the LReLU' factor of layer l-1 (applied by its edge backward)
     if (feat_drop_on(c)) return launch_feat_drop_bwd(c->layers[l - 1].g, c->n_rows, y.F, drop_args(c, kDropFeat, l), c->stream);
     return 0;
@@ -1129,6 +1216,7 @@ static int forward_exchange_pipelined(gat_ctx* c, int l) {
     char* own_rows = reinterpret_cast<char*>(y.PL) + c->table_row0 * y.HD * st_bytes(c);
     Scope t(c, GAT_K_EXCHANGE);                                            // timed as a whole: projection chunks + their exchanges
     GAT_TRY(drop_prepare_input(c, l));
+    if (y.R != nullptr) GAT_TRY(launch_project_res(Xin_of(c, l), Wres_of(c, l), y.R, c->n_rows, y.F, y.HD, c->stream, ldX_of(c, l)));
     for (int k = 0; k < K; ++k) {
         const int64_t r0 = (int64_t)k * rpc, r1s = std::min<int64_t>(r0 + rpc, max_rows), r1 = std::min<int64_t>(r1s, c->n_rows);
         if (r0 >= max_rows) break;
@@ -1197,7 +1285,7 @@ static int head_step(gat_ctx* c, bool with_gh = true) {
 // of the forward's rows left in the caches when a pass's gathers exceed the Infinity Cache; fused per row, the second walk of
 // a row's sources comes a few microseconds after the first.
 static bool fused_last(gat_ctx* c) {
-    if (!fused_head(c) || bf16(c) || c->comm || c->n_table != c->n_rows || c->cfg.flat_lrelu_index) return false;
+    if (!fused_head(c) || bf16(c) || c->comm || c->n_table != c->n_rows || c->cfg.flat_lrelu_index || res_on(c)) return false;   // no residual form
     const Layer& y = c->layers.back();
     if (!edge_fast_path(y.H, y.D, c->n_table) || !y.stash || c->stash == nullptr || c->gH == nullptr) return false;
     if (!edge_last_fused_supported(y.H, y.D, c->cfg.num_classes) || c->dbg != 0 || drop_on(c)) return false;   // no dropout form
@@ -1265,7 +1353,7 @@ static int overlap_prepare(gat_ctx* c) {
     static const int env = [] { const char* e = choice_env("GAT_OVERLAP"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
     const int L = c->cfg.num_layers;
     const bool want = env == 1;
-    if (!want || L < 2 || c->gPL_bound || c->Xtab) return 0;
+    if (!want || L < 2 || c->gPL_bound || c->Xtab || res_on(c)) return 0;      // (residual: one G buffer, read by grad_w)
     if (!c->gPL_alt) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(c->stream, &cs);
@@ -1332,7 +1420,7 @@ static int backward_phases(gat_ctx* c, bool head_done = false, bool last_edges_d
 // tail of the packed gradient buffer -> host values (after an all-reduce the sums over shards)
 static int read_result_tail(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
     float t[3] = {0.f, 0.f, 0.f};
-    GAT_HIP(hipMemcpyAsync(t, c->grads + c->nW + c->nA + c->nWo, sizeof(t), hipMemcpyDeviceToHost, c->stream));
+    GAT_HIP(hipMemcpyAsync(t, c->grads + n_params(c), sizeof(t), hipMemcpyDeviceToHost, c->stream));
     GAT_HIP(hipStreamSynchronize(c->stream));
     if (loss_sum) *loss_sum = t[0];
     if (n_correct) *n_correct = (int32_t)(t[1] + 4096.0f * t[2] + 0.5f);
@@ -1344,7 +1432,7 @@ int gat_forward(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
     if (!c->comm) return gat_head_forward(c, loss_sum, n_correct);
     GAT_TRY(gat_head_forward(c, nullptr, nullptr));
     if (!loss_sum && !n_correct) return 0;
-    float* tail = c->grads + c->nW + c->nA + c->nWo;
+    float* tail = c->grads + n_params(c);
     GAT_TRY(launch_pack_result(c->loss_out, c->correct_out, tail, c->stream));
     {
         Scope t(c, GAT_K_EXCHANGE);
@@ -1358,7 +1446,7 @@ int gat_forward(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
 // without this, a second step before gat_zero_grad would reduce the earlier sums again (x world).
 static int reduce_begin(gat_ctx* c) {
     if (!c->comm) return 0;
-    const int64_t np = c->nW + c->nA + c->nWo;
+    const int64_t np = n_params(c);
     if (!c->grads_prev) GAT_TRY(dalloc(c, &c->grads_prev, np));
     Scope t(c, GAT_K_MISC);
     GAT_HIP(hipMemcpyAsync(c->grads_prev, c->grads, (size_t)np * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
@@ -1372,7 +1460,7 @@ static int reduce_end(gat_ctx* c, int64_t count) {          // count: n_params, 
         GAT_TRY(c->comm->all_reduce(c->grads, count, c->stream));
     }
     Scope t(c, GAT_K_MISC);
-    return launch_reduce_partials_add(c->grads_prev, 1, c->nW + c->nA + c->nWo, c->grads, c->stream);
+    return launch_reduce_partials_add(c->grads_prev, 1, n_params(c), c->grads, c->stream);
 }
 // Slab reductions of the backward (grad_Wo, grad_a and grad_W of every layer) and the result pack as one launch at the
 // end (ReduceBatch).  Not with replicated layer-0 input: its two grad_w launches share one slab region.  GAT_REDUCE_BATCH=0: A/B.
@@ -1385,7 +1473,7 @@ struct BatchScope {
     }
     // host_tail: pinned copy of the packed result written by the same kernel (*host_done = it was: no copy node needed)
     int finish(gat_ctx* c, bool pack, float* host_tail = nullptr, bool* host_done = nullptr) {
-        float* tail = c->grads + c->nW + c->nA + c->nWo;
+        float* tail = c->grads + n_params(c);
         if (host_done) *host_done = on && pack && host_tail != nullptr;
         if (!on) return pack ? launch_pack_result(c->loss_out, c->correct_out, tail, c->stream) : 0;
         on = false;
@@ -1403,7 +1491,7 @@ int gat_backward(gat_ctx* c) {
         GAT_TRY(backward_phases(c));
         GAT_TRY(batch.finish(c, false));
     }
-    return reduce_end(c, c->nW + c->nA + c->nWo);
+    return reduce_end(c, n_params(c));
 }
 // The whole step as ONE graph launch: small graphs (Cora / Pubmed / Arxiv shapes) are launch-bound — ~25
 // kernels of a few microseconds each — so the sequence is captured once from the context's stream and
@@ -1439,7 +1527,7 @@ static int step_body(gat_ctx* c, float* host_tail = nullptr, bool* host_done = n
     return batch.finish(c, true, host_tail, host_done);
 }
 static int step_graph(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
-    const int64_t np = c->nW + c->nA + c->nWo;
+    const int64_t np = n_params(c);
     if (c->graph_state == 1 && c->graph_warm == 0) {            // eager warm-up
         GAT_TRY(step_body(c));
         c->graph_warm = 1;
@@ -1478,6 +1566,35 @@ int gat_step_graph(gat_ctx* c, int32_t enable) {
     if (enable && c->cfg.collect_timing) return fail(GAT_E_UNSUPPORTED, "gat_step_graph: not with collect_timing (event pairs cannot be read back from a replay)");
     graph_drop(c);
     c->graph_state = enable ? 1 : 0;
+    return 0;
+}
+// ---- residual / bias --------------------------------------------------------------------------------------------
+int gat_set_residual(gat_ctx* c, int32_t flags) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (flags & ~(GAT_RES_LINEAR | GAT_RES_BIAS)) return fail(GAT_E_INVALID, "gat_set_residual: unknown flag bits");
+    if (c->params_touched)
+        return fail(GAT_E_STATE, "gat_set_residual: call it before the first gat_params_*, gat_grads_* or gat_set_graph* call (the packed buffers change size)");
+    if (flags == c->res_flags) return 0;                 // (0 on a fresh context: nothing is touched)
+#ifdef GAT_EXPERIMENTS                               // (the release library does not know the switch's name)
+    if (c->dbg != 0 && flags != 0)
+        return fail(GAT_E_UNSUPPORTED, "gat_set_residual: not with a GAT_DBG timing experiment (those kernels have no residual form)");
+#endif
+    int64_t wr = 0, bo = 0;
+    for (int l = 0; l < c->cfg.num_layers; ++l) {
+        Layer& y = c->layers[l];
+        y.wres_off = wr; y.b_off = bo;
+        if (flags & GAT_RES_LINEAR) wr += (int64_t)y.HD * y.F;
+        if (flags & GAT_RES_BIAS) bo += y.HD;
+    }
+    c->nWres = wr; c->nB = bo; c->res_flags = flags;
+    const int64_t np = n_params(c);                      // the packed buffers at their new size (nothing has read or written them yet)
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    dfree(c, c->params); dfree(c, c->grads);
+    c->params = nullptr; c->grads = nullptr;
+    GAT_TRY(dalloc(c, &c->params, np));
+    GAT_TRY(dalloc(c, &c->grads, np + 4));
+    GAT_HIP(hipMemsetAsync(c->params, 0, np * sizeof(float), c->stream));
+    GAT_HIP(hipMemsetAsync(c->grads, 0, np * sizeof(float), c->stream));
     return 0;
 }
 // ---- dropout ---------------------------------------------------------------------------------------------------
@@ -1557,7 +1674,7 @@ int gat_step(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
     if (c->graph_state != 0) return step_graph(c, loss_sum, n_correct);
     GAT_TRY(reduce_begin(c));
     GAT_TRY(step_body(c));                              // ends with the packed {loss, correct} behind the gradients
-    GAT_TRY(reduce_end(c, c->nW + c->nA + c->nWo + 3));
+    GAT_TRY(reduce_end(c, n_params(c) + 3));
     if (!loss_sum && !n_correct) return 0;
     return read_result_tail(c, loss_sum, n_correct);
 }
@@ -1625,7 +1742,7 @@ int gat_comm_halo_info(gat_ctx* c, int32_t* active, int64_t* rows_received, int6
 int gat_zero_grad(gat_ctx* c) {
     if (!c) return fail(GAT_E_INVALID, "null context");
     Scope t(c, GAT_K_MISC);
-    GAT_HIP(hipMemsetAsync(c->grads, 0, (size_t)(c->nW + c->nA + c->nWo) * sizeof(float), c->stream));
+    GAT_HIP(hipMemsetAsync(c->grads, 0, (size_t)n_params(c) * sizeof(float), c->stream));
     return 0;
 }
 int gat_clip(gat_ctx* c, float threshold) {
@@ -1633,18 +1750,22 @@ int gat_clip(gat_ctx* c, float threshold) {
     Scope t(c, GAT_K_MISC);
     GAT_TRY(launch_clip(c->grads, c->nW, threshold, c->clip_scratch, c->stream));
     GAT_TRY(launch_clip(c->grads + c->nW, c->nA, threshold, c->clip_scratch + 1, c->stream));
-    return launch_clip(c->grads + c->nW + c->nA, c->nWo, threshold, c->clip_scratch + 2, c->stream);
+    GAT_TRY(launch_clip(c->grads + c->nW + c->nA, c->nWo, threshold, c->clip_scratch + 2, c->stream));
+    // the residual groups: each clipped by its own norm, like the reference's three
+    if (c->nWres) GAT_TRY(launch_clip(c->grads + c->nW + c->nA + c->nWo, c->nWres, threshold, c->clip_scratch + 3, c->stream));
+    if (c->nB) GAT_TRY(launch_clip(c->grads + c->nW + c->nA + c->nWo + c->nWres, c->nB, threshold, c->clip_scratch + 4, c->stream));
+    return 0;
 }
 int gat_step_sgd(gat_ctx* c, float lr) {
     if (!c) return fail(GAT_E_INVALID, "null context");
     Scope t(c, GAT_K_MISC);
-    return launch_sgd(c->params, c->grads, lr, c->nW + c->nA + c->nWo, c->stream);
+    return launch_sgd(c->params, c->grads, lr, n_params(c), c->stream);
 }
 int gat_step_adam(gat_ctx* c, float lr, float b1, float b2, float eps, int32_t t_) {
     if (!c) return fail(GAT_E_INVALID, "null context");
     if (!(b1 > 0.f && b1 < 1.f && b2 > 0.f && b2 < 1.f))
         return fail(GAT_E_INVALID, "For Adam optimizer, beta1 and beta2 must be in (0,1).");
-    const int64_t np = c->nW + c->nA + c->nWo;
+    const int64_t np = n_params(c);
     if (!c->adam_m) {
         GAT_TRY(dalloc(c, &c->adam_m, np));
         GAT_TRY(dalloc(c, &c->adam_v, np));
@@ -1997,6 +2118,26 @@ int gat_request_bytes_shape(const gat_config* cfg, int64_t n_rows, int64_t n_edg
 }
 int gat_algorithmic_bytes(gat_ctx* c, double* bytes_step, double* per_kernel) {
     if (!c || !c->have_graph) return fail(GAT_E_STATE, "graph not set");
+    if (res_on(c)) {
+        // residual (gatv2_abi.h "residual"): the N-sized traffic it adds, fp32 throughout — R written, read by the edge forward and by
+        // the N-sized backward kernel; that kernel's h_pre and g read, G and agg written; G, x' and Wres in the two dense terms
+        double k[GAT_K_COUNT] = {0}, tot = 0;
+        GAT_TRY(gat_algorithmic_bytes_shape(&c->cfg, c->n_rows, c->n_edges, c->n_table, c->Xtab != nullptr, nullptr, k));
+        const double N = (double)c->n_rows;
+        for (int l = 0; l < c->cfg.num_layers; ++l) {
+            const double HD = c->layers[l].HD, F = c->layers[l].F;
+            const bool lin = (c->res_flags & GAT_RES_LINEAR) != 0;
+            k[GAT_K_MISC] += 4.0 * N * HD * (lin ? 5 : 4);
+            if (!lin) continue;
+            k[GAT_K_PROJECT] += 4.0 * (N * HD + HD * F + N * F);
+            k[GAT_K_EDGE_FWD] += 4.0 * N * HD;
+            k[GAT_K_GRAD_W] += 4.0 * (N * HD + N * F + HD * F);
+            if (l > 0) k[GAT_K_GRAD_X] += 4.0 * (N * HD + 2 * N * F + HD * F);
+        }
+        for (int i = 0; i < GAT_K_COUNT; ++i) { tot += k[i]; if (per_kernel) per_kernel[i] = k[i]; }
+        if (bytes_step) *bytes_step = tot;
+        return 0;
+    }
     GAT_TRY(gat_algorithmic_bytes_shape(&c->cfg, c->n_rows, c->n_edges, c->n_table, c->Xtab != nullptr, bytes_step, per_kernel));
     if (per_kernel && c->buffers_ready && fused_last(c)) {
         // gat_step runs the last layer's forward and backward edge passes (and forms gH) in ONE kernel class: its share of

@@ -511,9 +511,106 @@ __global__ __launch_bounds__(256) void clip_scale_kernel(float* g, int64_t n, co
     if (i < n) g[i] *= scale;
 }
 
+// ---- residual / bias backward (gatv2_abi.h "residual"): one pass over the N x HD tensors of a layer -----------------------------
+// G = dL/dh_pre (fp32), agg = h_pre - (R + b), and the block's column sums of G for grad_b.  A block is rpb rows of LPR lanes, a
+// lane owns V consecutive channels of ITS column group for every row it visits (rows blockIdx*rpb + r_in, stride gridDim*rpb), so
+// its running sum is a fixed-order sum over rows; the block then adds its rpb row lanes in ascending order: partial[block][c] is
+// bitwise reproducible, and the sum over blocks is finished by the fixed-order slab reduction.  V = 4: 16-byte loads and stores.
+template <int V>
+__global__ __launch_bounds__(256) void res_backward_kernel(ResBwdArgs A, int32_t LPR, int32_t rpb) {
+    __shared__ float red[256 * 4];
+    const int HD = A.H * A.D;
+    const int t = threadIdx.x;
+    const int r_in = t / LPR, cl = t % LPR;
+    const float inv_heads = 1.0f / (float)A.H;
+    for (int base = 0; base < HD; base += LPR * V) {     // one round unless H*D exceeds what 256 lanes cover (generic shapes only);
+        const int c0 = base + cl * V;                    // the round count is the same for every lane (barriers below)
+        const bool active = r_in < rpb && c0 < HD;
+        float sum[V];
+        float bv[V];
+#pragma unroll
+        for (int i = 0; i < V; ++i) { sum[i] = 0.f; bv[i] = (active && A.bias != nullptr) ? A.bias[c0 + i] : 0.f; }
+        if (active) {
+            for (int64_t row = (int64_t)blockIdx.x * rpb + r_in; row < A.n_rows; row += (int64_t)gridDim.x * rpb) {
+                const int64_t o = row * HD + c0;
+                float hp[V], gv[V], rv[V];
+                if constexpr (V == 4) {
+                    const float4 h4 = *reinterpret_cast<const float4*>(A.hpre + o);
+                    hp[0] = h4.x; hp[1] = h4.y; hp[2] = h4.z; hp[3] = h4.w;
+                    float4 r4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (A.res != nullptr) r4 = *reinterpret_cast<const float4*>(A.res + o);
+                    rv[0] = r4.x; rv[1] = r4.y; rv[2] = r4.z; rv[3] = r4.w;
+                    if (A.gh == nullptr) {
+                        const float4 g4 = *reinterpret_cast<const float4*>(A.g + o);
+                        gv[0] = g4.x; gv[1] = g4.y; gv[2] = g4.z; gv[3] = g4.w;
+                    }
+                } else {
+                    hp[0] = A.hpre[o];
+                    rv[0] = A.res != nullptr ? A.res[o] : 0.f;
+                    if (A.gh == nullptr) gv[0] = A.g[o];
+                }
+                float G[V], ag[V];
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    const float d = hp[i] > 0.f ? 1.0f : A.slope;
+                    if (A.gh != nullptr) G[i] = A.gh[row * A.gh_stride + (c0 + i) % A.D] * d * inv_heads;     // E:598-603
+                    else G[i] = A.g_raw ? gv[i] * d : gv[i];                                               // E:888-892
+                    ag[i] = hp[i] - (rv[i] + bv[i]);
+                    sum[i] += G[i];
+                }
+                if constexpr (V == 4) {
+                    *reinterpret_cast<float4*>(A.G + o) = make_float4(G[0], G[1], G[2], G[3]);
+                    *reinterpret_cast<float4*>(A.agg + o) = make_float4(ag[0], ag[1], ag[2], ag[3]);
+                } else {
+                    A.G[o] = G[0];
+                    A.agg[o] = ag[0];
+                }
+            }
+        }
+        if (A.partial != nullptr) {                       // (uniform per block: every lane reaches the barriers)
+#pragma unroll
+            for (int i = 0; i < V; ++i) red[t * V + i] = sum[i];
+            __syncthreads();
+            if (r_in == 0 && c0 < HD) {
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    float tot = 0.f;
+                    for (int r = 0; r < rpb; ++r) tot += red[(r * LPR + cl) * V + i];
+                    A.partial[(int64_t)blockIdx.x * HD + c0 + i] = tot;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
 }  // namespace
 
 // ---- launchers -----------------------------------------------------------------------------------------------------
+static void res_backward_shape(int32_t HD, int* V, int* LPR, int* rpb) {
+    *V = HD % 4 == 0 ? 4 : 1;
+    const int groups = HD / *V;                          // column groups of a row
+    *LPR = groups < 256 ? groups : 256;
+    *rpb = 256 / *LPR;
+}
+int res_backward_blocks(int64_t n_rows, int32_t HD) {
+    int V, LPR, rpb;
+    res_backward_shape(HD, &V, &LPR, &rpb);
+    const void* fn = V == 4 ? (const void*)res_backward_kernel<4> : (const void*)res_backward_kernel<1>;
+    const int64_t want = std::max<int64_t>(1, (n_rows + rpb - 1) / rpb);
+    return (int)std::min({want, resident_blocks(fn, 0), (int64_t)kResPartialRows});
+}
+int launch_res_backward(const ResBwdArgs& a, hipStream_t s) {
+    if (a.n_rows <= 0) return 0;
+    if (a.blocks < 1 || a.blocks > kResPartialRows) return fail(GAT_E_INVALID, "res_backward: blocks must come from res_backward_blocks()");
+    if (a.gh == nullptr && a.g == nullptr) return fail(GAT_E_INVALID, "res_backward: no output gradient");
+    int V, LPR, rpb;
+    res_backward_shape(a.H * a.D, &V, &LPR, &rpb);
+    if (V == 4) hipLaunchKernelGGL(res_backward_kernel<4>, dim3((unsigned)a.blocks), dim3(256), 0, s, a, LPR, rpb);
+    else hipLaunchKernelGGL(res_backward_kernel<1>, dim3((unsigned)a.blocks), dim3(256), 0, s, a, LPR, rpb);
+    GAT_HIP(hipGetLastError());
+    return 0;
+}
 static thread_local ReduceBatch t_batch;
 static thread_local bool t_batch_on = false;
 void reduce_batch_begin() { t_batch = ReduceBatch{}; t_batch_on = true; }

@@ -146,12 +146,14 @@ __global__ __launch_bounds__(256) void csr_to_coo_kernel(const int32_t* __restri
 // group are issued back to back before any is consumed.  Scores are kept in the log2 domain
 // (a pre-scaled by log2 e) so that every softmax term is one v_exp_f32.
 // ------------------------------------------------------------------------------------------------
-template <int HD, int D>
+// RES: the residual term rs = R[row][c] + b[c] (gatv2_abi.h "residual") joins h_pre here, before anything is written
+template <int HD, int D, bool RES = false>
 __device__ __forceinline__ void fwd_write_row(const EdgeFwdArgs& A, int64_t row, int lane, float m2, float Z,
-                                              float acc) {
+                                              float acc, [[maybe_unused]] float rs = 0.f) {
     constexpr int H = HD / D;
     const int c = lane % HD, gidx = lane / HD;
-    const float hp = acc * __builtin_amdgcn_rcpf(Z + 1e-8f);     // E:379 epsilon
+    float hp = acc * __builtin_amdgcn_rcpf(Z + 1e-8f);           // E:379 epsilon
+    if constexpr (RES) hp += rs;
     if (gidx == 0) {
         A.hpre[row * HD + c] = hp;
         if ((c % D) == 0) {                          // softmax stats, log2 domain: the backward
@@ -237,6 +239,14 @@ __device__ __forceinline__ void store_row(float* __restrict__ msg, int slot, int
 
 // One chunk of UU slots per edge group: UU independent gathers issued back to back (indices
 // clamped into the item, so loads need no predicate), then scores, then the online-softmax update.
+// R[row][c] + b[c] of the lane's channel(s), 0 where a pointer is null (the DROP instantiations' argument struct carries them)
+__device__ __forceinline__ float res_term(const EdgeFwdDropArgs& A, int64_t row, int HD, int c) {
+    float r = 0.f;
+    if (A.res != nullptr) r = A.res[row * HD + c];
+    if (A.bias != nullptr) r += A.bias[c];
+    return r;
+}
+
 template <int HD, int D, int UU, int USC, bool ALPHA, bool BF, bool DROP = false, class AT = EdgeFwdArgs>
 __device__ __forceinline__ void fwd_chunk(const AT& A, int e0, int e_end, int e_end_v, int c, int gidx,
                                           float pr, float ac2, bool multi, float (&sc)[USC], float& m, float& Z,
@@ -320,7 +330,8 @@ __global__ __launch_bounds__(256) void edge_fwd_kernel(FwdArgsT<DROP> A) {
     uint32_t kd = 0;
     int rb = 0;
     uint32_t ke = 0;
-    if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; ke = edge_row_key(A.drop, row); }
+    [[maybe_unused]] float rs = 0.f;
+    if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; ke = edge_row_key(A.drop, row); if (!split) rs = res_term(A, row, HD, c); }
 
     for (int e0 = b; e0 < e_end; e0 += CH) {
         if constexpr (U >= 2) {
@@ -367,13 +378,14 @@ __global__ __launch_bounds__(256) void edge_fwd_kernel(FwdArgsT<DROP> A) {
         fwd_normalize_slice<HD, D>(A, b, e_end, lane, m, inv);
     }
     }
-    fwd_write_row<HD, D>(A, row, lane, m, Z, acc);
+    fwd_write_row<HD, D, DROP>(A, row, lane, m, Z, acc, rs);
 }
 
 // Split rows: one wave per segment merges ALL partials of its row (L2-hot, <= a few hundred
 // bytes each), normalises its own alpha slice, and the row's first segment writes the outputs.
-template <int HD, int D, bool ALPHA>
-__global__ __launch_bounds__(256) void edge_fwd_fix_kernel(EdgeFwdArgs A) {
+// RES: the residual form (argument struct of the DROP instantiations): the row's R + b joins the combined sum once, here
+template <int HD, int D, bool ALPHA, bool RES = false>
+__global__ __launch_bounds__(256) void edge_fwd_fix_kernel(FwdArgsT<RES> A) {
     constexpr int H = HD / D;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -413,7 +425,8 @@ __global__ __launch_bounds__(256) void edge_fwd_fix_kernel(EdgeFwdArgs A) {
     for (; sg < s_end; ++sg)
         merge(A.part_mz[(int64_t)sg * 2 * H + c / D], A.part_mz[(int64_t)sg * 2 * H + H + c / D], A.part_acc[(int64_t)sg * HD + c]);
     if constexpr (ALPHA) fwd_normalize_slice<HD, D>(A, item.y, item.z, lane, m, __builtin_amdgcn_rcpf(Z + 1e-8f));
-    if (slot == info.y) fwd_write_row<HD, D>(A, info.x, lane, m, Z, acc);
+    if constexpr (RES) { if (slot == info.y) fwd_write_row<HD, D, true>(A, info.x, lane, m, Z, acc, res_term(A, info.x, HD, c)); }
+    else if (slot == info.y) fwd_write_row<HD, D>(A, info.x, lane, m, Z, acc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -648,6 +661,15 @@ __device__ __forceinline__ void store_row_n(float* __restrict__ msg, int slot, i
 // Forward edge pass in the packed layout (training path: alpha not materialised).  Same online softmax as
 // fwd_chunk; partials of split rows go to the same [slot][HD] / [slot][2H] arrays, so edge_fwd_fix_kernel
 // finishes them unchanged.
+// the N-channel form of res_term: 8- / 16-byte loads (c is a multiple of N, H*D too)
+template <int N>
+__device__ __forceinline__ vnf<N> res_term_n(const EdgeFwdDropArgs& A, int64_t row, int HD, int c) {
+    vnf<N> r = vzero<N>();
+    if (A.res != nullptr) r = *reinterpret_cast<const vnf<N>*>(A.res + row * HD + c);
+    if (A.bias != nullptr) r += *reinterpret_cast<const vnf<N>*>(A.bias + c);
+    return r;
+}
+
 template <int HD, int D, int N, int UU, bool BF, bool DROP = false, class AT = EdgeFwdArgs>
 __device__ __forceinline__ void fwd2_chunk(const AT& A, int e0, int e_end_v, int cp, int gidx, int srcv,
                                            vnf<N> pr, vnf<N> ac2, float& m, float& Z, vnf<N>& acc, uint32_t kd = 0, int rb = 0,
@@ -749,7 +771,8 @@ __global__ __launch_bounds__(256) void edge_fwd2_kernel(FwdArgsT<DROP> A) {
         }
         return;
     }
-    const vnf<N> hp = acc * __builtin_amdgcn_rcpf(Z + 1e-8f);    // E:379 epsilon
+    vnf<N> hp = acc * __builtin_amdgcn_rcpf(Z + 1e-8f);          // E:379 epsilon
+    if constexpr (DROP) hp += res_term_n<N>(A, row, HD, c);      // residual / bias: before h_pre and hout are written
     if (gidx == 0) {
         *reinterpret_cast<vnf<N>*>(A.hpre + row * HD + c) = hp;
         if ((c % D) == 0) { A.mstat[row * H + c / D] = m; A.zstat[row * H + c / D] = Z; }
@@ -858,7 +881,8 @@ __global__ __launch_bounds__(256) void edge_fwd3_kernel(FwdArgsT<DROP> A) {
         }
         return;
     }
-    const vnf<N> hp = acc * __builtin_amdgcn_rcpf(Z + 1e-8f);    // E:379 epsilon
+    vnf<N> hp = acc * __builtin_amdgcn_rcpf(Z + 1e-8f);          // E:379 epsilon
+    if constexpr (DROP) hp += res_term_n<N>(A, row, HD, c);      // residual / bias: before h_pre and hout are written
     stream_store(reinterpret_cast<vnf<N>*>(A.hpre + (int64_t)row * HD + c), hp);
     if ((c % D) == 0) { A.mstat[(int64_t)row * H + c / D] = m; A.zstat[(int64_t)row * H + c / D] = Z; }
     const vnf<N> act = lrelu_n<N>(hp, A.slope);
@@ -1774,7 +1798,10 @@ __global__ __launch_bounds__(256) void edge_bwd_fix_kernel(const int4* __restric
 // fast path; same math, literal alpha-weighted sums in ascending edge order.
 // dynamic LDS: forward  act[HD];  backward dot[H] ge[H] al[H] ga[HD] gpr[HD]
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void edge_fwd_generic(EdgeFwdArgs A, DropArgs dr) {
+// RES: res / bias (either may be null) join the row's sum before h_pre is written (gatv2_abi.h "residual")
+template <bool RES>
+__device__ __forceinline__ void edge_fwd_generic_body(const EdgeFwdArgs& A, const DropArgs& dr, [[maybe_unused]] const float* __restrict__ res,
+                                                      [[maybe_unused]] const float* __restrict__ bias) {
     extern __shared__ float lds[];
     const int H = A.H, D = A.D, HD = H * D;
     const int lane = threadIdx.x;
@@ -1821,6 +1848,10 @@ __global__ __launch_bounds__(64) void edge_fwd_generic(EdgeFwdArgs A, DropArgs d
                 if (dr.on) w *= attn_keep(dr, kd, e - b, ch / D);   // attention dropout: the term, not alpha
                 acc += w * A.PL[sid * HD + ch];
             }
+            if constexpr (RES) {
+                if (res != nullptr) acc += res[row * HD + ch];
+                if (bias != nullptr) acc += bias[ch];
+            }
             A.hpre[row * HD + ch] = acc;
             const float act = lrelu(acc, slope);
             if (!A.is_last) A.hout[row * HD + ch] = act; else lds[ch] = act;
@@ -1835,6 +1866,10 @@ __global__ __launch_bounds__(64) void edge_fwd_generic(EdgeFwdArgs A, DropArgs d
         }
         __syncthreads();
     }
+}
+__global__ __launch_bounds__(64) void edge_fwd_generic(EdgeFwdArgs A, DropArgs dr) { edge_fwd_generic_body<false>(A, dr, nullptr, nullptr); }
+__global__ __launch_bounds__(64) void edge_fwd_generic_res(EdgeFwdArgs A, DropArgs dr, const float* res, const float* bias) {
+    edge_fwd_generic_body<true>(A, dr, res, bias);
 }
 
 __global__ __launch_bounds__(64) void edge_bwd_generic(EdgeBwdArgs A, DropArgs dr) {
@@ -1978,16 +2013,18 @@ struct EdgePick {
 // block — the parity-tap form with alpha, else the group-per-row kernel where the shape has one, else the packed wave-per-row
 // kernel.  The A/B switches of the default path (GAT_ROWGROUP, GAT_PACKED, GAT_CPL, GAT_FWD_WAVES) do not apply to it: only these
 // instantiations exist.
+// res: a residual / bias context — always with drop (the DROP instantiations' argument struct carries the pointers); its fix-up kernel
+// is the RES form, which takes that struct too.
 template <int HD, int D, bool BF>
-EdgePick pick_fwd(const EdgeFwdArgs& a, bool drop) {
+EdgePick pick_fwd(const EdgeFwdArgs& a, bool drop, bool res) {
     static_assert(D % 2 == 0, "every fast-path shape has an even D");
     constexpr int N3 = stash_n<HD, D>(), N2 = (HD >= 32 && D % 4 == 0) ? 4 : 2;
     constexpr int G3 = N3 != 0 ? 64 / (HD / (N3 != 0 ? N3 : 1)) : 1;             // rows per wave of the group-per-row kernel
     if (a.alpha != nullptr) {                                                     // parity-tap form: alpha (and scores) materialised
-        const void* fix = GAT_K(edge_fwd_fix_kernel<HD, D, true>);
+        const void* fix = res ? GAT_K(edge_fwd_fix_kernel<HD, D, true, true>) : GAT_K(edge_fwd_fix_kernel<HD, D, true>);
         return {drop ? GAT_K(edge_fwd_kernel<HD, D, true, BF, true>) : GAT_K(edge_fwd_kernel<HD, D, true, BF>), 256, 4, fix};
     }
-    const void* fix = GAT_K(edge_fwd_fix_kernel<HD, D, false>);
+    const void* fix = res ? GAT_K(edge_fwd_fix_kernel<HD, D, false, true>) : GAT_K(edge_fwd_fix_kernel<HD, D, false>);
     if (drop) {
         if constexpr (N3 != 0) return {GAT_K(edge_fwd3_kernel<HD, D, N3, BF, true>), 64, G3, fix};
         else return {GAT_K(edge_fwd2_kernel<HD, D, N2, BF, true>), 64, 1, fix};
@@ -2077,8 +2114,8 @@ EdgePick pick_bwd(const EdgeBwdArgs& a, bool drop, int dbg) {
 #define GAT_SHAPE_CASE(hd, d, FN, BF, ...) case hd * 1000 + d: return (BF) ? FN<hd, d, true>(__VA_ARGS__) : FN<hd, d, false>(__VA_ARGS__);
 #define GAT_DISPATCH_HD_D(HD, D, FN, BF, ...) \
     switch ((HD) * 1000 + (D)) { GAT_EDGE_SHAPES(GAT_SHAPE_CASE, FN, BF, __VA_ARGS__) default: break; }
-static EdgePick pick_forward(const EdgeFwdArgs& a, bool drop) {
-    GAT_DISPATCH_HD_D(a.H * a.D, a.D, pick_fwd, a.bf16 != 0, a, drop)
+static EdgePick pick_forward(const EdgeFwdArgs& a, bool drop, bool res) {
+    GAT_DISPATCH_HD_D(a.H * a.D, a.D, pick_fwd, a.bf16 != 0, a, drop, res)
     return {};
 }
 static EdgePick pick_backward(const EdgeBwdArgs& a, bool drop, int dbg) {
@@ -2106,10 +2143,11 @@ static int resident_blocks(const void* fn, unsigned block) {
 }
 
 // the split rows' partial sums -> their rows (after either forward kernel)
-static int launch_fwd_fix(const EdgePick& p, const EdgeFwdArgs& a, hipStream_t s) {
+// arg: the kernel's argument struct (EdgeFwdArgs, or EdgeFwdDropArgs for the RES form)
+static int launch_fwd_fix(const EdgePick& p, const EdgeFwdArgs& a, void* arg, hipStream_t s) {
     if (a.n_slots <= 0) return 0;
     const int64_t n = a.alpha != nullptr ? a.n_slots : a.n_split;                 // per segment with alpha, else per split row
-    void* args[] = {const_cast<EdgeFwdArgs*>(&a)};
+    void* args[] = {arg};
     GAT_HIP(hipLaunchKernel(p.fix, dim3((unsigned)((n + 3) / 4)), dim3(256), args, 0, s));
     return 0;
 }
@@ -2135,22 +2173,28 @@ int edge_stash_words(int32_t H, int32_t D) {
     return n ? H * D / n : 0;
 }
 
-int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const DropArgs* drop) {
+int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const DropArgs* drop, const float* res, const float* bias) {
     if (a.n_rows <= 0) return 0;
-    const DropArgs dr = drop != nullptr ? *drop : DropArgs{};
+    DropArgs dr = drop != nullptr ? *drop : DropArgs{};
+    const bool with_res = res != nullptr || bias != nullptr;
     if (edge_fast_path(a.H, a.D, a.n_table)) {
         if (a.items == nullptr) return fail(GAT_E_INVALID, "edge_forward: work-item list missing");
         if (a.mstat == nullptr || a.zstat == nullptr) return fail(GAT_E_INVALID, "edge_forward: stats buffers missing");
-        const EdgePick p = pick_forward(a, dr.on != 0);
+        if (with_res && !dr.on) {                        // the DROP instantiations with nothing dropped: T = Te = 0 keeps every draw, scale 1
+            if (dr.step == nullptr) return fail(GAT_E_INVALID, "edge_forward: the residual form needs the step counter of the mask arguments");
+            dr.on = 1; dr.T = 0; dr.Te = 0; dr.scale = 1.f; dr.eflags = 0;
+        }
+        const EdgePick p = pick_forward(a, dr.on != 0, with_res);
         EdgeFwdDropArgs ad;                              // the argument struct of the DROP instantiations
-        if (dr.on) { static_cast<EdgeFwdArgs&>(ad) = a; ad.drop = dr; }
+        if (dr.on) { static_cast<EdgeFwdArgs&>(ad) = a; ad.drop = dr; ad.res = res; ad.bias = bias; }
         void* args[] = {dr.on ? (void*)&ad : (void*)const_cast<EdgeFwdArgs*>(&a)};
         GAT_HIP(hipLaunchKernel(p.fn, dim3((unsigned)((a.n_items + p.per_block - 1) / p.per_block)), dim3(p.block), args, 0, s));
-        return launch_fwd_fix(p, a, s);
+        return launch_fwd_fix(p, a, with_res ? (void*)&ad : (void*)const_cast<EdgeFwdArgs*>(&a), s);
     }
     const int HD = a.H * a.D;
     const int64_t blocks = a.n_rows < kGenericBlocks * 8 ? a.n_rows : kGenericBlocks * 8;
-    hipLaunchKernelGGL(edge_fwd_generic, dim3((unsigned)blocks), dim3(64), (size_t)HD * sizeof(float), s, a, dr);
+    if (with_res) hipLaunchKernelGGL(edge_fwd_generic_res, dim3((unsigned)blocks), dim3(64), (size_t)HD * sizeof(float), s, a, dr, res, bias);
+    else hipLaunchKernelGGL(edge_fwd_generic, dim3((unsigned)blocks), dim3(64), (size_t)HD * sizeof(float), s, a, dr);
     GAT_HIP(hipGetLastError());
     return 0;
 }

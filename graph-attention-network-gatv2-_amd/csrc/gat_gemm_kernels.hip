@@ -64,6 +64,17 @@ struct BSrcGradX {                // B(k=c, j=f): c < HD ? W[c][f] : W[c-HD][F+f
     }
     static constexpr bool kAlongK = false;
 };
+// residual weight Wres [HD][F] (gatv2_abi.h "residual"): its projection reads it as B(k=f, j) = Wres[j][k0+f], its grad_x as B(k=c, j=f) = Wres[c][f]
+struct BSrcResProject {
+    const float* W; int32_t F;
+    __device__ __forceinline__ float at(int k, int j) const { return W[(int64_t)j * F + k]; }
+    static constexpr bool kAlongK = true;
+};
+struct BSrcResGradX {
+    const float* W; int32_t F;
+    __device__ __forceinline__ float at(int k, int j) const { return W[(int64_t)k * F + j]; }
+    static constexpr bool kAlongK = false;
+};
 // ---- epilogues ---------------------------------------------------------------------------------------
 template <bool BF>
 struct EpiProject {               // cols j0+j < HD -> PL rows (bf16 rows when BF: round to nearest even), else PR
@@ -103,6 +114,14 @@ struct EpiStore {                 // out[i][j] = v
     __device__ __forceinline__ float pre(int64_t, int) const { return 0.f; }
     __device__ __forceinline__ void apply(int64_t i, int j, float v, float) const { out[i * ld + j] = v; }
     __device__ __forceinline__ void operator()(int64_t i, int j, float v) const { out[i * ld + j] = v; }
+};
+
+struct EpiAccum {                 // out[i][j] += v   (two-phase like EpiGradX: the tile's old values are loaded first, then all stores)
+    static constexpr bool kTwoPhase = true;
+    float* out; int32_t ld;
+    __device__ __forceinline__ float pre(int64_t i, int j) const { return out[i * ld + j]; }
+    __device__ __forceinline__ void apply(int64_t i, int j, float v, float old) const { out[i * ld + j] = old + v; }
+    __device__ __forceinline__ void operator()(int64_t i, int j, float v) const { apply(i, j, v, pre(i, j)); }
 };
 
 constexpr int kKC = 128;          // K chunk resident in LDS
@@ -1169,9 +1188,9 @@ int64_t grad_w_scratch_floats(int64_t n_rows, int32_t F, int32_t HD) {
     return need;
 }
 
-int launch_grad_w(const float* gPL_rows, const float* gPR, const float* X, float* gradW, float* scratch,
-                  int64_t n_rows, int32_t F, int32_t HD, int32_t part, hipStream_t s, int32_t ldx) {
-    if (n_rows <= 0) return 0;
+// the slabs of launch_grad_w (scratch [ksplit][M][F]); *ksplit_out = their number
+static int grad_w_slabs(const float* gPL_rows, const float* gPR, const float* X, float* scratch, int64_t n_rows, int32_t F, int32_t HD,
+                        int32_t part, hipStream_t s, int32_t ldx, int32_t* ksplit_out) {
     if (ldx < F) ldx = F;
     const int M = part == kPartBoth ? 2 * HD : HD;
     const int c_base = part == kPartRight ? HD : 0;
@@ -1193,7 +1212,48 @@ int launch_grad_w(const float* gPL_rows, const float* gPR, const float* X, float
     else { if (bm == 128 && bn == 64) GAT_GRADW(false, 2, 64); else if (bm == 128) GAT_GRADW(false, 2, 128); else GAT_GRADW(false, 1, 128); }
 #undef GAT_GRADW
     GAT_HIP(hipGetLastError());
-    return launch_reduce_gradw(scratch, (int32_t)ksplit, HD, F, c_base, M, gradW, s);
+    *ksplit_out = (int32_t)ksplit;
+    return 0;
+}
+int launch_grad_w(const float* gPL_rows, const float* gPR, const float* X, float* gradW, float* scratch,
+                  int64_t n_rows, int32_t F, int32_t HD, int32_t part, hipStream_t s, int32_t ldx) {
+    if (n_rows <= 0) return 0;
+    int32_t ksplit = 0;
+    GAT_TRY(grad_w_slabs(gPL_rows, gPR, X, scratch, n_rows, F, HD, part, s, ldx, &ksplit));
+    return launch_reduce_gradw(scratch, ksplit, HD, F, part == kPartRight ? HD : 0, part == kPartBoth ? 2 * HD : HD, gradW, s);
+}
+
+// ---- residual / bias (gatv2_abi.h "residual") ----------------------------------------------------------------------
+// R = X Wres^T with the three-piece product of the projections.  The row-streaming kernel keeps all of K in LDS up to K = 128:
+// a longer K is walked in chunks of 128 columns of X, the first storing, the others adding into R (fixed order).
+int launch_project_res(const float* X, const float* Wres, float* R, int64_t n_rows, int32_t F, int32_t HD, hipStream_t s, int32_t ldx) {
+    if (ldx < F) ldx = F;
+    const bool vec4 = (ldx % 4 == 0) && aligned16(X);
+    for (int32_t k0 = 0; k0 < F; k0 += kKC) {
+        const int32_t kc = F - k0 < kKC ? F - k0 : kKC;
+        ASrcRows as{X + k0, ldx};
+        BSrcResProject bs{Wres + k0, F};
+        if (k0 == 0) GAT_TRY(run_rowgemm(as, bs, EpiStore{R, HD}, n_rows, HD, kc, vec4, s));
+        else GAT_TRY(run_rowgemm(as, bs, EpiAccum{R, HD}, n_rows, HD, kc, vec4, s));
+    }
+    return 0;
+}
+// gradWres += G^T X: the grad_w kernels on the left half alone (slabs [ksplit][HD][F] are already in Wres's layout)
+int launch_grad_wres(const float* G, const float* X, float* gradWres, float* scratch, int64_t n_rows, int32_t F, int32_t HD,
+                     hipStream_t s, int32_t ldx) {
+    if (n_rows <= 0) return 0;
+    int32_t ksplit = 0;
+    GAT_TRY(grad_w_slabs(G, G, X, scratch, n_rows, F, HD, kPartLeft, s, ldx, &ksplit));
+    return launch_reduce_partials_add(scratch, ksplit, (int64_t)HD * F, gradWres, s);
+}
+// gx += G Wres: the grad_x kernel, K = HD walked in chunks of 128 columns of G, every chunk adding into gx
+int launch_grad_x_res(const float* G, const float* Wres, float* gx, int64_t n_rows, int32_t F, int32_t HD, hipStream_t s) {
+    const bool vec4 = (HD % 4 == 0) && aligned16(G);
+    for (int32_t k0 = 0; k0 < HD; k0 += kKC) {
+        const int32_t kc = HD - k0 < kKC ? HD - k0 : kKC;
+        GAT_TRY(run_rowgemm(ASrcRows{G + k0, HD}, BSrcResGradX{Wres + (int64_t)k0 * F, F}, EpiAccum{gx, F}, n_rows, F, kc, vec4, s));
+    }
+    return 0;
 }
 
 }  // namespace gat

@@ -140,8 +140,16 @@ struct WorkList {
 void build_worklist(const int32_t* row_ptr, int64_t n_rows, WorkList& w);
 // drop (optional): attention dropout; drop->on selects the DROP instantiations, whose kernel argument is the struct below.  The
 // default kernels keep the plain argument struct (same layout, same machine code as without the feature).
-int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const DropArgs* drop = nullptr);
-struct EdgeFwdDropArgs : EdgeFwdArgs { DropArgs drop; };
+// res / bias (optional, gatv2_abi.h "residual"): h_pre[row][c] += res[row][c] + bias[c] in the row epilogue, before h_pre and hout
+// are written (split rows: once, in the fix-up kernel's combine).  Either one selects the DROP instantiations too — with nothing
+// dropped when drop is null or off — whose argument struct carries the two pointers.
+int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const DropArgs* drop = nullptr, const float* res = nullptr,
+                        const float* bias = nullptr);
+struct EdgeFwdDropArgs : EdgeFwdArgs {
+    DropArgs drop;
+    const float* res = nullptr;   // [n_rows][HD] R = x' Wres^T of the shard's own rows, or null
+    const float* bias = nullptr;  // [HD], or null
+};
 
 struct EdgeBwdArgs {
     const int32_t* row_ptr;
@@ -365,6 +373,32 @@ int launch_grad_w(const float* gPL_rows, const float* gPR, const float* X, float
 // hpre_prev == nullptr: the plain sum is stored (the consumer applies LReLU', see EdgeBwdArgs::g_raw)
 int launch_grad_x(const float* gPL_rows, const float* gPR, const float* W, const float* hpre_prev,
                   float* gprev, int64_t n_rows, int32_t F, int32_t HD, float slope, hipStream_t s);
+
+// ---- residual / bias (gatv2_abi.h "residual") ------------------------------------------------------------------
+// R[i][j] = sum_f X[i][f] * Wres[j][f]   (Wres flat [HD][F]; the three-piece product of launch_project, K walked in chunks of 128)
+int launch_project_res(const float* X, const float* Wres, float* R, int64_t n_rows, int32_t F, int32_t HD, hipStream_t s, int32_t ldx = 0);
+// gradWres[j][f] += sum_n G[n][j] X[n][f]   (the grad_w kernels on one half; scratch: grad_w_scratch_floats(n_rows, F, HD) floats)
+int launch_grad_wres(const float* G, const float* X, float* gradWres, float* scratch, int64_t n_rows, int32_t F, int32_t HD,
+                     hipStream_t s, int32_t ldx = 0);
+// gx[n][f] += sum_j G[n][j] Wres[j][f]   (the grad_x kernel with an accumulating epilogue; run after launch_grad_x)
+int launch_grad_x_res(const float* G, const float* Wres, float* gx, int64_t n_rows, int32_t F, int32_t HD, hipStream_t s);
+// One N-sized pass of a residual layer's backward.  G = dL/dh_pre in fp32:
+//   g_raw != 0 : g[n][c] * LReLU'(hpre[n][c])                       (hidden layers)
+//   gh != null : gh[n][c % D] * LReLU'(hpre[n][c]) / H              (last layer; rows of gh_stride floats)
+//   otherwise  : g[n][c]                                            (last layer with flat_lrelu_index: the head applied the factor)
+// agg[n][c] = hpre[n][c] - (res[n][c] + bias[c]): the aggregate alone, which the edge backward takes in place of h_pre (its
+// <g, h_pre> stands for sum_e alpha * galpha, true of the aggregate only).  partial [blocks][HD]: per-block column sums of G in
+// fixed order (null: not formed), blocks = res_backward_blocks(...) <= kResPartialRows; finished by launch_reduce_partials_add.
+struct ResBwdArgs {
+    const float* hpre; const float* g; const float* gh; const float* res; const float* bias;
+    float* G; float* agg; float* partial;
+    int64_t n_rows;
+    int32_t H, D, gh_stride, g_raw, blocks;
+    float slope;
+};
+constexpr int kResPartialRows = 1024;
+int res_backward_blocks(int64_t n_rows, int32_t HD);
+int launch_res_backward(const ResBwdArgs& a, hipStream_t s);
 
 struct HeadArgs {
     const float* Wo;          // [C][DL]

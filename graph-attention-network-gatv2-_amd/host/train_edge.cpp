@@ -24,6 +24,9 @@
 // --drop-edge P (default 0): DropEdge (gatv2_abi.h "DropEdge"): every training step drops each edge with probability P BEFORE the
 // softmax, masks keyed by --seed; --drop-edge-keep-self never drops self-loops, --drop-edge-shared draws one mask per step for all
 // layers.  Validation (--val-mask) then comes from an eval-mode forward, as with dropout.
+// --residual / --bias: every layer adds Wres x' / b to h_pre (gatv2_abi.h "residual"); Wres is Xavier-initialised from --seed after the
+// other parameters (which keep their values), b starts at 0.  --dump-params / --load-params then carry the groups Wres and b behind
+// W, a and Wo — only the groups whose flag is on, so files written without the flags keep their format.
 // --add-self-loops / --undirected / --coalesce: the graph is rebuilt on the device before training (gat_graph_from_coo:
 // GAT_GRAPH_SELF_LOOPS / SYMMETRIZE / COALESCE, applied in that order); a CSR dataset is expanded to an edge list first.
 // Edge-list dataset: a folder with edges.txt (one "src dst" pair per line, a message flows src -> dst) instead of
@@ -78,6 +81,7 @@ struct Options {
     std::string train_mask, val_mask;     // text files of N 0/1 values (beyond the reference: README R:134 "later")
     float dropout = 0.f, attn_dropout = 0.f;
     float drop_edge = 0.f; int drop_edge_flags = 0;   // GAT_DROPEDGE_*: --drop-edge-keep-self, --drop-edge-shared
+    int residual_flags = 0;                           // GAT_RES_*: --residual, --bias
     int graph_flags = 0;                  // GAT_GRAPH_*: --add-self-loops, --undirected, --coalesce
 };
 
@@ -97,6 +101,9 @@ const char* kUsage =
     "            --train-mask FILE --val-mask FILE --dropout P --attn-dropout P\n"
     "            --drop-edge P [--drop-edge-keep-self] [--drop-edge-shared]   DropEdge: each training step drops every edge with\n"
     "                          probability P before the softmax (never a self-loop / one mask for all layers instead of one per layer)\n"
+    "            --residual         every layer adds Wres x' to h_pre (a skip connection through a learned linear map)\n"
+    "            --bias             every layer adds a learned bias b to h_pre\n"
+    "                          (--dump-params / --load-params then append Wres and b behind W, a and Wo)\n"
     "            --ranks P [--transport rccl|host] [--halo 0|1|2]\n";
 
 struct RankEnv {                      // one forked process per GPU
@@ -177,6 +184,8 @@ Options parse_args(int argc, char** argv) {
         else if (a == "--drop-edge" && has_val) o.drop_edge = std::strtof(argv[++i], nullptr);
         else if (a == "--drop-edge-keep-self") o.drop_edge_flags |= GAT_DROPEDGE_KEEP_SELF;
         else if (a == "--drop-edge-shared") o.drop_edge_flags |= GAT_DROPEDGE_SHARED_LAYERS;
+        else if (a == "--residual") o.residual_flags |= GAT_RES_LINEAR;
+        else if (a == "--bias") o.residual_flags |= GAT_RES_BIAS;
         else if (a == "--transport" && has_val) {
             o.transport = argv[++i];
             if (o.transport != "rccl" && o.transport != "host") die("Invalid transport choice. Use 'rccl' or 'host'\n");
@@ -454,8 +463,11 @@ int run(const Options& o, const RankEnv& env) {
     }
     gat_ctx* ctx = nullptr;
     check(gat_create(&cfg, &ctx), "gat_create");
-    int64_t nW = 0, nA = 0, nWo = 0;
+    // residual / bias: before anything sizes the packed buffers; every rank of --ranks runs this with the same options
+    if (o.residual_flags) check(gat_set_residual(ctx, o.residual_flags), "gat_set_residual");
+    int64_t nW = 0, nA = 0, nWo = 0, nWres = 0, nB = 0;
     gat_param_count(ctx, GAT_PARAM_W, &nW); gat_param_count(ctx, GAT_PARAM_A, &nA); gat_param_count(ctx, GAT_PARAM_WO, &nWo);
+    gat_param_count(ctx, GAT_PARAM_WRES, &nWres); gat_param_count(ctx, GAT_PARAM_B, &nB);     // 0 without the flags
     if (env.world == 1) {
         check(gat_set_graph(ctx, row_ptr.data(), col_idx.data(), N, E, N, 0), "csr_to_coo_kernel");
         check(gat_set_features(ctx, x.data(), N, F0), "gat_set_features");
@@ -488,7 +500,7 @@ int run(const Options& o, const RankEnv& env) {
         } else {
             int64_t hd_max = 0;
             for (int l = 0; l < L; ++l) hd_max = std::max<int64_t>(hd_max, (int64_t)o.heads[l] * o.outdims[l]);
-            const int64_t bytes = std::max<int64_t>(plan.n_table() * hd_max + 64, nW + nA + nWo + 3) * (int64_t)sizeof(float);   // (+ 64: block offsets of a halo exchange)
+            const int64_t bytes = std::max<int64_t>(plan.n_table() * hd_max + 64, nW + nA + nWo + nWres + nB + 3) * (int64_t)sizeof(float);   // (+ 64: block offsets of a halo exchange)
             check(gat_comm_init_host(ctx, env.world, env.rank, env.shm_name.c_str(), bytes), "gat_comm_init_host");
         }
         if (o.halo != 0) check(gat_comm_option(ctx, GAT_COMM_HALO, o.halo), "gat_comm_option(GAT_COMM_HALO)");      // collective: every rank
@@ -533,12 +545,14 @@ int run(const Options& o, const RankEnv& env) {
     if (o.drop_edge > 0.f) check(gat_set_dropedge(ctx, o.drop_edge, o.drop_edge_flags), "gat_set_dropedge");
     check(gat_params_init(ctx, o.seed), "xavier_init_kernel");
     if (!o.load_params.empty()) {
-        std::vector<float> p(nW + nA + nWo);
+        std::vector<float> p(nW + nA + nWo + nWres + nB);    // the residual groups follow the others, only with their flags
         std::ifstream f(o.load_params, std::ios::binary);
         if (!f.read(reinterpret_cast<char*>(p.data()), p.size() * sizeof(float))) die("Error: cannot read --load-params file\n");
         check(gat_params_set(ctx, GAT_PARAM_W, p.data(), nW), "gat_params_set");
         check(gat_params_set(ctx, GAT_PARAM_A, p.data() + nW, nA), "gat_params_set");
         check(gat_params_set(ctx, GAT_PARAM_WO, p.data() + nW + nA, nWo), "gat_params_set");
+        if (nWres) check(gat_params_set(ctx, GAT_PARAM_WRES, p.data() + nW + nA + nWo, nWres), "gat_params_set");
+        if (nB) check(gat_params_set(ctx, GAT_PARAM_B, p.data() + nW + nA + nWo + nWres, nB), "gat_params_set");
     }
 
     size_t free_after = 0;
@@ -579,10 +593,12 @@ int run(const Options& o, const RankEnv& env) {
     }
 
     if (!o.dump_params.empty() && env.rank == 0) {
-        std::vector<float> p(nW + nA + nWo);
+        std::vector<float> p(nW + nA + nWo + nWres + nB);    // without --residual / --bias: the format of always
         check(gat_params_get(ctx, GAT_PARAM_W, p.data(), nW), "gat_params_get");
         check(gat_params_get(ctx, GAT_PARAM_A, p.data() + nW, nA), "gat_params_get");
         check(gat_params_get(ctx, GAT_PARAM_WO, p.data() + nW + nA, nWo), "gat_params_get");
+        if (nWres) check(gat_params_get(ctx, GAT_PARAM_WRES, p.data() + nW + nA + nWo, nWres), "gat_params_get");
+        if (nB) check(gat_params_get(ctx, GAT_PARAM_B, p.data() + nW + nA + nWo + nWres, nB), "gat_params_get");
         std::ofstream f(o.dump_params, std::ios::binary);
         f.write(reinterpret_cast<const char*>(p.data()), p.size() * sizeof(float));
     }

@@ -178,15 +178,21 @@ enum { GAT_CSR_OK = 0, GAT_CSR_BAD_START = 1, GAT_CSR_BAD_END = 2, GAT_CSR_NOT_M
 int gat_graph_check_device(const int32_t* d_row_ptr, const int32_t* d_col_idx, int64_t n_rows, int64_t n_edges, int64_t n_table,
                            int32_t* problem, int64_t* where, void* stream);
 
-/* ---- parameters (Xavier init E:186-248; flat layouts E:1242-1258) --------------------------- */
-enum { GAT_PARAM_W = 0, GAT_PARAM_A = 1, GAT_PARAM_WO = 2 };
+/* ---- parameters (Xavier init E:186-248; flat layouts E:1242-1258) ---------------------------
+ * GAT_PARAM_WRES flat [l][H_l*D_l][F_l] and GAT_PARAM_B flat [l][H_l*D_l] exist on a context with gat_set_residual (see
+ * "residual" below); with their flag off the group's count is 0 and a set / get of 0 floats is a no-op that succeeds. */
+enum { GAT_PARAM_W = 0, GAT_PARAM_A = 1, GAT_PARAM_WO = 2, GAT_PARAM_WRES = 3, GAT_PARAM_B = 4 };
 int gat_param_count(gat_ctx* ctx, int group, int64_t* count);
-int gat_params_init(gat_ctx* ctx, uint64_t seed);     /* U(-lim,lim], lim as E:208, 236 */
+/* U(-lim,lim], lim as E:208, 236.  With GAT_RES_LINEAR: Wres_l Xavier-uniform with lim = sqrt(6 / (F_l + H_l*D_l)), drawn from the same
+ * counter stream AFTER all existing draws (layer by layer), so W, a and Wo of a seed are those of a context without it; b = 0. */
+int gat_params_init(gat_ctx* ctx, uint64_t seed);
 int gat_params_set(gat_ctx* ctx, int group, const float* host, int64_t count);
 int gat_params_get(gat_ctx* ctx, int group, float* host, int64_t count);
 int gat_grads_get(gat_ctx* ctx, int group, float* host, int64_t count);
 int gat_grads_set(gat_ctx* ctx, int group, const float* host, int64_t count);
-/* Device address of the packed gradient buffer [gradW | grada | gradWo] (for the all-reduce). */
+/* Device address of the packed gradient buffer [gradW | grada | gradWo | gradWres | gradb] (for the all-reduce; the last two
+ * groups only with gat_set_residual).  count = n_params, the sum of the five group counts; the three-float result tail of
+ * gat_result_export sits behind it, and the host transport's bytes_per_rank rule stays (n_params + 3) * 4. */
 int gat_grads_device(gat_ctx* ctx, void** d_ptr, int64_t* count);
 /* Async D2D copies of the packed gradients on the context's stream, to / from a caller-owned
  * device buffer of `count` floats (the buffer the host all-reduces). */
@@ -385,6 +391,52 @@ int gat_set_shard_bounds(gat_ctx* ctx, int32_t world, const int64_t* bounds);
  * edge would not need are not subtracted). */
 enum { GAT_DROPEDGE_KEEP_SELF = 1, GAT_DROPEDGE_SHARED_LAYERS = 2 };
 int gat_set_dropedge(gat_ctx* ctx, float edge_p, int32_t flags);
+
+/* ---- residual connections and per-layer bias (beyond the reference; GATv2 of the paper / PyG's GATv2Conv has both) ------------
+ * With flags != 0 every layer l computes
+ *     h_pre[n,h,d] = sum_{e->n} kappa*s_a*alpha[h,e] * PL[src_e][h,d]        (as without the feature, all regularisers included)
+ *                  + sum_f Wres_l[h*D+d][f] * x'_l[n][f]                      GAT_RES_LINEAR
+ *                  + b_l[h*D+d]                                               GAT_RES_BIAS
+ * x'_l is the layer's input after feature dropout: the tensor both projections read.  Everything downstream of h_pre is unchanged
+ * (LeakyReLU, the hidden concatenation, the mean over heads of the last layer, the output head).  The score s = PL[src] + PR[dst]
+ * does not see the residual, and the softmax statistics are untouched: a row without in-edges — also one DropEdge emptied, and a
+ * padding row of a shard — keeps max = -1e9f, sum = 0 and has h_pre = Wres x' + b instead of 0.
+ * Backward, with G = dL/dh_pre including the LReLU'(h_pre) factor:
+ *     gradWres_l = G^T x'_l      gradb_l = sum_n G[n]      dL/dx'_l += G Wres_l
+ * the last added to the two existing terms BEFORE the feature-dropout factor and before the LReLU' factor of the layer below;
+ * layer 0 forms no input gradient, as always.
+ * Where it runs.  Forward: R = x' Wres^T is a third projection over the shard's own rows (the three-bf16-piece product of the other
+ *   two, K walked in chunks of 128), and R + b joins the row's sum in the row epilogue of the edge forward while the accumulator is
+ *   on chip, before h_pre and hout are written once: whole rows in the wave-per-row / group-per-row kernels, split hub rows once in
+ *   the fix-up kernel's combine, the generic kernel alike.  A residual context runs the DROP instantiations of the forward (the ones
+ *   dropout selects) with nothing dropped and the two pointers in their argument struct, so the default-path A/B switches
+ *   (GAT_ROWGROUP, GAT_PACKED, GAT_CPL, GAT_FWD_WAVES) do not apply to its forward.
+ *   Backward: one N-sized kernel per layer forms G in fp32 into a buffer of its own, the aggregate agg = h_pre - (R + b), and
+ *   fixed-order per-block column sums of G (finished by the deferred slab reduction: grad_b is bitwise reproducible, no float
+ *   atomics).  The edge backward kernels and the source-major passes are unchanged: they take G and agg where they took g and h_pre
+ *   (their <g, h_pre> stands for sum_e alpha*galpha, which holds for the aggregate alone), so the last layer's decision-byte pull
+ *   form is not used.  gradWres and the G Wres term of grad_x run on the three-piece GEMM kernels (the second as an adding launch
+ *   after the existing grad_x).  Extra device memory: R per layer and two [n_rows][max H*D] buffers.
+ * gat_set_residual is allowed only BEFORE the first gat_params_*, gat_grads_*, gat_set_graph* call on the context (the packed
+ *   parameter and gradient buffers change size): later it gives GAT_E_STATE.  Unknown flag bits: GAT_E_INVALID.  flags == 0 is the
+ *   default and leaves the context exactly as it is: same buffers, same kernels, same launch counts, bitwise the same results.
+ * Optimizer: gat_zero_grad, gat_step_sgd and gat_step_adam cover the new groups (Adam moments included); gat_clip clips every
+ *   group on its own, as the reference clips its three (five norms with both flags).
+ * Works with every (H, D) family incl. the generic path, bf16 storage (R, G and agg stay fp32), keep_taps, the phase API
+ *   (gat_layer_project forms R, gat_layer_backward_edges runs the N-sized kernel first, gat_layer_backward_dense adds the two dense
+ *   terms), gat_step, gat_step_graph replay, training masks, all three regularisers, and shards on any transport: the residual
+ *   rows are the shard's own (with replicated layer-0 input: its own rows of the table), nothing more is exchanged, and the
+ *   parameter-gradient all-reduce sums the new groups with the others.
+ * Not with: the GAT_FUSE_LAST=1 experiment (a residual context runs the separate passes instead); GAT_DBG in the experiment
+ *   library (gat_set_residual gives GAT_E_UNSUPPORTED); the gat_op_* seams stay residual-free.  GAT_TAP_G keeps returning
+ *   g (.) LReLU'(h_pre), which IS G.
+ * gat_algorithmic_bytes*: unchanged with flags == 0.  gat_algorithmic_bytes (the context form) adds per layer, at 4 bytes:
+ *   project += N*HD (R written) + HD*F (Wres read), x' counted as read once more (N*F) with GAT_RES_LINEAR;
+ *   edge_forward += N*HD (R read); misc += N*HD * (h_pre + g read, G + agg written, + R read with GAT_RES_LINEAR);
+ *   grad_w += N*HD + N*F + HD*F (G, x', gradWres) and, l >= 1, grad_x += N*HD + 2*N*F + HD*F (G, gX read and written, Wres) with
+ *   GAT_RES_LINEAR.  gat_algorithmic_bytes_shape has no context and prices the model without the feature. */
+enum { GAT_RES_LINEAR = 1, GAT_RES_BIAS = 2 };
+int gat_set_residual(gat_ctx* ctx, int32_t flags);
 
 /* ---- op-level entry points, whole layers: caller-provided DEVICE pointers in the reference layouts
  *      (unit parity).  `stream` may be NULL (default stream).  One entry point per reference KERNEL: below. ---- */

@@ -1,0 +1,140 @@
+"""Residual connections and per-layer bias without a GPU (include/gatv2_abi.h "residual"): the new ABI symbols, the fp64
+model of tests/residual_ref.py against the model without the feature and against finite differences, the share of Xavier
+seeds the GPU tests may skip for the LeakyReLU kink, and the train_edge flags."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import residual_ref as RR
+import torch_ref
+from conftest import small_graph
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "graph-attention-network-gatv2-_amd", "train_edge")
+
+
+def _graph(seed, n=40, e=300, F=6, C=3):
+    rng = np.random.default_rng(seed)
+    rp, ci = small_graph(rng, n, e, hub=(7, 40), empty=(3,))
+    x = rng.standard_normal((n, F)).astype(np.float32)
+    lab = rng.integers(0, C, n).astype(np.int32)
+    return dict(row_ptr=rp, col_idx=ci, x=x, labels=lab, n=n, f=F, c=C)
+
+
+def test_symbols_declared_and_exported(pkg):
+    A = pkg.abi
+    assert "gat_set_residual" in A.declared_symbols()
+    assert hasattr(ctypes.CDLL(A.LIB_PATH), "gat_set_residual")
+    assert (A.PARAM_WRES, A.PARAM_B) == (3, 4)
+    assert (A.RES_LINEAR, A.RES_BIAS) == (1, 2)
+    assert A.load_library().gat_abi_version() == 6
+    hdr = open(os.path.join(ROOT, "include", "gatv2_abi.h")).read()
+    assert "#define GAT_ABI_VERSION 6" in hdr
+    assert "GAT_PARAM_WRES = 3, GAT_PARAM_B = 4" in hdr and "GAT_RES_LINEAR = 1, GAT_RES_BIAS = 2" in hdr
+    assert "int gat_set_residual(gat_ctx* ctx, int32_t flags);" in hdr
+    assert hasattr(pkg.GatContext, "set_residual")
+
+
+def test_zero_residual_is_the_model_without_it(orc):
+    g = _graph(1)
+    cfg = orc.Config([4, 2], [4, 8], g["f"], g["c"])
+    P = orc.xavier_params(cfg, 3)
+    wo, bo = RR.offsets(cfg)
+    want = torch_ref.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P)
+    for Wres, b in ((None, None), (np.zeros(wo[-1]), np.zeros(bo[-1])), (np.zeros(wo[-1]), None), (None, np.zeros(bo[-1]))):
+        got = RR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, Wres=Wres, b=b)
+        assert abs(got["loss"].item() - want["loss"].item()) <= 1e-12 * abs(want["loss"].item())
+        for x, y in zip(got["hpre"], want["hpre"]):
+            assert (x - y).abs().max().item() <= 1e-12
+    want["loss"].backward()
+    got["loss"].backward()
+    for k in ("W", "a", "Wo"):
+        assert (got[k].grad - want[k].grad).abs().max().item() <= 1e-12 * max(1.0, want[k].grad.abs().max().item())
+
+
+def test_empty_row_is_the_residual_alone(orc):
+    g = _graph(2)
+    cfg = orc.Config([4, 2], [4, 8], g["f"], g["c"])
+    P = orc.xavier_params(cfg, 1)
+    Wres, b = RR.xavier_wres(cfg, 1)
+    wo, bo = RR.offsets(cfg)
+    ref = RR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, Wres=Wres, b=b)
+    assert g["row_ptr"][3] == g["row_ptr"][4]
+    want = Wres[:wo[1]].astype(np.float64).reshape(16, g["f"]) @ g["x"][3].astype(np.float64) + b[:bo[1]]
+    assert np.abs(ref["hpre"][0][3].detach().numpy().reshape(-1) - want).max() < 1e-12
+
+
+def test_autograd_matches_central_differences(orc):
+    g = _graph(4, n=25, e=120)
+    cfg = orc.Config([2, 2], [3, 4], g["f"], g["c"])
+    P = orc.xavier_params(cfg, 2)
+    Wres, b = RR.xavier_wres(cfg, 2)
+    Wres, b = Wres.astype(np.float64), b.astype(np.float64)
+    feat = [(np.random.default_rng(9 + l).random((g["n"], cfg.in_dims[l])) > 0.3) * (1 / 0.7) for l in range(2)]
+
+    def run(Wr, bb):
+        return RR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, Wres=Wr, b=bb, feat=feat)
+    ref = run(Wres, b)
+    assert ref["s_min"] > 1e-4 and ref["hpre_min"] > 1e-4      # the probes below stay on one side of every kink
+    ref["loss"].backward()
+    rng = np.random.default_rng(0)
+    h = 1e-6
+    for name, base in (("Wres", Wres), ("b", b)):
+        grad = ref[name].grad.numpy()
+        assert np.abs(grad).max() > 0
+        for i in rng.choice(base.size, 12, replace=False):
+            up, dn = base.copy(), base.copy()
+            up[i] += h; dn[i] -= h
+            lu = run(up, b)["loss"].item() if name == "Wres" else run(Wres, up)["loss"].item()
+            ld = run(dn, b)["loss"].item() if name == "Wres" else run(Wres, dn)["loss"].item()
+            fd = (lu - ld) / (2 * h)
+            assert abs(fd - grad[i]) <= 1e-6 * max(1.0, np.abs(grad).max()), (name, i, fd, grad[i])
+
+
+def test_flat_index_model(orc):
+    """flat_lrelu_index is a rule for the GRADIENT (E:598), not the derivative of any loss: the value is unchanged, with one head
+    in the last layer it is the exact index, with more heads the gradients differ."""
+    g = _graph(4, n=25, e=120)
+    for heads, same in (([2, 1], True), ([2, 2], False)):
+        cfg = orc.Config(heads, [3, 4], g["f"], g["c"])
+        P = orc.xavier_params(cfg, 2)
+        Wres, b = RR.xavier_wres(cfg, 2)
+        r0 = RR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, Wres=Wres, b=b)
+        r1 = RR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, Wres=Wres, b=b, flat_lrelu_index=True)
+        assert r0["loss"].item() == r1["loss"].item()
+        r0["loss"].backward(); r1["loss"].backward()
+        diff = max((r0[k].grad - r1[k].grad).abs().max().item() for k in ("W", "a", "Wo", "Wres", "b"))
+        assert (diff == 0) == same, (heads, diff)
+
+
+# the (heads, outdims, bf16) the parity cases of tests/test_residual.py run on its graph
+GPU_SHAPES = [
+    ([8, 8], [8, 8], False), ([16, 16], [4, 4], False), ([4, 4], [16, 16], False), ([2, 2], [8, 8], False), ([3, 2], [5, 8], False),
+    ([16, 2], [8, 8], False), ([8, 8], [8, 8], True), ([8, 8, 8], [8, 8, 8], False),
+]
+
+
+@pytest.mark.parametrize("heads,outdims,bf16", GPU_SHAPES,
+                         ids=[f"{'x'.join(map(str, h))}_{'x'.join(map(str, d))}{'_bf16' if b else ''}" for h, d, b in GPU_SHAPES])
+def test_some_of_the_first_40_seeds_is_clear_of_the_kink(orc, heads, outdims, bf16):
+    """The GPU tests pick the first Xavier seed with min |s| and min |h_pre| above 1e-5; the reference alone must offer one among
+    the first 40, for every mode (linear, bias, both), plain and with the three regularisers on (pick_params raises otherwise)."""
+    import test_residual as T
+    g = T.parity_graph()
+    assert int(g["row_ptr"][8] - g["row_ptr"][7]) == 300 and g["row_ptr"][3] == g["row_ptr"][4]
+    cfg = orc.Config(heads, outdims, g["f"], g["c"])
+    modes = T.MODES if len(heads) == 2 else T.MODES[2:]
+    for mode in modes:
+        for reg in (None, T.REG):
+            T.pick_params(orc, cfg, g, mode, reg, bf16=bf16)
+    if heads == [8, 8] and not bf16:
+        T.pick_params(orc, cfg, g, T.MODES[2], flat=True)
+
+
+def test_train_edge_help_lists_the_flags():
+    out = subprocess.run([BIN, "--help"], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0
+    assert "--residual" in out.stdout and "--bias" in out.stdout
