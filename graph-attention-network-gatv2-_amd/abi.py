@@ -47,7 +47,9 @@ class _Config(C.Structure):
 
 # enums of the header
 PARAM_W, PARAM_A, PARAM_WO, PARAM_WRES, PARAM_B = 0, 1, 2, 3, 4
+PARAM_LN_G, PARAM_LN_B = 5, 6
 RES_LINEAR, RES_BIAS = 1, 2
+NORM_LAYER, NORM_SKIP_LAST = 1, 2
 TABLE_PL, TABLE_GPL = 0, 1
 COMM_GPL_BF16 = 1
 COMM_PIPELINE = 2
@@ -198,6 +200,7 @@ def _declare(lib: C.CDLL) -> None:
         "gat_set_dropout": [vp, f32, f32, C.c_uint64, C.c_uint64],
         "gat_set_dropedge": [vp, f32, i32],
         "gat_set_residual": [vp, i32],
+        "gat_set_norm": [vp, i32, f32],
         "gat_set_training": [vp, i32],
         "gat_dropout_step": [vp, P(C.c_uint64)],
         "gat_set_shard_bounds": [vp, i32, vp],
@@ -413,13 +416,20 @@ class GatContext:
 
     @property
     def n_params(self) -> int:
-        return sum(self.param_count(g) for g in (PARAM_W, PARAM_A, PARAM_WO, PARAM_WRES, PARAM_B))
+        return sum(self.param_count(g) for g in (PARAM_W, PARAM_A, PARAM_WO, PARAM_WRES, PARAM_B, PARAM_LN_G, PARAM_LN_B))
 
     # -- residual / bias (gatv2_abi.h "residual")
     def set_residual(self, linear: bool = False, bias: bool = False, flags: int = 0):
         """h_pre += Wres x' (linear) + b (bias) in every layer, with the parameter groups PARAM_WRES / PARAM_B.  Only before the
         first params_* / grads_* / set_graph* call on the context.  ``flags``: extra raw GAT_RES_* bits (or-ed in)."""
         _chk(self.lib.gat_set_residual(self._ctx, int(flags) | (RES_LINEAR if linear else 0) | (RES_BIAS if bias else 0)))
+
+    # -- layer normalisation (gatv2_abi.h "layer normalisation")
+    def set_norm(self, layer: bool = True, skip_last: bool = False, eps: float = 1e-5, flags: int = 0):
+        """LayerNorm over each row's H*D channels between the aggregation and the LeakyReLU, in every layer (``skip_last``: every layer
+        but the last), with the parameter groups PARAM_LN_G / PARAM_LN_B.  Only before the first params_* / grads_* / set_graph*
+        call on the context.  ``flags``: extra raw GAT_NORM_* bits (or-ed in)."""
+        _chk(self.lib.gat_set_norm(self._ctx, int(flags) | (NORM_LAYER if layer else 0) | (NORM_SKIP_LAST if skip_last else 0), float(eps)))
 
     # -- dropout (gatv2_abi.h "dropout")
     def set_dropout(self, feat_p: float = 0.0, attn_p: float = 0.0, seed: int = 0, first_step: int = 0):

@@ -44,6 +44,7 @@ struct Layer {
     int32_t H = 0, D = 0, F = 0, HD = 0;
     int64_t w_off = 0, a_off = 0;
     int64_t wres_off = 0, b_off = 0;                // inside the Wres / b groups (gat_set_residual)
+    int64_t ln_off = 0;                             // inside the gamma and the beta group (gat_set_norm)
     float* R = nullptr;       // [n_rows][HD]  x' Wres^T of the shard's own rows (GAT_RES_LINEAR)
     float* PL = nullptr;      // [n_table][HD]  (table; may be caller-owned)
     bool PL_bound = false;
@@ -140,12 +141,15 @@ struct gat_ctx {
     int64_t nW = 0, nA = 0, nWo = 0;
     int64_t nWres = 0, nB = 0;                      // 0 unless gat_set_residual switched the group on
     int32_t res_flags = 0;                          // GAT_RES_* (gat_set_residual)
+    int64_t nLnG = 0, nLnB = 0;                     // 0 unless gat_set_norm switched the groups on
+    int32_t norm_flags = 0; float norm_eps = 0.f;   // GAT_NORM_* (gat_set_norm)
+    float* norm_partial = nullptr;                  // [L][2][kResPartialRows][HDmax] block column sums for grad_gamma / grad_beta
     bool params_touched = false;                    // a gat_params_* / gat_grads_* / gat_set_graph* call was made: the packed buffers keep their size
     float* resG = nullptr; float* res_agg = nullptr;   // [n_rows][HDmax] dL/dh_pre and h_pre - (R + b) of the layer whose backward runs
     float* res_partial = nullptr;                   // [L][kResPartialRows][HDmax] block column sums of G (grad_b), one region per layer
     float* res_gw_scratch = nullptr; std::vector<int64_t> res_gw_off;     // slabs of gradWres, one region per layer
-    float* params = nullptr;   // [W | a | Wo | Wres | b]
-    float* grads = nullptr;    // [gradW | grada | gradWo | gradWres | gradb] + 4 floats of tail: [loss, correct lo, correct hi, -]
+    float* params = nullptr;   // [W | a | Wo | Wres | b | gamma | beta]
+    float* grads = nullptr;    // [gradW | grada | gradWo | gradWres | gradb | gradgamma | gradbeta] + 4 floats of tail: [loss, correct lo, correct hi, -]
     std::unique_ptr<gat::Comm> comm;                // exchange transport of a shard (gat_comm_init_*)
     int32_t comm_chunks = 1;                        // gat_comm_option(GAT_COMM_PIPELINE): row chunks of the pipelined forward exchange
     hipStream_t comm_stream = nullptr;              // second stream of the pipelined exchange (created on first use)
@@ -279,8 +283,25 @@ static float* Wo_of(gat_ctx* c) { return c->params + c->nW + c->nA; }
 static float* gW_of(gat_ctx* c, int l) { return c->grads + c->layers[l].w_off; }
 static float* ga_of(gat_ctx* c, int l) { return c->grads + c->nW + c->layers[l].a_off; }
 static float* gWo_of(gat_ctx* c) { return c->grads + c->nW + c->nA; }
-static int64_t n_params(const gat_ctx* c) { return c->nW + c->nA + c->nWo + c->nWres + c->nB; }
+static int64_t n_params(const gat_ctx* c) { return c->nW + c->nA + c->nWo + c->nWres + c->nB + c->nLnG + c->nLnB; }
 static bool res_on(const gat_ctx* c) { return c->res_flags != 0; }
+static bool norm_on(const gat_ctx* c) { return c->norm_flags != 0; }
+// layer l is normalised (gatv2_abi.h "layer normalisation")
+static bool norm_layer(const gat_ctx* c, int l) {
+    return norm_on(c) && !((c->norm_flags & GAT_NORM_SKIP_LAST) && l == c->cfg.num_layers - 1);
+}
+// the context runs the residual route: DROP instantiations of the forward, the N-sized backward kernel, G and agg in the edge backward
+static bool res_route(const gat_ctx* c) { return res_on(c) || norm_on(c); }
+static int64_t ln_base(const gat_ctx* c) { return c->nW + c->nA + c->nWo + c->nWres + c->nB; }
+static float* lng_of(gat_ctx* c, int l) { return c->params + ln_base(c) + c->layers[l].ln_off; }
+static float* lnb_of(gat_ctx* c, int l) { return c->params + ln_base(c) + c->nLnG + c->layers[l].ln_off; }
+static float* glng_of(gat_ctx* c, int l) { return c->grads + ln_base(c) + c->layers[l].ln_off; }
+static float* glnb_of(gat_ctx* c, int l) { return c->grads + ln_base(c) + c->nLnG + c->layers[l].ln_off; }
+static LnArgs ln_args(gat_ctx* c, int l) {
+    LnArgs a;
+    if (norm_layer(c, l)) { a.gamma = lng_of(c, l); a.beta = lnb_of(c, l); a.eps = c->norm_eps; }
+    return a;
+}
 // null while the group is off
 static float* Wres_of(gat_ctx* c, int l) { return c->nWres ? c->params + c->nW + c->nA + c->nWo + c->layers[l].wres_off : nullptr; }
 static float* b_of(gat_ctx* c, int l) { return c->nB ? c->params + c->nW + c->nA + c->nWo + c->nWres + c->layers[l].b_off : nullptr; }
@@ -483,7 +504,8 @@ static int ensure_buffers(gat_ctx* c) {
     GAT_TRY(dalloc(c, &c->loss_out, 1));
     GAT_TRY(dalloc(c, &c->correct_out, 1));
     GAT_TRY(dalloc(c, &c->y, N * C));
-    if (res_on(c)) {                                 // gatv2_abi.h "residual"
+    if (res_route(c)) {                              // gatv2_abi.h "residual" / "layer normalisation"
+        if (norm_on(c)) GAT_TRY(dalloc(c, &c->norm_partial, (int64_t)L * 2 * kResPartialRows * c->HDmax));
         GAT_TRY(dalloc(c, &c->resG, N * c->HDmax));
         GAT_TRY(dalloc(c, &c->res_agg, N * c->HDmax));
         GAT_TRY(dalloc(c, &c->res_partial, (int64_t)L * kResPartialRows * c->HDmax));
@@ -862,6 +884,8 @@ static int group_span(gat_ctx* c, int group, int64_t* off, int64_t* cnt) {
         case GAT_PARAM_WO: *off = c->nW + c->nA; *cnt = c->nWo; return 0;
         case GAT_PARAM_WRES: *off = c->nW + c->nA + c->nWo; *cnt = c->nWres; return 0;
         case GAT_PARAM_B: *off = c->nW + c->nA + c->nWo + c->nWres; *cnt = c->nB; return 0;
+        case GAT_PARAM_LN_G: *off = ln_base(c); *cnt = c->nLnG; return 0;
+        case GAT_PARAM_LN_B: *off = ln_base(c) + c->nLnG; *cnt = c->nLnB; return 0;
         default: return fail(GAT_E_INVALID, "unknown parameter group");
     }
 }
@@ -952,6 +976,11 @@ int gat_params_init(gat_ctx* c, uint64_t seed) {
         }
     }
     if (c->nB) GAT_HIP(hipMemsetAsync(b_of(c, 0), 0, (size_t)c->nB * sizeof(float), c->stream));
+    const std::vector<float> ones((size_t)c->nLnG, 1.0f);      // layer normalisation: gamma = 1, beta = 0, no draws
+    if (c->nLnG) {
+        GAT_HIP(hipMemcpyAsync(lng_of(c, 0), ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        GAT_HIP(hipMemsetAsync(lnb_of(c, 0), 0, (size_t)c->nLnB * sizeof(float), c->stream));
+    }
     GAT_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1003,12 +1032,13 @@ int gat_layer_forward_edges(gat_ctx* c, int32_t l) {
     GAT_TRY(check_layer(c, l));
     const EdgeFwdArgs a = plan_forward_edges(c, l);
     DropArgs d = attn_drop_args(c, l);
-    if (res_on(c) && !d.on) {                         // residual without a mask: the DROP instantiations with nothing dropped
+    if (res_route(c) && !d.on) {                      // residual / norm without a mask: the DROP instantiations with nothing dropped
         d = drop_args(c, kDropAttn, l);
         d.T = 0; d.scale = 1.f; d.on = 0;
     }
+    const LnArgs ln = ln_args(c, l);
     Scope t(c, GAT_K_EDGE_FWD);
-    return launch_edge_forward(a, c->stream, &d, c->layers[l].R, b_of(c, l));
+    return launch_edge_forward(a, c->stream, &d, c->layers[l].R, b_of(c, l), &ln);
 }
 static EdgeFwdArgs plan_forward_edges(gat_ctx* c, int32_t l) {
     Layer& y = c->layers[l];
@@ -1069,7 +1099,7 @@ static int plan_backward_edges(gat_ctx* c, int32_t l, BwdPlan* P) {
     a.hpre = y.hpre; a.g = y.g; a.gPL = gPL_of(c, l); a.gPR = gPR_of(c, l); a.ge = y.ge; a.galpha = y.galpha;
     a.g_raw = l < c->cfg.num_layers - 1;           // hidden layers: written by launch_grad_x without the LReLU' factor
     a.gh = (l == c->cfg.num_layers - 1) ? c->gH : nullptr; a.gh_stride = c->gh_stride; a.hb_stride = 64;
-    if (res_on(c)) {                                // residual: G (complete) and the aggregate h_pre - (R + b), from res_backward_layer
+    if (res_route(c)) {                             // residual / norm: G (complete) and the aggregate h_pre - (R + b), from res_backward_layer
         a.g = c->resG; a.g_raw = 0; a.gh = nullptr; a.hpre = c->res_agg;
     }
     a.pos = store ? c->csc_pos : nullptr; a.msg = store ? c->msg : nullptr;
@@ -1122,9 +1152,22 @@ static int res_backward_layer(gat_ctx* c, int32_t l) {
     r.G = c->resG; r.agg = c->res_agg;
     r.partial = c->nB ? c->res_partial + (int64_t)l * kResPartialRows * c->HDmax : nullptr;
     r.n_rows = c->n_rows; r.H = y.H; r.D = y.D; r.gh_stride = c->gh_stride; r.g_raw = last ? 0 : 1;
-    r.blocks = res_backward_blocks(c->n_rows, y.HD); r.slope = c->cfg.negative_slope;
+    r.slope = c->cfg.negative_slope;
     Scope t(c, GAT_K_MISC);
-    GAT_TRY(launch_res_backward(r, c->stream));
+    if (norm_layer(c, l)) {                          // normalised layer: the norm's own kernel stands in (G through the normalisation)
+        NormBwdArgs n{};
+        n.gamma = lng_of(c, l); n.beta = lnb_of(c, l); n.eps = c->norm_eps;
+        n.part_gamma = c->norm_partial + (int64_t)l * 2 * kResPartialRows * c->HDmax;
+        n.part_beta = n.part_gamma + (int64_t)kResPartialRows * c->HDmax;
+        r.blocks = norm_backward_blocks(c->n_rows, y.HD);
+        n.r = r;
+        GAT_TRY(launch_norm_backward(n, c->stream));
+        GAT_TRY(launch_reduce_partials_add(n.part_gamma, r.blocks, y.HD, glng_of(c, l), c->stream));
+        GAT_TRY(launch_reduce_partials_add(n.part_beta, r.blocks, y.HD, glnb_of(c, l), c->stream));
+    } else {
+        r.blocks = res_backward_blocks(c->n_rows, y.HD);
+        GAT_TRY(launch_res_backward(r, c->stream));
+    }
     if (r.partial != nullptr) return launch_reduce_partials_add(r.partial, r.blocks, y.HD, gb_of(c, l), c->stream);
     return 0;
 }
@@ -1133,7 +1176,7 @@ int gat_layer_backward_edges(gat_ctx* c, int32_t l) {
     Layer& y = c->layers[l];
     BwdPlan P;
     GAT_TRY(plan_backward_edges(c, l, &P));
-    if (res_on(c)) GAT_TRY(res_backward_layer(c, l));
+    if (res_route(c)) GAT_TRY(res_backward_layer(c, l));
     if (!P.store) {
         Scope t(c, GAT_K_MISC);
         GAT_HIP(hipMemsetAsync(gPL_of(c, l), 0, (size_t)c->n_table * y.HD * sizeof(float), c->stream));
@@ -1285,7 +1328,7 @@ static int head_step(gat_ctx* c, bool with_gh = true) {
 // of the forward's rows left in the caches when a pass's gathers exceed the Infinity Cache; fused per row, the second walk of
 // a row's sources comes a few microseconds after the first.
 static bool fused_last(gat_ctx* c) {
-    if (!fused_head(c) || bf16(c) || c->comm || c->n_table != c->n_rows || c->cfg.flat_lrelu_index || res_on(c)) return false;   // no residual form
+    if (!fused_head(c) || bf16(c) || c->comm || c->n_table != c->n_rows || c->cfg.flat_lrelu_index || res_route(c)) return false;   // no residual / norm form
     const Layer& y = c->layers.back();
     if (!edge_fast_path(y.H, y.D, c->n_table) || !y.stash || c->stash == nullptr || c->gH == nullptr) return false;
     if (!edge_last_fused_supported(y.H, y.D, c->cfg.num_classes) || c->dbg != 0 || drop_on(c)) return false;   // no dropout form
@@ -1353,7 +1396,7 @@ static int overlap_prepare(gat_ctx* c) {
     static const int env = [] { const char* e = choice_env("GAT_OVERLAP"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
     const int L = c->cfg.num_layers;
     const bool want = env == 1;
-    if (!want || L < 2 || c->gPL_bound || c->Xtab || res_on(c)) return 0;      // (residual: one G buffer, read by grad_w)
+    if (!want || L < 2 || c->gPL_bound || c->Xtab || res_route(c)) return 0;      // (residual: one G buffer, read by grad_w)
     if (!c->gPL_alt) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(c->stream, &cs);
@@ -1568,6 +1611,18 @@ int gat_step_graph(gat_ctx* c, int32_t enable) {
     c->graph_state = enable ? 1 : 0;
     return 0;
 }
+// the packed buffers at their new size (gat_set_residual / gat_set_norm: nothing has read or written them yet)
+static int resize_packed(gat_ctx* c) {
+    const int64_t np = n_params(c);
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    dfree(c, c->params); dfree(c, c->grads);
+    c->params = nullptr; c->grads = nullptr;
+    GAT_TRY(dalloc(c, &c->params, np));
+    GAT_TRY(dalloc(c, &c->grads, np + 4));
+    GAT_HIP(hipMemsetAsync(c->params, 0, np * sizeof(float), c->stream));
+    GAT_HIP(hipMemsetAsync(c->grads, 0, np * sizeof(float), c->stream));
+    return 0;
+}
 // ---- residual / bias --------------------------------------------------------------------------------------------
 int gat_set_residual(gat_ctx* c, int32_t flags) {
     if (!c) return fail(GAT_E_INVALID, "null context");
@@ -1587,15 +1642,30 @@ int gat_set_residual(gat_ctx* c, int32_t flags) {
         if (flags & GAT_RES_BIAS) bo += y.HD;
     }
     c->nWres = wr; c->nB = bo; c->res_flags = flags;
-    const int64_t np = n_params(c);                      // the packed buffers at their new size (nothing has read or written them yet)
-    GAT_HIP(hipStreamSynchronize(c->stream));
-    dfree(c, c->params); dfree(c, c->grads);
-    c->params = nullptr; c->grads = nullptr;
-    GAT_TRY(dalloc(c, &c->params, np));
-    GAT_TRY(dalloc(c, &c->grads, np + 4));
-    GAT_HIP(hipMemsetAsync(c->params, 0, np * sizeof(float), c->stream));
-    GAT_HIP(hipMemsetAsync(c->grads, 0, np * sizeof(float), c->stream));
-    return 0;
+    return resize_packed(c);
+}
+// ---- layer normalisation ----------------------------------------------------------------------------------------
+int gat_set_norm(gat_ctx* c, int32_t flags, float eps) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (flags & ~(GAT_NORM_LAYER | GAT_NORM_SKIP_LAST)) return fail(GAT_E_INVALID, "gat_set_norm: unknown flag bits");
+    if ((flags & GAT_NORM_SKIP_LAST) && !(flags & GAT_NORM_LAYER)) return fail(GAT_E_INVALID, "gat_set_norm: GAT_NORM_SKIP_LAST needs GAT_NORM_LAYER");
+    if (flags != 0 && !(std::isfinite(eps) && eps > 0.f)) return fail(GAT_E_INVALID, "gat_set_norm: eps must be finite and > 0");
+    if (c->params_touched)
+        return fail(GAT_E_STATE, "gat_set_norm: call it before the first gat_params_*, gat_grads_* or gat_set_graph* call (the packed buffers change size)");
+    if (flags == 0 && c->norm_flags == 0) return 0;      // the default: nothing is touched
+    if (flags != 0 && c->cfg.flat_lrelu_index)
+        return fail(GAT_E_UNSUPPORTED, "gat_set_norm: not with flat_lrelu_index (the reference's flat index has no meaning on the normalised row)");
+#ifdef GAT_EXPERIMENTS                               // (the release library does not know the switch's name)
+    if (c->dbg != 0 && flags != 0)
+        return fail(GAT_E_UNSUPPORTED, "gat_set_norm: not with a GAT_DBG timing experiment (those kernels have no normalised form)");
+#endif
+    int64_t o = 0;
+    for (int l = 0; l < c->cfg.num_layers; ++l) {
+        c->layers[l].ln_off = o;
+        if (flags != 0) o += c->layers[l].HD;            // all L layers; with GAT_NORM_SKIP_LAST the last one's entries are never read
+    }
+    c->nLnG = o; c->nLnB = o; c->norm_flags = flags; c->norm_eps = flags != 0 ? eps : 0.f;
+    return resize_packed(c);
 }
 // ---- dropout ---------------------------------------------------------------------------------------------------
 int gat_set_dropout(gat_ctx* c, float feat_p, float attn_p, uint64_t seed, uint64_t first_step) {
@@ -1754,6 +1824,9 @@ int gat_clip(gat_ctx* c, float threshold) {
     // the residual groups: each clipped by its own norm, like the reference's three
     if (c->nWres) GAT_TRY(launch_clip(c->grads + c->nW + c->nA + c->nWo, c->nWres, threshold, c->clip_scratch + 3, c->stream));
     if (c->nB) GAT_TRY(launch_clip(c->grads + c->nW + c->nA + c->nWo + c->nWres, c->nB, threshold, c->clip_scratch + 4, c->stream));
+    // the norm groups: gamma and beta each by its own norm
+    if (c->nLnG) GAT_TRY(launch_clip(c->grads + ln_base(c), c->nLnG, threshold, c->clip_scratch + 5, c->stream));
+    if (c->nLnB) GAT_TRY(launch_clip(c->grads + ln_base(c) + c->nLnG, c->nLnB, threshold, c->clip_scratch + 6, c->stream));
     return 0;
 }
 int gat_step_sgd(gat_ctx* c, float lr) {
@@ -1868,6 +1941,20 @@ int gat_tap(gat_ctx* c, int tensor, int32_t l, void* host, int64_t count) {
             return d2h(c, host, c->y, N * c->cfg.num_classes * sizeof(float));
         case GAT_TAP_G: {
             GAT_TRY(need(N * y.HD));
+            if (norm_layer(c, l)) {                     // dL/dh_pre through the normalisation: the backward kernel's row function again, on the
+                NormBwdArgs n{};                        // layer's stored output gradient and h_pre (no column sums, no aggregate)
+                n.r.hpre = y.hpre; n.r.g = y.g; n.r.gh = (last && c->gH != nullptr) ? c->gH : nullptr;
+                n.r.n_rows = N; n.r.H = y.H; n.r.D = y.D; n.r.gh_stride = c->gh_stride; n.r.slope = c->cfg.negative_slope;
+                n.r.blocks = norm_backward_blocks(N, y.HD);
+                n.gamma = lng_of(c, l); n.beta = lnb_of(c, l); n.eps = c->norm_eps;
+                float* tmp = nullptr;
+                GAT_HIP(hipMalloc((void**)&tmp, (size_t)std::max<int64_t>(N * y.HD, 1) * sizeof(float)));
+                n.r.G = tmp;
+                int rc = launch_norm_backward(n, c->stream);
+                if (rc == 0) rc = d2h(c, host, tmp, (size_t)(N * y.HD) * sizeof(float));
+                (void)hipFree(tmp);
+                return rc;
+            }
             if (last && c->gH) {                        // formed on the fly by the kernels: same expression, same order
                 std::vector<float> hp((size_t)(N * y.HD)), gh((size_t)(N * c->gh_stride));
                 GAT_TRY(d2h(c, hp.data(), y.hpre, hp.size() * sizeof(float)));
@@ -2118,7 +2205,7 @@ int gat_request_bytes_shape(const gat_config* cfg, int64_t n_rows, int64_t n_edg
 }
 int gat_algorithmic_bytes(gat_ctx* c, double* bytes_step, double* per_kernel) {
     if (!c || !c->have_graph) return fail(GAT_E_STATE, "graph not set");
-    if (res_on(c)) {
+    if (res_route(c)) {
         // residual (gatv2_abi.h "residual"): the N-sized traffic it adds, fp32 throughout — R written, read by the edge forward and by
         // the N-sized backward kernel; that kernel's h_pre and g read, G and agg written; G, x' and Wres in the two dense terms
         double k[GAT_K_COUNT] = {0}, tot = 0;
@@ -2127,7 +2214,10 @@ int gat_algorithmic_bytes(gat_ctx* c, double* bytes_step, double* per_kernel) {
         for (int l = 0; l < c->cfg.num_layers; ++l) {
             const double HD = c->layers[l].HD, F = c->layers[l].F;
             const bool lin = (c->res_flags & GAT_RES_LINEAR) != 0;
+            // a norm context without residual flags runs the same N-sized kernel (h_pre + g read, G + agg written); a normalised layer
+            // adds gamma and beta, read by the forward epilogue and by the backward kernel: 2*HD floats per pass
             k[GAT_K_MISC] += 4.0 * N * HD * (lin ? 5 : 4);
+            if (norm_layer(c, l)) k[GAT_K_MISC] += 4.0 * 2 * HD * 2;       // (both passes priced under misc)
             if (!lin) continue;
             k[GAT_K_PROJECT] += 4.0 * (N * HD + HD * F + N * F);
             k[GAT_K_EDGE_FWD] += 4.0 * N * HD;

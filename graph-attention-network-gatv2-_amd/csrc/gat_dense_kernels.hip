@@ -584,6 +584,133 @@ __global__ __launch_bounds__(256) void res_backward_kernel(ResBwdArgs A, int32_t
     }
 }
 
+// ---- layer normalisation backward (gatv2_abi.h "layer normalisation"): one pass over the N x HD tensors of a normalised layer ------
+// A row is LPR lanes (a power of two <= 64, inside one wave), a lane owns V consecutive channels per round of LPR * V channels; a block
+// is rpb = 256 / LPR rows.  The row's four means (u; (u - mu)^2; dxh; dxh * xhat) are butterfly sums over the row's lanes: every lane
+// ends with the same bits, in an order that depends on nothing but LPR.  ONE: the row fits one round, and the compiler keeps it in
+// registers over the passes; else the outer loop writes one round of channels at a time and walks the row again for the means
+// (generic shapes only).  Column sums as in res_backward_kernel: a lane's running sum over its rows, then the block's row lanes in
+// ascending order.
+__device__ __forceinline__ float row_lanes_sum(float x, int LPR) {
+    for (int off = LPR >> 1; off > 0; off >>= 1) x += __shfl_xor(x, off);
+    return x;
+}
+template <int V>
+__device__ __forceinline__ void load_channels(const float* __restrict__ p, float (&x)[V]) {
+    if constexpr (V == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(p);
+        x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w;
+    } else {
+        x[0] = p[0];
+    }
+}
+template <int V, bool ONE>
+__global__ __launch_bounds__(256) void norm_backward_kernel(NormBwdArgs A, int32_t LPR, int32_t rpb) {
+    __shared__ float red[256 * 4];
+    const ResBwdArgs& R = A.r;
+    const int HD = R.H * R.D;
+    const int t = threadIdx.x;
+    const int r_in = t / LPR, cl = t % LPR;
+    const int span = LPR * V;
+    const int walk = ONE ? 1 : HD;                       // bound of the loops over the row's rounds
+    const float inv_heads = 1.0f / (float)R.H, inv_hd = 1.0f / (float)HD;
+    // channel c .. c+V-1 of a row: xhat, dv = dL/dhout * LReLU'(v), dxh = dv * gamma
+    auto channels = [&](int64_t row, int c, float mu, float rstd, float (&u)[V], float (&xh)[V], float (&dv)[V], float (&dxh)[V]) {
+        load_channels<V>(R.hpre + row * HD + c, u);
+        float go[V];
+        if (R.gh == nullptr) load_channels<V>(R.g + row * HD + c, go);
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const float gm = A.gamma[c + i];
+            xh[i] = (u[i] - mu) * rstd;
+            const float v = gm * xh[i] + A.beta[c + i];
+            if (R.gh != nullptr) go[i] = R.gh[row * R.gh_stride + (c + i) % R.D] * inv_heads;     // mean over heads (E:440-449)
+            dv[i] = go[i] * (v > 0.f ? 1.0f : R.slope);
+            dxh[i] = dv[i] * gm;
+        }
+    };
+    for (int ob = 0; ob < HD; ob += span) {              // the round this pass writes; the same count for every lane (barriers below)
+        const int c0 = ob + cl * V;
+        const bool own = c0 < HD;
+        float sG[V], sg[V], sb[V], bv[V];
+#pragma unroll
+        for (int i = 0; i < V; ++i) { sG[i] = 0.f; sg[i] = 0.f; sb[i] = 0.f; bv[i] = (own && R.bias != nullptr) ? R.bias[c0 + i] : 0.f; }
+        // (rows are uniform over a row's lanes: they share r_in)
+        for (int64_t row = (int64_t)blockIdx.x * rpb + r_in; row < R.n_rows; row += (int64_t)gridDim.x * rpb) {
+            float u[V], xh[V], dv[V], dxh[V];
+            float s = 0.f;
+            for (int rb = 0; rb < walk; rb += span) {
+                const int c = rb + cl * V;
+                if (c < HD) {
+                    load_channels<V>(R.hpre + row * HD + c, u);
+#pragma unroll
+                    for (int i = 0; i < V; ++i) s += u[i];
+                }
+            }
+            const float mu = row_lanes_sum(s, LPR) * inv_hd;
+            float q = 0.f;
+            for (int rb = 0; rb < walk; rb += span) {
+                const int c = rb + cl * V;
+                if (c < HD) {
+                    load_channels<V>(R.hpre + row * HD + c, u);
+#pragma unroll
+                    for (int i = 0; i < V; ++i) q += (u[i] - mu) * (u[i] - mu);
+                }
+            }
+            const float rstd = 1.0f / sqrtf(row_lanes_sum(q, LPR) * inv_hd + A.eps);
+            float a1 = 0.f, a2 = 0.f;
+            for (int rb = 0; rb < walk; rb += span) {
+                const int c = rb + cl * V;
+                if (c < HD) {
+                    channels(row, c, mu, rstd, u, xh, dv, dxh);
+#pragma unroll
+                    for (int i = 0; i < V; ++i) { a1 += dxh[i]; a2 += dxh[i] * xh[i]; }
+                }
+            }
+            const float m1 = row_lanes_sum(a1, LPR) * inv_hd, m2 = row_lanes_sum(a2, LPR) * inv_hd;
+            if (own) {
+                channels(row, c0, mu, rstd, u, xh, dv, dxh);
+                const int64_t o = row * HD + c0;
+                float rv[V], G[V], ag[V];
+#pragma unroll
+                for (int i = 0; i < V; ++i) rv[i] = 0.f;
+                if (R.res != nullptr) load_channels<V>(R.res + o, rv);
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    G[i] = rstd * (dxh[i] - m1 - xh[i] * m2);
+                    ag[i] = u[i] - (rv[i] + bv[i]);
+                    sG[i] += G[i]; sg[i] += dv[i] * xh[i]; sb[i] += dv[i];
+                }
+                if constexpr (V == 4) {
+                    *reinterpret_cast<float4*>(R.G + o) = make_float4(G[0], G[1], G[2], G[3]);
+                    if (R.agg != nullptr) *reinterpret_cast<float4*>(R.agg + o) = make_float4(ag[0], ag[1], ag[2], ag[3]);
+                } else {
+                    R.G[o] = G[0];
+                    if (R.agg != nullptr) R.agg[o] = ag[0];
+                }
+            }
+        }
+        auto flush = [&](const float (&sum)[V], float* __restrict__ partial) {     // (partial: uniform per block)
+            if (partial == nullptr) return;
+#pragma unroll
+            for (int i = 0; i < V; ++i) red[t * V + i] = sum[i];
+            __syncthreads();
+            if (r_in == 0 && own) {
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    float tot = 0.f;
+                    for (int r = 0; r < rpb; ++r) tot += red[(r * LPR + cl) * V + i];
+                    partial[(int64_t)blockIdx.x * HD + c0 + i] = tot;
+                }
+            }
+            __syncthreads();
+        };
+        flush(sg, A.part_gamma);
+        flush(sb, A.part_beta);
+        flush(sG, R.partial);
+    }
+}
+
 }  // namespace
 
 // ---- launchers -----------------------------------------------------------------------------------------------------
@@ -609,6 +736,39 @@ int launch_res_backward(const ResBwdArgs& a, hipStream_t s) {
     if (V == 4) hipLaunchKernelGGL(res_backward_kernel<4>, dim3((unsigned)a.blocks), dim3(256), 0, s, a, LPR, rpb);
     else hipLaunchKernelGGL(res_backward_kernel<1>, dim3((unsigned)a.blocks), dim3(256), 0, s, a, LPR, rpb);
     GAT_HIP(hipGetLastError());
+    return 0;
+}
+static void norm_backward_shape(int32_t HD, int* V, int* LPR, int* rpb, bool* one) {
+    *V = HD % 4 == 0 ? 4 : 1;
+    const int groups = HD / *V;                          // column groups of a row
+    int l = 1;
+    while (l < groups && l < 64) l <<= 1;                // the row's lanes: a power of two inside one wave
+    *LPR = l;
+    *rpb = 256 / l;
+    *one = groups <= l;
+}
+static const void* norm_backward_fn(int V, bool one) {
+    if (V == 4) return one ? (const void*)norm_backward_kernel<4, true> : (const void*)norm_backward_kernel<4, false>;
+    return one ? (const void*)norm_backward_kernel<1, true> : (const void*)norm_backward_kernel<1, false>;
+}
+int norm_backward_blocks(int64_t n_rows, int32_t HD) {
+    int V, LPR, rpb;
+    bool one;
+    norm_backward_shape(HD, &V, &LPR, &rpb, &one);
+    const int64_t want = std::max<int64_t>(1, (n_rows + rpb - 1) / rpb);
+    return (int)std::min({want, resident_blocks(norm_backward_fn(V, one), 0), (int64_t)kResPartialRows});
+}
+int launch_norm_backward(const NormBwdArgs& a, hipStream_t s) {
+    if (a.r.n_rows <= 0) return 0;
+    if (a.r.blocks < 1 || a.r.blocks > kResPartialRows) return fail(GAT_E_INVALID, "norm_backward: blocks must come from norm_backward_blocks()");
+    if (a.r.gh == nullptr && a.r.g == nullptr) return fail(GAT_E_INVALID, "norm_backward: no output gradient");
+    if (a.gamma == nullptr || a.beta == nullptr || a.r.G == nullptr || a.r.H < 1 || a.r.D < 1) return fail(GAT_E_INVALID, "norm_backward: null argument");
+    int V, LPR, rpb;
+    bool one;
+    norm_backward_shape(a.r.H * a.r.D, &V, &LPR, &rpb, &one);
+    NormBwdArgs arg = a;
+    void* args[] = {&arg, &LPR, &rpb};
+    GAT_HIP(hipLaunchKernel(norm_backward_fn(V, one), dim3((unsigned)a.r.blocks), dim3(256), args, 0, s));
     return 0;
 }
 static thread_local ReduceBatch t_batch;

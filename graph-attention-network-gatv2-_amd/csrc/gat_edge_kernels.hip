@@ -146,6 +146,21 @@ __global__ __launch_bounds__(256) void csr_to_coo_kernel(const int32_t* __restri
 // group are issued back to back before any is consumed.  Scores are kept in the log2 domain
 // (a pre-scaled by log2 e) so that every softmax term is one v_exp_f32.
 // ------------------------------------------------------------------------------------------------
+// Layer normalisation of a row held one channel per lane by LANES consecutive lanes (gatv2_abi.h "layer normalisation"): two passes
+// over the on-chip row, both means as butterfly sums over the row's lanes (fixed order, every lane ends with the same bits).
+template <int LANES>
+__device__ __forceinline__ float row_lanes_sum(float x) {
+#pragma unroll
+    for (int off = 1; off < LANES; off <<= 1) x += __shfl_xor(x, off);
+    return x;
+}
+template <int HD>
+__device__ __forceinline__ float ln_row(float u, const LnArgs& ln, int c) {
+    const float d = u - row_lanes_sum<HD>(u) * (1.0f / (float)HD);
+    const float rstd = 1.0f / sqrtf(row_lanes_sum<HD>(d * d) * (1.0f / (float)HD) + ln.eps);
+    return ln.gamma[c] * (d * rstd) + ln.beta[c];
+}
+
 // RES: the residual term rs = R[row][c] + b[c] (gatv2_abi.h "residual") joins h_pre here, before anything is written
 template <int HD, int D, bool RES = false>
 __device__ __forceinline__ void fwd_write_row(const EdgeFwdArgs& A, int64_t row, int lane, float m2, float Z,
@@ -166,6 +181,30 @@ __device__ __forceinline__ void fwd_write_row(const EdgeFwdArgs& A, int64_t row,
         if (gidx == 0) A.hout[row * HD + c] = act;   // concat heads (E:452-457)
     } else {
         float t = act;                               // activate, then average heads (E:440-449)
+#pragma unroll
+        for (int off = D; off < HD; off <<= 1) t += __shfl_xor(t, off);
+        if (lane < D) A.hout[row * D + lane] = t / (float)H;
+    }
+}
+// The row epilogue of the DROP / RES forms (a function of its own: the one above stays the default path's, token for token): the
+// residual term joins h_pre, and with ln.gamma the row is then normalised — hout = LReLU(v), h_pre stays u.  (Every lane group holds
+// the whole row: the sums stay inside one.)
+template <int HD, int D>
+__device__ __forceinline__ void fwd_write_row_ln(const EdgeFwdArgs& A, int64_t row, int lane, float m2, float Z, float acc, float rs,
+                                                 const LnArgs& ln) {
+    constexpr int H = HD / D;
+    const int c = lane % HD, gidx = lane / HD;
+    float hp = acc * __builtin_amdgcn_rcpf(Z + 1e-8f) + rs;      // E:379 epsilon
+    if (gidx == 0) {
+        A.hpre[row * HD + c] = hp;
+        if ((c % D) == 0) { A.mstat[row * H + c / D] = m2; A.zstat[row * H + c / D] = Z; }
+    }
+    if (ln.gamma != nullptr) hp = ln_row<HD>(hp, ln, c);
+    const float act = lrelu(hp, A.slope);
+    if (!A.is_last) {
+        if (gidx == 0) A.hout[row * HD + c] = act;
+    } else {
+        float t = act;
 #pragma unroll
         for (int off = D; off < HD; off <<= 1) t += __shfl_xor(t, off);
         if (lane < D) A.hout[row * D + lane] = t / (float)H;
@@ -378,7 +417,8 @@ __global__ __launch_bounds__(256) void edge_fwd_kernel(FwdArgsT<DROP> A) {
         fwd_normalize_slice<HD, D>(A, b, e_end, lane, m, inv);
     }
     }
-    fwd_write_row<HD, D, DROP>(A, row, lane, m, Z, acc, rs);
+    if constexpr (DROP) fwd_write_row_ln<HD, D>(A, row, lane, m, Z, acc, rs, A.ln);
+    else fwd_write_row<HD, D, DROP>(A, row, lane, m, Z, acc, rs);
 }
 
 // Split rows: one wave per segment merges ALL partials of its row (L2-hot, <= a few hundred
@@ -425,7 +465,7 @@ __global__ __launch_bounds__(256) void edge_fwd_fix_kernel(FwdArgsT<RES> A) {
     for (; sg < s_end; ++sg)
         merge(A.part_mz[(int64_t)sg * 2 * H + c / D], A.part_mz[(int64_t)sg * 2 * H + H + c / D], A.part_acc[(int64_t)sg * HD + c]);
     if constexpr (ALPHA) fwd_normalize_slice<HD, D>(A, item.y, item.z, lane, m, __builtin_amdgcn_rcpf(Z + 1e-8f));
-    if constexpr (RES) { if (slot == info.y) fwd_write_row<HD, D, true>(A, info.x, lane, m, Z, acc, res_term(A, info.x, HD, c)); }
+    if constexpr (RES) { if (slot == info.y) fwd_write_row_ln<HD, D>(A, info.x, lane, m, Z, acc, res_term(A, info.x, HD, c), A.ln); }
     else if (slot == info.y) fwd_write_row<HD, D>(A, info.x, lane, m, Z, acc);
 }
 
@@ -670,6 +710,19 @@ __device__ __forceinline__ vnf<N> res_term_n(const EdgeFwdDropArgs& A, int64_t r
     return r;
 }
 
+// the N-channel form of ln_row: the row is LPE lanes of N channels each (gamma / beta: element loads, the packed parameter buffer
+// aligns a group to 4 bytes only)
+template <int HD, int N>
+__device__ __forceinline__ vnf<N> ln_row_n(vnf<N> u, const LnArgs& ln, int c) {
+    constexpr int LPE = HD / N;
+    const vnf<N> d = u - row_lanes_sum<LPE>(hsum<N>(u)) * (1.0f / (float)HD);
+    const float rstd = 1.0f / sqrtf(row_lanes_sum<LPE>(hsum<N>(d * d)) * (1.0f / (float)HD) + ln.eps);
+    vnf<N> v;
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = ln.gamma[c + i] * (d[i] * rstd) + ln.beta[c + i];
+    return v;
+}
+
 template <int HD, int D, int N, int UU, bool BF, bool DROP = false, class AT = EdgeFwdArgs>
 __device__ __forceinline__ void fwd2_chunk(const AT& A, int e0, int e_end_v, int cp, int gidx, int srcv,
                                            vnf<N> pr, vnf<N> ac2, float& m, float& Z, vnf<N>& acc, uint32_t kd = 0, int rb = 0,
@@ -777,6 +830,7 @@ __global__ __launch_bounds__(256) void edge_fwd2_kernel(FwdArgsT<DROP> A) {
         *reinterpret_cast<vnf<N>*>(A.hpre + row * HD + c) = hp;
         if ((c % D) == 0) { A.mstat[row * H + c / D] = m; A.zstat[row * H + c / D] = Z; }
     }
+    if constexpr (DROP) { if (A.ln.gamma != nullptr) hp = ln_row_n<HD, N>(hp, A.ln, c); }     // hout = LReLU(v); h_pre stays u
     const vnf<N> act = lrelu_n<N>(hp, A.slope);
     if (!A.is_last) {
         if (gidx == 0) *reinterpret_cast<vnf<N>*>(A.hout + row * HD + c) = act;   // concat heads (E:452-457)
@@ -885,6 +939,7 @@ __global__ __launch_bounds__(256) void edge_fwd3_kernel(FwdArgsT<DROP> A) {
     if constexpr (DROP) hp += res_term_n<N>(A, row, HD, c);      // residual / bias: before h_pre and hout are written
     stream_store(reinterpret_cast<vnf<N>*>(A.hpre + (int64_t)row * HD + c), hp);
     if ((c % D) == 0) { A.mstat[(int64_t)row * H + c / D] = m; A.zstat[(int64_t)row * H + c / D] = Z; }
+    if constexpr (DROP) { if (A.ln.gamma != nullptr) hp = ln_row_n<HD, N>(hp, A.ln, c); }     // hout = LReLU(v); h_pre stays u
     const vnf<N> act = lrelu_n<N>(hp, A.slope);
     if (!A.is_last) {
         stream_store(reinterpret_cast<vnf<N>*>(A.hout + (int64_t)row * HD + c), act);     // concat heads (E:452-457)
@@ -1799,9 +1854,11 @@ __global__ __launch_bounds__(256) void edge_bwd_fix_kernel(const int4* __restric
 // dynamic LDS: forward  act[HD];  backward dot[H] ge[H] al[H] ga[HD] gpr[HD]
 // ------------------------------------------------------------------------------------------------
 // RES: res / bias (either may be null) join the row's sum before h_pre is written (gatv2_abi.h "residual")
+// and, with ln.gamma, the row u is parked in LDS, normalised over its H*D channels (lane-strided sums in ascending order, then the
+// wave's butterfly) and hout = LReLU(v) (gatv2_abi.h "layer normalisation")
 template <bool RES>
 __device__ __forceinline__ void edge_fwd_generic_body(const EdgeFwdArgs& A, const DropArgs& dr, [[maybe_unused]] const float* __restrict__ res,
-                                                      [[maybe_unused]] const float* __restrict__ bias) {
+                                                      [[maybe_unused]] const float* __restrict__ bias, [[maybe_unused]] const LnArgs& ln = LnArgs{}) {
     extern __shared__ float lds[];
     const int H = A.H, D = A.D, HD = H * D;
     const int lane = threadIdx.x;
@@ -1853,8 +1910,25 @@ __device__ __forceinline__ void edge_fwd_generic_body(const EdgeFwdArgs& A, cons
                 if (bias != nullptr) acc += bias[ch];
             }
             A.hpre[row * HD + ch] = acc;
+            if constexpr (RES) { if (ln.gamma != nullptr) { lds[ch] = acc; continue; } }
             const float act = lrelu(acc, slope);
             if (!A.is_last) A.hout[row * HD + ch] = act; else lds[ch] = act;
+        }
+        if constexpr (RES) {
+            if (ln.gamma != nullptr) {                   // (uniform: every lane reaches the barriers)
+                __syncthreads();
+                float sm = 0.f;
+                for (int ch = lane; ch < HD; ch += 64) sm += lds[ch];
+                const float mu = row_lanes_sum<64>(sm) / (float)HD;
+                float q = 0.f;
+                for (int ch = lane; ch < HD; ch += 64) q += (lds[ch] - mu) * (lds[ch] - mu);
+                const float rstd = 1.0f / sqrtf(row_lanes_sum<64>(q) / (float)HD + ln.eps);
+                __syncthreads();                         // all of u read before a lane replaces its channels
+                for (int ch = lane; ch < HD; ch += 64) {
+                    const float act = lrelu(ln.gamma[ch] * ((lds[ch] - mu) * rstd) + ln.beta[ch], slope);
+                    if (!A.is_last) A.hout[row * HD + ch] = act; else lds[ch] = act;
+                }
+            }
         }
         if (A.is_last) {
             __syncthreads();
@@ -1868,8 +1942,8 @@ __device__ __forceinline__ void edge_fwd_generic_body(const EdgeFwdArgs& A, cons
     }
 }
 __global__ __launch_bounds__(64) void edge_fwd_generic(EdgeFwdArgs A, DropArgs dr) { edge_fwd_generic_body<false>(A, dr, nullptr, nullptr); }
-__global__ __launch_bounds__(64) void edge_fwd_generic_res(EdgeFwdArgs A, DropArgs dr, const float* res, const float* bias) {
-    edge_fwd_generic_body<true>(A, dr, res, bias);
+__global__ __launch_bounds__(64) void edge_fwd_generic_res(EdgeFwdArgs A, DropArgs dr, const float* res, const float* bias, LnArgs ln) {
+    edge_fwd_generic_body<true>(A, dr, res, bias, ln);
 }
 
 __global__ __launch_bounds__(64) void edge_bwd_generic(EdgeBwdArgs A, DropArgs dr) {
@@ -2173,10 +2247,12 @@ int edge_stash_words(int32_t H, int32_t D) {
     return n ? H * D / n : 0;
 }
 
-int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const DropArgs* drop, const float* res, const float* bias) {
+int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const DropArgs* drop, const float* res, const float* bias, const LnArgs* ln) {
     if (a.n_rows <= 0) return 0;
     DropArgs dr = drop != nullptr ? *drop : DropArgs{};
-    const bool with_res = res != nullptr || bias != nullptr;
+    const LnArgs lna = (ln != nullptr && ln->gamma != nullptr) ? *ln : LnArgs{};
+    if (lna.gamma != nullptr && lna.beta == nullptr) return fail(GAT_E_INVALID, "edge_forward: layer normalisation without beta");
+    const bool with_res = res != nullptr || bias != nullptr || lna.gamma != nullptr;    // the RES forms: residual, bias, norm
     if (edge_fast_path(a.H, a.D, a.n_table)) {
         if (a.items == nullptr) return fail(GAT_E_INVALID, "edge_forward: work-item list missing");
         if (a.mstat == nullptr || a.zstat == nullptr) return fail(GAT_E_INVALID, "edge_forward: stats buffers missing");
@@ -2186,14 +2262,14 @@ int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const DropArgs* dro
         }
         const EdgePick p = pick_forward(a, dr.on != 0, with_res);
         EdgeFwdDropArgs ad;                              // the argument struct of the DROP instantiations
-        if (dr.on) { static_cast<EdgeFwdArgs&>(ad) = a; ad.drop = dr; ad.res = res; ad.bias = bias; }
+        if (dr.on) { static_cast<EdgeFwdArgs&>(ad) = a; ad.drop = dr; ad.res = res; ad.bias = bias; ad.ln = lna; }
         void* args[] = {dr.on ? (void*)&ad : (void*)const_cast<EdgeFwdArgs*>(&a)};
         GAT_HIP(hipLaunchKernel(p.fn, dim3((unsigned)((a.n_items + p.per_block - 1) / p.per_block)), dim3(p.block), args, 0, s));
         return launch_fwd_fix(p, a, with_res ? (void*)&ad : (void*)const_cast<EdgeFwdArgs*>(&a), s);
     }
     const int HD = a.H * a.D;
     const int64_t blocks = a.n_rows < kGenericBlocks * 8 ? a.n_rows : kGenericBlocks * 8;
-    if (with_res) hipLaunchKernelGGL(edge_fwd_generic_res, dim3((unsigned)blocks), dim3(64), (size_t)HD * sizeof(float), s, a, dr, res, bias);
+    if (with_res) hipLaunchKernelGGL(edge_fwd_generic_res, dim3((unsigned)blocks), dim3(64), (size_t)HD * sizeof(float), s, a, dr, res, bias, lna);
     else hipLaunchKernelGGL(edge_fwd_generic, dim3((unsigned)blocks), dim3(64), (size_t)HD * sizeof(float), s, a, dr);
     GAT_HIP(hipGetLastError());
     return 0;

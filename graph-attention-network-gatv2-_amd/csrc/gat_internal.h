@@ -143,12 +143,21 @@ void build_worklist(const int32_t* row_ptr, int64_t n_rows, WorkList& w);
 // res / bias (optional, gatv2_abi.h "residual"): h_pre[row][c] += res[row][c] + bias[c] in the row epilogue, before h_pre and hout
 // are written (split rows: once, in the fix-up kernel's combine).  Either one selects the DROP instantiations too — with nothing
 // dropped when drop is null or off — whose argument struct carries the two pointers.
+// ln (optional, gatv2_abi.h "layer normalisation"): with ln->gamma set, the row u = h_pre (residual term included) is normalised over
+// its H*D channels in the same epilogue, v = gamma * (u - mu) * rstd + beta, and hout = LReLU(v); h_pre stays u.  It selects the DROP
+// instantiations and their fix-up form like res / bias, and travels in the same argument struct.
+struct LnArgs {
+    const float* gamma = nullptr; // [HD], null: no normalisation
+    const float* beta = nullptr;  // [HD]
+    float eps = 0.f;
+};
 int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const DropArgs* drop = nullptr, const float* res = nullptr,
-                        const float* bias = nullptr);
+                        const float* bias = nullptr, const LnArgs* ln = nullptr);
 struct EdgeFwdDropArgs : EdgeFwdArgs {
     DropArgs drop;
     const float* res = nullptr;   // [n_rows][HD] R = x' Wres^T of the shard's own rows, or null
     const float* bias = nullptr;  // [HD], or null
+    LnArgs ln;
 };
 
 struct EdgeBwdArgs {
@@ -399,6 +408,24 @@ struct ResBwdArgs {
 constexpr int kResPartialRows = 1024;
 int res_backward_blocks(int64_t n_rows, int32_t HD);
 int launch_res_backward(const ResBwdArgs& a, hipStream_t s);
+
+// ---- layer normalisation (gatv2_abi.h "layer normalisation") ---------------------------------------------------
+// The N-sized pass of a NORMALISED layer's backward, in res_backward's place.  Per row it recomputes mu, rstd and
+// v = gamma * xhat + beta from u = r.hpre (two passes, as the forward), takes dL/dhout from r.g (hidden) or r.gh / H (last layer),
+// dv = dL/dhout * LReLU'(v), and writes
+//   G[n][c]   = rstd * (dxh - mean_c dxh - xhat * mean_c (dxh * xhat)),  dxh = dv * gamma        (r.G)
+//   agg[n][c] = u - (res + bias)                                                                (r.agg; null: not written)
+// with per-block fixed-order column sums  part_gamma = sum dv * xhat,  part_beta = sum dv,  r.partial = sum G  (each [blocks][HD], null:
+// not formed), blocks = norm_backward_blocks(...) <= kResPartialRows; finished by launch_reduce_partials_add.  r.g_raw is not read.
+// Any H*D >= 1: rows wider than one pass of the row's lanes are walked in rounds.
+struct NormBwdArgs {
+    ResBwdArgs r;
+    const float* gamma; const float* beta;
+    float* part_gamma; float* part_beta;
+    float eps;
+};
+int norm_backward_blocks(int64_t n_rows, int32_t HD);
+int launch_norm_backward(const NormBwdArgs& a, hipStream_t s);
 
 struct HeadArgs {
     const float* Wo;          // [C][DL]

@@ -27,6 +27,9 @@
 // --residual / --bias: every layer adds Wres x' / b to h_pre (gatv2_abi.h "residual"); Wres is Xavier-initialised from --seed after the
 // other parameters (which keep their values), b starts at 0.  --dump-params / --load-params then carry the groups Wres and b behind
 // W, a and Wo — only the groups whose flag is on, so files written without the flags keep their format.
+// --layer-norm [--norm-eps X] [--norm-skip-last]: LayerNorm over each row's H*D channels between the aggregation and the LeakyReLU
+// (gatv2_abi.h "layer normalisation"; eps default 1e-5; --norm-skip-last leaves the last layer un-normalised); gamma starts at 1, beta
+// at 0, and --dump-params / --load-params carry gamma and beta behind the residual groups, only with the flag.
 // --add-self-loops / --undirected / --coalesce: the graph is rebuilt on the device before training (gat_graph_from_coo:
 // GAT_GRAPH_SELF_LOOPS / SYMMETRIZE / COALESCE, applied in that order); a CSR dataset is expanded to an edge list first.
 // Edge-list dataset: a folder with edges.txt (one "src dst" pair per line, a message flows src -> dst) instead of
@@ -82,6 +85,7 @@ struct Options {
     float dropout = 0.f, attn_dropout = 0.f;
     float drop_edge = 0.f; int drop_edge_flags = 0;   // GAT_DROPEDGE_*: --drop-edge-keep-self, --drop-edge-shared
     int residual_flags = 0;                           // GAT_RES_*: --residual, --bias
+    int norm_flags = 0; float norm_eps = 1e-5f;       // GAT_NORM_*: --layer-norm, --norm-skip-last; --norm-eps
     int graph_flags = 0;                  // GAT_GRAPH_*: --add-self-loops, --undirected, --coalesce
 };
 
@@ -104,6 +108,8 @@ const char* kUsage =
     "            --residual         every layer adds Wres x' to h_pre (a skip connection through a learned linear map)\n"
     "            --bias             every layer adds a learned bias b to h_pre\n"
     "                          (--dump-params / --load-params then append Wres and b behind W, a and Wo)\n"
+    "            --layer-norm [--norm-eps X] [--norm-skip-last]   LayerNorm over each row's H*D channels before the LeakyReLU\n"
+    "                          (eps X, default 1e-5 / not in the last layer; gamma and beta follow b in --dump-params / --load-params)\n"
     "            --ranks P [--transport rccl|host] [--halo 0|1|2]\n";
 
 struct RankEnv {                      // one forked process per GPU
@@ -186,6 +192,9 @@ Options parse_args(int argc, char** argv) {
         else if (a == "--drop-edge-shared") o.drop_edge_flags |= GAT_DROPEDGE_SHARED_LAYERS;
         else if (a == "--residual") o.residual_flags |= GAT_RES_LINEAR;
         else if (a == "--bias") o.residual_flags |= GAT_RES_BIAS;
+        else if (a == "--layer-norm") o.norm_flags |= GAT_NORM_LAYER;
+        else if (a == "--norm-skip-last") o.norm_flags |= GAT_NORM_SKIP_LAST;
+        else if (a == "--norm-eps" && has_val) o.norm_eps = std::strtof(argv[++i], nullptr);
         else if (a == "--transport" && has_val) {
             o.transport = argv[++i];
             if (o.transport != "rccl" && o.transport != "host") die("Invalid transport choice. Use 'rccl' or 'host'\n");
@@ -465,9 +474,11 @@ int run(const Options& o, const RankEnv& env) {
     check(gat_create(&cfg, &ctx), "gat_create");
     // residual / bias: before anything sizes the packed buffers; every rank of --ranks runs this with the same options
     if (o.residual_flags) check(gat_set_residual(ctx, o.residual_flags), "gat_set_residual");
-    int64_t nW = 0, nA = 0, nWo = 0, nWres = 0, nB = 0;
+    if (o.norm_flags) check(gat_set_norm(ctx, o.norm_flags, o.norm_eps), "gat_set_norm");
+    int64_t nW = 0, nA = 0, nWo = 0, nWres = 0, nB = 0, nLnG = 0, nLnB = 0;
     gat_param_count(ctx, GAT_PARAM_W, &nW); gat_param_count(ctx, GAT_PARAM_A, &nA); gat_param_count(ctx, GAT_PARAM_WO, &nWo);
     gat_param_count(ctx, GAT_PARAM_WRES, &nWres); gat_param_count(ctx, GAT_PARAM_B, &nB);     // 0 without the flags
+    gat_param_count(ctx, GAT_PARAM_LN_G, &nLnG); gat_param_count(ctx, GAT_PARAM_LN_B, &nLnB);
     if (env.world == 1) {
         check(gat_set_graph(ctx, row_ptr.data(), col_idx.data(), N, E, N, 0), "csr_to_coo_kernel");
         check(gat_set_features(ctx, x.data(), N, F0), "gat_set_features");
@@ -500,7 +511,7 @@ int run(const Options& o, const RankEnv& env) {
         } else {
             int64_t hd_max = 0;
             for (int l = 0; l < L; ++l) hd_max = std::max<int64_t>(hd_max, (int64_t)o.heads[l] * o.outdims[l]);
-            const int64_t bytes = std::max<int64_t>(plan.n_table() * hd_max + 64, nW + nA + nWo + nWres + nB + 3) * (int64_t)sizeof(float);   // (+ 64: block offsets of a halo exchange)
+            const int64_t bytes = std::max<int64_t>(plan.n_table() * hd_max + 64, nW + nA + nWo + nWres + nB + nLnG + nLnB + 3) * (int64_t)sizeof(float);   // (+ 64: block offsets of a halo exchange)
             check(gat_comm_init_host(ctx, env.world, env.rank, env.shm_name.c_str(), bytes), "gat_comm_init_host");
         }
         if (o.halo != 0) check(gat_comm_option(ctx, GAT_COMM_HALO, o.halo), "gat_comm_option(GAT_COMM_HALO)");      // collective: every rank
@@ -545,7 +556,7 @@ int run(const Options& o, const RankEnv& env) {
     if (o.drop_edge > 0.f) check(gat_set_dropedge(ctx, o.drop_edge, o.drop_edge_flags), "gat_set_dropedge");
     check(gat_params_init(ctx, o.seed), "xavier_init_kernel");
     if (!o.load_params.empty()) {
-        std::vector<float> p(nW + nA + nWo + nWres + nB);    // the residual groups follow the others, only with their flags
+        std::vector<float> p(nW + nA + nWo + nWres + nB + nLnG + nLnB);    // the residual and norm groups follow the others, only with their flags
         std::ifstream f(o.load_params, std::ios::binary);
         if (!f.read(reinterpret_cast<char*>(p.data()), p.size() * sizeof(float))) die("Error: cannot read --load-params file\n");
         check(gat_params_set(ctx, GAT_PARAM_W, p.data(), nW), "gat_params_set");
@@ -553,6 +564,8 @@ int run(const Options& o, const RankEnv& env) {
         check(gat_params_set(ctx, GAT_PARAM_WO, p.data() + nW + nA, nWo), "gat_params_set");
         if (nWres) check(gat_params_set(ctx, GAT_PARAM_WRES, p.data() + nW + nA + nWo, nWres), "gat_params_set");
         if (nB) check(gat_params_set(ctx, GAT_PARAM_B, p.data() + nW + nA + nWo + nWres, nB), "gat_params_set");
+        if (nLnG) check(gat_params_set(ctx, GAT_PARAM_LN_G, p.data() + nW + nA + nWo + nWres + nB, nLnG), "gat_params_set");
+        if (nLnB) check(gat_params_set(ctx, GAT_PARAM_LN_B, p.data() + nW + nA + nWo + nWres + nB + nLnG, nLnB), "gat_params_set");
     }
 
     size_t free_after = 0;
@@ -593,12 +606,14 @@ int run(const Options& o, const RankEnv& env) {
     }
 
     if (!o.dump_params.empty() && env.rank == 0) {
-        std::vector<float> p(nW + nA + nWo + nWres + nB);    // without --residual / --bias: the format of always
+        std::vector<float> p(nW + nA + nWo + nWres + nB + nLnG + nLnB);    // without --residual / --bias / --layer-norm: the format of always
         check(gat_params_get(ctx, GAT_PARAM_W, p.data(), nW), "gat_params_get");
         check(gat_params_get(ctx, GAT_PARAM_A, p.data() + nW, nA), "gat_params_get");
         check(gat_params_get(ctx, GAT_PARAM_WO, p.data() + nW + nA, nWo), "gat_params_get");
         if (nWres) check(gat_params_get(ctx, GAT_PARAM_WRES, p.data() + nW + nA + nWo, nWres), "gat_params_get");
         if (nB) check(gat_params_get(ctx, GAT_PARAM_B, p.data() + nW + nA + nWo + nWres, nB), "gat_params_get");
+        if (nLnG) check(gat_params_get(ctx, GAT_PARAM_LN_G, p.data() + nW + nA + nWo + nWres + nB, nLnG), "gat_params_get");
+        if (nLnB) check(gat_params_get(ctx, GAT_PARAM_LN_B, p.data() + nW + nA + nWo + nWres + nB + nLnG, nLnB), "gat_params_get");
         std::ofstream f(o.dump_params, std::ios::binary);
         f.write(reinterpret_cast<const char*>(p.data()), p.size() * sizeof(float));
     }

@@ -180,18 +180,21 @@ int gat_graph_check_device(const int32_t* d_row_ptr, const int32_t* d_col_idx, i
 
 /* ---- parameters (Xavier init E:186-248; flat layouts E:1242-1258) ---------------------------
  * GAT_PARAM_WRES flat [l][H_l*D_l][F_l] and GAT_PARAM_B flat [l][H_l*D_l] exist on a context with gat_set_residual (see
- * "residual" below); with their flag off the group's count is 0 and a set / get of 0 floats is a no-op that succeeds. */
-enum { GAT_PARAM_W = 0, GAT_PARAM_A = 1, GAT_PARAM_WO = 2, GAT_PARAM_WRES = 3, GAT_PARAM_B = 4 };
+ * "residual" below); with their flag off the group's count is 0 and a set / get of 0 floats is a no-op that succeeds.
+ * GAT_PARAM_LN_G / GAT_PARAM_LN_B, each flat [l][H_l*D_l] over all L layers, exist on a context with gat_set_norm (see "layer
+ * normalisation" below) and sit behind the other five; off, their counts are 0 as well. */
+enum { GAT_PARAM_W = 0, GAT_PARAM_A = 1, GAT_PARAM_WO = 2, GAT_PARAM_WRES = 3, GAT_PARAM_B = 4, GAT_PARAM_LN_G = 5, GAT_PARAM_LN_B = 6 };
 int gat_param_count(gat_ctx* ctx, int group, int64_t* count);
 /* U(-lim,lim], lim as E:208, 236.  With GAT_RES_LINEAR: Wres_l Xavier-uniform with lim = sqrt(6 / (F_l + H_l*D_l)), drawn from the same
- * counter stream AFTER all existing draws (layer by layer), so W, a and Wo of a seed are those of a context without it; b = 0. */
+ * counter stream AFTER all existing draws (layer by layer), so W, a and Wo of a seed are those of a context without it; b = 0.
+ * With gat_set_norm: gamma = 1, beta = 0, no draws. */
 int gat_params_init(gat_ctx* ctx, uint64_t seed);
 int gat_params_set(gat_ctx* ctx, int group, const float* host, int64_t count);
 int gat_params_get(gat_ctx* ctx, int group, float* host, int64_t count);
 int gat_grads_get(gat_ctx* ctx, int group, float* host, int64_t count);
 int gat_grads_set(gat_ctx* ctx, int group, const float* host, int64_t count);
-/* Device address of the packed gradient buffer [gradW | grada | gradWo | gradWres | gradb] (for the all-reduce; the last two
- * groups only with gat_set_residual).  count = n_params, the sum of the five group counts; the three-float result tail of
+/* Device address of the packed gradient buffer [gradW | grada | gradWo | gradWres | gradb | gradgamma | gradbeta] (for the all-reduce;
+ * groups 3 and 4 only with gat_set_residual, 5 and 6 only with gat_set_norm).  count = n_params, the sum of the seven group counts; the three-float result tail of
  * gat_result_export sits behind it, and the host transport's bytes_per_rank rule stays (n_params + 3) * 4. */
 int gat_grads_device(gat_ctx* ctx, void** d_ptr, int64_t* count);
 /* Async D2D copies of the packed gradients on the context's stream, to / from a caller-owned
@@ -437,6 +440,56 @@ int gat_set_dropedge(gat_ctx* ctx, float edge_p, int32_t flags);
  *   GAT_RES_LINEAR.  gat_algorithmic_bytes_shape has no context and prices the model without the feature. */
 enum { GAT_RES_LINEAR = 1, GAT_RES_BIAS = 2 };
 int gat_set_residual(gat_ctx* ctx, int32_t flags);
+
+/* ---- layer normalisation between the aggregation and the activation (beyond the reference; PyG's GAT takes norm="layer") ------
+ * With GAT_NORM_LAYER every layer l — with GAT_NORM_SKIP_LAST every layer but the last — computes, with u[n,c] = h_pre exactly as
+ * without the feature (attention dropout, DropEdge, Wres x' and b included) and c = h*D + d over the HD = H_l*D_l channels of the row,
+ *     mu[n]   = (1/HD) sum_c u[n,c]
+ *     var[n]  = (1/HD) sum_c (u[n,c] - mu[n])^2          (biased; two passes over the on-chip row, not E[u^2] - mu^2)
+ *     rstd[n] = 1 / sqrt(var[n] + eps)
+ *     v[n,c]  = gamma_l[c] * (u[n,c] - mu[n]) * rstd[n] + beta_l[c]
+ *     hout    = LReLU(v)      hidden layers: concatenated; last layer: mean over heads of LReLU(v), as E:440-457 does with h_pre
+ * Everything upstream of u is unchanged: the score, the softmax statistics, alpha, and GAT_TAP_HPRE, which keeps returning u.
+ * A row without in-edges (also one DropEdge emptied, and a padding row of a shard) has u = 0 without residual flags, hence v = beta and
+ * hout = LReLU(beta); with residual flags u = Wres x' + b is normalised like any row.  H*D = 1 gives var = 0 and v = beta; nothing
+ * becomes NaN or Inf for a finite u.
+ * Backward, with xhat = (u - mu) * rstd and dv = dL/dhout (.) LReLU'(v) — dL/dhout being the hidden g written by grad_x, or gH / H of
+ * the head; the factor is LReLU'(v), never LReLU'(h_pre), for every consumer of a normalised layer:
+ *     grad_gamma_l[c] = sum_n dv[n,c] * xhat[n,c]        grad_beta_l[c] = sum_n dv[n,c]
+ *     G[n,c] = rstd[n] * (dxh[n,c] - mean_c dxh[n,.] - xhat[n,c] * mean_c (dxh (.) xhat)[n,.]),   dxh = dv (.) gamma_l
+ * and G = dL/dh_pre plays the role it plays in a residual context: the edge backward takes G and agg = u - (R + b),
+ * gradWres = G^T x', grad_b = sum_n G, grad_x += G Wres.
+ * Parameters: GAT_PARAM_LN_G and GAT_PARAM_LN_B, flat [l][H_l*D_l] over ALL L layers, behind the five other groups in the packed
+ *   parameter, gradient and Adam buffers (gat_grads_device reports the new n_params; the result tail stays behind it).  With
+ *   GAT_NORM_SKIP_LAST the last layer's entries exist, are never read, and their gradients are exactly 0.  gat_params_init sets
+ *   gamma = 1, beta = 0 and makes no draws.  gat_zero_grad, gat_step_sgd and gat_step_adam cover the groups; gat_clip clips each by
+ *   its own norm.
+ * Where it runs.  Forward: in the row epilogue of the edge forward, after the residual term, before h_pre (still u) and hout are
+ *   written once — whole rows in the wave-per-row / group-per-row kernels, split hub rows once in the fix-up kernel's combine, the
+ *   generic kernel alike.  The two sums over the row's lanes are butterfly sums in a fixed order.  A norm context runs the DROP
+ *   instantiations of the forward, like a residual context; gamma, beta and eps travel in their argument struct.  No N-sized forward
+ *   kernel, no N-sized forward traffic; the default-path instantiations are untouched.
+ *   Backward: one N-sized kernel per normalised layer in the residual kernel's place.  It reads u, the output gradient, R, b, gamma
+ *   and beta, recomputes mu, rstd and v (the forward stores nothing extra), writes G and agg, and per-block fixed-order column sums for
+ *   grad_gamma, grad_beta and (GAT_RES_BIAS) grad_b, finished by the slab reduction: no float atomics, bitwise reproducible on the
+ *   fast families.  A norm context without residual flags takes the same route (agg = u).  Every H*D the generic path allows.
+ *   Downstream is the code of a residual context; GAT_FUSE_LAST and the last layer's decision-byte pull form are not used.
+ * Taps: GAT_TAP_HOUT returns LReLU(v); GAT_TAP_G returns G = dL/dh_pre of any layer, recomputed on the device from the layer's stored
+ *   output gradient and h_pre by the backward kernel's row function.
+ * gat_set_norm follows gat_set_residual's state rules: only BEFORE the first gat_params_*, gat_grads_*, gat_set_graph* call (later:
+ *   GAT_E_STATE), before or after gat_set_residual.  Unknown flag bits, GAT_NORM_SKIP_LAST without GAT_NORM_LAYER, and — with
+ *   flags != 0 — an eps that is not finite and > 0 (NaN included): GAT_E_INVALID.  flags == 0 ignores eps and leaves the context
+ *   exactly as it is.  A context created with flat_lrelu_index = 1: GAT_E_UNSUPPORTED (the reference's flat index has no meaning on
+ *   v); the experiment library with GAT_DBG set: GAT_E_UNSUPPORTED.
+ * Works with every (H, D) family incl. both generic ones, bf16 storage (the norm arithmetic, G and agg stay fp32), keep_taps, the
+ *   phase API (gat_layer_forward_edges normalises, gat_layer_backward_edges runs the N-sized kernel first), gat_step, gat_step_graph
+ *   replay, training masks, eval mode, all three regularisers, and shards on any transport: statistics are row-local, nothing more
+ *   is exchanged, and the parameter-gradient all-reduce sums the new groups.
+ * gat_algorithmic_bytes (context form): unchanged with the feature off.  On, every layer is priced on the residual route (misc +=
+ *   N*HD * 4 at 4 bytes without GAT_RES_LINEAR: u + g read, G + agg written — already counted in a residual context), and each
+ *   normalised layer adds 2*HD floats of parameters per pass to misc.  gat_algorithmic_bytes_shape prices the model without it. */
+enum { GAT_NORM_LAYER = 1, GAT_NORM_SKIP_LAST = 2 };
+int gat_set_norm(gat_ctx* ctx, int32_t flags, float eps);
 
 /* ---- op-level entry points, whole layers: caller-provided DEVICE pointers in the reference layouts
  *      (unit parity).  `stream` may be NULL (default stream).  One entry point per reference KERNEL: below. ---- */

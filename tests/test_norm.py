@@ -1,0 +1,540 @@
+"""Layer normalisation on the GPU (include/gatv2_abi.h "layer normalisation"): off is off, parity of every dispatcher family
+against the fp64 model of tests/norm_ref.py (norm only and norm + both residual flags; plain and with all three regularisers; one
+skip_last case), empty and emptied rows, H*D = 1, rows wider than one round of the backward kernel, a three-layer model, the step
+paths against each other, eval mode, the optimizer, init and dump / load, shards, error codes.
+
+The graph is parity_graph of tests/test_residual.py: 150 nodes, 700 edges, F = 24, C = 5, one empty row (3) and a hub row (7) of 300
+in-edges that is processed as segments — the smallest shapes that reach the split-row combine, the empty row and every family."""
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+
+import dropedge_ref as E
+import norm_ref as NR
+import parity
+import residual_ref as RR
+from conftest import small_graph
+from test_dropedge import FAMILIES, make_graph
+from test_residual import REG, masks, parity_graph
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "graph-attention-network-gatv2-_amd", "train_edge")
+
+MODES = [("norm", False, False), ("norm_res", True, True)]       # (name, GAT_RES_LINEAR, GAT_RES_BIAS)
+EPS = 1e-5
+GROUPS = "W a Wo Wres b gamma beta".split()
+
+
+def lrelu(t, slope=0.01):
+    return np.where(t > 0, t, slope * t)
+
+
+def pick_params(orc, cfg, g, mode, reg=None, bf16=False, skip_last=False, keeps=None):
+    """First parameter seed (of 40) whose fp64 model keeps every |s| above 1e-5 and every |v| above 1e-4: no kink correction is needed.
+    -> (W, a, Wo), Wres | None, b | None, gamma, beta, the model's outputs."""
+    _, lin, bias = mode
+    k, attn, feat = masks(cfg, g, cfg.heads, reg)
+    keeps = k if keeps is None else keeps
+    for ps in range(40):
+        P = orc.xavier_params(cfg, ps)
+        Wres, b = RR.xavier_wres(cfg, ps)
+        Wres, b = (Wres if lin else None), (b if bias else None)
+        gamma, beta = NR.ln_params(cfg, ps)
+        ref = NR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, Wres=Wres, b=b, gamma=gamma, beta=beta, eps=EPS,
+                         skip_last=skip_last, keeps=keeps, attn=attn, feat=feat, bf16_pl=bf16)
+        if ref["s_min"] > 1e-5 and ref["v_min"] > 1e-4:
+            return P, Wres, b, gamma, beta, ref
+    raise AssertionError("no parameter seed clear of the LeakyReLU kink")
+
+
+ROWS_PE, ROWS_SEED = 0.9, 1
+
+
+def rows_keeps(g):
+    return [E.edge_keep(ROWS_SEED, 1, l, g["row_ptr"], g["col_idx"], ROWS_PE) for l in range(2)]
+
+
+def pick_rows_params(orc, cfg, g, mode):
+    return pick_params(orc, cfg, g, mode, keeps=rows_keeps(g))
+
+
+def make_ctx(pkg, g, heads, outdims, P, mode, Wres, b, gamma, beta, reg=None, skip_last=False, **kw):
+    A = pkg.abi
+    ctx = pkg.GatContext(heads, outdims, g["f"], g["c"], **kw)
+    ctx.set_norm(skip_last=skip_last, eps=EPS)
+    if mode[1] or mode[2]:
+        ctx.set_residual(linear=mode[1], bias=mode[2])           # after gat_set_norm: either order is allowed
+    ctx.set_graph(g["row_ptr"], g["col_idx"])
+    ctx.set_features(g["x"])
+    ctx.set_labels(g["labels"])
+    for grp, arr in zip((A.PARAM_W, A.PARAM_A, A.PARAM_WO, A.PARAM_WRES, A.PARAM_B, A.PARAM_LN_G, A.PARAM_LN_B), (*P, Wres, b, gamma, beta)):
+        if arr is not None:
+            ctx.params_set(grp, arr)
+    if reg is not None:
+        ctx.set_dropout(reg["pf"], reg["pa"], seed=reg["seed"], first_step=0)
+        ctx.set_dropedge(reg["pe"])
+    ctx.zero_grad()
+    return ctx
+
+
+def all_grads(pkg, ctx):
+    return [ctx.grads_get(k) for k in range(7)]
+
+
+def compare(pkg, ctx, g, cfg, ref, loss, tol):
+    """loss / N, every layer's h_pre, GAT_TAP_HOUT, GAT_TAP_G and all seven gradient groups at tol of max-abs (recorded)."""
+    A = pkg.abi
+    n = g["n"]
+    parity.record("loss/N", abs(loss / n - ref["loss"].item() / n), tol, kind="abs")
+    assert abs(loss / n - ref["loss"].item() / n) < tol, (loss / n, ref["loss"].item() / n)
+    for l in range(cfg.L):
+        for name, tap, want in (("hpre", A.TAP_HPRE, ref["hpre"][l]), ("hout", A.TAP_HOUT, ref["hout"][l]), ("G", A.TAP_G, ref["hpre"][l].grad)):
+            want = want.detach().numpy()
+            assert np.abs(want).max() > 0
+            parity.check_rel(f"{name}[{l}]", ctx.tap(tap, l).reshape(want.shape), want, tol)
+    for name, got in zip(GROUPS, all_grads(pkg, ctx)):
+        leaf = ref[name]
+        if leaf is None:
+            assert got.size == 0, name
+            continue
+        want = leaf.grad.numpy()
+        assert got.shape == want.shape and np.abs(want).max() > 0
+        parity.check_rel(f"grad {name}", got, want, tol)
+
+
+def test_off_is_off(pkg, orc):
+    A = pkg.abi
+    g = make_graph(1)
+    cfg = orc.Config([8, 8], [8, 8], g["f"], g["c"])
+    P = orc.xavier_params(cfg, 3)
+
+    def ctx_of(touch):
+        ctx = pkg.GatContext([8, 8], [8, 8], g["f"], g["c"], collect_timing=True)
+        if touch:
+            ctx.set_norm(layer=False, eps=float("nan"))      # flags == 0: eps is ignored
+        ctx.set_graph(g["row_ptr"], g["col_idx"]); ctx.set_features(g["x"]); ctx.set_labels(g["labels"])
+        for grp, arr in zip((A.PARAM_W, A.PARAM_A, A.PARAM_WO), P):
+            ctx.params_set(grp, arr)
+        ctx.zero_grad()
+        return ctx
+    with ctx_of(False) as a, ctx_of(True) as b:
+        assert b.param_count(A.PARAM_LN_G) == 0 and b.param_count(A.PARAM_LN_B) == 0
+        b.params_set(A.PARAM_LN_G, np.zeros(0, np.float32))
+        assert b.params_get(A.PARAM_LN_B).size == 0
+        assert a.n_params == b.n_params
+        for c in (a, b):
+            c.kernel_stats_reset()
+        ra, rb = a.step(), b.step()
+        assert ra == rb
+        for x, y in zip(all_grads(pkg, a), all_grads(pkg, b)):
+            assert np.array_equal(x, y)
+        for l in range(2):
+            assert np.array_equal(a.tap(A.TAP_HPRE, l), b.tap(A.TAP_HPRE, l))
+        sa, sb = a.kernel_stats(), b.kernel_stats()
+        assert {k: v[0] for k, v in sa.items()} == {k: v[0] for k, v in sb.items()}      # the same launches, class by class
+        assert a.algorithmic_bytes() == b.algorithmic_bytes()
+
+
+@pytest.mark.parametrize("reg", [None, REG], ids=["plain", "regularised"])
+@pytest.mark.parametrize("mode", MODES, ids=[m[0] for m in MODES])
+@pytest.mark.parametrize("name,heads,outdims,kw", FAMILIES, ids=[f[0] for f in FAMILIES])
+def test_parity_against_fp64(pkg, orc, name, heads, outdims, kw, mode, reg):
+    g = parity_graph()
+    cfg = orc.Config(heads, outdims, g["f"], g["c"])
+    bf16 = kw.get("dtype") == "bf16"
+    P, Wres, b, gamma, beta, ref = pick_params(orc, cfg, g, mode, reg, bf16=bf16)
+    ref["loss"].backward()
+    with make_ctx(pkg, g, heads, outdims, P, mode, Wres, b, gamma, beta, reg, **kw) as ctx:
+        loss, _ = ctx.step()
+        compare(pkg, ctx, g, cfg, ref, loss, 1e-2 if bf16 else 1e-4)
+
+
+def test_skip_last(pkg, orc):
+    """GAT_NORM_SKIP_LAST: the last layer is the residual layer of always; its gamma / beta entries exist, are never read — NaN in
+    them changes nothing — and their gradients are exactly 0."""
+    A = pkg.abi
+    g = parity_graph()
+    heads, outdims = [8, 8], [8, 8]
+    cfg = orc.Config(heads, outdims, g["f"], g["c"])
+    P, Wres, b, gamma, beta, ref = pick_params(orc, cfg, g, MODES[1], skip_last=True)
+    ref["loss"].backward()
+    gamma, beta = gamma.copy(), beta.copy()
+    gamma[64:] = np.nan; beta[64:] = np.nan
+    with make_ctx(pkg, g, heads, outdims, P, MODES[1], Wres, b, gamma, beta, skip_last=True) as ctx:
+        assert ctx.param_count(A.PARAM_LN_G) == 128 and ctx.param_count(A.PARAM_LN_B) == 128
+        loss, _ = ctx.step()
+        compare(pkg, ctx, g, cfg, ref, loss, 1e-4)
+        for k in (A.PARAM_LN_G, A.PARAM_LN_B):
+            assert (ctx.grads_get(k)[64:] == 0).all()
+
+
+@pytest.mark.parametrize("mode", MODES, ids=[m[0] for m in MODES])
+def test_empty_and_emptied_rows(pkg, orc, mode):
+    """Norm only: the empty row (3) and the rows DropEdge empties at p_e = 0.9 have hout = LReLU(beta) to 1e-6; with both residual
+    flags they are the model's rows (u = Wres x' + b, normalised like any row)."""
+    A = pkg.abi
+    g = parity_graph()
+    heads, outdims = [8, 8], [8, 8]
+    cfg = orc.Config(heads, outdims, g["f"], g["c"])
+    keeps = rows_keeps(g)
+    deg = np.diff(g["row_ptr"])
+    emptied = [np.flatnonzero((deg > 0) & (np.diff(E.reduce_graph(g["row_ptr"], g["col_idx"], k)[0]) == 0)) for k in keeps]
+    assert all(len(e) >= 1 for e in emptied)
+    P, Wres, b, gamma, beta, ref = pick_rows_params(orc, cfg, g, mode)
+    ref["loss"].backward()
+    with make_ctx(pkg, g, heads, outdims, P, mode, Wres, b, gamma, beta) as ctx:
+        ctx.set_dropout(0.0, 0.0, seed=ROWS_SEED)
+        ctx.set_dropedge(ROWS_PE)
+        loss, _ = ctx.step()
+        compare(pkg, ctx, g, cfg, ref, loss, 1e-4)
+        hout0 = ctx.tap(A.TAP_HOUT, 0).reshape(g["n"], 64)
+        want0 = ref["hout"][0].detach().numpy()
+        for r in [3] + list(emptied[0]):
+            if mode[0] == "norm":
+                assert np.abs(hout0[r] - lrelu(beta[:64].astype(np.float64))).max() <= 1e-6, r
+            else:
+                assert np.abs(hout0[r] - want0[r]).max() <= 1e-4 * np.abs(want0).max(), r
+                assert np.abs(hout0[r] - lrelu(beta[:64].astype(np.float64))).max() > 1e-3, r
+
+
+def test_one_channel_rows(pkg, orc):
+    """H*D = 1 in layer 0 (heads [1, 2], outdims [1, 8]): var = 0, v = beta — finite results and hout = LReLU(beta_0) in every row."""
+    A = pkg.abi
+    g = parity_graph()
+    heads, outdims = [1, 2], [1, 8]
+    cfg = orc.Config(heads, outdims, g["f"], g["c"])
+    P = orc.xavier_params(cfg, 1)
+    gamma, beta = NR.ln_params(cfg, 1)
+    with make_ctx(pkg, g, heads, outdims, P, MODES[0], None, None, gamma, beta) as ctx:
+        loss, _ = ctx.step()
+        assert np.isfinite(loss)
+        hout0 = ctx.tap(A.TAP_HOUT, 0)
+        assert np.abs(hout0 - lrelu(np.float64(beta[0]))).max() <= 1e-6
+        for l in range(2):
+            assert np.isfinite(ctx.tap(A.TAP_G, l)).all() and np.isfinite(ctx.tap(A.TAP_HOUT, l)).all()
+        # nothing reaches u through a one-channel normalisation: G = rstd * (dxh - mean dxh) is 0 up to the rounding of dxh = g gamma
+        g0 = ctx.tap(A.TAP_GX, 1)                                # dL/dhout of layer 0
+        assert np.abs(ctx.tap(A.TAP_G, 0)).max() <= 4 * 2.0 ** -24 / np.sqrt(EPS) * np.abs(g0).max() * abs(float(gamma[0]))
+        assert all(np.isfinite(x).all() for x in all_grads(pkg, ctx))
+
+
+# rows wider than one round of the backward kernel's row lanes: H*D = 65 (not a multiple of 4: one channel per lane, 64 lanes, two
+# rounds) and H*D = 260 (four channels per lane, two rounds); both on the generic edge kernels
+WIDE = [("hd65", [5, 2], [13, 8]), ("hd260", [20, 2], [13, 8])]
+
+
+def wide_graph():
+    """40 nodes, 200 edges, F = 12, one empty row: with 260 channels a larger graph leaves no seed clear of the kinks."""
+    rng = np.random.default_rng(9)
+    rp, ci = small_graph(rng, 40, 200, empty=(3,))
+    return dict(row_ptr=rp, col_idx=ci, x=rng.standard_normal((40, 12)).astype(np.float32), labels=rng.integers(0, 4, 40).astype(np.int32),
+                n=40, f=12, c=4)
+
+
+@pytest.mark.parametrize("name,heads,outdims", WIDE, ids=[w[0] for w in WIDE])
+def test_wide_rows(pkg, orc, name, heads, outdims):
+    g = wide_graph()
+    cfg = orc.Config(heads, outdims, g["f"], g["c"])
+    P, Wres, b, gamma, beta, ref = pick_params(orc, cfg, g, MODES[1])
+    ref["loss"].backward()
+    with make_ctx(pkg, g, heads, outdims, P, MODES[1], Wres, b, gamma, beta) as ctx:
+        loss, _ = ctx.step()
+        compare(pkg, ctx, g, cfg, ref, loss, 1e-4)
+
+
+@pytest.mark.parametrize("reg", [None, REG], ids=["plain", "regularised"])
+def test_three_layers(pkg, orc, reg):
+    g = parity_graph()
+    heads, outdims = [8, 8, 8], [8, 8, 8]
+    cfg = orc.Config(heads, outdims, g["f"], g["c"])
+    P, Wres, b, gamma, beta, ref = pick_params(orc, cfg, g, MODES[1], reg)
+    ref["loss"].backward()
+    with make_ctx(pkg, g, heads, outdims, P, MODES[1], Wres, b, gamma, beta, reg) as ctx:
+        loss, _ = ctx.step()
+        compare(pkg, ctx, g, cfg, ref, loss, 1e-4)
+
+
+@pytest.mark.parametrize("name,heads,outdims,kw", [f for f in FAMILIES if f[0] in ("records_d8", "msg_rows_d16", "generic")],
+                         ids=["records_d8", "msg_rows_d16", "generic"])
+def test_paths_agree(pkg, orc, name, heads, outdims, kw):
+    """As tests/test_residual.py::test_paths_agree: gat_step = gat_forward + gat_backward within 1e-5; the phase API = gat_backward
+    bitwise; a gat_step_graph replay = the eager step bitwise; two runs bitwise equal (generic: grad_W, fed by a float-atomic
+    scatter, at 1e-5 instead; the six other groups, the new ones among them, bitwise)."""
+    g = make_graph(2)
+    cfg = orc.Config(heads, outdims, g["f"], g["c"])
+    P = orc.xavier_params(cfg, 3)
+    Wres, b = RR.xavier_wres(cfg, 3)
+    gamma, beta = NR.ln_params(cfg, 3)
+
+    def new():
+        return make_ctx(pkg, g, heads, outdims, P, MODES[1], Wres, b, gamma, beta, **kw)
+
+    def same(xs, ys):
+        for i, (x, y) in enumerate(zip(xs, ys)):
+            if i == 0 and name == "generic":
+                assert np.abs(x - y).max() <= 1e-5 * np.abs(y).max()
+            else:
+                assert np.array_equal(x, y), i
+        return True
+    with new() as s1, new() as s2, new() as fb, new() as ph, new() as gr:
+        l1, l2 = s1.step(), s2.step()
+        g1, g2 = all_grads(pkg, s1), all_grads(pkg, s2)
+        assert l1 == l2 and same(g1, g2)                                                # two runs
+        assert all(np.abs(x).max() > 0 for x in g1)
+        lf = fb.forward(); fb.backward()
+        gf = all_grads(pkg, fb)
+        assert abs(lf[0] - l1[0]) <= 1e-5 * max(1.0, abs(l1[0])) and lf[1] == l1[1]
+        for x, y in zip(g1, gf):
+            assert np.abs(x - y).max() <= 1e-5 * np.abs(y).max()
+        for l in range(cfg.L):                                                          # the phase API
+            ph.layer_project(l); ph.layer_forward_edges(l)
+        lp = ph.head_forward(); ph.head_backward()
+        for l in range(cfg.L - 1, -1, -1):
+            ph.layer_backward_edges(l); ph.layer_backward_dense(l)
+        assert lp == lf and same(all_grads(pkg, ph), gf)
+        gr.step_graph(True)
+        for k in range(3):                                                              # eager warm-up, capture + launch, replay
+            gr.zero_grad()
+            lg = gr.step()
+            assert lg == l1, k
+            assert same(all_grads(pkg, gr), g1), k
+
+
+def test_eval_mode_keeps_the_norm(pkg, orc):
+    """set_training(False): the regularisers are off, the normalisation is not — the eval forward is the plain model's."""
+    A = pkg.abi
+    g = parity_graph()
+    heads, outdims = [8, 8], [8, 8]
+    cfg = orc.Config(heads, outdims, g["f"], g["c"])
+    P, Wres, b, gamma, beta, ref = pick_params(orc, cfg, g, MODES[1])
+    with make_ctx(pkg, g, heads, outdims, P, MODES[1], Wres, b, gamma, beta, REG) as ctx:
+        ctx.set_training(False)
+        loss, _ = ctx.forward()
+        assert abs(loss / g["n"] - ref["loss"].item() / g["n"]) < 1e-4
+        for l in range(2):
+            want = ref["hout"][l].detach().numpy()
+            parity.check_rel(f"eval hout[{l}]", ctx.tap(A.TAP_HOUT, l).reshape(want.shape), want, 1e-4)
+
+
+def _adam64(p, g, m, v, lr, b1, b2, eps, t):
+    m[:] = b1 * m + (1.0 - b1) * g
+    v[:] = b2 * v + (1.0 - b2) * g * g
+    p -= lr * (m / (1.0 - b1 ** t)) / (np.sqrt(v / (1.0 - b2 ** t)) + eps)
+
+
+def test_optimizer_moves_the_new_groups(pkg):
+    """One clip + Adam step and one SGD step on values written straight into a norm + residual context, against fp64 numpy at the bars
+    of tests/test_optimizer.py (sgd: 1 ulp of max(|p|, |lr g|); adam: t (1e-5 lr + 2^-23 max|p|); clip: norm 1e-5, direction 2^-23)."""
+    A = pkg.abi
+    F32 = np.float32
+    rng = np.random.default_rng(21)
+    groups = tuple(range(7))
+    thr = 5.0
+    lr, b1, b2, eps = (float(F32(v)) for v in (0.01, 0.9, 0.999, 1e-8))
+    with pkg.GatContext([8, 4], [8, 4], 37, 3) as ctx:
+        ctx.set_residual(linear=True, bias=True)
+        ctx.set_norm()                                           # after gat_set_residual: either order is allowed
+        counts = [ctx.param_count(k) for k in groups]
+        assert counts[5] == 64 + 16 and counts[6] == 64 + 16 and ctx.n_params == sum(counts)
+        p0 = [rng.standard_normal(n).astype(F32) for n in counts]
+        gr = [(rng.standard_normal(n) * s).astype(F32) for n, s in zip(counts, (0.01, 0.01, 0.01, 0.001, 0.01, 2.0, 3.0))]   # gamma, beta above thr
+        norms = [np.linalg.norm(x.astype(np.float64)) for x in gr]
+        assert norms[5] > 2 * thr and norms[6] > 2 * thr and abs(norms[5] - norms[6]) > 1 and all(nn < thr / 2 for nn in norms[:5])
+        for k, p, x in zip(groups, p0, gr):
+            ctx.params_set(k, p); ctx.grads_set(k, x)
+        ctx.clip(thr)
+        clipped = [ctx.grads_get(k) for k in groups]
+        for i in range(5):                                         # below the threshold: untouched, each group by its own norm
+            assert np.array_equal(clipped[i].view(np.uint32), gr[i].view(np.uint32))
+        for i in (5, 6):
+            c64, w64 = clipped[i].astype(np.float64), gr[i].astype(np.float64)
+            err = abs(np.linalg.norm(c64) / thr - 1.0)
+            parity.record(f"clip group {i}: |norm after / thr - 1|", err, 1e-5)
+            assert err <= 1e-5
+            s = float(c64 @ w64) / float(w64 @ w64)
+            assert 0 < s < 1 and float((np.abs(c64 - s * w64) / np.maximum(np.abs(c64), 1e-30)).max()) <= 2.0 ** -23
+        ctx.step_adam(lr, b1, b2, eps, 1)
+        pmax = max(float(np.abs(p).max()) for p in p0) + 3.2 * lr
+        after = []
+        for k, p, x in zip(groups, p0, clipped):
+            want = p.astype(np.float64)
+            _adam64(want, x.astype(np.float64), np.zeros(len(p)), np.zeros(len(p)), lr, b1, b2, eps, 1)
+            got = ctx.params_get(k)
+            assert float(np.abs(got - want).max()) <= 1e-5 * lr + 2.0 ** -23 * pmax, k
+            assert float(np.abs(got - p).max()) > 0.5 * lr        # the group moved
+            after.append(got)
+        slr = F32(0.37)
+        ctx.step_sgd(float(slr))
+        for k, p, x in zip(groups, after, clipped):
+            step = np.float64(slr) * x.astype(np.float64)
+            want = p.astype(np.float64) - step
+            ulp = np.spacing(np.maximum(np.abs(p), np.abs(step).astype(F32))).astype(np.float64)
+            assert float((np.abs(ctx.params_get(k) - want) / ulp).max()) <= 1.0, k
+        ctx.zero_grad()
+        assert all((ctx.grads_get(k) == 0).all() for k in groups)
+
+
+def test_params_init_keeps_the_other_groups(pkg):
+    A = pkg.abi
+    with pkg.GatContext([8, 4], [8, 4], 37, 3) as res, pkg.GatContext([8, 4], [8, 4], 37, 3) as nrm:
+        res.set_residual(linear=True, bias=True)
+        nrm.set_norm(); nrm.set_residual(linear=True, bias=True)
+        res.params_init(9); nrm.params_init(9)
+        for k in range(5):
+            assert np.array_equal(res.params_get(k), nrm.params_get(k)) and res.params_get(k).size > 0
+        assert (nrm.params_get(A.PARAM_LN_G) == 1).all() and nrm.params_get(A.PARAM_LN_G).size == 80
+        assert (nrm.params_get(A.PARAM_LN_B) == 0).all() and nrm.params_get(A.PARAM_LN_B).size == 80
+
+
+def _problem():
+    return make_graph(4, n=90, e=700, F=12, C=4)
+
+
+def _shard_inputs(orc, g):
+    cfg = orc.Config([8, 8], [8, 8], g["f"], g["c"])
+    return (*orc.xavier_params(cfg, 11), *RR.xavier_wres(cfg, 11), *NR.ln_params(cfg, 11))
+
+
+def _shard_worker(rank, world, outdir, shm, replicate):
+    sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import __graft_entry__ as entry
+    pkg = entry.load_package(); orc = entry.load_oracle()
+    g = _problem()
+    heads, outdims = [8, 8], [8, 8]
+    S = pkg.shard
+    plan = S.make_plan(g["row_ptr"], world, rank)
+    rp_l, ci_l = S.local_csr(plan, g["row_ptr"], g["col_idx"])
+    lo, hi = plan.row0, plan.row0 + plan.n_rows
+    ctx = pkg.GatContext(heads, outdims, g["f"], g["c"], device=0)
+    ctx.set_residual(linear=True, bias=True)
+    ctx.set_norm(eps=EPS)
+    ctx.set_graph(rp_l, ci_l, n_table=plan.n_table, table_row0=plan.table_row0)
+    if replicate:
+        ctx.set_source_features(plan.table_features(g["x"]))
+    else:
+        ctx.set_features(g["x"][lo:hi])
+    ctx.set_labels(g["labels"][lo:hi])
+    for grp, arr in enumerate(_shard_inputs(orc, g)):
+        ctx.params_set(grp, arr)
+    ctx.comm_init_host(world, rank, shm, 4 * max(plan.n_table * 64, ctx.n_params + 3))
+    ctx.zero_grad()
+    loss, correct = ctx.step()
+    grads = np.concatenate([ctx.grads_get(k) for k in range(7)])
+    np.savez(os.path.join(outdir, f"r{rank}.npz"), loss=loss, correct=correct, grads=grads)
+    ctx.close()
+
+
+@pytest.mark.parametrize("replicate", [False, True], ids=["exchange", "replicated_input"])
+@pytest.mark.parametrize("world", [2, 3])
+def test_shards_on_the_host_transport(pkg, orc, world, replicate):
+    """`world` processes sharing one GPU equal the single-GPU gradients at 1e-5 (all seven groups; the all-reduce sums the new ones)."""
+    import torch.multiprocessing as mp
+    g = _problem()
+    inp = _shard_inputs(orc, g)
+    with make_ctx(pkg, g, [8, 8], [8, 8], inp[:3], MODES[1], *inp[3:]) as one:
+        loss1, correct1 = one.step()
+        gs = all_grads(pkg, one)
+        assert all(np.abs(x).max() > 0 for x in gs)
+        want = np.concatenate(gs)
+    with tempfile.TemporaryDirectory() as d:
+        mp.spawn(_shard_worker, args=(world, d, f"/gatv2_norm_{os.getpid()}_{world}_{int(replicate)}", replicate), nprocs=world, join=True)
+        outs = [np.load(os.path.join(d, f"r{r}.npz")) for r in range(world)]
+    for o in outs:
+        assert abs(float(o["loss"]) - loss1) <= 1e-5 * max(1.0, abs(loss1)) and int(o["correct"]) == correct1
+        assert o["grads"].shape == want.shape
+        assert np.abs(o["grads"] - want).max() <= 1e-5 * np.abs(want).max()
+        assert np.array_equal(o["grads"], outs[0]["grads"])
+
+
+def test_train_edge_ranks_and_dump_load(pkg, tmp_path):
+    """train_edge --ranks 2 --layer-norm --residual --bias ends at the parameters of --ranks 1 (through --dump-params, which carries
+    gamma and beta behind the residual groups); the flag changes the run; a dumped file loads back and round-trips."""
+    ds = pkg.synth.make_dataset("cora", scale=0.15)
+    pkg.synth.write_text_dataset(ds, str(tmp_path), "tiny")
+    base = ["--dataset", "tiny", "--data-root", str(tmp_path), "--num-layers", "2", "--heads", "8,8", "--outdims", "8,8",
+            "--epochs", "3", "--optimizer", "sgd", "--lr", "0.001", "--seed", "5", "--residual", "--bias", "--layer-norm"]
+    env = dict(os.environ)
+    env.pop("DATA_ROOT", None)
+
+    def run(args):
+        r = subprocess.run([BIN] + args, capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr
+        return r
+    one = run(base + ["--dump-params", str(tmp_path / "p1.bin")])
+    two = run(base + ["--ranks", "2", "--transport", "host", "--dump-params", str(tmp_path / "p2.bin")])
+    run(base[:-1] + ["--dump-params", str(tmp_path / "p0.bin")])
+    p0, p1, p2 = (np.fromfile(tmp_path / f, dtype=np.float32) for f in ("p0.bin", "p1.bin", "p2.bin"))
+    f, c = ds["f"], ds["c"]
+    n_res = 64 * 2 * f + 64 * 2 * 64 + 128 + c * 8 + 64 * f + 64 * 64 + 128
+    assert p0.size == n_res and p1.size == n_res + 256 and p2.size == p1.size
+    assert np.abs(p1 - p2).max() < 1e-4 * max(1.0, np.abs(p1).max())
+    gam, bet = p1[n_res:n_res + 128], p1[n_res + 128:]
+    assert np.abs(gam - 1).max() > 0 and np.abs(gam - 1).max() < 0.5 and np.abs(bet).max() > 0      # started at 1 / 0 and moved
+    assert not np.array_equal(p1[:n_res], p0)
+    import re
+    pat = r"Avg Loss: ([0-9.]+), Accuracy: ([0-9.]+)%"
+    a, b = re.findall(pat, one.stdout), re.findall(pat, two.stdout)
+    assert len(a) == 3 and len(b) == 3
+    for (la, aa), (lb, ab) in zip(a, b):
+        assert abs(float(la) - float(lb)) < 1e-4 and abs(float(aa) - float(ab)) < 0.011
+    # a file written with the flags loads back with them: zero epochs of training between load and dump keep every float
+    run(base + ["--epochs", "0", "--load-params", str(tmp_path / "p1.bin"), "--dump-params", str(tmp_path / "p3.bin")])
+    assert np.array_equal(np.fromfile(tmp_path / "p3.bin", dtype=np.float32), p1)
+
+
+def test_errors(pkg, orc):
+    A = pkg.abi
+    g = make_graph(7)
+    INVALID, STATE, UNSUPPORTED = 10001, 10002, 10004
+
+    def refused(ctx, code, **kw):
+        with pytest.raises(A.GatError) as ei:
+            ctx.set_norm(**kw)
+        assert ei.value.code == code, kw
+    with pkg.GatContext([8, 8], [8, 8], g["f"], g["c"]) as ctx:
+        for flags in (4, 8, -1):
+            refused(ctx, INVALID, flags=flags)
+        refused(ctx, INVALID, layer=False, skip_last=True)       # GAT_NORM_SKIP_LAST alone
+        for eps in (0.0, -1e-5, float("inf"), float("nan")):
+            refused(ctx, INVALID, eps=eps)
+        assert ctx.param_count(A.PARAM_LN_G) == 0                # nothing above took effect
+        ctx.set_norm()
+        ctx.set_norm(skip_last=True)                             # again, while nothing sized the buffers
+        assert ctx.param_count(A.PARAM_LN_G) == 128 and ctx.param_count(A.PARAM_LN_B) == 128
+        ctx.params_set(A.PARAM_LN_B, np.ones(128, np.float32))
+        refused(ctx, STATE)                                      # after gat_params_set
+    with pkg.GatContext([8, 8], [8, 8], g["f"], g["c"]) as ctx:
+        ctx.set_graph(g["row_ptr"], g["col_idx"])
+        refused(ctx, STATE)                                      # after gat_set_graph
+        refused(ctx, STATE, layer=False)                         # flags == 0 too: the rule is about the call order
+    with pkg.GatContext([8, 8], [8, 8], g["f"], g["c"]) as ctx:
+        ctx.grads_get(A.PARAM_W)
+        refused(ctx, STATE)                                      # after gat_grads_get
+    with pkg.GatContext([8, 8], [8, 8], g["f"], g["c"], flat_lrelu_index=True) as ctx:
+        refused(ctx, UNSUPPORTED)
+        ctx.set_norm(layer=False)                                # off stays allowed
+
+
+def test_experiment_library_refuses_norm_with_gat_dbg(pkg):
+    exp = os.path.join(ROOT, "graph-attention-network-gatv2-_amd", "libgatv2_hip_exp.so")
+    code = f"""
+import sys; sys.path.insert(0, {ROOT!r})
+import __graft_entry__ as entry
+pkg = entry.load_package(); A = pkg.abi
+ctx = pkg.GatContext([8, 8], [8, 8], 16, 4)
+try:
+    ctx.set_norm()
+except A.GatError as e:
+    print("CODE", e.code)
+ctx.set_norm(layer=False)          # off stays allowed
+print("OK")
+"""
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, GATV2_LIB=exp, GAT_DBG="1"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "CODE 10004" in r.stdout and "OK" in r.stdout, r.stdout
