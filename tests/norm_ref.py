@@ -27,7 +27,8 @@ def forward(cfg, row_ptr, col_idx, labels, X, W, a, Wo, Wres=None, b=None, gamma
             keeps=None, attn=None, feat=None, slope=0.01, bf16_pl=False):
     """fp64 step.  gamma / beta: flat groups, or None (both): no layer is normalised and the model is residual_ref.forward's.
     skip_last: the last layer is left un-normalised.  The other arguments as in residual_ref.forward.
-    -> dict(loss, hpre[l] (= u, grad retained: G = dL/dh_pre), hout[l] (grad retained: dL/dhout), s_min, v_min (smallest non-zero |v| over the layers; |h_pre| of a
+    -> dict(loss, hpre[l] (= u, grad retained: G = dL/dh_pre), hout[l] (grad retained: dL/dhout), alpha[l] (numpy [H][E]: the softmax
+    over the surviving edges before the attention-dropout factor, pe / Z without the 1e-8 guard, 0 at dropped edges: GAT_TAP_ALPHA), s_min, v_min (smallest non-zero |v| over the layers; |h_pre| of a
     layer left un-normalised), leaf tensors W, a, Wo, Wres, b, gamma, beta (None when absent))."""
     import torch
     dt = torch.float64
@@ -40,7 +41,7 @@ def forward(cfg, row_ptr, col_idx, labels, X, W, a, Wo, Wres=None, b=None, gamma
     wro, bo = RR.offsets(cfg)
     lo = offsets(cfg)
     x = torch.tensor(np.asarray(X), dtype=dt)
-    out = {"hpre": [], "hout": [], "W": Wt, "a": at, "Wo": Wot, "Wres": Wrt, "b": bt, "gamma": gt, "beta": bet,
+    out = {"hpre": [], "hout": [], "alpha": [], "W": Wt, "a": at, "Wo": Wot, "Wres": Wrt, "b": bt, "gamma": gt, "beta": bet,
            "s_min": np.inf, "v_min": np.inf}
     for l in range(cfg.L):
         k = np.ones(E, bool) if keeps is None else np.asarray(keeps[l], bool)
@@ -62,6 +63,9 @@ def forward(cfg, row_ptr, col_idx, labels, X, W, a, Wo, Wres=None, b=None, gamma
         pe = torch.exp(e - m[dst])
         Z = torch.zeros((N, H), dtype=dt).index_add(0, dst, pe)
         alpha = pe / (Z[dst] + 1e-8)
+        full = np.zeros((H, E))                                      # GAT_TAP_ALPHA: [H][E], exactly 0 at dropped edges
+        full[:, k] = (pe / Z[dst]).detach().numpy().T                # the softmax itself: the model's weight above is within 1e-8 of it
+        out["alpha"].append(full)
         w = alpha if attn is None else alpha * torch.from_numpy(np.asarray(attn[l], np.float64)[:, k].T)
         hpre = torch.zeros((N, H, D), dtype=dt).index_add(0, dst, w[..., None] * PL[src])
         if Wrt is not None:
