@@ -119,6 +119,7 @@ void build_worklist(const int32_t* rp, int64_t n_rows, WorkList& w) {
 
 }  // namespace gat
 
+constexpr int kParamGroups = GAT_PARAM_LN_B + 1;   // GAT_PARAM_* are 0 .. 6, in packed order
 struct gat_ctx {
     gat_config cfg{};
     std::vector<int32_t> heads, outdims;
@@ -138,10 +139,10 @@ struct gat_ctx {
     int32_t ld0 = 0;                                // floats between rows of X0 / Xtab: in_dim rounded up to a multiple of 4 (zeros behind
                                                     // column in_dim), so that an odd in_dim — Cora's 1,433 — still gets 16-byte loads
     float* Xtab = nullptr;                          // [n_table][in_dim] replicated layer-0 input (gat_set_source_features)
-    int64_t nW = 0, nA = 0, nWo = 0;
-    int64_t nWres = 0, nB = 0;                      // 0 unless gat_set_residual switched the group on
+    // the packed parameter layout by GAT_PARAM_* (layout_params): floats in each group — Wres / b are empty unless gat_set_residual,
+    // gamma / beta unless gat_set_norm switched them on — and the group's first float in params / grads
+    int64_t group_cnt[kParamGroups] = {0}, group_off[kParamGroups] = {0};
     int32_t res_flags = 0;                          // GAT_RES_* (gat_set_residual)
-    int64_t nLnG = 0, nLnB = 0;                     // 0 unless gat_set_norm switched the groups on
     int32_t norm_flags = 0; float norm_eps = 0.f;   // GAT_NORM_* (gat_set_norm)
     float* norm_partial = nullptr;                  // [L][2][kResPartialRows][HDmax] block column sums for grad_gamma / grad_beta
     bool params_touched = false;                    // a gat_params_* / gat_grads_* / gat_set_graph* call was made: the packed buffers keep their size
@@ -277,36 +278,55 @@ static int check_layer(gat_ctx* c, int32_t l) {
     return 0;
 }
 
-static float* W_of(gat_ctx* c, int l) { return c->params + c->layers[l].w_off; }
-static float* a_of(gat_ctx* c, int l) { return c->params + c->nW + c->layers[l].a_off; }
-static float* Wo_of(gat_ctx* c) { return c->params + c->nW + c->nA; }
-static float* gW_of(gat_ctx* c, int l) { return c->grads + c->layers[l].w_off; }
-static float* ga_of(gat_ctx* c, int l) { return c->grads + c->nW + c->layers[l].a_off; }
-static float* gWo_of(gat_ctx* c) { return c->grads + c->nW + c->nA; }
-static int64_t n_params(const gat_ctx* c) { return c->nW + c->nA + c->nWo + c->nWres + c->nB + c->nLnG + c->nLnB; }
+// layer l's part of a parameter group (layer_off: the layer's offset inside the group) and of its gradient
+static float* param_of(gat_ctx* c, int group, int64_t layer_off = 0) { return c->params + c->group_off[group] + layer_off; }
+static float* grad_of(gat_ctx* c, int group, int64_t layer_off = 0) { return c->grads + c->group_off[group] + layer_off; }
+static float* W_of(gat_ctx* c, int l) { return param_of(c, GAT_PARAM_W, c->layers[l].w_off); }
+static float* a_of(gat_ctx* c, int l) { return param_of(c, GAT_PARAM_A, c->layers[l].a_off); }
+static float* Wo_of(gat_ctx* c) { return param_of(c, GAT_PARAM_WO); }
+static float* gW_of(gat_ctx* c, int l) { return grad_of(c, GAT_PARAM_W, c->layers[l].w_off); }
+static float* ga_of(gat_ctx* c, int l) { return grad_of(c, GAT_PARAM_A, c->layers[l].a_off); }
+static float* gWo_of(gat_ctx* c) { return grad_of(c, GAT_PARAM_WO); }
+static int64_t n_params(const gat_ctx* c) { return c->group_off[kParamGroups - 1] + c->group_cnt[kParamGroups - 1]; }
+// The packed layout [W | a | Wo | Wres | b | gamma | beta]: every layer's offset inside the groups, the groups' sizes and where they
+// start.  Called whenever the set of groups changes (gat_create, gat_set_residual, gat_set_norm).
+static void layout_params(gat_ctx* c) {
+    int64_t* n = c->group_cnt;
+    std::fill(n, n + kParamGroups, (int64_t)0);
+    for (Layer& y : c->layers) {
+        y.w_off = n[GAT_PARAM_W]; y.a_off = n[GAT_PARAM_A]; y.wres_off = n[GAT_PARAM_WRES]; y.b_off = n[GAT_PARAM_B]; y.ln_off = n[GAT_PARAM_LN_G];
+        n[GAT_PARAM_W] += (int64_t)y.HD * 2 * y.F;                       // E:1248-1254
+        n[GAT_PARAM_A] += y.HD;
+        if (c->res_flags & GAT_RES_LINEAR) n[GAT_PARAM_WRES] += (int64_t)y.HD * y.F;
+        if (c->res_flags & GAT_RES_BIAS) n[GAT_PARAM_B] += y.HD;
+        if (c->norm_flags != 0) n[GAT_PARAM_LN_G] += y.HD;               // all L layers; with GAT_NORM_SKIP_LAST the last one's entries are never read
+    }
+    n[GAT_PARAM_WO] = (int64_t)c->cfg.num_classes * c->layers.back().D;
+    n[GAT_PARAM_LN_B] = n[GAT_PARAM_LN_G];
+    for (int k = 0; k < kParamGroups; ++k) c->group_off[k] = k ? c->group_off[k - 1] + n[k - 1] : 0;
+}
 static bool res_on(const gat_ctx* c) { return c->res_flags != 0; }
 static bool norm_on(const gat_ctx* c) { return c->norm_flags != 0; }
 // layer l is normalised (gatv2_abi.h "layer normalisation")
 static bool norm_layer(const gat_ctx* c, int l) {
     return norm_on(c) && !((c->norm_flags & GAT_NORM_SKIP_LAST) && l == c->cfg.num_layers - 1);
 }
-// the context runs the residual route: DROP instantiations of the forward, the N-sized backward kernel, G and agg in the edge backward
+// the context runs the residual route: the forward takes EdgeFwdExtras, the backward the N-sized kernel, G and agg in the edge backward
 static bool res_route(const gat_ctx* c) { return res_on(c) || norm_on(c); }
-static int64_t ln_base(const gat_ctx* c) { return c->nW + c->nA + c->nWo + c->nWres + c->nB; }
-static float* lng_of(gat_ctx* c, int l) { return c->params + ln_base(c) + c->layers[l].ln_off; }
-static float* lnb_of(gat_ctx* c, int l) { return c->params + ln_base(c) + c->nLnG + c->layers[l].ln_off; }
-static float* glng_of(gat_ctx* c, int l) { return c->grads + ln_base(c) + c->layers[l].ln_off; }
-static float* glnb_of(gat_ctx* c, int l) { return c->grads + ln_base(c) + c->nLnG + c->layers[l].ln_off; }
+static float* lng_of(gat_ctx* c, int l) { return param_of(c, GAT_PARAM_LN_G, c->layers[l].ln_off); }
+static float* lnb_of(gat_ctx* c, int l) { return param_of(c, GAT_PARAM_LN_B, c->layers[l].ln_off); }
+static float* glng_of(gat_ctx* c, int l) { return grad_of(c, GAT_PARAM_LN_G, c->layers[l].ln_off); }
+static float* glnb_of(gat_ctx* c, int l) { return grad_of(c, GAT_PARAM_LN_B, c->layers[l].ln_off); }
 static LnArgs ln_args(gat_ctx* c, int l) {
     LnArgs a;
     if (norm_layer(c, l)) { a.gamma = lng_of(c, l); a.beta = lnb_of(c, l); a.eps = c->norm_eps; }
     return a;
 }
 // null while the group is off
-static float* Wres_of(gat_ctx* c, int l) { return c->nWres ? c->params + c->nW + c->nA + c->nWo + c->layers[l].wres_off : nullptr; }
-static float* b_of(gat_ctx* c, int l) { return c->nB ? c->params + c->nW + c->nA + c->nWo + c->nWres + c->layers[l].b_off : nullptr; }
-static float* gWres_of(gat_ctx* c, int l) { return c->grads + c->nW + c->nA + c->nWo + c->layers[l].wres_off; }
-static float* gb_of(gat_ctx* c, int l) { return c->grads + c->nW + c->nA + c->nWo + c->nWres + c->layers[l].b_off; }
+static float* Wres_of(gat_ctx* c, int l) { return c->group_cnt[GAT_PARAM_WRES] ? param_of(c, GAT_PARAM_WRES, c->layers[l].wres_off) : nullptr; }
+static float* b_of(gat_ctx* c, int l) { return c->group_cnt[GAT_PARAM_B] ? param_of(c, GAT_PARAM_B, c->layers[l].b_off) : nullptr; }
+static float* gWres_of(gat_ctx* c, int l) { return grad_of(c, GAT_PARAM_WRES, c->layers[l].wres_off); }
+static float* gb_of(gat_ctx* c, int l) { return grad_of(c, GAT_PARAM_B, c->layers[l].b_off); }
 static bool feat_drop_on(const gat_ctx* c) { return c->training && c->drop_pf > 0.f; }
 static bool attn_drop_on(const gat_ctx* c) { return c->training && c->drop_pa > 0.f; }
 static bool edge_drop_on(const gat_ctx* c) { return c->training && c->edge_p > 0.f; }
@@ -316,16 +336,32 @@ static const float* Xin_raw(gat_ctx* c, int l) { return l == 0 ? c->X0 : c->laye
 static const float* Xin_of(gat_ctx* c, int l) { return feat_drop_on(c) && (size_t)l < c->xdrop.size() && c->xdrop[(size_t)l] ? c->xdrop[(size_t)l] : Xin_raw(c, l); }
 static const float* Xtab_of(gat_ctx* c) { return feat_drop_on(c) && c->xdrop_tab ? c->xdrop_tab : c->Xtab; }
 static uint32_t drop_threshold(double p) { return (uint32_t)std::min<double>(16777216.0, std::floor(p * 16777216.0 + 0.5)); }
-static DropArgs drop_args(gat_ctx* c, int32_t kind, int32_t l) {
-    const double p = kind == kDropAttn ? c->drop_pa : c->drop_pf;
+// The mask parameters of layer l, fully identified (step, seed, bounds, row0, layer).  kind = kDropAttn: what the edge passes take —
+// attention dropout and DropEdge; kDropFeat: the feature mask of the layer's input.  The thresholds are those of the masks that are
+// active now (training mode, p > 0) — with `setting`, those of the settings whatever the mode (the taps) — and 0 / scale 1 otherwise;
+// on: a mask is active (under `setting` it says the same of the settings; the tap kernels do not read it, and the attention-keep tap
+// ignores the DropEdge fields it is handed along).
+static DropArgs drop_args(gat_ctx* c, int32_t l, int32_t kind = kDropAttn, bool setting = false) {
+    const bool live = c->training || setting;
+    const double p = !live ? 0.0 : kind == kDropAttn ? c->drop_pa : c->drop_pf;
+    const bool edges = live && kind == kDropAttn && c->edge_p > 0.f;
     DropArgs d{};
     d.step = c->drop_step; d.bounds = c->drop_bounds; d.max_rows = c->drop_max_rows; d.row0 = c->table_row0;
     d.seed_lo = (uint32_t)c->drop_seed; d.seed_hi = (uint32_t)(c->drop_seed >> 32);
     d.T = drop_threshold(p);
     d.scale = (float)(1.0 / (1.0 - p));
+    if (edges) { d.Te = drop_threshold(c->edge_p); d.eflags = c->edge_flags; }
     d.layer = l;
-    d.on = 1;
+    d.on = p > 0.0 || edges;
     return d;
+}
+// the dropout step counter, zeroed when first needed (before gat_set_dropout: seed 0, counter 0)
+static int ensure_drop_step(gat_ctx* c) {
+    if (c->drop_step) return 0;
+    GAT_TRY(dalloc(c, &c->drop_step, 1));
+    GAT_HIP(hipMemsetAsync(c->drop_step, 0, sizeof(uint64_t), c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    return 0;
 }
 static int32_t ldX_of(gat_ctx* c, int l) { return l == 0 ? c->ld0 : c->layers[l].F; }
 // rows of in_dim floats -> rows of ld0 floats with zeros behind column in_dim
@@ -509,7 +545,7 @@ static int ensure_buffers(gat_ctx* c) {
         GAT_TRY(dalloc(c, &c->resG, N * c->HDmax));
         GAT_TRY(dalloc(c, &c->res_agg, N * c->HDmax));
         GAT_TRY(dalloc(c, &c->res_partial, (int64_t)L * kResPartialRows * c->HDmax));
-        if (c->nWres) {
+        if (c->group_cnt[GAT_PARAM_WRES]) {
             int64_t rg = 0;
             c->res_gw_off.assign((size_t)L, 0);
             for (int l = 0; l < L; ++l) {
@@ -519,11 +555,7 @@ static int ensure_buffers(gat_ctx* c) {
             }
             GAT_TRY(dalloc(c, &c->res_gw_scratch, std::max<int64_t>(rg, 1)));
         }
-        if (!c->drop_step) {                         // the forward's DROP instantiations read the step counter (nothing is dropped)
-            GAT_TRY(dalloc(c, &c->drop_step, 1));
-            GAT_HIP(hipMemsetAsync(c->drop_step, 0, sizeof(uint64_t), c->stream));
-            GAT_HIP(hipStreamSynchronize(c->stream));
-        }
+        GAT_TRY(ensure_drop_step(c));                // the forward's extended kernels read the step counter (nothing is dropped)
     }
     c->buffers_ready = true;
     GAT_TRY(ensure_drop_buffers(c));
@@ -585,21 +617,16 @@ int gat_create(const gat_config* cfg, gat_ctx** out) {
     if (!(c->cfg.negative_slope > 0.0f && c->cfg.negative_slope <= 1.0f))
         return fail(GAT_E_INVALID, "negative_slope must be in (0, 1] (the kernels use LReLU(x) = max(x, slope*x))");
     c->layers.resize(cfg->num_layers);
-    int64_t woff = 0, aoff = 0;
     for (int l = 0; l < cfg->num_layers; ++l) {
         Layer& y = c->layers[l];
         y.H = c->heads[l]; y.D = c->outdims[l];
         if (y.H <= 0 || y.D <= 0) return fail(GAT_E_INVALID, "heads/outdims must be positive");
         y.HD = y.H * y.D;
         y.F = (l == 0) ? cfg->in_dim : c->layers[l - 1].HD;            // E:1115-1118
-        y.w_off = woff; y.a_off = aoff;
-        woff += (int64_t)y.HD * 2 * y.F;                                 // E:1248-1254
-        aoff += y.HD;
         c->HDmax = std::max(c->HDmax, y.HD);
         c->Hmax = std::max(c->Hmax, y.H);
     }
-    c->nW = woff; c->nA = aoff;
-    c->nWo = (int64_t)cfg->num_classes * c->layers.back().D;
+    layout_params(c.get());
     if (cfg->storage_dtype != GAT_DTYPE_F32 && cfg->storage_dtype != GAT_DTYPE_BF16)
         return fail(GAT_E_INVALID, "storage_dtype must be GAT_DTYPE_F32 or GAT_DTYPE_BF16");
 #ifdef GAT_EXPERIMENTS                               // the release library does not know the name: a stray variable cannot change results
@@ -608,7 +635,7 @@ int gat_create(const gat_config* cfg, gat_ctx** out) {
     if (cfg->stream) { c->stream = (hipStream_t)cfg->stream; c->own_stream = false; }
     else { GAT_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
     gat_ctx* p = c.get();
-    const int64_t np = c->nW + c->nA + c->nWo;
+    const int64_t np = n_params(p);
     GAT_TRY(dalloc(p, &p->params, np));
     GAT_TRY(dalloc(p, &p->grads, np + 4));
     GAT_TRY(dalloc(p, &p->clip_scratch, 8));
@@ -878,16 +905,9 @@ int gat_set_labels_device(gat_ctx* c, const int32_t* labels, int64_t n_rows) {
 // ---- parameters --------------------------------------------------------------------------------------------
 static int group_span(gat_ctx* c, int group, int64_t* off, int64_t* cnt) {
     if (!c) return fail(GAT_E_INVALID, "null context");
-    switch (group) {
-        case GAT_PARAM_W: *off = 0; *cnt = c->nW; return 0;
-        case GAT_PARAM_A: *off = c->nW; *cnt = c->nA; return 0;
-        case GAT_PARAM_WO: *off = c->nW + c->nA; *cnt = c->nWo; return 0;
-        case GAT_PARAM_WRES: *off = c->nW + c->nA + c->nWo; *cnt = c->nWres; return 0;
-        case GAT_PARAM_B: *off = c->nW + c->nA + c->nWo + c->nWres; *cnt = c->nB; return 0;
-        case GAT_PARAM_LN_G: *off = ln_base(c); *cnt = c->nLnG; return 0;
-        case GAT_PARAM_LN_B: *off = ln_base(c) + c->nLnG; *cnt = c->nLnB; return 0;
-        default: return fail(GAT_E_INVALID, "unknown parameter group");
-    }
+    if (group < 0 || group >= kParamGroups) return fail(GAT_E_INVALID, "unknown parameter group");
+    *off = c->group_off[group]; *cnt = c->group_cnt[group];
+    return 0;
 }
 int gat_param_count(gat_ctx* c, int group, int64_t* count) {
     int64_t off;
@@ -959,15 +979,15 @@ int gat_params_init(gat_ctx* c, uint64_t seed) {
         const Layer& y = c->layers[l];
         const float lim = sqrtf(6.0f / (float)(2 * y.F + y.D));
         const int64_t nw = (int64_t)y.HD * 2 * y.F;
-        GAT_TRY(launch_xavier_init(c->params + y.w_off, nw, s0, draw, lim, c->stream));
+        GAT_TRY(launch_xavier_init(W_of(c, l), nw, s0, draw, lim, c->stream));
         draw += (uint64_t)nw;
-        GAT_TRY(launch_xavier_init(c->params + c->nW + y.a_off, y.HD, s0, draw, lim, c->stream));
+        GAT_TRY(launch_xavier_init(a_of(c, l), y.HD, s0, draw, lim, c->stream));
         draw += (uint64_t)y.HD;
     }
     const float limo = sqrtf(6.0f / (float)(c->cfg.num_classes + c->layers.back().D));
-    GAT_TRY(launch_xavier_init(c->params + c->nW + c->nA, c->nWo, s0, draw, limo, c->stream));
-    draw += (uint64_t)c->nWo;
-    if (c->nWres) {                                  // after every existing draw: W, a and Wo of a seed do not depend on the flag
+    GAT_TRY(launch_xavier_init(Wo_of(c), c->group_cnt[GAT_PARAM_WO], s0, draw, limo, c->stream));
+    draw += (uint64_t)c->group_cnt[GAT_PARAM_WO];
+    if (c->group_cnt[GAT_PARAM_WRES]) {                                  // after every existing draw: W, a and Wo of a seed do not depend on the flag
         for (int l = 0; l < c->cfg.num_layers; ++l) {
             const Layer& y = c->layers[l];
             const int64_t nr = (int64_t)y.HD * y.F;
@@ -975,11 +995,11 @@ int gat_params_init(gat_ctx* c, uint64_t seed) {
             draw += (uint64_t)nr;
         }
     }
-    if (c->nB) GAT_HIP(hipMemsetAsync(b_of(c, 0), 0, (size_t)c->nB * sizeof(float), c->stream));
-    const std::vector<float> ones((size_t)c->nLnG, 1.0f);      // layer normalisation: gamma = 1, beta = 0, no draws
-    if (c->nLnG) {
+    if (b_of(c, 0)) GAT_HIP(hipMemsetAsync(b_of(c, 0), 0, (size_t)c->group_cnt[GAT_PARAM_B] * sizeof(float), c->stream));
+    const std::vector<float> ones((size_t)c->group_cnt[GAT_PARAM_LN_G], 1.0f);      // layer normalisation: gamma = 1, beta = 0, no draws
+    if (!ones.empty()) {
         GAT_HIP(hipMemcpyAsync(lng_of(c, 0), ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        GAT_HIP(hipMemsetAsync(lnb_of(c, 0), 0, (size_t)c->nLnB * sizeof(float), c->stream));
+        GAT_HIP(hipMemsetAsync(lnb_of(c, 0), 0, ones.size() * sizeof(float), c->stream));
     }
     GAT_HIP(hipStreamSynchronize(c->stream));
     return 0;
@@ -994,7 +1014,7 @@ static int drop_prepare_input(gat_ctx* c, int32_t l) {
     if (!feat_drop_on(c)) return 0;
     if (c->xdrop.empty() || (c->Xtab && !c->xdrop_tab)) GAT_TRY(ensure_drop_buffers(c));
     const Layer& y = c->layers[l];
-    DropArgs d = drop_args(c, kDropFeat, l);
+    DropArgs d = drop_args(c, l, kDropFeat);
     GAT_TRY(launch_feat_drop_fwd(Xin_raw(c, l), c->xdrop[(size_t)l], c->n_rows, y.F, ldX_of(c, l), d, c->stream));
     if (l == 0 && c->Xtab) {      // the replicated table: its rows are table rows, the same node ids
         d.row0 = 0;
@@ -1018,27 +1038,13 @@ int gat_layer_project(gat_ctx* c, int32_t l) {
 }
 
 static EdgeFwdArgs plan_forward_edges(gat_ctx* c, int32_t l);
-// the DropEdge part of the mask parameters, from the context's setting whatever the mode (the tap; the passes ask edge_drop_on first)
-static void set_edge_drop(const gat_ctx* c, DropArgs* d) { d->Te = drop_threshold(c->edge_p); d->eflags = c->edge_flags; }
-// what the edge passes of layer l take: attention dropout and / or DropEdge (either one selects the DROP instantiations)
-static DropArgs attn_drop_args(gat_ctx* c, int32_t l) {
-    if (!attn_drop_on(c) && !edge_drop_on(c)) return DropArgs{};
-    DropArgs d = drop_args(c, kDropAttn, l);
-    if (!attn_drop_on(c)) { d.T = 0; d.scale = 1.f; }
-    if (edge_drop_on(c)) set_edge_drop(c, &d);
-    return d;
-}
 int gat_layer_forward_edges(gat_ctx* c, int32_t l) {
     GAT_TRY(check_layer(c, l));
     const EdgeFwdArgs a = plan_forward_edges(c, l);
-    DropArgs d = attn_drop_args(c, l);
-    if (res_route(c) && !d.on) {                      // residual / norm without a mask: the DROP instantiations with nothing dropped
-        d = drop_args(c, kDropAttn, l);
-        d.T = 0; d.scale = 1.f; d.on = 0;
-    }
-    const LnArgs ln = ln_args(c, l);
+    EdgeFwdExtras x;                                 // masks, residual, bias, norm: whatever of them is on (launch_edge_forward: none = the plain kernels)
+    x.drop = drop_args(c, l); x.res = c->layers[l].R; x.bias = b_of(c, l); x.ln = ln_args(c, l);
     Scope t(c, GAT_K_EDGE_FWD);
-    return launch_edge_forward(a, c->stream, &d, c->layers[l].R, b_of(c, l), &ln);
+    return launch_edge_forward(a, c->stream, &x);
 }
 static EdgeFwdArgs plan_forward_edges(gat_ctx* c, int32_t l) {
     Layer& y = c->layers[l];
@@ -1120,7 +1126,7 @@ static int plan_backward_edges(gat_ctx* c, int32_t l, BwdPlan* P) {
     a.dbg = c->dbg;
     a.ga_partial = c->ga_partial + (int64_t)l * kGaPartialRows * c->HDmax; a.n_rows = c->n_rows; a.n_table = c->n_table; a.bf16 = bf16(c); a.H = y.H; a.D = y.D;
     a.slope = c->cfg.negative_slope;
-    P->drop = attn_drop_args(c, l);
+    P->drop = drop_args(c, l);
     a.ga_blocks = edge_backward_blocks(a, &P->drop);
     P->a = a; P->store = store; P->stash = stash; P->last_g = last_g;
     return 0;
@@ -1150,7 +1156,7 @@ static int res_backward_layer(gat_ctx* c, int32_t l) {
     ResBwdArgs r{};
     r.hpre = y.hpre; r.g = y.g; r.gh = (last && c->gH != nullptr) ? c->gH : nullptr; r.res = y.R; r.bias = b_of(c, l);
     r.G = c->resG; r.agg = c->res_agg;
-    r.partial = c->nB ? c->res_partial + (int64_t)l * kResPartialRows * c->HDmax : nullptr;
+    r.partial = b_of(c, l) ? c->res_partial + (int64_t)l * kResPartialRows * c->HDmax : nullptr;
     r.n_rows = c->n_rows; r.H = y.H; r.D = y.D; r.gh_stride = c->gh_stride; r.g_raw = last ? 0 : 1;
     r.slope = c->cfg.negative_slope;
     Scope t(c, GAT_K_MISC);
@@ -1217,7 +1223,7 @@ static int backward_grad_x(gat_ctx* c, int32_t l) {
     // residual: + G Wres, before the feature-dropout factor and before the LReLU' factor of the layer below
     if (y.R != nullptr) GAT_TRY(launch_grad_x_res(c->resG, Wres_of(c, l), c->layers[l - 1].g, c->n_rows, y.F, y.HD, c->stream));
     // feature dropout: dL/dx_l = dL/dx'_l (.) kappa s_f, before the LReLU' factor of layer l-1 (applied by its edge backward)
-    if (feat_drop_on(c)) return launch_feat_drop_bwd(c->layers[l - 1].g, c->n_rows, y.F, drop_args(c, kDropFeat, l), c->stream);
+    if (feat_drop_on(c)) return launch_feat_drop_bwd(c->layers[l - 1].g, c->n_rows, y.F, drop_args(c, l, kDropFeat), c->stream);
     return 0;
 }
 int gat_layer_backward_dense(gat_ctx* c, int32_t l) {
@@ -1634,14 +1640,8 @@ int gat_set_residual(gat_ctx* c, int32_t flags) {
     if (c->dbg != 0 && flags != 0)
         return fail(GAT_E_UNSUPPORTED, "gat_set_residual: not with a GAT_DBG timing experiment (those kernels have no residual form)");
 #endif
-    int64_t wr = 0, bo = 0;
-    for (int l = 0; l < c->cfg.num_layers; ++l) {
-        Layer& y = c->layers[l];
-        y.wres_off = wr; y.b_off = bo;
-        if (flags & GAT_RES_LINEAR) wr += (int64_t)y.HD * y.F;
-        if (flags & GAT_RES_BIAS) bo += y.HD;
-    }
-    c->nWres = wr; c->nB = bo; c->res_flags = flags;
+    c->res_flags = flags;
+    layout_params(c);
     return resize_packed(c);
 }
 // ---- layer normalisation ----------------------------------------------------------------------------------------
@@ -1659,12 +1659,8 @@ int gat_set_norm(gat_ctx* c, int32_t flags, float eps) {
     if (c->dbg != 0 && flags != 0)
         return fail(GAT_E_UNSUPPORTED, "gat_set_norm: not with a GAT_DBG timing experiment (those kernels have no normalised form)");
 #endif
-    int64_t o = 0;
-    for (int l = 0; l < c->cfg.num_layers; ++l) {
-        c->layers[l].ln_off = o;
-        if (flags != 0) o += c->layers[l].HD;            // all L layers; with GAT_NORM_SKIP_LAST the last one's entries are never read
-    }
-    c->nLnG = o; c->nLnB = o; c->norm_flags = flags; c->norm_eps = flags != 0 ? eps : 0.f;
+    c->norm_flags = flags; c->norm_eps = flags != 0 ? eps : 0.f;
+    layout_params(c);
     return resize_packed(c);
 }
 // ---- dropout ---------------------------------------------------------------------------------------------------
@@ -1676,7 +1672,7 @@ int gat_set_dropout(gat_ctx* c, float feat_p, float attn_p, uint64_t seed, uint6
     if (c->dbg != 0 && (feat_p > 0.f || attn_p > 0.f))
         return fail(GAT_E_UNSUPPORTED, "gat_set_dropout: not with a GAT_DBG timing experiment (those kernels have no dropout form)");
 #endif
-    if (!c->drop_step) GAT_TRY(dalloc(c, &c->drop_step, 1));
+    GAT_TRY(ensure_drop_step(c));
     GAT_HIP(hipMemcpyAsync(c->drop_step, &first_step, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     GAT_HIP(hipStreamSynchronize(c->stream));
     graph_drop(c);                                       // a captured step holds the other kernel sequence
@@ -1691,11 +1687,7 @@ int gat_set_dropedge(gat_ctx* c, float edge_p, int32_t flags) {
     if (c->dbg != 0 && edge_p > 0.f)
         return fail(GAT_E_UNSUPPORTED, "gat_set_dropedge: not with a GAT_DBG timing experiment (those kernels have no dropout form)");
 #endif
-    if (!c->drop_step) {                                 // gat_set_dropout was never called: seed 0, counter 0
-        GAT_TRY(dalloc(c, &c->drop_step, 1));
-        GAT_HIP(hipMemsetAsync(c->drop_step, 0, sizeof(uint64_t), c->stream));
-        GAT_HIP(hipStreamSynchronize(c->stream));
-    }
+    GAT_TRY(ensure_drop_step(c));
     graph_drop(c);                                       // a captured step holds the other kernel sequence
     c->edge_p = edge_p; c->edge_flags = flags;
     return 0;
@@ -1818,15 +1810,8 @@ int gat_zero_grad(gat_ctx* c) {
 int gat_clip(gat_ctx* c, float threshold) {
     if (!c) return fail(GAT_E_INVALID, "null context");
     Scope t(c, GAT_K_MISC);
-    GAT_TRY(launch_clip(c->grads, c->nW, threshold, c->clip_scratch, c->stream));
-    GAT_TRY(launch_clip(c->grads + c->nW, c->nA, threshold, c->clip_scratch + 1, c->stream));
-    GAT_TRY(launch_clip(c->grads + c->nW + c->nA, c->nWo, threshold, c->clip_scratch + 2, c->stream));
-    // the residual groups: each clipped by its own norm, like the reference's three
-    if (c->nWres) GAT_TRY(launch_clip(c->grads + c->nW + c->nA + c->nWo, c->nWres, threshold, c->clip_scratch + 3, c->stream));
-    if (c->nB) GAT_TRY(launch_clip(c->grads + c->nW + c->nA + c->nWo + c->nWres, c->nB, threshold, c->clip_scratch + 4, c->stream));
-    // the norm groups: gamma and beta each by its own norm
-    if (c->nLnG) GAT_TRY(launch_clip(c->grads + ln_base(c), c->nLnG, threshold, c->clip_scratch + 5, c->stream));
-    if (c->nLnB) GAT_TRY(launch_clip(c->grads + ln_base(c) + c->nLnG, c->nLnB, threshold, c->clip_scratch + 6, c->stream));
+    for (int k = 0; k < kParamGroups; ++k)          // every group by its own norm, like the reference's three (E:250-278); scratch slot k
+        if (c->group_cnt[k]) GAT_TRY(launch_clip(grad_of(c, k), c->group_cnt[k], threshold, c->clip_scratch + k, c->stream));
     return 0;
 }
 int gat_step_sgd(gat_ctx* c, float lr) {
@@ -1994,7 +1979,7 @@ int gat_tap(gat_ctx* c, int tensor, int32_t l, void* host, int64_t count) {
             if (!c->drop_step) return fail(GAT_E_STATE, "gat_tap: dropout was never set (gat_set_dropout)");
             float* tmp = nullptr;
             GAT_HIP(hipMalloc((void**)&tmp, (size_t)std::max<int64_t>(n, 1) * sizeof(float)));
-            const DropArgs d = drop_args(c, attn ? kDropAttn : kDropFeat, l);
+            const DropArgs d = drop_args(c, l, attn ? kDropAttn : kDropFeat, true);
             int rc = attn ? launch_attn_keep_tap(c->row_ptr, N, E, y.H, d, tmp, c->stream) : launch_feat_keep_tap(N, y.F, d, tmp, c->stream);
             if (rc == 0) rc = d2h(c, host, tmp, (size_t)n * sizeof(float));
             (void)hipFree(tmp);
@@ -2005,8 +1990,7 @@ int gat_tap(gat_ctx* c, int tensor, int32_t l, void* host, int64_t count) {
             if (!c->drop_step) return fail(GAT_E_STATE, "gat_tap: DropEdge was never set (gat_set_dropedge)");
             float* tmp = nullptr;
             GAT_HIP(hipMalloc((void**)&tmp, (size_t)std::max<int64_t>(E, 1) * sizeof(float)));
-            DropArgs d = drop_args(c, kDropAttn, l);
-            set_edge_drop(c, &d);
+            const DropArgs d = drop_args(c, l, kDropAttn, true);
             int rc = launch_edge_keep_tap(c->row_ptr, c->col_idx, N, E, d, tmp, c->stream);
             if (rc == 0) rc = d2h(c, host, tmp, (size_t)E * sizeof(float));
             (void)hipFree(tmp);

@@ -1,6 +1,6 @@
 // gat_dropout.hip — the dense side of dropout (include/gatv2_abi.h "dropout"): the step counter, the feature-dropout
 // copy of a layer's input and its backward, and the mask taps (DropEdge's included).  Attention dropout lives inside the edge kernels
-// (gat_edge_kernels.hip, DROP instantiations).  Every kernel evaluates the masks with the same device functions
+// (gat_edge_kernels.hip: the forward's EXT and the backward's DROP instantiations).  Every kernel evaluates the masks with the same device functions
 // (gat_internal.h drop_*), so the taps show exactly what the passes used.
 #include "gat_internal.h"
 

@@ -46,12 +46,18 @@ __device__ __forceinline__ float attn_keep(const DropArgs& d, uint32_t kd, int k
 // A dropped edge is handled like a padded slot of a chunk: its score is replaced by -inf BY PREDICATE before the max (p = exp2(-inf) = 0
 // exactly, it never enters m or Z), and the backward selects ge = alpha = 0 for it — so its record / message row is all zero.
 __device__ __forceinline__ uint32_t edge_row_key(const DropArgs& d, int64_t row) { return drop_mix(drop_edge_key(d), drop_node(d, row)); }
-// kernel argument of the DROP instantiations: the plain struct + the mask parameters (the default ones keep the plain struct)
-template <bool DROP> struct FwdArgsOf { typedef EdgeFwdArgs T; };
-template <> struct FwdArgsOf<true> { typedef EdgeFwdDropArgs T; };
+// the per-row mask keys: kd = mix(K(attention, l), node(row)), ke as edge_row_key, rb = the row's first CSR edge (draws count from it)
+struct RowKeys { uint32_t kd, ke; int rb; };
+__device__ __forceinline__ void row_keys(const DropArgs& d, int64_t row, const int32_t* row_ptr, RowKeys& k) {
+    k.kd = drop_mix(drop_key(d, kDropAttn), drop_node(d, row)); k.rb = row_ptr[row]; k.ke = edge_row_key(d, row);
+}
+// kernel argument: the forward's EXT instantiations take the plain struct + EdgeFwdExtras (masks and / or residual, bias, norm), the
+// backward's DROP instantiations the plain struct + the mask parameters; the default ones keep the plain struct
+template <bool EXT> struct FwdArgsOf { typedef EdgeFwdArgs T; };
+template <> struct FwdArgsOf<true> { typedef EdgeFwdExtArgs T; };
 template <bool DROP> struct BwdArgsOf { typedef EdgeBwdArgs T; };
 template <> struct BwdArgsOf<true> { typedef EdgeBwdDropArgs T; };
-template <bool DROP> using FwdArgsT = typename FwdArgsOf<DROP>::T;
+template <bool EXT> using FwdArgsT = typename FwdArgsOf<EXT>::T;
 template <bool DROP> using BwdArgsT = typename BwdArgsOf<DROP>::T;
 
 template <int CTRL>
@@ -161,14 +167,17 @@ __device__ __forceinline__ float ln_row(float u, const LnArgs& ln, int c) {
     return ln.gamma[c] * (d * rstd) + ln.beta[c];
 }
 
-// RES: the residual term rs = R[row][c] + b[c] (gatv2_abi.h "residual") joins h_pre here, before anything is written
-template <int HD, int D, bool RES = false>
-__device__ __forceinline__ void fwd_write_row(const EdgeFwdArgs& A, int64_t row, int lane, float m2, float Z,
-                                              float acc, [[maybe_unused]] float rs = 0.f) {
+// The row epilogue of the wave-per-row forward kernel and the fix-up kernel: h_pre = acc / (Z + eps), the softmax stats, LReLU, concat
+// or head average.  EXT: the residual term rs = R[row][c] + b[c] (gatv2_abi.h "residual") joins h_pre before anything is written, and
+// with ln.gamma the row is then normalised — hout = LReLU(v), h_pre stays u.  (Every lane group holds the whole row: the sums stay
+// inside one.)
+template <int HD, int D, bool EXT>
+__device__ __forceinline__ void fwd_write_row(const FwdArgsT<EXT>& A, int64_t row, int lane, float m2, float Z, float acc,
+                                              [[maybe_unused]] float rs = 0.f) {
     constexpr int H = HD / D;
     const int c = lane % HD, gidx = lane / HD;
     float hp = acc * __builtin_amdgcn_rcpf(Z + 1e-8f);           // E:379 epsilon
-    if constexpr (RES) hp += rs;
+    if constexpr (EXT) hp += rs;
     if (gidx == 0) {
         A.hpre[row * HD + c] = hp;
         if ((c % D) == 0) {                          // softmax stats, log2 domain: the backward
@@ -176,35 +185,12 @@ __device__ __forceinline__ void fwd_write_row(const EdgeFwdArgs& A, int64_t row,
             A.zstat[row * H + c / D] = Z;
         }
     }
+    if constexpr (EXT) { if (A.x.ln.gamma != nullptr) hp = ln_row<HD>(hp, A.x.ln, c); }
     const float act = lrelu(hp, A.slope);
     if (!A.is_last) {
         if (gidx == 0) A.hout[row * HD + c] = act;   // concat heads (E:452-457)
     } else {
         float t = act;                               // activate, then average heads (E:440-449)
-#pragma unroll
-        for (int off = D; off < HD; off <<= 1) t += __shfl_xor(t, off);
-        if (lane < D) A.hout[row * D + lane] = t / (float)H;
-    }
-}
-// The row epilogue of the DROP / RES forms (a function of its own: the one above stays the default path's, token for token): the
-// residual term joins h_pre, and with ln.gamma the row is then normalised — hout = LReLU(v), h_pre stays u.  (Every lane group holds
-// the whole row: the sums stay inside one.)
-template <int HD, int D>
-__device__ __forceinline__ void fwd_write_row_ln(const EdgeFwdArgs& A, int64_t row, int lane, float m2, float Z, float acc, float rs,
-                                                 const LnArgs& ln) {
-    constexpr int H = HD / D;
-    const int c = lane % HD, gidx = lane / HD;
-    float hp = acc * __builtin_amdgcn_rcpf(Z + 1e-8f) + rs;      // E:379 epsilon
-    if (gidx == 0) {
-        A.hpre[row * HD + c] = hp;
-        if ((c % D) == 0) { A.mstat[row * H + c / D] = m2; A.zstat[row * H + c / D] = Z; }
-    }
-    if (ln.gamma != nullptr) hp = ln_row<HD>(hp, ln, c);
-    const float act = lrelu(hp, A.slope);
-    if (!A.is_last) {
-        if (gidx == 0) A.hout[row * HD + c] = act;
-    } else {
-        float t = act;
 #pragma unroll
         for (int off = D; off < HD; off <<= 1) t += __shfl_xor(t, off);
         if (lane < D) A.hout[row * D + lane] = t / (float)H;
@@ -278,15 +264,15 @@ __device__ __forceinline__ void store_row(float* __restrict__ msg, int slot, int
 
 // One chunk of UU slots per edge group: UU independent gathers issued back to back (indices
 // clamped into the item, so loads need no predicate), then scores, then the online-softmax update.
-// R[row][c] + b[c] of the lane's channel(s), 0 where a pointer is null (the DROP instantiations' argument struct carries them)
-__device__ __forceinline__ float res_term(const EdgeFwdDropArgs& A, int64_t row, int HD, int c) {
+// R[row][c] + b[c] of the lane's channel(s), 0 where a pointer is null
+__device__ __forceinline__ float res_term(const EdgeFwdExtras& X, int64_t row, int HD, int c) {
     float r = 0.f;
-    if (A.res != nullptr) r = A.res[row * HD + c];
-    if (A.bias != nullptr) r += A.bias[c];
+    if (X.res != nullptr) r = X.res[row * HD + c];
+    if (X.bias != nullptr) r += X.bias[c];
     return r;
 }
 
-template <int HD, int D, int UU, int USC, bool ALPHA, bool BF, bool DROP = false, class AT = EdgeFwdArgs>
+template <int HD, int D, int UU, int USC, bool ALPHA, bool BF, bool EXT = false, class AT = EdgeFwdArgs>
 __device__ __forceinline__ void fwd_chunk(const AT& A, int e0, int e_end, int e_end_v, int c, int gidx,
                                           float pr, float ac2, bool multi, float (&sc)[USC], float& m, float& Z,
                                           float& acc, uint32_t kd = 0, int rb = 0, uint32_t ke = 0, int64_t row = 0) {
@@ -300,7 +286,7 @@ __device__ __forceinline__ void fwd_chunk(const AT& A, int e0, int e_end, int e_
         const int jc = j < e_end ? j : e_end - 1;
         const int src = A.col_idx[jc];
         v[u] = gather_row<HD, BF>(A.PL, src, c);
-        if constexpr (DROP) ek[u] = drop_edge_kept(A.drop, ke, jc - rb, src, row);
+        if constexpr (EXT) ek[u] = drop_edge_kept(A.x.drop, ke, jc - rb, src, row);
     }
     // scores: the cross-lane stages run slot-interleaved (UU independent DPP chains), so that no
     // stage waits on the VALU->DPP hazard of its own predecessor
@@ -313,7 +299,7 @@ __device__ __forceinline__ void fwd_chunk(const AT& A, int e0, int e_end, int e_
     for (int u = 0; u < UU; ++u) {
         const int j = e0 + u * G + gidx;
         bool in = j < e_end_v;
-        if constexpr (DROP) in = in && ek[u];        // a dropped edge: out of the max, Z and the sum, alpha exactly 0
+        if constexpr (EXT) in = in && ek[u];         // a dropped edge: out of the max, Z and the sum, alpha exactly 0
         sc[u] = in ? t[u] : -INFINITY;
         cm = fmaxf(cm, sc[u]);
         if constexpr (ALPHA) {                       // tap: the reference's attn_score (natural-log domain, E:323)
@@ -328,7 +314,7 @@ __device__ __forceinline__ void fwd_chunk(const AT& A, int e0, int e_end, int e_
     for (int u = 0; u < UU; ++u) {
         const float p = exp2_fast(sc[u] - mn);       // 0 for padded slots
         Z += p;
-        if constexpr (DROP) acc = fmaf(p * attn_keep(A.drop, kd, e0 + u * G + gidx - rb, c / D), v[u], acc);   // the term, not Z
+        if constexpr (EXT) acc = fmaf(p * attn_keep(A.x.drop, kd, e0 + u * G + gidx - rb, c / D), v[u], acc);   // the term, not Z
         else acc = fmaf(p, v[u], acc);
     }
     m = mn;
@@ -343,8 +329,9 @@ __device__ __forceinline__ void fwd_chunk(const AT& A, int e0, int e_end, int e_
 }
 
 // ALPHA: also materialise attn_coeff [E][H] (parity taps only; the training path never needs it).
-template <int HD, int D, bool ALPHA, bool BF = false, bool DROP = false>
-__global__ __launch_bounds__(256) void edge_fwd_kernel(FwdArgsT<DROP> A) {
+// EXT: the extended argument struct (EdgeFwdExtras: masks and / or residual, bias, norm); every edge is hashed
+template <int HD, int D, bool ALPHA, bool BF = false, bool EXT = false>
+__global__ __launch_bounds__(256) void edge_fwd_kernel(FwdArgsT<EXT> A) {
     constexpr int G = 64 / HD;      // edges per wave-instruction
     constexpr int U = 16 / G;       // gathers in flight per group
     constexpr int CH = 16;          // edges per chunk (= U*G)
@@ -366,18 +353,16 @@ __global__ __launch_bounds__(256) void edge_fwd_kernel(FwdArgsT<DROP> A) {
     float sc[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) sc[u] = -INFINITY;
-    uint32_t kd = 0;
-    int rb = 0;
-    uint32_t ke = 0;
+    RowKeys k{};
     [[maybe_unused]] float rs = 0.f;
-    if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; ke = edge_row_key(A.drop, row); if (!split) rs = res_term(A, row, HD, c); }
+    if constexpr (EXT) { row_keys(A.x.drop, row, A.row_ptr, k); if (!split) rs = res_term(A.x, row, HD, c); }
 
     for (int e0 = b; e0 < e_end; e0 += CH) {
         if constexpr (U >= 2) {
-            if (e_end - e0 <= CH / 2) fwd_chunk<HD, D, U / 2, U, ALPHA, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, kd, rb, ke, row);
-            else fwd_chunk<HD, D, U, U, ALPHA, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, kd, rb, ke, row);
+            if (e_end - e0 <= CH / 2) fwd_chunk<HD, D, U / 2, U, ALPHA, BF, EXT>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, k.kd, k.rb, k.ke, row);
+            else fwd_chunk<HD, D, U, U, ALPHA, BF, EXT>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, k.kd, k.rb, k.ke, row);
         } else {
-            fwd_chunk<HD, D, U, U, ALPHA, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, kd, rb, ke, row);
+            fwd_chunk<HD, D, U, U, ALPHA, BF, EXT>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, k.kd, k.rb, k.ke, row);
         }
     }
 
@@ -417,15 +402,15 @@ __global__ __launch_bounds__(256) void edge_fwd_kernel(FwdArgsT<DROP> A) {
         fwd_normalize_slice<HD, D>(A, b, e_end, lane, m, inv);
     }
     }
-    if constexpr (DROP) fwd_write_row_ln<HD, D>(A, row, lane, m, Z, acc, rs, A.ln);
-    else fwd_write_row<HD, D, DROP>(A, row, lane, m, Z, acc, rs);
+    fwd_write_row<HD, D, EXT>(A, row, lane, m, Z, acc, rs);
 }
 
 // Split rows: one wave per segment merges ALL partials of its row (L2-hot, <= a few hundred
 // bytes each), normalises its own alpha slice, and the row's first segment writes the outputs.
-// RES: the residual form (argument struct of the DROP instantiations): the row's R + b joins the combined sum once, here
-template <int HD, int D, bool ALPHA, bool RES = false>
-__global__ __launch_bounds__(256) void edge_fwd_fix_kernel(FwdArgsT<RES> A) {
+// EXT: the extended argument struct — the row's R + b joins the combined sum once, here, and the row is normalised (the masks were
+// applied by the segments)
+template <int HD, int D, bool ALPHA, bool EXT = false>
+__global__ __launch_bounds__(256) void edge_fwd_fix_kernel(FwdArgsT<EXT> A) {
     constexpr int H = HD / D;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -465,8 +450,8 @@ __global__ __launch_bounds__(256) void edge_fwd_fix_kernel(FwdArgsT<RES> A) {
     for (; sg < s_end; ++sg)
         merge(A.part_mz[(int64_t)sg * 2 * H + c / D], A.part_mz[(int64_t)sg * 2 * H + H + c / D], A.part_acc[(int64_t)sg * HD + c]);
     if constexpr (ALPHA) fwd_normalize_slice<HD, D>(A, item.y, item.z, lane, m, __builtin_amdgcn_rcpf(Z + 1e-8f));
-    if constexpr (RES) { if (slot == info.y) fwd_write_row_ln<HD, D>(A, info.x, lane, m, Z, acc, res_term(A, info.x, HD, c), A.ln); }
-    else if (slot == info.y) fwd_write_row<HD, D>(A, info.x, lane, m, Z, acc);
+    if constexpr (EXT) { if (slot == info.y) fwd_write_row<HD, D, true>(A, info.x, lane, m, Z, acc, res_term(A.x, info.x, HD, c)); }
+    else if (slot == info.y) fwd_write_row<HD, D, false>(A, info.x, lane, m, Z, acc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -577,16 +562,14 @@ __global__ __launch_bounds__(256) void edge_bwd_kernel(BwdArgsT<DROP> A) {
         const float m2 = A.mstat[row * (HD / D) + c / D];
         const float inv = __builtin_amdgcn_rcpf(A.zstat[row * (HD / D) + c / D] + 1e-8f);
         float gpr = 0.f;
-        uint32_t kd = 0;
-        int rb = 0;
-        uint32_t ke = 0;
-        if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; ke = edge_row_key(A.drop, row); }
+        RowKeys k{};                                 // (filled in place: through row_keys() the compiler schedules this kernel differently)
+        if constexpr (DROP) { k.kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); k.rb = A.row_ptr[row]; k.ke = edge_row_key(A.drop, row); }
         for (int e0 = b; e0 < e_end; e0 += CH) {
             if constexpr (U >= 2) {
-                if (e_end - e0 <= CH / 2) bwd_chunk<HD, D, U / 2, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, kd, rb, ke, row);
-                else bwd_chunk<HD, D, U, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, kd, rb, ke, row);
+                if (e_end - e0 <= CH / 2) bwd_chunk<HD, D, U / 2, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
+                else bwd_chunk<HD, D, U, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
             } else {
-                bwd_chunk<HD, D, U, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, kd, rb, ke, row);
+                bwd_chunk<HD, D, U, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
             }
         }
 #pragma unroll
@@ -703,10 +686,10 @@ __device__ __forceinline__ void store_row_n(float* __restrict__ msg, int slot, i
 // finishes them unchanged.
 // the N-channel form of res_term: 8- / 16-byte loads (c is a multiple of N, H*D too)
 template <int N>
-__device__ __forceinline__ vnf<N> res_term_n(const EdgeFwdDropArgs& A, int64_t row, int HD, int c) {
+__device__ __forceinline__ vnf<N> res_term_n(const EdgeFwdExtras& X, int64_t row, int HD, int c) {
     vnf<N> r = vzero<N>();
-    if (A.res != nullptr) r = *reinterpret_cast<const vnf<N>*>(A.res + row * HD + c);
-    if (A.bias != nullptr) r += *reinterpret_cast<const vnf<N>*>(A.bias + c);
+    if (X.res != nullptr) r = *reinterpret_cast<const vnf<N>*>(X.res + row * HD + c);
+    if (X.bias != nullptr) r += *reinterpret_cast<const vnf<N>*>(X.bias + c);
     return r;
 }
 
@@ -723,7 +706,7 @@ __device__ __forceinline__ vnf<N> ln_row_n(vnf<N> u, const LnArgs& ln, int c) {
     return v;
 }
 
-template <int HD, int D, int N, int UU, bool BF, bool DROP = false, class AT = EdgeFwdArgs>
+template <int HD, int D, int N, int UU, bool BF, bool EXT = false, class AT = EdgeFwdArgs>
 __device__ __forceinline__ void fwd2_chunk(const AT& A, int e0, int e_end_v, int cp, int gidx, int srcv,
                                            vnf<N> pr, vnf<N> ac2, float& m, float& Z, vnf<N>& acc, uint32_t kd = 0, int rb = 0,
                                            uint32_t ke = 0, int64_t row = 0) {
@@ -734,7 +717,7 @@ __device__ __forceinline__ void fwd2_chunk(const AT& A, int e0, int e_end_v, int
     for (int u = 0; u < UU; ++u) {
         const int src = __shfl(srcv, u * G + gidx);
         v[u] = gather_row_n<HD, N, BF>(A.PL, src, cp);
-        if constexpr (DROP) ek[u] = drop_edge_kept(A.drop, ke, e0 + u * G + gidx - rb, src, row);
+        if constexpr (EXT) ek[u] = drop_edge_kept(A.x.drop, ke, e0 + u * G + gidx - rb, src, row);
     }
     float t[UU];
 #pragma unroll
@@ -745,7 +728,7 @@ __device__ __forceinline__ void fwd2_chunk(const AT& A, int e0, int e_end_v, int
     for (int u = 0; u < UU; ++u) {
         const int j = e0 + u * G + gidx;
         bool in = j < e_end_v;
-        if constexpr (DROP) in = in && ek[u];        // a dropped edge: out of the max, Z and the sum
+        if constexpr (EXT) in = in && ek[u];         // a dropped edge: out of the max, Z and the sum
         t[u] = in ? t[u] : -INFINITY;
         cm = fmaxf(cm, t[u]);
     }
@@ -757,14 +740,14 @@ __device__ __forceinline__ void fwd2_chunk(const AT& A, int e0, int e_end_v, int
     for (int u = 0; u < UU; ++u) {
         const float p = exp2_fast(t[u] - mn);        // 0 for padded slots
         Z += p;
-        if constexpr (DROP) acc += (p * attn_keep(A.drop, kd, e0 + u * G + gidx - rb, (N * cp) / D)) * v[u];
+        if constexpr (EXT) acc += (p * attn_keep(A.x.drop, kd, e0 + u * G + gidx - rb, (N * cp) / D)) * v[u];
         else acc += p * v[u];
     }
     m = mn;
 }
 
-template <int HD, int D, int N, bool BF = false, bool DROP = false>
-__global__ __launch_bounds__(256) void edge_fwd2_kernel(FwdArgsT<DROP> A) {
+template <int HD, int D, int N, bool BF = false, bool EXT = false>
+__global__ __launch_bounds__(256) void edge_fwd2_kernel(FwdArgsT<EXT> A) {
     constexpr int LPE = HD / N, G = 64 / LPE, DL = D / N, H = HD / D;
     constexpr int CH = 16;
     constexpr int U = CH / G;
@@ -789,17 +772,15 @@ __global__ __launch_bounds__(256) void edge_fwd2_kernel(FwdArgsT<DROP> A) {
     };
     int srcv = 0;
     if (b < e_end) srcv = load_idx(b);               // empty item (zero in-degree row): e_end - 1 would be b - 1, i.e. -1 for row 0
-    uint32_t kd = 0;
-    int rb = 0;
-    uint32_t ke = 0;
-    if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; ke = edge_row_key(A.drop, row); }
+    RowKeys k{};
+    if constexpr (EXT) row_keys(A.x.drop, row, A.row_ptr, k);
     for (int e0 = b; e0 < e_end; e0 += CH) {
         const int srcn = (e0 + CH < e_end) ? load_idx(e0 + CH) : 0;
         if constexpr (U >= 2) {
-            if (e_end - e0 <= CH / 2) fwd2_chunk<HD, D, N, U / 2, BF, DROP>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, kd, rb, ke, row);
-            else fwd2_chunk<HD, D, N, U, BF, DROP>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, kd, rb, ke, row);
+            if (e_end - e0 <= CH / 2) fwd2_chunk<HD, D, N, U / 2, BF, EXT>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, k.kd, k.rb, k.ke, row);
+            else fwd2_chunk<HD, D, N, U, BF, EXT>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, k.kd, k.rb, k.ke, row);
         } else {
-            fwd2_chunk<HD, D, N, U, BF, DROP>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, kd, rb, ke, row);
+            fwd2_chunk<HD, D, N, U, BF, EXT>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, k.kd, k.rb, k.ke, row);
         }
         srcv = srcn;
     }
@@ -825,12 +806,12 @@ __global__ __launch_bounds__(256) void edge_fwd2_kernel(FwdArgsT<DROP> A) {
         return;
     }
     vnf<N> hp = acc * __builtin_amdgcn_rcpf(Z + 1e-8f);          // E:379 epsilon
-    if constexpr (DROP) hp += res_term_n<N>(A, row, HD, c);      // residual / bias: before h_pre and hout are written
+    if constexpr (EXT) hp += res_term_n<N>(A.x, row, HD, c);      // residual / bias: before h_pre and hout are written
     if (gidx == 0) {
         *reinterpret_cast<vnf<N>*>(A.hpre + row * HD + c) = hp;
         if ((c % D) == 0) { A.mstat[row * H + c / D] = m; A.zstat[row * H + c / D] = Z; }
     }
-    if constexpr (DROP) { if (A.ln.gamma != nullptr) hp = ln_row_n<HD, N>(hp, A.ln, c); }     // hout = LReLU(v); h_pre stays u
+    if constexpr (EXT) { if (A.x.ln.gamma != nullptr) hp = ln_row_n<HD, N>(hp, A.x.ln, c); }     // hout = LReLU(v); h_pre stays u
     const vnf<N> act = lrelu_n<N>(hp, A.slope);
     if (!A.is_last) {
         if (gidx == 0) *reinterpret_cast<vnf<N>*>(A.hout + row * HD + c) = act;   // concat heads (E:452-457)
@@ -860,8 +841,8 @@ __device__ __forceinline__ int wave_max_over_groups(int v) {
     return __builtin_amdgcn_readfirstlane(v);
 }
 
-template <int HD, int D, int N, bool BF = false, bool DROP = false>
-__global__ __launch_bounds__(256) void edge_fwd3_kernel(FwdArgsT<DROP> A) {
+template <int HD, int D, int N, bool BF = false, bool EXT = false>
+__global__ __launch_bounds__(256) void edge_fwd3_kernel(FwdArgsT<EXT> A) {
     constexpr int LPE = HD / N, G = 64 / LPE, DL = D / N, H = HD / D;
     constexpr int U = 4;                             // edges per group and step: G*U gathers in flight per wave
     static_assert(D % N == 0 && LPE >= U, "lane layout");
@@ -886,10 +867,8 @@ __global__ __launch_bounds__(256) void edge_fwd3_kernel(FwdArgsT<DROP> A) {
         return A.col_idx[j > 0 ? j : 0];
     };
     int srcv = load_idx(0);
-    [[maybe_unused]] uint32_t kd = 0;
-    [[maybe_unused]] int rb = 0;
-    [[maybe_unused]] uint32_t ke = 0;
-    if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, rowc)); rb = A.row_ptr[rowc]; ke = edge_row_key(A.drop, rowc); }
+    [[maybe_unused]] RowKeys k{};                    // (filled in place: through row_keys() the compiler schedules this kernel differently)
+    if constexpr (EXT) { k.kd = drop_mix(drop_key(A.x.drop, kDropAttn), drop_node(A.x.drop, rowc)); k.rb = A.row_ptr[rowc]; k.ke = edge_row_key(A.x.drop, rowc); }
     for (int st = 0; st < nst; ++st) {
         const int srcn = load_idx(st + 1);           // next step's indices: in flight during this one
         vnf<N> v[U];
@@ -898,7 +877,7 @@ __global__ __launch_bounds__(256) void edge_fwd3_kernel(FwdArgsT<DROP> A) {
         for (int u = 0; u < U; ++u) {
             const int src = __shfl(srcv, gidx * LPE + u);
             v[u] = gather_row_n<HD, N, BF>(A.PL, src, cp);
-            if constexpr (DROP) ek[u] = drop_edge_kept(A.drop, ke, b + st * U + u - rb, src, rowc);
+            if constexpr (EXT) ek[u] = drop_edge_kept(A.x.drop, k.ke, b + st * U + u - k.rb, src, rowc);
         }
         float t[U];
 #pragma unroll
@@ -908,7 +887,7 @@ __global__ __launch_bounds__(256) void edge_fwd3_kernel(FwdArgsT<DROP> A) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             bool in = b + st * U + u < e;
-            if constexpr (DROP) in = in && ek[u];    // a dropped edge: out of the max, Z and the sum
+            if constexpr (EXT) in = in && ek[u];     // a dropped edge: out of the max, Z and the sum
             t[u] = in ? t[u] : -INFINITY;
             cm = fmaxf(cm, t[u]);
         }
@@ -920,7 +899,7 @@ __global__ __launch_bounds__(256) void edge_fwd3_kernel(FwdArgsT<DROP> A) {
         for (int u = 0; u < U; ++u) {
             const float p = exp2_fast(t[u] - mn);    // 0 for padded slots
             Z += p;
-            if constexpr (DROP) acc += (p * attn_keep(A.drop, kd, b + st * U + u - rb, c / D)) * v[u];   // the term, not Z
+            if constexpr (EXT) acc += (p * attn_keep(A.x.drop, k.kd, b + st * U + u - k.rb, c / D)) * v[u];   // the term, not Z
             else acc += p * v[u];
         }
         m = mn;
@@ -936,10 +915,10 @@ __global__ __launch_bounds__(256) void edge_fwd3_kernel(FwdArgsT<DROP> A) {
         return;
     }
     vnf<N> hp = acc * __builtin_amdgcn_rcpf(Z + 1e-8f);          // E:379 epsilon
-    if constexpr (DROP) hp += res_term_n<N>(A, row, HD, c);      // residual / bias: before h_pre and hout are written
+    if constexpr (EXT) hp += res_term_n<N>(A.x, row, HD, c);      // residual / bias: before h_pre and hout are written
     stream_store(reinterpret_cast<vnf<N>*>(A.hpre + (int64_t)row * HD + c), hp);
     if ((c % D) == 0) { A.mstat[(int64_t)row * H + c / D] = m; A.zstat[(int64_t)row * H + c / D] = Z; }
-    if constexpr (DROP) { if (A.ln.gamma != nullptr) hp = ln_row_n<HD, N>(hp, A.ln, c); }     // hout = LReLU(v); h_pre stays u
+    if constexpr (EXT) { if (A.x.ln.gamma != nullptr) hp = ln_row_n<HD, N>(hp, A.x.ln, c); }     // hout = LReLU(v); h_pre stays u
     const vnf<N> act = lrelu_n<N>(hp, A.slope);
     if (!A.is_last) {
         stream_store(reinterpret_cast<vnf<N>*>(A.hout + (int64_t)row * HD + c), act);     // concat heads (E:452-457)
@@ -1094,18 +1073,16 @@ __device__ __forceinline__ void edge_bwd2_body(const AT& A) {
         };
         int srcv = 0, posv = 0;
         if (b < e_end) load_idx(b, srcv, posv);                      // empty item: nothing to prefetch (e_end - 1 < b)
-        uint32_t kd = 0;
-        int rb = 0;
-        uint32_t ke = 0;
-        if constexpr (DROP) { kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); rb = A.row_ptr[row]; ke = edge_row_key(A.drop, row); }
+        RowKeys k{};
+        if constexpr (DROP) row_keys(A.drop, row, A.row_ptr, k);
         for (int e0 = b; e0 < e_end; e0 += CH) {
             int srcn = 0, posn = 0;
             if (e0 + CH < e_end) load_idx(e0 + CH, srcn, posn);      // next chunk's indices: in flight during this one
             if constexpr (U >= 2) {
-                if (e_end - e0 <= CH / 2) bwd2_chunk<HD, D, N, U / 2, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, kd, rb, ke, row);
-                else bwd2_chunk<HD, D, N, U, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, kd, rb, ke, row);
+                if (e_end - e0 <= CH / 2) bwd2_chunk<HD, D, N, U / 2, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
+                else bwd2_chunk<HD, D, N, U, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
             } else {
-                bwd2_chunk<HD, D, N, U, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, kd, rb, ke, row);
+                bwd2_chunk<HD, D, N, U, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
             }
             srcv = srcn; posv = posn;
         }
@@ -1857,8 +1834,11 @@ __global__ __launch_bounds__(256) void edge_bwd_fix_kernel(const int4* __restric
 // and, with ln.gamma, the row u is parked in LDS, normalised over its H*D channels (lane-strided sums in ascending order, then the
 // wave's butterfly) and hout = LReLU(v) (gatv2_abi.h "layer normalisation")
 template <bool RES>
-__device__ __forceinline__ void edge_fwd_generic_body(const EdgeFwdArgs& A, const DropArgs& dr, [[maybe_unused]] const float* __restrict__ res,
-                                                      [[maybe_unused]] const float* __restrict__ bias, [[maybe_unused]] const LnArgs& ln = LnArgs{}) {
+__device__ __forceinline__ void edge_fwd_generic_body(const EdgeFwdArgs& A, const EdgeFwdExtras& X) {
+    const DropArgs& dr = X.drop;
+    [[maybe_unused]] const float* __restrict__ res = X.res;
+    [[maybe_unused]] const float* __restrict__ bias = X.bias;
+    [[maybe_unused]] const LnArgs& ln = X.ln;
     extern __shared__ float lds[];
     const int H = A.H, D = A.D, HD = H * D;
     const int lane = threadIdx.x;
@@ -1941,10 +1921,8 @@ __device__ __forceinline__ void edge_fwd_generic_body(const EdgeFwdArgs& A, cons
         __syncthreads();
     }
 }
-__global__ __launch_bounds__(64) void edge_fwd_generic(EdgeFwdArgs A, DropArgs dr) { edge_fwd_generic_body<false>(A, dr, nullptr, nullptr); }
-__global__ __launch_bounds__(64) void edge_fwd_generic_res(EdgeFwdArgs A, DropArgs dr, const float* res, const float* bias, LnArgs ln) {
-    edge_fwd_generic_body<true>(A, dr, res, bias, ln);
-}
+__global__ __launch_bounds__(64) void edge_fwd_generic(EdgeFwdArgs A, EdgeFwdExtras X) { edge_fwd_generic_body<false>(A, X); }
+__global__ __launch_bounds__(64) void edge_fwd_generic_res(EdgeFwdArgs A, EdgeFwdExtras X) { edge_fwd_generic_body<true>(A, X); }
 
 __global__ __launch_bounds__(64) void edge_bwd_generic(EdgeBwdArgs A, DropArgs dr) {
     extern __shared__ float lds[];
@@ -2083,23 +2061,22 @@ struct EdgePick {
 };
 #define GAT_K(...) ((const void*)(__VA_ARGS__))
 
-// Forward.  Attention dropout / DropEdge (drop): the DROP instantiation of the kernel the default settings pick, one wave per
-// block — the parity-tap form with alpha, else the group-per-row kernel where the shape has one, else the packed wave-per-row
-// kernel.  The A/B switches of the default path (GAT_ROWGROUP, GAT_PACKED, GAT_CPL, GAT_FWD_WAVES) do not apply to it: only these
-// instantiations exist.
-// res: a residual / bias context — always with drop (the DROP instantiations' argument struct carries the pointers); its fix-up kernel
-// is the RES form, which takes that struct too.
+// Forward.  ext (EdgeFwdExtras were passed: masks and / or residual, bias, norm): the EXT instantiation of the kernel the default
+// settings pick, one wave per block — the parity-tap form with alpha, else the group-per-row kernel where the shape has one, else the
+// packed wave-per-row kernel.  The A/B switches of the default path (GAT_ROWGROUP, GAT_PACKED, GAT_CPL, GAT_FWD_WAVES) do not apply to
+// it: only these instantiations exist.
+// res (residual, bias or norm, always with ext): the fix-up kernel is the EXT form too — the masks alone leave it the plain one.
 template <int HD, int D, bool BF>
-EdgePick pick_fwd(const EdgeFwdArgs& a, bool drop, bool res) {
+EdgePick pick_fwd(const EdgeFwdArgs& a, bool ext, bool res) {
     static_assert(D % 2 == 0, "every fast-path shape has an even D");
     constexpr int N3 = stash_n<HD, D>(), N2 = (HD >= 32 && D % 4 == 0) ? 4 : 2;
     constexpr int G3 = N3 != 0 ? 64 / (HD / (N3 != 0 ? N3 : 1)) : 1;             // rows per wave of the group-per-row kernel
     if (a.alpha != nullptr) {                                                     // parity-tap form: alpha (and scores) materialised
         const void* fix = res ? GAT_K(edge_fwd_fix_kernel<HD, D, true, true>) : GAT_K(edge_fwd_fix_kernel<HD, D, true>);
-        return {drop ? GAT_K(edge_fwd_kernel<HD, D, true, BF, true>) : GAT_K(edge_fwd_kernel<HD, D, true, BF>), 256, 4, fix};
+        return {ext ? GAT_K(edge_fwd_kernel<HD, D, true, BF, true>) : GAT_K(edge_fwd_kernel<HD, D, true, BF>), 256, 4, fix};
     }
     const void* fix = res ? GAT_K(edge_fwd_fix_kernel<HD, D, false, true>) : GAT_K(edge_fwd_fix_kernel<HD, D, false>);
-    if (drop) {
+    if (ext) {
         if constexpr (N3 != 0) return {GAT_K(edge_fwd3_kernel<HD, D, N3, BF, true>), 64, G3, fix};
         else return {GAT_K(edge_fwd2_kernel<HD, D, N2, BF, true>), 64, 1, fix};
     }
@@ -2188,8 +2165,8 @@ EdgePick pick_bwd(const EdgeBwdArgs& a, bool drop, int dbg) {
 #define GAT_SHAPE_CASE(hd, d, FN, BF, ...) case hd * 1000 + d: return (BF) ? FN<hd, d, true>(__VA_ARGS__) : FN<hd, d, false>(__VA_ARGS__);
 #define GAT_DISPATCH_HD_D(HD, D, FN, BF, ...) \
     switch ((HD) * 1000 + (D)) { GAT_EDGE_SHAPES(GAT_SHAPE_CASE, FN, BF, __VA_ARGS__) default: break; }
-static EdgePick pick_forward(const EdgeFwdArgs& a, bool drop, bool res) {
-    GAT_DISPATCH_HD_D(a.H * a.D, a.D, pick_fwd, a.bf16 != 0, a, drop, res)
+static EdgePick pick_forward(const EdgeFwdArgs& a, bool ext, bool res) {
+    GAT_DISPATCH_HD_D(a.H * a.D, a.D, pick_fwd, a.bf16 != 0, a, ext, res)
     return {};
 }
 static EdgePick pick_backward(const EdgeBwdArgs& a, bool drop, int dbg) {
@@ -2216,12 +2193,11 @@ static int resident_blocks(const void* fn, unsigned block) {
     return cache[key] = per_cu * (cus > 0 ? cus : 256);
 }
 
-// the split rows' partial sums -> their rows (after either forward kernel)
-// arg: the kernel's argument struct (EdgeFwdArgs, or EdgeFwdDropArgs for the RES form)
-static int launch_fwd_fix(const EdgePick& p, const EdgeFwdArgs& a, void* arg, hipStream_t s) {
+// the split rows' partial sums -> their rows (after either forward kernel; the plain fix-up kernel reads the EdgeFwdArgs part of `a`)
+static int launch_fwd_fix(const EdgePick& p, EdgeFwdExtArgs& a, hipStream_t s) {
     if (a.n_slots <= 0) return 0;
     const int64_t n = a.alpha != nullptr ? a.n_slots : a.n_split;                 // per segment with alpha, else per split row
-    void* args[] = {arg};
+    void* args[] = {&a};
     GAT_HIP(hipLaunchKernel(p.fix, dim3((unsigned)((n + 3) / 4)), dim3(256), args, 0, s));
     return 0;
 }
@@ -2247,31 +2223,32 @@ int edge_stash_words(int32_t H, int32_t D) {
     return n ? H * D / n : 0;
 }
 
-int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const DropArgs* drop, const float* res, const float* bias, const LnArgs* ln) {
+int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const EdgeFwdExtras* extras) {
     if (a.n_rows <= 0) return 0;
-    DropArgs dr = drop != nullptr ? *drop : DropArgs{};
-    const LnArgs lna = (ln != nullptr && ln->gamma != nullptr) ? *ln : LnArgs{};
-    if (lna.gamma != nullptr && lna.beta == nullptr) return fail(GAT_E_INVALID, "edge_forward: layer normalisation without beta");
-    const bool with_res = res != nullptr || bias != nullptr || lna.gamma != nullptr;    // the RES forms: residual, bias, norm
+    EdgeFwdExtArgs ax;                                   // the extended argument struct; the plain kernels read its EdgeFwdArgs part
+    static_cast<EdgeFwdArgs&>(ax) = a;
+    if (extras != nullptr) ax.x = *extras;
+    EdgeFwdExtras& x = ax.x;
+    if (x.ln.gamma == nullptr) x.ln = LnArgs{};
+    else if (x.ln.beta == nullptr) return fail(GAT_E_INVALID, "edge_forward: layer normalisation without beta");
+    const bool with_res = x.res != nullptr || x.bias != nullptr || x.ln.gamma != nullptr;    // residual, bias, norm
+    // THE RULE (gat_internal.h EdgeFwdExtras): extras without an active mask — every draw keeps, nothing is scaled
+    if (!x.drop.on) { x.drop.T = 0; x.drop.Te = 0; x.drop.scale = 1.f; x.drop.eflags = 0; }
     if (edge_fast_path(a.H, a.D, a.n_table)) {
         if (a.items == nullptr) return fail(GAT_E_INVALID, "edge_forward: work-item list missing");
         if (a.mstat == nullptr || a.zstat == nullptr) return fail(GAT_E_INVALID, "edge_forward: stats buffers missing");
-        if (with_res && !dr.on) {                        // the DROP instantiations with nothing dropped: T = Te = 0 keeps every draw, scale 1
-            if (dr.step == nullptr) return fail(GAT_E_INVALID, "edge_forward: the residual form needs the step counter of the mask arguments");
-            dr.on = 1; dr.T = 0; dr.Te = 0; dr.scale = 1.f; dr.eflags = 0;
-        }
-        const EdgePick p = pick_forward(a, dr.on != 0, with_res);
-        EdgeFwdDropArgs ad;                              // the argument struct of the DROP instantiations
-        if (dr.on) { static_cast<EdgeFwdArgs&>(ad) = a; ad.drop = dr; ad.res = res; ad.bias = bias; ad.ln = lna; }
-        void* args[] = {dr.on ? (void*)&ad : (void*)const_cast<EdgeFwdArgs*>(&a)};
+        const bool ext = with_res || x.drop.on != 0;
+        if (ext && x.drop.step == nullptr) return fail(GAT_E_INVALID, "edge_forward: extras without DropArgs::step (the extended kernels read the device counter)");
+        const EdgePick p = pick_forward(a, ext, with_res);
+        void* args[] = {&ax};
         GAT_HIP(hipLaunchKernel(p.fn, dim3((unsigned)((a.n_items + p.per_block - 1) / p.per_block)), dim3(p.block), args, 0, s));
-        return launch_fwd_fix(p, a, with_res ? (void*)&ad : (void*)const_cast<EdgeFwdArgs*>(&a), s);
+        return launch_fwd_fix(p, ax, s);
     }
     const int HD = a.H * a.D;
     const int64_t blocks = a.n_rows < kGenericBlocks * 8 ? a.n_rows : kGenericBlocks * 8;
-    if (with_res) hipLaunchKernelGGL(edge_fwd_generic_res, dim3((unsigned)blocks), dim3(64), (size_t)HD * sizeof(float), s, a, dr, res, bias, lna);
-    else hipLaunchKernelGGL(edge_fwd_generic, dim3((unsigned)blocks), dim3(64), (size_t)HD * sizeof(float), s, a, dr);
-    GAT_HIP(hipGetLastError());
+    void* args[] = {&ax, &x};                            // (EdgeFwdArgs, EdgeFwdExtras)
+    GAT_HIP(hipLaunchKernel(with_res ? GAT_K(edge_fwd_generic_res) : GAT_K(edge_fwd_generic), dim3((unsigned)blocks), dim3(64), args,
+                            (size_t)HD * sizeof(float), s));
     return 0;
 }
 

@@ -138,27 +138,30 @@ struct WorkList {
     int32_t n_split = 0;              // rows cut into segments (entries n_slots .. n_slots+n_split-1 of slot_info)
 };
 void build_worklist(const int32_t* row_ptr, int64_t n_rows, WorkList& w);
-// drop (optional): attention dropout; drop->on selects the DROP instantiations, whose kernel argument is the struct below.  The
-// default kernels keep the plain argument struct (same layout, same machine code as without the feature).
-// res / bias (optional, gatv2_abi.h "residual"): h_pre[row][c] += res[row][c] + bias[c] in the row epilogue, before h_pre and hout
-// are written (split rows: once, in the fix-up kernel's combine).  Either one selects the DROP instantiations too — with nothing
-// dropped when drop is null or off — whose argument struct carries the two pointers.
-// ln (optional, gatv2_abi.h "layer normalisation"): with ln->gamma set, the row u = h_pre (residual term included) is normalised over
-// its H*D channels in the same epilogue, v = gamma * (u - mu) * rstd + beta, and hout = LReLU(v); h_pre stays u.  It selects the DROP
-// instantiations and their fix-up form like res / bias, and travels in the same argument struct.
 struct LnArgs {
     const float* gamma = nullptr; // [HD], null: no normalisation
     const float* beta = nullptr;  // [HD]
     float eps = 0.f;
 };
-int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const DropArgs* drop = nullptr, const float* res = nullptr,
-                        const float* bias = nullptr, const LnArgs* ln = nullptr);
-struct EdgeFwdDropArgs : EdgeFwdArgs {
+// What a forward may take beyond EdgeFwdArgs.  Any of it selects the extended instantiations of the kernels (and of the fix-up kernel),
+// whose argument struct is EdgeFwdExtArgs below; without extras the kernels keep the plain struct and the machine code they have
+// without these features.
+// drop: attention dropout / DropEdge (drop.on: a mask is active).  drop.step must point at a device counter whenever extras are
+//   passed: the extended instantiations hash every edge.  THE RULE, applied in launch_edge_forward and nowhere else: extras without
+//   an active mask run the extended instantiation with T = Te = 0, scale = 1 — every draw keeps, nothing is scaled.  (The generic
+//   kernels get the same struct and read drop.on at run time: off, they do not hash at all.  The template kernels never read it.)
+// res / bias (either may be null, gatv2_abi.h "residual"): h_pre[row][c] += res[row][c] + bias[c] in the row epilogue, before h_pre
+//   and hout are written (split rows: once, in the fix-up kernel's combine).
+// ln (gatv2_abi.h "layer normalisation"): with ln.gamma set, the row u = h_pre (residual term included) is normalised over its H*D
+//   channels in the same epilogue, v = gamma * (u - mu) * rstd + beta, and hout = LReLU(v); h_pre stays u.
+struct EdgeFwdExtras {
     DropArgs drop;
     const float* res = nullptr;   // [n_rows][HD] R = x' Wres^T of the shard's own rows, or null
     const float* bias = nullptr;  // [HD], or null
     LnArgs ln;
 };
+int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const EdgeFwdExtras* extras = nullptr);
+struct EdgeFwdExtArgs : EdgeFwdArgs { EdgeFwdExtras x; };
 
 struct EdgeBwdArgs {
     const int32_t* row_ptr;

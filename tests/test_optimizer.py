@@ -137,3 +137,44 @@ def test_clip_groups_independently(pkg):
     assert 0 < s < 1 and dev <= 2.0 ** -23, (s, dev)
     for r0, r1 in zip(*results):                            # fixed summation order: two contexts agree bit for bit
         assert np.array_equal(r0.view(np.uint32), r1.view(np.uint32))
+
+
+def test_clip_all_seven_groups(pkg):
+    """test_clip_groups_independently on a context that has every parameter group: each group's gradient is a constant of its own,
+    some norms above the threshold and some below; every group is clipped by its own norm (the fp64 bars of the test above), a
+    group below the threshold comes back bit for bit."""
+    A = pkg.abi
+    thr = 5.0
+    ALL = (A.PARAM_W, A.PARAM_A, A.PARAM_WO, A.PARAM_WRES, A.PARAM_B, A.PARAM_LN_G, A.PARAM_LN_B)
+    with pkg.GatContext([2, 2], [4, 4], 5, 3) as ctx:
+        ctx.set_residual(linear=True, bias=True)
+        ctx.set_norm()
+        n = 12                                              # a ring of a dozen nodes with self-loops (clip reads no graph: the context is complete)
+        row_ptr = (2 * np.arange(n + 1)).astype(np.int32)
+        col_idx = np.stack([np.arange(n), (np.arange(n) + 1) % n], 1).reshape(-1).astype(np.int32)
+        ctx.set_graph(row_ptr, col_idx)
+        ctx.set_features(np.zeros((n, 5), F32))
+        ctx.set_labels(np.zeros(n, np.int32))
+        counts = [ctx.param_count(g) for g in ALL]
+        assert counts == [8 * 2 * 5 + 8 * 2 * 8, 16, 12, 8 * 5 + 8 * 8, 16, 16, 16]
+        # constants 3 (-1)^k / (k + 1): norms 43.3 (W), 6 (a), 7.6 (Wres) above thr = 5; 3.5 (Wo), 2.4 (b), 2 (gamma), 1.7 (beta) below
+        grads = [np.full(cnt, (-1.0) ** k * 3.0 / (k + 1), F32) for k, cnt in enumerate(counts)]
+        norms = [np.linalg.norm(g.astype(np.float64)) for g in grads]
+        above = [nm > thr for nm in norms]
+        assert above == [True, True, False, True, False, False, False] and all(abs(nm / thr - 1.0) > 0.15 for nm in norms)
+        for grp, g in zip(ALL, grads):
+            ctx.grads_set(grp, g)
+        ctx.clip(thr)
+        for k, (grp, g) in enumerate(zip(ALL, grads)):
+            got = ctx.grads_get(grp)
+            if not above[k]:
+                assert np.array_equal(got.view(np.uint32), g.view(np.uint32)), k
+                continue
+            w64, c64 = g.astype(np.float64), got.astype(np.float64)
+            err = abs(np.linalg.norm(c64) / thr - 1.0)
+            parity.record(f"clip, seven groups, group {k}: |norm after / thr - 1|", err, 1e-5)
+            assert err <= 1e-5, (k, err)
+            s = float(c64 @ w64) / float(w64 @ w64)
+            dev = float((np.abs(c64 - s * w64) / np.maximum(np.abs(c64), 1e-30)).max())
+            parity.record(f"clip, seven groups, group {k}: direction, relative deviation per entry", dev, 2.0 ** -23)
+            assert 0 < s < 1 and dev <= 2.0 ** -23, (k, s, dev)
