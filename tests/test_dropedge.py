@@ -10,41 +10,13 @@ import pytest
 
 import dropedge_ref as E
 import dropout_ref as R
-from conftest import small_graph
+import feature_cases as FC
+from feature_cases import FAMILIES, make_ctx, make_graph
 
 pytestmark = pytest.mark.gpu
+WAWO = ["W", "a", "Wo"]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "graph-attention-network-gatv2-_amd", "train_edge")
-
-
-def make_graph(seed, n=300, e=4000, F=24, C=5, self_loops=False):
-    """A graph with an empty row and a hub row of 300 in-edges (split into segments: its edge positions span them).
-    self_loops: the first edge of every non-empty row is replaced by the row's self-loop."""
-    rng = np.random.default_rng(seed)
-    rp, ci = small_graph(rng, n, e, hub=(7, 300), empty=(3,))
-    if self_loops:
-        ne = np.diff(rp) > 0
-        ci = ci.copy()
-        ci[rp[:-1][ne]] = np.arange(n, dtype=np.int32)[ne]
-    x = rng.standard_normal((n, F)).astype(np.float32)
-    lab = rng.integers(0, C, n).astype(np.int32)
-    return dict(row_ptr=rp, col_idx=ci, x=x, labels=lab, n=n, f=F, c=C)
-
-
-def make_ctx(pkg, g, heads, outdims, params, **kw):
-    A = pkg.abi
-    ctx = pkg.GatContext(heads, outdims, g["f"], g["c"], **kw)
-    ctx.set_graph(g["row_ptr"], g["col_idx"])
-    ctx.set_features(g["x"])
-    ctx.set_labels(g["labels"])
-    W, a, Wo = params
-    ctx.params_set(A.PARAM_W, W); ctx.params_set(A.PARAM_A, a); ctx.params_set(A.PARAM_WO, Wo)
-    ctx.zero_grad()
-    return ctx
-
-
-def grads(pkg, ctx):
-    return [ctx.grads_get(k) for k in (pkg.abi.PARAM_W, pkg.abi.PARAM_A, pkg.abi.PARAM_WO)]
 
 
 def test_off_is_off(pkg, orc):
@@ -55,7 +27,7 @@ def test_off_is_off(pkg, orc):
         b.set_dropedge(0.0, keep_self=True, shared_layers=True)
         ra, rb = a.step(), b.step()
         assert ra == rb
-        for x, y in zip(grads(pkg, a), grads(pkg, b)):
+        for x, y in zip(FC.grads(pkg, a, WAWO), FC.grads(pkg, b, WAWO)):
             assert np.array_equal(x, y)
         assert b.dropout_step() == 0                         # nothing runs, nothing advances
 
@@ -104,49 +76,10 @@ def test_without_set_dropout_seed_and_counter_are_zero(pkg, orc):
         assert np.array_equal(ctx.tap(A.TAP_EDGE_KEEP, 1), want.astype(np.float32))
 
 
-def _pick_params(orc, cfg, g, model):
-    """First Xavier seed whose fp64 model keeps every |s| and |h_pre| away from the LeakyReLU kink (no kink correction)."""
-    for ps in range(40):
-        P = orc.xavier_params(cfg, ps)
-        ref = model(P)
-        if ref["s_min"] > 1e-5 and ref["hpre_min"] > 1e-5:
-            return P, ref
-    raise AssertionError("no parameter seed clear of the LeakyReLU kink")
-
-
-FAMILIES = [
-    ("records_d8", [8, 8], [8, 8], {}),
-    ("records_d4", [16, 16], [4, 4], {}),
-    ("msg_rows_d16", [4, 4], [16, 16], {}),
-    ("hd16", [2, 2], [8, 8], {}),
-    ("generic", [3, 2], [5, 8], {}),
-    ("hd128_generic", [16, 2], [8, 8], {}),
-    ("keep_taps", [8, 8], [8, 8], {"keep_taps": True}),
-    ("bf16", [8, 8], [8, 8], {"dtype": "bf16"}),
-]
-
-
-def _compare(pkg, ctx, g, cfg, ref, loss, tol):
-    A = pkg.abi
-    n = g["n"]
-    want_loss = ref["loss"].item()
-    print("loss/N", loss / n, want_loss / n)
-    assert abs(loss / n - want_loss / n) < tol, (loss / n, want_loss / n)
-    for l in range(cfg.L):
-        want = ref["hpre"][l].detach().numpy()
-        got = ctx.tap(A.TAP_HPRE, l)
-        print("hpre", l, np.abs(got - want).max(), np.abs(want).max())
-        assert np.abs(got - want).max() <= tol * np.abs(want).max(), ("hpre", l)
-    for name, got, leaf in zip("W a Wo".split(), grads(pkg, ctx), (ref["W"], ref["a"], ref["Wo"])):
-        want = leaf.grad.numpy()
-        print("grad", name, np.abs(got - want).max(), np.abs(want).max())
-        assert np.abs(got - want).max() <= tol * np.abs(want).max(), name
-
-
 @pytest.mark.parametrize("pa,pf", [(0.0, 0.0), (0.3, 0.5)])
 @pytest.mark.parametrize("name,heads,outdims,kw", FAMILIES, ids=[f[0] for f in FAMILIES])
 def test_parity_against_fp64(pkg, orc, name, heads, outdims, kw, pa, pf):
-    """One mask per step for all layers, so that the model is dropout_ref.forward on ONE reduced graph."""
+    """One mask per step for all layers, so that the model is dropedge_ref.forward: the step model on ONE reduced graph."""
     pe, seed = 0.4, 77
     g = make_graph(5, n=150, e=700)              # small enough that some Xavier seed keeps every |s|, |h_pre| off the kink
     cfg = orc.Config(heads, outdims, g["f"], g["c"])
@@ -156,8 +89,8 @@ def test_parity_against_fp64(pkg, orc, name, heads, outdims, kw, pa, pf):
     attn = [R.attn_factor(seed, 1, l, g["row_ptr"], heads[l], pa) for l in range(cfg.L)] if pa > 0 else None
     feat = [R.feat_factor(seed, 1, l, g["n"], cfg.in_dims[l], pf) for l in range(cfg.L)] if pf > 0 else None
     bf16 = kw.get("dtype") == "bf16"
-    P, ref = _pick_params(orc, cfg, g, lambda P: E.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, keep=keep,
-                                                          attn=attn, feat=feat, bf16_pl=bf16))
+    P, ref = FC.pick_params(orc, cfg, lambda ps, P: (E.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, keep=keep,
+                                                               attn=attn, feat=feat, bf16_pl=bf16),), FC.CLEAR_HPRE)
     ref["loss"].backward()
     tol = 1e-2 if bf16 else 1e-4
     with make_ctx(pkg, g, heads, outdims, P, **kw) as ctx:
@@ -165,7 +98,7 @@ def test_parity_against_fp64(pkg, orc, name, heads, outdims, kw, pa, pf):
         ctx.set_dropedge(pe, shared_layers=True)
         loss, _ = ctx.step()
         assert ctx.dropout_step() == 1           # once per forward, whichever regularisers are on
-        _compare(pkg, ctx, g, cfg, ref, loss, tol)
+        FC.compare(pkg, ctx, g, cfg, ref, loss, tol, taps=["hpre"], groups=WAWO)
         if kw.get("keep_taps"):                  # alpha: exactly 0 at dropped edges, rows of survivors sum to 1
             A = pkg.abi
             for tap in (A.TAP_ALPHA, A.TAP_GE, A.TAP_GALPHA):
@@ -187,14 +120,14 @@ def test_parity_with_a_mask_per_layer(pkg, orc, name, heads, outdims, kw):
     assert not np.array_equal(keeps[0], keeps[1])
     attn = [R.attn_factor(seed, 1, l, g["row_ptr"], heads[l], pa) for l in range(cfg.L)]
     feat = [R.feat_factor(seed, 1, l, g["n"], cfg.in_dims[l], pf) for l in range(cfg.L)]
-    P, ref = _pick_params(orc, cfg, g, lambda P: E.forward_layers(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P,
-                                                                 keeps=keeps, attn=attn, feat=feat, bf16_pl=bf16))
+    P, ref = FC.pick_params(orc, cfg, lambda ps, P: (FC.run_model(cfg, g, P, keeps=keeps, attn=attn, feat=feat, bf16_pl=bf16),),
+                            FC.CLEAR_HPRE)
     ref["loss"].backward()
     with make_ctx(pkg, g, heads, outdims, P, **kw) as ctx:
         ctx.set_dropout(pf, pa, seed=seed, first_step=0)
         ctx.set_dropedge(pe)
         loss, _ = ctx.step()
-        _compare(pkg, ctx, g, cfg, ref, loss, 1e-2 if bf16 else 1e-4)
+        FC.compare(pkg, ctx, g, cfg, ref, loss, 1e-2 if bf16 else 1e-4, taps=["hpre"], groups=WAWO)
 
 
 @pytest.mark.parametrize("name,heads,outdims,kw", [f for f in FAMILIES if f[0] in ("records_d8", "msg_rows_d16", "generic", "keep_taps")],
@@ -220,7 +153,7 @@ def test_equivalence_with_the_reduced_graph(pkg, orc, name, heads, outdims, kw):
             x, y = a.tap(A.TAP_HPRE, l), b.tap(A.TAP_HPRE, l)
             print("hpre", l, np.abs(x - y).max(), np.abs(y).max())
             assert np.abs(x - y).max() <= 1e-4 * np.abs(y).max()
-        for x, y in zip(grads(pkg, a), grads(pkg, b)):
+        for x, y in zip(FC.grads(pkg, a, WAWO), FC.grads(pkg, b, WAWO)):
             print("grad", np.abs(x - y).max(), np.abs(y).max())
             assert np.abs(x - y).max() <= 1e-4 * np.abs(y).max()
         if kw.get("keep_taps"):
@@ -263,7 +196,7 @@ def test_row_that_loses_all_its_edges(pkg, orc, kw):
                 mx, sm = ctx.tap(A.TAP_MAX, l), ctx.tap(A.TAP_SUM, l)
                 assert (mx[:, emptied[l]] == mx[:, [3]]).all() and (sm[:, emptied[l]] == 0).all()
                 assert (ctx.tap(A.TAP_ALPHA, l)[:, ~keeps[l]] == 0).all()
-        for x in grads(pkg, ctx):
+        for x in FC.grads(pkg, ctx, WAWO):
             assert np.isfinite(x).all() and np.abs(x).max() > 0
 
 
@@ -312,7 +245,7 @@ def test_first_step_resumes_the_sequence(pkg, orc):
             ctx.set_dropout(0.0, 0.0, seed=9, first_step=first)
             for _ in range(k):
                 ctx.zero_grad()
-                out.append((ctx.step(), grads(pkg, ctx)))
+                out.append((ctx.step(), FC.grads(pkg, ctx, WAWO)))
         return out
     a, b = run(0, 7), run(5, 2)
     for (la, ga), (lb, gb) in zip(a[5:], b):
@@ -335,7 +268,7 @@ def test_graph_replay_equals_eager(pkg, orc):
             le, lr = e.step(), r.step()
             assert le == lr
             losses.append(le)
-            for x, y in zip(grads(pkg, e), grads(pkg, r)):
+            for x, y in zip(FC.grads(pkg, e, WAWO), FC.grads(pkg, r, WAWO)):
                 assert np.array_equal(x, y)
         assert len(set(losses)) == 3             # a replay draws fresh masks
 
@@ -405,7 +338,7 @@ def test_products_full_size(pkg):
         for _ in range(2):                       # the same step twice: bitwise equal
             ctx.set_dropout(0.0, 0.0, seed=3, first_step=0)
             ctx.zero_grad()
-            outs.append((ctx.step(), grads(pkg, ctx)))
+            outs.append((ctx.step(), FC.grads(pkg, ctx, WAWO)))
         assert outs[0][0] == outs[1][0]
         assert all(np.array_equal(x, y) for x, y in zip(outs[0][1], outs[1][1]))
         assert all(np.isfinite(x).all() for x in outs[0][1])

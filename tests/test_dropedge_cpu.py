@@ -9,6 +9,7 @@ import pytest
 
 import dropedge_ref as E
 import dropout_ref as R
+import step_ref
 from conftest import small_graph
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -112,7 +113,7 @@ def test_reduce_graph():
 
 
 def test_layered_model_equals_the_reduced_graph_model(orc):
-    """forward_layers with one mask for all layers is dropout_ref.forward on the reduced graph."""
+    """step_ref.forward with one mask for all layers is dropedge_ref.forward: the same model on the reduced graph."""
     rng = np.random.default_rng(2)
     n, F, C = 60, 12, 4
     rp, ci = small_graph(rng, n, 400, empty=(3,))
@@ -123,7 +124,7 @@ def test_layered_model_equals_the_reduced_graph_model(orc):
     keep = E.edge_keep(4, 1, 0, rp, ci, 0.4, shared=True)
     attn = [R.attn_factor(4, 1, l, rp, 2, 0.3) for l in range(2)]
     a = E.forward(cfg, rp, ci, lab, x, *P, keep=keep, attn=attn)
-    b = E.forward_layers(cfg, rp, ci, lab, x, *P, keeps=[keep, keep], attn=attn)
+    b = step_ref.forward(cfg, rp, ci, lab, x, *P, keeps=[keep, keep], attn=attn)
     assert abs(a["loss"].item() - b["loss"].item()) < 1e-12 * abs(a["loss"].item())
     for u, v in zip(a["hpre"], b["hpre"]):
         assert np.allclose(u.detach().numpy(), v.detach().numpy(), rtol=0, atol=1e-13)

@@ -10,36 +10,13 @@ import numpy as np
 import pytest
 
 import dropout_ref as R
-from conftest import small_graph
+import feature_cases as FC
+from feature_cases import FAMILIES, make_ctx, make_graph
 
 pytestmark = pytest.mark.gpu
+WAWO = ["W", "a", "Wo"]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "graph-attention-network-gatv2-_amd", "train_edge")
-
-
-def make_graph(seed, n=300, e=4000, F=24, C=5):
-    """A graph with an empty row and a hub row of 300 in-edges (split into segments: its edge positions span them)."""
-    rng = np.random.default_rng(seed)
-    rp, ci = small_graph(rng, n, e, hub=(7, 300), empty=(3,))
-    x = rng.standard_normal((n, F)).astype(np.float32)
-    lab = rng.integers(0, C, n).astype(np.int32)
-    return dict(row_ptr=rp, col_idx=ci, x=x, labels=lab, n=n, f=F, c=C)
-
-
-def make_ctx(pkg, g, heads, outdims, params, **kw):
-    A = pkg.abi
-    ctx = pkg.GatContext(heads, outdims, g["f"], g["c"], **kw)
-    ctx.set_graph(g["row_ptr"], g["col_idx"])
-    ctx.set_features(g["x"])
-    ctx.set_labels(g["labels"])
-    W, a, Wo = params
-    ctx.params_set(A.PARAM_W, W); ctx.params_set(A.PARAM_A, a); ctx.params_set(A.PARAM_WO, Wo)
-    ctx.zero_grad()
-    return ctx
-
-
-def grads(pkg, ctx):
-    return [ctx.grads_get(k) for k in (pkg.abi.PARAM_W, pkg.abi.PARAM_A, pkg.abi.PARAM_WO)]
 
 
 def test_off_is_off(pkg, orc):
@@ -50,7 +27,7 @@ def test_off_is_off(pkg, orc):
         b.set_dropout(0.0, 0.0, seed=99, first_step=4)
         ra, rb = a.step(), b.step()
         assert ra == rb
-        for x, y in zip(grads(pkg, a), grads(pkg, b)):
+        for x, y in zip(FC.grads(pkg, a, WAWO), FC.grads(pkg, b, WAWO)):
             assert np.array_equal(x, y)
         assert b.dropout_step() == 4                         # nothing runs, nothing advances
 
@@ -75,28 +52,6 @@ def test_mask_taps_equal_the_numpy_hash(pkg, orc):
         assert hub.stop - hub.start == 300
 
 
-def _pick_params(orc, cfg, g, attn, feat, bf16=False):
-    """First Xavier seed whose fp64 model keeps every |s| and |h_pre| away from the LeakyReLU kink (no kink correction)."""
-    for ps in range(40):
-        P = orc.xavier_params(cfg, ps)
-        ref = R.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, attn=attn, feat=feat, bf16_pl=bf16)
-        if ref["s_min"] > 1e-5 and ref["hpre_min"] > 1e-5:
-            return P, ref
-    raise AssertionError("no parameter seed clear of the LeakyReLU kink")
-
-
-FAMILIES = [
-    ("records_d8", [8, 8], [8, 8], {}),
-    ("records_d4", [16, 16], [4, 4], {}),
-    ("msg_rows_d16", [4, 4], [16, 16], {}),
-    ("hd16", [2, 2], [8, 8], {}),
-    ("generic", [3, 2], [5, 8], {}),
-    ("hd128_generic", [16, 2], [8, 8], {}),
-    ("keep_taps", [8, 8], [8, 8], {"keep_taps": True}),
-    ("bf16", [8, 8], [8, 8], {"dtype": "bf16"}),
-]
-
-
 @pytest.mark.parametrize("pf", [0.0, 0.5])
 @pytest.mark.parametrize("name,heads,outdims,kw", FAMILIES, ids=[f[0] for f in FAMILIES])
 def test_parity_against_fp64(pkg, orc, name, heads, outdims, kw, pf):
@@ -107,22 +62,14 @@ def test_parity_against_fp64(pkg, orc, name, heads, outdims, kw, pf):
     attn = [R.attn_factor(seed, 1, l, g["row_ptr"], heads[l], pa) for l in range(cfg.L)]
     feat = [R.feat_factor(seed, 1, l, g["n"], cfg.in_dims[l], pf) for l in range(cfg.L)] if pf > 0 else None
     bf16 = kw.get("dtype") == "bf16"
-    P, ref = _pick_params(orc, cfg, g, attn, feat, bf16)      # bf16: the reference gathers the bf16-rounded table too
+    P, ref = FC.pick_params(orc, cfg, lambda ps, P: (FC.run_model(cfg, g, P, attn=attn, feat=feat, bf16_pl=bf16),),
+                            FC.CLEAR_HPRE)                   # bf16: the reference gathers the bf16-rounded table too
     ref["loss"].backward()
     tol = 1e-2 if kw.get("dtype") == "bf16" else 1e-4
     with make_ctx(pkg, g, heads, outdims, P, **kw) as ctx:
         ctx.set_dropout(pf, pa, seed=seed, first_step=0)
         loss, _ = ctx.step()
-        n = g["n"]
-        want_loss = ref["loss"].item()
-        assert abs(loss / n - want_loss / n) < tol, (loss / n, want_loss / n)
-        for l in range(cfg.L):
-            want = ref["hpre"][l].detach().numpy()
-            got = ctx.tap(A.TAP_HPRE, l)
-            assert np.abs(got - want).max() <= tol * np.abs(want).max(), ("hpre", l)
-        for got, leaf in zip(grads(pkg, ctx), (ref["W"], ref["a"], ref["Wo"])):
-            want = leaf.grad.numpy()
-            assert np.abs(got - want).max() <= tol * np.abs(want).max()
+        FC.compare(pkg, ctx, g, cfg, ref, loss, tol, taps=["hpre"], groups=WAWO)
         if kw.get("keep_taps"):                  # the kept alpha is the softmax's (rows sum to 1), not kappa*s_a*alpha
             al = ctx.tap(A.TAP_ALPHA, 0)
             rp = g["row_ptr"]
@@ -171,7 +118,7 @@ def test_first_step_resumes_the_sequence(pkg, orc):
             ctx.set_dropout(0.5, 0.3, seed=9, first_step=first)
             for _ in range(k):
                 ctx.zero_grad()
-                out.append((ctx.step(), grads(pkg, ctx)))
+                out.append((ctx.step(), FC.grads(pkg, ctx, WAWO)))
         return out
     a, b = run(0, 7), run(5, 2)
     for (la, ga), (lb, gb) in zip(a[5:], b):
@@ -190,7 +137,7 @@ def test_graph_replay_equals_eager(pkg, orc):
         for _ in range(3):
             e.zero_grad(); r.zero_grad()
             assert e.step() == r.step()
-            for x, y in zip(grads(pkg, e), grads(pkg, r)):
+            for x, y in zip(FC.grads(pkg, e, WAWO), FC.grads(pkg, r, WAWO)):
                 assert np.array_equal(x, y)
 
 
@@ -276,7 +223,7 @@ def test_products_full_size(pkg):
         for _ in range(2):                       # the same step twice: bitwise equal
             ctx.set_dropout(0.5, 0.5, seed=3, first_step=0)
             ctx.zero_grad()
-            outs.append((ctx.step(), grads(pkg, ctx)))
+            outs.append((ctx.step(), FC.grads(pkg, ctx, WAWO)))
         assert outs[0][0] == outs[1][0]
         assert all(np.array_equal(x, y) for x, y in zip(outs[0][1], outs[1][1]))
         keep = ctx.tap(A.TAP_ATTN_KEEP, 1)       # [H][E] of the last layer

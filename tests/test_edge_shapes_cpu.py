@@ -1,15 +1,14 @@
 """tests/test_edge_shapes.py without a GPU: which kernel instantiation each of its 112 cases reaches (COVERAGE, restated from pick_fwd /
 pick_bwd of csrc/gat_edge_kernels.hip and the record-path rule of csrc/gat_abi.hip — documentation that cannot silently shrink, it
-inspects no binary), the new `alpha` key of tests/norm_ref.py, and — a condition, not a skip — a parameter seed clear of the
+inspects no binary), the `alpha` key of tests/step_ref.py, and — a condition, not a skip — a parameter seed clear of the
 LeakyReLU kinks among the first 40 for every case of the matrix."""
 import re
 
 import numpy as np
 import pytest
 
-import norm_ref as NR
-import test_edge_shapes as T
-from test_residual import REG, masks, parity_graph
+import feature_cases as T
+from feature_cases import REG, masks, parity_graph
 
 
 def stash_n(hd, d):
@@ -132,19 +131,19 @@ def test_the_graph_is_the_one_the_cases_need():
 @pytest.mark.parametrize("dt", T.DTYPES)
 @pytest.mark.parametrize("hd,d", T.SHAPES, ids=[f"hd{hd}_d{d}" for hd, d in T.SHAPES])
 def test_some_of_the_first_40_seeds_is_clear_of_the_kink(orc, hd, d, dt):
-    """pick_params of tests/test_edge_shapes.py raises when none of the first 40 seeds keeps the model off the kinks; the reference
+    """pick_shape of tests/feature_cases.py raises when none of the first 40 seeds keeps the model off the kinks; the reference
     alone must offer one for each of the three models the four forms run (the keep_taps form shares res_norm_reg's)."""
-    g, heads, outdims, cfg = T.model(orc, hd, d)
+    g, heads, outdims, cfg = T.shape_model(orc, hd, d)
     assert heads[0] * outdims[0] == hd
     for norm, reg in ((False, True), (True, False), (True, True)):
-        T.pick_params(orc, cfg, g, norm, REG if reg else None, dt == "bf16")
+        T.pick_shape(orc, cfg, g, norm, REG if reg else None, dt == "bf16")
 
 
 def _alpha_cases(orc, hd, d, reg):
-    g, heads, outdims, cfg = T.model(orc, hd, d)
+    g, heads, outdims, cfg = T.shape_model(orc, hd, d)
     keeps, attn, feat = masks(cfg, g, cfg.heads, reg)
     P = orc.xavier_params(cfg, 1)
-    ref = NR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, keeps=keeps, attn=attn, feat=feat)
+    ref = T.run_model(cfg, g, P, keeps=keeps, attn=attn, feat=feat)
     return g, cfg, P, keeps, ref
 
 

@@ -1,9 +1,9 @@
 """Layer normalisation on the GPU (include/gatv2_abi.h "layer normalisation"): off is off, parity of every dispatcher family
-against the fp64 model of tests/norm_ref.py (norm only and norm + both residual flags; plain and with all three regularisers; one
+against the fp64 model of tests/step_ref.py (norm only and norm + both residual flags; plain and with all three regularisers; one
 skip_last case), empty and emptied rows, H*D = 1, rows wider than one round of the backward kernel, a three-layer model, the step
 paths against each other, eval mode, the optimizer, init and dump / load, shards, error codes.
 
-The graph is parity_graph of tests/test_residual.py: 150 nodes, 700 edges, F = 24, C = 5, one empty row (3) and a hub row (7) of 300
+The graph is parity_graph of tests/feature_cases.py: 150 nodes, 700 edges, F = 24, C = 5, one empty row (3) and a hub row (7) of 300
 in-edges that is processed as segments — the smallest shapes that reach the split-row combine, the empty row and every family."""
 import os
 import subprocess
@@ -14,97 +14,30 @@ import numpy as np
 import pytest
 
 import dropedge_ref as E
-import norm_ref as NR
+import feature_cases as FC
 import parity
-import residual_ref as RR
-from conftest import small_graph
-from test_dropedge import FAMILIES, make_graph
-from test_residual import REG, masks, parity_graph
+import step_ref as SR
+from feature_cases import EPS, FAMILIES, REG, WIDE, compare, make_ctx, make_graph, parity_graph, pick_case, rows_keeps, wide_graph
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "graph-attention-network-gatv2-_amd", "train_edge")
 
-MODES = [("norm", False, False), ("norm_res", True, True)]       # (name, GAT_RES_LINEAR, GAT_RES_BIAS)
-EPS = 1e-5
-GROUPS = "W a Wo Wres b gamma beta".split()
+MODES = FC.NORM_MODES
+GROUPS = FC.GROUPS
+TAPS = ["hpre", "hout", "G"]
 
 
 def lrelu(t, slope=0.01):
     return np.where(t > 0, t, slope * t)
 
 
-def pick_params(orc, cfg, g, mode, reg=None, bf16=False, skip_last=False, keeps=None):
-    """First parameter seed (of 40) whose fp64 model keeps every |s| above 1e-5 and every |v| above 1e-4: no kink correction is needed.
-    -> (W, a, Wo), Wres | None, b | None, gamma, beta, the model's outputs."""
-    _, lin, bias = mode
-    k, attn, feat = masks(cfg, g, cfg.heads, reg)
-    keeps = k if keeps is None else keeps
-    for ps in range(40):
-        P = orc.xavier_params(cfg, ps)
-        Wres, b = RR.xavier_wres(cfg, ps)
-        Wres, b = (Wres if lin else None), (b if bias else None)
-        gamma, beta = NR.ln_params(cfg, ps)
-        ref = NR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, Wres=Wres, b=b, gamma=gamma, beta=beta, eps=EPS,
-                         skip_last=skip_last, keeps=keeps, attn=attn, feat=feat, bf16_pl=bf16)
-        if ref["s_min"] > 1e-5 and ref["v_min"] > 1e-4:
-            return P, Wres, b, gamma, beta, ref
-    raise AssertionError("no parameter seed clear of the LeakyReLU kink")
-
-
-ROWS_PE, ROWS_SEED = 0.9, 1
-
-
-def rows_keeps(g):
-    return [E.edge_keep(ROWS_SEED, 1, l, g["row_ptr"], g["col_idx"], ROWS_PE) for l in range(2)]
-
-
-def pick_rows_params(orc, cfg, g, mode):
-    return pick_params(orc, cfg, g, mode, keeps=rows_keeps(g))
-
-
-def make_ctx(pkg, g, heads, outdims, P, mode, Wres, b, gamma, beta, reg=None, skip_last=False, **kw):
-    A = pkg.abi
-    ctx = pkg.GatContext(heads, outdims, g["f"], g["c"], **kw)
-    ctx.set_norm(skip_last=skip_last, eps=EPS)
-    if mode[1] or mode[2]:
-        ctx.set_residual(linear=mode[1], bias=mode[2])           # after gat_set_norm: either order is allowed
-    ctx.set_graph(g["row_ptr"], g["col_idx"])
-    ctx.set_features(g["x"])
-    ctx.set_labels(g["labels"])
-    for grp, arr in zip((A.PARAM_W, A.PARAM_A, A.PARAM_WO, A.PARAM_WRES, A.PARAM_B, A.PARAM_LN_G, A.PARAM_LN_B), (*P, Wres, b, gamma, beta)):
-        if arr is not None:
-            ctx.params_set(grp, arr)
-    if reg is not None:
-        ctx.set_dropout(reg["pf"], reg["pa"], seed=reg["seed"], first_step=0)
-        ctx.set_dropedge(reg["pe"])
-    ctx.zero_grad()
-    return ctx
+def setters(mode, skip_last=False):
+    return FC.setters(mode, norm=True, skip_last=skip_last)
 
 
 def all_grads(pkg, ctx):
-    return [ctx.grads_get(k) for k in range(7)]
-
-
-def compare(pkg, ctx, g, cfg, ref, loss, tol):
-    """loss / N, every layer's h_pre, GAT_TAP_HOUT, GAT_TAP_G and all seven gradient groups at tol of max-abs (recorded)."""
-    A = pkg.abi
-    n = g["n"]
-    parity.record("loss/N", abs(loss / n - ref["loss"].item() / n), tol, kind="abs")
-    assert abs(loss / n - ref["loss"].item() / n) < tol, (loss / n, ref["loss"].item() / n)
-    for l in range(cfg.L):
-        for name, tap, want in (("hpre", A.TAP_HPRE, ref["hpre"][l]), ("hout", A.TAP_HOUT, ref["hout"][l]), ("G", A.TAP_G, ref["hpre"][l].grad)):
-            want = want.detach().numpy()
-            assert np.abs(want).max() > 0
-            parity.check_rel(f"{name}[{l}]", ctx.tap(tap, l).reshape(want.shape), want, tol)
-    for name, got in zip(GROUPS, all_grads(pkg, ctx)):
-        leaf = ref[name]
-        if leaf is None:
-            assert got.size == 0, name
-            continue
-        want = leaf.grad.numpy()
-        assert got.shape == want.shape and np.abs(want).max() > 0
-        parity.check_rel(f"grad {name}", got, want, tol)
+    return FC.grads(pkg, ctx, GROUPS)
 
 
 def test_off_is_off(pkg, orc):
@@ -113,15 +46,8 @@ def test_off_is_off(pkg, orc):
     cfg = orc.Config([8, 8], [8, 8], g["f"], g["c"])
     P = orc.xavier_params(cfg, 3)
 
-    def ctx_of(touch):
-        ctx = pkg.GatContext([8, 8], [8, 8], g["f"], g["c"], collect_timing=True)
-        if touch:
-            ctx.set_norm(layer=False, eps=float("nan"))      # flags == 0: eps is ignored
-        ctx.set_graph(g["row_ptr"], g["col_idx"]); ctx.set_features(g["x"]); ctx.set_labels(g["labels"])
-        for grp, arr in zip((A.PARAM_W, A.PARAM_A, A.PARAM_WO), P):
-            ctx.params_set(grp, arr)
-        ctx.zero_grad()
-        return ctx
+    def ctx_of(touch):                                       # flags == 0: eps is ignored
+        return make_ctx(pkg, g, [8, 8], [8, 8], P, norm=dict(layer=False, eps=float("nan")) if touch else None, collect_timing=True)
     with ctx_of(False) as a, ctx_of(True) as b:
         assert b.param_count(A.PARAM_LN_G) == 0 and b.param_count(A.PARAM_LN_B) == 0
         b.params_set(A.PARAM_LN_G, np.zeros(0, np.float32))
@@ -147,11 +73,11 @@ def test_parity_against_fp64(pkg, orc, name, heads, outdims, kw, mode, reg):
     g = parity_graph()
     cfg = orc.Config(heads, outdims, g["f"], g["c"])
     bf16 = kw.get("dtype") == "bf16"
-    P, Wres, b, gamma, beta, ref = pick_params(orc, cfg, g, mode, reg, bf16=bf16)
+    P, inp, ref = pick_case(orc, cfg, g, mode, norm=True, reg=reg, bf16_pl=bf16)
     ref["loss"].backward()
-    with make_ctx(pkg, g, heads, outdims, P, mode, Wres, b, gamma, beta, reg, **kw) as ctx:
+    with make_ctx(pkg, g, heads, outdims, P, **inp, **setters(mode), reg=reg, **kw) as ctx:
         loss, _ = ctx.step()
-        compare(pkg, ctx, g, cfg, ref, loss, 1e-2 if bf16 else 1e-4)
+        compare(pkg, ctx, g, cfg, ref, loss, 1e-2 if bf16 else 1e-4, TAPS, GROUPS)
 
 
 def test_skip_last(pkg, orc):
@@ -161,14 +87,14 @@ def test_skip_last(pkg, orc):
     g = parity_graph()
     heads, outdims = [8, 8], [8, 8]
     cfg = orc.Config(heads, outdims, g["f"], g["c"])
-    P, Wres, b, gamma, beta, ref = pick_params(orc, cfg, g, MODES[1], skip_last=True)
+    P, inp, ref = pick_case(orc, cfg, g, MODES[1], norm=True, skip_last=True)
     ref["loss"].backward()
-    gamma, beta = gamma.copy(), beta.copy()
+    gamma, beta = inp["gamma"].copy(), inp["beta"].copy()
     gamma[64:] = np.nan; beta[64:] = np.nan
-    with make_ctx(pkg, g, heads, outdims, P, MODES[1], Wres, b, gamma, beta, skip_last=True) as ctx:
+    with make_ctx(pkg, g, heads, outdims, P, **dict(inp, gamma=gamma, beta=beta), **setters(MODES[1], skip_last=True)) as ctx:
         assert ctx.param_count(A.PARAM_LN_G) == 128 and ctx.param_count(A.PARAM_LN_B) == 128
         loss, _ = ctx.step()
-        compare(pkg, ctx, g, cfg, ref, loss, 1e-4)
+        compare(pkg, ctx, g, cfg, ref, loss, 1e-4, TAPS, GROUPS)
         for k in (A.PARAM_LN_G, A.PARAM_LN_B):
             assert (ctx.grads_get(k)[64:] == 0).all()
 
@@ -185,13 +111,14 @@ def test_empty_and_emptied_rows(pkg, orc, mode):
     deg = np.diff(g["row_ptr"])
     emptied = [np.flatnonzero((deg > 0) & (np.diff(E.reduce_graph(g["row_ptr"], g["col_idx"], k)[0]) == 0)) for k in keeps]
     assert all(len(e) >= 1 for e in emptied)
-    P, Wres, b, gamma, beta, ref = pick_rows_params(orc, cfg, g, mode)
+    P, inp, ref = pick_case(orc, cfg, g, mode, norm=True, keeps=keeps)
+    beta = inp["beta"]
     ref["loss"].backward()
-    with make_ctx(pkg, g, heads, outdims, P, mode, Wres, b, gamma, beta) as ctx:
-        ctx.set_dropout(0.0, 0.0, seed=ROWS_SEED)
-        ctx.set_dropedge(ROWS_PE)
+    with make_ctx(pkg, g, heads, outdims, P, **inp, **setters(mode)) as ctx:
+        ctx.set_dropout(0.0, 0.0, seed=FC.ROWS_SEED)
+        ctx.set_dropedge(FC.ROWS_PE)
         loss, _ = ctx.step()
-        compare(pkg, ctx, g, cfg, ref, loss, 1e-4)
+        compare(pkg, ctx, g, cfg, ref, loss, 1e-4, TAPS, GROUPS)
         hout0 = ctx.tap(A.TAP_HOUT, 0).reshape(g["n"], 64)
         want0 = ref["hout"][0].detach().numpy()
         for r in [3] + list(emptied[0]):
@@ -209,8 +136,8 @@ def test_one_channel_rows(pkg, orc):
     heads, outdims = [1, 2], [1, 8]
     cfg = orc.Config(heads, outdims, g["f"], g["c"])
     P = orc.xavier_params(cfg, 1)
-    gamma, beta = NR.ln_params(cfg, 1)
-    with make_ctx(pkg, g, heads, outdims, P, MODES[0], None, None, gamma, beta) as ctx:
+    gamma, beta = SR.ln_params(cfg, 1)
+    with make_ctx(pkg, g, heads, outdims, P, gamma=gamma, beta=beta, **setters(MODES[0])) as ctx:
         loss, _ = ctx.step()
         assert np.isfinite(loss)
         hout0 = ctx.tap(A.TAP_HOUT, 0)
@@ -223,28 +150,15 @@ def test_one_channel_rows(pkg, orc):
         assert all(np.isfinite(x).all() for x in all_grads(pkg, ctx))
 
 
-# rows wider than one round of the backward kernel's row lanes: H*D = 65 (not a multiple of 4: one channel per lane, 64 lanes, two
-# rounds) and H*D = 260 (four channels per lane, two rounds); both on the generic edge kernels
-WIDE = [("hd65", [5, 2], [13, 8]), ("hd260", [20, 2], [13, 8])]
-
-
-def wide_graph():
-    """40 nodes, 200 edges, F = 12, one empty row: with 260 channels a larger graph leaves no seed clear of the kinks."""
-    rng = np.random.default_rng(9)
-    rp, ci = small_graph(rng, 40, 200, empty=(3,))
-    return dict(row_ptr=rp, col_idx=ci, x=rng.standard_normal((40, 12)).astype(np.float32), labels=rng.integers(0, 4, 40).astype(np.int32),
-                n=40, f=12, c=4)
-
-
 @pytest.mark.parametrize("name,heads,outdims", WIDE, ids=[w[0] for w in WIDE])
 def test_wide_rows(pkg, orc, name, heads, outdims):
     g = wide_graph()
     cfg = orc.Config(heads, outdims, g["f"], g["c"])
-    P, Wres, b, gamma, beta, ref = pick_params(orc, cfg, g, MODES[1])
+    P, inp, ref = pick_case(orc, cfg, g, MODES[1], norm=True)
     ref["loss"].backward()
-    with make_ctx(pkg, g, heads, outdims, P, MODES[1], Wres, b, gamma, beta) as ctx:
+    with make_ctx(pkg, g, heads, outdims, P, **inp, **setters(MODES[1])) as ctx:
         loss, _ = ctx.step()
-        compare(pkg, ctx, g, cfg, ref, loss, 1e-4)
+        compare(pkg, ctx, g, cfg, ref, loss, 1e-4, TAPS, GROUPS)
 
 
 @pytest.mark.parametrize("reg", [None, REG], ids=["plain", "regularised"])
@@ -252,11 +166,11 @@ def test_three_layers(pkg, orc, reg):
     g = parity_graph()
     heads, outdims = [8, 8, 8], [8, 8, 8]
     cfg = orc.Config(heads, outdims, g["f"], g["c"])
-    P, Wres, b, gamma, beta, ref = pick_params(orc, cfg, g, MODES[1], reg)
+    P, inp, ref = pick_case(orc, cfg, g, MODES[1], norm=True, reg=reg)
     ref["loss"].backward()
-    with make_ctx(pkg, g, heads, outdims, P, MODES[1], Wres, b, gamma, beta, reg) as ctx:
+    with make_ctx(pkg, g, heads, outdims, P, **inp, **setters(MODES[1]), reg=reg) as ctx:
         loss, _ = ctx.step()
-        compare(pkg, ctx, g, cfg, ref, loss, 1e-4)
+        compare(pkg, ctx, g, cfg, ref, loss, 1e-4, TAPS, GROUPS)
 
 
 @pytest.mark.parametrize("name,heads,outdims,kw", [f for f in FAMILIES if f[0] in ("records_d8", "msg_rows_d16", "generic")],
@@ -268,11 +182,11 @@ def test_paths_agree(pkg, orc, name, heads, outdims, kw):
     g = make_graph(2)
     cfg = orc.Config(heads, outdims, g["f"], g["c"])
     P = orc.xavier_params(cfg, 3)
-    Wres, b = RR.xavier_wres(cfg, 3)
-    gamma, beta = NR.ln_params(cfg, 3)
+    Wres, b = SR.xavier_wres(cfg, 3)
+    gamma, beta = SR.ln_params(cfg, 3)
 
     def new():
-        return make_ctx(pkg, g, heads, outdims, P, MODES[1], Wres, b, gamma, beta, **kw)
+        return make_ctx(pkg, g, heads, outdims, P, Wres=Wres, b=b, gamma=gamma, beta=beta, **setters(MODES[1]), **kw)
 
     def same(xs, ys):
         for i, (x, y) in enumerate(zip(xs, ys)):
@@ -311,20 +225,14 @@ def test_eval_mode_keeps_the_norm(pkg, orc):
     g = parity_graph()
     heads, outdims = [8, 8], [8, 8]
     cfg = orc.Config(heads, outdims, g["f"], g["c"])
-    P, Wres, b, gamma, beta, ref = pick_params(orc, cfg, g, MODES[1])
-    with make_ctx(pkg, g, heads, outdims, P, MODES[1], Wres, b, gamma, beta, REG) as ctx:
+    P, inp, ref = pick_case(orc, cfg, g, MODES[1], norm=True)
+    with make_ctx(pkg, g, heads, outdims, P, **inp, **setters(MODES[1]), reg=REG) as ctx:
         ctx.set_training(False)
         loss, _ = ctx.forward()
         assert abs(loss / g["n"] - ref["loss"].item() / g["n"]) < 1e-4
         for l in range(2):
             want = ref["hout"][l].detach().numpy()
             parity.check_rel(f"eval hout[{l}]", ctx.tap(A.TAP_HOUT, l).reshape(want.shape), want, 1e-4)
-
-
-def _adam64(p, g, m, v, lr, b1, b2, eps, t):
-    m[:] = b1 * m + (1.0 - b1) * g
-    v[:] = b2 * v + (1.0 - b2) * g * g
-    p -= lr * (m / (1.0 - b1 ** t)) / (np.sqrt(v / (1.0 - b2 ** t)) + eps)
 
 
 def test_optimizer_moves_the_new_groups(pkg):
@@ -363,7 +271,7 @@ def test_optimizer_moves_the_new_groups(pkg):
         after = []
         for k, p, x in zip(groups, p0, clipped):
             want = p.astype(np.float64)
-            _adam64(want, x.astype(np.float64), np.zeros(len(p)), np.zeros(len(p)), lr, b1, b2, eps, 1)
+            FC.adam64(want, x.astype(np.float64), np.zeros(len(p)), np.zeros(len(p)), lr, b1, b2, eps, 1)
             got = ctx.params_get(k)
             assert float(np.abs(got - want).max()) <= 1e-5 * lr + 2.0 ** -23 * pmax, k
             assert float(np.abs(got - p).max()) > 0.5 * lr        # the group moved
@@ -391,58 +299,20 @@ def test_params_init_keeps_the_other_groups(pkg):
         assert (nrm.params_get(A.PARAM_LN_B) == 0).all() and nrm.params_get(A.PARAM_LN_B).size == 80
 
 
-def _problem():
-    return make_graph(4, n=90, e=700, F=12, C=4)
-
-
-def _shard_inputs(orc, g):
-    cfg = orc.Config([8, 8], [8, 8], g["f"], g["c"])
-    return (*orc.xavier_params(cfg, 11), *RR.xavier_wres(cfg, 11), *NR.ln_params(cfg, 11))
-
-
-def _shard_worker(rank, world, outdir, shm, replicate):
-    sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import __graft_entry__ as entry
-    pkg = entry.load_package(); orc = entry.load_oracle()
-    g = _problem()
-    heads, outdims = [8, 8], [8, 8]
-    S = pkg.shard
-    plan = S.make_plan(g["row_ptr"], world, rank)
-    rp_l, ci_l = S.local_csr(plan, g["row_ptr"], g["col_idx"])
-    lo, hi = plan.row0, plan.row0 + plan.n_rows
-    ctx = pkg.GatContext(heads, outdims, g["f"], g["c"], device=0)
-    ctx.set_residual(linear=True, bias=True)
-    ctx.set_norm(eps=EPS)
-    ctx.set_graph(rp_l, ci_l, n_table=plan.n_table, table_row0=plan.table_row0)
-    if replicate:
-        ctx.set_source_features(plan.table_features(g["x"]))
-    else:
-        ctx.set_features(g["x"][lo:hi])
-    ctx.set_labels(g["labels"][lo:hi])
-    for grp, arr in enumerate(_shard_inputs(orc, g)):
-        ctx.params_set(grp, arr)
-    ctx.comm_init_host(world, rank, shm, 4 * max(plan.n_table * 64, ctx.n_params + 3))
-    ctx.zero_grad()
-    loss, correct = ctx.step()
-    grads = np.concatenate([ctx.grads_get(k) for k in range(7)])
-    np.savez(os.path.join(outdir, f"r{rank}.npz"), loss=loss, correct=correct, grads=grads)
-    ctx.close()
-
-
 @pytest.mark.parametrize("replicate", [False, True], ids=["exchange", "replicated_input"])
 @pytest.mark.parametrize("world", [2, 3])
 def test_shards_on_the_host_transport(pkg, orc, world, replicate):
     """`world` processes sharing one GPU equal the single-GPU gradients at 1e-5 (all seven groups; the all-reduce sums the new ones)."""
     import torch.multiprocessing as mp
-    g = _problem()
-    inp = _shard_inputs(orc, g)
-    with make_ctx(pkg, g, [8, 8], [8, 8], inp[:3], MODES[1], *inp[3:]) as one:
+    g = FC.shard_problem()
+    inp = FC.shard_inputs(orc, g, norm=True)
+    with make_ctx(pkg, g, [8, 8], [8, 8], inp[:3], **dict(zip(GROUPS[3:], inp[3:])), **setters(MODES[1])) as one:
         loss1, correct1 = one.step()
         gs = all_grads(pkg, one)
         assert all(np.abs(x).max() > 0 for x in gs)
         want = np.concatenate(gs)
     with tempfile.TemporaryDirectory() as d:
-        mp.spawn(_shard_worker, args=(world, d, f"/gatv2_norm_{os.getpid()}_{world}_{int(replicate)}", replicate), nprocs=world, join=True)
+        mp.spawn(FC.shard_worker, args=(world, d, f"/gatv2_norm_{os.getpid()}_{world}_{int(replicate)}", replicate, True), nprocs=world, join=True)
         outs = [np.load(os.path.join(d, f"r{r}.npz")) for r in range(world)]
     for o in outs:
         assert abs(float(o["loss"]) - loss1) <= 1e-5 * max(1.0, abs(loss1)) and int(o["correct"]) == correct1

@@ -1,6 +1,6 @@
 """Layer normalisation without a GPU (include/gatv2_abi.h "layer normalisation"): the new ABI symbols, the fp64 model of
-tests/norm_ref.py against a hand formula, against the model without the feature and against central differences, the train_edge
-flags, and — a condition, not a skip — a parameter seed clear of the LeakyReLU kinks for every case tests/test_norm.py runs."""
+tests/step_ref.py against a hand formula and against central differences (tests/test_step_ref_cpu.py pins it against the models it
+replaced), the train_edge flags, and — a condition, not a skip — a parameter seed clear of the LeakyReLU kinks for every case tests/test_norm.py runs."""
 import ctypes
 import os
 import subprocess
@@ -8,24 +8,16 @@ import subprocess
 import numpy as np
 import pytest
 
-import norm_ref as NR
-import residual_ref as RR
-from conftest import small_graph
+import feature_cases as T
+import step_ref as SR
+from feature_cases import host_graph as _graph
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "graph-attention-network-gatv2-_amd", "train_edge")
 
 
-def _graph(seed, n=40, e=300, F=6, C=3):
-    rng = np.random.default_rng(seed)
-    rp, ci = small_graph(rng, n, e, hub=(7, 40), empty=(3,))
-    x = rng.standard_normal((n, F)).astype(np.float32)
-    lab = rng.integers(0, C, n).astype(np.int32)
-    return dict(row_ptr=rp, col_idx=ci, x=x, labels=lab, n=n, f=F, c=C)
-
-
 def _run(cfg, g, P, **kw):
-    return NR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, **kw)
+    return T.run_model(cfg, g, P, **kw)
 
 
 def test_symbols_declared_and_exported(pkg):
@@ -48,7 +40,7 @@ def test_one_row_against_the_hand_formula(orc):
     g = _graph(1)
     cfg = orc.Config([4, 2], [4, 8], g["f"], g["c"])
     P = orc.xavier_params(cfg, 3)
-    n = NR.offsets(cfg)[-1]
+    n = SR.ln_offsets(cfg)[-1]
     row = 11
     lrelu = lambda t: np.where(t > 0, t, 0.01 * t)
     for eps in (1e-5, 1e6):
@@ -63,28 +55,11 @@ def test_one_row_against_the_hand_formula(orc):
             assert np.abs(got - lrelu(d / 1e3)).max() <= 1e-6 * np.abs(got).max()
 
 
-def test_norm_off_is_the_residual_model(orc):
-    g = _graph(1)
-    cfg = orc.Config([4, 2], [4, 8], g["f"], g["c"])
-    P = orc.xavier_params(cfg, 3)
-    Wres, b = RR.xavier_wres(cfg, 3)
-    want = RR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, Wres=Wres, b=b)
-    got = _run(cfg, g, P, Wres=Wres, b=b)
-    assert got["loss"].item() == want["loss"].item()
-    for x, y in zip(got["hpre"], want["hpre"]):
-        assert np.array_equal(x.detach().numpy(), y.detach().numpy())
-    want["loss"].backward()
-    got["loss"].backward()
-    for k in ("W", "a", "Wo", "Wres", "b"):
-        assert np.array_equal(got[k].grad.numpy(), want[k].grad.numpy())
-    assert got["gamma"] is None and got["beta"] is None
-
-
 def test_empty_row_without_residual_has_v_equal_beta(orc):
     g = _graph(2)
     cfg = orc.Config([4, 2], [4, 8], g["f"], g["c"])
     P = orc.xavier_params(cfg, 1)
-    gamma, beta = NR.ln_params(cfg, 1)
+    gamma, beta = SR.ln_params(cfg, 1)
     ref = _run(cfg, g, P, gamma=gamma, beta=beta)
     assert g["row_ptr"][3] == g["row_ptr"][4]
     assert (ref["hpre"][0][3] == 0).all()
@@ -96,9 +71,9 @@ def test_autograd_matches_central_differences(orc):
     g = _graph(4, n=25, e=120)
     cfg = orc.Config([2, 2], [3, 4], g["f"], g["c"])
     P = orc.xavier_params(cfg, 2)
-    Wres, b = RR.xavier_wres(cfg, 2)
+    Wres, b = SR.xavier_wres(cfg, 2)
     for ps in range(40):
-        gamma, beta = (v.astype(np.float64) for v in NR.ln_params(cfg, ps))
+        gamma, beta = (v.astype(np.float64) for v in SR.ln_params(cfg, ps))
         ref = _run(cfg, g, P, Wres=Wres, b=b, gamma=gamma, beta=beta)
         if ref["s_min"] > 1e-4 and ref["v_min"] > 1e-4:      # the probes below stay on one side of every kink
             break
@@ -126,12 +101,12 @@ def test_the_contracts_backward_formulas_are_autograd(orc):
     g = _graph(4, n=25, e=120)
     cfg = orc.Config([2, 2], [3, 4], g["f"], g["c"])
     P = orc.xavier_params(cfg, 2)
-    Wres, b = RR.xavier_wres(cfg, 2)
-    gamma, beta = (v.astype(np.float64) for v in NR.ln_params(cfg, 2))
+    Wres, b = SR.xavier_wres(cfg, 2)
+    gamma, beta = (v.astype(np.float64) for v in SR.ln_params(cfg, 2))
     eps, slope = 1e-5, 0.01
     ref = _run(cfg, g, P, Wres=Wres, b=b, gamma=gamma, beta=beta, eps=eps)
     ref["loss"].backward()
-    o = NR.offsets(cfg)
+    o = SR.ln_offsets(cfg)
     for l in range(2):
         H, D = cfg.heads[l], cfg.outdims[l]
         u = ref["hpre"][l].detach().numpy().reshape(g["n"], H * D)
@@ -157,10 +132,10 @@ def test_skip_last_leaves_the_last_entries_without_gradient(orc):
     g = _graph(4, n=25, e=120)
     cfg = orc.Config([2, 2], [3, 4], g["f"], g["c"])
     P = orc.xavier_params(cfg, 2)
-    gamma, beta = NR.ln_params(cfg, 2)
+    gamma, beta = SR.ln_params(cfg, 2)
     ref = _run(cfg, g, P, gamma=gamma, beta=beta, skip_last=True)
     ref["loss"].backward()
-    o = NR.offsets(cfg)
+    o = SR.ln_offsets(cfg)
     for k in ("gamma", "beta"):
         assert (ref[k].grad[o[1]:] == 0).all() and ref[k].grad[:o[1]].abs().max() > 0
 
@@ -182,24 +157,22 @@ GPU_SHAPES = [
                          ids=[f"{'x'.join(map(str, h))}_{'x'.join(map(str, d))}{'_bf16' if b else ''}" for h, d, b in GPU_SHAPES])
 def test_some_of_the_first_40_seeds_is_clear_of_the_kink(orc, heads, outdims, bf16):
     """The GPU tests pick the first parameter seed with min |s| above 1e-5 and min |v| above 1e-4; the reference alone must offer one
-    among the first 40, for every case they run (pick_params raises otherwise): norm only and norm + both residual flags, plain and
+    among the first 40, for every case they run (pick_case of tests/feature_cases.py raises otherwise): norm only and norm + both residual flags, plain and
     with the three regularisers on, and the skip_last case."""
-    import test_norm as T
     g = T.parity_graph()
     assert int(g["row_ptr"][8] - g["row_ptr"][7]) == 300 and g["row_ptr"][3] == g["row_ptr"][4]
     cfg = orc.Config(heads, outdims, g["f"], g["c"])
-    for mode in T.MODES:
+    for mode in T.NORM_MODES:
         for reg in (None, T.REG):
-            T.pick_params(orc, cfg, g, mode, reg, bf16=bf16)
+            T.pick_case(orc, cfg, g, mode, norm=True, reg=reg, bf16_pl=bf16)
     if heads == [8, 8] and not bf16:
-        T.pick_params(orc, cfg, g, T.MODES[1], skip_last=True)
-        T.pick_rows_params(orc, cfg, g, T.MODES[0])
-        T.pick_rows_params(orc, cfg, g, T.MODES[1])
+        T.pick_case(orc, cfg, g, T.NORM_MODES[1], norm=True, skip_last=True)
+        for mode in T.NORM_MODES:
+            T.pick_case(orc, cfg, g, mode, norm=True, keeps=T.rows_keeps(g))
 
 
 def test_the_wide_shapes_have_a_seed_too(orc):
-    import test_norm as T
     g = T.wide_graph()
     assert g["row_ptr"][3] == g["row_ptr"][4]
     for _, heads, outdims in T.WIDE:
-        T.pick_params(orc, orc.Config(heads, outdims, g["f"], g["c"]), g, T.MODES[1])
+        T.pick_case(orc, orc.Config(heads, outdims, g["f"], g["c"]), g, T.NORM_MODES[1], norm=True)

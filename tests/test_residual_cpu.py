@@ -1,5 +1,5 @@
 """Residual connections and per-layer bias without a GPU (include/gatv2_abi.h "residual"): the new ABI symbols, the fp64
-model of tests/residual_ref.py against the model without the feature and against finite differences, the share of Xavier
+model of tests/step_ref.py against the model without the feature and against finite differences, the share of Xavier
 seeds the GPU tests may skip for the LeakyReLU kink, and the train_edge flags."""
 import ctypes
 import os
@@ -8,20 +8,13 @@ import subprocess
 import numpy as np
 import pytest
 
-import residual_ref as RR
+import feature_cases as T
+import step_ref as RR
 import torch_ref
-from conftest import small_graph
+from feature_cases import host_graph as _graph
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "graph-attention-network-gatv2-_amd", "train_edge")
-
-
-def _graph(seed, n=40, e=300, F=6, C=3):
-    rng = np.random.default_rng(seed)
-    rp, ci = small_graph(rng, n, e, hub=(7, 40), empty=(3,))
-    x = rng.standard_normal((n, F)).astype(np.float32)
-    lab = rng.integers(0, C, n).astype(np.int32)
-    return dict(row_ptr=rp, col_idx=ci, x=x, labels=lab, n=n, f=F, c=C)
 
 
 def test_symbols_declared_and_exported(pkg):
@@ -42,7 +35,7 @@ def test_zero_residual_is_the_model_without_it(orc):
     g = _graph(1)
     cfg = orc.Config([4, 2], [4, 8], g["f"], g["c"])
     P = orc.xavier_params(cfg, 3)
-    wo, bo = RR.offsets(cfg)
+    wo, bo = RR.res_offsets(cfg)
     want = torch_ref.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P)
     for Wres, b in ((None, None), (np.zeros(wo[-1]), np.zeros(bo[-1])), (np.zeros(wo[-1]), None), (None, np.zeros(bo[-1]))):
         got = RR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, Wres=Wres, b=b)
@@ -60,7 +53,7 @@ def test_empty_row_is_the_residual_alone(orc):
     cfg = orc.Config([4, 2], [4, 8], g["f"], g["c"])
     P = orc.xavier_params(cfg, 1)
     Wres, b = RR.xavier_wres(cfg, 1)
-    wo, bo = RR.offsets(cfg)
+    wo, bo = RR.res_offsets(cfg)
     ref = RR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, Wres=Wres, b=b)
     assert g["row_ptr"][3] == g["row_ptr"][4]
     want = Wres[:wo[1]].astype(np.float64).reshape(16, g["f"]) @ g["x"][3].astype(np.float64) + b[:bo[1]]
@@ -121,17 +114,17 @@ GPU_SHAPES = [
                          ids=[f"{'x'.join(map(str, h))}_{'x'.join(map(str, d))}{'_bf16' if b else ''}" for h, d, b in GPU_SHAPES])
 def test_some_of_the_first_40_seeds_is_clear_of_the_kink(orc, heads, outdims, bf16):
     """The GPU tests pick the first Xavier seed with min |s| and min |h_pre| above 1e-5; the reference alone must offer one among
-    the first 40, for every mode (linear, bias, both), plain and with the three regularisers on (pick_params raises otherwise)."""
-    import test_residual as T
+    the first 40, for every mode (linear, bias, both), plain and with the three regularisers on (pick_case of tests/feature_cases.py
+    raises otherwise)."""
     g = T.parity_graph()
     assert int(g["row_ptr"][8] - g["row_ptr"][7]) == 300 and g["row_ptr"][3] == g["row_ptr"][4]
     cfg = orc.Config(heads, outdims, g["f"], g["c"])
-    modes = T.MODES if len(heads) == 2 else T.MODES[2:]
+    modes = T.RES_MODES if len(heads) == 2 else T.RES_MODES[2:]
     for mode in modes:
         for reg in (None, T.REG):
-            T.pick_params(orc, cfg, g, mode, reg, bf16=bf16)
+            T.pick_case(orc, cfg, g, mode, reg=reg, bf16_pl=bf16)
     if heads == [8, 8] and not bf16:
-        T.pick_params(orc, cfg, g, T.MODES[2], flat=True)
+        T.pick_case(orc, cfg, g, T.RES_MODES[2], flat_lrelu_index=True)
 
 
 def test_train_edge_help_lists_the_flags():
