@@ -177,15 +177,9 @@ struct gat_ctx {
     int32_t gh_stride = 0;                          // D_last, or 16: 64-B records {gH row | the row's LReLU'(h_pre) decision bytes at +32}
     bool y_valid = false;                           // c->y holds the last forward's probabilities (not after a fused head step)
     int32_t* csc_pos = nullptr;                     // [E] slot of each CSR edge in source-major order
-    int32_t* csc_ptr = nullptr;                     // [n_table+1]
-    int4* gpl_chunks = nullptr; int4* gpl_heavy = nullptr; float* gpl_part = nullptr;   // long source lists (HeavyList)
-    int4* pull_items = nullptr; int64_t n_pull_items = 0;                               // length-sorted source items of the pull pass
-    int32_t n_gpl_chunks = 0, n_gpl_heavy = 0;
+    gat::SourceIndex src_index;                     // everything else the source-major pass walks (src_ptr null = not built)
     float* msg = nullptr; int32_t msg_hd = 0;       // [E][msg_hd] per-edge message rows (store path)
     uint32_t* stash = nullptr; int32_t stash_words = 0;   // [E][stash_words] per-edge records (stash path: Layer::stash)
-    int32_t* csc_dst = nullptr;                     // [E] destination row of every slot (stash path)
-    int32_t* csc_src = nullptr;                     // [E + pad] table row of every slot (slot-parallel source-major pass)
-    gat::SlotRuns runs;                             // its device-side index (csrc null = not built)
     float* gfull = nullptr;                         // [n_rows][HDmax] dL/dh_pre incl. LReLU' (stash path: gathered by the pull pass)
     uint8_t* hbits = nullptr;                       // [n_rows][HD_last/N] LReLU'(h_pre) decisions of the last layer (EdgeBwdArgs::hbits)
     int32_t dbg = 0;                                // GAT_DBG timing experiments (0 = product behaviour)
@@ -458,6 +452,7 @@ static int ensure_buffers(gat_ctx* c) {
     const char* force = choice_env("GAT_BWD_ATOMICS");
     if ((msg_hd > 0 || stash_words > 0) && E > 0 && !(force && force[0] == '1')) {
         float* m = nullptr;
+        int32_t *src_ptr = nullptr, *cdst = nullptr, *csrc = nullptr;      // the SourceIndex's arrays while they are written
         // E + 1 rows / records: the last one takes the stores of the group-per-row kernels' padded lanes; kPullPad records of
         // padding behind the records and the destination list: the pull pass reads whole 16-slot chunks without clamping
         if (hipMalloc((void**)&m, std::max<size_t>((size_t)(E + kPullPad) * msg_hd * (size_t)st_bytes(c), (size_t)(E + kPullPad) * stash_words * sizeof(uint32_t))) == hipSuccess) {
@@ -468,47 +463,52 @@ static int ensure_buffers(gat_ctx* c) {
                 if (msg_hd == 0) { c->msg = m; c->msg_hd = 0; }
                 GAT_TRY(dalloc(c, &c->gfull, N * c->HDmax));
                 if (c->layers[L - 1].stash && c->gH != nullptr && c->gh_stride == 16) c->hbits = reinterpret_cast<uint8_t*>(c->gH) + 32;
-                GAT_TRY(dalloc(c, &c->csc_dst, E + kPullPad));
-                GAT_HIP(hipMemsetAsync(c->csc_dst + E, 0, (size_t)kPullPad * sizeof(int32_t), c->stream));      // padding: row 0 (any valid row)
+                GAT_TRY(dalloc(c, &cdst, E + kPullPad));
+                GAT_HIP(hipMemsetAsync(cdst + E, 0, (size_t)kPullPad * sizeof(int32_t), c->stream));      // padding: row 0 (any valid row)
                 GAT_HIP(hipMemsetAsync(reinterpret_cast<uint32_t*>(m) + (size_t)E * stash_words, 0, (size_t)kPullPad * stash_words * sizeof(uint32_t), c->stream));
             }
             GAT_TRY(dalloc(c, &c->csc_pos, E));
-            GAT_TRY(dalloc(c, &c->csc_ptr, T + 1));
+            GAT_TRY(dalloc(c, &src_ptr, T + 1));
             // slot-parallel source-major pass (gat_csc.hip "runs"): the source of every slot + the lists crossing a run boundary.
             // GAT_PULL_RUN=<slots per run> (a multiple of 32; 0 = do not build)
             static const int run_env = [] { const char* e = choice_env("GAT_PULL_RUN"); return e ? atoi(e) : -1; }();
             const int32_t run = run_env >= 0 ? (run_env / 32) * 32 : 64;
-            if (run > 0) GAT_TRY(dalloc(c, &c->csc_src, E + kPullPad));
-            GAT_TRY(build_csc(c->col_idx, E, T, c->csc_pos, c->csc_ptr, c->csc_src, c->stream));
-            if (c->csc_dst) GAT_TRY(build_csc_dst(c->row_ptr, c->csc_pos, c->csc_dst, N, E, c->stream));
+            if (run > 0) GAT_TRY(dalloc(c, &csrc, E + kPullPad));
+            GAT_TRY(build_csc(c->col_idx, E, T, c->csc_pos, src_ptr, csrc, c->stream));
+            if (cdst) GAT_TRY(build_csc_dst(c->row_ptr, c->csc_pos, cdst, N, E, c->stream));
+            SourceIndex& ix = c->src_index;
+            ix.src_ptr = src_ptr; ix.cdst = cdst; ix.n_table = T; ix.n_slots = E; ix.slot_capacity = E + kPullPad;
             HeavyList hl;
-            GAT_TRY(build_heavy_list(c->csc_ptr, T, E, &hl, c->stream, run));
-            if (hl.run > 0 && c->csc_src != nullptr) {
-                SlotRuns& R = c->runs;
-                R.run = hl.run; R.n_runs = hl.n_runs; R.n_open = (int32_t)(hl.open.size() / 4); R.n_empty = (int64_t)hl.empty.size();
+            GAT_TRY(build_heavy_list(src_ptr, T, E, &hl, c->stream, run));
+            // device copy of one of the host lists (int4 entries as 4 int32), at least one entry allocated
+            auto upload = [&](auto** d, const std::vector<int32_t>& h, int per) -> int {
+                GAT_TRY(dalloc(c, d, std::max<int64_t>((int64_t)(h.size() / per), 1)));
+                if (!h.empty()) GAT_HIP(hipMemcpyAsync(*d, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+                return 0;
+            };
+            if (hl.run > 0 && csrc != nullptr) {
+                ix.run = hl.run; ix.n_runs = hl.n_runs; ix.n_open = (int32_t)(hl.open.size() / 4); ix.n_empty = (int64_t)hl.empty.size();
                 int4* d_open = nullptr; int32_t* d_empty = nullptr;
-                GAT_TRY(dalloc(c, &d_open, std::max<int64_t>(R.n_open, 1)));
-                GAT_TRY(dalloc(c, &d_empty, std::max<int64_t>(R.n_empty, 1)));
-                GAT_TRY(dalloc(c, &R.part, std::max<int64_t>(2 * R.n_runs, 1) * c->HDmax));
-                if (R.n_open > 0) GAT_HIP(hipMemcpyAsync(d_open, hl.open.data(), hl.open.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-                if (R.n_empty > 0) GAT_HIP(hipMemcpyAsync(d_empty, hl.empty.data(), hl.empty.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+                GAT_TRY(upload(&d_open, hl.open, 4));
+                GAT_TRY(upload(&d_empty, hl.empty, 1));
+                GAT_TRY(dalloc(c, &ix.run_part, std::max<int64_t>(2 * ix.n_runs, 1) * c->HDmax));
                 GAT_HIP(hipStreamSynchronize(c->stream));
-                R.open = d_open; R.empty = d_empty; R.csrc = c->csc_src;
+                ix.open = d_open; ix.empty = d_empty; ix.csrc = csrc;
             }
-            c->n_gpl_chunks = (int32_t)(hl.chunks.size() / 4); c->n_gpl_heavy = (int32_t)(hl.heavy.size() / 4);
+            ix.n_chunks = (int32_t)(hl.chunks.size() / 4); ix.n_heavy = (int32_t)(hl.heavy.size() / 4);
             if (c->stash != nullptr && !hl.items.empty()) {
-                c->n_pull_items = (int64_t)(hl.items.size() / 4);
-                GAT_TRY(dalloc(c, &c->pull_items, c->n_pull_items));
-                GAT_HIP(hipMemcpyAsync(c->pull_items, hl.items.data(), hl.items.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+                int4* d_items = nullptr;
+                GAT_TRY(upload(&d_items, hl.items, 4));
                 GAT_HIP(hipStreamSynchronize(c->stream));
+                ix.items = d_items; ix.n_items = (int64_t)(hl.items.size() / 4);
             }
-            if (c->n_gpl_heavy > 0) {
-                GAT_TRY(dalloc(c, &c->gpl_chunks, c->n_gpl_chunks));
-                GAT_TRY(dalloc(c, &c->gpl_heavy, c->n_gpl_heavy));
-                GAT_TRY(dalloc(c, &c->gpl_part, (int64_t)c->n_gpl_chunks * c->HDmax));
-                GAT_HIP(hipMemcpyAsync(c->gpl_chunks, hl.chunks.data(), hl.chunks.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-                GAT_HIP(hipMemcpyAsync(c->gpl_heavy, hl.heavy.data(), hl.heavy.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            if (ix.n_heavy > 0) {
+                int4* d_chunks = nullptr; int4* d_heavy = nullptr;
+                GAT_TRY(upload(&d_chunks, hl.chunks, 4));
+                GAT_TRY(upload(&d_heavy, hl.heavy, 4));
+                GAT_TRY(dalloc(c, &ix.part, (int64_t)ix.n_chunks * c->HDmax));
                 GAT_HIP(hipStreamSynchronize(c->stream));
+                ix.chunks = d_chunks; ix.heavy = d_heavy;
             }
         } else {
             (void)hipGetLastError();      // not enough HBM for the scratch: atomics variant
@@ -1116,7 +1116,7 @@ static int plan_backward_edges(gat_ctx* c, int32_t l, BwdPlan* P) {
     static const int pull_last = [] { const char* e = choice_env("GAT_PULL_LAST"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
     // With the slot-parallel pull pass (short lists: shards) the records pay from 64 MB of g rows on: one cache line per slot instead
     // of two, and that pass is bound by lines per second (Products P = 8 shard, 78 MB: 0.84 -> 0.78 ms per step; Arxiv 43 MB: equal)
-    const bool runs_form = c->runs.csrc != nullptr && c->n_edges < 8 * c->n_table && c->n_edges >= ((int64_t)512 << 10);
+    const bool runs_form = c->src_index.csrc != nullptr && short_lists_take_runs(c->n_edges, c->n_table);
     const bool big_rows = (int64_t)c->n_rows * y.H * y.D * 4 > ((int64_t)(runs_form ? 64 : 128) << 20);
     const bool last_g = stash && a.gh != nullptr && c->hbits != nullptr && !bf16(c) && (pull_last >= 0 ? pull_last == 1 : big_rows) &&
                         c->n_rows < ((int64_t)1 << 26);             // the pull pass addresses the 64-byte node records with 32-bit offsets
@@ -1134,19 +1134,14 @@ static int plan_backward_edges(gat_ctx* c, int32_t l, BwdPlan* P) {
 // The source-major pass of layer l (records -> gPL, or message rows -> gPL)
 static int sum_backward_edges(gat_ctx* c, int32_t l, const BwdPlan& P) {
     Layer& y = c->layers[l];
+    if (!P.stash && !P.store) return 0;
+    Scope t(c, GAT_K_GPL_SUM);
     if (P.stash) {
-        Scope t(c, GAT_K_GPL_SUM);
-        return launch_gpl_pull(c->csc_ptr, c->stash, c->csc_dst, c->gfull, bf16(c), P.last_g ? c->gH : nullptr, P.last_g ? c->hbits : nullptr, c->gh_stride, 64,
-                               a_of(c, l), c->cfg.negative_slope, gPL_of(c, l), c->n_table,
-                               c->n_edges, y.H, y.D, c->gpl_chunks, c->n_gpl_chunks, c->gpl_heavy, c->n_gpl_heavy, c->gpl_part,
-                               c->pull_items, c->n_pull_items, c->runs.csrc ? &c->runs : nullptr, c->n_edges + kPullPad, c->stream);
+        const PullArgs p{c->stash, c->gfull, bf16(c), P.last_g ? c->gH : nullptr, P.last_g ? c->hbits : nullptr, c->gh_stride, 64,
+                         a_of(c, l), c->cfg.negative_slope, gPL_of(c, l), y.H, y.D};
+        return launch_gpl_pull(c->src_index, p, c->stream);
     }
-    if (P.store) {
-        Scope t(c, GAT_K_GPL_SUM);
-        return launch_gpl_sum(c->csc_ptr, c->msg, gPL_of(c, l), c->n_table, c->n_edges, y.HD, bf16(c), c->gpl_chunks, c->n_gpl_chunks,
-                              c->gpl_heavy, c->n_gpl_heavy, c->gpl_part, c->stream, c->runs.csrc ? &c->runs : nullptr);
-    }
-    return 0;
+    return launch_gpl_sum(c->src_index, c->msg, bf16(c), gPL_of(c, l), y.HD, c->stream);
 }
 // Residual layer, before its edge backward: G = dL/dh_pre and agg = h_pre - (R + b) into the context's two N-sized buffers, the
 // block column sums of G into the layer's region, and their fixed-order reduction into grad_b (queued in a ReduceBatch)

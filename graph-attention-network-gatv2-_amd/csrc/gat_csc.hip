@@ -10,11 +10,13 @@
 //   pos[e]      = slot of CSR edge e in (src, e)-sorted order   (stable radix sort: fixed order
 //                 inside every source's list => bitwise reproducible sums)
 //   src_ptr[s]  = first slot of table row s, src_ptr[n_table] = E
-//   csc_src[j]  = table row of slot j (the sorted keys), csc_dst[j] = destination row of slot j
+//   csrc[j]     = table row of slot j (the sorted keys), cdst[j] = destination row of slot j
+// (the device-side index as a whole: SourceIndex, gat_internal.h)
 // Two families of second-pass kernels: LIST kernels (a source's slot list per wave or lane group: gpl_pull_kernel, gpl_pull3_kernel,
 // gpl_sum_*; long lists chunked) for graphs with ~25 slots per list, and the SLOT-PARALLEL form (runs of consecutive slots per
-// lane group, segmented by csc_src: gpl_pull_runs_kernel, gpl_sum_runs_kernel) where lists are short — destination-range shards
-// and sparse graphs (round 4).  run_pull / launch_gpl_sum hold the selection rules and the measurements behind them.
+// lane group, segmented by csrc: gpl_pull_runs_kernel, gpl_sum_runs_kernel) where lists are short — destination-range shards
+// and sparse graphs (round 4).  pick_pull / pick_sum hold the selection rules and the measurements behind them (the short-list rule
+// itself: short_lists_take_runs, gat_internal.h); launch_gpl_pull / launch_gpl_sum run what they pick.
 #include "gat_internal.h"
 
 #include <hipcub/hipcub.hpp>
@@ -715,7 +717,7 @@ __global__ __launch_bounds__(256) void gpl_pull3_kernel(const int4* __restrict__
 // as (number of lists) x (latency) / (waves in flight), whatever it moves.  Here the FLAT slot stream is cut into runs of
 // `run` consecutive slots, one run per lane group (64/(HD/N) runs side by side per wave), whatever sources they belong
 // to:
-//   * no per-list descriptor: the group streams csc_src[slot] (4 B per slot) beside the records and destinations;
+//   * no per-list descriptor: the group streams csrc[slot] (4 B per slot) beside the records and destinations;
 //     a slot whose successor has another source ends a segment;
 //   * a segment that lies inside its run is stored straight to gPL[source]; a run's first segment when it began in
 //     an earlier run goes to partial row 2r, its last segment when it continues goes to partial row 2r + 1 (a run
@@ -735,9 +737,6 @@ __device__ __forceinline__ int group_bcast(int v, int gidx) {       // lane U of
     else return __shfl(v, gidx * LPE + U);
 }
 
-// below this many slots the runs cannot fill the chip (Pubmed shape: 44 k slots = 173 waves; 0.244 -> 0.268 ms per step with
-// runs, Cora shape 0.190 -> 0.216) and the list-per-wave kernels stay; Arxiv shape (1.17 M slots): 0.256 -> 0.195 ms per step
-constexpr int64_t kRunsMinSlots = 512 << 10;
 struct RunsDev {
     const int32_t* csrc;       // [n_slots + kPullPad] table row of every slot; -1 behind the last
     const int32_t* empty;      // [n_empty] table rows without slots
@@ -991,56 +990,99 @@ int build_csc_dst(const int32_t* row_ptr, const int32_t* pos, int32_t* cdst, int
     return 0;
 }
 
+// ---- host side: which kernel runs -----------------------------------------------------------------------------------
+// One reader per switch, read where the value is first used (gat_switches() reports what a run consulted).
+// GAT_PULL_RUNS=0|1: the slot-parallel form forced off / on, in both passes (-1: not set)
+static int pull_runs_env() {
+    static const int v = [] { const char* e = choice_env("GAT_PULL_RUNS"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
+    return v;
+}
+// GAT_PULL_GROUPS=1: the group-per-source kernel of the pull pass, set to anything else: not (-1: not set)
+static int pull_groups_env() {
+    static const int v = [] { const char* e = choice_env("GAT_PULL_GROUPS"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
+    return v;
+}
+// GAT_PULL_U=4|16, experiment: slots per batch of the slot-parallel pull kernel with 16-lane groups (anything else: its default)
+static int pull_u_env() {
+    static const int v = [] { const char* e = choice_env("GAT_PULL_U"); return e ? atoi(e) : 0; }();
+    return v;
+}
+// GAT_PULL_V2=0|1|2: one form of the slot walk on every layer, see pick_pull (negative: not set)
+static int pull_v2_env() {
+    static const int v = [] { const char* e = choice_env("GAT_PULL_V2"); return e ? atoi(e) : -1; }();
+    return v;
+}
+// GAT_GPL_WAVES=1|2|4: waves per block of the wave-per-list kernels, A/B (0: not set, or none of these — each pass has its own default)
+static int gpl_waves_env() {
+    static const int v = [] { const char* e = choice_env("GAT_GPL_WAVES"); const int w = e ? atoi(e) : 0; return (w == 1 || w == 2 || w == 4) ? w : 0; }();
+    return v;
+}
+// GAT_GPL_GROUP, A/B of the fp32 message-row sum: 1 = group per source, anything else = wave per source (-1: not set)
+static int gpl_group_env() {
+    static const int v = [] { const char* e = choice_env("GAT_GPL_GROUP"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
+    return v;
+}
+// GAT_GPL_BF16_GROUP=0, A/B of the bf16 message-row sum: wave per source instead of group per source (-1: not set)
+static int gpl_bf16_group_env() {
+    static const int v = [] { const char* e = choice_env("GAT_GPL_BF16_GROUP"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
+    return v;
+}
+
+namespace {
+// The kernel of one source-major pass and what its launch needs.  pick_pull / pick_sum below are the only places that name an
+// instantiation of the gpl_* template kernels; run_pick() runs what they return.
+struct GplPick {
+    enum Form { kLists, kItems, kRuns };
+    const void* fn = nullptr;       // null: no kernel for this shape
+    Form form = kLists;             // kLists: a list per wave or lane group, from src_ptr; kItems: from the item list; kRuns: slot-parallel
+    const void* chunk_fn = nullptr; // kLists: the kernel of the long lists' chunks (kItems: the item list carries the chunks)
+    unsigned grid = 0, block = 256;
+    RunsDev rd{};                   // kRuns
+};
+#define GAT_K(...) ((const void*)(__VA_ARGS__))
+
+// the slot-parallel form of either pass: G runs side by side per wave
+static GplPick pick_runs(const SourceIndex& ix, const void* fn, int G) {
+    GplPick p{fn, GplPick::kRuns};
+    RunsDev& rd = p.rd;
+    rd.csrc = ix.csrc; rd.empty = ix.empty; rd.part = ix.run_part; rd.n_empty = ix.n_empty; rd.n_slots = ix.n_slots; rd.n_table = ix.n_table;
+    rd.run = ix.run; rd.zero_blocks = (int32_t)((ix.n_empty + 4 * G * 8 - 1) / (4 * G * 8));
+    const int64_t waves = (ix.n_runs + G - 1) / G;
+    p.grid = (unsigned)(rd.zero_blocks + (waves + 3) / 4);
+    return p;
+}
+
+// Pull pass (records -> gPL).  padded: the record buffer and the destination list carry kPullPad slots behind the last.
 template <int HD, int N, bool BF, int LASTD>
-static int run_pull(const int32_t* src_ptr, const uint32_t* stash, const int32_t* cdst, const float* gfull, const uint8_t* hbits,
-                    int gh_stride, int hb_stride, const float* a, float slope, float* gPL, int64_t n_table, const int4* chunks, int32_t n_chunks, const int4* heavy,
-                    int32_t n_heavy, float* part, int wpb, int64_t n_slots, const int4* items, int64_t n_items, const SlotRuns* runs, bool padded, hipStream_t s) {
+GplPick pick_pull(const SourceIndex& ix, const PullArgs& A, bool padded) {
+    constexpr int LPE = HD / N, G = 64 / LPE;
+    // one wave per block for the pull kernel (GAT_GPL_WAVES=1|2|4): 5.03 / 5.11 / 5.30 ms per step on the Products shape — a
+    // 4-wave block lives as long as its longest list; the message-row sum (pick_sum) measured the other way round
+    const int wpb = gpl_waves_env() ? gpl_waves_env() : 1;
     // Slot-parallel form (gpl_pull_runs_kernel): default where the lists are short (a destination-range shard: the list-per-group
     // kernel below pays three dependent latencies per ~4 slots); GAT_PULL_RUNS=0|1 forces.  The last layer's variant reads the
     // 64-byte node records (gh_stride 16, decision bytes at +32).
-    static const int runs_env = [] { const char* e = choice_env("GAT_PULL_RUNS"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
-    static const int groups_env = [] { const char* e = choice_env("GAT_PULL_GROUPS"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
-    const bool runs_ok = runs != nullptr && runs->csrc != nullptr && runs->run % (HD / N) == 0 && (LASTD == 0 || (gh_stride == 16 && hb_stride == 64));
-    if (runs_ok && (runs_env >= 0 ? runs_env == 1 : (groups_env < 0 && n_slots < 8 * n_table && n_slots >= kRunsMinSlots))) {     // an explicit GAT_PULL_GROUPS selects among the list kernels
-        constexpr int G = 64 / (HD / N), U = (HD / N) % 8 == 0 ? 8 : 4;
-        RunsDev rd{};
-        rd.csrc = runs->csrc; rd.empty = runs->empty; rd.part = runs->part; rd.n_empty = runs->n_empty; rd.n_slots = n_slots; rd.n_table = n_table;
-        rd.run = runs->run; rd.zero_blocks = (int32_t)((runs->n_empty + 4 * G * 8 - 1) / (4 * G * 8));
-        const int64_t waves = (runs->n_runs + G - 1) / G, blocks = rd.zero_blocks + (waves + 3) / 4;
-        static const int u_env = [] { const char* e = choice_env("GAT_PULL_U"); return e ? atoi(e) : 0; }();      // experiment: slots per batch (16-lane groups)
-        if (blocks > 0) {
-            if constexpr (HD / N == 16 && !BF) {
-                if (u_env == 4) hipLaunchKernelGGL((gpl_pull_runs_kernel<HD, N, BF, LASTD, 4>), dim3((unsigned)blocks), dim3(256), 0, s, stash, cdst, gfull, hbits, a, slope, gPL, rd);
-                else if (u_env == 16) hipLaunchKernelGGL((gpl_pull_runs_kernel<HD, N, BF, LASTD, 16>), dim3((unsigned)blocks), dim3(256), 0, s, stash, cdst, gfull, hbits, a, slope, gPL, rd);
-                else hipLaunchKernelGGL((gpl_pull_runs_kernel<HD, N, BF, LASTD, U>), dim3((unsigned)blocks), dim3(256), 0, s, stash, cdst, gfull, hbits, a, slope, gPL, rd);
-            } else {
-                hipLaunchKernelGGL((gpl_pull_runs_kernel<HD, N, BF, LASTD, U>), dim3((unsigned)blocks), dim3(256), 0, s, stash, cdst, gfull, hbits, a, slope, gPL, rd);
-            }
+    const int runs_env = pull_runs_env(), groups_env = pull_groups_env();
+    const bool records64 = LASTD == 0 || (A.gh_stride == 16 && A.hb_stride == 64);
+    const bool runs_ok = padded && ix.csrc != nullptr && ix.run % LPE == 0 && records64;
+    if (runs_ok && (runs_env >= 0 ? runs_env == 1 : (groups_env < 0 && short_lists_take_runs(ix.n_slots, ix.n_table)))) {     // an explicit GAT_PULL_GROUPS selects among the list kernels
+        constexpr int U = LPE % 8 == 0 ? 8 : 4;
+        const int u_env = pull_u_env();
+        if constexpr (LPE == 16 && !BF) {
+            if (u_env == 4) return pick_runs(ix, GAT_K(gpl_pull_runs_kernel<HD, N, BF, LASTD, 4>), G);
+            if (u_env == 16) return pick_runs(ix, GAT_K(gpl_pull_runs_kernel<HD, N, BF, LASTD, 16>), G);
         }
-        if (runs->n_open > 0) {
-            const int64_t threads = (int64_t)runs->n_open * (HD / 4);
-            hipLaunchKernelGGL(gpl_runs_fix_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, runs->open, runs->n_open, runs->part, gPL, HD / 4);
-        }
-        GAT_HIP(hipGetLastError());
-        return 0;
+        return pick_runs(ix, GAT_K(gpl_pull_runs_kernel<HD, N, BF, LASTD, U>), G);
     }
     // GAT_PULL_GROUPS=1: the group-per-source kernel.  Measured SLOWER on the Products shape (5.8 vs 5.36 ms per step), as was
     // everything else that shortened this pass's dependency chains or shrank its gathers: see DESIGN §4 (random-row rate)
     // default: groups only where the lists are short (a destination-range shard sees ~deg/P slots per source: one wave
     // per 3-slot list wastes 15 of its 16 gather slots) — the same rule the message-row sum used (n_slots < 8 n_table)
     // ... and only with enough lists to give every resident wave several (Pubmed shape, 19,717 lists: one wave per list 0.27 vs 0.30 ms per step)
-    const bool groups = groups_env >= 0 ? groups_env == 1 : (n_slots < 8 * n_table && n_items >= 32768);
-    if (items != nullptr && groups) {
-        constexpr int G = 64 / (HD / N);
-        const int64_t quads = (n_items + G - 1) / G;
-        hipLaunchKernelGGL((gpl_pull3_kernel<HD, N, BF, LASTD>), dim3((unsigned)((quads + 3) / 4)), dim3(256), 0, s, items, n_items, stash, cdst,
-                           gfull, hbits, gh_stride, hb_stride, a, slope, gPL, part);
-        if (n_heavy > 0) {
-            const int64_t threads = (int64_t)n_heavy * HD;
-            hipLaunchKernelGGL(gpl_heavy_fix_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, heavy, n_heavy, part, gPL, HD);
-        }
-        GAT_HIP(hipGetLastError());
-        return 0;
+    const bool groups = groups_env >= 0 ? groups_env == 1 : (ix.n_slots < 8 * ix.n_table && ix.n_items >= 32768);
+    if (ix.items != nullptr && groups) {
+        const int64_t quads = (ix.n_items + G - 1) / G;
+        return {GAT_K(gpl_pull3_kernel<HD, N, BF, LASTD>), GplPick::kItems, nullptr, (unsigned)((quads + 3) / 4)};
     }
     // second form of the slot walk (pull_range2): fp32 tables; the last-layer variant needs the 64-byte node records.
     // GAT_PULL_V2 = 0 first form | 1 second form, multipliers from LDS tables | 2 second form, multipliers by bit selects (A/B)
@@ -1050,64 +1092,112 @@ static int run_pull(const int32_t* src_ptr, const uint32_t* stash, const int32_t
     // busy) and gains from the shorter instruction stream; the hidden layer's is bound by its two-line gathers and loses to the
     // second form's unclamped chunk reads (+8 % record lines).  Default: second form for the last layer only; GAT_PULL_V2 forces
     // one form on both (0 | 1 | 2).
-    static const int v2_env = [] { const char* e = choice_env("GAT_PULL_V2"); return e ? atoi(e) : -1; }();
+    const int v2_env = pull_v2_env();
     const int v2_want = v2_env >= 0 ? v2_env : (LASTD > 0 ? 2 : 0);
-    const int v2 = (padded && !BF && (LASTD == 0 || (gh_stride == 16 && hb_stride == 64))) ? v2_want : 0;
-    const dim3 cgrid((unsigned)((n_chunks + 3) / 4)), pgrid((unsigned)((n_table + wpb - 1) / wpb)), pblock(64 * wpb);
-#define GAT_PULL_LAUNCH(V2_)                                                                                                          \
-    do {                                                                                                                              \
-        if (n_heavy > 0) {                             /* long lists first: they are the longest-running waves */                      \
-            hipLaunchKernelGGL((gpl_pull_chunk_kernel<HD, N, BF, LASTD, V2_>), cgrid, dim3(256), 0, s, chunks, n_chunks, stash, cdst, gfull, hbits, \
-                               gh_stride, hb_stride, a, slope, part);                                                                  \
-            const int64_t threads = (int64_t)n_heavy * HD;                                                                              \
-            hipLaunchKernelGGL(gpl_heavy_fix_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, heavy, n_heavy, part, gPL, HD); \
-        }                                                                                                                             \
-        hipLaunchKernelGGL((gpl_pull_kernel<HD, N, BF, LASTD, V2_>), pgrid, pblock, 0, s, src_ptr, stash, cdst, gfull, hbits, gh_stride, hb_stride, \
-                           a, slope, gPL, n_table, heavy_slots(n_slots));                                                              \
-    } while (0)
+    const int v2 = (padded && !BF && records64) ? v2_want : 0;
+    const unsigned grid = (unsigned)((ix.n_table + wpb - 1) / wpb), block = 64u * wpb;
     if constexpr (!BF) {
-        if (v2 == 1) GAT_PULL_LAUNCH(1);
-        else if (v2 == 2) GAT_PULL_LAUNCH(2);
-        else GAT_PULL_LAUNCH(0);
-    } else {
-        GAT_PULL_LAUNCH(0);
+        if (v2 == 1) return {GAT_K(gpl_pull_kernel<HD, N, BF, LASTD, 1>), GplPick::kLists, GAT_K(gpl_pull_chunk_kernel<HD, N, BF, LASTD, 1>), grid, block};
+        if (v2 == 2) return {GAT_K(gpl_pull_kernel<HD, N, BF, LASTD, 2>), GplPick::kLists, GAT_K(gpl_pull_chunk_kernel<HD, N, BF, LASTD, 2>), grid, block};
     }
-#undef GAT_PULL_LAUNCH
+    return {GAT_K(gpl_pull_kernel<HD, N, BF, LASTD, 0>), GplPick::kLists, GAT_K(gpl_pull_chunk_kernel<HD, N, BF, LASTD, 0>), grid, block};
+}
+
+// Sum pass (message rows -> gPL).
+template <int HD>
+GplPick pick_sum(const SourceIndex& ix, bool bf) {
+    // slot-parallel form (gpl_sum_runs_kernel): the default on short lists (a destination-range shard) of fp32 rows; GAT_PULL_RUNS=0|1
+    // forces.  Not for bf16 rows: a 64-byte row is FOUR lanes, and a segment end is a store instruction of its own per group (two
+    // half-line requests per 128-byte gPL row), where the list kernel's 16 groups store 16 consecutive rows with one instruction —
+    // BASELINE config 5's P = 8 shard measured 1.49-1.54 ms per step against 1.31 (profiles/r04/experiments)
+    const int runs_env = pull_runs_env();
+    const bool group_env = gpl_group_env() >= 0 || gpl_bf16_group_env() >= 0;
+    if (ix.csrc != nullptr && ix.run % 16 == 0 &&
+        (runs_env >= 0 ? runs_env == 1 : (!group_env && !bf && short_lists_take_runs(ix.n_slots, ix.n_table))))
+        return pick_runs(ix, bf ? GAT_K(gpl_sum_runs_kernel<HD, true>) : GAT_K(gpl_sum_runs_kernel<HD, false>), 64 / (HD / (bf ? 8 : 4)));
+    // waves per block of the per-source kernels (GAT_GPL_WAVES, A/B): unlike the edge forward, 4 beats 1 here
+    // (6.15 vs 6.31 ms per step on one box)
+    const int wpb = gpl_waves_env() ? gpl_waves_env() : 4;
+    const unsigned wgrid = (unsigned)((ix.n_table + wpb - 1) / wpb), wblock = 64u * wpb;
+    const int rpi = 64 / (HD / (bf ? 8 : 4));                            // sources per wave of the group kernels
+    const unsigned ggrid = (unsigned)((ix.n_table + 4 * rpi - 1) / (4 * rpi));
+    if (bf) {
+        const void* chunk = GAT_K(gpl_chunk_kernel<HD, true>);
+        // group per source unless GAT_GPL_BF16_GROUP=0 (A/B): 10 M / 250 M shape, H*D = 32
+        if (gpl_bf16_group_env() != 0) return {GAT_K(gpl_sum_bf16_group_kernel<HD>), GplPick::kLists, chunk, ggrid};
+        return {GAT_K(gpl_sum_bf16_kernel<HD>), GplPick::kLists, chunk, wgrid, wblock};
+    }
+    const void* chunk = GAT_K(gpl_chunk_kernel<HD, false>);
+    const int force = gpl_group_env();                               // A/B switch: 0 = wave per source, 1 = group per source
+    const bool group = force >= 0 ? force == 1 : ix.n_slots < 8 * ix.n_table;   // measured: 3.2 slots/source 1.24 -> 1.00 ms, 12.6: 3.20 -> 3.31
+    if (group) return {GAT_K(gpl_sum_group_kernel<HD>), GplPick::kLists, chunk, ggrid};
+    return {GAT_K(gpl_sum_kernel<HD>), GplPick::kLists, chunk, wgrid, wblock};
+}
+
+}  // namespace
+
+// The templates' entries.  Pull: (H*D, channels per lane, D) of the shapes with a record path (edge_stash_words), then the storage
+// and the last layer's node records; sum: H*D of the wave-per-row shapes.  An empty pick: no kernel for this shape.
+static GplPick pick_pull_pass(const SourceIndex& ix, const PullArgs& A, bool last, bool padded) {
+#define GAT_PULL_SHAPE(HD_, N_, D_)                                                                      \
+    case HD_ * 1000 + D_:                                                                                \
+        if (last) return pick_pull<HD_, N_, false, D_>(ix, A, padded);                                   \
+        return A.g_bf16 ? pick_pull<HD_, N_, true, 0>(ix, A, padded) : pick_pull<HD_, N_, false, 0>(ix, A, padded);
+    switch (A.H * A.D * 1000 + A.D) {
+        GAT_PULL_SHAPE(64, 4, 8) GAT_PULL_SHAPE(32, 4, 8) GAT_PULL_SHAPE(64, 2, 4) GAT_PULL_SHAPE(32, 2, 4) GAT_PULL_SHAPE(16, 2, 4) GAT_PULL_SHAPE(8, 2, 4)
+        default: return {};
+    }
+#undef GAT_PULL_SHAPE
+}
+static GplPick pick_sum_pass(const SourceIndex& ix, int32_t HD, bool bf) {
+    switch (HD) {
+        case 64: return pick_sum<64>(ix, bf);
+        case 32: return pick_sum<32>(ix, bf);
+        case 16: return pick_sum<16>(ix, bf);
+        case 8: return pick_sum<8>(ix, bf);
+        default: return {};
+    }
+}
+
+// Runs a pick: `args` the arguments of its kernel, chunk_args those of its chunk kernel.
+static int run_pick(const SourceIndex& ix, const GplPick& p, void** args, void** chunk_args, float* gPL, int32_t HD, hipStream_t s) {
+    const bool heavy = p.form != GplPick::kRuns && ix.n_heavy > 0;       // long lists, cut into chunks: their partial rows are added per source
+    auto heavy_fix = [&] {
+        const int64_t threads = (int64_t)ix.n_heavy * HD;
+        hipLaunchKernelGGL(gpl_heavy_fix_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ix.heavy, ix.n_heavy, ix.part, gPL, HD);
+    };
+    if (heavy && p.chunk_fn != nullptr) {               // long lists first: they are the longest-running waves
+        GAT_HIP(hipLaunchKernel(p.chunk_fn, dim3((unsigned)((ix.n_chunks + 3) / 4)), dim3(256), chunk_args, 0, s));
+        heavy_fix();
+    }
+    if (p.grid > 0) GAT_HIP(hipLaunchKernel(p.fn, dim3(p.grid), dim3(p.block), args, 0, s));
+    if (heavy && p.chunk_fn == nullptr) heavy_fix();    // the chunks ran as items
+    if (p.form == GplPick::kRuns && ix.n_open > 0) {
+        const int64_t threads = (int64_t)ix.n_open * (HD / 4);
+        hipLaunchKernelGGL(gpl_runs_fix_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ix.open, ix.n_open, ix.run_part, gPL, HD / 4);
+    }
     GAT_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_gpl_pull(const int32_t* src_ptr, const uint32_t* stash, const int32_t* cdst, const float* gfull, bool g_bf16,
-                    const float* gh, const uint8_t* hbits, int32_t gh_stride, int32_t hb_stride, const float* a,
-                    float slope, float* gPL, int64_t n_table, int64_t n_slots, int32_t H, int32_t D, const int4* chunks,
-                    int32_t n_chunks, const int4* heavy, int32_t n_heavy, float* part, const int4* items, int64_t n_items, const SlotRuns* runs,
-                    int64_t slot_capacity, hipStream_t s) {
-    if (n_table <= 0) return 0;
+int launch_gpl_pull(const SourceIndex& ix, const PullArgs& A, hipStream_t s) {
+    if (ix.n_table <= 0) return 0;
     // the second form of the slot walk and the slot-parallel form read whole 16-slot chunks without clamping: the record buffer and
     // the destination list must hold kPullPad slots behind the last (gat_internal.h); a caller with exact-size buffers gets the
     // clamped first form on per-list kernels instead of an out-of-bounds read
-    const bool padded = slot_capacity >= n_slots + kPullPad;
-    if (!padded) runs = nullptr;
-    // one wave per block for the pull kernel (GAT_GPL_WAVES=1|2|4): 5.03 / 5.11 / 5.30 ms per step on the Products shape — a
-    // 4-wave block lives as long as its longest list; the message-row sum (launch_gpl_sum) measured the other way round
-    static const int wpb = [] { const char* e = choice_env("GAT_GPL_WAVES"); const int v = e ? atoi(e) : 1; return (v == 1 || v == 2 || v == 4) ? v : 1; }();
-    const int HD = H * D;
-    const bool last = gh != nullptr && hbits != nullptr;
-#define PULL_ARGS(G_) src_ptr, stash, cdst, G_, hbits, gh_stride, hb_stride, a, slope, gPL, n_table, chunks, n_chunks, heavy, n_heavy, part, wpb, n_slots, items, n_items, runs, padded, s
-#define PULL(HD_, N_, D_)                                                                           \
-    {                                                                                               \
-        if (last) return run_pull<HD_, N_, false, D_>(PULL_ARGS(gh));                               \
-        return g_bf16 ? run_pull<HD_, N_, true, 0>(PULL_ARGS(gfull)) : run_pull<HD_, N_, false, 0>(PULL_ARGS(gfull)); \
-    }
-    if (D == 8 && HD == 64) PULL(64, 4, 8)
-    if (D == 8 && HD == 32) PULL(32, 4, 8)
-    if (D == 4 && HD == 64) PULL(64, 2, 4)
-    if (D == 4 && HD == 32) PULL(32, 2, 4)
-    if (D == 4 && HD == 16) PULL(16, 2, 4)
-    if (D == 4 && HD == 8) PULL(8, 2, 4)
-#undef PULL
-#undef PULL_ARGS
-    return fail(GAT_E_UNSUPPORTED, "gpl_pull: no stash path for this (H, D)");
+    const bool padded = ix.slot_capacity >= ix.n_slots + kPullPad;
+    const bool last = A.gh != nullptr && A.hbits != nullptr;
+    GplPick p = pick_pull_pass(ix, A, last, padded);
+    if (p.fn == nullptr) return fail(GAT_E_UNSUPPORTED, "gpl_pull: no stash path for this (H, D)");
+    SourceIndex x = ix;                                 // the kernels' arguments, by address
+    PullArgs q = A;
+    const float* g = last ? A.gh : A.gfull;
+    int32_t hs = heavy_slots(ix.n_slots);
+    void* lists[] = {&x.src_ptr, &q.stash, &x.cdst, &g, &q.hbits, &q.gh_stride, &q.hb_stride, &q.a, &q.slope, &q.gPL, &x.n_table, &hs};
+    void* chunk[] = {&x.chunks, &x.n_chunks, &q.stash, &x.cdst, &g, &q.hbits, &q.gh_stride, &q.hb_stride, &q.a, &q.slope, &x.part};
+    void* items[] = {&x.items, &x.n_items, &q.stash, &x.cdst, &g, &q.hbits, &q.gh_stride, &q.hb_stride, &q.a, &q.slope, &q.gPL, &x.part};
+    void* runs[] = {&q.stash, &x.cdst, &g, &q.hbits, &q.a, &q.slope, &q.gPL, &p.rd};
+    return run_pick(ix, p, p.form == GplPick::kRuns ? runs : p.form == GplPick::kItems ? items : lists, chunk, A.gPL, A.H * A.D, s);
 }
 
 int build_csc(const int32_t* col_idx, int64_t n_edges, int64_t n_table, int32_t* pos, int32_t* src_ptr,
@@ -1202,113 +1292,16 @@ int build_heavy_list(const int32_t* d_src_ptr, int64_t n_table, int64_t n_edges,
     return 0;
 }
 
-template <int HD>
-static int run_heavy(const float* msg, float* gPL, bool bf, const int4* chunks, int32_t n_chunks, const int4* heavy,
-                     int32_t n_heavy, float* part, hipStream_t s) {
-    const dim3 grid((unsigned)((n_chunks + 3) / 4)), block(256);
-    if (bf) hipLaunchKernelGGL((gpl_chunk_kernel<HD, true>), grid, block, 0, s, chunks, n_chunks, msg, part);
-    else hipLaunchKernelGGL((gpl_chunk_kernel<HD, false>), grid, block, 0, s, chunks, n_chunks, msg, part);
-    const int64_t threads = (int64_t)n_heavy * HD;
-    hipLaunchKernelGGL(gpl_heavy_fix_kernel, dim3((unsigned)((threads + 255) / 256)), block, 0, s, heavy, n_heavy, part, gPL, HD);
-    GAT_HIP(hipGetLastError());
-    return 0;
-}
-
-int launch_gpl_sum(const int32_t* src_ptr, const float* msg, float* gPL, int64_t n_table, int64_t n_slots,
-                   int32_t HD, bool msg_bf16, const int4* chunks, int32_t n_chunks, const int4* heavy,
-                   int32_t n_heavy, float* part, hipStream_t s, const SlotRuns* runs) {
-    if (n_table <= 0) return 0;
-    // slot-parallel form (gpl_sum_runs_kernel): the default on short lists (a destination-range shard) of fp32 rows; GAT_PULL_RUNS=0|1
-    // forces.  Not for bf16 rows: a 64-byte row is FOUR lanes, and a segment end is a store instruction of its own per group (two
-    // half-line requests per 128-byte gPL row), where the list kernel's 16 groups store 16 consecutive rows with one instruction —
-    // BASELINE config 5's P = 8 shard measured 1.49-1.54 ms per step against 1.31 (profiles/r04/experiments)
-    static const int runs_env = [] { const char* e = choice_env("GAT_PULL_RUNS"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
-    static const bool group_env = choice_env("GAT_GPL_GROUP") != nullptr || choice_env("GAT_GPL_BF16_GROUP") != nullptr;
-    if (runs != nullptr && runs->csrc != nullptr && runs->run % 16 == 0 && (HD == 64 || HD == 32 || HD == 16 || HD == 8) &&
-        (runs_env >= 0 ? runs_env == 1 : (!group_env && !msg_bf16 && n_slots < 8 * n_table && n_slots >= kRunsMinSlots))) {
-        const int G = 64 / (HD / (msg_bf16 ? 8 : 4));
-        RunsDev rd{};
-        rd.csrc = runs->csrc; rd.empty = runs->empty; rd.part = runs->part; rd.n_empty = runs->n_empty; rd.n_slots = n_slots; rd.n_table = n_table;
-        rd.run = runs->run; rd.zero_blocks = (int32_t)((runs->n_empty + 4 * G * 8 - 1) / (4 * G * 8));
-        const int64_t waves = (runs->n_runs + G - 1) / G, blocks = rd.zero_blocks + (waves + 3) / 4;
-        const dim3 grid((unsigned)blocks), block(256);
-        if (blocks > 0) {
-#define SUM_RUNS(HD_) do { if (msg_bf16) hipLaunchKernelGGL((gpl_sum_runs_kernel<HD_, true>), grid, block, 0, s, msg, gPL, rd); \
-                           else hipLaunchKernelGGL((gpl_sum_runs_kernel<HD_, false>), grid, block, 0, s, msg, gPL, rd); } while (0)
-            switch (HD) { case 64: SUM_RUNS(64); break; case 32: SUM_RUNS(32); break; case 16: SUM_RUNS(16); break; default: SUM_RUNS(8); break; }
-#undef SUM_RUNS
-        }
-        if (runs->n_open > 0) {
-            const int64_t threads = (int64_t)runs->n_open * (HD / 4);
-            hipLaunchKernelGGL(gpl_runs_fix_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, runs->open, runs->n_open, runs->part, gPL, HD / 4);
-        }
-        GAT_HIP(hipGetLastError());
-        return 0;
-    }
-    if (n_heavy > 0) {                                  // long lists first: they are the longest-running waves
-        switch (HD) {
-            case 64: GAT_TRY(run_heavy<64>(msg, gPL, msg_bf16, chunks, n_chunks, heavy, n_heavy, part, s)); break;
-            case 32: GAT_TRY(run_heavy<32>(msg, gPL, msg_bf16, chunks, n_chunks, heavy, n_heavy, part, s)); break;
-            case 16: GAT_TRY(run_heavy<16>(msg, gPL, msg_bf16, chunks, n_chunks, heavy, n_heavy, part, s)); break;
-            case 8: GAT_TRY(run_heavy<8>(msg, gPL, msg_bf16, chunks, n_chunks, heavy, n_heavy, part, s)); break;
-            default: return fail(GAT_E_UNSUPPORTED, "gpl_sum: H*D outside the fast path");
-        }
-    }
-    // waves per block of the per-source kernels (GAT_GPL_WAVES, A/B): unlike the edge forward, 4 beats 1 here
-    // (6.15 vs 6.31 ms per step on one box)
-    static const int wpb = [] { const char* e = choice_env("GAT_GPL_WAVES"); const int v = e ? atoi(e) : 4; return (v == 1 || v == 2 || v == 4) ? v : 4; }();
-    if (msg_bf16) {
-        // group per source unless GAT_GPL_BF16_GROUP=0 (A/B): 10 M / 250 M shape, H*D = 32
-        static const bool bgroup = [] { const char* e = choice_env("GAT_GPL_BF16_GROUP"); return !(e && e[0] == '0'); }();
-        if (bgroup) {
-            const int rpi = 64 / (HD / 8);
-            const dim3 ggrid((unsigned)((n_table + 4 * rpi - 1) / (4 * rpi)));
-            switch (HD) {
-                case 64: hipLaunchKernelGGL(gpl_sum_bf16_group_kernel<64>, ggrid, dim3(256), 0, s, src_ptr, msg, gPL, n_table, heavy_slots(n_slots)); break;
-                case 32: hipLaunchKernelGGL(gpl_sum_bf16_group_kernel<32>, ggrid, dim3(256), 0, s, src_ptr, msg, gPL, n_table, heavy_slots(n_slots)); break;
-                case 16: hipLaunchKernelGGL(gpl_sum_bf16_group_kernel<16>, ggrid, dim3(256), 0, s, src_ptr, msg, gPL, n_table, heavy_slots(n_slots)); break;
-                case 8: hipLaunchKernelGGL(gpl_sum_bf16_group_kernel<8>, ggrid, dim3(256), 0, s, src_ptr, msg, gPL, n_table, heavy_slots(n_slots)); break;
-                default: return fail(GAT_E_UNSUPPORTED, "gpl_sum: H*D outside the fast path");
-            }
-            GAT_HIP(hipGetLastError());
-            return 0;
-        }
-        const dim3 grid((unsigned)((n_table + wpb - 1) / wpb)), block(64 * wpb);
-        switch (HD) {
-            case 64: hipLaunchKernelGGL(gpl_sum_bf16_kernel<64>, grid, block, 0, s, src_ptr, msg, gPL, n_table, heavy_slots(n_slots)); break;
-            case 32: hipLaunchKernelGGL(gpl_sum_bf16_kernel<32>, grid, block, 0, s, src_ptr, msg, gPL, n_table, heavy_slots(n_slots)); break;
-            case 16: hipLaunchKernelGGL(gpl_sum_bf16_kernel<16>, grid, block, 0, s, src_ptr, msg, gPL, n_table, heavy_slots(n_slots)); break;
-            case 8: hipLaunchKernelGGL(gpl_sum_bf16_kernel<8>, grid, block, 0, s, src_ptr, msg, gPL, n_table, heavy_slots(n_slots)); break;
-            default: return fail(GAT_E_UNSUPPORTED, "gpl_sum: H*D outside the fast path");
-        }
-        GAT_HIP(hipGetLastError());
-        return 0;
-    }
-    static const char* force = choice_env("GAT_GPL_GROUP");          // A/B switch: 0 = wave per source, 1 = group per source
-    const bool group = force ? force[0] == '1' : n_slots < 8 * n_table;   // measured: 3.2 slots/source 1.24 -> 1.00 ms, 12.6: 3.20 -> 3.31
-    if (group && HD >= 8 && HD <= 64) {
-        const int rpi = 64 / (HD / 4);
-        const dim3 grid((unsigned)((n_table + 4 * rpi - 1) / (4 * rpi))), block(256);
-        switch (HD) {
-            case 64: hipLaunchKernelGGL(gpl_sum_group_kernel<64>, grid, block, 0, s, src_ptr, msg, gPL, n_table, heavy_slots(n_slots)); break;
-            case 32: hipLaunchKernelGGL(gpl_sum_group_kernel<32>, grid, block, 0, s, src_ptr, msg, gPL, n_table, heavy_slots(n_slots)); break;
-            case 16: hipLaunchKernelGGL(gpl_sum_group_kernel<16>, grid, block, 0, s, src_ptr, msg, gPL, n_table, heavy_slots(n_slots)); break;
-            case 8: hipLaunchKernelGGL(gpl_sum_group_kernel<8>, grid, block, 0, s, src_ptr, msg, gPL, n_table, heavy_slots(n_slots)); break;
-            default: return fail(GAT_E_UNSUPPORTED, "gpl_sum: H*D outside the fast path");
-        }
-        GAT_HIP(hipGetLastError());
-        return 0;
-    }
-    const dim3 grid((unsigned)((n_table + wpb - 1) / wpb)), block(64 * wpb);
-    switch (HD) {
-        case 64: hipLaunchKernelGGL(gpl_sum_kernel<64>, grid, block, 0, s, src_ptr, msg, gPL, n_table, heavy_slots(n_slots)); break;
-        case 32: hipLaunchKernelGGL(gpl_sum_kernel<32>, grid, block, 0, s, src_ptr, msg, gPL, n_table, heavy_slots(n_slots)); break;
-        case 16: hipLaunchKernelGGL(gpl_sum_kernel<16>, grid, block, 0, s, src_ptr, msg, gPL, n_table, heavy_slots(n_slots)); break;
-        case 8: hipLaunchKernelGGL(gpl_sum_kernel<8>, grid, block, 0, s, src_ptr, msg, gPL, n_table, heavy_slots(n_slots)); break;
-        default: return fail(GAT_E_UNSUPPORTED, "gpl_sum: H*D outside the fast path");
-    }
-    GAT_HIP(hipGetLastError());
-    return 0;
+int launch_gpl_sum(const SourceIndex& ix, const float* msg, bool msg_bf16, float* gPL, int32_t HD, hipStream_t s) {
+    if (ix.n_table <= 0) return 0;
+    GplPick p = pick_sum_pass(ix, HD, msg_bf16);
+    if (p.fn == nullptr) return fail(GAT_E_UNSUPPORTED, "gpl_sum: H*D outside the fast path");
+    SourceIndex x = ix;                                 // the kernels' arguments, by address
+    int32_t hs = heavy_slots(ix.n_slots);
+    void* lists[] = {&x.src_ptr, &msg, &gPL, &x.n_table, &hs};
+    void* chunk[] = {&x.chunks, &x.n_chunks, &msg, &x.part};
+    void* runs[] = {&msg, &gPL, &p.rd};
+    return run_pick(ix, p, p.form == GplPick::kRuns ? runs : lists, chunk, gPL, HD, s);
 }
 
 }  // namespace gat

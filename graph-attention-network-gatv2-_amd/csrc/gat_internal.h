@@ -249,40 +249,56 @@ struct HeavyList {
     std::vector<int32_t> heavy;     // int4 {source, first partial, partial count, -}
     int32_t threshold = 0;          // slots above which a list is chunked (depends on the graph size)
     std::vector<int32_t> items;     // int4 {source, first slot, end slot, partial row | -1}: chunks first, then the other sources by length
-    // slot-parallel form (SlotRuns): run length (0 = not built), number of runs, lists crossing a run boundary, rows without slots
+    // slot-parallel form (SourceIndex::run ...): run length (0 = not built), number of runs, lists crossing a run boundary, rows without slots
     int32_t run = 0; int64_t n_runs = 0;
     std::vector<int32_t> open;      // int4 {source, first run, last run, -}
     std::vector<int32_t> empty;     // table rows without slots
 };
 int build_heavy_list(const int32_t* d_src_ptr, int64_t n_table, int64_t n_edges, HeavyList* out, hipStream_t s, int32_t run = 0);
-// Slot-parallel ("runs") form of the source-major pass (gat_csc.hip gpl_pull_runs_kernel): the flat slot stream cut into runs of
-// `run` slots, one per lane group, segmented by a streamed source id per slot.  Device-side index, built once per graph.
-struct SlotRuns {
-    const int32_t* csrc = nullptr;      // [n_slots + kPullPad] table row of every slot, -1 behind the last
+// slots of padding behind the record buffer and the destination list: the pull pass reads whole 16-slot chunks (and one chunk
+// of destinations ahead) without clamping its indices
+// REQUIREMENT on callers of launch_gpl_pull: SourceIndex::slot_capacity is the allocated slot count; below n_slots + kPullPad the
+// clamped first form is used.  The padding's CONTENT is not relied on (slots beyond a list are zeroed after their load), only its presence;
+// the gathered tables are addressed with 32-bit byte offsets (n_table * H*D * 4 < 4 GiB: edge_fast_path; node records: n_rows < 2^26).
+constexpr int64_t kPullPad = 32;
+// The device-side source-major index of one graph, everything the second pass walks beside the records or rows themselves.  Built
+// once per graph by gat_abi.hip ensure_buffers (which owns the allocations) from build_csc / build_csc_dst / build_heavy_list.
+struct SourceIndex {
+    const int32_t* src_ptr = nullptr;   // [n_table + 1] first slot of every table row
+    const int32_t* cdst = nullptr;      // [slot_capacity] destination row of every slot (record path), or null
+    // slot-parallel ("runs") form (gat_csc.hip gpl_pull_runs_kernel): the flat slot stream cut into runs of `run` slots, one per
+    // lane group, segmented by a streamed source id per slot
+    const int32_t* csrc = nullptr;      // [n_slots + kPullPad] table row of every slot, -1 behind the last; null = runs not built
     int32_t run = 0;                    // slots per run (a multiple of 32)
     int64_t n_runs = 0;
     const int4* open = nullptr; int32_t n_open = 0;       // lists crossing a run boundary {source, first run, last run, -}
     const int32_t* empty = nullptr; int64_t n_empty = 0;  // table rows without slots
-    float* part = nullptr;              // [2 n_runs][HDmax] partial rows of the runs' open segments
+    float* run_part = nullptr;          // [2 n_runs][HDmax] partial rows of the runs' open segments
+    // long source lists, cut into chunks (HeavyList)
+    const int4* chunks = nullptr; int32_t n_chunks = 0;   // {first slot, end slot, partial row, -}
+    const int4* heavy = nullptr; int32_t n_heavy = 0;     // {source, first partial, partial count, -}
+    float* part = nullptr;              // [n_chunks][HDmax] partial rows of the chunks
+    const int4* items = nullptr; int64_t n_items = 0;     // length-sorted source items of the pull pass (HeavyList::items), or null
+    int64_t n_table = 0, n_slots = 0;
+    int64_t slot_capacity = 0;          // slots allocated in the record buffer AND cdst: n_slots + kPullPad enables the unclamped forms
 };
-int launch_gpl_sum(const int32_t* src_ptr, const float* msg, float* gPL, int64_t n_table, int64_t n_slots,
-                   int32_t HD, bool msg_bf16, const int4* chunks, int32_t n_chunks, const int4* heavy,
-                   int32_t n_heavy, float* part, hipStream_t s, const SlotRuns* runs = nullptr);
-// slots of padding behind the record buffer and the destination list: the pull pass reads whole 16-slot chunks (and one chunk
-// of destinations ahead) without clamping its indices
-// REQUIREMENT on callers of launch_gpl_pull: pass the allocated slot count as slot_capacity; below n_slots + kPullPad the clamped
-// first form is used.  The padding's CONTENT is not relied on (slots beyond a list are zeroed after their load), only its presence;
-// the gathered tables are addressed with 32-bit byte offsets (n_table * H*D * 4 < 4 GiB: edge_fast_path; node records: n_rows < 2^26).
-constexpr int64_t kPullPad = 32;
+// below this many slots the runs cannot fill the chip (Pubmed shape: 44 k slots = 173 waves; 0.244 -> 0.268 ms per step with
+// runs, Cora shape 0.190 -> 0.216) and the list-per-wave kernels stay; Arxiv shape (1.17 M slots): 0.256 -> 0.195 ms per step
+constexpr int64_t kRunsMinSlots = 512 << 10;
+// THE short-list rule: lists this short (a destination-range shard, a sparse graph), and enough of them, take the slot-parallel
+// form.  Unforced: the callers apply their switches (GAT_PULL_RUNS, ...) and their own conditions around it.
+inline bool short_lists_take_runs(int64_t n_slots, int64_t n_table) { return n_slots < 8 * n_table && n_slots >= kRunsMinSlots; }
+// message rows: gPL[s][:] = sum over the slots of s of msg[slot][:]   (rows of HD floats, or HD bf16 with msg_bf16)
+int launch_gpl_sum(const SourceIndex& ix, const float* msg, bool msg_bf16, float* gPL, int32_t HD, hipStream_t s);
 // cdst[pos[e]] = destination row of CSR edge e (the source-major twin of a1's dst array; built once per graph)
 int build_csc_dst(const int32_t* row_ptr, const int32_t* pos, int32_t* cdst, int64_t n_rows, int64_t n_edges, hipStream_t s);
 // Stash path: gPL[s][:] = sum over the slots of s of  g[cdst][:] * alpha + ge * a (.) LReLU'  rebuilt from the records
 // gh / hbits non-null (last layer): g rows are rebuilt from gh [n_rows][D] and the per-lane decision bytes instead of read from gfull
-int launch_gpl_pull(const int32_t* src_ptr, const uint32_t* stash, const int32_t* cdst, const float* gfull, bool g_bf16,
-                    const float* gh, const uint8_t* hbits, int32_t gh_stride, int32_t hb_stride, const float* a,
-                    float slope, float* gPL, int64_t n_table, int64_t n_slots, int32_t H, int32_t D, const int4* chunks,
-                    int32_t n_chunks, const int4* heavy, int32_t n_heavy, float* part, const int4* items, int64_t n_items, const SlotRuns* runs,
-                    int64_t slot_capacity /* slots allocated in stash AND cdst: n_slots + kPullPad enables the unclamped forms */, hipStream_t s);
+struct PullArgs {
+    const uint32_t* stash; const float* gfull; bool g_bf16; const float* gh; const uint8_t* hbits;
+    int32_t gh_stride, hb_stride; const float* a; float slope; float* gPL; int32_t H, D;
+};
+int launch_gpl_pull(const SourceIndex& ix, const PullArgs& p, hipStream_t s);
 
 int launch_csr_to_coo(const int32_t* row_ptr, const int32_t* col_idx, int32_t* src, int32_t* dst,
                       int64_t n_rows, int64_t n_edges, int64_t table_row0, hipStream_t s);

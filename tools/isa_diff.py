@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""isa_diff.py OLD.s NEW.s [--show N] — are two hipcc -S listings the same kernels?
+"""isa_diff.py OLD.s NEW.s [--show N] [--pairs FILE] — are two hipcc -S listings the same kernels?
 
 Per kernel: the .amdhsa figures tools/isa_stats.py prints must be equal, and the instruction lines must be equal once comments,
-register numbers and local labels are masked ("registers renamed").  Kernels whose mangled name exists on one side only are paired
-by the longest common prefix of their names (a renamed parameter type changes the tail only) and listed.
+register numbers and local labels are masked ("registers renamed").  "Byte-identical" is the kernel's text as it stands, but for
+the number of the function inside its local labels (.LBB<function>_<block>), which moves when another kernel is emitted before it.  Kernels whose mangled name exists on one side only are paired
+by the longest common prefix of their names (a renamed parameter type changes the tail only) and listed; --pairs FILE pairs by hand
+first ("OLD_NAME NEW_NAME" per line: kernels folded into one template, whose names differ in the middle).
 Prints one summary line; exit status 1 if any kernel has other differences or stays unpaired."""
 import difflib
 import re
@@ -34,6 +36,12 @@ def masked(body):
     return lines
 
 
+def unnumbered(body):
+    """Local labels, and the comments that cite them, carry the number of their function in the file (.LBB<function>_<block>):
+    where a kernel is emitted is not its code."""
+    return re.sub(r"(BB|JTI)\d+_(?=\d)", r"\1_", body)
+
+
 def prefix_len(a, b):
     n = 0
     while n < min(len(a), len(b)) and a[n] == b[n]:
@@ -46,6 +54,10 @@ def main():
     old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
     pairs = [(n, n) for n in old if n in new]
     lone_old, lone_new = [n for n in old if n not in new], [n for n in new if n not in old]
+    if "--pairs" in sys.argv:
+        for a, b in (ln.split() for ln in open(sys.argv[sys.argv.index("--pairs") + 1]) if ln.strip()):
+            print("paired by hand:", a, "->", b)
+            pairs.append((a, b)); lone_old.remove(a); lone_new.remove(b)
     for a in list(lone_old):            # the same kernel under another parameter type: the longest common prefix, both ways
         b = max(lone_new, key=lambda n: prefix_len(a, n), default=None)
         if b is not None and max(lone_old, key=lambda n: prefix_len(n, b)) == a:
@@ -58,7 +70,7 @@ def main():
     for a, b in pairs:
         (ba, fa), (bb, fb) = old[a], new[b]
         ma, mb = masked(ba), masked(bb)
-        if fa == fb and ba == bb:
+        if fa == fb and unnumbered(ba) == unnumbered(bb):
             same += 1
         elif fa == fb and ma == mb:
             renamed += 1
