@@ -48,6 +48,9 @@ class _Config(C.Structure):
 # enums of the header
 PARAM_W, PARAM_A, PARAM_WO, PARAM_WRES, PARAM_B = 0, 1, 2, 3, 4
 PARAM_LN_G, PARAM_LN_B = 5, 6
+PARAM_WE = 7                                # edge features (set_edge_dim): flat [l][H_l*D_l][Fe], behind the others
+PARAM_GROUPS = (PARAM_W, PARAM_A, PARAM_WO, PARAM_WRES, PARAM_B, PARAM_LN_G, PARAM_LN_B, PARAM_WE)      # the packed order
+EDGE_DIM_MAX = 64
 RES_LINEAR, RES_BIAS = 1, 2
 NORM_LAYER, NORM_SKIP_LAST = 1, 2
 TABLE_PL, TABLE_GPL = 0, 1
@@ -201,6 +204,9 @@ def _declare(lib: C.CDLL) -> None:
         "gat_set_dropedge": [vp, f32, i32],
         "gat_set_residual": [vp, i32],
         "gat_set_norm": [vp, i32, f32],
+        "gat_set_edge_dim": [vp, i32],
+        "gat_set_edge_features": [vp, vp, i64, i32],
+        "gat_set_edge_features_device": [vp, vp, i64, i32],
         "gat_set_training": [vp, i32],
         "gat_dropout_step": [vp, P(C.c_uint64)],
         "gat_set_shard_bounds": [vp, i32, vp],
@@ -416,7 +422,7 @@ class GatContext:
 
     @property
     def n_params(self) -> int:
-        return sum(self.param_count(g) for g in (PARAM_W, PARAM_A, PARAM_WO, PARAM_WRES, PARAM_B, PARAM_LN_G, PARAM_LN_B))
+        return sum(self.param_count(g) for g in PARAM_GROUPS)
 
     # -- residual / bias (gatv2_abi.h "residual")
     def set_residual(self, linear: bool = False, bias: bool = False, flags: int = 0):
@@ -430,6 +436,22 @@ class GatContext:
         but the last), with the parameter groups PARAM_LN_G / PARAM_LN_B.  Only before the first params_* / grads_* / set_graph*
         call on the context.  ``flags``: extra raw GAT_NORM_* bits (or-ed in)."""
         _chk(self.lib.gat_set_norm(self._ctx, int(flags) | (NORM_LAYER if layer else 0) | (NORM_SKIP_LAST if skip_last else 0), float(eps)))
+
+    # -- edge features (gatv2_abi.h "edge features")
+    def set_edge_dim(self, edge_dim: int):
+        """Per-edge attributes of ``edge_dim`` floats enter the attention score through the parameter group PARAM_WE (PyG's
+        GATv2Conv ``edge_dim``).  Only before the first params_* / grads_* / set_graph* call on the context; 0 = off."""
+        _chk(self.lib.gat_set_edge_dim(self._ctx, int(edge_dim)))
+
+    def set_edge_features(self, ea):
+        """The attribute rows [n_edges][edge_dim] in the order of the context's CSR (what graph() returns); after set_graph*."""
+        a = np.ascontiguousarray(ea, np.float32)
+        if a.ndim != 2:
+            raise ValueError(f"edge features must be [n_edges][edge_dim], got shape {a.shape}")
+        _chk(self.lib.gat_set_edge_features(self._ctx, _np_ptr(a), a.shape[0], a.shape[1]))
+
+    def set_edge_features_device(self, d_ea: int, n_edges: int, edge_dim: int):
+        _chk(self.lib.gat_set_edge_features_device(self._ctx, C.c_void_p(d_ea or None), n_edges, edge_dim))
 
     # -- dropout (gatv2_abi.h "dropout")
     def set_dropout(self, feat_p: float = 0.0, attn_p: float = 0.0, seed: int = 0, first_step: int = 0):

@@ -45,6 +45,8 @@ struct Layer {
     int64_t w_off = 0, a_off = 0;
     int64_t wres_off = 0, b_off = 0;                // inside the Wres / b groups (gat_set_residual)
     int64_t ln_off = 0;                             // inside the gamma and the beta group (gat_set_norm)
+    int64_t we_off = 0;                             // inside the We group (gat_set_edge_dim)
+    float* PE = nullptr;      // [n_edges][HD]  EA We^T, fp32 also under bf16 storage (streamed by the edge passes, never gathered)
     float* R = nullptr;       // [n_rows][HD]  x' Wres^T of the shard's own rows (GAT_RES_LINEAR)
     float* PL = nullptr;      // [n_table][HD]  (table; may be caller-owned)
     bool PL_bound = false;
@@ -119,7 +121,7 @@ void build_worklist(const int32_t* rp, int64_t n_rows, WorkList& w) {
 
 }  // namespace gat
 
-constexpr int kParamGroups = GAT_PARAM_LN_B + 1;   // GAT_PARAM_* are 0 .. 6, in packed order
+constexpr int kParamGroups = GAT_PARAM_WE + 1;   // GAT_PARAM_* are 0 .. 7, in packed order
 struct gat_ctx {
     gat_config cfg{};
     std::vector<int32_t> heads, outdims;
@@ -140,17 +142,23 @@ struct gat_ctx {
                                                     // column in_dim), so that an odd in_dim — Cora's 1,433 — still gets 16-byte loads
     float* Xtab = nullptr;                          // [n_table][in_dim] replicated layer-0 input (gat_set_source_features)
     // the packed parameter layout by GAT_PARAM_* (layout_params): floats in each group — Wres / b are empty unless gat_set_residual,
-    // gamma / beta unless gat_set_norm switched them on — and the group's first float in params / grads
+    // gamma / beta unless gat_set_norm, We unless gat_set_edge_dim switched them on — and the group's first float in params / grads
     int64_t group_cnt[kParamGroups] = {0}, group_off[kParamGroups] = {0};
     int32_t res_flags = 0;                          // GAT_RES_* (gat_set_residual)
     int32_t norm_flags = 0; float norm_eps = 0.f;   // GAT_NORM_* (gat_set_norm)
     float* norm_partial = nullptr;                  // [L][2][kResPartialRows][HDmax] block column sums for grad_gamma / grad_beta
+    // edge features (gatv2_abi.h "edge features"): Fe, the attribute rows (pitch ea_ld = Fe rounded up to 4, zeros behind column Fe), the
+    // one dL/dPE buffer the layers share (rows of the running layer's HD floats), the slabs of gradWe (one region per layer)
+    int32_t edge_dim = 0, ea_ld = 0;
+    float* EA = nullptr; bool have_ea = false;      // [n_edges][ea_ld]
+    float* gPE = nullptr;                           // [n_edges][HDmax]
+    float* we_gw_scratch = nullptr; std::vector<int64_t> we_gw_off;
     bool params_touched = false;                    // a gat_params_* / gat_grads_* / gat_set_graph* call was made: the packed buffers keep their size
     float* resG = nullptr; float* res_agg = nullptr;   // [n_rows][HDmax] dL/dh_pre and h_pre - (R + b) of the layer whose backward runs
     float* res_partial = nullptr;                   // [L][kResPartialRows][HDmax] block column sums of G (grad_b), one region per layer
     float* res_gw_scratch = nullptr; std::vector<int64_t> res_gw_off;     // slabs of gradWres, one region per layer
-    float* params = nullptr;   // [W | a | Wo | Wres | b | gamma | beta]
-    float* grads = nullptr;    // [gradW | grada | gradWo | gradWres | gradb | gradgamma | gradbeta] + 4 floats of tail: [loss, correct lo, correct hi, -]
+    float* params = nullptr;   // [W | a | Wo | Wres | b | gamma | beta | We]
+    float* grads = nullptr;    // [gradW | grada | gradWo | gradWres | gradb | gradgamma | gradbeta | gradWe] + 4 floats of tail: [loss, correct lo, correct hi, -]
     std::unique_ptr<gat::Comm> comm;                // exchange transport of a shard (gat_comm_init_*)
     int32_t comm_chunks = 1;                        // gat_comm_option(GAT_COMM_PIPELINE): row chunks of the pipelined forward exchange
     hipStream_t comm_stream = nullptr;              // second stream of the pipelined exchange (created on first use)
@@ -282,18 +290,19 @@ static float* gW_of(gat_ctx* c, int l) { return grad_of(c, GAT_PARAM_W, c->layer
 static float* ga_of(gat_ctx* c, int l) { return grad_of(c, GAT_PARAM_A, c->layers[l].a_off); }
 static float* gWo_of(gat_ctx* c) { return grad_of(c, GAT_PARAM_WO); }
 static int64_t n_params(const gat_ctx* c) { return c->group_off[kParamGroups - 1] + c->group_cnt[kParamGroups - 1]; }
-// The packed layout [W | a | Wo | Wres | b | gamma | beta]: every layer's offset inside the groups, the groups' sizes and where they
-// start.  Called whenever the set of groups changes (gat_create, gat_set_residual, gat_set_norm).
+// The packed layout [W | a | Wo | Wres | b | gamma | beta | We]: every layer's offset inside the groups, the groups' sizes and where they
+// start.  Called whenever the set of groups changes (gat_create, gat_set_residual, gat_set_norm, gat_set_edge_dim).
 static void layout_params(gat_ctx* c) {
     int64_t* n = c->group_cnt;
     std::fill(n, n + kParamGroups, (int64_t)0);
     for (Layer& y : c->layers) {
-        y.w_off = n[GAT_PARAM_W]; y.a_off = n[GAT_PARAM_A]; y.wres_off = n[GAT_PARAM_WRES]; y.b_off = n[GAT_PARAM_B]; y.ln_off = n[GAT_PARAM_LN_G];
+        y.w_off = n[GAT_PARAM_W]; y.a_off = n[GAT_PARAM_A]; y.wres_off = n[GAT_PARAM_WRES]; y.b_off = n[GAT_PARAM_B]; y.ln_off = n[GAT_PARAM_LN_G]; y.we_off = n[GAT_PARAM_WE];
         n[GAT_PARAM_W] += (int64_t)y.HD * 2 * y.F;                       // E:1248-1254
         n[GAT_PARAM_A] += y.HD;
         if (c->res_flags & GAT_RES_LINEAR) n[GAT_PARAM_WRES] += (int64_t)y.HD * y.F;
         if (c->res_flags & GAT_RES_BIAS) n[GAT_PARAM_B] += y.HD;
         if (c->norm_flags != 0) n[GAT_PARAM_LN_G] += y.HD;               // all L layers; with GAT_NORM_SKIP_LAST the last one's entries are never read
+        n[GAT_PARAM_WE] += (int64_t)y.HD * c->edge_dim;
     }
     n[GAT_PARAM_WO] = (int64_t)c->cfg.num_classes * c->layers.back().D;
     n[GAT_PARAM_LN_B] = n[GAT_PARAM_LN_G];
@@ -307,6 +316,15 @@ static bool norm_layer(const gat_ctx* c, int l) {
 }
 // the context runs the residual route: the forward takes EdgeFwdExtras, the backward the N-sized kernel, G and agg in the edge backward
 static bool res_route(const gat_ctx* c) { return res_on(c) || norm_on(c); }
+static bool edge_feat_on(const gat_ctx* c) { return c->edge_dim > 0; }
+static float* We_of(gat_ctx* c, int l) { return param_of(c, GAT_PARAM_WE, c->layers[l].we_off); }
+static float* gWe_of(gat_ctx* c, int l) { return grad_of(c, GAT_PARAM_WE, c->layers[l].we_off); }
+// a step / phase on a context with edge_dim > 0 needs the attribute rows
+static int check_edge_features(gat_ctx* c) {
+    if (edge_feat_on(c) && !c->have_ea)
+        return fail(GAT_E_STATE, "edge features not set: the context has edge_dim > 0 (gat_set_edge_dim) but gat_set_edge_features was never called");
+    return 0;
+}
 static float* lng_of(gat_ctx* c, int l) { return param_of(c, GAT_PARAM_LN_G, c->layers[l].ln_off); }
 static float* lnb_of(gat_ctx* c, int l) { return param_of(c, GAT_PARAM_LN_B, c->layers[l].ln_off); }
 static float* glng_of(gat_ctx* c, int l) { return grad_of(c, GAT_PARAM_LN_G, c->layers[l].ln_off); }
@@ -556,6 +574,19 @@ static int ensure_buffers(gat_ctx* c) {
             GAT_TRY(dalloc(c, &c->res_gw_scratch, std::max<int64_t>(rg, 1)));
         }
         GAT_TRY(ensure_drop_step(c));                // the forward's extended kernels read the step counter (nothing is dropped)
+    }
+    if (edge_feat_on(c)) {                           // gatv2_abi.h "edge features": PE per layer, one gPE, the slabs of gradWe
+        const int64_t Ea = std::max<int64_t>(E, 1);  // (the edge kernels clamp their index prefetch to edge 0: one row always exists)
+        int64_t wg = 0;
+        c->we_gw_off.assign((size_t)L, 0);
+        for (int l = 0; l < L; ++l) {
+            GAT_TRY(dalloc(c, &c->layers[l].PE, Ea * c->layers[l].HD));
+            c->we_gw_off[(size_t)l] = wg;
+            wg += grad_w_scratch_floats(E, c->edge_dim, c->layers[l].HD);
+        }
+        GAT_TRY(dalloc(c, &c->gPE, Ea * c->HDmax));
+        GAT_TRY(dalloc(c, &c->we_gw_scratch, std::max<int64_t>(wg, 1)));
+        GAT_TRY(ensure_drop_step(c));                // both passes run extended kernels, which read the step counter
     }
     c->buffers_ready = true;
     GAT_TRY(ensure_drop_buffers(c));
@@ -995,6 +1026,14 @@ int gat_params_init(gat_ctx* c, uint64_t seed) {
             draw += (uint64_t)nr;
         }
     }
+    if (edge_feat_on(c)) {                                               // after Wres: every other group of a seed is unchanged
+        for (int l = 0; l < c->cfg.num_layers; ++l) {
+            const Layer& y = c->layers[l];
+            const int64_t ne = (int64_t)y.HD * c->edge_dim;
+            GAT_TRY(launch_xavier_init(We_of(c, l), ne, s0, draw, sqrtf(6.0f / (float)(c->edge_dim + y.HD)), c->stream));
+            draw += (uint64_t)ne;
+        }
+    }
     if (b_of(c, 0)) GAT_HIP(hipMemsetAsync(b_of(c, 0), 0, (size_t)c->group_cnt[GAT_PARAM_B] * sizeof(float), c->stream));
     const std::vector<float> ones((size_t)c->group_cnt[GAT_PARAM_LN_G], 1.0f);      // layer normalisation: gamma = 1, beta = 0, no draws
     if (!ones.empty()) {
@@ -1024,9 +1063,12 @@ static int drop_prepare_input(gat_ctx* c, int32_t l) {
 }
 int gat_layer_project(gat_ctx* c, int32_t l) {
     GAT_TRY(check_layer(c, l));
+    GAT_TRY(check_edge_features(c));
     Layer& y = c->layers[l];
     Scope t(c, GAT_K_PROJECT);
     GAT_TRY(drop_prepare_input(c, l));
+    // edge features: PE = EA We^T over the E edges of the shard's own CSR — the residual term's product with rows = E, K = Fe
+    if (y.PE != nullptr && c->n_edges > 0) GAT_TRY(launch_project_res(c->EA, We_of(c, l), y.PE, c->n_edges, c->edge_dim, y.HD, c->stream, c->ea_ld));
     // residual: R = x' Wres^T over the shard's own rows (with replicated input: its own rows of the table) — the third projection
     if (y.R != nullptr) GAT_TRY(launch_project_res(Xin_of(c, l), Wres_of(c, l), y.R, c->n_rows, y.F, y.HD, c->stream, ldX_of(c, l)));
     if (l == 0 && c->Xtab) {      // replicated input: whole PL table from the table rows, PR from the shard's rows
@@ -1040,9 +1082,10 @@ int gat_layer_project(gat_ctx* c, int32_t l) {
 static EdgeFwdArgs plan_forward_edges(gat_ctx* c, int32_t l);
 int gat_layer_forward_edges(gat_ctx* c, int32_t l) {
     GAT_TRY(check_layer(c, l));
+    GAT_TRY(check_edge_features(c));
     const EdgeFwdArgs a = plan_forward_edges(c, l);
-    EdgeFwdExtras x;                                 // masks, residual, bias, norm: whatever of them is on (launch_edge_forward: none = the plain kernels)
-    x.drop = drop_args(c, l); x.res = c->layers[l].R; x.bias = b_of(c, l); x.ln = ln_args(c, l);
+    EdgeFwdExtras x;                                 // masks, residual, bias, norm, edge term: whatever of them is on (launch_edge_forward: none = the plain kernels)
+    x.drop = drop_args(c, l); x.res = c->layers[l].R; x.bias = b_of(c, l); x.ln = ln_args(c, l); x.pe = c->layers[l].PE;
     Scope t(c, GAT_K_EDGE_FWD);
     return launch_edge_forward(a, c->stream, &x);
 }
@@ -1118,7 +1161,7 @@ static int plan_backward_edges(gat_ctx* c, int32_t l, BwdPlan* P) {
     // of two, and that pass is bound by lines per second (Products P = 8 shard, 78 MB: 0.84 -> 0.78 ms per step; Arxiv 43 MB: equal)
     const bool runs_form = c->src_index.csrc != nullptr && short_lists_take_runs(c->n_edges, c->n_table);
     const bool big_rows = (int64_t)c->n_rows * y.H * y.D * 4 > ((int64_t)(runs_form ? 64 : 128) << 20);
-    const bool last_g = stash && a.gh != nullptr && c->hbits != nullptr && !bf16(c) && (pull_last >= 0 ? pull_last == 1 : big_rows) &&
+    const bool last_g = stash && a.gh != nullptr && c->hbits != nullptr && !bf16(c) && !edge_feat_on(c) && (pull_last >= 0 ? pull_last == 1 : big_rows) &&
                         c->n_rows < ((int64_t)1 << 26);             // the pull pass addresses the 64-byte node records with 32-bit offsets
     a.hbits = last_g ? c->hbits : nullptr;
     a.items = c->items; a.n_items = c->work.n_items; a.slot_info = c->slot_info; a.n_slots = c->work.n_slots; a.n_split = c->work.n_split;
@@ -1127,7 +1170,7 @@ static int plan_backward_edges(gat_ctx* c, int32_t l, BwdPlan* P) {
     a.ga_partial = c->ga_partial + (int64_t)l * kGaPartialRows * c->HDmax; a.n_rows = c->n_rows; a.n_table = c->n_table; a.bf16 = bf16(c); a.H = y.H; a.D = y.D;
     a.slope = c->cfg.negative_slope;
     P->drop = drop_args(c, l);
-    a.ga_blocks = edge_backward_blocks(a, &P->drop);
+    a.ga_blocks = edge_backward_blocks(a, &P->drop, y.PE != nullptr);
     P->a = a; P->store = store; P->stash = stash; P->last_g = last_g;
     return 0;
 }
@@ -1174,6 +1217,7 @@ static int res_backward_layer(gat_ctx* c, int32_t l) {
 }
 int gat_layer_backward_edges(gat_ctx* c, int32_t l) {
     GAT_TRY(check_layer(c, l));
+    GAT_TRY(check_edge_features(c));
     Layer& y = c->layers[l];
     BwdPlan P;
     GAT_TRY(plan_backward_edges(c, l, &P));
@@ -1184,7 +1228,8 @@ int gat_layer_backward_edges(gat_ctx* c, int32_t l) {
     }
     {
         Scope t(c, GAT_K_EDGE_BWD);
-        GAT_TRY(launch_edge_backward(P.a, c->stream, &P.drop));
+        // edge features: the PE instantiations; gs of every edge goes to the shared gPE buffer (rows of this layer's HD floats)
+        GAT_TRY(launch_edge_backward(P.a, c->stream, &P.drop, y.PE, y.PE != nullptr ? c->gPE : nullptr));
     }
     GAT_TRY(sum_backward_edges(c, l, P));
     Scope t(c, GAT_K_MISC);
@@ -1200,6 +1245,10 @@ static int backward_grad_w(gat_ctx* c, int32_t l, hipStream_t st) {
     // on the same stream; the side stream of GAT_OVERLAP is not used with a residual context)
     if (y.R != nullptr)
         GAT_TRY(launch_grad_wres(c->resG, Xin_of(c, l), gWres_of(c, l), c->res_gw_scratch + c->res_gw_off[(size_t)l], c->n_rows, y.F, y.HD, st, ldX_of(c, l)));
+    // edge features: gradWe += gPE^T EA over the E edges (gPE: this layer's, still in place — the next layer's edge backward runs later on
+    // the same stream; the side stream of GAT_OVERLAP is not used with edge features)
+    if (y.PE != nullptr)
+        GAT_TRY(launch_grad_wres(c->gPE, c->EA, gWe_of(c, l), c->we_gw_scratch + c->we_gw_off[(size_t)l], c->n_edges, c->edge_dim, y.HD, st, c->ea_ld));
     if (l == 0 && c->Xtab) {  // partial gPL over the whole table x replicated input; the gradient all-reduce sums shards
         GAT_TRY(launch_grad_w(gPL_of(c, l), nullptr, Xtab_of(c), gW_of(c, l), c->gw_scratch, c->n_table, y.F, y.HD, kPartLeft, st, c->ld0));
         return launch_grad_w(nullptr, gPR_of(c, l), Xin_of(c, 0), gW_of(c, l), c->gw_scratch, c->n_rows, y.F, y.HD, kPartRight, st, c->ld0);
@@ -1223,6 +1272,7 @@ static int backward_grad_x(gat_ctx* c, int32_t l) {
 }
 int gat_layer_backward_dense(gat_ctx* c, int32_t l) {
     GAT_TRY(check_layer(c, l));
+    GAT_TRY(check_edge_features(c));
     GAT_TRY(backward_grad_w(c, l, c->stream));
     return backward_grad_x(c, l);
 }
@@ -1233,6 +1283,7 @@ static int64_t pl_slice(gat_ctx* c, const Layer& y) { return table_slice(c, y) *
 static bool needs_exchange(gat_ctx* c, int l) { return c->n_table != c->n_rows && !(l == 0 && c->Xtab); }
 static int check_step(gat_ctx* c, const char* who) {
     GAT_TRY(check_layer(c, 0));
+    GAT_TRY(check_edge_features(c));
     if (c->n_table != c->n_rows && !c->comm)
         return fail(GAT_E_STATE, std::string(who) + ": sharded context — attach a transport (gat_comm_init_*) or drive "
                                                    "the phase API with the exchange steps");
@@ -1260,6 +1311,7 @@ static int forward_exchange_pipelined(gat_ctx* c, int l) {
     char* own_rows = reinterpret_cast<char*>(y.PL) + c->table_row0 * y.HD * st_bytes(c);
     Scope t(c, GAT_K_EXCHANGE);                                            // timed as a whole: projection chunks + their exchanges
     GAT_TRY(drop_prepare_input(c, l));
+    if (y.PE != nullptr && c->n_edges > 0) GAT_TRY(launch_project_res(c->EA, We_of(c, l), y.PE, c->n_edges, c->edge_dim, y.HD, c->stream, c->ea_ld));
     if (y.R != nullptr) GAT_TRY(launch_project_res(Xin_of(c, l), Wres_of(c, l), y.R, c->n_rows, y.F, y.HD, c->stream, ldX_of(c, l)));
     for (int k = 0; k < K; ++k) {
         const int64_t r0 = (int64_t)k * rpc, r1s = std::min<int64_t>(r0 + rpc, max_rows), r1 = std::min<int64_t>(r1s, c->n_rows);
@@ -1285,6 +1337,7 @@ static int forward_phases(gat_ctx* c, int l_end = -1, bool last_edges = true) {
         if (c->comm && needs_exchange(c, l) && c->comm_chunks > 1 && !c->halo_on &&
             project_scratch_floats(c->n_rows, c->layers[l].F, c->layers[l].HD, kPartBoth) == 0) {
             GAT_TRY(check_layer(c, l));
+            GAT_TRY(check_edge_features(c));
             GAT_TRY(forward_exchange_pipelined(c, l));
             if (edges) GAT_TRY(gat_layer_forward_edges(c, l));
             continue;
@@ -1329,7 +1382,7 @@ static int head_step(gat_ctx* c, bool with_gh = true) {
 // of the forward's rows left in the caches when a pass's gathers exceed the Infinity Cache; fused per row, the second walk of
 // a row's sources comes a few microseconds after the first.
 static bool fused_last(gat_ctx* c) {
-    if (!fused_head(c) || bf16(c) || c->comm || c->n_table != c->n_rows || c->cfg.flat_lrelu_index || res_route(c)) return false;   // no residual / norm form
+    if (!fused_head(c) || bf16(c) || c->comm || c->n_table != c->n_rows || c->cfg.flat_lrelu_index || res_route(c) || edge_feat_on(c)) return false;   // no residual / norm / edge-feature form
     const Layer& y = c->layers.back();
     if (!edge_fast_path(y.H, y.D, c->n_table) || !y.stash || c->stash == nullptr || c->gH == nullptr) return false;
     if (!edge_last_fused_supported(y.H, y.D, c->cfg.num_classes) || c->dbg != 0 || drop_on(c)) return false;   // no dropout form
@@ -1397,7 +1450,7 @@ static int overlap_prepare(gat_ctx* c) {
     static const int env = [] { const char* e = choice_env("GAT_OVERLAP"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
     const int L = c->cfg.num_layers;
     const bool want = env == 1;
-    if (!want || L < 2 || c->gPL_bound || c->Xtab || res_route(c)) return 0;      // (residual: one G buffer, read by grad_w)
+    if (!want || L < 2 || c->gPL_bound || c->Xtab || res_route(c) || edge_feat_on(c)) return 0;      // (residual: one G buffer, read by grad_w; edge features: one gPE)
     if (!c->gPL_alt) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(c->stream, &cs);
@@ -1638,6 +1691,46 @@ int gat_set_residual(gat_ctx* c, int32_t flags) {
     c->res_flags = flags;
     layout_params(c);
     return resize_packed(c);
+}
+// ---- edge features ------------------------------------------------------------------------------------------------
+int gat_set_edge_dim(gat_ctx* c, int32_t edge_dim) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (edge_dim < 0 || edge_dim > GAT_EDGE_DIM_MAX) return fail(GAT_E_INVALID, "gat_set_edge_dim: edge_dim must be in [0, " + std::to_string(GAT_EDGE_DIM_MAX) + "]");
+    if (c->params_touched)
+        return fail(GAT_E_STATE, "gat_set_edge_dim: call it before the first gat_params_*, gat_grads_* or gat_set_graph* call (the packed buffers change size)");
+    if (edge_dim == c->edge_dim) return 0;               // (0 on a fresh context: nothing is touched)
+#ifdef GAT_EXPERIMENTS                               // (the release library does not know the switch's name)
+    if (c->dbg != 0 && edge_dim != 0)
+        return fail(GAT_E_UNSUPPORTED, "gat_set_edge_dim: not with a GAT_DBG timing experiment (those kernels have no edge-feature form)");
+#endif
+    c->edge_dim = edge_dim; c->ea_ld = (edge_dim + 3) / 4 * 4;
+    layout_params(c);
+    return resize_packed(c);
+}
+static int set_edge_features_common(gat_ctx* c, const float* ea, int64_t n_edges, int32_t edge_dim, hipMemcpyKind kind) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (!c->have_graph) return fail(GAT_E_STATE, "gat_set_edge_features: set the graph first (the rows are in the order of its CSR)");
+    if (edge_dim != c->edge_dim) return fail(GAT_E_INVALID, "gat_set_edge_features: edge_dim differs from the context's (gat_set_edge_dim)");
+    if (n_edges != c->n_edges) return fail(GAT_E_INVALID, "gat_set_edge_features: row count differs from the graph's edge count");
+    if (edge_dim == 0) return 0;                         // a context without the feature: nothing to copy
+    if (!ea && n_edges > 0) return fail(GAT_E_INVALID, "gat_set_edge_features: null argument");
+    const int64_t Ea = std::max<int64_t>(n_edges, 1);
+    if (!c->EA) {                                        // allocated once: a later call refills the same buffer (a captured step stays valid)
+        GAT_TRY(dalloc(c, &c->EA, Ea * c->ea_ld));
+        GAT_HIP(hipMemsetAsync(c->EA, 0, (size_t)(Ea * c->ea_ld) * sizeof(float), c->stream));
+    }
+    if (n_edges > 0)
+        GAT_HIP(hipMemcpy2DAsync(c->EA, (size_t)c->ea_ld * sizeof(float), ea, (size_t)edge_dim * sizeof(float), (size_t)edge_dim * sizeof(float),
+                                 (size_t)n_edges, kind, c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    c->have_ea = true;
+    return 0;
+}
+int gat_set_edge_features(gat_ctx* c, const float* ea, int64_t n_edges, int32_t edge_dim) {
+    return set_edge_features_common(c, ea, n_edges, edge_dim, hipMemcpyHostToDevice);
+}
+int gat_set_edge_features_device(gat_ctx* c, const float* d_ea, int64_t n_edges, int32_t edge_dim) {
+    return set_edge_features_common(c, d_ea, n_edges, edge_dim, hipMemcpyDeviceToDevice);
 }
 // ---- layer normalisation ----------------------------------------------------------------------------------------
 int gat_set_norm(gat_ctx* c, int32_t flags, float eps) {
@@ -2182,8 +2275,29 @@ int gat_request_bytes_shape(const gat_config* cfg, int64_t n_rows, int64_t n_edg
     if (bytes_step) *bytes_step = tot;
     return 0;
 }
+// edge features (gatv2_abi.h "edge features"): what the dense per-edge term adds, fp32 throughout — EA and We read and PE written by the
+// projection, PE read by the edge forward, PE read and gPE written by the edge backward, gPE, EA and gradWe in the dense term
+static void edge_feature_bytes(const gat_ctx* c, double* k) {
+    if (!edge_feat_on(c)) return;
+    const double E = (double)c->n_edges, Fe = c->edge_dim;
+    for (int l = 0; l < c->cfg.num_layers; ++l) {
+        const double HD = c->layers[l].HD;
+        k[GAT_K_PROJECT] += 4.0 * (E * Fe + HD * Fe + E * HD);
+        k[GAT_K_EDGE_FWD] += 4.0 * E * HD;
+        k[GAT_K_EDGE_BWD] += 4.0 * 2 * E * HD;
+        k[GAT_K_GRAD_W] += 4.0 * (E * HD + E * Fe + HD * Fe);
+    }
+}
 int gat_algorithmic_bytes(gat_ctx* c, double* bytes_step, double* per_kernel) {
     if (!c || !c->have_graph) return fail(GAT_E_STATE, "graph not set");
+    if (edge_feat_on(c) && !res_route(c)) {
+        double k[GAT_K_COUNT] = {0}, tot = 0;
+        GAT_TRY(gat_algorithmic_bytes_shape(&c->cfg, c->n_rows, c->n_edges, c->n_table, c->Xtab != nullptr, nullptr, k));
+        edge_feature_bytes(c, k);
+        for (int i = 0; i < GAT_K_COUNT; ++i) { tot += k[i]; if (per_kernel) per_kernel[i] = k[i]; }
+        if (bytes_step) *bytes_step = tot;
+        return 0;
+    }
     if (res_route(c)) {
         // residual (gatv2_abi.h "residual"): the N-sized traffic it adds, fp32 throughout — R written, read by the edge forward and by
         // the N-sized backward kernel; that kernel's h_pre and g read, G and agg written; G, x' and Wres in the two dense terms
@@ -2203,6 +2317,7 @@ int gat_algorithmic_bytes(gat_ctx* c, double* bytes_step, double* per_kernel) {
             k[GAT_K_GRAD_W] += 4.0 * (N * HD + N * F + HD * F);
             if (l > 0) k[GAT_K_GRAD_X] += 4.0 * (N * HD + 2 * N * F + HD * F);
         }
+        edge_feature_bytes(c, k);
         for (int i = 0; i < GAT_K_COUNT; ++i) { tot += k[i]; if (per_kernel) per_kernel[i] = k[i]; }
         if (bytes_step) *bytes_step = tot;
         return 0;

@@ -51,6 +51,10 @@ struct RowKeys { uint32_t kd, ke; int rb; };
 __device__ __forceinline__ void row_keys(const DropArgs& d, int64_t row, const int32_t* row_ptr, RowKeys& k) {
     k.kd = drop_mix(drop_key(d, kDropAttn), drop_node(d, row)); k.rb = row_ptr[row]; k.ke = edge_row_key(d, row);
 }
+// edge features (gatv2_abi.h "edge features"): row j of a [n_edges][HD] fp32 array at the lane's channel(s).  The array is E*H*D*4 bytes
+// (as large as the message array): 64-bit row base.  PE[j] is a streamed read at a CSR-contiguous address next to the PL[src] gather
+// (callers clamp j the way they clamp the edge index, so the load needs no predicate); gPE[j] is written once and never read back here.
+__device__ __forceinline__ float pe_load(const float* __restrict__ pe, int j, int HD, int c) { return pe[(int64_t)j * HD + c]; }
 // kernel argument: the forward's EXT instantiations take the plain struct + EdgeFwdExtras (masks and / or residual, bias, norm), the
 // backward's DROP instantiations the plain struct + the mask parameters; the default ones keep the plain struct
 template <bool EXT> struct FwdArgsOf { typedef EdgeFwdArgs T; };
@@ -272,7 +276,7 @@ __device__ __forceinline__ float res_term(const EdgeFwdExtras& X, int64_t row, i
     return r;
 }
 
-template <int HD, int D, int UU, int USC, bool ALPHA, bool BF, bool EXT = false, class AT = EdgeFwdArgs>
+template <int HD, int D, int UU, int USC, bool ALPHA, bool BF, bool EXT = false, bool PE = false, class AT = EdgeFwdArgs>
 __device__ __forceinline__ void fwd_chunk(const AT& A, int e0, int e_end, int e_end_v, int c, int gidx,
                                           float pr, float ac2, bool multi, float (&sc)[USC], float& m, float& Z,
                                           float& acc, uint32_t kd = 0, int rb = 0, uint32_t ke = 0, int64_t row = 0) {
@@ -280,19 +284,25 @@ __device__ __forceinline__ void fwd_chunk(const AT& A, int e0, int e_end, int e_
     constexpr int H = HD / D;
     float v[UU];
     [[maybe_unused]] bool ek[UU];                    // DropEdge: the edge is kept (one draw per edge, all heads)
+    [[maybe_unused]] float pev[UU];                  // PE[j] of the lane's channel
 #pragma unroll
     for (int u = 0; u < UU; ++u) {
         const int j = e0 + u * G + gidx;
         const int jc = j < e_end ? j : e_end - 1;
         const int src = A.col_idx[jc];
         v[u] = gather_row<HD, BF>(A.PL, src, c);
+        if constexpr (PE) pev[u] = pe_load(A.x.pe, jc, HD, c);
         if constexpr (EXT) ek[u] = drop_edge_kept(A.x.drop, ke, jc - rb, src, row);
     }
     // scores: the cross-lane stages run slot-interleaved (UU independent DPP chains), so that no
     // stage waits on the VALU->DPP hazard of its own predecessor
     float t[UU];
 #pragma unroll
-    for (int u = 0; u < UU; ++u) { const float s = v[u] + pr; t[u] = ac2 * fmaxf(s, s * A.slope); }
+    for (int u = 0; u < UU; ++u) {
+        float s = v[u] + pr;
+        if constexpr (PE) s += pev[u];               // the edge term: in the score only, the message stays PL[src]
+        t[u] = ac2 * fmaxf(s, s * A.slope);
+    }
     group_sum_n<D, UU>(t);
     float cm = -INFINITY;
 #pragma unroll
@@ -330,8 +340,10 @@ __device__ __forceinline__ void fwd_chunk(const AT& A, int e0, int e_end, int e_
 
 // ALPHA: also materialise attn_coeff [E][H] (parity taps only; the training path never needs it).
 // EXT: the extended argument struct (EdgeFwdExtras: masks and / or residual, bias, norm); every edge is hashed
-template <int HD, int D, bool ALPHA, bool BF = false, bool EXT = false>
+// PE (with EXT): the score takes the edge term A.x.pe[j]
+template <int HD, int D, bool ALPHA, bool BF = false, bool EXT = false, bool PE = false>
 __global__ __launch_bounds__(256) void edge_fwd_kernel(FwdArgsT<EXT> A) {
+    static_assert(EXT || !PE, "the edge term travels in the extended argument struct");
     constexpr int G = 64 / HD;      // edges per wave-instruction
     constexpr int U = 16 / G;       // gathers in flight per group
     constexpr int CH = 16;          // edges per chunk (= U*G)
@@ -359,10 +371,10 @@ __global__ __launch_bounds__(256) void edge_fwd_kernel(FwdArgsT<EXT> A) {
 
     for (int e0 = b; e0 < e_end; e0 += CH) {
         if constexpr (U >= 2) {
-            if (e_end - e0 <= CH / 2) fwd_chunk<HD, D, U / 2, U, ALPHA, BF, EXT>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, k.kd, k.rb, k.ke, row);
-            else fwd_chunk<HD, D, U, U, ALPHA, BF, EXT>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, k.kd, k.rb, k.ke, row);
+            if (e_end - e0 <= CH / 2) fwd_chunk<HD, D, U / 2, U, ALPHA, BF, EXT, PE>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, k.kd, k.rb, k.ke, row);
+            else fwd_chunk<HD, D, U, U, ALPHA, BF, EXT, PE>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, k.kd, k.rb, k.ke, row);
         } else {
-            fwd_chunk<HD, D, U, U, ALPHA, BF, EXT>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, k.kd, k.rb, k.ke, row);
+            fwd_chunk<HD, D, U, U, ALPHA, BF, EXT, PE>(A, e0, e_end, e_end_v, c, gidx, pr, ac2, multi, sc, m, Z, acc, k.kd, k.rb, k.ke, row);
         }
     }
 
@@ -464,7 +476,7 @@ __global__ __launch_bounds__(256) void edge_fwd_fix_kernel(FwdArgsT<EXT> A) {
 //   grad_a += ge LReLU(s)   gPR[dst] += gs   gPL[src] += g alpha + gs   (E:769-782, 859-869)
 // STORE: message row -> its CSC slot (summed per source by gpl_sum_kernel); else float atomics.
 // ------------------------------------------------------------------------------------------------
-template <int HD, int D, int UU, bool STORE, bool TAPS, int DBG, bool BF, bool DROP = false, class AT = EdgeBwdArgs>
+template <int HD, int D, int UU, bool STORE, bool TAPS, int DBG, bool BF, bool DROP = false, bool PE = false, class AT = EdgeBwdArgs>
 __device__ __forceinline__ void bwd_chunk(const AT& A, int e0, int e_end, int e_end_v, int c, int gidx,
                                           float g, float pr, float dot, float ac, float ac2, float m2, float inv,
                                           float& ga, float& gpr, uint32_t kd = 0, int rb = 0, uint32_t ke = 0, int64_t row = 0) {
@@ -473,12 +485,14 @@ __device__ __forceinline__ void bwd_chunk(const AT& A, int e0, int e_end, int e_
     float v[UU];
     int sid[UU];            // gPL row (atomics path) or message slot (store path)
     [[maybe_unused]] bool ek[UU];                                // DropEdge: the edge is kept
+    [[maybe_unused]] float pev[UU];                              // PE[j] of the lane's channel
 #pragma unroll
     for (int u = 0; u < UU; ++u) {
         const int j = e0 + u * G + gidx;
         const int jc = j < e_end ? j : e_end - 1;                // clamped: loads need no predicate
         const int src = A.col_idx[jc];
         v[u] = gather_row<HD, BF>(A.PL, src, c);
+        if constexpr (PE) pev[u] = pe_load(A.pe, jc, HD, c);
         if constexpr (DROP) ek[u] = drop_edge_kept(A.drop, ke, jc - rb, src, row);
         if constexpr (STORE) sid[u] = (DBG == 2) ? jc : A.pos[jc]; else sid[u] = src;
     }
@@ -491,7 +505,11 @@ __device__ __forceinline__ void bwd_chunk(const AT& A, int e0, int e_end, int e_
     for (int p0 = 0; p0 < UU; p0 += P) {
         float al[P], ga_[P];
 #pragma unroll
-        for (int q = 0; q < P; ++q) { const float s = v[p0 + q] + pr; al[q] = ac2 * fmaxf(s, s * A.slope); }
+        for (int q = 0; q < P; ++q) {
+            float s = v[p0 + q] + pr;
+            if constexpr (PE) s += pev[p0 + q];
+            al[q] = ac2 * fmaxf(s, s * A.slope);
+        }
         group_sum_n<D, P>(al);
 #pragma unroll
         for (int q = 0; q < P; ++q) { al[q] = exp2_fast(al[q] - m2) * inv; ga_[q] = g * v[p0 + q]; }
@@ -509,11 +527,13 @@ __device__ __forceinline__ void bwd_chunk(const AT& A, int e0, int e_end, int e_
             bool valid = inr;
             if constexpr (DROP) valid = inr && ek[u];                // a dropped edge: ge = alpha = 0 by selection, a zero message row
             const float ge = valid ? al[q] * (ga_[q] - dot) : 0.f;   // padded slots contribute nothing
-            const float s = v[u] + pr;
+            float s = v[u] + pr;
+            if constexpr (PE) s += pev[u];
             const bool pos = s > 0.f;
             const float gs = ge * ac * (pos ? 1.0f : A.slope);
             ga = fmaf(ge, fmaxf(s, s * A.slope), ga);
             gpr += gs;
+            if constexpr (PE) { if (inr) A.gpe[(int64_t)j * HD + c] = gs; }     // dL/dPE[j]: zeros at a dropped edge (ge = 0 by selection)
             float alm = al[q];
             if constexpr (DROP) alm = valid ? al[q] * kf[q] : 0.f;
             const float msg = fmaf(g, alm, gs);                      // d/dPL[src] from this edge
@@ -531,8 +551,9 @@ __device__ __forceinline__ void bwd_chunk(const AT& A, int e0, int e_end, int e_
     }
 }
 
-template <int HD, int D, bool STORE, bool TAPS, int DBG = 0, bool BF = false, bool DROP = false>
+template <int HD, int D, bool STORE, bool TAPS, int DBG = 0, bool BF = false, bool DROP = false, bool PE = false>
 __global__ __launch_bounds__(256) void edge_bwd_kernel(BwdArgsT<DROP> A) {
+    static_assert(DROP || !PE, "the edge term travels in the extended argument struct");
     constexpr int G = 64 / HD;
     constexpr int U = 16 / G;
     constexpr int CH = 16;
@@ -566,10 +587,10 @@ __global__ __launch_bounds__(256) void edge_bwd_kernel(BwdArgsT<DROP> A) {
         if constexpr (DROP) { k.kd = drop_mix(drop_key(A.drop, kDropAttn), drop_node(A.drop, row)); k.rb = A.row_ptr[row]; k.ke = edge_row_key(A.drop, row); }
         for (int e0 = b; e0 < e_end; e0 += CH) {
             if constexpr (U >= 2) {
-                if (e_end - e0 <= CH / 2) bwd_chunk<HD, D, U / 2, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
-                else bwd_chunk<HD, D, U, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
+                if (e_end - e0 <= CH / 2) bwd_chunk<HD, D, U / 2, STORE, TAPS, DBG, BF, DROP, PE>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
+                else bwd_chunk<HD, D, U, STORE, TAPS, DBG, BF, DROP, PE>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
             } else {
-                bwd_chunk<HD, D, U, STORE, TAPS, DBG, BF, DROP>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
+                bwd_chunk<HD, D, U, STORE, TAPS, DBG, BF, DROP, PE>(A, e0, e_end, e_end_v, c, gidx, g, pr, dot, ac, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
             }
         }
 #pragma unroll
@@ -681,6 +702,16 @@ __device__ __forceinline__ void store_row_n(float* __restrict__ msg, int slot, i
     }
 }
 
+// the N-channel form of pe_load, and the streamed store of a gPE row (j inside the item: the caller's predicate)
+template <int N>
+__device__ __forceinline__ vnf<N> pe_load_n(const float* __restrict__ pe, int j, int HD, int c) {
+    return *reinterpret_cast<const vnf<N>*>(pe + (int64_t)j * HD + c);
+}
+template <int N>
+__device__ __forceinline__ void gpe_store_n(float* __restrict__ gpe, int j, int HD, int c, vnf<N> gs) {
+    stream_store(reinterpret_cast<vnf<N>*>(gpe + (int64_t)j * HD + c), gs);
+}
+
 // Forward edge pass in the packed layout (training path: alpha not materialised).  Same online softmax as
 // fwd_chunk; partials of split rows go to the same [slot][HD] / [slot][2H] arrays, so edge_fwd_fix_kernel
 // finishes them unchanged.
@@ -706,22 +737,28 @@ __device__ __forceinline__ vnf<N> ln_row_n(vnf<N> u, const LnArgs& ln, int c) {
     return v;
 }
 
-template <int HD, int D, int N, int UU, bool BF, bool EXT = false, class AT = EdgeFwdArgs>
+template <int HD, int D, int N, int UU, bool BF, bool EXT = false, bool PE = false, class AT = EdgeFwdArgs>
 __device__ __forceinline__ void fwd2_chunk(const AT& A, int e0, int e_end_v, int cp, int gidx, int srcv,
                                            vnf<N> pr, vnf<N> ac2, float& m, float& Z, vnf<N>& acc, uint32_t kd = 0, int rb = 0,
                                            uint32_t ke = 0, int64_t row = 0) {
     constexpr int LPE = HD / N, G = 64 / LPE, DL = D / N;
     vnf<N> v[UU];
     [[maybe_unused]] bool ek[UU];                    // DropEdge: the edge is kept
+    [[maybe_unused]] vnf<N> pev[UU];                 // PE[j] of the lane's channels (j clamped into the item, like the edge index)
 #pragma unroll
     for (int u = 0; u < UU; ++u) {
         const int src = __shfl(srcv, u * G + gidx);
         v[u] = gather_row_n<HD, N, BF>(A.PL, src, cp);
+        if constexpr (PE) { const int j = e0 + u * G + gidx; pev[u] = pe_load_n<N>(A.x.pe, j < e_end_v ? j : e_end_v - 1, HD, N * cp); }
         if constexpr (EXT) ek[u] = drop_edge_kept(A.x.drop, ke, e0 + u * G + gidx - rb, src, row);
     }
     float t[UU];
 #pragma unroll
-    for (int u = 0; u < UU; ++u) t[u] = hsum<N>(ac2 * lrelu_n<N>(v[u] + pr, A.slope));
+    for (int u = 0; u < UU; ++u) {
+        vnf<N> s = v[u] + pr;
+        if constexpr (PE) s += pev[u];               // the edge term: in the score only, the message stays PL[src]
+        t[u] = hsum<N>(ac2 * lrelu_n<N>(s, A.slope));
+    }
     group_sum_n<DL, UU>(t);
     float cm = -INFINITY;
 #pragma unroll
@@ -746,8 +783,9 @@ __device__ __forceinline__ void fwd2_chunk(const AT& A, int e0, int e_end_v, int
     m = mn;
 }
 
-template <int HD, int D, int N, bool BF = false, bool EXT = false>
+template <int HD, int D, int N, bool BF = false, bool EXT = false, bool PE = false>
 __global__ __launch_bounds__(256) void edge_fwd2_kernel(FwdArgsT<EXT> A) {
+    static_assert(EXT || !PE, "the edge term travels in the extended argument struct");
     constexpr int LPE = HD / N, G = 64 / LPE, DL = D / N, H = HD / D;
     constexpr int CH = 16;
     constexpr int U = CH / G;
@@ -777,10 +815,10 @@ __global__ __launch_bounds__(256) void edge_fwd2_kernel(FwdArgsT<EXT> A) {
     for (int e0 = b; e0 < e_end; e0 += CH) {
         const int srcn = (e0 + CH < e_end) ? load_idx(e0 + CH) : 0;
         if constexpr (U >= 2) {
-            if (e_end - e0 <= CH / 2) fwd2_chunk<HD, D, N, U / 2, BF, EXT>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, k.kd, k.rb, k.ke, row);
-            else fwd2_chunk<HD, D, N, U, BF, EXT>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, k.kd, k.rb, k.ke, row);
+            if (e_end - e0 <= CH / 2) fwd2_chunk<HD, D, N, U / 2, BF, EXT, PE>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, k.kd, k.rb, k.ke, row);
+            else fwd2_chunk<HD, D, N, U, BF, EXT, PE>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, k.kd, k.rb, k.ke, row);
         } else {
-            fwd2_chunk<HD, D, N, U, BF, EXT>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, k.kd, k.rb, k.ke, row);
+            fwd2_chunk<HD, D, N, U, BF, EXT, PE>(A, e0, e_end_v, cp, gidx, srcv, pr, ac2, m, Z, acc, k.kd, k.rb, k.ke, row);
         }
         srcv = srcn;
     }
@@ -841,8 +879,9 @@ __device__ __forceinline__ int wave_max_over_groups(int v) {
     return __builtin_amdgcn_readfirstlane(v);
 }
 
-template <int HD, int D, int N, bool BF = false, bool EXT = false>
+template <int HD, int D, int N, bool BF = false, bool EXT = false, bool PE = false>
 __global__ __launch_bounds__(256) void edge_fwd3_kernel(FwdArgsT<EXT> A) {
+    static_assert(EXT || !PE, "the edge term travels in the extended argument struct");
     constexpr int LPE = HD / N, G = 64 / LPE, DL = D / N, H = HD / D;
     constexpr int U = 4;                             // edges per group and step: G*U gathers in flight per wave
     static_assert(D % N == 0 && LPE >= U, "lane layout");
@@ -873,15 +912,25 @@ __global__ __launch_bounds__(256) void edge_fwd3_kernel(FwdArgsT<EXT> A) {
         const int srcn = load_idx(st + 1);           // next step's indices: in flight during this one
         vnf<N> v[U];
         [[maybe_unused]] bool ek[U];                 // DropEdge: the edge is kept (lane masks; the hash runs under the gathers' latency)
+        [[maybe_unused]] vnf<N> pev[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int src = __shfl(srcv, gidx * LPE + u);
             v[u] = gather_row_n<HD, N, BF>(A.PL, src, cp);
+            if constexpr (PE) {                      // PE[j]: a row load at a CSR-contiguous address, j clamped like the edge index
+                int j = b + st * U + u;
+                j = j < e ? j : e - 1;
+                pev[u] = pe_load_n<N>(A.x.pe, j > 0 ? j : 0, HD, c);
+            }
             if constexpr (EXT) ek[u] = drop_edge_kept(A.x.drop, k.ke, b + st * U + u - k.rb, src, rowc);
         }
         float t[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) t[u] = hsum<N>(ac2 * lrelu_n<N>(v[u] + pr, A.slope));
+        for (int u = 0; u < U; ++u) {
+            vnf<N> s = v[u] + pr;
+            if constexpr (PE) s += pev[u];           // the edge term: in the score only, the message stays PL[src]
+            t[u] = hsum<N>(ac2 * lrelu_n<N>(s, A.slope));
+        }
         group_sum_n<DL, U>(t);
         float cm = -INFINITY;
 #pragma unroll
@@ -933,7 +982,7 @@ __global__ __launch_bounds__(256) void edge_fwd3_kernel(FwdArgsT<EXT> A) {
 // STASH (see edge_bwd2_kernel): instead of the H*D-float message row an edge leaves a record of H*D/N words in its
 // source-major slot — per head alpha and grad_attn_score, with the N LeakyReLU' decisions of the lane's channels in
 // the N low mantissa bits of the word (value rounded to nearest at that precision: relative 2^-(24-N)).
-template <int HD, int D, int N, int UU, int DBG, bool BF, bool STASH, bool DROP = false, class AT = EdgeBwdArgs>
+template <int HD, int D, int N, int UU, int DBG, bool BF, bool STASH, bool DROP = false, bool PE = false, class AT = EdgeBwdArgs>
 __device__ __forceinline__ void bwd2_chunk(const AT& A, int e0, int e_end, int e_end_v, int cp, int gidx,
                                            int srcv, int posv, vnf<N> g, vnf<N> pr, float dot, vnf<N> ac, vnf<N> acs,
                                            vnf<N> ac2, float m2, float inv, vnf<N>& ga, vnf<N>& gpr, uint32_t kd = 0, int rb = 0,
@@ -947,10 +996,12 @@ __device__ __forceinline__ void bwd2_chunk(const AT& A, int e0, int e_end, int e
     // with ONE coalesced load each), handed to the owning lanes through the LDS crossbar: per-lane index loads
     // would put a second memory latency in front of every gather
     [[maybe_unused]] bool ek[UU];       // DropEdge: the edge is kept
+    [[maybe_unused]] vnf<N> pev[UU];    // PE[j] of the lane's channels (j clamped into the item, like the edge index)
 #pragma unroll
     for (int u = 0; u < UU; ++u) {
         const int src = __shfl(srcv, u * G + gidx);
         v[u] = gather_row_n<HD, N, BF>(A.PL, src, cp);
+        if constexpr (PE) { const int j = e0 + u * G + gidx; pev[u] = pe_load_n<N>(A.pe, j < e_end ? j : e_end - 1, HD, N * cp); }
         if constexpr (DROP) ek[u] = drop_edge_kept(A.drop, ke, e0 + u * G + gidx - rb, src, row);
         if constexpr (!STASH) sid[u] = __shfl(posv, u * G + gidx);     // STASH: fetched at the store (16 fewer live VGPRs: 4 waves/SIMD)
     }
@@ -965,7 +1016,11 @@ __device__ __forceinline__ void bwd2_chunk(const AT& A, int e0, int e_end, int e
             for (int q = 0; q < P; ++q) slots[q] = DBG == 2 ? (uint32_t)(e0 + (p0 + q) * G + gidx) : (uint32_t)__shfl(posv, (p0 + q) * G + gidx);
         }
 #pragma unroll
-        for (int q = 0; q < P; ++q) al[q] = hsum<N>(ac2 * lrelu_n<N>(v[p0 + q] + pr, A.slope));
+        for (int q = 0; q < P; ++q) {
+            vnf<N> s = v[p0 + q] + pr;
+            if constexpr (PE) s += pev[p0 + q];
+            al[q] = hsum<N>(ac2 * lrelu_n<N>(s, A.slope));
+        }
         group_sum_n<DL, P>(al);
 #pragma unroll
         for (int q = 0; q < P; ++q) {
@@ -986,10 +1041,12 @@ __device__ __forceinline__ void bwd2_chunk(const AT& A, int e0, int e_end, int e
             bool valid = inr;
             if constexpr (DROP) valid = inr && ek[u];                // a dropped edge: ge = alpha = 0 by selection, a zero record / row
             const float ge = valid ? al[q] * (ga_[q] - dot) : 0.f;   // padded slots contribute nothing
-            const vnf<N> s = v[u] + pr;
+            vnf<N> s = v[u] + pr;
+            if constexpr (PE) s += pev[u];
             const vnf<N> gs = ge * select_pos<N>(s, ac, acs);        // ge * a * LReLU'(s)
             ga += ge * lrelu_n<N>(s, A.slope);
             gpr += gs;
+            if constexpr (PE) { if (inr) gpe_store_n<N>(A.gpe, j, HD, N * cp, gs); }     // dL/dPE[j]: zeros at a dropped edge
             if constexpr (DROP) al[q] = valid ? al[q] * kf[q] : 0.f;
             if constexpr (STASH) {
                 static_assert(D / N == 2, "stash records: two lanes per head (one carries alpha, the other ge)");
@@ -1014,7 +1071,7 @@ __device__ __forceinline__ void bwd2_chunk(const AT& A, int e0, int e_end, int e
 // per-edge record is H*D/N words (64 B at H*D = 64) instead of the H*D*4-byte message row, and gpl_pull_kernel
 // (gat_csc.hip) rebuilds each message from the record and ONE gathered row of g[dst] while it sums per source.
 // This kernel then also writes g[row] (dL/dh_pre with the LeakyReLU' factor applied) for that gather.
-template <int HD, int D, int N, int DBG, bool BF, bool STASH, bool DROP = false, class AT = EdgeBwdArgs>
+template <int HD, int D, int N, int DBG, bool BF, bool STASH, bool DROP = false, bool PE = false, class AT = EdgeBwdArgs>
 __device__ __forceinline__ void edge_bwd2_body(const AT& A) {
     constexpr int LPE = HD / N, G = 64 / LPE, DL = D / N, H = HD / D;
     constexpr int U = 16 / G;
@@ -1079,10 +1136,10 @@ __device__ __forceinline__ void edge_bwd2_body(const AT& A) {
             int srcn = 0, posn = 0;
             if (e0 + CH < e_end) load_idx(e0 + CH, srcn, posn);      // next chunk's indices: in flight during this one
             if constexpr (U >= 2) {
-                if (e_end - e0 <= CH / 2) bwd2_chunk<HD, D, N, U / 2, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
-                else bwd2_chunk<HD, D, N, U, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
+                if (e_end - e0 <= CH / 2) bwd2_chunk<HD, D, N, U / 2, DBG, BF, STASH, DROP, PE>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
+                else bwd2_chunk<HD, D, N, U, DBG, BF, STASH, DROP, PE>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
             } else {
-                bwd2_chunk<HD, D, N, U, DBG, BF, STASH, DROP>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
+                bwd2_chunk<HD, D, N, U, DBG, BF, STASH, DROP, PE>(A, e0, e_end, e_end_v, cp, gidx, srcv, posv, g, pr, dot, ac, acs, ac2, m2, inv, ga, gpr, k.kd, k.rb, k.ke, row);
             }
             srcv = srcn; posv = posn;
         }
@@ -1105,8 +1162,11 @@ __device__ __forceinline__ void edge_bwd2_body(const AT& A) {
             (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
-template <int HD, int D, int N, int DBG = 0, bool BF = false, bool STASH = false, bool DROP = false>
-__global__ __launch_bounds__(256) void edge_bwd2_kernel(BwdArgsT<DROP> A) { edge_bwd2_body<HD, D, N, DBG, BF, STASH, DROP>(A); }
+template <int HD, int D, int N, int DBG = 0, bool BF = false, bool STASH = false, bool DROP = false, bool PE = false>
+__global__ __launch_bounds__(256) void edge_bwd2_kernel(BwdArgsT<DROP> A) {
+    static_assert(DROP || !PE, "the edge term travels in the extended argument struct");
+    edge_bwd2_body<HD, D, N, DBG, BF, STASH, DROP, PE>(A);
+}
 // The stash variant sits a few registers above 128 VGPRs when left alone (3 waves/SIMD); it is told to fit 4 waves.
 template <int HD, int D, int N, int DBG = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void edge_bwd2s_kernel(EdgeBwdArgs A) {
@@ -1120,8 +1180,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 // of a record, nothing is written for the pull pass (no gfull / decision bytes), any D/N lanes per head.
 // DROP: the mask hash does not fit the 128-VGPR budget of 4 waves / SIMD without spilling (measured: 36-80 B/lane of scratch at
 // N = 4); the attention-dropout instantiations are allowed 3 waves / SIMD instead.
-template <int HD, int D, int N, int DBG = 0, bool BF = false, bool MSG = false, bool DROP = false>
+// PE (with DROP): s takes the edge term A.pe[j] in the score recomputation and in the LReLU / LReLU' terms alike, and gs is streamed to
+// A.gpe[j] for the edges inside the item (no spare row: padded lanes do not write).  The PE rows of a step are loaded next to its
+// gathers; gs goes out in the step that forms it.
+template <int HD, int D, int N, int DBG = 0, bool BF = false, bool MSG = false, bool DROP = false, bool PE = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DROP ? 3 : 4, 8))) void edge_bwd3_kernel(BwdArgsT<DROP> A) {
+    static_assert(DROP || !PE, "the edge term travels in the extended argument struct");
     constexpr int LPE = HD / N, G = 64 / LPE, DL = D / N, H = HD / D;
     constexpr int U = 4;
     static_assert((MSG || DL == 2) && LPE >= U, "records: two lanes per head (one carries alpha, the other ge)");
@@ -1246,6 +1310,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DROP ? 3 : 
             vnf<N> v[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) v[u] = gather_row_n<HD, N, BF>(A.PL, src[u], cp);
+            [[maybe_unused]] vnf<N> pev[U];          // PE[j], j clamped into the item like the edge index
+            if constexpr (PE) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    int j = b + st * U + u;
+                    j = j < e ? j : e - 1;
+                    pev[u] = pe_load_n<N>(A.pe, j > 0 ? j : 0, HD, c);
+                }
+            }
             // DropEdge: the step's keep decisions (lane masks), drawn under the gathers' latency and before src[] moves on
             [[maybe_unused]] bool ek[U];
             if constexpr (DROP) {
@@ -1271,7 +1344,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DROP ? 3 : 
             load_idx(st + 2, srcn, posn);
             float al[U], ga_[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) al[u] = hsum<N>(ac2 * lrelu_n<N>(v[u] + pr, A.slope));
+            for (int u = 0; u < U; ++u) {
+                vnf<N> s = v[u] + pr;
+                if constexpr (PE) s += pev[u];
+                al[u] = hsum<N>(ac2 * lrelu_n<N>(s, A.slope));
+            }
             group_sum_n<DL, U>(al);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -1294,10 +1371,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DROP ? 3 : 
                 bool valid = b + st * U + u < e;
                 if constexpr (DROP) valid = valid && ek[u];              // a dropped edge: ge = alpha = 0 by selection, a zero record / row
                 const float ge = valid ? al[u] * (ga_[u] - dot) : 0.f;   // padded slots contribute nothing
-                const vnf<N> s = v[u] + pr;
+                vnf<N> s = v[u] + pr;
+                if constexpr (PE) s += pev[u];
                 const vnf<N> gs = ge * select_pos<N>(s, ac, acs);        // ge * a * LReLU'(s)
                 ga += ge * lrelu_n<N>(s, A.slope);
                 gpr += gs;
+                if constexpr (PE) { if (b + st * U + u < e) gpe_store_n<N>(A.gpe, b + st * U + u, HD, c, gs); }   // dL/dPE[j]: zeros at a dropped edge
                 if constexpr (DROP) al[u] = kp[u] ? al[u] * A.drop.scale : 0.f;   // kp includes the edge's own keep
                 if constexpr (MSG) {
                     pend_m[u] = g * al[u] + gs;                          // d/dPL[src] from this edge (E:859-869)
@@ -1833,7 +1912,8 @@ __global__ __launch_bounds__(256) void edge_bwd_fix_kernel(const int4* __restric
 // RES: res / bias (either may be null) join the row's sum before h_pre is written (gatv2_abi.h "residual")
 // and, with ln.gamma, the row u is parked in LDS, normalised over its H*D channels (lane-strided sums in ascending order, then the
 // wave's butterfly) and hout = LReLU(v) (gatv2_abi.h "layer normalisation")
-template <bool RES>
+// PE: the score takes the edge term X.pe[e] (gatv2_abi.h "edge features")
+template <bool RES, bool PE = false>
 __device__ __forceinline__ void edge_fwd_generic_body(const EdgeFwdArgs& A, const EdgeFwdExtras& X) {
     const DropArgs& dr = X.drop;
     [[maybe_unused]] const float* __restrict__ res = X.res;
@@ -1861,7 +1941,9 @@ __device__ __forceinline__ void edge_fwd_generic_body(const EdgeFwdArgs& A, cons
                 float s = 0.f;
                 for (int k = 0; k < D; ++k) {
                     const int ch = h * D + k;
-                    s += A.a[ch] * lrelu(A.PL[sid * HD + ch] + A.PR[row * HD + ch], slope);
+                    float sc = A.PL[sid * HD + ch] + A.PR[row * HD + ch];
+                    if constexpr (PE) sc += X.pe[(int64_t)e * HD + ch];
+                    s += A.a[ch] * lrelu(sc, slope);
                 }
                 A.alpha[(int64_t)e * H + h] = s;
                 if (A.score != nullptr) A.score[(int64_t)e * H + h] = s;
@@ -1923,8 +2005,12 @@ __device__ __forceinline__ void edge_fwd_generic_body(const EdgeFwdArgs& A, cons
 }
 __global__ __launch_bounds__(64) void edge_fwd_generic(EdgeFwdArgs A, EdgeFwdExtras X) { edge_fwd_generic_body<false>(A, X); }
 __global__ __launch_bounds__(64) void edge_fwd_generic_res(EdgeFwdArgs A, EdgeFwdExtras X) { edge_fwd_generic_body<true>(A, X); }
+__global__ __launch_bounds__(64) void edge_fwd_generic_pe(EdgeFwdArgs A, EdgeFwdExtras X) { edge_fwd_generic_body<true, true>(A, X); }
 
-__global__ __launch_bounds__(64) void edge_bwd_generic(EdgeBwdArgs A, DropArgs dr) {
+// PE: s takes the edge term pe[e]; gs of every edge goes to gpe[e] (zeros at a dropped edge)
+template <bool PE>
+__device__ __forceinline__ void edge_bwd_generic_body(const EdgeBwdArgs& A, const DropArgs& dr, [[maybe_unused]] const float* __restrict__ pe,
+                                                      [[maybe_unused]] float* __restrict__ gpe) {
     extern __shared__ float lds[];
     const int H = A.H, D = A.D, HD = H * D;
     float* s_dot = lds;
@@ -1960,6 +2046,7 @@ __global__ __launch_bounds__(64) void edge_bwd_generic(EdgeBwdArgs A, DropArgs d
                     if (A.ge != nullptr) A.ge[(int64_t)e * H + h] = 0.f;
                     if (A.galpha != nullptr) A.galpha[(int64_t)e * H + h] = 0.f;
                 }
+                if constexpr (PE) { for (int ch = lane; ch < HD; ch += 64) gpe[(int64_t)e * HD + ch] = 0.f; }
                 continue;
             }
             for (int h = lane; h < H; h += 64) {
@@ -1977,12 +2064,14 @@ __global__ __launch_bounds__(64) void edge_bwd_generic(EdgeBwdArgs A, DropArgs d
             __syncthreads();
             for (int ch = lane; ch < HD; ch += 64) {
                 const float v = A.PL[sid * HD + ch];
-                const float s = v + A.PR[row * HD + ch];
+                float s = v + A.PR[row * HD + ch];
+                if constexpr (PE) s += pe[(int64_t)e * HD + ch];
                 const bool pos = s > 0.f;
                 const float ge = s_ge[ch / D];
                 const float gs = ge * A.a[ch] * (pos ? 1.0f : slope);
                 s_ga[ch] += ge * (pos ? s : s * slope);
                 s_gpr[ch] += gs;
+                if constexpr (PE) gpe[(int64_t)e * HD + ch] = gs;
                 unsafeAtomicAdd(A.gPL + sid * HD + ch, gval(row * HD + ch) * s_al[ch / D] + gs);
             }
             __syncthreads();
@@ -1991,6 +2080,10 @@ __global__ __launch_bounds__(64) void edge_bwd_generic(EdgeBwdArgs A, DropArgs d
         __syncthreads();
     }
     for (int ch = lane; ch < HD; ch += 64) A.ga_partial[(int64_t)blockIdx.x * HD + ch] = s_ga[ch];
+}
+__global__ __launch_bounds__(64) void edge_bwd_generic(EdgeBwdArgs A, DropArgs dr) { edge_bwd_generic_body<false>(A, dr, nullptr, nullptr); }
+__global__ __launch_bounds__(64) void edge_bwd_generic_pe(EdgeBwdArgs A, DropArgs dr, const float* pe, float* gpe) {
+    edge_bwd_generic_body<true>(A, dr, pe, gpe);
 }
 
 // [A][B] -> [B][A] elementwise transposes for taps (small / test-only traffic)
@@ -2066,16 +2159,22 @@ struct EdgePick {
 // packed wave-per-row kernel.  The A/B switches of the default path (GAT_ROWGROUP, GAT_PACKED, GAT_CPL, GAT_FWD_WAVES) do not apply to
 // it: only these instantiations exist.
 // res (residual, bias or norm, always with ext): the fix-up kernel is the EXT form too — the masks alone leave it the plain one.
+// pe (edge features, always with ext): the PE instantiation of the same kernel; the fix-up kernels never see the edge term.
 template <int HD, int D, bool BF>
-EdgePick pick_fwd(const EdgeFwdArgs& a, bool ext, bool res) {
+EdgePick pick_fwd(const EdgeFwdArgs& a, bool ext, bool res, bool pe) {
     static_assert(D % 2 == 0, "every fast-path shape has an even D");
     constexpr int N3 = stash_n<HD, D>(), N2 = (HD >= 32 && D % 4 == 0) ? 4 : 2;
     constexpr int G3 = N3 != 0 ? 64 / (HD / (N3 != 0 ? N3 : 1)) : 1;             // rows per wave of the group-per-row kernel
     if (a.alpha != nullptr) {                                                     // parity-tap form: alpha (and scores) materialised
         const void* fix = res ? GAT_K(edge_fwd_fix_kernel<HD, D, true, true>) : GAT_K(edge_fwd_fix_kernel<HD, D, true>);
+        if (pe) return {GAT_K(edge_fwd_kernel<HD, D, true, BF, true, true>), 256, 4, fix};
         return {ext ? GAT_K(edge_fwd_kernel<HD, D, true, BF, true>) : GAT_K(edge_fwd_kernel<HD, D, true, BF>), 256, 4, fix};
     }
     const void* fix = res ? GAT_K(edge_fwd_fix_kernel<HD, D, false, true>) : GAT_K(edge_fwd_fix_kernel<HD, D, false>);
+    if (pe) {
+        if constexpr (N3 != 0) return {GAT_K(edge_fwd3_kernel<HD, D, N3, BF, true, true>), 64, G3, fix};
+        else return {GAT_K(edge_fwd2_kernel<HD, D, N2, BF, true, true>), 64, 1, fix};
+    }
     if (ext) {
         if constexpr (N3 != 0) return {GAT_K(edge_fwd3_kernel<HD, D, N3, BF, true>), 64, G3, fix};
         else return {GAT_K(edge_fwd2_kernel<HD, D, N2, BF, true>), 64, 1, fix};
@@ -2105,12 +2204,18 @@ const void* bwd3_dbg(int dbg) {
 // stash: per-edge records + pull pass instead of message rows.  Attention dropout / DropEdge (drop) exist for the store path only,
 // as the DROP instantiation of the kernel the default settings pick; the A/B switches do not apply to them.
 // dbg (experiment library only, GAT_DBG): timing variants, most with WRONG results; 0 = the product kernel of the selection.
+// pe (edge features, always with drop): the PE instantiation of the same DROP kernel.
 template <int HD, int D, bool BF>
-EdgePick pick_bwd(const EdgeBwdArgs& a, bool drop, int dbg) {
+EdgePick pick_bwd(const EdgeBwdArgs& a, bool drop, int dbg, bool pe) {
     constexpr int N3 = stash_n<HD, D>(), N2 = (HD >= 32 && D % 4 == 0) ? 4 : 2;
     const bool store = a.pos != nullptr && a.msg != nullptr, taps = a.ge != nullptr, stash = a.stash != nullptr && !taps;
     if (drop) {
         if (!store) return {};
+        if (pe) {
+            if (taps) return {GAT_K(edge_bwd_kernel<HD, D, true, true, 0, BF, true, true>)};
+            if constexpr (N3 != 0) return {stash ? GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, false, true, true>) : GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, true, true, true>)};
+            else return {GAT_K(edge_bwd2_kernel<HD, D, N2, 0, BF, false, true, true>)};
+        }
         if (taps) return {GAT_K(edge_bwd_kernel<HD, D, true, true, 0, BF, true>)};
         if constexpr (N3 != 0) return {stash ? GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, false, true>) : GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, true, true>)};
         else return {GAT_K(edge_bwd2_kernel<HD, D, N2, 0, BF, false, true>)};
@@ -2165,12 +2270,12 @@ EdgePick pick_bwd(const EdgeBwdArgs& a, bool drop, int dbg) {
 #define GAT_SHAPE_CASE(hd, d, FN, BF, ...) case hd * 1000 + d: return (BF) ? FN<hd, d, true>(__VA_ARGS__) : FN<hd, d, false>(__VA_ARGS__);
 #define GAT_DISPATCH_HD_D(HD, D, FN, BF, ...) \
     switch ((HD) * 1000 + (D)) { GAT_EDGE_SHAPES(GAT_SHAPE_CASE, FN, BF, __VA_ARGS__) default: break; }
-static EdgePick pick_forward(const EdgeFwdArgs& a, bool ext, bool res) {
-    GAT_DISPATCH_HD_D(a.H * a.D, a.D, pick_fwd, a.bf16 != 0, a, ext, res)
+static EdgePick pick_forward(const EdgeFwdArgs& a, bool ext, bool res, bool pe) {
+    GAT_DISPATCH_HD_D(a.H * a.D, a.D, pick_fwd, a.bf16 != 0, a, ext, res, pe)
     return {};
 }
-static EdgePick pick_backward(const EdgeBwdArgs& a, bool drop, int dbg) {
-    GAT_DISPATCH_HD_D(a.H * a.D, a.D, pick_bwd, a.bf16 != 0, a, drop, dbg)
+static EdgePick pick_backward(const EdgeBwdArgs& a, bool drop, int dbg, bool pe = false) {
+    GAT_DISPATCH_HD_D(a.H * a.D, a.D, pick_bwd, a.bf16 != 0, a, drop, dbg, pe)
     return {};
 }
 
@@ -2237,9 +2342,9 @@ int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const EdgeFwdExtras
     if (edge_fast_path(a.H, a.D, a.n_table)) {
         if (a.items == nullptr) return fail(GAT_E_INVALID, "edge_forward: work-item list missing");
         if (a.mstat == nullptr || a.zstat == nullptr) return fail(GAT_E_INVALID, "edge_forward: stats buffers missing");
-        const bool ext = with_res || x.drop.on != 0;
+        const bool ext = with_res || x.drop.on != 0 || x.pe != nullptr;
         if (ext && x.drop.step == nullptr) return fail(GAT_E_INVALID, "edge_forward: extras without DropArgs::step (the extended kernels read the device counter)");
-        const EdgePick p = pick_forward(a, ext, with_res);
+        const EdgePick p = pick_forward(a, ext, with_res, x.pe != nullptr);
         void* args[] = {&ax};
         GAT_HIP(hipLaunchKernel(p.fn, dim3((unsigned)((a.n_items + p.per_block - 1) / p.per_block)), dim3(p.block), args, 0, s));
         return launch_fwd_fix(p, ax, s);
@@ -2247,17 +2352,17 @@ int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const EdgeFwdExtras
     const int HD = a.H * a.D;
     const int64_t blocks = a.n_rows < kGenericBlocks * 8 ? a.n_rows : kGenericBlocks * 8;
     void* args[] = {&ax, &x};                            // (EdgeFwdArgs, EdgeFwdExtras)
-    GAT_HIP(hipLaunchKernel(with_res ? GAT_K(edge_fwd_generic_res) : GAT_K(edge_fwd_generic), dim3((unsigned)blocks), dim3(64), args,
+    GAT_HIP(hipLaunchKernel(x.pe != nullptr ? GAT_K(edge_fwd_generic_pe) : with_res ? GAT_K(edge_fwd_generic_res) : GAT_K(edge_fwd_generic), dim3((unsigned)blocks), dim3(64), args,
                             (size_t)HD * sizeof(float), s));
     return 0;
 }
 
-int edge_backward_blocks(const EdgeBwdArgs& a, const DropArgs* drop) {
+int edge_backward_blocks(const EdgeBwdArgs& a, const DropArgs* drop, bool pe) {
     if (!edge_fast_path(a.H, a.D, a.n_table))            // generic path: one wave per block, a row at a time
         return (int)std::min<int64_t>(std::max<int64_t>(a.n_rows, 1), kGaPartialRows);
-    const bool on = drop != nullptr && drop->on != 0;
+    const bool on = (drop != nullptr && drop->on != 0) || pe;     // edge features: the DROP instantiations, masks or not
     // the experiment kernels (dbg) run on the grid of the product kernel of their selection
-    EdgePick p = pick_backward(a, on, 0);
+    EdgePick p = pick_backward(a, on, 0, pe);
     if (p.fn == nullptr) p = pick_backward(a, false, 0);  // no dropout form: launch_edge_backward reports it
     int64_t cap = resident_blocks(p.fn, p.block);
 #ifdef GAT_EXPERIMENTS
@@ -2266,19 +2371,25 @@ int edge_backward_blocks(const EdgeBwdArgs& a, const DropArgs* drop) {
     return (int)std::min({std::max<int64_t>((a.n_items + 3) / 4, 1), cap, (int64_t)kGaPartialRows});
 }
 
-int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s, const DropArgs* drop) {
+int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s, const DropArgs* drop, const float* pe, float* gpe) {
     if (a.ga_blocks < 1) return fail(GAT_E_INVALID, "edge_backward: ga_blocks must come from edge_backward_blocks()");
-    const DropArgs dr = drop != nullptr ? *drop : DropArgs{};
+    DropArgs dr = drop != nullptr ? *drop : DropArgs{};
+    const bool with_pe = pe != nullptr;
+    if (with_pe != (gpe != nullptr)) return fail(GAT_E_INVALID, "edge_backward: the edge term needs both PE and gPE");
+    // THE RULE of launch_edge_forward: the extended instantiations without an active mask — every draw keeps, nothing is scaled
+    if (with_pe && !dr.on) { dr.T = 0; dr.Te = 0; dr.scale = 1.f; dr.eflags = 0; }
+    const bool ext = dr.on != 0 || with_pe;
     if (edge_fast_path(a.H, a.D, a.n_table)) {
         if (a.items == nullptr) return fail(GAT_E_INVALID, "edge_backward: work-item list missing");
         if (a.stash != nullptr && a.ge == nullptr && (a.gfull == nullptr || a.pos == nullptr))
             return fail(GAT_E_INVALID, "edge_backward: stash path needs gfull and pos");
-        const EdgePick p = pick_backward(a, dr.on != 0, a.dbg);
+        if (ext && dr.step == nullptr) return fail(GAT_E_INVALID, "edge_backward: the extended kernels read the device counter (DropArgs::step)");
+        const EdgePick p = pick_backward(a, ext, a.dbg, with_pe);
         if (p.fn == nullptr)
-            return fail(GAT_E_UNSUPPORTED, "edge_backward: attention dropout / DropEdge need the store path (not with GAT_BWD_ATOMICS=1 or without the message scratch)");
+            return fail(GAT_E_UNSUPPORTED, "edge_backward: attention dropout / DropEdge / edge features need the store path (not with GAT_BWD_ATOMICS=1 or without the message scratch)");
         EdgeBwdDropArgs ad;
-        if (dr.on) { static_cast<EdgeBwdArgs&>(ad) = a; ad.drop = dr; }
-        void* args[] = {dr.on ? (void*)&ad : (void*)const_cast<EdgeBwdArgs*>(&a)};
+        if (ext) { static_cast<EdgeBwdArgs&>(ad) = a; ad.drop = dr; ad.pe = pe; ad.gpe = gpe; }
+        void* args[] = {ext ? (void*)&ad : (void*)const_cast<EdgeBwdArgs*>(&a)};
         GAT_HIP(hipLaunchKernel(p.fn, dim3((unsigned)a.ga_blocks), dim3(p.block), args, 0, s));
         return launch_bwd_fix(a, s);
     }
@@ -2286,7 +2397,8 @@ int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s, const DropArgs* dr
     const int HD = a.H * a.D;
     const size_t lds = (size_t)(3 * a.H + 2 * HD) * sizeof(float);
     if (lds > 64 * 1024) return fail(GAT_E_UNSUPPORTED, "edge_backward: H*D too large for the generic path");
-    hipLaunchKernelGGL(edge_bwd_generic, dim3((unsigned)a.ga_blocks), dim3(64), lds, s, a, dr);
+    if (with_pe) hipLaunchKernelGGL(edge_bwd_generic_pe, dim3((unsigned)a.ga_blocks), dim3(64), lds, s, a, dr, pe, gpe);
+    else hipLaunchKernelGGL(edge_bwd_generic, dim3((unsigned)a.ga_blocks), dim3(64), lds, s, a, dr);
     GAT_HIP(hipGetLastError());
     return 0;
 }

@@ -154,11 +154,14 @@ struct LnArgs {
 //   and hout are written (split rows: once, in the fix-up kernel's combine).
 // ln (gatv2_abi.h "layer normalisation"): with ln.gamma set, the row u = h_pre (residual term included) is normalised over its H*D
 //   channels in the same epilogue, v = gamma * (u - mu) * rstd + beta, and hout = LReLU(v); h_pre stays u.
+// pe (gatv2_abi.h "edge features"): PE = EA We^T, one fp32 row per CSR edge, joins the score s = PL[src] + PR[dst] + PE[j]; the message
+//   stays PL[src].  Non-null selects the PE instantiations of the extended kernels (their last template flag).
 struct EdgeFwdExtras {
     DropArgs drop;
     const float* res = nullptr;   // [n_rows][HD] R = x' Wres^T of the shard's own rows, or null
     const float* bias = nullptr;  // [HD], or null
     LnArgs ln;
+    const float* pe = nullptr;    // [n_edges][HD] fp32 in CSR order, or null
 };
 int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const EdgeFwdExtras* extras = nullptr);
 struct EdgeFwdExtArgs : EdgeFwdArgs { EdgeFwdExtras x; };
@@ -208,8 +211,11 @@ struct EdgeBwdArgs {
     int32_t dbg;
 };
 // drop: the attention dropout of the forward this backward follows (same masks)
-int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s, const DropArgs* drop = nullptr);
-struct EdgeBwdDropArgs : EdgeBwdArgs { DropArgs drop; };
+// pe / gpe (both or neither; gatv2_abi.h "edge features"): the forward's PE rows, and where gs = ge * a * LReLU'(s) of every CSR edge is
+//   written ([n_edges][HD] fp32, zeros at dropped edges).  They select the PE instantiations of the DROP kernels, under the forward's
+//   rule: without an active mask those run with T = Te = 0, scale = 1 (drop->step must still point at the device counter).
+int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s, const DropArgs* drop = nullptr, const float* pe = nullptr, float* gpe = nullptr);
+struct EdgeBwdDropArgs : EdgeBwdArgs { DropArgs drop; const float* pe = nullptr; float* gpe = nullptr; };
 // Last layer, fused per row (gat_step): forward edge pass + output head + backward edge pass of every WHOLE row in one kernel
 // (edge_last_fused_kernel); f / b as for the separate passes (f.items / f.n_items: the whole-row items only; b.ga_partial /
 // b.ga_blocks from edge_last_fused_blocks), gh_out = the [n_rows][gh_stride] node records the pull pass reads.
@@ -233,8 +239,8 @@ int edge_stash_words(int32_t H, int32_t D);
 // Rows of ga_partial a layer's backward may write: the cap of every grid that writes one row per block
 constexpr int kGaPartialRows = 2048;
 // Grid size (== rows of ga_partial, <= kGaPartialRows) for the backward launch_edge_backward(a, s, drop) will run: sized for the
-// kernel those arguments select (a.ga_blocks is not read)
-int edge_backward_blocks(const EdgeBwdArgs& a, const DropArgs* drop = nullptr);
+// kernel those arguments select (a.ga_blocks is not read); pe: the backward will be given PE rows
+int edge_backward_blocks(const EdgeBwdArgs& a, const DropArgs* drop = nullptr, bool pe = false);
 // wave-per-row templates cover this (H, D), and the gathered table is < 4 GiB (they address it as
 // uniform base + 32-bit byte offset); anything else runs the generic kernels
 bool edge_fast_path(int32_t H, int32_t D, int64_t n_table);

@@ -30,6 +30,11 @@
 // --layer-norm [--norm-eps X] [--norm-skip-last]: LayerNorm over each row's H*D channels between the aggregation and the LeakyReLU
 // (gatv2_abi.h "layer normalisation"; eps default 1e-5; --norm-skip-last leaves the last layer un-normalised); gamma starts at 1, beta
 // at 0, and --dump-params / --load-params carry gamma and beta behind the residual groups, only with the flag.
+// --edge-features: per-edge attributes in the attention score (gatv2_abi.h "edge features"): edge_features.txt of the dataset folder holds
+// E lines of Fe values, line j for CSR edge j (Fe is derived from the count); We is Xavier-initialised from --seed after every other
+// parameter, and --dump-params / --load-params carry We behind beta, only with the flag.  CSR datasets as they are, one rank: the flag
+// is refused with an edges.txt dataset, with --add-self-loops / --undirected / --coalesce (the graph would be rebuilt and the rows
+// would no longer match its edges) and with --ranks > 1.
 // --add-self-loops / --undirected / --coalesce: the graph is rebuilt on the device before training (gat_graph_from_coo:
 // GAT_GRAPH_SELF_LOOPS / SYMMETRIZE / COALESCE, applied in that order); a CSR dataset is expanded to an edge list first.
 // Edge-list dataset: a folder with edges.txt (one "src dst" pair per line, a message flows src -> dst) instead of
@@ -87,6 +92,7 @@ struct Options {
     int residual_flags = 0;                           // GAT_RES_*: --residual, --bias
     int norm_flags = 0; float norm_eps = 1e-5f;       // GAT_NORM_*: --layer-norm, --norm-skip-last; --norm-eps
     int graph_flags = 0;                  // GAT_GRAPH_*: --add-self-loops, --undirected, --coalesce
+    bool edge_features = false;           // --edge-features: edge_features.txt of the dataset folder enters the attention score
 };
 
 // A CSR built before the ranks were forked (main): row_ptr [n + 1] then col_idx [e] in shared memory.
@@ -110,6 +116,9 @@ const char* kUsage =
     "                          (--dump-params / --load-params then append Wres and b behind W, a and Wo)\n"
     "            --layer-norm [--norm-eps X] [--norm-skip-last]   LayerNorm over each row's H*D channels before the LeakyReLU\n"
     "                          (eps X, default 1e-5 / not in the last layer; gamma and beta follow b in --dump-params / --load-params)\n"
+    "            --edge-features    per-edge attributes enter the attention score: edge_features.txt of the dataset folder, E lines of Fe\n"
+    "                          values in CSR order (CSR datasets only, not with the graph flags, --ranks 1; We follows beta in\n"
+    "                          --dump-params / --load-params)\n"
     "            --ranks P [--transport rccl|host] [--halo 0|1|2]\n";
 
 struct RankEnv {                      // one forked process per GPU
@@ -195,6 +204,7 @@ Options parse_args(int argc, char** argv) {
         else if (a == "--layer-norm") o.norm_flags |= GAT_NORM_LAYER;
         else if (a == "--norm-skip-last") o.norm_flags |= GAT_NORM_SKIP_LAST;
         else if (a == "--norm-eps" && has_val) o.norm_eps = std::strtof(argv[++i], nullptr);
+        else if (a == "--edge-features") o.edge_features = true;
         else if (a == "--transport" && has_val) {
             o.transport = argv[++i];
             if (o.transport != "rccl" && o.transport != "host") die("Invalid transport choice. Use 'rccl' or 'host'\n");
@@ -424,6 +434,21 @@ int run(const Options& o, const RankEnv& env) {
         std::vector<int32_t>().swap(e_src); std::vector<int32_t>().swap(e_dst);
     }
     const int64_t E = (int64_t)col_idx.size();
+    std::vector<float> ea;                      // --edge-features: [E][Fe], row j for CSR edge j
+    int Fe = 0;
+    if (o.edge_features) {
+        if (edge_list)
+            die("Error: --edge-features needs a CSR dataset (row_ptr.txt + col_idx.txt): edge_features.txt lists one row per CSR edge, and an "
+                "edges.txt dataset is rebuilt into another order on the device\n");
+        int64_t ne = 0;
+        load_features(path + "edge_features.txt", ea, ne, Fe);
+        if (ne != E || Fe < 1 || (int64_t)ea.size() != E * Fe) {
+            std::cerr << "Invalid edge_features.txt: expected " << E << " lines of equal length, one per CSR edge\n";
+            return 1;
+        }
+        if (Fe > GAT_EDGE_DIM_MAX) { std::cerr << "Invalid edge_features.txt: more than " << GAT_EDGE_DIM_MAX << " values per edge\n"; return 1; }
+        std::cout << "Edge features: " << Fe << " per edge" << std::endl;
+    }
 
     int max_degree = 0;
     for (int64_t i = 0; i < N; ++i) max_degree = std::max(max_degree, row_ptr[i + 1] - row_ptr[i]);
@@ -475,7 +500,9 @@ int run(const Options& o, const RankEnv& env) {
     // residual / bias: before anything sizes the packed buffers; every rank of --ranks runs this with the same options
     if (o.residual_flags) check(gat_set_residual(ctx, o.residual_flags), "gat_set_residual");
     if (o.norm_flags) check(gat_set_norm(ctx, o.norm_flags, o.norm_eps), "gat_set_norm");
-    int64_t nW = 0, nA = 0, nWo = 0, nWres = 0, nB = 0, nLnG = 0, nLnB = 0;
+    if (o.edge_features) check(gat_set_edge_dim(ctx, Fe), "gat_set_edge_dim");
+    int64_t nW = 0, nA = 0, nWo = 0, nWres = 0, nB = 0, nLnG = 0, nLnB = 0, nWe = 0;
+    gat_param_count(ctx, GAT_PARAM_WE, &nWe);                                                 // 0 without --edge-features
     gat_param_count(ctx, GAT_PARAM_W, &nW); gat_param_count(ctx, GAT_PARAM_A, &nA); gat_param_count(ctx, GAT_PARAM_WO, &nWo);
     gat_param_count(ctx, GAT_PARAM_WRES, &nWres); gat_param_count(ctx, GAT_PARAM_B, &nB);     // 0 without the flags
     gat_param_count(ctx, GAT_PARAM_LN_G, &nLnG); gat_param_count(ctx, GAT_PARAM_LN_B, &nLnB);
@@ -483,6 +510,7 @@ int run(const Options& o, const RankEnv& env) {
         check(gat_set_graph(ctx, row_ptr.data(), col_idx.data(), N, E, N, 0), "csr_to_coo_kernel");
         check(gat_set_features(ctx, x.data(), N, F0), "gat_set_features");
         check(gat_set_labels(ctx, labels.data(), N), "gat_set_labels");
+        if (o.edge_features) check(gat_set_edge_features(ctx, ea.data(), E, Fe), "gat_set_edge_features");
     } else {
         // this rank's destination range; sources as rows of the padded [world][max_rows] table; the static
         // input features replicated for every table row (layer 0 then needs no exchange)
@@ -511,7 +539,7 @@ int run(const Options& o, const RankEnv& env) {
         } else {
             int64_t hd_max = 0;
             for (int l = 0; l < L; ++l) hd_max = std::max<int64_t>(hd_max, (int64_t)o.heads[l] * o.outdims[l]);
-            const int64_t bytes = std::max<int64_t>(plan.n_table() * hd_max + 64, nW + nA + nWo + nWres + nB + nLnG + nLnB + 3) * (int64_t)sizeof(float);   // (+ 64: block offsets of a halo exchange)
+            const int64_t bytes = std::max<int64_t>(plan.n_table() * hd_max + 64, nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe + 3) * (int64_t)sizeof(float);   // (+ 64: block offsets of a halo exchange)
             check(gat_comm_init_host(ctx, env.world, env.rank, env.shm_name.c_str(), bytes), "gat_comm_init_host");
         }
         if (o.halo != 0) check(gat_comm_option(ctx, GAT_COMM_HALO, o.halo), "gat_comm_option(GAT_COMM_HALO)");      // collective: every rank
@@ -556,7 +584,7 @@ int run(const Options& o, const RankEnv& env) {
     if (o.drop_edge > 0.f) check(gat_set_dropedge(ctx, o.drop_edge, o.drop_edge_flags), "gat_set_dropedge");
     check(gat_params_init(ctx, o.seed), "xavier_init_kernel");
     if (!o.load_params.empty()) {
-        std::vector<float> p(nW + nA + nWo + nWres + nB + nLnG + nLnB);    // the residual and norm groups follow the others, only with their flags
+        std::vector<float> p(nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe);    // the residual, norm and edge-feature groups follow the others, only with their flags
         std::ifstream f(o.load_params, std::ios::binary);
         if (!f.read(reinterpret_cast<char*>(p.data()), p.size() * sizeof(float))) die("Error: cannot read --load-params file\n");
         check(gat_params_set(ctx, GAT_PARAM_W, p.data(), nW), "gat_params_set");
@@ -566,6 +594,7 @@ int run(const Options& o, const RankEnv& env) {
         if (nB) check(gat_params_set(ctx, GAT_PARAM_B, p.data() + nW + nA + nWo + nWres, nB), "gat_params_set");
         if (nLnG) check(gat_params_set(ctx, GAT_PARAM_LN_G, p.data() + nW + nA + nWo + nWres + nB, nLnG), "gat_params_set");
         if (nLnB) check(gat_params_set(ctx, GAT_PARAM_LN_B, p.data() + nW + nA + nWo + nWres + nB + nLnG, nLnB), "gat_params_set");
+        if (nWe) check(gat_params_set(ctx, GAT_PARAM_WE, p.data() + nW + nA + nWo + nWres + nB + nLnG + nLnB, nWe), "gat_params_set");
     }
 
     size_t free_after = 0;
@@ -606,7 +635,7 @@ int run(const Options& o, const RankEnv& env) {
     }
 
     if (!o.dump_params.empty() && env.rank == 0) {
-        std::vector<float> p(nW + nA + nWo + nWres + nB + nLnG + nLnB);    // without --residual / --bias / --layer-norm: the format of always
+        std::vector<float> p(nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe);    // without --residual / --bias / --layer-norm / --edge-features: the format of always
         check(gat_params_get(ctx, GAT_PARAM_W, p.data(), nW), "gat_params_get");
         check(gat_params_get(ctx, GAT_PARAM_A, p.data() + nW, nA), "gat_params_get");
         check(gat_params_get(ctx, GAT_PARAM_WO, p.data() + nW + nA, nWo), "gat_params_get");
@@ -614,6 +643,7 @@ int run(const Options& o, const RankEnv& env) {
         if (nB) check(gat_params_get(ctx, GAT_PARAM_B, p.data() + nW + nA + nWo + nWres, nB), "gat_params_get");
         if (nLnG) check(gat_params_get(ctx, GAT_PARAM_LN_G, p.data() + nW + nA + nWo + nWres + nB, nLnG), "gat_params_get");
         if (nLnB) check(gat_params_get(ctx, GAT_PARAM_LN_B, p.data() + nW + nA + nWo + nWres + nB + nLnG, nLnB), "gat_params_get");
+        if (nWe) check(gat_params_get(ctx, GAT_PARAM_WE, p.data() + nW + nA + nWo + nWres + nB + nLnG + nLnB, nWe), "gat_params_get");
         std::ofstream f(o.dump_params, std::ios::binary);
         f.write(reinterpret_cast<const char*>(p.data()), p.size() * sizeof(float));
     }
@@ -635,13 +665,21 @@ int main(int argc, char** argv) {
         const float p = std::strtof(argv[i + 1], &end);
         if (end == argv[i + 1] || *end != '\0' || !(p >= 0.f && p < 1.f)) die("Error: " + a + " must be in [0, 1)\n");
     }
-    // --help, and graph flags without a graph to apply them to, end here: before anything touches the GPU
-    bool graph_flag = false;
+    // --help, --edge-features with what it cannot be combined with, and graph flags without a graph to apply them to, end here: before
+    // anything touches the GPU
+    bool graph_flag = false, edge_feat_flag = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--help") { std::cout << kUsage; return 0; }
         if (a == "--add-self-loops" || a == "--undirected" || a == "--coalesce") graph_flag = true;
+        if (a == "--edge-features") edge_feat_flag = true;
     }
+    if (edge_feat_flag && graph_flag)
+        die("Error: --edge-features cannot be combined with --add-self-loops / --undirected / --coalesce: they rebuild the graph, and the rows of "
+            "edge_features.txt (one per CSR edge of the dataset) would no longer match its edges\n");
+    if (edge_feat_flag && multi)
+        die("Error: --edge-features needs --ranks 1: this program does not cut edge_features.txt into shards (the library does: "
+            "gat_set_edge_features on every shard's own CSR)\n");
     if (graph_flag) {
         std::string root = "./data", name = "pubmed";
         bool root_given = false;

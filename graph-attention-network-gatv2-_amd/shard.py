@@ -104,6 +104,17 @@ def local_csr(plan: ShardPlan, row_ptr: np.ndarray, col_idx: np.ndarray):
     return rp, ci
 
 
+def local_edge_features(plan: ShardPlan, row_ptr: np.ndarray, ea: np.ndarray) -> np.ndarray:
+    """Global per-edge attributes [E][Fe] (rows in the order of the global CSR) -> the rows of this shard's own CSR, in its order:
+    local_csr keeps the edges of rows [row0, row0 + n_rows) as one contiguous run, so the slice is that run (a copy).  Edge
+    attributes belong to the destination shard: nothing about them is exchanged."""
+    ea = np.asarray(ea)
+    if ea.ndim != 2 or ea.shape[0] != int(row_ptr[-1]):
+        raise ValueError(f"edge features must be [E][Fe] with E = {int(row_ptr[-1])}, got shape {ea.shape}")
+    s, t = plan.row0, plan.row0 + plan.n_rows
+    return np.ascontiguousarray(ea[int(row_ptr[s]):int(row_ptr[t])])
+
+
 def plan_from_coo(src, dst, n_nodes: int, world: int, rank: int, flags: int = 0, device: int = 0):
     """Edge-list input for a sharded run: the GLOBAL CSR is built on the device with the builder's flags
     (abi.graph_from_coo: self-loops / symmetrize / coalesce apply to the whole graph, before it is cut), then planned and cut

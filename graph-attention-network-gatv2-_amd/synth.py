@@ -182,11 +182,23 @@ def make_dataset_device(name: str, device, scale: float = 1.0, seed: int = GRAPH
 
 
 def write_text_dataset(ds: dict, root: str, name: Optional[str] = None) -> str:
-    """Write the four whitespace text files the reference loads (R:20-27, E:1079-1099)."""
+    """Write the four whitespace text files the reference loads (R:20-27, E:1079-1099); with ds["edge_features"] ([E][Fe], rows in CSR
+    order) also edge_features.txt, which train_edge --edge-features reads."""
     d = os.path.join(root, name or ds["name"])
     os.makedirs(d, exist_ok=True)
     np.savetxt(os.path.join(d, "features.txt"), ds["x"], fmt="%.9g")
     np.savetxt(os.path.join(d, "row_ptr.txt"), ds["row_ptr"], fmt="%d")
     np.savetxt(os.path.join(d, "col_idx.txt"), ds["col_idx"], fmt="%d")
     np.savetxt(os.path.join(d, "labels.txt"), ds["labels"], fmt="%d")
+    if ds.get("edge_features") is not None:
+        np.savetxt(os.path.join(d, "edge_features.txt"), np.asarray(ds["edge_features"]).reshape(len(ds["col_idx"]), -1), fmt="%.9g")
     return d
+
+
+def edge_features(seed: int, n_edges: int, fe: int) -> np.ndarray:
+    """Deterministic per-edge attributes [n_edges][fe] (fp32, standard normal) for the tests and tools of the edge-feature path
+    (gatv2_abi.h "edge features"): row j belongs to CSR edge j.  A function of (seed, n_edges, fe) alone."""
+    if n_edges < 0 or fe < 1:
+        raise ValueError(f"edge_features: bad sizes (n_edges={n_edges}, fe={fe})")
+    rng = np.random.default_rng([int(seed) & (2 ** 63 - 1), 0xEA])
+    return rng.standard_normal((int(n_edges), int(fe))).astype(np.float32)

@@ -182,19 +182,22 @@ int gat_graph_check_device(const int32_t* d_row_ptr, const int32_t* d_col_idx, i
  * GAT_PARAM_WRES flat [l][H_l*D_l][F_l] and GAT_PARAM_B flat [l][H_l*D_l] exist on a context with gat_set_residual (see
  * "residual" below); with their flag off the group's count is 0 and a set / get of 0 floats is a no-op that succeeds.
  * GAT_PARAM_LN_G / GAT_PARAM_LN_B, each flat [l][H_l*D_l] over all L layers, exist on a context with gat_set_norm (see "layer
- * normalisation" below) and sit behind the other five; off, their counts are 0 as well. */
-enum { GAT_PARAM_W = 0, GAT_PARAM_A = 1, GAT_PARAM_WO = 2, GAT_PARAM_WRES = 3, GAT_PARAM_B = 4, GAT_PARAM_LN_G = 5, GAT_PARAM_LN_B = 6 };
+ * normalisation" below) and sit behind the other five; off, their counts are 0 as well.
+ * GAT_PARAM_WE flat [l][H_l*D_l][Fe] exists on a context with gat_set_edge_dim(Fe > 0) (see "edge features" below) and sits behind
+ * the other six; with edge_dim == 0 its count is 0. */
+enum { GAT_PARAM_W = 0, GAT_PARAM_A = 1, GAT_PARAM_WO = 2, GAT_PARAM_WRES = 3, GAT_PARAM_B = 4, GAT_PARAM_LN_G = 5, GAT_PARAM_LN_B = 6, GAT_PARAM_WE = 7 };
 int gat_param_count(gat_ctx* ctx, int group, int64_t* count);
 /* U(-lim,lim], lim as E:208, 236.  With GAT_RES_LINEAR: Wres_l Xavier-uniform with lim = sqrt(6 / (F_l + H_l*D_l)), drawn from the same
  * counter stream AFTER all existing draws (layer by layer), so W, a and Wo of a seed are those of a context without it; b = 0.
- * With gat_set_norm: gamma = 1, beta = 0, no draws. */
+ * With gat_set_norm: gamma = 1, beta = 0, no draws.  With gat_set_edge_dim: We_l Xavier-uniform with lim = sqrt(6 / (Fe + H_l*D_l)), drawn
+ * after every other draw (after Wres), so all other groups of a seed are unchanged. */
 int gat_params_init(gat_ctx* ctx, uint64_t seed);
 int gat_params_set(gat_ctx* ctx, int group, const float* host, int64_t count);
 int gat_params_get(gat_ctx* ctx, int group, float* host, int64_t count);
 int gat_grads_get(gat_ctx* ctx, int group, float* host, int64_t count);
 int gat_grads_set(gat_ctx* ctx, int group, const float* host, int64_t count);
-/* Device address of the packed gradient buffer [gradW | grada | gradWo | gradWres | gradb | gradgamma | gradbeta] (for the all-reduce;
- * groups 3 and 4 only with gat_set_residual, 5 and 6 only with gat_set_norm).  count = n_params, the sum of the seven group counts; the three-float result tail of
+/* Device address of the packed gradient buffer [gradW | grada | gradWo | gradWres | gradb | gradgamma | gradbeta | gradWe] (for the all-reduce;
+ * groups 3 and 4 only with gat_set_residual, 5 and 6 only with gat_set_norm, 7 only with gat_set_edge_dim).  count = n_params, the sum of the eight group counts; the three-float result tail of
  * gat_result_export sits behind it, and the host transport's bytes_per_rank rule stays (n_params + 3) * 4. */
 int gat_grads_device(gat_ctx* ctx, void** d_ptr, int64_t* count);
 /* Async D2D copies of the packed gradients on the context's stream, to / from a caller-owned
@@ -490,6 +493,56 @@ int gat_set_residual(gat_ctx* ctx, int32_t flags);
  *   normalised layer adds 2*HD floats of parameters per pass to misc.  gat_algorithmic_bytes_shape prices the model without it. */
 enum { GAT_NORM_LAYER = 1, GAT_NORM_SKIP_LAST = 2 };
 int gat_set_norm(gat_ctx* ctx, int32_t flags, float eps);
+
+/* ---- edge features in the attention score (beyond the reference; the `edge_dim` argument of PyG's GATv2Conv) ----------------------
+ * With edge_dim = Fe > 0 every layer l has a parameter We_l, flat [H_l*D_l][Fe], and every CSR edge j of the context's graph an
+ * attribute row EA[j] ([E][Fe], fp32, in the order of the context's CSR: the order gat_graph_get returns).  With dst the row of edge j:
+ *     PE_l[j][c]  = sum_f We_l[c][f] * EA[j][f]
+ *     s[j][c]     = PL[src_j][c] + PR[dst][c] + PE_l[j][c]
+ *     score[j][h] = sum_d a[h,d] * LReLU(s[j][h,d])
+ * The softmax, alpha, the aggregation, the residual, the norm and the head are as without it: the MESSAGE STAYS PL[src] (as in PyG),
+ * the edge term is in the score only.  The same EA serves every layer.  Rows without in-edges are unaffected.
+ * Backward, with ge = dL/dscore as without the feature:
+ *     gs[j][c] = ge[j][h] * a[c] * LReLU'(s[j][c])      gPL[src] += gs + g * kappa*s_a*alpha      gPR[dst] += gs      ga += ge * LReLU(s)
+ *     gPE_l[j] = gs[j]                                   gradWe_l += gPE_l^T EA
+ * LReLU and LReLU' take the new s wherever they appear.  EA is an input: it gets no gradient.  A DropEdge-dropped edge has gPE[j] = 0;
+ * attention dropout leaves gPE as the formula gives it (ge already contains kappa).
+ * gat_set_edge_dim follows gat_set_residual's state rules: only BEFORE the first gat_params_*, gat_grads_*, gat_set_graph* call (later:
+ *   GAT_E_STATE), in any order with gat_set_residual / gat_set_norm.  edge_dim < 0 or > GAT_EDGE_DIM_MAX: GAT_E_INVALID.  0 is the
+ *   default and leaves the context exactly as it is: same buffers, same kernels, same launch counts, bitwise the same results.  The
+ *   experiment library with GAT_DBG set: GAT_E_UNSUPPORTED.
+ * gat_set_edge_features[_device] is called AFTER the graph is set (before: GAT_E_STATE); n_edges and edge_dim must be the context's
+ *   (GAT_E_INVALID otherwise; with edge_dim == 0 on both sides the call does nothing).  The array is copied (rows padded to a multiple of 4 floats with
+ *   zeros) and may be replaced by a later call.  A step / phase call on a context with edge_dim > 0 and no edge features set gives
+ *   GAT_E_STATE and says so.  After gat_set_graph_coo* the rows are still "in the order of gat_graph_get": carrying attributes through
+ *   GAT_GRAPH_SYMMETRIZE / SELF_LOOPS / COALESCE (PyG's fill_value) is the caller's business and out of scope.
+ * Parameters: GAT_PARAM_WE, flat [l][H_l*D_l][Fe], behind the seven other groups in the packed parameter, gradient and Adam buffers
+ *   (gat_grads_device reports the new n_params; the three-float result tail stays behind it; the host transport's
+ *   (n_params + 3) * 4 rule holds with the new n_params).  gat_zero_grad, gat_step_sgd and gat_step_adam cover it; gat_clip clips it by
+ *   its own norm.
+ * Where it runs.  PE_l = EA We_l^T is a fourth dense product of gat_layer_project (the three-bf16-piece kernels of the residual term,
+ *   rows = E, K = Fe), kept per layer in fp32 also under bf16 storage (it is streamed, never gathered).  Both edge passes run the PE
+ *   instantiations of their extended kernels (EXT forward, DROP backward; without an active mask at T = Te = 0, scale = 1): per edge
+ *   one more row load PE[j] at a CSR-contiguous address next to the PL[src] gather, and in the backward one streamed row store
+ *   gPE[j] = gs into a single [E][max H*D] fp32 buffer shared by the layers.  gat_layer_backward_dense adds gradWe_l = gPE^T EA (the
+ *   grad_W kernels on one half).  The fix-up kernels and the source-major passes are unchanged: the per-edge records / message rows
+ *   already carry the LReLU'(s) decisions.  Destination-range shards: an edge's attributes belong to the destination shard's own CSR,
+ *   nothing more is exchanged, and the packed all-reduce sums the new group.  Computing PE inside the edge kernels is out of scope.
+ *   Extra device memory: (L + 1) * E * HD * 4 bytes at equal HD (PE per layer + gPE), plus E * ld * 4 for EA (ld = Fe rounded up to 4).
+ * Works with every (H, D) family incl. both generic ones, bf16 storage, keep_taps (GAT_TAP_SCORE includes the edge term), the phase
+ *   API (project forms PE_l, backward_edges writes gPE, backward_dense adds gradWe_l), gat_step, gat_step_graph replay, training
+ *   masks, eval mode, all three regularisers, residual, bias, norm, and shards on any transport.
+ * Not with: GAT_FUSE_LAST=1 and the last layer's decision-byte pull form (such a context runs the separate passes and gathers g rows,
+ *   as a residual context does); GAT_BWD_ATOMICS=1 (GAT_E_UNSUPPORTED at the backward, as with dropout).  The gat_op_* seams stay
+ *   edge-feature-free.
+ * gat_algorithmic_bytes (context form): unchanged with the feature off.  On, per layer at 4 bytes:
+ *   project += E*Fe + HD*Fe + E*HD; edge_forward += E*HD; edge_backward += 2*E*HD; grad_w += E*HD + E*Fe + HD*Fe.
+ *   gat_algorithmic_bytes_shape prices the model without it.  At the Products shape and HD = 64 the step's bytes roughly double: the
+ *   price of a dense per-edge term. */
+#define GAT_EDGE_DIM_MAX 64
+int gat_set_edge_dim(gat_ctx* ctx, int32_t edge_dim);
+int gat_set_edge_features(gat_ctx* ctx, const float* ea, int64_t n_edges, int32_t edge_dim);              /* [n_edges][edge_dim], host */
+int gat_set_edge_features_device(gat_ctx* ctx, const float* d_ea, int64_t n_edges, int32_t edge_dim);    /* the same, device pointer */
 
 /* ---- op-level entry points, whole layers: caller-provided DEVICE pointers in the reference layouts
  *      (unit parity).  `stream` may be NULL (default stream).  One entry point per reference KERNEL: below. ---- */
