@@ -61,7 +61,10 @@ COMM_HALO = 3
  TAP_PR, TAP_SCORE, TAP_GALPHA, TAP_GX) = range(15)
 TAP_ATTN_KEEP, TAP_FEAT_KEEP = 15, 16       # dropout factors (0 or 1/(1-p)) for the step the counter holds
 TAP_EDGE_KEEP = 17                          # DropEdge: 1 = edge kept, 0 = dropped, [E], likewise
+TAP_POOLED = 18                             # readout: the pooled rows the head reads, [n_graphs][D_last] (last layer)
 DROPEDGE_KEEP_SELF, DROPEDGE_SHARED_LAYERS = 1, 2
+READOUT_NONE, READOUT_MEAN, READOUT_SUM, READOUT_MAX = 0, 1, 2, 3      # graph-level readout (set_readout)
+READOUT_MODES = {"none": READOUT_NONE, "mean": READOUT_MEAN, "sum": READOUT_SUM, "max": READOUT_MAX}
 (K_PROJECT, K_EDGE_FWD, K_HEAD_FWD, K_HEAD_BWD, K_EDGE_BWD, K_GPL_SUM, K_GRAD_W, K_GRAD_X, K_MISC,
  K_EXCHANGE, K_EDGE_FUSED, K_COUNT) = range(12)
 COMM_ID_BYTES = 128
@@ -207,6 +210,11 @@ def _declare(lib: C.CDLL) -> None:
         "gat_set_edge_dim": [vp, i32],
         "gat_set_edge_features": [vp, vp, i64, i32],
         "gat_set_edge_features_device": [vp, vp, i64, i32],
+        "gat_set_readout": [vp, i32, vp, i64],
+        "gat_set_readout_device": [vp, i32, vp, i64],
+        "gat_readout_info": [vp, P(i32), P(i64)],
+        "gat_op_readout_forward": [vp, i64, vp, i64, i64, i32, i32, vp, vp, vp],
+        "gat_op_readout_backward": [vp, vp, i64, i64, i32, i32, vp, vp, i64, vp],
         "gat_set_training": [vp, i32],
         "gat_dropout_step": [vp, P(C.c_uint64)],
         "gat_set_shard_bounds": [vp, i32, vp],
@@ -267,6 +275,7 @@ class GatContext:
         _chk(self.lib.gat_create(C.byref(cfg), C.byref(self._ctx)))
         self.n_rows = self.n_edges = self.n_table = 0
         self.table_row0 = 0
+        self.n_graphs = 0                               # > 0 on a readout context (set_readout)
 
     # -- lifecycle
     def close(self):
@@ -366,7 +375,7 @@ class GatContext:
         _chk(self.lib.gat_set_labels(self._ctx, _np_ptr(lab), len(lab)))
 
     def set_train_mask(self, mask):
-        """mask: bool/uint8 [n_rows] (None: every node trains, the reference's behaviour)."""
+        """mask: bool/uint8 [n_rows] — [n_graphs] on a readout context (None: every node / graph trains, the reference's behaviour)."""
         if mask is None:
             _chk(self.lib.gat_set_train_mask(self._ctx, None, 0))
             return
@@ -374,7 +383,7 @@ class GatContext:
         _chk(self.lib.gat_set_train_mask(self._ctx, _np_ptr(m), len(m)))
 
     def eval_mask(self, mask):
-        """-> (loss sum, #correct, #nodes) of the last forward over the nodes of `mask`."""
+        """-> (loss sum, #correct, #nodes) of the last forward over the nodes of `mask` (a readout context: over its graphs)."""
         m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
         l, c, n = C.c_double(), C.c_int32(), C.c_int32()
         _chk(self.lib.gat_eval_mask(self._ctx, _np_ptr(m), len(m), C.byref(l), C.byref(c), C.byref(n)))
@@ -452,6 +461,35 @@ class GatContext:
 
     def set_edge_features_device(self, d_ea: int, n_edges: int, edge_dim: int):
         _chk(self.lib.gat_set_edge_features_device(self._ctx, C.c_void_p(d_ea or None), n_edges, edge_dim))
+
+    # -- graph-level readout (gatv2_abi.h "graph-level readout")
+    def set_readout(self, mode, graph_ptr=None, batch=None):
+        """One label per GRAPH: the last layer's rows are pooled per graph ("mean", "sum", "max" or the GAT_READOUT_* integer) in front
+        of the output head.  graph_ptr [n_graphs + 1]: graph g owns rows graph_ptr[g] .. graph_ptr[g+1]-1 (PyG's Batch.ptr); or batch
+        [n_rows]: the sorted graph id of every row (PyG's Batch.batch; an unsorted one raises ValueError).  After set_graph*, before
+        set_labels; labels and masks are then per graph.  Mode 0 / "none" leaves the context as it is."""
+        m = readout_mode(mode)
+        if m == READOUT_NONE:
+            _chk(self.lib.gat_set_readout(self._ctx, m, None, 0))
+            return
+        if (graph_ptr is None) == (batch is None):
+            raise ValueError("set_readout: give graph_ptr or batch (one of them)")
+        gp = batch_to_graph_ptr(batch) if graph_ptr is None else np.ascontiguousarray(graph_ptr, np.int32)
+        if gp.ndim != 1 or len(gp) < 2:
+            raise ValueError("graph_ptr must be one-dimensional with n_graphs + 1 >= 2 entries")
+        _chk(self.lib.gat_set_readout(self._ctx, m, _np_ptr(gp), len(gp) - 1))
+        self.n_graphs = len(gp) - 1
+
+    def set_readout_device(self, mode, d_graph_ptr: int, n_graphs: int):
+        """set_readout on a device graph_ptr [n_graphs + 1] (checked on the device)."""
+        _chk(self.lib.gat_set_readout_device(self._ctx, readout_mode(mode), C.c_void_p(d_graph_ptr or None), n_graphs))
+        self.n_graphs = int(n_graphs)
+
+    def readout_info(self):
+        """(mode, n_graphs); (0, 0) while readout is off."""
+        m, g = C.c_int32(), C.c_int64()
+        _chk(self.lib.gat_readout_info(self._ctx, C.byref(m), C.byref(g)))
+        return m.value, g.value
 
     # -- dropout (gatv2_abi.h "dropout")
     def set_dropout(self, feat_p: float = 0.0, attn_p: float = 0.0, seed: int = 0, first_step: int = 0):
@@ -591,13 +629,15 @@ class GatContext:
         N, E = self.n_rows, self.n_edges
         H, D = self.heads[l], self.outdims[l]
         last = l == self.L - 1
+        G = self.n_graphs                               # readout: the head has one row per graph
         shapes = {
             TAP_SRC: ((E,), np.int32), TAP_DST: ((E,), np.int32),
             TAP_ALPHA: ((H, E), np.float32), TAP_GE: ((H, E), np.float32),
             TAP_MAX: ((H, N), np.float32), TAP_SUM: ((H, N), np.float32),
             TAP_HPRE: ((N, H, D), np.float32), TAP_G: ((N, H, D), np.float32),
             TAP_HOUT: ((N, D if last else H * D), np.float32),
-            TAP_Y: ((N, self.C), np.float32),
+            TAP_Y: ((G or N, self.C), np.float32),
+            TAP_POOLED: ((G, self.outdims[-1]), np.float32),
             TAP_PL: ((self.n_table, H * D), np.float32), TAP_PR: ((N, H * D), np.float32),
             TAP_SCORE: ((H, E), np.float32), TAP_GALPHA: ((H, E), np.float32),
             TAP_GX: ((N, self.heads[l - 1] * self.outdims[l - 1] if l > 0 else 0), np.float32),
@@ -662,6 +702,47 @@ def request_bytes_shape(heads: Sequence[int], outdims: Sequence[int], in_dim: in
     _chk(lib.gat_request_bytes_shape(C.byref(cfg), n_rows, n_edges, n_rows if n_table is None else n_table,
                                      int(replicated_input), C.byref(tot), per))
     return tot.value, {lib.gat_kernel_name(k).decode(): per[k] for k in range(K_COUNT)}
+
+
+def readout_mode(mode) -> int:
+    """"mean" / "sum" / "max" / "none" or the GAT_READOUT_* integer -> the integer."""
+    if isinstance(mode, str):
+        if mode not in READOUT_MODES:
+            raise ValueError(f"readout mode must be one of {sorted(READOUT_MODES)}, got {mode!r}")
+        return READOUT_MODES[mode]
+    return int(mode)
+
+
+def batch_to_graph_ptr(batch) -> np.ndarray:
+    """A sorted graph id per row (PyG's Batch.batch) -> graph_ptr [n_graphs + 1] int32, n_graphs = batch[-1] + 1 (ids that do not
+    occur are empty graphs).  ValueError for an unsorted, negative or empty vector."""
+    b = np.asarray(batch)
+    if b.ndim != 1 or b.size == 0:
+        raise ValueError("batch must be a non-empty one-dimensional vector")
+    if b.dtype.kind not in "iu":
+        raise TypeError(f"batch must hold integers, got {b.dtype}")
+    if int(b.min()) < 0:
+        raise ValueError("batch holds a negative graph id")
+    if np.any(np.diff(b.astype(np.int64)) < 0):
+        raise ValueError("batch must be sorted (the rows of a graph are contiguous)")
+    g = int(b[-1]) + 1
+    return np.searchsorted(b, np.arange(g + 1)).astype(np.int32)
+
+
+def op_readout_forward(d_x: int, x_stride: int, d_graph_ptr: int, n_graphs: int, n_rows: int, width: int, mode, d_pooled: int,
+                       d_argmax: int = 0, stream: int = 0):
+    """gat_op_readout_forward on device pointers: pooled [n_graphs][width] (and argmax for "max") of the rows of x."""
+    _chk(load_library().gat_op_readout_forward(C.c_void_p(d_x or None), x_stride, C.c_void_p(d_graph_ptr or None), n_graphs, n_rows, width,
+                                               readout_mode(mode), C.c_void_p(d_pooled or None), C.c_void_p(d_argmax or None),
+                                               C.c_void_p(stream or None)))
+
+
+def op_readout_backward(d_gpooled: int, d_graph_ptr: int, n_graphs: int, n_rows: int, width: int, mode, d_argmax: int, d_gh: int,
+                        gh_stride: int, stream: int = 0):
+    """gat_op_readout_backward on device pointers: floats 0..width-1 of every gh row from the pooled gradient."""
+    _chk(load_library().gat_op_readout_backward(C.c_void_p(d_gpooled or None), C.c_void_p(d_graph_ptr or None), n_graphs, n_rows, width,
+                                                readout_mode(mode), C.c_void_p(d_argmax or None), C.c_void_p(d_gh or None), gh_stride,
+                                                C.c_void_p(stream or None)))
 
 
 def _coo_sizes(n_in: int, n_rows: int, n_table: Optional[int], flags: int) -> int:

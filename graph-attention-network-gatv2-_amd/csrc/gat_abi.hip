@@ -210,6 +210,14 @@ struct gat_ctx {
     float* loss_out = nullptr; int32_t* correct_out = nullptr;
     float* clip_scratch = nullptr;
     float* y = nullptr;
+    // graph-level readout (gatv2_abi.h "graph-level readout"): mode, the graphs' row ranges, the graph of every row, the pooling's work
+    // list and partial rows, the pooled rows P the head reads, its gradient gP, and the argmax rows of GAT_READOUT_MAX
+    int32_t readout_mode = 0; int64_t n_graphs = 0;
+    int32_t* ro_graph_ptr = nullptr; int32_t* ro_node_graph = nullptr;       // [n_graphs + 1], [n_rows]
+    int4* ro_items = nullptr; int64_t ro_n_items = 0;
+    int4* ro_split = nullptr; int32_t ro_n_split = 0;
+    float* ro_part = nullptr; int32_t* ro_part_arg = nullptr;                // [n_parts][D_last]
+    float* ro_P = nullptr; float* ro_gP = nullptr; int32_t* ro_argmax = nullptr;     // [n_graphs][D_last]
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_free;
     std::vector<gat::Pending> ev_pending;
@@ -317,6 +325,9 @@ static bool norm_layer(const gat_ctx* c, int l) {
 // the context runs the residual route: the forward takes EdgeFwdExtras, the backward the N-sized kernel, G and agg in the edge backward
 static bool res_route(const gat_ctx* c) { return res_on(c) || norm_on(c); }
 static bool edge_feat_on(const gat_ctx* c) { return c->edge_dim > 0; }
+static bool readout_on(const gat_ctx* c) { return c->readout_mode != GAT_READOUT_NONE; }
+// rows of the output head, hence of the labels, the masks and y: the graphs with readout on, else the nodes
+static int64_t head_rows(const gat_ctx* c) { return readout_on(c) ? c->n_graphs : c->n_rows; }
 static float* We_of(gat_ctx* c, int l) { return param_of(c, GAT_PARAM_WE, c->layers[l].we_off); }
 static float* gWe_of(gat_ctx* c, int l) { return grad_of(c, GAT_PARAM_WE, c->layers[l].we_off); }
 // a step / phase on a context with edge_dim > 0 needs the attribute rows
@@ -552,12 +563,13 @@ static int ensure_buffers(gat_ctx* c) {
     GAT_TRY(dalloc(c, &c->gw_scratch, gw));
     c->gw_scratch_floats = gw;
     const int C = c->cfg.num_classes, DL = c->layers[L - 1].D;
-    GAT_TRY(dalloc(c, &c->hb_partial, (int64_t)head_bwd_blocks(N, C, DL) * C * DL));
-    GAT_TRY(dalloc(c, &c->loss_partial, head_blocks(N)));
-    GAT_TRY(dalloc(c, &c->correct_partial, head_blocks(N)));
+    const int64_t NH = head_rows(c);                 // graphs with readout on
+    GAT_TRY(dalloc(c, &c->hb_partial, (int64_t)head_bwd_blocks(NH, C, DL) * C * DL));
+    GAT_TRY(dalloc(c, &c->loss_partial, head_blocks(NH)));
+    GAT_TRY(dalloc(c, &c->correct_partial, head_blocks(NH)));
     GAT_TRY(dalloc(c, &c->loss_out, 1));
     GAT_TRY(dalloc(c, &c->correct_out, 1));
-    GAT_TRY(dalloc(c, &c->y, N * C));
+    GAT_TRY(dalloc(c, &c->y, NH * C));
     if (res_route(c)) {                              // gatv2_abi.h "residual" / "layer normalisation"
         if (norm_on(c)) GAT_TRY(dalloc(c, &c->norm_partial, (int64_t)L * 2 * kResPartialRows * c->HDmax));
         GAT_TRY(dalloc(c, &c->resG, N * c->HDmax));
@@ -870,7 +882,7 @@ int gat_layer_exchange(gat_ctx* c, int32_t l, int32_t* needed) {
 static void graph_drop_fwd(gat_ctx* c);             // a captured step (gat_step_graph) holds pointers: re-arm when they change
 static int set_labels_common(gat_ctx* c, const int32_t* labels, int64_t n_rows, hipMemcpyKind kind) {
     if (!c || !labels) return fail(GAT_E_INVALID, "gat_set_labels: null argument");
-    if (c->have_graph && n_rows != c->n_rows) return fail(GAT_E_INVALID, "Invalid labels length");
+    if (c->have_graph && n_rows != head_rows(c)) return fail(GAT_E_INVALID, readout_on(c) ? "Invalid labels length (with readout: one label per graph)" : "Invalid labels length");
     if (kind == hipMemcpyHostToDevice)
         for (int64_t i = 0; i < n_rows; ++i)
             if (labels[i] < 0 || labels[i] >= c->cfg.num_classes) return fail(GAT_E_INVALID, "label outside [0, num_classes)");
@@ -887,7 +899,8 @@ static int set_labels_common(gat_ctx* c, const int32_t* labels, int64_t n_rows, 
 // ---- train / validation masks (the reference trains and evaluates on ALL nodes, README R:134: "later") ----------
 static int upload_mask(gat_ctx* c, const uint8_t* mask, int64_t n_rows, uint8_t** dst) {
     if (!c->have_labels) return fail(GAT_E_STATE, "set the labels first");
-    if (n_rows != c->n_labels || (c->have_graph && n_rows != c->n_rows)) return fail(GAT_E_INVALID, "mask length differs from the node count");
+    if (n_rows != c->n_labels || (c->have_graph && n_rows != head_rows(c)))
+        return fail(GAT_E_INVALID, readout_on(c) ? "mask length differs from the graph count" : "mask length differs from the node count");
     if (!*dst) GAT_TRY(dalloc(c, dst, n_rows));
     GAT_HIP(hipMemcpyAsync(*dst, mask, (size_t)n_rows, hipMemcpyHostToDevice, c->stream));
     return 0;
@@ -1101,14 +1114,34 @@ static EdgeFwdArgs plan_forward_edges(gat_ctx* c, int32_t l) {
     return a;
 }
 
+// Readout: P = pool(hout of the last layer) in front of the head, gH = un-pool(gP) behind it (both no-ops with readout off).  Plain
+// launches on the context's stream: capturable, no host synchronisation.
+static int readout_pool(gat_ctx* c) {
+    if (!readout_on(c)) return 0;
+    const Layer& y = c->layers.back();
+    ReadoutFwdArgs a{};
+    a.x = y.hout; a.x_stride = y.D; a.graph_ptr = c->ro_graph_ptr;
+    a.items = c->ro_items; a.n_items = c->ro_n_items; a.split = c->ro_split; a.n_split = c->ro_n_split;
+    a.pooled = c->ro_P; a.argmax = c->ro_argmax; a.part = c->ro_part; a.part_arg = c->ro_part_arg;
+    a.width = y.D; a.mode = c->readout_mode;
+    Scope t(c, GAT_K_HEAD_FWD);
+    return launch_readout_forward(a, c->stream);
+}
+static int readout_unpool(gat_ctx* c) {
+    if (!readout_on(c)) return 0;
+    ReadoutBwdArgs a{};
+    a.gpooled = c->ro_gP; a.argmax = c->ro_argmax; a.graph_ptr = c->ro_graph_ptr; a.node_graph = c->ro_node_graph;
+    a.gh = c->gH; a.gh_stride = c->gh_stride; a.n_rows = c->n_rows;
+    a.width = c->layers.back().D; a.mode = c->readout_mode;
+    Scope t(c, GAT_K_HEAD_BWD);
+    return launch_readout_backward(a, c->stream);
+}
+static void head_args(gat_ctx* c, HeadArgs* f, HeadBwdArgs* b);
 int gat_head_forward(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
     GAT_TRY(check_layer(c, 0));
-    const Layer& y = c->layers.back();
-    HeadArgs a{};
-    a.Wo = Wo_of(c); a.HL = y.hout; a.labels = c->labels_eff ? c->labels_eff : c->labels; a.y = c->y;
-    a.loss_partial = c->loss_partial; a.correct_partial = c->correct_partial;
-    a.loss_out = c->loss_out; a.correct_out = c->correct_out;
-    a.n_rows = c->n_rows; a.C = c->cfg.num_classes; a.DL = y.D;
+    HeadArgs a{}; HeadBwdArgs unused{};
+    head_args(c, &a, &unused);
+    GAT_TRY(readout_pool(c));
     {
         Scope t(c, GAT_K_HEAD_FWD);
         GAT_TRY(launch_head_forward(a, c->stream));
@@ -1127,13 +1160,13 @@ int gat_head_forward(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
 
 int gat_head_backward(gat_ctx* c) {
     GAT_TRY(check_layer(c, 0));
-    const Layer& y = c->layers.back();
-    HeadBwdArgs a{};
-    a.Wo = Wo_of(c); a.HL = y.hout; a.y = c->y; a.labels = c->labels_eff ? c->labels_eff : c->labels; a.hpre = y.hpre; a.g = y.g; a.gh_out = c->gH; a.gh_stride = c->gh_stride;
-    a.gradWo = gWo_of(c); a.partial = c->hb_partial; a.n_rows = c->n_rows; a.C = c->cfg.num_classes;
-    a.DL = y.D; a.H = y.H; a.slope = c->cfg.negative_slope; a.flat_index = c->cfg.flat_lrelu_index;
-    Scope t(c, GAT_K_HEAD_BWD);
-    return launch_head_backward(a, c->stream);
+    HeadArgs unused{}; HeadBwdArgs a{};
+    head_args(c, &unused, &a);
+    {
+        Scope t(c, GAT_K_HEAD_BWD);
+        GAT_TRY(launch_head_backward(a, c->stream));
+    }
+    return readout_unpool(c);
 }
 
 // Arguments of layer l's edge backward (shared by gat_layer_backward_edges and the fused last layer of gat_step).
@@ -1361,6 +1394,12 @@ static void head_args(gat_ctx* c, HeadArgs* f, HeadBwdArgs* b) {
     b->Wo = Wo_of(c); b->HL = y.hout; b->y = c->y; b->labels = c->labels_eff ? c->labels_eff : c->labels; b->hpre = y.hpre; b->g = y.g; b->gh_out = c->gH; b->gh_stride = c->gh_stride;
     b->gradWo = gWo_of(c); b->partial = c->hb_partial; b->n_rows = c->n_rows; b->C = c->cfg.num_classes;
     b->DL = y.D; b->H = y.H; b->slope = c->cfg.negative_slope; b->flat_index = c->cfg.flat_lrelu_index;
+    if (readout_on(c)) {
+        // the head on the pooled rows: one row per graph, its gradient into gP (rows of D_last floats); the un-pool fills c->gH
+        // afterwards and the last layer's edge backward expands that as always, so the head never writes a g of its own
+        f->HL = b->HL = c->ro_P; f->n_rows = b->n_rows = c->n_graphs;
+        b->g = nullptr; b->hpre = nullptr; b->gh_out = c->ro_gP; b->gh_stride = y.D;
+    }
 }
 // gat_step: the head's forward and backward as ONE kernel when nothing needs the class probabilities in HBM
 static bool fused_head(gat_ctx* c) {
@@ -1373,16 +1412,20 @@ static int head_step(gat_ctx* c, bool with_gh = true) {
     HeadArgs f{}; HeadBwdArgs b{};
     head_args(c, &f, &b);
     if (!with_gh) b.gh_out = nullptr;               // loss, #correct and grad_Wo only (the fused last layer formed gH itself)
-    Scope t(c, GAT_K_HEAD_BWD);
-    c->y_valid = false;
-    return launch_head_step(f, b, c->stream);
+    GAT_TRY(readout_pool(c));
+    {
+        Scope t(c, GAT_K_HEAD_BWD);
+        c->y_valid = false;
+        GAT_TRY(launch_head_step(f, b, c->stream));
+    }
+    return readout_unpool(c);
 }
 // gat_step: the last layer's forward edge pass, the output head and its backward edge pass fused per destination row
 // (edge_last_fused_kernel) — single shard, fp32, H*D = 64 / D = 8 record path.  The idea: the separate backward finds nothing
 // of the forward's rows left in the caches when a pass's gathers exceed the Infinity Cache; fused per row, the second walk of
 // a row's sources comes a few microseconds after the first.
 static bool fused_last(gat_ctx* c) {
-    if (!fused_head(c) || bf16(c) || c->comm || c->n_table != c->n_rows || c->cfg.flat_lrelu_index || res_route(c) || edge_feat_on(c)) return false;   // no residual / norm / edge-feature form
+    if (!fused_head(c) || bf16(c) || c->comm || c->n_table != c->n_rows || c->cfg.flat_lrelu_index || res_route(c) || edge_feat_on(c) || readout_on(c)) return false;   // no residual / norm / edge-feature / readout form
     const Layer& y = c->layers.back();
     if (!edge_fast_path(y.H, y.D, c->n_table) || !y.stash || c->stash == nullptr || c->gH == nullptr) return false;
     if (!edge_last_fused_supported(y.H, y.D, c->cfg.num_classes) || c->dbg != 0 || drop_on(c)) return false;   // no dropout form
@@ -1733,6 +1776,143 @@ int gat_set_edge_features_device(gat_ctx* c, const float* d_ea, int64_t n_edges,
     return set_edge_features_common(c, d_ea, n_edges, edge_dim, hipMemcpyDeviceToDevice);
 }
 // ---- layer normalisation ----------------------------------------------------------------------------------------
+// ---- graph-level readout ------------------------------------------------------------------------------------------
+// device copy of one of the plan's int4 lists (at least one entry allocated)
+static int upload_int4(gat_ctx* c, int4** d, const std::vector<int32_t>& h) {
+    GAT_TRY(dalloc(c, d, std::max<int64_t>((int64_t)(h.size() / 4), 1)));
+    if (!h.empty()) GAT_HIP(hipMemcpyAsync(*d, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+static int set_readout_common(gat_ctx* c, int32_t mode, const int32_t* graph_ptr, int64_t n_graphs, bool on_host) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (mode < GAT_READOUT_NONE || mode > GAT_READOUT_MAX) return fail(GAT_E_INVALID, "gat_set_readout: mode must be 0 (none), 1 (mean), 2 (sum) or 3 (max)");
+    if (mode == GAT_READOUT_NONE) return 0;              // the default: nothing is touched
+    if (readout_on(c)) return fail(GAT_E_STATE, "gat_set_readout: readout already set (create a new context)");
+    if (!c->have_graph) return fail(GAT_E_STATE, "gat_set_readout: set the graph first");
+    if (c->have_labels) return fail(GAT_E_STATE, "gat_set_readout: call it before gat_set_labels (the label, mask and head buffers are sized by it)");
+    if (c->n_table != c->n_rows || c->comm)
+        return fail(GAT_E_UNSUPPORTED, "gat_set_readout: not on a destination-range shard or with a transport (a graph may straddle shards)");
+    if (c->cfg.flat_lrelu_index)
+        return fail(GAT_E_UNSUPPORTED, "gat_set_readout: not with flat_lrelu_index = 1 (the head would write the last layer's g itself)");
+#ifdef GAT_EXPERIMENTS                               // (the release library does not know the switch's name)
+    if (c->dbg != 0) return fail(GAT_E_UNSUPPORTED, "gat_set_readout: not with a GAT_DBG timing experiment");
+#endif
+    if (!graph_ptr) return fail(GAT_E_INVALID, "gat_set_readout: null graph_ptr");
+    if (n_graphs < 1 || n_graphs >= 0x7fffffffLL) return fail(GAT_E_INVALID, "gat_set_readout: n_graphs must be >= 1 and fit int32");
+    const int64_t N = c->n_rows, G = n_graphs;
+    int32_t problem = 0; int64_t where = -1;
+    std::vector<int32_t> fetched;
+    if (on_host) {
+        GAT_TRY(graph_ptr_check_host(graph_ptr, G, N, &problem, &where));
+    } else {                                             // the same rules on the caller's device array, before anything walks it
+        GAT_TRY(graph_ptr_check_device(graph_ptr, G, N, &problem, &where, c->stream));
+    }
+    if (problem) return fail(GAT_E_INVALID, "gat_set_readout: " + graph_ptr_problem_text(problem, where, N));
+    if (!on_host) {                                      // the work list is built on the host (as the edge passes' is)
+        fetched.resize((size_t)G + 1);
+        GAT_HIP(hipMemcpy(fetched.data(), graph_ptr, (size_t)(G + 1) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    const int32_t* gp = on_host ? graph_ptr : fetched.data();
+    ReadoutPlan plan;
+    build_readout_plan(gp, G, plan);
+    const int32_t DL = c->layers.back().D;
+    GAT_TRY(dalloc(c, &c->ro_graph_ptr, G + 1));
+    GAT_TRY(dalloc(c, &c->ro_node_graph, N));
+    GAT_HIP(hipMemcpyAsync(c->ro_graph_ptr, gp, (size_t)(G + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    GAT_TRY(upload_int4(c, &c->ro_items, plan.items));
+    GAT_TRY(upload_int4(c, &c->ro_split, plan.split));
+    GAT_TRY(dalloc(c, &c->ro_part, (int64_t)std::max<int32_t>(plan.n_parts, 1) * DL));
+    if (mode == GAT_READOUT_MAX) {
+        GAT_TRY(dalloc(c, &c->ro_part_arg, (int64_t)std::max<int32_t>(plan.n_parts, 1) * DL));
+        GAT_TRY(dalloc(c, &c->ro_argmax, G * DL));
+    }
+    GAT_TRY(dalloc(c, &c->ro_P, G * DL));
+    GAT_TRY(dalloc(c, &c->ro_gP, G * DL));
+    GAT_TRY(launch_node_graph(c->ro_graph_ptr, G, N, c->ro_node_graph, c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));            // (the host lists go out of scope)
+    c->ro_n_items = plan.n_items; c->ro_n_split = plan.n_split;
+    c->readout_mode = mode; c->n_graphs = G;
+    c->y_valid = false;                                  // the head's outputs change shape: nothing of an earlier forward stays
+    graph_drop_fwd(c);
+    return 0;
+}
+int gat_set_readout(gat_ctx* c, int32_t mode, const int32_t* graph_ptr, int64_t n_graphs) {
+    return set_readout_common(c, mode, graph_ptr, n_graphs, true);
+}
+int gat_set_readout_device(gat_ctx* c, int32_t mode, const int32_t* d_graph_ptr, int64_t n_graphs) {
+    return set_readout_common(c, mode, d_graph_ptr, n_graphs, false);
+}
+int gat_readout_info(gat_ctx* c, int32_t* mode, int64_t* n_graphs) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (mode) *mode = c->readout_mode;
+    if (n_graphs) *n_graphs = c->n_graphs;
+    return 0;
+}
+// The two kernels on caller-owned device pointers.  The graph_ptr is checked on the device before anything reads through it.
+struct ReadoutTmp {
+    std::vector<void*> bufs;
+    ~ReadoutTmp() { for (void* p : bufs) (void)hipFree(p); }
+    int get(void** p, int64_t bytes) {
+        GAT_HIP(hipMalloc(p, (size_t)std::max<int64_t>(bytes, 16)));
+        bufs.push_back(*p);
+        return 0;
+    }
+};
+static int op_readout_check(const char* who, const int32_t* d_graph_ptr, int64_t n_graphs, int64_t n_rows, int32_t width, int32_t mode, hipStream_t s) {
+    if (!d_graph_ptr) return fail(GAT_E_INVALID, std::string(who) + ": null argument");
+    if (mode < GAT_READOUT_MEAN || mode > GAT_READOUT_MAX) return fail(GAT_E_INVALID, std::string(who) + ": mode must be 1 (mean), 2 (sum) or 3 (max)");
+    if (n_graphs < 1 || n_graphs >= 0x7fffffffLL || n_rows < 0 || n_rows >= 0x7fffffffLL || width < 1) return fail(GAT_E_INVALID, std::string(who) + ": bad sizes");
+    int32_t problem = 0; int64_t where = -1;
+    GAT_TRY(graph_ptr_check_device(d_graph_ptr, n_graphs, n_rows, &problem, &where, s));
+    if (problem) return fail(GAT_E_INVALID, std::string(who) + ": " + graph_ptr_problem_text(problem, where, n_rows));
+    return 0;
+}
+int gat_op_readout_forward(const float* d_x, int64_t x_stride, const int32_t* d_graph_ptr, int64_t n_graphs, int64_t n_rows,
+                           int32_t width, int32_t mode, float* d_pooled, int32_t* d_argmax, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    GAT_TRY(op_readout_check("gat_op_readout_forward", d_graph_ptr, n_graphs, n_rows, width, mode, s));
+    if ((!d_x && n_rows > 0) || !d_pooled || (mode == GAT_READOUT_MAX && !d_argmax)) return fail(GAT_E_INVALID, "gat_op_readout_forward: null argument");
+    if (x_stride < width) return fail(GAT_E_INVALID, "gat_op_readout_forward: x_stride below width");
+    std::vector<int32_t> gp((size_t)n_graphs + 1);
+    GAT_HIP(hipMemcpy(gp.data(), d_graph_ptr, gp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    ReadoutPlan plan;
+    build_readout_plan(gp.data(), n_graphs, plan);
+    ReadoutTmp tmp;
+    int4 *items = nullptr, *split = nullptr; float* part = nullptr; int32_t* part_arg = nullptr;
+    GAT_TRY(tmp.get((void**)&items, plan.n_items * (int64_t)sizeof(int4)));
+    GAT_TRY(tmp.get((void**)&split, plan.n_split * (int64_t)sizeof(int4)));
+    GAT_TRY(tmp.get((void**)&part, (int64_t)plan.n_parts * width * 4));
+    GAT_TRY(tmp.get((void**)&part_arg, (int64_t)plan.n_parts * width * 4));
+    GAT_HIP(hipMemcpyAsync(items, plan.items.data(), plan.items.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (plan.n_split > 0) GAT_HIP(hipMemcpyAsync(split, plan.split.data(), plan.split.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    ReadoutFwdArgs a{};
+    a.x = d_x ? d_x : d_pooled; a.x_stride = x_stride; a.graph_ptr = d_graph_ptr;      // (n_rows == 0: no item has a row to load)
+    a.items = items; a.n_items = plan.n_items; a.split = split; a.n_split = plan.n_split;
+    a.pooled = d_pooled; a.argmax = d_argmax; a.part = part; a.part_arg = part_arg; a.width = width; a.mode = mode;
+    int rc = launch_readout_forward(a, s);
+    const hipError_t e = hipStreamSynchronize(s);        // before the scratch is freed
+    if (rc == 0 && e != hipSuccess) rc = fail((int)e, std::string("gat_op_readout_forward: ") + hipGetErrorString(e));
+    return rc;
+}
+int gat_op_readout_backward(const float* d_gpooled, const int32_t* d_graph_ptr, int64_t n_graphs, int64_t n_rows, int32_t width,
+                            int32_t mode, const int32_t* d_argmax, float* d_gh, int64_t gh_stride, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    GAT_TRY(op_readout_check("gat_op_readout_backward", d_graph_ptr, n_graphs, n_rows, width, mode, s));
+    if (!d_gpooled || (!d_gh && n_rows > 0) || (mode == GAT_READOUT_MAX && !d_argmax)) return fail(GAT_E_INVALID, "gat_op_readout_backward: null argument");
+    if (gh_stride < width) return fail(GAT_E_INVALID, "gat_op_readout_backward: gh_stride below width");
+    if (n_rows == 0) return 0;
+    ReadoutTmp tmp;
+    int32_t* node_graph = nullptr;
+    GAT_TRY(tmp.get((void**)&node_graph, n_rows * 4));
+    GAT_TRY(launch_node_graph(d_graph_ptr, n_graphs, n_rows, node_graph, s));
+    ReadoutBwdArgs a{};
+    a.gpooled = d_gpooled; a.argmax = d_argmax; a.graph_ptr = d_graph_ptr; a.node_graph = node_graph;
+    a.gh = d_gh; a.gh_stride = gh_stride; a.n_rows = n_rows; a.width = width; a.mode = mode;
+    int rc = launch_readout_backward(a, s);
+    const hipError_t e = hipStreamSynchronize(s);
+    if (rc == 0 && e != hipSuccess) rc = fail((int)e, std::string("gat_op_readout_backward: ") + hipGetErrorString(e));
+    return rc;
+}
 int gat_set_norm(gat_ctx* c, int32_t flags, float eps) {
     if (!c) return fail(GAT_E_INVALID, "null context");
     if (flags & ~(GAT_NORM_LAYER | GAT_NORM_SKIP_LAST)) return fail(GAT_E_INVALID, "gat_set_norm: unknown flag bits");
@@ -1834,6 +2014,7 @@ static int check_comm_target(gat_ctx* c, int32_t world, int32_t rank) {
     if (!c) return fail(GAT_E_INVALID, "null context");
     if (c->comm) return fail(GAT_E_STATE, "a transport is already attached");
     if (!c->have_graph) return fail(GAT_E_STATE, "gat_comm_init: set the graph first");
+    if (readout_on(c)) return fail(GAT_E_UNSUPPORTED, "gat_comm_init: not on a readout context (a graph may straddle shards)");
     if (world < 1 || rank < 0 || rank >= world) return fail(GAT_E_INVALID, "gat_comm_init: bad world / rank");
     if (c->n_table % world != 0 || c->table_row0 != (int64_t)rank * (c->n_table / world) || c->n_rows > c->n_table / world)
         return fail(GAT_E_INVALID, "gat_comm_init: the source table must be [world][max_rows] with this shard's rows at rank*max_rows");
@@ -2008,10 +2189,15 @@ int gat_tap(gat_ctx* c, int tensor, int32_t l, void* host, int64_t count) {
         case GAT_TAP_SUM: GAT_TRY(need(N * y.H)); return transposed(y.zstat, N, y.H, false);
         case GAT_TAP_HPRE: GAT_TRY(need(N * y.HD)); return d2h(c, host, y.hpre, N * y.HD * sizeof(float));
         case GAT_TAP_HOUT: { const int64_t n = N * (last ? y.D : y.HD); GAT_TRY(need(n)); return d2h(c, host, y.hout, n * sizeof(float)); }
-        case GAT_TAP_Y:
-            GAT_TRY(need(N * c->cfg.num_classes));
+        case GAT_TAP_Y:                               // one row per graph with readout on
+            GAT_TRY(need(head_rows(c) * c->cfg.num_classes));
             if (!c->y_valid) GAT_TRY(gat_head_forward(c, nullptr, nullptr));     // after a fused head step: y = f(H_L, Wo), both still there
-            return d2h(c, host, c->y, N * c->cfg.num_classes * sizeof(float));
+            return d2h(c, host, c->y, head_rows(c) * c->cfg.num_classes * sizeof(float));
+        case GAT_TAP_POOLED:                          // what the last head forward (or head step) pooled
+            if (!readout_on(c)) return fail(GAT_E_STATE, "gat_tap: GAT_TAP_POOLED needs gat_set_readout");
+            if (!last) return fail(GAT_E_INVALID, "gat_tap: GAT_TAP_POOLED exists for the last layer only");
+            GAT_TRY(need(c->n_graphs * y.D));
+            return d2h(c, host, c->ro_P, c->n_graphs * y.D * sizeof(float));
         case GAT_TAP_G: {
             GAT_TRY(need(N * y.HD));
             if (norm_layer(c, l)) {                     // dL/dh_pre through the normalisation: the backward kernel's row function again, on the
@@ -2288,8 +2474,24 @@ static void edge_feature_bytes(const gat_ctx* c, double* k) {
         k[GAT_K_GRAD_W] += 4.0 * (E * HD + E * Fe + HD * Fe);
     }
 }
+static int algorithmic_bytes_nodes(gat_ctx* c, double* bytes_step, double* per_kernel);
 int gat_algorithmic_bytes(gat_ctx* c, double* bytes_step, double* per_kernel) {
     if (!c || !c->have_graph) return fail(GAT_E_STATE, "graph not set");
+    if (!readout_on(c)) return algorithmic_bytes_nodes(c, bytes_step, per_kernel);
+    // readout (gatv2_abi.h "graph-level readout"): the head classes priced with G rows; the pool reads N*DL and writes G*DL, the un-pool
+    // reads G*DL and writes N*DL (under misc, fp32)
+    double k[GAT_K_COUNT] = {0}, tot = 0;
+    GAT_TRY(algorithmic_bytes_nodes(c, nullptr, k));
+    const double N = (double)c->n_rows, G = (double)c->n_graphs, DL = c->layers.back().D;
+    const double head = 2.0 * 4.0 * G * (DL + 2.0 * c->cfg.num_classes + 2.0);
+    k[GAT_K_HEAD_FWD] = head / 2; k[GAT_K_HEAD_BWD] = head / 2;
+    k[GAT_K_MISC] += 4.0 * (N * DL + G * DL) + 4.0 * (G * DL + N * DL);
+    for (int i = 0; i < GAT_K_COUNT; ++i) { tot += k[i]; if (per_kernel) per_kernel[i] = k[i]; }
+    if (bytes_step) *bytes_step = tot;
+    return 0;
+}
+// the figure of a context whose head has one row per node
+static int algorithmic_bytes_nodes(gat_ctx* c, double* bytes_step, double* per_kernel) {
     if (edge_feat_on(c) && !res_route(c)) {
         double k[GAT_K_COUNT] = {0}, tot = 0;
         GAT_TRY(gat_algorithmic_bytes_shape(&c->cfg, c->n_rows, c->n_edges, c->n_table, c->Xtab != nullptr, nullptr, k));

@@ -490,6 +490,43 @@ int launch_head_backward(const HeadBwdArgs& a, hipStream_t s);
 bool head_step_supported(const HeadBwdArgs& b);
 int launch_head_step(const HeadArgs& f, const HeadBwdArgs& b, hipStream_t s);
 
+// ---- graph-level readout (gat_readout.hip; the contract is in gatv2_abi.h "graph-level readout") ----------------------
+// Work decomposition of the pooling: a graph of at most kReadoutSegRows rows is one item (an empty graph too), a longer one is cut into
+// segments of kReadoutSegRows rows whose partial rows the combine kernel adds in ascending order.  256 like the hub rows' kSegEdges.
+constexpr int kReadoutSegRows = 256;
+struct ReadoutPlan {
+    std::vector<int32_t> items;       // 4 per item {graph, first row, end row, partial row | -1}
+    std::vector<int32_t> split;       // 4 per split graph {graph, first partial row, partial rows, -}
+    int64_t n_items = 0;
+    int32_t n_split = 0, n_parts = 0;
+};
+void build_readout_plan(const int32_t* graph_ptr, int64_t n_graphs, ReadoutPlan& p);
+// the rules of gat_set_readout on a graph_ptr: *problem = 0, or 1 (entry 0 is not 0) / 2 (the last entry is not n_rows) / 3 (decreasing),
+// *where = the lowest offending index (-1: none).  The device form is one pass and synchronises s.
+int graph_ptr_check_host(const int32_t* graph_ptr, int64_t n_graphs, int64_t n_rows, int32_t* problem, int64_t* where);
+int graph_ptr_check_device(const int32_t* d_graph_ptr, int64_t n_graphs, int64_t n_rows, int32_t* problem, int64_t* where, hipStream_t s);
+std::string graph_ptr_problem_text(int32_t problem, int64_t where, int64_t n_rows);
+// node_graph[n] = graph of row n (a checked graph_ptr)
+int launch_node_graph(const int32_t* d_graph_ptr, int64_t n_graphs, int64_t n_rows, int32_t* d_node_graph, hipStream_t s);
+struct ReadoutFwdArgs {
+    const float* x; int64_t x_stride;       // [n_rows] rows of x_stride floats, the first `width` pooled
+    const int32_t* graph_ptr;               // [n_graphs + 1]
+    const int4* items; int64_t n_items;     // ReadoutPlan::items
+    const int4* split; int32_t n_split;     // ReadoutPlan::split
+    float* pooled; int32_t* argmax;         // [n_graphs][width]; argmax: GAT_READOUT_MAX only
+    float* part; int32_t* part_arg;         // [n_parts][width] partial rows of the segments (part_arg: GAT_READOUT_MAX only)
+    int32_t width, mode;
+};
+int launch_readout_forward(const ReadoutFwdArgs& a, hipStream_t s);
+// gh[n][0:width] = gpooled[g] (SUM), gpooled[g] / cnt_g (MEAN), gpooled[g][d] where argmax[g][d] == n, else 0 (MAX); floats behind
+// column `width` of a gh row are not touched
+struct ReadoutBwdArgs {
+    const float* gpooled; const int32_t* argmax; const int32_t* graph_ptr; const int32_t* node_graph;
+    float* gh; int64_t gh_stride; int64_t n_rows;
+    int32_t width, mode;
+};
+int launch_readout_backward(const ReadoutBwdArgs& a, hipStream_t s);
+
 // train / validation masks (README R:134 "later"): labels_eff = mask ? label : ~label — the head kernels skip negative
 // labels (no loss, no count, dz = 0); eval_mask: fixed-order block partials of loss / #correct / #nodes over a mask
 int launch_apply_mask(const int32_t* labels, const uint8_t* mask, int32_t* eff, int64_t n, hipStream_t s);

@@ -35,6 +35,10 @@
 // parameter, and --dump-params / --load-params carry We behind beta, only with the flag.  CSR datasets as they are, one rank: the flag
 // is refused with an edges.txt dataset, with --add-self-loops / --undirected / --coalesce (the graph would be rebuilt and the rows
 // would no longer match its edges) and with --ranks > 1.
+// --readout mean|sum|max: graph classification (gatv2_abi.h "graph-level readout"): the dataset is a batch of graphs packed block-diagonally
+// into one CSR, graph_ptr.txt of the dataset folder holds G+1 integers (graph g owns nodes graph_ptr[g] .. graph_ptr[g+1]-1), and
+// labels.txt, --train-mask and --val-mask files hold G lines.  The last layer's rows are pooled per graph in front of the output head;
+// the epoch lines keep their format, loss and accuracy are over graphs.  One rank only (a graph may straddle shards); --cache is not used.
 // --add-self-loops / --undirected / --coalesce: the graph is rebuilt on the device before training (gat_graph_from_coo:
 // GAT_GRAPH_SELF_LOOPS / SYMMETRIZE / COALESCE, applied in that order); a CSR dataset is expanded to an edge list first.
 // Edge-list dataset: a folder with edges.txt (one "src dst" pair per line, a message flows src -> dst) instead of
@@ -92,6 +96,7 @@ struct Options {
     int residual_flags = 0;                           // GAT_RES_*: --residual, --bias
     int norm_flags = 0; float norm_eps = 1e-5f;       // GAT_NORM_*: --layer-norm, --norm-skip-last; --norm-eps
     int graph_flags = 0;                  // GAT_GRAPH_*: --add-self-loops, --undirected, --coalesce
+    std::string readout;                  // --readout mean|sum|max: graph_ptr.txt of the dataset folder, one label per graph
     bool edge_features = false;           // --edge-features: edge_features.txt of the dataset folder enters the attention score
 };
 
@@ -119,6 +124,9 @@ const char* kUsage =
     "            --edge-features    per-edge attributes enter the attention score: edge_features.txt of the dataset folder, E lines of Fe\n"
     "                          values in CSR order (CSR datasets only, not with the graph flags, --ranks 1; We follows beta in\n"
     "                          --dump-params / --load-params)\n"
+    "            --readout mean|sum|max   graph classification: graph_ptr.txt of the dataset folder holds G+1 integers (graph g owns nodes\n"
+    "                          graph_ptr[g] .. graph_ptr[g+1]-1); labels.txt, --train-mask and --val-mask then hold G lines; the last\n"
+    "                          layer's rows are pooled per graph before the output head; loss and accuracy are over graphs (--ranks 1)\n"
     "            --ranks P [--transport rccl|host] [--halo 0|1|2]\n";
 
 struct RankEnv {                      // one forked process per GPU
@@ -205,6 +213,7 @@ Options parse_args(int argc, char** argv) {
         else if (a == "--norm-skip-last") o.norm_flags |= GAT_NORM_SKIP_LAST;
         else if (a == "--norm-eps" && has_val) o.norm_eps = std::strtof(argv[++i], nullptr);
         else if (a == "--edge-features") o.edge_features = true;
+        else if (a == "--readout" && has_val) o.readout = argv[++i];
         else if (a == "--transport" && has_val) {
             o.transport = argv[++i];
             if (o.transport != "rccl" && o.transport != "host") die("Invalid transport choice. Use 'rccl' or 'host'\n");
@@ -400,22 +409,34 @@ int run(const Options& o, const RankEnv& env) {
     // start-up bottleneck at Products scale (~2 GB of text); the cache is rewritten whenever a text
     // file is newer than it.
     const std::string cache = path + "gatv2_cache.bin";
+    const int readout = o.readout == "mean" ? GAT_READOUT_MEAN : o.readout == "sum" ? GAT_READOUT_SUM : o.readout == "max" ? GAT_READOUT_MAX : GAT_READOUT_NONE;
     const bool edge_list = edge_list_dataset(path);
     std::vector<int32_t> e_src, e_dst;
     if (edge_list) {
         load_features(path + "features.txt", x, N, F0);
         if (!env.graph.row_ptr && !load_edges(path + "edges.txt", e_src, e_dst)) return 1;
         load_ints(path + "labels.txt", labels);
-        if ((int64_t)labels.size() != N) { std::cerr << "Invalid labels length\n"; return 1; }
-    } else if (!(o.cache && load_cache(cache, path, x, N, F0, row_ptr, col_idx, labels))) {
+        if (!readout && (int64_t)labels.size() != N) { std::cerr << "Invalid labels length\n"; return 1; }
+    } else if (!(o.cache && !readout && load_cache(cache, path, x, N, F0, row_ptr, col_idx, labels))) {
         load_features(path + "features.txt", x, N, F0);
         load_ints(path + "row_ptr.txt", row_ptr);
         if ((int64_t)row_ptr.size() != N + 1) { std::cerr << "Invalid row_ptr length\n"; return 1; }
         load_ints(path + "col_idx.txt", col_idx);
         load_ints(path + "labels.txt", labels);
-        if ((int64_t)labels.size() != N) { std::cerr << "Invalid labels length\n"; return 1; }
-        if (o.cache) save_cache(cache, x, N, F0, row_ptr, col_idx, labels);
+        if (!readout && (int64_t)labels.size() != N) { std::cerr << "Invalid labels length\n"; return 1; }
+        if (o.cache && !readout) save_cache(cache, x, N, F0, row_ptr, col_idx, labels);
     }
+    // --readout: the graphs' node ranges; labels.txt then holds one line per graph
+    std::vector<int32_t> graph_ptr;
+    if (readout) {
+        load_ints(path + "graph_ptr.txt", graph_ptr);
+        bool ok = graph_ptr.size() >= 2 && graph_ptr.front() == 0 && (int64_t)graph_ptr.back() == N;
+        for (size_t i = 0; ok && i + 1 < graph_ptr.size(); ++i) ok = graph_ptr[i + 1] >= graph_ptr[i];
+        if (!ok) { std::cerr << "Invalid graph_ptr.txt: expected G+1 non-decreasing integers from 0 to the node count\n"; return 1; }
+        if (labels.size() + 1 != graph_ptr.size()) { std::cerr << "Invalid labels length\n"; return 1; }
+        std::cout << "Readout: " << o.readout << " over " << graph_ptr.size() - 1 << " graphs" << std::endl;
+    }
+    const int64_t NH = readout ? (int64_t)graph_ptr.size() - 1 : N;        // rows of the output head: graphs with --readout, else nodes
     if (env.graph.row_ptr) {                    // built before the ranks were forked
         if (env.graph.n != N) { std::cerr << "Invalid labels length\n"; return 1; }
         row_ptr.assign(env.graph.row_ptr, env.graph.row_ptr + N + 1);
@@ -509,7 +530,8 @@ int run(const Options& o, const RankEnv& env) {
     if (env.world == 1) {
         check(gat_set_graph(ctx, row_ptr.data(), col_idx.data(), N, E, N, 0), "csr_to_coo_kernel");
         check(gat_set_features(ctx, x.data(), N, F0), "gat_set_features");
-        check(gat_set_labels(ctx, labels.data(), N), "gat_set_labels");
+        if (readout) check(gat_set_readout(ctx, readout, graph_ptr.data(), NH), "gat_set_readout");      // before the labels: they are per graph
+        check(gat_set_labels(ctx, labels.data(), NH), "gat_set_labels");
         if (o.edge_features) check(gat_set_edge_features(ctx, ea.data(), E, Fe), "gat_set_edge_features");
     } else {
         // this rank's destination range; sources as rows of the padded [world][max_rows] table; the static
@@ -557,13 +579,13 @@ int run(const Options& o, const RankEnv& env) {
     }
     // optional splits: loss / accuracy / gradient over the training nodes, an extra validation line per epoch
     std::vector<uint8_t> train_m, val_m;
-    int64_t n_train = N;
+    int64_t n_train = NH;
     auto load_mask = [&](const std::string& file, std::vector<uint8_t>& m, const char* what) {
         std::vector<int32_t> v;
         load_ints(file, v);
-        if ((int64_t)v.size() != N) die(std::string("Invalid ") + what + " length\n");
-        m.resize((size_t)N);
-        for (int64_t i = 0; i < N; ++i) m[(size_t)i] = v[(size_t)i] != 0;
+        if ((int64_t)v.size() != NH) die(std::string("Invalid ") + what + " length\n");
+        m.resize((size_t)NH);
+        for (int64_t i = 0; i < NH; ++i) m[(size_t)i] = v[(size_t)i] != 0;
     };
     if (!o.train_mask.empty()) {
         load_mask(o.train_mask, train_m, "train mask");
@@ -571,9 +593,9 @@ int run(const Options& o, const RankEnv& env) {
         for (uint8_t b : train_m) n_train += b;
         if (n_train == 0) die("Error: --train-mask selects no node\n");
         const int64_t r0 = env.world == 1 ? 0 : gatshard::make_plan(row_ptr.data(), N, env.world, env.rank).row0();
-        const int64_t nr = env.world == 1 ? N : gatshard::make_plan(row_ptr.data(), N, env.world, env.rank).n_rows();
+        const int64_t nr = env.world == 1 ? NH : gatshard::make_plan(row_ptr.data(), N, env.world, env.rank).n_rows();
         check(gat_set_train_mask(ctx, train_m.data() + r0, nr), "gat_set_train_mask");
-        std::printf("Training nodes: %lld of %lld\n", (long long)n_train, (long long)N);
+        std::printf("Training nodes: %lld of %lld\n", (long long)n_train, (long long)NH);
     }
     if (!o.val_mask.empty()) {
         if (env.world != 1) die("Error: --val-mask needs --ranks 1\n");
@@ -613,7 +635,7 @@ int run(const Options& o, const RankEnv& env) {
         std::printf("\nAvg Loss: %f, Accuracy: %.2f%%\n", loss_sum / n_train, 100.0f * (static_cast<float>(n_correct) / n_train));
         if (!val_m.empty() && !dropout) {
             double vl = 0.0; int32_t vc = 0, vn = 0;
-            check(gat_eval_mask(ctx, val_m.data(), N, &vl, &vc, &vn), "gat_eval_mask");
+            check(gat_eval_mask(ctx, val_m.data(), NH, &vl, &vc, &vn), "gat_eval_mask");
             std::printf("Val Loss: %f, Val Accuracy: %.2f%%\n", vn ? vl / vn : 0.0, vn ? 100.0f * (static_cast<float>(vc) / vn) : 0.0f);
         }
         check(gat_backward(ctx), "gatv2 backward");
@@ -625,7 +647,7 @@ int run(const Options& o, const RankEnv& env) {
             double vl = 0.0; int32_t vc = 0, vn = 0;
             check(gat_set_training(ctx, 0), "gat_set_training");
             check(gat_forward(ctx, nullptr, nullptr), "gatv2 forward");
-            check(gat_eval_mask(ctx, val_m.data(), N, &vl, &vc, &vn), "gat_eval_mask");
+            check(gat_eval_mask(ctx, val_m.data(), NH, &vl, &vc, &vn), "gat_eval_mask");
             check(gat_set_training(ctx, 1), "gat_set_training");
             std::printf("Val Loss: %f, Val Accuracy: %.2f%%\n", vn ? vl / vn : 0.0, vn ? 100.0f * (static_cast<float>(vc) / vn) : 0.0f);
         }
@@ -667,10 +689,15 @@ int main(int argc, char** argv) {
     }
     // --help, --edge-features with what it cannot be combined with, and graph flags without a graph to apply them to, end here: before
     // anything touches the GPU
-    bool graph_flag = false, edge_feat_flag = false;
+    bool graph_flag = false, edge_feat_flag = false, readout_flag = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--help") { std::cout << kUsage; return 0; }
+        if (a == "--readout") {
+            const std::string v = i + 1 < argc ? argv[i + 1] : "";
+            if (v != "mean" && v != "sum" && v != "max") die("Error: --readout must be mean, sum or max\n");
+            readout_flag = true;
+        }
         if (a == "--add-self-loops" || a == "--undirected" || a == "--coalesce") graph_flag = true;
         if (a == "--edge-features") edge_feat_flag = true;
     }
@@ -680,7 +707,9 @@ int main(int argc, char** argv) {
     if (edge_feat_flag && multi)
         die("Error: --edge-features needs --ranks 1: this program does not cut edge_features.txt into shards (the library does: "
             "gat_set_edge_features on every shard's own CSR)\n");
-    if (graph_flag) {
+    if (readout_flag && multi)
+        die("Error: --readout needs --ranks 1: a graph of the batch may straddle two destination-range shards\n");
+    if (graph_flag || readout_flag) {
         std::string root = "./data", name = "pubmed";
         bool root_given = false;
         for (int i = 1; i + 1 < argc; ++i) {
@@ -691,7 +720,9 @@ int main(int argc, char** argv) {
         if (env_root && !root_given) root = env_root;
         if (!root.empty() && root.back() != '/' && root.back() != '\\') root += '/';
         const std::string dir = root + name + "/";
-        if (!file_exists(dir + "edges.txt") && !(file_exists(dir + "row_ptr.txt") && file_exists(dir + "col_idx.txt")))
+        if (readout_flag && !file_exists(dir + "graph_ptr.txt"))
+            die("Error: --readout needs graph_ptr.txt (G+1 integers: the first node of every graph, then the node count) in " + dir + "\n");
+        if (graph_flag && !file_exists(dir + "edges.txt") && !(file_exists(dir + "row_ptr.txt") && file_exists(dir + "col_idx.txt")))
             die("Error: --add-self-loops / --undirected / --coalesce need a graph: no edges.txt and no row_ptr.txt + col_idx.txt in " + dir + "\n");
     }
     if (!multi) print_memory_tracker_before();

@@ -202,3 +202,36 @@ def edge_features(seed: int, n_edges: int, fe: int) -> np.ndarray:
         raise ValueError(f"edge_features: bad sizes (n_edges={n_edges}, fe={fe})")
     rng = np.random.default_rng([int(seed) & (2 ** 63 - 1), 0xEA])
     return rng.standard_normal((int(n_edges), int(fe))).astype(np.float32)
+
+
+def graph_batch(n_graphs: int, nodes_lo: int, nodes_hi: int, avg_degree: float, seed: int = GRAPH_SEED, f: int = 32, c: int = 4):
+    """A batch of n_graphs small graphs (molecule-like) packed block-diagonally into one CSR, for the graph-level readout
+    (gatv2_abi.h "graph-level readout"): graph g has a size drawn uniformly from [nodes_lo, nodes_hi] and owns the contiguous nodes
+    graph_ptr[g] .. graph_ptr[g+1]-1; every node gets one self-loop plus Poisson(avg_degree - 1) in-edges from uniformly drawn nodes of
+    its own graph, sources ascending inside a row (rows = destinations).  Features are `features(n, f)`, the labels — one per GRAPH —
+    `labels(n_graphs, c)`.  A function of the arguments alone.
+    -> dict(row_ptr, col_idx, graph_ptr, x, labels [n_graphs], n, e, f, c, n_graphs)."""
+    if n_graphs < 1 or nodes_lo < 1 or nodes_hi < nodes_lo or avg_degree < 1.0:
+        raise ValueError(f"graph_batch: bad arguments (n_graphs={n_graphs}, nodes {nodes_lo}..{nodes_hi}, avg_degree={avg_degree})")
+    rng = np.random.default_rng([int(seed) & (2 ** 63 - 1), 0x6B])
+    sizes = rng.integers(nodes_lo, nodes_hi + 1, n_graphs)
+    graph_ptr = np.zeros(n_graphs + 1, np.int64)
+    graph_ptr[1:] = np.cumsum(sizes)
+    n = int(graph_ptr[-1])
+    if n >= 2 ** 31 - 1:
+        raise ValueError("graph_batch: the node count does not fit int32")
+    first = np.repeat(graph_ptr[:-1], sizes)                  # first node of the node's graph
+    size = np.repeat(sizes, sizes)
+    deg = 1 + rng.poisson(avg_degree - 1.0, n)
+    row_ptr = np.zeros(n + 1, np.int64)
+    row_ptr[1:] = np.cumsum(deg)
+    e = int(row_ptr[-1])
+    if e > 2 ** 31 - 1:
+        raise ValueError("graph_batch: the edge count does not fit int32")
+    dst = np.repeat(np.arange(n, dtype=np.int64), deg)
+    src = first[dst] + (rng.random(e) * size[dst]).astype(np.int64)
+    src[row_ptr[:-1]] = np.arange(n)                          # the first edge of every row is its self-loop
+    src = src[np.lexsort((src, dst))]                         # ascending inside a row (dst is sorted already)
+    return dict(row_ptr=row_ptr.astype(np.int32), col_idx=src.astype(np.int32), graph_ptr=graph_ptr.astype(np.int32),
+                x=features(n, f, seed + 1), labels=labels(n_graphs, c, seed + 2), n=n, e=e, f=f, c=c, n_graphs=n_graphs,
+                name=f"graph_batch_{n_graphs}")

@@ -309,10 +309,12 @@ enum {
     GAT_TAP_ATTN_KEEP = 15, /* [H][E]                attention-dropout factor kappa*s_a (0 or s_a) of layer l for the step the
                                                       counter holds (after a training forward: the masks that forward used) */
     GAT_TAP_FEAT_KEEP = 16, /* [N][F_l]              feature-dropout factor kappa*s_f (0 or s_f) of layer l's input, likewise */
-    GAT_TAP_EDGE_KEEP = 17  /* [E]                   DropEdge: 1 = CSR edge kept, 0 = dropped, for layer l and the step the counter
+    GAT_TAP_EDGE_KEEP = 17, /* [E]                   DropEdge: 1 = CSR edge kept, 0 = dropped, for layer l and the step the counter
                                                       holds, likewise (all 1 at edge_p = 0; needs gat_set_dropedge or gat_set_dropout).  Like the two
                                                       taps above it reports the mask of the SETTING, whatever the mode: in eval mode the passes drop
                                                       nothing, the tap still shows what a training forward at that counter value draws */
+    GAT_TAP_POOLED = 18     /* [n_graphs][D_last]    the pooled rows the head reads (last layer only; needs gat_set_readout, see
+                                                      "graph-level readout", where GAT_TAP_Y becomes [n_graphs][C]) */
 };
 int gat_tap(gat_ctx* ctx, int tensor, int32_t layer, void* host_dst, int64_t count);
 
@@ -543,6 +545,58 @@ int gat_set_norm(gat_ctx* ctx, int32_t flags, float eps);
 int gat_set_edge_dim(gat_ctx* ctx, int32_t edge_dim);
 int gat_set_edge_features(gat_ctx* ctx, const float* ea, int64_t n_edges, int32_t edge_dim);              /* [n_edges][edge_dim], host */
 int gat_set_edge_features_device(gat_ctx* ctx, const float* d_ea, int64_t n_edges, int32_t edge_dim);    /* the same, device pointer */
+
+/* ---- graph-level readout (beyond the reference, which has one label per node; PyG's global_add_pool / global_mean_pool / global_max_pool) ----
+ * Many small graphs packed block-diagonally into one CSR, ONE label per graph.  Graph g owns the contiguous rows
+ * [graph_ptr[g], graph_ptr[g+1]) — the `ptr` of a PyG Batch; a sorted `batch` vector is the same information.  With X = the last layer's
+ * output ([n_rows][D_last], after the mean over heads) and cnt_g the row count of graph g:
+ *     GAT_READOUT_SUM   P[g][d] = sum_n X[n][d]                      dL/dX[n][d] = gP[g][d]
+ *     GAT_READOUT_MEAN  P[g][d] = (sum_n X[n][d]) / (float)cnt_g     dL/dX[n][d] = gP[g][d] / (float)cnt_g
+ *     GAT_READOUT_MAX   P[g][d] = max_n X[n][d]                      dL/dX[n][d] = gP[g][d] if n == argmax[g][d], else 0
+ * argmax is the LOWEST row attaining the maximum.  An empty graph (cnt_g == 0) has P[g] = 0 in every mode, argmax -1, and sends no
+ * gradient.  The output head runs unchanged on P with n_graphs rows where it had n_rows: z = P Wo^T, the reference's softmax and loss
+ * (E:132-141, E:514-537), dz = y - onehot, gradWo += dz^T P, gP = dz Wo.  Wo keeps its shape [C][D_last]: no parameter group changes
+ * size.  Labels, the training mask, gat_eval_mask, GAT_TAP_Y, loss_sum and n_correct are all PER GRAPH.  Everything from dL/dX downward
+ * is the code of a context without readout (the / H and LReLU' expansion in the last layer's edge backward, the residual and norm kernels).
+ * gat_set_readout[_device] is called AFTER the graph is set and BEFORE the labels (else GAT_E_STATE: the label, mask and head buffers are
+ *   sized by it), at most once with a non-zero mode (a second one: GAT_E_STATE).  mode == 0 (GAT_READOUT_NONE) is the default and leaves the
+ *   context exactly as it is: same buffers, same kernels, same launch counts, bitwise the same results (the other arguments are not read).
+ *   mode outside 0..3: GAT_E_INVALID.  n_graphs >= 1 and must fit int32.  graph_ptr [n_graphs + 1] must start at 0, end at n_rows and never
+ *   decrease, else GAT_E_INVALID with a text naming the lowest offending index (0; n_graphs; the i with graph_ptr[i+1] < graph_ptr[i]).
+ *   The device form checks its argument in one pass on the device before anything walks it (as gat_graph_check_device does).  The array
+ *   is copied.
+ * With readout on, gat_set_labels[_device], gat_set_train_mask and gat_eval_mask take n_graphs where they took n_rows (another length:
+ *   GAT_E_INVALID); gat_eval_mask's n_nodes counts graphs.
+ * Where it runs.  Forward: a work list built once (a graph of at most 256 rows is one item, a longer one is cut into 256-row segments); one
+ *   wave per item streams the item's contiguous rows — float4 loads with D_last / 4 lanes per row and the other lanes on the next rows when
+ *   D_last is a multiple of 4, scalar loads otherwise, any D_last >= 1 — and combines its row slots by a fixed-order butterfly; the
+ *   segments of a long graph leave partial rows that a second small kernel combines in ascending order.  Backward: one N-sized elementwise
+ *   kernel that writes the first D_last floats of every row of the head's gradient buffer (all rows, zeros included).  No float atomics:
+ *   bitwise reproducible.  The two launches are part of gat_head_forward (which pools first) and gat_head_backward (which ends with the
+ *   un-pool), of gat_forward / gat_backward, gat_step and a gat_step_graph replay (no host synchronisation), and are timed under
+ *   GAT_K_HEAD_FWD / GAT_K_HEAD_BWD.
+ * Works with every (H, D) family incl. both generic ones, bf16 storage (pooling and the head stay fp32), keep_taps, eval mode, all three
+ *   regularisers, residual, bias, norm and edge features.
+ * Refused with GAT_E_UNSUPPORTED: a destination-range shard (n_table != n_rows) or a context with a transport (a graph may straddle shards;
+ *   gat_comm_init_* on a readout context is refused alike); flat_lrelu_index = 1 (the head would write the last layer's g itself); the
+ *   experiment library with GAT_DBG set.  GAT_FUSE_LAST=1 is not used by a readout context: it runs the separate passes.
+ * gat_set_graph_coo* keeps the row order, so a caller's graph_ptr stays valid after a build; it is not carried through by the library.
+ * gat_algorithmic_bytes (context form): unchanged with readout off.  On, the head classes are priced with n_graphs rows, and misc gains
+ *   4 * (N*D_last + G*D_last) for the pool and 4 * (G*D_last + N*D_last) for the un-pool.  gat_algorithmic_bytes_shape has no context and
+ *   prices the model without the feature. */
+enum { GAT_READOUT_NONE = 0, GAT_READOUT_MEAN = 1, GAT_READOUT_SUM = 2, GAT_READOUT_MAX = 3 };
+int gat_set_readout(gat_ctx* ctx, int32_t mode, const int32_t* graph_ptr, int64_t n_graphs);            /* host graph_ptr[n_graphs+1] */
+int gat_set_readout_device(gat_ctx* ctx, int32_t mode, const int32_t* d_graph_ptr, int64_t n_graphs);   /* checked on the device */
+int gat_readout_info(gat_ctx* ctx, int32_t* mode, int64_t* n_graphs);                                   /* (0, 0) while off; pointers may be NULL */
+/* The two kernels as stateless seams on caller-owned DEVICE pointers (current device), like the gat_op_* below: d_x rows of x_stride >=
+ * width floats, d_pooled [n_graphs][width], d_argmax [n_graphs][width] int32 (GAT_READOUT_MAX only, else may be NULL); the backward writes
+ * floats 0..width-1 of every d_gh row (gh_stride >= width floats apart) and nothing behind them.  Each call checks d_graph_ptr with
+ * gat_set_readout's rules (same codes and texts) before any kernel reads through it, builds its work list, allocates and frees its scratch,
+ * and synchronises `stream` (may be NULL): parity seams, not the fast path. */
+int gat_op_readout_forward(const float* d_x, int64_t x_stride, const int32_t* d_graph_ptr, int64_t n_graphs, int64_t n_rows,
+                           int32_t width, int32_t mode, float* d_pooled, int32_t* d_argmax, void* stream);
+int gat_op_readout_backward(const float* d_gpooled, const int32_t* d_graph_ptr, int64_t n_graphs, int64_t n_rows, int32_t width,
+                            int32_t mode, const int32_t* d_argmax, float* d_gh, int64_t gh_stride, void* stream);
 
 /* ---- op-level entry points, whole layers: caller-provided DEVICE pointers in the reference layouts
  *      (unit parity).  `stream` may be NULL (default stream).  One entry point per reference KERNEL: below. ---- */

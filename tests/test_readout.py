@@ -1,0 +1,425 @@
+"""Graph-level readout on the GPU (include/gatv2_abi.h "graph-level readout"): the two kernels through their stateless seams, exactly;
+the whole step of every dispatcher family against the fp64 model of tests/readout_ref.py at the project's bars (1e-4 of max-abs, 1e-2
+with bf16 storage); the step paths against each other; eval_mask over graphs; the state and refusal matrix; off is the parent; the
+train_edge host.
+
+tests/test_readout_cpu.py proves on the host that every parity case has a parameter seed clear of the LeakyReLU kinks AND, for MAX, a
+clear winner in every (graph, column): the fp64 comparison of MAX holds only where both sides pick the same row."""
+import os
+import re
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import feature_cases as FC
+import parity
+import readout_ref as RR
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "graph-attention-network-gatv2-_amd", "train_edge")
+
+E_INVALID, E_STATE, E_UNSUPPORTED = 10001, 10002, 10004
+U = 2.0 ** -24
+SEG = 256                                        # kReadoutSegRows (csrc/gat_internal.h): a power of two <= 512, covered by the sizes below
+SIZES = [0, 1, 2, 15, 16, 17, 63, 64, 65, 255, 256, 257, 511, 512, 513, 700, 1500]
+WIDTHS = [1, 4, 5, 8, 13, 16, 32, 64, 65]
+SENTINEL = -12345.0
+
+
+def ptr_of(sizes):
+    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+
+
+def seam_batches():
+    """name -> graph_ptr"""
+    n = 37
+    return {"sizes": ptr_of(SIZES), "one_graph": ptr_of([sum(SIZES[:12])]), "one_row_each": ptr_of([1] * n),
+            "empties": ptr_of([0, 0, 5, 0, 0, 3, 300, 0, 0])}
+
+
+def seam_input(gp, width, rng):
+    """X [N][width] with planted exact ties for MAX: in every graph of at least 10 rows, rows 3 and 9 (inside one segment) share the
+    column maximum; in every graph of more than 300 rows, rows 3 and 300 (across a segment boundary) do; where a graph is longer than
+    two segments, rows 255, 256 and the last row tie in the last column instead."""
+    n = int(gp[-1])
+    x = rng.standard_normal((n, width)).astype(np.float32)
+    for g in range(len(gp) - 1):
+        b, cnt = int(gp[g]), int(gp[g + 1] - gp[g])
+        if cnt >= 10:
+            x[b + 3] = x[b + 9] = 50.0
+        if cnt > 300:
+            x[b + 3] = x[b + 300] = 60.0
+        if cnt > 2 * SEG:
+            x[b + 255, -1] = x[b + 256, -1] = x[b + cnt - 1, -1] = 70.0
+    return x
+
+
+def ref_pool(x, gp, mode):
+    """fp64 P, first-occurrence argmax (-1: empty), per-entry sum of |X|, cnt"""
+    G, w = len(gp) - 1, x.shape[1]
+    P = np.zeros((G, w)); arg = np.full((G, w), -1, np.int32); sabs = np.zeros((G, w))
+    cnt = np.diff(gp)
+    x64 = x.astype(np.float64)
+    for g in range(G):
+        b, e = int(gp[g]), int(gp[g + 1])
+        if e == b:
+            continue
+        sabs[g] = np.abs(x64[b:e]).sum(0)
+        if mode == "max":
+            P[g] = x64[b:e].max(0); arg[g] = b + np.argmax(x[b:e], axis=0)
+        else:
+            P[g] = x64[b:e].sum(0) / (cnt[g] if mode == "mean" else 1)
+    return P, arg, sabs, cnt
+
+
+@pytest.fixture(scope="module")
+def torch_dev():
+    import torch
+    assert torch.cuda.is_available(), "the seam tests need the GPU"
+    return torch, torch.device("cuda:0")
+
+
+def run_forward(A, torch, dev, x, gp, mode, x_stride):
+    n, w = x.shape
+    G = len(gp) - 1
+    xs = np.full((max(n, 1), x_stride), SENTINEL, np.float32)
+    xs[:n, :w] = x
+    d_x = torch.from_numpy(xs).to(dev)
+    d_gp = torch.from_numpy(gp).to(dev)
+    d_p = torch.full((G, w), SENTINEL, device=dev)
+    d_a = torch.full((G, w), -7, dtype=torch.int32, device=dev)
+    A.op_readout_forward(d_x.data_ptr(), x_stride, d_gp.data_ptr(), G, n, w, mode, d_p.data_ptr(), d_a.data_ptr() if mode == "max" else 0)
+    return d_p.cpu().numpy(), d_a.cpu().numpy()
+
+
+@pytest.mark.parametrize("width", WIDTHS)
+def test_seams_forward_and_backward(pkg, torch_dev, width):
+    A = pkg.abi
+    torch, dev = torch_dev
+    rng = np.random.default_rng(100 + width)
+    for bname, gp in seam_batches().items():
+        x = seam_input(gp, width, rng)
+        n, G = x.shape[0], len(gp) - 1
+        cnt = np.diff(gp)
+        for mode in RR.MODES:
+            P, arg, sabs, _ = ref_pool(x, gp, mode)
+            got = None
+            for x_stride in (width, width + 3, width + 4):
+                p, a = run_forward(A, torch, dev, x, gp, mode, x_stride)
+                p2, a2 = run_forward(A, torch, dev, x, gp, mode, x_stride)
+                assert np.array_equal(p, p2) and np.array_equal(a, a2), (bname, mode, "not reproducible")
+                if mode == "max":
+                    assert np.array_equal(p, P.astype(np.float32)), (bname, mode, x_stride)          # bitwise X.max, 0 for an empty graph
+                    assert np.array_equal(a, arg), (bname, mode, x_stride)                             # lowest row, -1 for an empty graph
+                else:
+                    bound = cnt[:, None] * U * sabs / (np.maximum(cnt, 1)[:, None] if mode == "mean" else 1)
+                    if mode == "mean":
+                        bound = bound + U * np.abs(P)
+                    err = np.abs(p.astype(np.float64) - P)
+                    assert np.all(err <= bound), (bname, mode, x_stride, float((err - bound).max()))
+                    assert np.all(p[cnt == 0] == 0)
+                got = (p, a)
+            # backward from the forward's own argmax
+            gP = rng.standard_normal((G, width)).astype(np.float32)
+            ng = RR.node_graph(gp)
+            if mode == "sum":
+                want = gP[ng]
+            elif mode == "mean":
+                want = gP[ng] / cnt[ng].astype(np.float32)[:, None]
+            else:
+                want = np.where(got[1][ng] == np.arange(n)[:, None], gP[ng], np.float32(0))
+            for gh_stride in ([width, 16] if width <= 8 else [width]):
+                d_gh = torch.full((max(n, 1), gh_stride), SENTINEL, device=dev)
+                d_gp, d_g = torch.from_numpy(gp).to(dev), torch.from_numpy(gP).to(dev)
+                d_a = torch.from_numpy(got[1]).to(dev)
+                for _ in range(2):
+                    A.op_readout_backward(d_g.data_ptr(), d_gp.data_ptr(), G, n, width, mode, d_a.data_ptr() if mode == "max" else 0,
+                                          d_gh.data_ptr(), gh_stride)
+                gh = d_gh.cpu().numpy()
+                assert np.array_equal(gh[:n, :width], want.astype(np.float32)), (bname, mode, gh_stride)
+                assert np.all(gh[:n, width:] == SENTINEL), (bname, mode, gh_stride)                    # the decision bytes' place stays
+
+
+def test_seams_refuse_bad_graph_ptr(pkg, torch_dev):
+    """A wrong first entry, a wrong last entry, a decreasing step: GAT_E_INVALID naming the index, before any kernel reads through it."""
+    A = pkg.abi
+    torch, dev = torch_dev
+    n, w = 20, 4
+    d_x = torch.zeros((n, w), device=dev); d_p = torch.zeros((4, w), device=dev); d_gh = torch.zeros((n, w), device=dev)
+    for gp, idx in (([1, 5, 9, 14, 20], 0), ([0, 5, 9, 14, 2000000], 4), ([0, 5, 900000, 14, 20], 2), ([0, -5, 9, 14, 20], 0)):
+        d_gp = torch.tensor(gp, dtype=torch.int32, device=dev)
+        for call in (lambda: A.op_readout_forward(d_x.data_ptr(), w, d_gp.data_ptr(), 4, n, w, "sum", d_p.data_ptr()),
+                     lambda: A.op_readout_backward(d_p.data_ptr(), d_gp.data_ptr(), 4, n, w, "sum", 0, d_gh.data_ptr(), w)):
+            with pytest.raises(A.GatError) as ei:
+                call()
+            assert ei.value.code == E_INVALID and f"entry {idx}" in str(ei.value), str(ei.value)
+    torch.cuda.synchronize()
+
+
+# -- the whole step against the fp64 model
+TAPS = ["hout", "G"]
+
+
+def compare_all(pkg, ctx, ci, ref, loss, tol):
+    """loss per graph, GAT_TAP_POOLED, GAT_TAP_Y, hout and G of both layers, all eight gradient groups."""
+    A = pkg.abi
+    G = len(ci["graph_ptr"]) - 1
+    FC.compare(pkg, ctx, dict(ci["g"], n=G), ci["cfg"], ref, loss, tol, TAPS, FC.GROUPS)
+    want = ref["pooled"].detach().numpy()
+    parity.check_rel("pooled", ctx.tap(A.TAP_POOLED, ci["cfg"].L - 1), want, tol)
+    parity.check_abs("y", ctx.tap(A.TAP_Y), ref["y"], tol)
+    got = ctx.grads_get(A.PARAM_WE)
+    if ref["We"] is None:
+        assert got.size == 0
+    else:
+        parity.check_rel("grad We", got, ref["We"].grad.numpy(), tol)
+
+
+def n_correct_of(ref, ci):
+    keep = np.ones(len(ci["glabels"]), bool) if ci["gmask"] is None else ci["gmask"]
+    return int(((np.argmax(ref["y"], axis=1) == ci["glabels"]) & keep).sum())
+
+
+CASES = RR.cases(FC)
+
+
+@pytest.mark.parametrize("case", CASES, ids=[RR.case_id(c) for c in CASES])
+def test_step_against_fp64(pkg, orc, case):
+    ci = RR.case_inputs(case)
+    ref = RR.model_of(ci)
+    tol = 1e-2 if ci["bf16"] else 1e-4
+    with RR.make_ctx(pkg, ci) as ctx:
+        assert ctx.readout_info() == (pkg.abi.READOUT_MODES[ci["mode"]], len(ci["graph_ptr"]) - 1)
+        loss, correct = ctx.step()
+        compare_all(pkg, ctx, ci, ref, loss, tol)
+        if not ci["bf16"]:
+            assert correct == n_correct_of(ref, ci)
+
+
+ALL_BOUNDARY = RR.BOUNDARY + RR.BOUNDARY_SPARSE
+
+
+@pytest.mark.parametrize("boundary", ALL_BOUNDARY, ids=[RR.boundary_id(b) for b in ALL_BOUNDARY])
+def test_step_across_a_segment_boundary(pkg, orc, boundary):
+    """Graphs of 300 and 600 rows: the pooling runs as 256-row segments and the combine kernel.
+    The e2500 cases take their parameter seed from behind the first 40 (tests/readout_ref.py BOUNDARY_SEEDS)."""
+    ci = RR.case_inputs(boundary=boundary)
+    ref = RR.model_of(ci)
+    with RR.make_ctx(pkg, ci) as ctx:
+        loss, _ = ctx.step()
+        compare_all(pkg, ctx, ci, ref, loss, 1e-4)
+
+
+# -- equal forms
+def all_grads(A, c):
+    return [c.grads_get(k) for k in A.PARAM_GROUPS]
+
+
+@pytest.mark.parametrize("mode", ["mean", "max"])
+def test_paths_agree(pkg, orc, mode):
+    """gat_step, gat_forward + gat_backward and the phase API.  records_d8 takes the fused head step in gat_step and the two-kernel head
+    elsewhere: gradWo at 1e-5 there (another summation order of the same terms, as in the halo test), everything else bitwise; a
+    gat_step_graph replay is bitwise the eager step."""
+    A = pkg.abi
+    ci = RR.case_inputs(("records_d8", [8, 8], [8, 8], {}, "plain", mode))
+    with RR.make_ctx(pkg, ci) as s1, RR.make_ctx(pkg, ci) as fb, RR.make_ctx(pkg, ci) as ph, RR.make_ctx(pkg, ci) as gr:
+        l1 = s1.step(); g1 = all_grads(A, s1)
+        lf = fb.forward(); fb.backward(); gf = all_grads(A, fb)
+        for l in range(2):
+            ph.layer_project(l); ph.layer_forward_edges(l)
+        lp = ph.head_forward()
+        ph.head_backward()
+        for l in (1, 0):
+            ph.layer_backward_edges(l); ph.layer_backward_dense(l)
+        gp = all_grads(A, ph)
+        assert lf == lp and lf[1] == l1[1] and abs(lf[0] - l1[0]) <= 1e-5 * abs(l1[0])
+        for k in A.PARAM_GROUPS:
+            assert np.array_equal(gf[k], gp[k]), k                       # the same kernels in both
+            if k == A.PARAM_WO:
+                assert parity.rel_err(gf[k], g1[k]) <= 1e-5
+            else:
+                assert np.array_equal(gf[k], g1[k]), k
+        assert np.array_equal(fb.tap(A.TAP_POOLED, 1), s1.tap(A.TAP_POOLED, 1))
+        gr.step_graph(True)
+        outs = []
+        for _ in range(3):                                               # eager warm-up, capture + replay, replay
+            gr.zero_grad()
+            outs.append((gr.step(), all_grads(A, gr)))
+        for (lg, gg) in outs:
+            assert lg == l1
+            for k in A.PARAM_GROUPS:
+                assert np.array_equal(gg[k], g1[k]), k
+
+
+def test_eval_mask_over_graphs(pkg, orc):
+    A = pkg.abi
+    ci = RR.case_inputs(("records_d8", [8, 8], [8, 8], {}, "plain", "mean"))
+    ref = RR.model_of(ci)
+    G = len(ci["glabels"])
+    pred_ok = np.argmax(ref["y"], axis=1) == ci["glabels"]
+    with RR.make_ctx(pkg, ci) as ctx:
+        ctx.step()                                                       # the fused head step: eval_mask re-runs the head forward
+        for mask in (np.ones(G, bool), np.array([1, 0, 1, 0, 1], bool), np.array([0, 0, 0, 1, 0], bool)):
+            loss, correct, count = ctx.eval_mask(mask)
+            assert count == int(mask.sum()) and correct == int((pred_ok & mask).sum())
+            assert abs(loss - ref["loss_per_graph"][mask].sum()) / mask.sum() < 1e-4
+        with pytest.raises(A.GatError) as ei:
+            ctx.eval_mask(np.ones(ci["g"]["n"], bool))                    # per node: the wrong length
+        assert ei.value.code == E_INVALID
+
+
+# -- states and refusals
+def test_state_and_refusal_matrix(pkg, orc, torch_dev):
+    A = pkg.abi
+    torch, dev = torch_dev
+    g = FC.parity_graph()
+    gp = np.array(RR.GRAPH_PTR, np.int32)
+    G = len(gp) - 1
+    glab = RR.graph_labels(G, g["c"])
+
+    def fresh(**kw):
+        c = pkg.GatContext([8, 8], [8, 8], g["f"], g["c"], **kw)
+        c.set_graph(g["row_ptr"], g["col_idx"])
+        return c
+
+    def refused(code, fn, text=None):
+        with pytest.raises(A.GatError) as ei:
+            fn()
+        assert ei.value.code == code, str(ei.value)
+        if text is not None:
+            assert text in str(ei.value), str(ei.value)
+
+    with pkg.GatContext([8, 8], [8, 8], g["f"], g["c"]) as c:            # before the graph
+        refused(E_STATE, lambda: c.set_readout("mean", graph_ptr=gp))
+    with fresh() as c:                                                   # after the labels
+        c.set_labels(g["labels"])
+        refused(E_STATE, lambda: c.set_readout("mean", graph_ptr=gp))
+        c.set_readout(0)                                                 # mode 0 is always a no-op
+        assert c.readout_info() == (0, 0)
+    with fresh() as c:
+        refused(E_INVALID, lambda: c.set_readout(4, graph_ptr=gp))
+        refused(E_INVALID, lambda: c.set_readout(-1, graph_ptr=gp))
+        for bad, idx in (([1, 0, 1, 40, 41, 150], 0), ([0, 0, 1, 40, 41, 149], 5), ([0, 0, 41, 40, 41, 150], 2)):
+            refused(E_INVALID, lambda: c.set_readout("sum", graph_ptr=bad), f"entry {idx}")
+            d_bad = torch.tensor(bad, dtype=torch.int32, device=dev)
+            refused(E_INVALID, lambda: c.set_readout_device("sum", d_bad.data_ptr(), G), f"entry {idx}")
+        assert c.readout_info() == (0, 0)                                # nothing stuck
+        d_gp = torch.from_numpy(gp).to(dev)
+        c.set_readout_device("max", d_gp.data_ptr(), G)                  # the device form
+        assert c.readout_info() == (A.READOUT_MAX, G)
+        refused(E_STATE, lambda: c.set_readout("mean", graph_ptr=gp))    # a second non-zero call
+        c.set_readout("none")
+        assert c.readout_info() == (A.READOUT_MAX, G)
+        c.set_features(g["x"])
+        refused(E_INVALID, lambda: c.set_labels(g["labels"]))            # one label per node: the wrong length
+        c.set_labels(glab)
+        refused(E_INVALID, lambda: c.set_train_mask(np.ones(g["n"], bool)))
+        c.set_train_mask(np.ones(G, bool))
+        refused(E_UNSUPPORTED, lambda: c.comm_init_host(1, 0, "/gat_readout_refused", 1 << 20))
+        c.params_init(1)
+        loss, correct = c.step()
+        assert np.isfinite(loss) and 0 <= correct <= G
+    with fresh(flat_lrelu_index=True) as c:
+        refused(E_UNSUPPORTED, lambda: c.set_readout("mean", graph_ptr=gp), "flat_lrelu_index")
+    with pkg.GatContext([8, 8], [8, 8], g["f"], g["c"]) as c:            # a destination-range shard
+        c.set_graph(g["row_ptr"], g["col_idx"], n_table=2 * g["n"], table_row0=0)
+        refused(E_UNSUPPORTED, lambda: c.set_readout("mean", graph_ptr=gp), "shard")
+
+
+def test_batch_vector_and_single_graph(pkg, orc):
+    """set_readout(batch=...) is set_readout(graph_ptr=...); G = 1 (the head on one row) runs."""
+    A = pkg.abi
+    ci = RR.case_inputs(("records_d8", [8, 8], [8, 8], {}, "plain", "sum"))
+    g = ci["g"]
+    batch = RR.node_graph(ci["graph_ptr"])                               # graph 0 is empty: id 0 does not occur
+    with RR.make_ctx(pkg, ci) as a, pkg.GatContext([8, 8], [8, 8], g["f"], g["c"]) as b, pkg.GatContext([8, 8], [8, 8], g["f"], g["c"]) as one:
+        b.set_graph(g["row_ptr"], g["col_idx"]); b.set_features(g["x"])
+        b.set_readout("sum", batch=batch)
+        b.set_labels(ci["glabels"])
+        for grp, arr in zip((A.PARAM_W, A.PARAM_A, A.PARAM_WO), ci["P"]):
+            b.params_set(grp, arr)
+        b.zero_grad()
+        assert a.step() == b.step()
+        for k in A.PARAM_GROUPS:
+            assert np.array_equal(a.grads_get(k), b.grads_get(k))
+        one.set_graph(g["row_ptr"], g["col_idx"]); one.set_features(g["x"])
+        one.set_readout("max", graph_ptr=[0, g["n"]])
+        one.set_labels([2])
+        for grp, arr in zip((A.PARAM_W, A.PARAM_A, A.PARAM_WO), ci["P"]):
+            one.params_set(grp, arr)
+        one.zero_grad()
+        loss, correct = one.step()
+        assert np.isfinite(loss) and correct in (0, 1)
+        assert np.array_equal(one.tap(A.TAP_POOLED, 1)[0], one.tap(A.TAP_HOUT, 1).max(0))
+        assert one.tap(A.TAP_Y).shape == (1, g["c"])
+
+
+# -- off is the parent
+def test_off_is_the_parent(pkg, orc):
+    A = pkg.abi
+    ci = RR.case_inputs(("records_d8", [8, 8], [8, 8], {}, "plain", "mean"))
+    with RR.make_ctx(pkg, ci, mode=False, collect_timing=True) as a, RR.make_ctx(pkg, ci, mode=0, collect_timing=True) as b:
+        for c in (a, b):
+            c.kernel_stats_reset()
+        assert a.step() == b.step()
+        for k in A.PARAM_GROUPS:
+            assert np.array_equal(a.grads_get(k), b.grads_get(k))
+        sa, sb = a.kernel_stats(), b.kernel_stats()
+        assert {k: v[0] for k, v in sa.items()} == {k: v[0] for k, v in sb.items()}      # the same launches, class by class
+        assert a.algorithmic_bytes() == b.algorithmic_bytes()
+        ta, pa = a.algorithmic_bytes()
+    with RR.make_ctx(pkg, ci) as r:                                      # on: the documented terms
+        tr, pr = r.algorithmic_bytes()
+        N, G, DL, Cn = ci["g"]["n"], len(ci["glabels"]), 8, ci["g"]["c"]
+        assert pr["misc"] - pa["misc"] == 4.0 * 2 * (N * DL + G * DL)
+        for k in ("head_forward", "head_backward"):
+            assert pr[k] == 4.0 * G * (DL + 2.0 * Cn + 2.0) and pa[k] == 4.0 * N * (DL + 2.0 * Cn + 2.0)
+        assert all(pr[k] == pa[k] for k in pa if k not in ("misc", "head_forward", "head_backward"))
+
+
+# -- the host program
+def test_train_edge_readout(pkg, orc):
+    """train_edge --readout mean on a dataset folder written here: two epochs match a GatContext driven the same way."""
+    assert os.path.exists(BIN), "build() makes the host binary"
+    A = pkg.abi
+    g = FC.host_graph(3)
+    n = g["n"]
+    gp = np.array([0, 7, 7, 20, 40], np.int32)
+    G = len(gp) - 1
+    glab = RR.graph_labels(G, g["c"], seed=5)
+    glab[0] = g["c"] - 1                                                 # the host takes num_classes = max(label) + 1
+    with tempfile.TemporaryDirectory() as root:
+        d = os.path.join(root, "tiny")
+        os.makedirs(d)
+        np.savetxt(os.path.join(d, "row_ptr.txt"), g["row_ptr"], fmt="%d")
+        np.savetxt(os.path.join(d, "col_idx.txt"), g["col_idx"], fmt="%d")
+        np.savetxt(os.path.join(d, "features.txt"), g["x"], fmt="%.9g")
+        np.savetxt(os.path.join(d, "labels.txt"), glab, fmt="%d")
+        np.savetxt(os.path.join(d, "graph_ptr.txt"), gp, fmt="%d")
+        x = np.loadtxt(os.path.join(d, "features.txt"), dtype=np.float32, ndmin=2)      # exactly what the binary reads
+        env = dict(os.environ)
+        env.pop("DATA_ROOT", None)
+        r = subprocess.run([BIN, "--dataset", "tiny", "--data-root", root, "--epochs", "2", "--optimizer", "adam", "--lr", "0.01", "--clip",
+                            "--num-layers", "2", "--heads", "8,8", "--outdims", "8,8", "--seed", "7", "--readout", "mean"],
+                           capture_output=True, text=True, env=env, timeout=300)
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert f"Readout: mean over {G} graphs\n" in r.stdout
+        got = re.findall(r"Avg Loss: ([0-9.]+), Accuracy: ([0-9.]+)%", r.stdout)
+        assert len(got) == 2, r.stdout
+    with pkg.GatContext([8, 8], [8, 8], g["f"], g["c"]) as ctx:
+        ctx.set_graph(g["row_ptr"], g["col_idx"]); ctx.set_features(x)
+        ctx.set_readout("mean", graph_ptr=gp)
+        ctx.set_labels(glab)
+        ctx.params_init(7)
+        ctx.zero_grad()
+        for t, (loss_txt, acc_txt) in enumerate(got, 1):                 # the host's epoch: forward, backward, clip, adam, zero_grad
+            loss, correct = ctx.forward()
+            ctx.backward()
+            ctx.clip(5.0)
+            ctx.step_adam(0.01, 0.9, 0.999, 1e-8, t)
+            ctx.zero_grad()
+            assert loss_txt == "%f" % (np.float32(loss) / G), (t, loss_txt, loss / G)
+            assert acc_txt == "%.2f" % (100.0 * np.float32(np.float32(correct) / G)), (t, acc_txt, correct)
