@@ -85,6 +85,27 @@ class FakeContext:
     def zero_grad(self):
         self.grads[:] = 0
 
+    def grads_get(self, group):
+        lo, hi = ((0, self.nW), (self.nW, self.nW + self.nA), (self.nW + self.nA, self.n_params))[group]
+        return self.grads[lo:hi].astype(np.float32)
+
+    def tap(self, tensor, l=0):
+        """The taps the lockstep shard harness reads (tests/shard_cases.py), by the ABI's GAT_TAP_* numbers and in its layouts."""
+        H, D, HD = self.heads[l], self.outdims[l], self.hd[l]
+        E = len(self.ci)
+        f32 = lambda a, shape: np.ascontiguousarray(a, np.float64).astype(np.float32).reshape(shape)
+        if tensor == 2: return f32(self.alpha[l].T, (H, E))
+        if tensor == 3: return f32(self.hpre[l], (self.n, H, D))
+        if tensor == 4: return f32(self.hout[l], (self.n, -1))
+        if tensor == 5: return f32(self.y, (self.n, self.C))
+        if tensor == 6: return f32(self.g[l], (self.n, H, D))
+        if tensor == 10: return self.tables[(0, l)].reshape(self.n_table, HD).copy()
+        if tensor == 11: return f32(self.PR[l], (self.n, HD))
+        if tensor == 12: return f32(self.score[l].T, (H, E))
+        if tensor == 13: return f32(self.galpha[l].T, (H, E))
+        if tensor == 14: return f32(self.gx[l], (self.n, self.F[l]))
+        raise ValueError(f"FakeContext.tap: tensor {tensor} is not modelled")
+
     # -- helpers
     def _Wl(self, l):
         H, D, F = self.heads[l], self.outdims[l], self.F[l]
@@ -105,6 +126,7 @@ class FakeContext:
     def layer_project(self, l):
         if l == 0:
             self.PR, self.hpre, self.hout, self.alpha, self.g = {}, {}, {}, {}, {}
+            self.score, self.galpha, self.gx = {}, {}, {}
         W, F, HD = self._Wl(l), self.F[l], self.hd[l]
         X = self._X(l)
         tab = self.tables[(0, l)].reshape(self.n_table, HD)
@@ -126,7 +148,7 @@ class FakeContext:
         Z = self._segsum(p)
         alpha = p / (Z[self.dst] + 1e-8)
         hpre = self._segsum(np.repeat(alpha, D, axis=1) * v)
-        self.alpha[l], self.hpre[l] = alpha, hpre
+        self.alpha[l], self.hpre[l], self.score[l] = alpha, hpre, e
         act = lrelu(hpre)
         self.hout[l] = act.reshape(self.n, H, D).mean(1) if l == self.L - 1 else act
 
@@ -158,6 +180,7 @@ class FakeContext:
         gd = g[self.dst]
         alpha = self.alpha[l]
         galpha = (gd * v).reshape(-1, H, D).sum(-1)
+        self.galpha[l] = galpha
         dot = (g * self.hpre[l]).reshape(self.n, H, D).sum(-1)
         ge = alpha * (galpha - dot[self.dst])
         ge_c = np.repeat(ge, D, axis=1)
@@ -181,4 +204,5 @@ class FakeContext:
         self.grads[self.w_off[l]:self.w_off[l + 1]] += gW.reshape(-1)
         if l > 0:
             gX = gPL @ W[:, :F] + self.gPR @ W[:, F:]
+            self.gx[l] = gX                                                         # GAT_TAP_GX: before the LReLU' factor
             self.g[l - 1] = gX * dlrelu(self.hpre[l - 1])

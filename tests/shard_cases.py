@@ -1,0 +1,547 @@
+"""The lockstep shard harness (TEST INFRASTRUCTURE; a plain module: tests/test_shard_cases_cpu.py, test_shard_shapes.py,
+test_shard_picks.py and test_shard.py import it).
+
+One process, one thread, no transport: the P shard contexts of a graph (shard.make_plan / shard.local_csr) are driven through the phase
+API in lockstep, and the three exchanges between the phases are done HERE, on the host, in numpy:
+
+    all-gather      slice copies of the raw table words (bf16 rows are copied as the 32-bit words they occupy), or, in the halo form,
+                    only the rows np.unique(col_idx_local) names
+    reduce-scatter  fp32 sums in ascending rank order with the own partial at its rank's position
+    all-reduce      the same sum over the parameter gradients
+
+which is the order of the library's host transport and of its halo sum kernel.  This is the plain restatement of the exchange
+operations; the kernels between them are the library's own (or, on a machine without a GPU, the numpy stand-in of tests/fake_ctx.py).
+
+A shard context is RECTANGULAR (n_table != n_rows, table_row0 != 0): most table rows are referenced by no edge of the shard, and a
+peer's slice ends in padding rows nobody wrote.  With poison=True the harness fills, before every layer_forward_edges of a rank, every PL
+row the rank's col_idx does not reference with NaN bit patterns of the storage type (peers' padding rows and the own slice's rows at or
+beyond n_rows included), and before every layer_backward_edges the whole gPL table; afterwards every gPL row of an unreferenced source
+must be exactly 0.0 and every referenced row finite, and nothing the step returns may hold a NaN."""
+import numpy as np
+
+import feature_cases as FC
+import parity
+
+# models beside feature_cases.SHAPES: (name, heads, outdims)
+HD15 = ("hd15", [3, 3], [5, 5])                  # H*D = 15: the scalar halo pack width; the generic edge kernels on a table
+HD7 = ("hd7", [1, 1], [7, 7])
+MIXED = ("mixed", [4, 3, 1], [4, 5, 7])          # layer width != max(H*D); fast-path and generic layers in one context
+GENERIC = [HD15, HD7, MIXED]
+SMALL_SHAPES = [(64, 8), (16, 4), (8, 8)]        # what the two edge graphs run, beside HD15
+PARAM_SEED = 11
+
+NODE_TAPS = ("pl", "pr", "hpre", "hout")         # per layer, rows = the rank's own rows
+EDGE_TAPS = ("alpha", "score", "galpha")         # per layer, [H][E of the rank]; keep_taps only
+
+
+def shape_name(hd, d):
+    return f"hd{hd}_d{d}"
+
+
+def shape_heads(hd, d):
+    return [hd // d] * 2, [d] * 2
+
+
+# ---- graphs ------------------------------------------------------------------------------------------------------------------------
+def _graph(rp, ci, seed, F=24, C=5):
+    rng = np.random.default_rng(seed)
+    n = len(rp) - 1
+    return dict(row_ptr=np.asarray(rp, np.int32), col_idx=np.asarray(ci, np.int32), x=rng.standard_normal((n, F)).astype(np.float32),
+                labels=rng.integers(0, C, n).astype(np.int32), n=n, f=F, c=C)
+
+
+def last_row_graph():
+    """40 nodes, every edge in the last row: at P = 3 the strictly increasing cuts leave ranks 0 and 1 without any edge."""
+    rng = np.random.default_rng(21)
+    rp = np.zeros(41, np.int32); rp[40] = 60
+    return _graph(rp, np.sort(rng.integers(0, 40, 60)), 22)
+
+
+def last_four_graph():
+    """40 nodes, every edge in the last four rows (36..39), sources drawn from 8..39: four from 8..35 per row, and row 36 <- 37,
+    row 37 <- 39, row 38 <- 38 (a one-row shard's self-loop).  At P = 4: three one-row shards, (rank, peer) pairs with and without a
+    referenced row, and table rows nobody references."""
+    rng = np.random.default_rng(31)
+    rows = [np.sort(np.concatenate([rng.integers(8, 36, 4), extra])) for extra in ([37], [39], [38], [])]
+    rp = np.zeros(41, np.int32); rp[37:] = np.cumsum([len(r) for r in rows])
+    return _graph(rp, np.concatenate(rows), 32)
+
+
+GRAPHS = {"parity": (FC.parity_graph, 3), "last_row": (last_row_graph, 3), "last_four": (last_four_graph, 4)}      # name -> (graph, P)
+
+
+class Shards:
+    """The P plans and local CSRs of a graph, and what a case relies on about them."""
+
+    def __init__(self, S, g, world):
+        self.g, self.world = g, world
+        self.plans = [S.make_plan(g["row_ptr"], world, r) for r in range(world)]
+        self.csr = [S.local_csr(p, g["row_ptr"], g["col_idx"]) for p in self.plans]
+        self.max_rows, self.n_table = self.plans[0].max_rows, self.plans[0].n_table
+        self.ref = [np.unique(ci) for _, ci in self.csr]                       # referenced table rows, sorted, per rank
+        self.unref = [np.setdiff1d(np.arange(self.n_table), r) for r in self.ref]
+        self.n_rows = [p.n_rows for p in self.plans]
+        self.edges = [len(ci) for _, ci in self.csr]
+
+    def own(self, r):
+        p = self.plans[r]
+        return slice(p.table_row0, p.table_row0 + p.n_rows)
+
+    def referenced_of_peer(self, r, q):
+        """How many REAL rows of q's slice rank r references."""
+        lo = q * self.max_rows
+        return int(((self.ref[r] >= lo) & (self.ref[r] < lo + self.n_rows[q])).sum())
+
+    def never_referenced(self):
+        """Real table rows no rank references."""
+        seen = np.zeros(self.n_table, bool)
+        for r in self.ref:
+            seen[r] = True
+        real = np.zeros(self.n_table, bool)
+        for q in range(self.world):
+            real[q * self.max_rows: q * self.max_rows + self.n_rows[q]] = True
+        return int((real & ~seen).sum())
+
+
+def check_plan(name, sh):
+    """The conditions a case of graph `name` relies on, asserted before the case is trusted: a later change of edge_balanced_bounds
+    cannot hollow the cases out silently."""
+    P = sh.world
+    for r in range(P):                      # every case is rectangular, and padding exists
+        assert sh.n_table != sh.n_rows[r] and all(len(sh.ref[r]) == 0 or sh.ref[r].max() < sh.n_table for r in range(P))
+    if name == "parity":
+        assert P == 3 and len(set(sh.n_rows)) > 1, sh.n_rows                               # n_rows differs between ranks
+        for r in range(P):                                                                 # some real row of some peer is unreferenced
+            assert any(sh.referenced_of_peer(r, q) < sh.n_rows[q] for q in range(P) if q != r), r
+        deg = [np.diff(rp).max(initial=0) for rp, _ in sh.csr]
+        assert max(deg) == 300 and max(deg) > 256, deg                                     # the hub row: beyond every segment length
+        assert min(sh.n_rows) < sh.max_rows                                                # a slice that ends in padding rows
+    elif name == "last_row":
+        assert P == 3 and sh.edges[:2] == [0, 0] and sh.edges[2] > 0 and sh.n_rows[2] == 1, (sh.edges, sh.n_rows)
+    elif name == "last_four":
+        assert P == 4 and sh.n_rows.count(1) == 3, sh.n_rows
+        zero = [(r, q) for r in range(P) for q in range(P) if r != q and sh.referenced_of_peer(r, q) == 0]
+        assert len(zero) >= 2, zero                                                        # (rank, peer) pairs without a referenced row
+        assert any(sh.referenced_of_peer(r, q) > 0 for r in range(P) for q in range(1, P) if r != q)       # ... and with one, into a one-row shard
+        assert sh.never_referenced() >= 8
+    else:
+        raise KeyError(name)
+
+
+# ---- NaN poison ---------------------------------------------------------------------------------------------------------------------
+def _poison_rows(table, n_table, hd, sb, rows):
+    """NaN bit patterns of the storage type into the given rows of a bound PL table (a flat fp32 torch tensor of n_table*hd*sb/4 words)."""
+    import torch
+    if len(rows) == 0:
+        return
+    idx = torch.as_tensor(np.asarray(rows, np.int64), device=table.device)
+    if sb == 4:
+        table.view(n_table, hd)[idx] = float("nan")
+    else:
+        table.view(torch.int16).view(n_table, hd)[idx] = 0x7FC0           # bf16 quiet NaN
+
+
+# ---- the lockstep step --------------------------------------------------------------------------------------------------------------
+def lockstep(pkg, g, world, heads, outdims, params, make_ctx, alloc, *, replicate=False, poison=False, halo=False, keep_taps=False,
+             gpl_bf16=False, inspect=None, stream=None):
+    """One forward + backward of the model on `world` destination-range shards of graph g.  make_ctx(rank) -> a context with the phase
+    API (created for the model, nothing set yet); alloc(k) -> a zeroed flat fp32 torch tensor of k words on the contexts' device.
+    params = (W, a, Wo).  gpl_bf16: remote gPL partials are rounded to bf16 (nearest even) before the fp32 sum, the own one is not (the
+    library's GAT_COMM_GPL_BF16).  inspect(ctxs, out): called after the step, before the contexts are closed.  -> dict:
+      loss (fp32 sum of the ranks' losses, ascending), losses (per rank), correct;  pl / pr / hpre / hout [l][rank], y [rank] (own rows);
+      pl_ref [l][rank]: the referenced rows of the exchanged table;
+      alpha / score / galpha [l][rank] with keep_taps;  G [l][rank], GX [l][rank] (l >= 1);  gpl [l][rank]: the reduced own slice (fed back to
+      the context where the layer is exchanged);  partial [l][rank]: the whole partial table;  grads: the reduced (W, a, Wo);
+      rank_grads [rank].  stream: a torch stream the whole step runs on (hip_factory's)."""
+    if stream is not None:
+        import torch
+        with torch.cuda.stream(stream):
+            return lockstep(pkg, g, world, heads, outdims, params, make_ctx, alloc, replicate=replicate, poison=poison, halo=halo,
+                            keep_taps=keep_taps, gpl_bf16=gpl_bf16, inspect=inspect)
+    A = pkg.abi
+    S = pkg.shard
+    sh = Shards(S, g, world)
+    L = len(heads)
+    hd = [int(h) * int(d) for h, d in zip(heads, outdims)]
+    nt, mr = sh.n_table, sh.max_rows
+    ctxs, pl, gpl = [], [], []
+    try:
+        for r in range(world):
+            ctx = make_ctx(r)
+            ctxs.append(ctx)
+            plan = sh.plans[r]
+            rp_l, ci_l = sh.csr[r]
+            lo, hi = plan.row0, plan.row0 + plan.n_rows
+            ctx.set_graph(rp_l, ci_l, n_table=nt, table_row0=plan.table_row0)
+            if hasattr(ctx, "set_shard_bounds"):
+                ctx.set_shard_bounds(plan.bounds)
+            if replicate:
+                ctx.set_source_features(plan.table_features(g["x"]))
+            else:
+                ctx.set_features(g["x"][lo:hi])
+            ctx.set_labels(g["labels"][lo:hi])
+            for grp, arr in enumerate(params):
+                ctx.params_set(grp, arr)
+            ctx.zero_grad()
+            sb = getattr(ctx, "storage_bytes", 4)
+            assert all(h * sb % 4 == 0 for h in hd)
+            tabs = []
+            for l in range(L):                               # as ShardedGat.__init__ binds them
+                t = alloc(nt * hd[l] * sb // 4)
+                ctx.bind_table(0, l, t.data_ptr(), t.numel() * 4)
+                tabs.append(t)
+            pl.append(tabs)
+            t = alloc(nt * max(hd))
+            ctx.bind_table(1, 0, t.data_ptr(), t.numel() * 4)
+            gpl.append(t)
+        sb = getattr(ctxs[0], "storage_bytes", 4)
+        exchange = [bool(ctxs[0].layer_exchange(l)) for l in range(L)]
+        assert exchange == ([not replicate] + [True] * (L - 1) if world > 1 else [False] * L), exchange
+        for ctx in ctxs:
+            assert [bool(ctx.layer_exchange(l)) for l in range(L)] == exchange
+        out = {k: [[None] * world for _ in range(L)] for k in NODE_TAPS + EDGE_TAPS + ("G", "GX", "gpl", "partial", "pl_ref")}
+
+        # ---- forward
+        for l in range(L):
+            rowf = hd[l] * sb // 4                           # 32-bit words per stored PL row
+            for ctx in ctxs:
+                ctx.layer_project(l)
+            if exchange[l]:
+                tables = [pl[r][l].cpu().numpy().reshape(nt, rowf) for r in range(world)]
+                for r in range(world):
+                    new = tables[r].copy()
+                    for q in range(world):
+                        if q == r:
+                            continue
+                        if halo:                             # only the rows rank r's edges reference
+                            rows = sh.ref[r][(sh.ref[r] >= q * mr) & (sh.ref[r] < (q + 1) * mr)]
+                            new[rows] = tables[q][rows]
+                        else:                                # the whole slice, padding rows and all
+                            new[q * mr:(q + 1) * mr] = tables[q][q * mr:(q + 1) * mr]
+                    pl[r][l].copy_(_to(pl[r][l], new.reshape(-1)))
+            for r, ctx in enumerate(ctxs):
+                full = ctx.tap(A.TAP_PL, l).reshape(nt, hd[l])
+                out["pl"][l][r] = full[sh.own(r)].copy()
+                out["pl_ref"][l][r] = full[sh.ref[r]].copy()   # the exchanged table where the rank's edges read it
+                if poison:
+                    _poison_rows(pl[r][l], nt, hd[l], sb, sh.unref[r])
+                ctx.layer_forward_edges(l)
+        losses, corrects = zip(*[ctx.head_forward() for ctx in ctxs])
+        for l in range(L):
+            for r, ctx in enumerate(ctxs):
+                out["pr"][l][r] = ctx.tap(A.TAP_PR, l)
+                out["hpre"][l][r] = ctx.tap(A.TAP_HPRE, l)
+                out["hout"][l][r] = ctx.tap(A.TAP_HOUT, l)
+                if keep_taps:
+                    out["alpha"][l][r] = ctx.tap(A.TAP_ALPHA, l)
+                    out["score"][l][r] = ctx.tap(A.TAP_SCORE, l)
+        out["y"] = [ctx.tap(A.TAP_Y, L - 1) for ctx in ctxs]
+        loss = np.float32(0)
+        for v in losses:
+            loss = np.float32(loss + np.float32(v))
+        out["loss"], out["losses"], out["correct"] = float(loss), [float(v) for v in losses], int(sum(corrects))
+
+        # ---- backward
+        for ctx in ctxs:
+            ctx.head_backward()
+        for l in range(L - 1, -1, -1):
+            part = []
+            for r, ctx in enumerate(ctxs):
+                if poison:
+                    gpl[r].fill_(float("nan"))               # the whole table, beyond this layer's n_table * H*D floats too
+                ctx.layer_backward_edges(l)
+                p = gpl[r][: nt * hd[l]].cpu().numpy().reshape(nt, hd[l]).copy()
+                if poison:
+                    assert np.all(p[sh.unref[r]] == 0.0), ("gPL row of an unreferenced source is not 0", l, r)
+                    assert np.all(np.isfinite(p[sh.ref[r]])), ("gPL row of a referenced source is not finite", l, r)
+                part.append(p)
+                out["partial"][l][r] = p
+                if keep_taps:
+                    out["galpha"][l][r] = ctx.tap(A.TAP_GALPHA, l)
+            for r, ctx in enumerate(ctxs):
+                acc = np.zeros((mr, hd[l]), np.float32)
+                for q in range(world):                       # ascending rank order, the own partial at its rank's position
+                    rows = part[q][r * mr:(r + 1) * mr]
+                    acc = acc + (to_bf16(rows) if gpl_bf16 and q != r else rows)
+                out["gpl"][l][r] = acc[: sh.n_rows[r]].copy()
+                if exchange[l]:                              # (a replicated layer 0 keeps its partial table: the sum above is only reported)
+                    cur = part[r].copy()
+                    cur[r * mr:(r + 1) * mr] = acc
+                    gpl[r][: nt * hd[l]].copy_(_to(gpl[r], cur.reshape(-1)))
+                ctx.layer_backward_dense(l)
+        for l in range(L):
+            for r, ctx in enumerate(ctxs):
+                out["G"][l][r] = ctx.tap(A.TAP_G, l)
+                if l > 0:
+                    out["GX"][l][r] = ctx.tap(A.TAP_GX, l)
+        out["rank_grads"] = [[ctx.grads_get(grp) for grp in range(3)] for ctx in ctxs]
+        grads = []
+        for grp in range(3):
+            acc = np.zeros_like(out["rank_grads"][0][grp])
+            for r in range(world):
+                acc = acc + out["rank_grads"][r][grp]
+            grads.append(acc)
+        out["grads"] = grads
+        out["shards"] = sh
+        if inspect is not None:
+            inspect(ctxs, out)
+    finally:
+        for ctx in ctxs:
+            if hasattr(ctx, "close"):
+                ctx.close()
+    if poison:
+        assert_no_nan(out)
+    return out
+
+
+def _to(like, words):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(words)).to(like.device)
+
+
+def to_bf16(a):
+    """fp32 -> the nearest bf16 (ties to even), returned as fp32."""
+    u = np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)
+    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+    return u.astype(np.uint32).view(np.float32).reshape(np.shape(a))
+
+
+def _leaves(out):
+    for k, v in out.items():
+        if k in ("shards", "partial"):
+            continue
+        if k in ("loss", "correct"):
+            yield k, np.asarray(v, np.float64)
+        elif k in ("losses", "y", "grads"):
+            for i, a in enumerate(v):
+                yield f"{k}[{i}]", np.asarray(a)
+        elif k == "rank_grads":
+            for r, gs in enumerate(v):
+                for i, a in enumerate(gs):
+                    yield f"{k}[{r}][{i}]", a
+        else:
+            for l, per in enumerate(v):
+                for r, a in enumerate(per):
+                    if a is not None:
+                        yield f"{k}[{l}][{r}]", a
+
+
+def assert_no_nan(out):
+    """Nothing a (poisoned) step returns or taps holds a NaN.  (The partial gPL tables are covered row by row inside the step.)"""
+    for name, a in _leaves(out):
+        assert not np.isnan(a).any(), ("NaN in " + name)
+
+
+def assert_same(a, b, what=""):
+    """Two results of the harness are bitwise equal (values; -0.0 == 0.0)."""
+    la, lb = dict(_leaves(a)), dict(_leaves(b))
+    assert la.keys() == lb.keys()
+    for k in la:
+        assert np.array_equal(la[k], lb[k]), (what, k)
+
+
+# ---- global layouts --------------------------------------------------------------------------------------------------------------------
+def stitched(out, L, keep_taps=False):
+    """The per-rank own rows / own edges of a result put together in the unsharded order: what a one-GPU context holds.  -> dict of lists
+    per layer (y: one array)."""
+    st = {k: [np.concatenate(out[k][l], axis=0) for l in range(L)] for k in NODE_TAPS + ("G", "gpl")}
+    st["GX"] = [None] + [np.concatenate(out["GX"][l], axis=0) for l in range(1, L)]
+    st["y"] = np.concatenate(out["y"], axis=0)
+    if keep_taps:
+        for k in EDGE_TAPS:
+            st[k] = [np.concatenate(out[k][l], axis=1) for l in range(L)]
+    return st
+
+
+def fake_factory(heads, outdims, g):
+    """make_ctx / alloc of the numpy stand-in (a machine without a GPU)."""
+    import torch
+    from fake_ctx import FakeContext
+    return (lambda rank: FakeContext(heads, outdims, g["f"], g["c"])), (lambda k: torch.zeros(k))
+
+
+def hip_factory(pkg, heads, outdims, g, dtype="fp32", keep_taps=False):
+    """make_ctx / alloc / stream of the real contexts: every rank on device 0 and on ONE torch stream, which lockstep(stream=) makes the
+    current one for its own copies and poison fills, so that the lockstep order is the execution order."""
+    import torch
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    kw = dict(device=0, stream=stream.cuda_stream, keep_taps=keep_taps, dtype={"fp32": "f32", "bf16": "bf16"}[dtype])
+    return ((lambda rank: pkg.GatContext(heads, outdims, g["f"], g["c"], **kw)),
+            (lambda k: torch.zeros(k, dtype=torch.float32, device=dev)), stream)
+
+
+# ---- a shard result against the one-GPU result ---------------------------------------------------------------------------------------
+XTOL = 1e-5                 # SURVEY 8e / DESIGN 7: the P-shard result equals the one-GPU result within 1e-5 of the tensor's max-abs
+BF16_TOL = 1e-2             # the project's bf16 bar (tests/test_bf16_storage.py, test_bf16_gpl_reduce_scatter_option)
+_ORACLE = {}                # (graph, model name) -> (g, cfg, params, oracle step): one oracle per graph and model in a process
+_ONE = {}                   # (graph, model name, dtype, keep_taps) -> the one-GPU result, already held to the oracle
+
+
+def conditioned_seed(orc, cfg, g, first=PARAM_SEED, tries=40):
+    """The first Xavier seed from `first` on at which bf16 storage CAN meet its bar against the fp32 oracle.  Rounding PL to bf16 moves
+    scores across the LeakyReLU kink; every such flip is a finite jump of the gradients that no kernel can avoid (tests/step_ref.py:
+    "the gradients differ by a few %"; on these 1000-edge graphs 0.2 % .. 13 % of L2, by the seed alone).  The size of that intrinsic part is
+    known without running a kernel: the fp64 model with the table rounded (bf16_pl) against the same model without.  A seed is taken
+    when that difference is at most 1e-2 of L2 for every parameter group: half of the 2e-2 bar of tests/test_bf16_storage.py, the other
+    half stays for the kernels.  Only the two fp64 models decide, never a result of the code under test (the conditioning filter of
+    tests/test_fuzz_shapes.py, applied to the parameters).  The same seed serves the fp32 cases of the model."""
+    import step_ref as SR
+    for ps in range(first, first + tries):
+        P = orc.xavier_params(cfg, ps)
+        grads = []
+        for bf in (False, True):
+            o = SR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, bf16_pl=bf)
+            o["loss"].backward()
+            grads.append([o[k].grad.numpy() for k in ("W", "a", "Wo")])
+        if all(np.linalg.norm(b - a) <= BF16_TOL * np.linalg.norm(a) for a, b in zip(*grads)):
+            return ps
+    raise AssertionError("no parameter seed at which bf16 rounding of PL stays within 1e-2 of the gradients")
+
+
+def oracle_case(orc, graph, name, heads, outdims):
+    key = (graph, name)
+    if key not in _ORACLE:
+        g = GRAPHS[graph][0]()
+        cfg = orc.Config(list(heads), list(outdims), g["f"], g["c"])
+        fast = all((h * d, d) in FC.SHAPES for h, d in zip(heads, outdims))          # the models that run in bf16 storage too
+        P = orc.xavier_params(cfg, conditioned_seed(orc, cfg, g) if fast else PARAM_SEED)
+        _ORACLE[key] = (g, cfg, P, orc.step(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P))
+    return _ORACLE[key]
+
+
+def one_gpu(pkg, orc, graph, name, heads, outdims, dtype, keep_taps):
+    """The ONE-GPU result of the same model, storage mode and keep_taps (the harness at world 1: a square context, no exchange), held
+    to the oracle by the existing means: parity.check_context_gradients at 1e-4 for fp32, the bars of tests/test_bf16_storage.py for
+    bf16.  Computed once per process and left unchanged."""
+    key = (graph, name, dtype, keep_taps)
+    if key in _ONE:
+        return _ONE[key]
+    g, cfg, P, ref = oracle_case(orc, graph, name, heads, outdims)
+    A = pkg.abi
+    n = g["n"]
+
+    def inspect(ctxs, out):
+        ctx = ctxs[0]
+        pre = f"1gpu {graph} {dtype} taps={int(keep_taps)}: "
+        if dtype == "fp32":
+            assert abs(out["loss"] - ref.loss_sum_f64) < 1e-4 * n and out["correct"] == ref.n_correct
+            parity.check_context_gradients(orc, A, cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, ref, ctx, taps=keep_taps, prefix=pre)
+            return
+        assert abs(out["loss"] - ref.loss_sum_f64) / max(1.0, abs(ref.loss_sum_f64)) < BF16_TOL
+        assert abs(out["correct"] - ref.n_correct) <= max(2, n // 50)
+        for l in range(cfg.L):
+            if keep_taps:
+                parity.check_abs(pre + f"alpha[{l}]", ctx.tap(A.TAP_ALPHA, l), ref.taps["alpha"][l], BF16_TOL)
+            want = ref.taps["hpre"][l]
+            parity.check_abs(pre + f"hpre[{l}]", ctx.tap(A.TAP_HPRE, l) / max(1.0, np.abs(want).max()), want / max(1.0, np.abs(want).max()), BF16_TOL)
+        for nm, grp, want in (("gradW", A.PARAM_W, ref.gradW), ("grada", A.PARAM_A, ref.grada), ("gradWo", A.PARAM_WO, ref.gradWo)):
+            got = ctx.grads_get(grp)
+            rel = float(np.linalg.norm(got - want) / max(np.linalg.norm(want), 1e-30))
+            parity.record(pre + nm + " (L2)", rel, 2 * BF16_TOL)
+            assert rel < 2 * BF16_TOL, (nm, rel)
+
+    make_ctx, alloc, stream = hip_factory(pkg, heads, outdims, g, dtype, keep_taps)
+    _ONE[key] = lockstep(pkg, g, 1, heads, outdims, P, make_ctx, alloc, keep_taps=keep_taps, inspect=inspect, stream=stream)
+    return _ONE[key]
+
+
+def _bitwise(tag, got, want):
+    same = bool(np.array_equal(got, want))
+    parity.record(tag, 0.0 if same else parity.rel_err(got, want), 0.0, kind="bitwise")
+    assert same, (tag, "not bitwise", parity.rel_err(got, want))
+
+
+def check_forward(tag, out, one, L, keep_taps):
+    """Every forward tap of a rank's own rows is a row-local function of bit-identical inputs (the edge kernels pick per row, the projection
+    per row tile, F <= 128 keeps both sides off the split-K projection): bitwise the one-GPU rows, and the same #correct.
+    The one relaxation: the LOSS.  head_forward sums the rows' losses per 128-node block of the context's OWN rows, adds the block
+    partials in fp64 and rounds to fp32 (gat_dense_kernels.hip head_finalize_kernel); P shards give P rounded fp32 partial sums that the
+    exchange adds in fp32 — a sum ordered by a size the shard changes.  Nothing is downstream of it (the backward starts from y), so only
+    the loss itself is held to 1e-5; y is bitwise."""
+    st, ost = stitched(out, L, keep_taps), stitched(one, L, keep_taps)
+    for k in NODE_TAPS + (("alpha", "score") if keep_taps else ()):
+        for l in range(L):
+            _bitwise(f"{tag} {k}[{l}]", st[k][l], ost[k][l])
+    _bitwise(f"{tag} y", st["y"], ost["y"])
+    assert out["correct"] == one["correct"], (tag, out["correct"], one["correct"])
+    err = abs(out["loss"] - one["loss"]) / max(1.0, abs(one["loss"]))
+    parity.record(f"{tag} loss", err, XTOL)
+    assert err <= XTOL, (tag, out["loss"], one["loss"])
+    return st, ost
+
+
+def check_backward(tag, out, one, cfg, dtype, keep_taps, st=None, ost=None):
+    """fp32: TAP_G, TAP_GX, the reduced gPL own slices and every parameter gradient within 1e-5 of the tensor's max-abs of the one-GPU values.
+    bf16: the same 1e-5 for everything between the head and the last layer's reduced gPL (nothing there is rounded to bf16 after a
+    cross-shard sum): the last layer's G, reduced gPL and GX, grad Wo, the last layer's grad W and grad a; below that a cross-shard sum
+    is re-rounded into bf16 message rows: the project's bf16 bar, 1e-2."""
+    L = cfg.L
+    st = st or stitched(out, L, keep_taps); ost = ost or stitched(one, L, keep_taps)
+    low = XTOL if dtype == "fp32" else BF16_TOL
+    for l in range(L):
+        tol = XTOL if l == L - 1 else low
+        parity.check_rel(f"{tag} G[{l}]", st["G"][l], ost["G"][l], tol)
+        parity.check_rel(f"{tag} gPL[{l}]", st["gpl"][l], ost["gpl"][l], tol)
+        if l > 0:
+            parity.check_rel(f"{tag} GX[{l}]", st["GX"][l], ost["GX"][l], tol)
+        if keep_taps:
+            parity.check_rel(f"{tag} galpha[{l}]", st["galpha"][l], ost["galpha"][l], tol)
+    gW, ga, gWo = out["grads"]; oW, oa, oWo = one["grads"]
+    parity.check_rel(f"{tag} gradWo", gWo, oWo, XTOL)
+    w_off, a_off = 0, 0
+    for l in range(L):
+        nw, na = cfg.heads[l] * cfg.outdims[l] * 2 * cfg.in_dims[l], cfg.heads[l] * cfg.outdims[l]
+        tol = XTOL if l == L - 1 else low
+        parity.check_rel(f"{tag} gradW[{l}]", gW[w_off:w_off + nw], oW[w_off:w_off + nw], tol)
+        parity.check_rel(f"{tag} grada[{l}]", ga[a_off:a_off + na], oa[a_off:a_off + na], tol)
+        w_off += nw; a_off += na
+    assert w_off == len(gW) and a_off == len(ga)
+
+
+BWD_KEYS = ("G", "GX", "gpl", "galpha", "grads", "rank_grads")
+
+
+def assert_same_forward_close_backward(a, b, what, tol=XTOL):
+    """Two runs of a model with a GENERIC layer: its edge backward adds into gPL (and from there into everything behind it) with float
+    atomics (gat_edge_kernels.hip, the generic backward kernel's unsafeAtomicAdd), so two runs agree bit for bit in the forward only; the
+    backward is held to 1e-5 of max-abs."""
+    la, lb = dict(_leaves(a)), dict(_leaves(b))
+    assert la.keys() == lb.keys()
+    for k in la:
+        if k.split("[")[0] in BWD_KEYS:
+            assert parity.rel_err(la[k], lb[k]) <= tol, (what, k, parity.rel_err(la[k], lb[k]))
+        else:
+            assert np.array_equal(la[k], lb[k]), (what, k)
+
+
+# ---- forced kernel picks on the rectangular context (tests/test_shard_picks.py: one process per switch setting) ----------------------
+PICK_SHAPES = [(64, 8), (64, 4), (32, 8), (16, 4), (8, 8)]
+
+
+def run(pkg, orc, graph, name, heads, outdims, dtype, keep_taps=False, **kw):
+    """One lockstep step of a model on graph `graph` at the graph's P, on the HIP contexts."""
+    g, cfg, P, _ = oracle_case(orc, graph, name, heads, outdims)
+    make_ctx, alloc, stream = hip_factory(pkg, heads, outdims, g, dtype, keep_taps)
+    return lockstep(pkg, g, GRAPHS[graph][1], heads, outdims, P, make_ctx, alloc, keep_taps=keep_taps, stream=stream, **kw)
+
+
+def pick_cases(pkg, orc, tag):
+    """Under the switch setting of this process: parity graph, P = 3, layer 0 exchanged, PICK_SHAPES x both storage modes, the poison on.
+    The one-GPU reference runs under the same setting (and is held to the oracle under it); forward bitwise, backward at the bars of
+    check_backward, a second poisoned run bitwise, and the clean run bitwise the poisoned one."""
+    n = 0
+    for hd, d in PICK_SHAPES:
+        name, (heads, outdims) = shape_name(hd, d), shape_heads(hd, d)
+        for dt in FC.DTYPES:
+            parity.set_test(f"shard picks{tag}: {name} {dt}")
+            _, cfg, _, _ = oracle_case(orc, "parity", name, heads, outdims)
+            one = one_gpu(pkg, orc, "parity", name, heads, outdims, dt, False)
+            out = run(pkg, orc, "parity", name, heads, outdims, dt, poison=True)
+            st, ost = check_forward("P3:", out, one, cfg.L, False)
+            check_backward("P3:", out, one, cfg, dt, False, st, ost)
+            assert_same(run(pkg, orc, "parity", name, heads, outdims, dt, poison=True), out, "second poisoned run")
+            assert_same(run(pkg, orc, "parity", name, heads, outdims, dt), out, "clean run vs poisoned run")
+            n += 1
+    parity.flush()
+    return n
