@@ -65,6 +65,8 @@ TAP_POOLED = 18                             # readout: the pooled rows the head 
 DROPEDGE_KEEP_SELF, DROPEDGE_SHARED_LAYERS = 1, 2
 READOUT_NONE, READOUT_MEAN, READOUT_SUM, READOUT_MAX = 0, 1, 2, 3      # graph-level readout (set_readout)
 READOUT_MODES = {"none": READOUT_NONE, "mean": READOUT_MEAN, "sum": READOUT_SUM, "max": READOUT_MAX}
+LOSS_SOFTMAX_CE, LOSS_BCE, LOSS_MSE = 0, 1, 2                          # loss modes of the output head (set_loss)
+LOSS_MODES = {"softmax": LOSS_SOFTMAX_CE, "bce": LOSS_BCE, "mse": LOSS_MSE}
 (K_PROJECT, K_EDGE_FWD, K_HEAD_FWD, K_HEAD_BWD, K_EDGE_BWD, K_GPL_SUM, K_GRAD_W, K_GRAD_X, K_MISC,
  K_EXCHANGE, K_EDGE_FUSED, K_COUNT) = range(12)
 COMM_ID_BYTES = 128
@@ -213,6 +215,11 @@ def _declare(lib: C.CDLL) -> None:
         "gat_set_readout": [vp, i32, vp, i64],
         "gat_set_readout_device": [vp, i32, vp, i64],
         "gat_readout_info": [vp, P(i32), P(i64)],
+        "gat_set_loss": [vp, i32],
+        "gat_set_targets": [vp, vp, i64, i32],
+        "gat_set_targets_device": [vp, vp, i64, i32],
+        "gat_loss_info": [vp, P(i32), P(i32)],
+        "gat_target_count": [vp, vp, i64, P(i64)],
         "gat_op_readout_forward": [vp, i64, vp, i64, i64, i32, i32, vp, vp, vp],
         "gat_op_readout_backward": [vp, vp, i64, i64, i32, i32, vp, vp, i64, vp],
         "gat_set_training": [vp, i32],
@@ -491,6 +498,40 @@ class GatContext:
         _chk(self.lib.gat_readout_info(self._ctx, C.byref(m), C.byref(g)))
         return m.value, g.value
 
+    # -- loss modes of the output head (gatv2_abi.h "loss modes of the output head")
+    def set_loss(self, mode):
+        """"softmax" (the default: int32 labels, set_labels), "bce" or "mse" (float targets [rows][C] with NaN = missing, set_targets),
+        or the GAT_LOSS_* integer.  Only before the first set_labels / set_targets call."""
+        _chk(self.lib.gat_set_loss(self._ctx, loss_mode(mode)))
+
+    def set_targets(self, t):
+        """Targets [n_rows][C] — [n_graphs][C] on a readout context — as floats; NaN marks a missing entry.  After set_graph* (and
+        set_readout).  A later call with the same shape replaces the values in place (a captured step reads the new ones)."""
+        a = np.ascontiguousarray(t, np.float32)
+        if a.ndim != 2:
+            raise ValueError(f"targets must be [n_rows][n_cols], got shape {a.shape}")
+        _chk(self.lib.gat_set_targets(self._ctx, _np_ptr(a), a.shape[0], a.shape[1]))
+
+    def set_targets_device(self, d_t: int, n_rows: int, n_cols: int):
+        """set_targets on a device array (checked on the device)."""
+        _chk(self.lib.gat_set_targets_device(self._ctx, C.c_void_p(d_t or None), n_rows, n_cols))
+
+    def loss_info(self):
+        """(mode, n_cols); (0, num_classes) by default."""
+        m, n = C.c_int32(), C.c_int32()
+        _chk(self.lib.gat_loss_info(self._ctx, C.byref(m), C.byref(n)))
+        return m.value, n.value
+
+    def target_count(self, mask=None) -> int:
+        """Present (non-NaN) target entries in the rows of `mask`; None: in the current training set.  The denominator of the loss sum."""
+        n = C.c_int64()
+        if mask is None:
+            _chk(self.lib.gat_target_count(self._ctx, None, 0, C.byref(n)))
+        else:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+            _chk(self.lib.gat_target_count(self._ctx, _np_ptr(m), len(m), C.byref(n)))
+        return n.value
+
     # -- dropout (gatv2_abi.h "dropout")
     def set_dropout(self, feat_p: float = 0.0, attn_p: float = 0.0, seed: int = 0, first_step: int = 0):
         """Inverted feature / attention dropout in training mode; p in [0, 1).  The mask counter starts at first_step."""
@@ -710,6 +751,15 @@ def readout_mode(mode) -> int:
         if mode not in READOUT_MODES:
             raise ValueError(f"readout mode must be one of {sorted(READOUT_MODES)}, got {mode!r}")
         return READOUT_MODES[mode]
+    return int(mode)
+
+
+def loss_mode(mode) -> int:
+    """"softmax" / "bce" / "mse" or the GAT_LOSS_* integer -> the integer."""
+    if isinstance(mode, str):
+        if mode not in LOSS_MODES:
+            raise ValueError(f"loss mode must be one of {sorted(LOSS_MODES)}, got {mode!r}")
+        return LOSS_MODES[mode]
     return int(mode)
 
 

@@ -136,6 +136,12 @@ struct gat_ctx {
     uint8_t* mask_tmp = nullptr;                    // [n_rows] device copy of the mask of the last gat_eval_mask
     uint8_t* train_mask = nullptr;                  // [n_rows] device copy of the active training mask (re-applied when the labels change)
     int64_t n_labels = 0;                           // length the labels were set with
+    // loss modes of the output head (gatv2_abi.h): the mode (fixed once labels or targets were given), the targets [head rows][C]
+    // (one buffer for the context's life: a captured step reads later values through the same pointer), whether the mask trains
+    int32_t loss_mode = 0; bool loss_locked = false;
+    float* targets = nullptr;
+    bool mask_on = false;                           // loss_mode != 0: train_mask is active (mode 0 carries the mask in labels_eff)
+    unsigned long long* tgt_scratch = nullptr;      // [256] device: the check's result word, the count's block partials
     double* eval_loss = nullptr; int32_t* eval_cnt = nullptr;      // block partials of gat_eval_mask
     float* X0 = nullptr;
     int32_t ld0 = 0;                                // floats between rows of X0 / Xtab: in_dim rounded up to a multiple of 4 (zeros behind
@@ -284,6 +290,8 @@ static int64_t st_bytes(const gat_ctx* c) { return bf16(c) ? 2 : 4; }       // e
 static int check_layer(gat_ctx* c, int32_t l) {
     if (!c) return fail(GAT_E_INVALID, "null context");
     if (l < 0 || l >= c->cfg.num_layers) return fail(GAT_E_INVALID, "layer index out of range");
+    if (!c->buffers_ready && c->loss_mode != 0 && !c->targets)
+        return fail(GAT_E_STATE, "targets not set: the context's loss mode needs gat_set_targets (after set_graph / set_features)");
     if (!c->buffers_ready) return fail(GAT_E_STATE, "set_graph / set_features / set_labels must come first");
     return 0;
 }
@@ -882,6 +890,7 @@ int gat_layer_exchange(gat_ctx* c, int32_t l, int32_t* needed) {
 static void graph_drop_fwd(gat_ctx* c);             // a captured step (gat_step_graph) holds pointers: re-arm when they change
 static int set_labels_common(gat_ctx* c, const int32_t* labels, int64_t n_rows, hipMemcpyKind kind) {
     if (!c || !labels) return fail(GAT_E_INVALID, "gat_set_labels: null argument");
+    if (c->loss_mode != 0) return fail(GAT_E_STATE, "gat_set_labels: the context's loss mode takes float targets: call gat_set_targets");
     if (c->have_graph && n_rows != head_rows(c)) return fail(GAT_E_INVALID, readout_on(c) ? "Invalid labels length (with readout: one label per graph)" : "Invalid labels length");
     if (kind == hipMemcpyHostToDevice)
         for (int64_t i = 0; i < n_rows; ++i)
@@ -894,6 +903,7 @@ static int set_labels_common(gat_ctx* c, const int32_t* labels, int64_t n_rows, 
     if (c->labels_eff != nullptr) GAT_TRY(launch_apply_mask(c->labels, c->train_mask, c->labels_eff_buf, n_rows, c->stream));
     GAT_HIP(hipStreamSynchronize(c->stream));
     c->have_labels = true;
+    c->loss_locked = true;
     return ensure_buffers(c);
 }
 // ---- train / validation masks (the reference trains and evaluates on ALL nodes, README R:134: "later") ----------
@@ -907,6 +917,15 @@ static int upload_mask(gat_ctx* c, const uint8_t* mask, int64_t n_rows, uint8_t*
 }
 int gat_set_train_mask(gat_ctx* c, const uint8_t* mask, int64_t n_rows) {
     if (!c) return fail(GAT_E_INVALID, "null context");
+    if (c->loss_mode != 0) {                        // the BCE / MSE head reads the mask byte of a row itself: no labels_eff
+        if (mask) {
+            GAT_TRY(upload_mask(c, mask, n_rows, &c->train_mask));
+            GAT_HIP(hipStreamSynchronize(c->stream));
+        }
+        c->mask_on = mask != nullptr;
+        graph_drop_fwd(c);                          // a captured step holds the old mask pointer (or none)
+        return 0;
+    }
     if (!mask) {                                    // back to the reference's behaviour: every node trains
         c->labels_eff = nullptr;                    // (the buffer stays owned by the context)
         graph_drop_fwd(c);
@@ -920,9 +939,12 @@ int gat_set_train_mask(gat_ctx* c, const uint8_t* mask, int64_t n_rows) {
     graph_drop_fwd(c);                              // a captured step holds the old label pointer
     return 0;
 }
+static int eval_mask_targets(gat_ctx* c, const uint8_t* mask, int64_t n_rows, double* loss_sum, int32_t* n_correct, int32_t* n_nodes);
+static LossHeadArgs loss_head_args(gat_ctx* c);
 int gat_eval_mask(gat_ctx* c, const uint8_t* mask, int64_t n_rows, double* loss_sum, int32_t* n_correct, int32_t* n_nodes) {
     GAT_TRY(check_layer(c, 0));
     if (!mask) return fail(GAT_E_INVALID, "gat_eval_mask: null mask");
+    if (c->loss_mode != 0) return eval_mask_targets(c, mask, n_rows, loss_sum, n_correct, n_nodes);
     if (!c->y_valid) GAT_TRY(gat_head_forward(c, nullptr, nullptr));     // after a fused head step: y = f(H_L, Wo), both still there
     GAT_TRY(upload_mask(c, mask, n_rows, &c->mask_tmp));
     const int blocks = 256;
@@ -944,6 +966,97 @@ int gat_set_labels(gat_ctx* c, const int32_t* labels, int64_t n_rows) {
 }
 int gat_set_labels_device(gat_ctx* c, const int32_t* labels, int64_t n_rows) {
     return set_labels_common(c, labels, n_rows, hipMemcpyDeviceToDevice);
+}
+
+// ---- loss modes of the output head (gatv2_abi.h) -------------------------------------------------------------------
+int gat_set_loss(gat_ctx* c, int32_t mode) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (mode < GAT_LOSS_SOFTMAX_CE || mode > GAT_LOSS_MSE) return fail(GAT_E_INVALID, "gat_set_loss: mode must be 0 (softmax cross-entropy), 1 (BCE) or 2 (MSE)");
+    if (c->loss_locked) return fail(GAT_E_STATE, "gat_set_loss: call it before the first gat_set_labels / gat_set_targets call");
+    if (mode == GAT_LOSS_SOFTMAX_CE) { c->loss_mode = 0; return 0; }      // the default: nothing is touched
+    if (c->cfg.flat_lrelu_index)
+        return fail(GAT_E_UNSUPPORTED, "gat_set_loss: not with flat_lrelu_index = 1 (the BCE / MSE head writes gH only, never the last layer's g)");
+#ifdef GAT_EXPERIMENTS                               // (the release library does not know the switch's name)
+    if (c->dbg != 0) return fail(GAT_E_UNSUPPORTED, "gat_set_loss: not with a GAT_DBG timing experiment");
+#endif
+    c->loss_mode = mode;
+    return 0;
+}
+int gat_loss_info(gat_ctx* c, int32_t* mode, int32_t* n_cols) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (mode) *mode = c->loss_mode;
+    if (n_cols) *n_cols = c->cfg.num_classes;
+    return 0;
+}
+static int set_targets_common(gat_ctx* c, const float* t, int64_t n_rows, int32_t n_cols, bool on_host) {
+    if (!c || !t) return fail(GAT_E_INVALID, "gat_set_targets: null argument");
+    if (c->loss_mode == 0) return fail(GAT_E_STATE, "gat_set_targets: the context's loss is softmax cross-entropy (gat_set_loss comes first); it takes gat_set_labels");
+    if (!c->have_graph) return fail(GAT_E_STATE, "gat_set_targets: set the graph first (and gat_set_readout, on a readout context)");
+    const int32_t C = c->cfg.num_classes;
+    if (n_cols != C) return fail(GAT_E_INVALID, "gat_set_targets: n_cols differs from num_classes");
+    if (n_rows < 0) return fail(GAT_E_INVALID, "gat_set_targets: negative n_rows");
+    if (n_rows * (int64_t)C >= (1ll << 31)) return fail(GAT_E_UNSUPPORTED, "gat_set_targets: n_rows * n_cols >= 2^31 (n_correct is int32)");
+    if (n_rows != head_rows(c)) return fail(GAT_E_INVALID, readout_on(c) ? "gat_set_targets: n_rows differs from the graph count (with readout: one target row per graph)" : "gat_set_targets: n_rows differs from the node count");
+    const int64_t n = n_rows * C;
+    if (!c->tgt_scratch) GAT_TRY(dalloc(c, &c->tgt_scratch, 256));
+    int64_t bad = -1;
+    if (on_host) bad = targets_check_host(t, n, c->loss_mode);
+    else GAT_TRY(targets_check_device(t, n, c->loss_mode, c->tgt_scratch, &bad, c->stream));      // before anything reads the array
+    if (bad >= 0)
+        return fail(GAT_E_INVALID, "gat_set_targets: entry " + std::to_string(bad) + " (row " + std::to_string(bad / C) + ", column " + std::to_string(bad % C) +
+                                   (c->loss_mode == GAT_LOSS_BCE ? ") is outside [0, 1] or infinite (BCE targets are probabilities or NaN)" : ") is infinite (MSE targets are finite or NaN)"));
+    if (!c->targets) GAT_TRY(dalloc(c, &c->targets, n));                 // later calls have the same shape: the same buffer
+    GAT_HIP(hipMemcpyAsync(c->targets, t, (size_t)n * sizeof(float), on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    c->n_labels = n_rows;
+    c->have_labels = true;                          // the head's rows have their supervision: the buffers can be sized
+    c->loss_locked = true;
+    return ensure_buffers(c);
+}
+int gat_set_targets(gat_ctx* c, const float* t, int64_t n_rows, int32_t n_cols) { return set_targets_common(c, t, n_rows, n_cols, true); }
+int gat_set_targets_device(gat_ctx* c, const float* d_t, int64_t n_rows, int32_t n_cols) { return set_targets_common(c, d_t, n_rows, n_cols, false); }
+int gat_target_count(gat_ctx* c, const uint8_t* mask, int64_t n_rows, int64_t* n_entries) {
+    if (!c || !n_entries) return fail(GAT_E_INVALID, "gat_target_count: null argument");
+    if (c->loss_mode == 0 || !c->targets) return fail(GAT_E_STATE, "gat_target_count: targets not set (gat_set_loss with BCE / MSE, then gat_set_targets)");
+    const uint8_t* d_mask = c->mask_on ? c->train_mask : nullptr;       // null argument: the current training set
+    if (mask) {
+        GAT_TRY(upload_mask(c, mask, n_rows, &c->mask_tmp));
+        d_mask = c->mask_tmp;
+    }
+    GAT_TRY(launch_target_count(c->targets, d_mask, c->n_labels, c->cfg.num_classes, c->tgt_scratch, c->stream));
+    unsigned long long part[256];
+    GAT_HIP(hipMemcpyAsync(part, c->tgt_scratch, sizeof(part), hipMemcpyDeviceToHost, c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    unsigned long long tot = 0;
+    for (int b = 0; b < 256; ++b) tot += part[b];
+    *n_entries = (int64_t)tot;
+    return 0;
+}
+// gat_eval_mask in the BCE / MSE modes: the forward kernel with the given mask in place of the training mask — the sum of the loss
+// terms and the correct count over the present entries of the mask's rows, from the head's input rows of the last forward
+static int eval_mask_targets(gat_ctx* c, const uint8_t* mask, int64_t n_rows, double* loss_sum, int32_t* n_correct, int32_t* n_nodes) {
+    GAT_TRY(upload_mask(c, mask, n_rows, &c->mask_tmp));
+    LossHeadArgs a = loss_head_args(c);
+    const int blocks = loss_head_blocks(a.n_rows, a.C, a.DL, a.mode);
+    if (blocks < 0) return fail(GAT_E_UNSUPPORTED, "output head: num_classes*D_last too large for the LDS tile");
+    if (!c->eval_loss) { GAT_TRY(dalloc(c, &c->eval_loss, head_blocks(a.n_rows))); GAT_TRY(dalloc(c, &c->eval_cnt, head_blocks(a.n_rows))); }
+    a.mask = c->mask_tmp; a.loss_partial = c->eval_loss; a.correct_partial = c->eval_cnt; a.loss_out = nullptr; a.correct_out = nullptr;
+    {
+        Scope t(c, GAT_K_HEAD_FWD);
+        GAT_TRY(launch_loss_head_forward(a, c->stream));
+    }
+    c->y_valid = true;                              // (y does not depend on the mask)
+    std::vector<double> hl((size_t)blocks); std::vector<int32_t> hc((size_t)blocks);
+    GAT_HIP(hipMemcpyAsync(hl.data(), c->eval_loss, (size_t)blocks * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    GAT_HIP(hipMemcpyAsync(hc.data(), c->eval_cnt, (size_t)blocks * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    double l = 0.0; int64_t cr = 0, nn = 0;
+    for (int b = 0; b < blocks; ++b) { l += hl[(size_t)b]; cr += hc[(size_t)b]; }
+    for (int64_t i = 0; i < n_rows; ++i) nn += mask[i] != 0;
+    if (loss_sum) *loss_sum = l;
+    if (n_correct) *n_correct = (int32_t)cr;
+    if (n_nodes) *n_nodes = (int32_t)nn;
+    return 0;
 }
 
 // ---- parameters --------------------------------------------------------------------------------------------
@@ -1137,6 +1250,7 @@ static int readout_unpool(gat_ctx* c) {
     return launch_readout_backward(a, c->stream);
 }
 static void head_args(gat_ctx* c, HeadArgs* f, HeadBwdArgs* b);
+static LossHeadArgs loss_head_args(gat_ctx* c);
 int gat_head_forward(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
     GAT_TRY(check_layer(c, 0));
     HeadArgs a{}; HeadBwdArgs unused{};
@@ -1144,7 +1258,8 @@ int gat_head_forward(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
     GAT_TRY(readout_pool(c));
     {
         Scope t(c, GAT_K_HEAD_FWD);
-        GAT_TRY(launch_head_forward(a, c->stream));
+        if (c->loss_mode != 0) GAT_TRY(launch_loss_head_forward(loss_head_args(c), c->stream));
+        else GAT_TRY(launch_head_forward(a, c->stream));
     }
     c->y_valid = true;
     if (loss_sum || n_correct) {
@@ -1164,7 +1279,8 @@ int gat_head_backward(gat_ctx* c) {
     head_args(c, &unused, &a);
     {
         Scope t(c, GAT_K_HEAD_BWD);
-        GAT_TRY(launch_head_backward(a, c->stream));
+        if (c->loss_mode != 0) GAT_TRY(launch_loss_head_grad(loss_head_args(c), false, c->stream));
+        else GAT_TRY(launch_head_backward(a, c->stream));
     }
     return readout_unpool(c);
 }
@@ -1401,9 +1517,21 @@ static void head_args(gat_ctx* c, HeadArgs* f, HeadBwdArgs* b) {
         b->g = nullptr; b->hpre = nullptr; b->gh_out = c->ro_gP; b->gh_stride = y.D;
     }
 }
+// the BCE / MSE head (gatv2_abi.h "loss modes of the output head"): the same rows, outputs and partial buffers as head_args
+static LossHeadArgs loss_head_args(gat_ctx* c) {
+    HeadArgs f{}; HeadBwdArgs b{};
+    head_args(c, &f, &b);
+    LossHeadArgs a{};
+    a.Wo = f.Wo; a.X = f.HL; a.T = c->targets; a.mask = c->mask_on ? c->train_mask : nullptr; a.y = f.y;
+    a.gh_out = b.gh_out; a.gh_stride = b.gh_stride; a.gradWo = b.gradWo; a.partial = b.partial;
+    a.loss_partial = f.loss_partial; a.correct_partial = f.correct_partial; a.loss_out = f.loss_out; a.correct_out = f.correct_out;
+    a.n_rows = f.n_rows; a.C = f.C; a.DL = f.DL; a.mode = c->loss_mode;
+    return a;
+}
 // gat_step: the head's forward and backward as ONE kernel when nothing needs the class probabilities in HBM
 static bool fused_head(gat_ctx* c) {
     if (c->cfg.keep_taps) return false;
+    if (c->loss_mode != 0) return true;             // the gradient kernel's FUSED form has no shape restriction of its own
     HeadArgs f{}; HeadBwdArgs b{};
     head_args(c, &f, &b);
     return head_step_supported(b);
@@ -1416,7 +1544,8 @@ static int head_step(gat_ctx* c, bool with_gh = true) {
     {
         Scope t(c, GAT_K_HEAD_BWD);
         c->y_valid = false;
-        GAT_TRY(launch_head_step(f, b, c->stream));
+        if (c->loss_mode != 0) GAT_TRY(launch_loss_head_grad(loss_head_args(c), true, c->stream));
+        else GAT_TRY(launch_head_step(f, b, c->stream));
     }
     return readout_unpool(c);
 }
@@ -1425,6 +1554,7 @@ static int head_step(gat_ctx* c, bool with_gh = true) {
 // of the forward's rows left in the caches when a pass's gathers exceed the Infinity Cache; fused per row, the second walk of
 // a row's sources comes a few microseconds after the first.
 static bool fused_last(gat_ctx* c) {
+    if (c->loss_mode != 0) return false;            // the BCE / MSE head runs the separate passes
     if (!fused_head(c) || bf16(c) || c->comm || c->n_table != c->n_rows || c->cfg.flat_lrelu_index || res_route(c) || edge_feat_on(c) || readout_on(c)) return false;   // no residual / norm / edge-feature / readout form
     const Layer& y = c->layers.back();
     if (!edge_fast_path(y.H, y.D, c->n_table) || !y.stash || c->stash == nullptr || c->gH == nullptr) return false;
@@ -2475,8 +2605,21 @@ static void edge_feature_bytes(const gat_ctx* c, double* k) {
     }
 }
 static int algorithmic_bytes_nodes(gat_ctx* c, double* bytes_step, double* per_kernel);
+static int algorithmic_bytes_softmax(gat_ctx* c, double* bytes_step, double* per_kernel);
 int gat_algorithmic_bytes(gat_ctx* c, double* bytes_step, double* per_kernel) {
     if (!c || !c->have_graph) return fail(GAT_E_STATE, "graph not set");
+    if (c->loss_mode == 0) return algorithmic_bytes_softmax(c, bytes_step, per_kernel);
+    // loss modes (gatv2_abi.h "loss modes of the output head"): each head class reads 4*rows*C bytes of targets where the softmax head
+    // reads 4*rows of labels
+    double k[GAT_K_COUNT] = {0}, tot = 0;
+    GAT_TRY(algorithmic_bytes_softmax(c, nullptr, k));
+    const double extra = 4.0 * (double)head_rows(c) * (c->cfg.num_classes - 1.0);
+    k[GAT_K_HEAD_FWD] += extra; k[GAT_K_HEAD_BWD] += extra;
+    for (int i = 0; i < GAT_K_COUNT; ++i) { tot += k[i]; if (per_kernel) per_kernel[i] = k[i]; }
+    if (bytes_step) *bytes_step = tot;
+    return 0;
+}
+static int algorithmic_bytes_softmax(gat_ctx* c, double* bytes_step, double* per_kernel) {
     if (!readout_on(c)) return algorithmic_bytes_nodes(c, bytes_step, per_kernel);
     // readout (gatv2_abi.h "graph-level readout"): the head classes priced with G rows; the pool reads N*DL and writes G*DL, the un-pool
     // reads G*DL and writes N*DL (under misc, fp32)

@@ -4,6 +4,7 @@
 #include "gat_internal.h"
 
 #include <algorithm>
+#include <type_traits>
 
 #include <cstdlib>
 
@@ -1014,6 +1015,467 @@ int launch_clip(float* g, int64_t n, float thresh, float* scratch, hipStream_t s
     hipLaunchKernelGGL(sumsq_kernel, dim3(1), dim3(1024), 0, s, g, n, scratch);
     GAT_HIP(hipGetLastError());
     hipLaunchKernelGGL(clip_scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g, n, scratch, thresh);
+    GAT_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- loss modes of the output head: BCE / MSE on float targets (gatv2_abi.h "loss modes of the output head") -----------------------
+// Both kernels are persistent over tiles of NB <= 128 rows.  LDS: Wo [C][ws], the tile's targets — afterwards dz — [NB][ldz], the
+// tile's input rows [NB][ldx]; ws, ldz, ldx odd.  Work inside a tile is dealt by flat entry index q = r*C + c (logits, loss, dz: the
+// global y / T accesses are q itself, coalesced), by r*DL + d (gH) and by c*DL + d (gradWo, registers across the tiles of a block):
+// no thread owns a row, so every C >= 1 and D_last >= 1 takes the same path (DLT = 0).
+// DLT = D_last in {4, 8, 16} with C <= 128 is the register-blocked form of the same tile, laid out like head_step_kernel: thread
+// (row, column half) keeps its input row in registers and walks its columns with wave-uniform (broadcast) reads of Wo; then waves 0-1
+// own a row each for gH and waves 2-3 own (column, row part) for gradWo, concurrently.  Every z is the same fmaf chain in both forms.
+namespace {
+
+// y, loss term, dz and "correct" of one entry from its logit and target (the expressions of the header, fp32; hardware exp2 / log2 /
+// rcp as in the softmax head: 1 ulp each, against the 1e-4 bars)
+template <int MODE>
+__device__ __forceinline__ void loss_entry(float z, float t, float& y, float& l, float& dz, int& ok) {
+    if constexpr (MODE == GAT_LOSS_BCE) {
+        const float e = __builtin_amdgcn_exp2f(-fabsf(z) * 1.4426950408889634f);     // exp(-|z|) in (0, 1]: no overflow for either sign
+        const float r = __builtin_amdgcn_rcpf(1.0f + e);
+        y = z >= 0.f ? r : e * r;
+        // log1p(e): below 2^-10 the series e - e^2/2 (error < e^3/3), where 1 + e would round e away; absolute error < 1e-7 throughout
+        const float lp = e < 0.0009765625f ? e * fmaf(-0.5f, e, 1.0f) : __logf(1.0f + e);
+        l = fmaf(-t, z, fmaxf(z, 0.f)) + lp;
+        dz = y - t;
+        ok = (z > 0.f) == (t > 0.5f);
+    } else {
+        const float d = z - t;
+        y = z; l = d * d; dz = 2.0f * d; ok = 0;
+    }
+}
+
+struct LossTile { float* s_wo; float* s_dz; float* s_x; int NB, ldz, ldx, ws; };
+
+__device__ __forceinline__ LossTile loss_tile_setup(const LossHeadArgs& A, float* lds, int NB, int ldz, int ldx, int ws) {
+    LossTile L{lds, lds + A.C * ws, lds + A.C * ws + NB * ldz, NB, ldz, ldx, ws};
+    const int DL = A.DL;
+    int c = threadIdx.x / DL, j = threadIdx.x % DL;
+    const int dq = 256 / DL, dr = 256 % DL;
+    for (int i = threadIdx.x; i < A.C * DL; i += 256) {
+        L.s_wo[c * ws + j] = A.Wo[i];
+        c += dq; j += dr;
+        if (j >= DL) { j -= DL; ++c; }
+    }
+    return L;
+}
+
+// the tile's targets (NaN where the entry does not contribute: missing, or a row outside the mask) and input rows -> LDS
+__device__ __forceinline__ void loss_tile_load(const LossHeadArgs& A, const LossTile& L, int64_t n0, int rows_here) {
+    const int C = A.C, DL = A.DL;
+    {
+        const float* tt = A.T + n0 * C;
+        const int tot = rows_here * C;
+        int r = threadIdx.x / C, c = threadIdx.x % C;
+        const int dq = 256 / C, dr = 256 % C;
+        constexpr int U = 8;                             // loads in flight per thread: the tile is one latency per 2048 entries, not per 256
+        for (int q0 = threadIdx.x; q0 < tot; q0 += 256 * U) {
+            float v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) { const int q = q0 + u * 256; v[u] = q < tot ? tt[q] : 0.f; }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (q0 + u * 256 < tot) {
+                    const bool on = A.mask == nullptr || A.mask[n0 + r] != 0;
+                    L.s_dz[r * L.ldz + c] = on ? v[u] : __builtin_nanf("");
+                }
+                r += dq; c += dr;
+                if (c >= C) { c -= C; ++r; }
+            }
+        }
+    }
+    {
+        const float* xt = A.X + n0 * DL;
+        int r = threadIdx.x / DL, j = threadIdx.x % DL;
+        const int dq = 256 / DL, dr = 256 % DL;
+        for (int q = threadIdx.x; q < rows_here * DL; q += 256) {
+            L.s_x[r * L.ldx + j] = xt[q];
+            r += dq; j += dr;
+            if (j >= DL) { j -= DL; ++r; }
+        }
+    }
+}
+
+// One entry: from its logit and target (NaN = does not contribute) the loss / count into the thread's accumulators (LOSS); -> what the
+// entry leaves behind: y (WRITE_Y) or dz (GRAD)
+template <int MODE, bool WRITE_Y, bool LOSS, bool GRAD>
+__device__ __forceinline__ float loss_entry_apply(float z, float t, double& loss_acc, int& corr_acc) {
+    float y, l, dz; int ok;
+    loss_entry<MODE>(z, t, y, l, dz, ok);
+    const bool on = !(t != t);
+    if constexpr (LOSS) { loss_acc += on ? (double)l : 0.0; corr_acc += (on && ok) ? 1 : 0; }
+    if constexpr (GRAD) return on ? dz : 0.0f;
+    return y;
+}
+
+// ---- the any-shape form: the tile's work dealt by flat index ----
+// logits of the tile's entries q = r*C + c: y straight to yt[q] (WRITE_Y), dz over the target in LDS (GRAD)
+template <int MODE, bool WRITE_Y, bool LOSS, bool GRAD>
+__device__ __forceinline__ void loss_entries_any(const LossHeadArgs& A, const LossTile& L, int rows_here, float* __restrict__ yt,
+                                                 double& loss_acc, int& corr_acc) {
+    const int C = A.C, DL = A.DL;
+    int r = threadIdx.x / C, c = threadIdx.x % C;
+    const int dq = 256 / C, dr = 256 % C;
+    for (int q = threadIdx.x; q < rows_here * C; q += 256) {
+        const float t = L.s_dz[r * L.ldz + c];
+        const float* w = L.s_wo + c * L.ws;
+        const float* x = L.s_x + r * L.ldx;
+        float z = 0.f;
+        for (int j = 0; j < DL; ++j) z = fmaf(w[j], x[j], z);          // ascending j, as the softmax head
+        const float out = loss_entry_apply<MODE, WRITE_Y, LOSS, GRAD>(z, t, loss_acc, corr_acc);
+        if constexpr (WRITE_Y) yt[q] = out;
+        if constexpr (GRAD) L.s_dz[r * L.ldz + c] = out;
+        r += dq; c += dr;
+        if (c >= C) { c -= C; ++r; }
+    }
+}
+// the block's gradWo partial: entry (c, d) = threadIdx.x + p*256 in wacc[p], p < ceil(C*DL / 256) <= 8
+struct GradWoAny {
+    float wacc[8]; int wc[8], wd[8];
+    __device__ __forceinline__ void init(int DL) {
+#pragma unroll
+        for (int p = 0; p < 8; ++p) { wacc[p] = 0.f; const int t = threadIdx.x + p * 256; wc[p] = t / DL; wd[p] = t % DL; }
+    }
+};
+// gH rows of the tile (one thread per (r, d)) and the tile's term of gradWo, from dz in LDS
+__device__ __forceinline__ void loss_grads_any(const LossHeadArgs& A, const LossTile& L, int64_t n0, int rows_here, GradWoAny& W) {
+    const int C = A.C, DL = A.DL, CD = C * DL;
+    const int gstride = A.gh_stride ? A.gh_stride : DL;
+    int r = threadIdx.x / DL, d = threadIdx.x % DL;
+    const int dq = 256 / DL, dr = 256 % DL;
+    for (int q = threadIdx.x; q < rows_here * DL; q += 256) {          // gH[r][d] = sum_c dz[r][c] Wo[c][d], ascending c
+        const float* dzr = L.s_dz + r * L.ldz;
+        float acc = 0.f;
+        for (int c = 0; c < C; ++c) acc = fmaf(L.s_wo[c * L.ws + d], dzr[c], acc);
+        A.gh_out[(n0 + r) * gstride + d] = acc;
+        r += dq; d += dr;
+        if (d >= DL) { d -= DL; ++r; }
+    }
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {                                       // gradWo[c][d] += sum_r dz[r][c] X[r][d], ascending r
+        if (threadIdx.x + p * 256 < CD) {
+            float acc = W.wacc[p];
+            const float* dzc = L.s_dz + W.wc[p];
+            const float* xd = L.s_x + W.wd[p];
+            for (int rr = 0; rr < rows_here; ++rr) acc = fmaf(dzc[rr * L.ldz], xd[rr * L.ldx], acc);
+            W.wacc[p] = acc;
+        }
+    }
+}
+__device__ __forceinline__ void loss_partial_any(const LossHeadArgs& A, const GradWoAny& W) {
+    const int CD = A.C * A.DL;
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+        const int t = threadIdx.x + p * 256;
+        if (t < CD) A.partial[(int64_t)blockIdx.x * CD + t] = W.wacc[p];
+    }
+}
+
+// ---- the register-blocked form: D_last = DLT in {4, 8, 16}, C <= 128, ws == DLT ----
+// thread (row, column half): the row's X in registers, its columns in ascending order; half is wave-uniform, so is c, and the Wo reads
+// broadcast.  What an entry leaves behind (y or dz) stays in the LDS tile.
+template <int MODE, int DLT, bool WRITE_Y, bool LOSS, bool GRAD>
+__device__ __forceinline__ void loss_entries_blocked(const LossHeadArgs& A, const LossTile& L, int rows_here, double& loss_acc, int& corr_acc) {
+    const int C = A.C;
+    const int r = threadIdx.x & 127, half = threadIdx.x >> 7;
+    const int ch = (C + 1) >> 1;
+    const int c0 = half * ch, c1 = (c0 + ch < C) ? c0 + ch : C;
+    if (r >= rows_here) return;
+    float x[DLT];
+#pragma unroll
+    for (int j = 0; j < DLT; ++j) x[j] = L.s_x[r * L.ldx + j];
+    float* tr = L.s_dz + r * L.ldz;
+    for (int c = c0; c < c1; ++c) {
+        const float* w = L.s_wo + c * DLT;
+        float z = 0.f;
+#pragma unroll
+        for (int j = 0; j < DLT; ++j) z = fmaf(w[j], x[j], z);          // ascending j, as the softmax head
+        tr[c] = loss_entry_apply<MODE, WRITE_Y, LOSS, GRAD>(z, tr[c], loss_acc, corr_acc);
+    }
+}
+// the tile's y: LDS -> one contiguous block of global memory, coalesced
+__device__ __forceinline__ void loss_store_y(const LossHeadArgs& A, const LossTile& L, int64_t n0, int rows_here) {
+    const int C = A.C;
+    float* yt = A.y + n0 * C;
+    int r = threadIdx.x / C, c = threadIdx.x % C;
+    const int dq = 256 / C, dr = 256 % C;
+    for (int q = threadIdx.x; q < rows_here * C; q += 256) {
+        yt[q] = L.s_dz[r * L.ldz + c];
+        r += dq; c += dr;
+        if (c >= C) { c -= C; ++r; }
+    }
+}
+// waves 0-1 own a row each for gH; waves 2-3 own (column, row part) for gradWo — nparts = 128 / C parts of ceil(NB / nparts)
+// consecutive rows — and run beside them
+template <int DLT>
+struct GradWoBlocked {
+    float wacc[DLT]; int wc, part, nparts, rows_per;
+    __device__ __forceinline__ void init(int C, int NB) {
+        const int t2 = (int)threadIdx.x - 128;
+        nparts = 128 / C; rows_per = (NB + nparts - 1) / nparts;
+        wc = t2 >= 0 ? t2 % C : 0; part = t2 >= 0 ? t2 / C : nparts;       // part >= nparts: no gradWo work
+#pragma unroll
+        for (int d = 0; d < DLT; ++d) wacc[d] = 0.f;
+    }
+};
+template <int DLT>
+__device__ __forceinline__ void loss_grads_blocked(const LossHeadArgs& A, const LossTile& L, int64_t n0, int rows_here, GradWoBlocked<DLT>& W) {
+    const int C = A.C, tid = threadIdx.x;
+    if (tid < 128) {
+        if (tid < rows_here) {                           // gH[r][:] = sum_c dz[r][c] Wo[c][:], ascending c
+            float acc[DLT];
+#pragma unroll
+            for (int d = 0; d < DLT; ++d) acc[d] = 0.f;
+            const float* dzr = L.s_dz + tid * L.ldz;
+            for (int c = 0; c < C; ++c) {
+                const float z = dzr[c];
+#pragma unroll
+                for (int d = 0; d < DLT; ++d) acc[d] = fmaf(L.s_wo[c * DLT + d], z, acc[d]);
+            }
+            float* out = A.gh_out + (n0 + tid) * (A.gh_stride ? A.gh_stride : DLT);
+#pragma unroll
+            for (int d = 0; d < DLT; ++d) out[d] = acc[d];
+        }
+    } else if (W.part < W.nparts) {                      // gradWo[c][:] += sum_r dz[r][c] X[r][:], ascending r inside the part
+        const int r0 = W.part * W.rows_per, r1 = (r0 + W.rows_per < rows_here) ? r0 + W.rows_per : rows_here;
+        for (int r = r0; r < r1; ++r) {
+            const float z = L.s_dz[r * L.ldz + W.wc];
+#pragma unroll
+            for (int d = 0; d < DLT; ++d) W.wacc[d] = fmaf(z, L.s_x[r * L.ldx + d], W.wacc[d]);
+        }
+    }
+}
+// the parts of a column added in ascending order; s_tmp [nparts][C][DLT] lies in the tile region (its size: loss_head_tile)
+template <int DLT>
+__device__ __forceinline__ void loss_partial_blocked(const LossHeadArgs& A, const LossTile& L, const GradWoBlocked<DLT>& W) {
+    const int C = A.C, CD = C * DLT;
+    __syncthreads();
+    float* s_tmp = L.s_dz;
+    if (W.part < W.nparts) {
+#pragma unroll
+        for (int d = 0; d < DLT; ++d) s_tmp[(W.part * C + W.wc) * DLT + d] = W.wacc[d];
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < CD; i += 256) {
+        float tot = s_tmp[i];
+        for (int p = 1; p < W.nparts; ++p) tot += s_tmp[p * CD + i];
+        A.partial[(int64_t)blockIdx.x * CD + i] = tot;
+    }
+}
+
+// the block's loss / count partial, fixed order: lanes by shuffle, then the four waves
+__device__ __forceinline__ void loss_block_partial(double loss_acc, int corr_acc, double* loss_partial, int32_t* correct_partial) {
+    __shared__ double s_loss[4];
+    __shared__ int32_t s_corr[4];
+    for (int off = 32; off > 0; off >>= 1) {
+        loss_acc += __shfl_down(loss_acc, off);
+        corr_acc += __shfl_down(corr_acc, off);
+    }
+    if ((threadIdx.x & 63) == 0) { s_loss[threadIdx.x >> 6] = loss_acc; s_corr[threadIdx.x >> 6] = corr_acc; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        loss_partial[blockIdx.x] = (s_loss[0] + s_loss[1]) + (s_loss[2] + s_loss[3]);
+        correct_partial[blockIdx.x] = s_corr[0] + s_corr[1] + s_corr[2] + s_corr[3];
+    }
+}
+
+// DLT = 0: the any-shape form; DLT = D_last: the register-blocked form
+template <int MODE, int DLT>
+__global__ __launch_bounds__(256) void loss_head_forward_kernel(LossHeadArgs A, int32_t NB, int32_t ldz, int32_t ldx, int32_t ws) {
+    extern __shared__ float lds[];
+    const LossTile L = loss_tile_setup(A, lds, NB, ldz, ldx, ws);
+    double loss_acc = 0.0;
+    int corr_acc = 0;
+    const int64_t ntiles = (A.n_rows + NB - 1) / NB;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t n0 = tile * NB;
+        const int rows_here = (int)((A.n_rows - n0 < NB) ? (A.n_rows - n0) : NB);
+        __syncthreads();                                 // previous tile fully consumed (and Wo loaded)
+        loss_tile_load(A, L, n0, rows_here);
+        __syncthreads();
+        if constexpr (DLT > 0) {
+            loss_entries_blocked<MODE, DLT, true, true, false>(A, L, rows_here, loss_acc, corr_acc);
+            __syncthreads();
+            loss_store_y(A, L, n0, rows_here);
+        } else {
+            loss_entries_any<MODE, true, true, false>(A, L, rows_here, A.y + n0 * A.C, loss_acc, corr_acc);
+        }
+    }
+    loss_block_partial(loss_acc, corr_acc, A.loss_partial, A.correct_partial);
+}
+
+// z recomputed as in the forward kernel; dz in LDS; gH rows and the block's gradWo partial.  FUSED: the loss / count partials too.
+template <int MODE, bool FUSED, int DLT>
+__global__ __launch_bounds__(256) void loss_head_grad_kernel(LossHeadArgs A, int32_t NB, int32_t ldz, int32_t ldx, int32_t ws) {
+    extern __shared__ float lds[];
+    const LossTile L = loss_tile_setup(A, lds, NB, ldz, ldx, ws);
+    double loss_acc = 0.0;
+    int corr_acc = 0;
+    typename std::conditional<(DLT > 0), GradWoBlocked<(DLT > 0 ? DLT : 1)>, GradWoAny>::type W;
+    if constexpr (DLT > 0) W.init(A.C, NB); else W.init(A.DL);
+    const int64_t ntiles = (A.n_rows + NB - 1) / NB;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t n0 = tile * NB;
+        const int rows_here = (int)((A.n_rows - n0 < NB) ? (A.n_rows - n0) : NB);
+        __syncthreads();                                 // previous tile fully consumed (and Wo loaded)
+        loss_tile_load(A, L, n0, rows_here);
+        __syncthreads();
+        if constexpr (DLT > 0) loss_entries_blocked<MODE, DLT, false, FUSED, true>(A, L, rows_here, loss_acc, corr_acc);
+        else loss_entries_any<MODE, false, FUSED, true>(A, L, rows_here, nullptr, loss_acc, corr_acc);
+        __syncthreads();
+        if constexpr (DLT > 0) loss_grads_blocked<DLT>(A, L, n0, rows_here, W);
+        else loss_grads_any(A, L, n0, rows_here, W);
+    }
+    if constexpr (DLT > 0) loss_partial_blocked<DLT>(A, L, W);
+    else loss_partial_any(A, W);
+    if constexpr (FUSED) loss_block_partial(loss_acc, corr_acc, A.loss_partial, A.correct_partial);
+}
+
+constexpr unsigned long long kNoBadTarget = ~0ull;
+__global__ __launch_bounds__(256) void targets_check_kernel(const float* __restrict__ t, int64_t n, int32_t bce,
+                                                            unsigned long long* __restrict__ result) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float v = t[i];
+        if (v != v) continue;                            // NaN: a missing entry
+        if (fabsf(v) == INFINITY || (bce && (v < 0.f || v > 1.f))) { atomicMin(result, (unsigned long long)i); break; }   // ascending i: the thread's lowest
+    }
+}
+
+__global__ __launch_bounds__(256) void target_count_kernel(const float* __restrict__ T, const uint8_t* __restrict__ mask, int64_t n_rows,
+                                                           int32_t C, unsigned long long* __restrict__ part) {
+    __shared__ unsigned long long s_n[256];
+    unsigned long long cnt = 0;
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n_rows; r += (int64_t)gridDim.x * 256) {
+        if (mask != nullptr && !mask[r]) continue;
+        const float* tr = T + r * C;
+        for (int c = 0; c < C; ++c) cnt += tr[c] == tr[c] ? 1 : 0;
+    }
+    s_n[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (threadIdx.x < off) s_n[threadIdx.x] += s_n[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = s_n[0];
+}
+
+// NB rows per tile (<= 128), the strides (ldz, ldx odd; ws odd, or D_last in the register-blocked form) and the form: *dlt = D_last when
+// D_last is 4, 8 or 16, C <= 128 and the parts of the block's gradWo fit in the tile region at the end, else 0 (the any-shape form).
+// false: not even one row fits beside Wo.  One function for both launchers: the same form and grid, hence the same loss bits.
+bool loss_head_tile(int32_t C, int32_t DL, int32_t* NB, int32_t* ldz, int32_t* ldx, int32_t* ws, int32_t* dlt) {
+    *ldz = C | 1; *ldx = DL | 1;
+    // GAT_LOSS_BLOCKED=0: the any-shape form at every shape (A/B: tools/loss_cost.py, tests/test_loss_modes.py)
+    static const bool blocked_on = [] { const char* e = choice_env("GAT_LOSS_BLOCKED"); return !(e && e[0] == '0'); }();
+    const bool blocked_shape = blocked_on && (DL == 4 || DL == 8 || DL == 16) && C <= 128;
+    *ws = blocked_shape ? DL : (DL | 1);
+    const int64_t budget = 60 * 1024 / 4 - (int64_t)C * *ws;       // floats
+    const int64_t nb = budget / (*ldz + *ldx);
+    *NB = (int32_t)(nb > 128 ? 128 : nb);
+    *dlt = 0;
+    if (nb < 1) return false;
+    if (blocked_shape && (int64_t)(128 / C) * C * DL <= (int64_t)*NB * (*ldz + *ldx)) *dlt = DL;
+    else *ws = DL | 1;
+    return true;
+}
+
+}  // namespace
+
+// the forward kernel and the two gradient kernels a (mode, form) can launch
+static void loss_head_fns(int32_t mode, int32_t dlt, const void* fn[3]) {
+#define GAT_LOSS_FNS(M, D) { fn[0] = (const void*)loss_head_forward_kernel<M, D>; fn[1] = (const void*)loss_head_grad_kernel<M, false, D>; fn[2] = (const void*)loss_head_grad_kernel<M, true, D>; }
+#define GAT_LOSS_FNS_D(M) switch (dlt) { case 4: GAT_LOSS_FNS(M, 4) break; case 8: GAT_LOSS_FNS(M, 8) break; case 16: GAT_LOSS_FNS(M, 16) break; default: GAT_LOSS_FNS(M, 0) break; }
+    if (mode == GAT_LOSS_BCE) { GAT_LOSS_FNS_D(GAT_LOSS_BCE) } else { GAT_LOSS_FNS_D(GAT_LOSS_MSE) }
+#undef GAT_LOSS_FNS_D
+#undef GAT_LOSS_FNS
+}
+// One grid for the three kernels of a mode (the loss partials of the forward and of the fused gradient kernel must pair up): the
+// tiles, the two partial buffers, and what is resident at once of the kernel that fits the fewest blocks — persistent as the softmax head.
+int loss_head_blocks(int64_t n_rows, int32_t C, int32_t DL, int32_t mode) {
+    int32_t NB, ldz, ldx, ws, dlt;
+    if (!loss_head_tile(C, DL, &NB, &ldz, &ldx, &ws, &dlt)) return -1;
+    const size_t lds = ((size_t)C * ws + (size_t)NB * (ldz + ldx)) * sizeof(float);
+    const void* fn[3];
+    loss_head_fns(mode, dlt, fn);
+    int64_t blocks = std::min<int64_t>((n_rows + NB - 1) / NB, std::min(head_bwd_blocks(n_rows, C, DL), head_blocks(n_rows)));
+    for (int k = 0; k < 3; ++k) blocks = std::min(blocks, resident_blocks(fn[k], lds));
+    return (int)std::max<int64_t>(1, blocks);
+}
+#define GAT_LOSS_LAUNCH(KERNEL) hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(256), lds, s, a, NB, ldz, ldx, ws)
+#define GAT_LOSS_FWD(M)                                                                            \
+    switch (dlt) {                                                                                 \
+        case 4: GAT_LOSS_LAUNCH((loss_head_forward_kernel<M, 4>)); break;                          \
+        case 8: GAT_LOSS_LAUNCH((loss_head_forward_kernel<M, 8>)); break;                          \
+        case 16: GAT_LOSS_LAUNCH((loss_head_forward_kernel<M, 16>)); break;                        \
+        default: GAT_LOSS_LAUNCH((loss_head_forward_kernel<M, 0>)); break;                         \
+    }
+#define GAT_LOSS_GRAD(M, F)                                                                        \
+    switch (dlt) {                                                                                 \
+        case 4: GAT_LOSS_LAUNCH((loss_head_grad_kernel<M, F, 4>)); break;                          \
+        case 8: GAT_LOSS_LAUNCH((loss_head_grad_kernel<M, F, 8>)); break;                          \
+        case 16: GAT_LOSS_LAUNCH((loss_head_grad_kernel<M, F, 16>)); break;                        \
+        default: GAT_LOSS_LAUNCH((loss_head_grad_kernel<M, F, 0>)); break;                         \
+    }
+int launch_loss_head_forward(const LossHeadArgs& a, hipStream_t s) {
+    int32_t NB, ldz, ldx, ws, dlt;
+    if (!loss_head_tile(a.C, a.DL, &NB, &ldz, &ldx, &ws, &dlt)) return fail(GAT_E_UNSUPPORTED, "output head: num_classes*D_last too large for the LDS tile");
+    const int blocks = loss_head_blocks(a.n_rows, a.C, a.DL, a.mode);
+    const size_t lds = ((size_t)a.C * ws + (size_t)NB * (ldz + ldx)) * sizeof(float);
+    if (a.mode == GAT_LOSS_BCE) { GAT_LOSS_FWD(GAT_LOSS_BCE) } else { GAT_LOSS_FWD(GAT_LOSS_MSE) }
+    GAT_HIP(hipGetLastError());
+    if (a.loss_out == nullptr) return 0;
+    hipLaunchKernelGGL(head_finalize_kernel, dim3(1), dim3(64), 0, s, a.loss_partial, a.correct_partial, blocks, a.loss_out, a.correct_out);
+    GAT_HIP(hipGetLastError());
+    return 0;
+}
+int launch_loss_head_grad(const LossHeadArgs& a, bool fused, hipStream_t s) {
+    if ((int64_t)a.C * a.DL > 2048) return fail(GAT_E_UNSUPPORTED, "output head: num_classes*D_last > 2048");
+    int32_t NB, ldz, ldx, ws, dlt;
+    if (!loss_head_tile(a.C, a.DL, &NB, &ldz, &ldx, &ws, &dlt)) return fail(GAT_E_UNSUPPORTED, "output head: num_classes*D_last too large for the LDS tile");
+    const int blocks = loss_head_blocks(a.n_rows, a.C, a.DL, a.mode);
+    const size_t lds = ((size_t)a.C * ws + (size_t)NB * (ldz + ldx)) * sizeof(float);
+    const bool bce = a.mode == GAT_LOSS_BCE;
+    if (bce && fused) { GAT_LOSS_GRAD(GAT_LOSS_BCE, true) }
+    else if (bce) { GAT_LOSS_GRAD(GAT_LOSS_BCE, false) }
+    else if (fused) { GAT_LOSS_GRAD(GAT_LOSS_MSE, true) }
+    else { GAT_LOSS_GRAD(GAT_LOSS_MSE, false) }
+    GAT_HIP(hipGetLastError());
+    if (fused && !reduce_batch_finalize(a.loss_partial, a.correct_partial, blocks, a.loss_out, a.correct_out)) {
+        hipLaunchKernelGGL(head_finalize_kernel, dim3(1), dim3(64), 0, s, a.loss_partial, a.correct_partial, blocks, a.loss_out, a.correct_out);
+        GAT_HIP(hipGetLastError());
+    }
+    return launch_reduce_partials_add(a.partial, blocks, (int64_t)a.C * a.DL, a.gradWo, s);
+}
+#undef GAT_LOSS_GRAD
+#undef GAT_LOSS_FWD
+#undef GAT_LOSS_LAUNCH
+
+int64_t targets_check_host(const float* t, int64_t n, int32_t mode) {
+    for (int64_t i = 0; i < n; ++i) {
+        const float v = t[i];
+        if (v != v) continue;
+        if (std::fabs(v) == INFINITY || (mode == GAT_LOSS_BCE && (v < 0.f || v > 1.f))) return i;
+    }
+    return -1;
+}
+int targets_check_device(const float* d_t, int64_t n, int32_t mode, unsigned long long* d_scratch, int64_t* where, hipStream_t s) {
+    GAT_HIP(hipMemsetAsync(d_scratch, 0xFF, sizeof(unsigned long long), s));
+    if (n > 0) {
+        hipLaunchKernelGGL(targets_check_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 2048)), dim3(256), 0, s, d_t, n,
+                           mode == GAT_LOSS_BCE ? 1 : 0, d_scratch);
+        GAT_HIP(hipGetLastError());
+    }
+    unsigned long long h = kNoBadTarget;
+    GAT_HIP(hipMemcpyAsync(&h, d_scratch, sizeof(h), hipMemcpyDeviceToHost, s));
+    GAT_HIP(hipStreamSynchronize(s));
+    *where = h == kNoBadTarget ? -1 : (int64_t)h;
+    return 0;
+}
+int launch_target_count(const float* T, const uint8_t* mask, int64_t n_rows, int32_t C, unsigned long long* part, hipStream_t s) {
+    hipLaunchKernelGGL(target_count_kernel, dim3(256), dim3(256), 0, s, T, mask, n_rows, C, part);
     GAT_HIP(hipGetLastError());
     return 0;
 }

@@ -490,6 +490,38 @@ int launch_head_backward(const HeadBwdArgs& a, hipStream_t s);
 bool head_step_supported(const HeadBwdArgs& b);
 int launch_head_step(const HeadArgs& f, const HeadBwdArgs& b, hipStream_t s);
 
+// ---- loss modes of the output head (gat_dense_kernels.hip; the contract is in gatv2_abi.h "loss modes of the output head") ----
+// BCE / MSE on a float target matrix.  An entry contributes when its row trains (mask null, or mask[r] != 0) and its target is not NaN;
+// every other entry has loss 0, count 0 and dz 0.  Both kernels form z with the same expression in the same order and run on the
+// same grid, so the loss of the forward kernel and of the fused gradient kernel are bitwise equal.
+struct LossHeadArgs {
+    const float* Wo;          // [C][DL]
+    const float* X;           // [n_rows][DL] the head's input rows (H_L, or the pooled rows of a readout context)
+    const float* T;           // [n_rows][C] targets, NaN = missing
+    const uint8_t* mask;      // [n_rows] or null: every row
+    float* y;                 // forward: [n_rows][C] sigmoid(z) (BCE) / z (MSE)
+    float* gh_out;            // gradient: rows of dz·Wo, gh_stride floats apart (0 = DL)
+    int32_t gh_stride;
+    float* gradWo;            // gradient: [C][DL] added into
+    float* partial;           // gradient: [blocks][C*DL]
+    double* loss_partial;     // [blocks]
+    int32_t* correct_partial; // [blocks]
+    float* loss_out;          // [1] device, or null: the block partials are left for the caller (gat_eval_mask)
+    int32_t* correct_out;
+    int64_t n_rows;
+    int32_t C, DL, mode;      // mode: GAT_LOSS_BCE or GAT_LOSS_MSE
+};
+// blocks either launch uses (<= head_bwd_blocks(n_rows, C, DL) <= head_blocks(n_rows)); < 0: the shape does not fit the LDS tile
+int loss_head_blocks(int64_t n_rows, int32_t C, int32_t DL, int32_t mode);
+int launch_loss_head_forward(const LossHeadArgs& a, hipStream_t s);
+// fused: also the loss / count partials and their finalize (gat_step without keep_taps)
+int launch_loss_head_grad(const LossHeadArgs& a, bool fused, hipStream_t s);
+// lowest flat index of an entry that is +-inf, or (BCE) outside [0, 1]; -1: none.  Device form: one pass, synchronises s.
+int64_t targets_check_host(const float* t, int64_t n, int32_t mode);
+int targets_check_device(const float* d_t, int64_t n, int32_t mode, unsigned long long* d_scratch, int64_t* where, hipStream_t s);
+// part[b] = present entries in the rows of mask (null: all rows) seen by block b, blocks = 256
+int launch_target_count(const float* T, const uint8_t* mask, int64_t n_rows, int32_t C, unsigned long long* part, hipStream_t s);
+
 // ---- graph-level readout (gat_readout.hip; the contract is in gatv2_abi.h "graph-level readout") ----------------------
 // Work decomposition of the pooling: a graph of at most kReadoutSegRows rows is one item (an empty graph too), a longer one is cut into
 // segments of kReadoutSegRows rows whose partial rows the combine kernel adds in ascending order.  256 like the hub rows' kSegEdges.

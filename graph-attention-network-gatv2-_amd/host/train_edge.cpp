@@ -48,6 +48,7 @@
 // --help prints the usage text.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -98,6 +99,7 @@ struct Options {
     int graph_flags = 0;                  // GAT_GRAPH_*: --add-self-loops, --undirected, --coalesce
     std::string readout;                  // --readout mean|sum|max: graph_ptr.txt of the dataset folder, one label per graph
     bool edge_features = false;           // --edge-features: edge_features.txt of the dataset folder enters the attention score
+    std::string loss = "softmax";         // --loss softmax|bce|mse: bce / mse read targets.txt (rows of C floats, nan allowed) in place of labels.txt
 };
 
 // A CSR built before the ranks were forked (main): row_ptr [n + 1] then col_idx [e] in shared memory.
@@ -127,6 +129,10 @@ const char* kUsage =
     "            --readout mean|sum|max   graph classification: graph_ptr.txt of the dataset folder holds G+1 integers (graph g owns nodes\n"
     "                          graph_ptr[g] .. graph_ptr[g+1]-1); labels.txt, --train-mask and --val-mask then hold G lines; the last\n"
     "                          layer's rows are pooled per graph before the output head; loss and accuracy are over graphs (--ranks 1)\n"
+    "            --loss softmax|bce|mse   the output head's loss (default softmax: labels.txt as always).  bce (multi-label) and mse\n"
+    "                          (regression) read targets.txt in place of labels.txt: one row of C floats per node — per graph with\n"
+    "                          --readout — where nan marks a missing entry; C is the row width.  The epoch line prints the loss sum over\n"
+    "                          the present entries of the training rows, and for bce the accuracy over those entries\n"
     "            --ranks P [--transport rccl|host] [--halo 0|1|2]\n";
 
 struct RankEnv {                      // one forked process per GPU
@@ -214,6 +220,7 @@ Options parse_args(int argc, char** argv) {
         else if (a == "--norm-eps" && has_val) o.norm_eps = std::strtof(argv[++i], nullptr);
         else if (a == "--edge-features") o.edge_features = true;
         else if (a == "--readout" && has_val) o.readout = argv[++i];
+        else if (a == "--loss" && has_val) o.loss = argv[++i];
         else if (a == "--transport" && has_val) {
             o.transport = argv[++i];
             if (o.transport != "rccl" && o.transport != "host") die("Invalid transport choice. Use 'rccl' or 'host'\n");
@@ -411,20 +418,35 @@ int run(const Options& o, const RankEnv& env) {
     const std::string cache = path + "gatv2_cache.bin";
     const int readout = o.readout == "mean" ? GAT_READOUT_MEAN : o.readout == "sum" ? GAT_READOUT_SUM : o.readout == "max" ? GAT_READOUT_MAX : GAT_READOUT_NONE;
     const bool edge_list = edge_list_dataset(path);
+    const int loss_mode = o.loss == "bce" ? GAT_LOSS_BCE : o.loss == "mse" ? GAT_LOSS_MSE : GAT_LOSS_SOFTMAX_CE;
+    const bool use_cache = o.cache && !readout && loss_mode == GAT_LOSS_SOFTMAX_CE;       // (the cache holds labels)
+    std::vector<float> targets;                 // --loss bce|mse: [rows][TC] in place of the labels
+    int64_t t_rows = 0; int TC = 0;
+    auto load_supervision = [&]() {
+        if (loss_mode == GAT_LOSS_SOFTMAX_CE) { load_ints(path + "labels.txt", labels); return; }
+        load_features(path + "targets.txt", targets, t_rows, TC);
+        labels.assign((size_t)t_rows, 0);       // (one entry per head row: the length checks below apply to the targets alike)
+    };
+    const char* bad_length = loss_mode == GAT_LOSS_SOFTMAX_CE ? "Invalid labels length\n"
+                                                              : "Invalid targets length: targets.txt must hold one row per node (per graph with --readout)\n";
     std::vector<int32_t> e_src, e_dst;
     if (edge_list) {
         load_features(path + "features.txt", x, N, F0);
         if (!env.graph.row_ptr && !load_edges(path + "edges.txt", e_src, e_dst)) return 1;
-        load_ints(path + "labels.txt", labels);
-        if (!readout && (int64_t)labels.size() != N) { std::cerr << "Invalid labels length\n"; return 1; }
-    } else if (!(o.cache && !readout && load_cache(cache, path, x, N, F0, row_ptr, col_idx, labels))) {
+        load_supervision();
+        if (!readout && (int64_t)labels.size() != N) { std::cerr << bad_length; return 1; }
+    } else if (!(use_cache && load_cache(cache, path, x, N, F0, row_ptr, col_idx, labels))) {
         load_features(path + "features.txt", x, N, F0);
         load_ints(path + "row_ptr.txt", row_ptr);
         if ((int64_t)row_ptr.size() != N + 1) { std::cerr << "Invalid row_ptr length\n"; return 1; }
         load_ints(path + "col_idx.txt", col_idx);
-        load_ints(path + "labels.txt", labels);
-        if (!readout && (int64_t)labels.size() != N) { std::cerr << "Invalid labels length\n"; return 1; }
-        if (o.cache && !readout) save_cache(cache, x, N, F0, row_ptr, col_idx, labels);
+        load_supervision();
+        if (!readout && (int64_t)labels.size() != N) { std::cerr << bad_length; return 1; }
+        if (use_cache) save_cache(cache, x, N, F0, row_ptr, col_idx, labels);
+    }
+    if (loss_mode != GAT_LOSS_SOFTMAX_CE) {
+        if (TC < 1 || (int64_t)targets.size() != t_rows * TC) { std::cerr << "Invalid targets.txt: expected rows of equal length\n"; return 1; }
+        std::cout << "Loss: " << o.loss << " on " << TC << " target column(s)" << std::endl;
     }
     // --readout: the graphs' node ranges; labels.txt then holds one line per graph
     std::vector<int32_t> graph_ptr;
@@ -433,7 +455,7 @@ int run(const Options& o, const RankEnv& env) {
         bool ok = graph_ptr.size() >= 2 && graph_ptr.front() == 0 && (int64_t)graph_ptr.back() == N;
         for (size_t i = 0; ok && i + 1 < graph_ptr.size(); ++i) ok = graph_ptr[i + 1] >= graph_ptr[i];
         if (!ok) { std::cerr << "Invalid graph_ptr.txt: expected G+1 non-decreasing integers from 0 to the node count\n"; return 1; }
-        if (labels.size() + 1 != graph_ptr.size()) { std::cerr << "Invalid labels length\n"; return 1; }
+        if (labels.size() + 1 != graph_ptr.size()) { std::cerr << bad_length; return 1; }
         std::cout << "Readout: " << o.readout << " over " << graph_ptr.size() - 1 << " graphs" << std::endl;
     }
     const int64_t NH = readout ? (int64_t)graph_ptr.size() - 1 : N;        // rows of the output head: graphs with --readout, else nodes
@@ -474,7 +496,7 @@ int run(const Options& o, const RankEnv& env) {
     int max_degree = 0;
     for (int64_t i = 0; i < N; ++i) max_degree = std::max(max_degree, row_ptr[i + 1] - row_ptr[i]);
     std::cout << "Max degree = " << max_degree << std::endl;
-    const int C = *std::max_element(labels.begin(), labels.end()) + 1;          // E:1106-1107
+    const int C = loss_mode != GAT_LOSS_SOFTMAX_CE ? TC : *std::max_element(labels.begin(), labels.end()) + 1;          // E:1106-1107
     std::cout << "Number of classes = " << C << std::endl;
     std::cout << "Graph loaded: " << N << " nodes, " << E << " edges, "
               << "input_feature_vector_dim = " << F0 << std::endl;
@@ -522,6 +544,7 @@ int run(const Options& o, const RankEnv& env) {
     if (o.residual_flags) check(gat_set_residual(ctx, o.residual_flags), "gat_set_residual");
     if (o.norm_flags) check(gat_set_norm(ctx, o.norm_flags, o.norm_eps), "gat_set_norm");
     if (o.edge_features) check(gat_set_edge_dim(ctx, Fe), "gat_set_edge_dim");
+    if (loss_mode != GAT_LOSS_SOFTMAX_CE) check(gat_set_loss(ctx, loss_mode), "gat_set_loss");
     int64_t nW = 0, nA = 0, nWo = 0, nWres = 0, nB = 0, nLnG = 0, nLnB = 0, nWe = 0;
     gat_param_count(ctx, GAT_PARAM_WE, &nWe);                                                 // 0 without --edge-features
     gat_param_count(ctx, GAT_PARAM_W, &nW); gat_param_count(ctx, GAT_PARAM_A, &nA); gat_param_count(ctx, GAT_PARAM_WO, &nWo);
@@ -531,7 +554,8 @@ int run(const Options& o, const RankEnv& env) {
         check(gat_set_graph(ctx, row_ptr.data(), col_idx.data(), N, E, N, 0), "csr_to_coo_kernel");
         check(gat_set_features(ctx, x.data(), N, F0), "gat_set_features");
         if (readout) check(gat_set_readout(ctx, readout, graph_ptr.data(), NH), "gat_set_readout");      // before the labels: they are per graph
-        check(gat_set_labels(ctx, labels.data(), NH), "gat_set_labels");
+        if (loss_mode != GAT_LOSS_SOFTMAX_CE) check(gat_set_targets(ctx, targets.data(), NH, C), "gat_set_targets");
+        else check(gat_set_labels(ctx, labels.data(), NH), "gat_set_labels");
         if (o.edge_features) check(gat_set_edge_features(ctx, ea.data(), E, Fe), "gat_set_edge_features");
     } else {
         // this rank's destination range; sources as rows of the padded [world][max_rows] table; the static
@@ -546,7 +570,8 @@ int run(const Options& o, const RankEnv& env) {
             const std::vector<float> xt = gatshard::table_features(plan, x.data(), F0);
             check(gat_set_source_features(ctx, xt.data(), plan.n_table(), F0), "gat_set_source_features");
         }
-        check(gat_set_labels(ctx, labels.data() + plan.row0(), plan.n_rows()), "gat_set_labels");
+        if (loss_mode != GAT_LOSS_SOFTMAX_CE) check(gat_set_targets(ctx, targets.data() + plan.row0() * C, plan.n_rows(), C), "gat_set_targets");   // the shard's own rows
+        else check(gat_set_labels(ctx, labels.data() + plan.row0(), plan.n_rows()), "gat_set_labels");
         check(gat_set_shard_bounds(ctx, env.world, plan.bounds.data()), "gat_set_shard_bounds");     // dropout masks: unsharded node ids
         if (o.transport == "rccl") {
             if (env.rank == 0) {
@@ -601,6 +626,26 @@ int run(const Options& o, const RankEnv& env) {
         if (env.world != 1) die("Error: --val-mask needs --ranks 1\n");
         load_mask(o.val_mask, val_m, "val mask");
     }
+    // --loss bce|mse: the denominators are entry counts — the present targets of the training rows (all shards), and of the validation rows
+    auto present = [&](const std::vector<uint8_t>& m) {
+        int64_t cnt = 0;
+        for (int64_t r = 0; r < NH; ++r) {
+            if (!m.empty() && !m[(size_t)r]) continue;
+            for (int c = 0; c < C; ++c) cnt += !std::isnan(targets[(size_t)(r * C + c)]);
+        }
+        return cnt;
+    };
+    const int64_t train_entries = loss_mode != GAT_LOSS_SOFTMAX_CE ? present(train_m) : 0;
+    const int64_t val_entries = loss_mode != GAT_LOSS_SOFTMAX_CE && !val_m.empty() ? present(val_m) : 0;
+    if (loss_mode != GAT_LOSS_SOFTMAX_CE) {
+        if (train_entries == 0) die("Error: targets.txt has no present entry in the training rows\n");
+        std::printf("Target entries: %lld present in the training rows\n", (long long)train_entries);
+    }
+    auto print_val = [&](double vl, int32_t vc, int32_t vn) {
+        if (loss_mode == GAT_LOSS_SOFTMAX_CE) std::printf("Val Loss: %f, Val Accuracy: %.2f%%\n", vn ? vl / vn : 0.0, vn ? 100.0f * (static_cast<float>(vc) / vn) : 0.0f);
+        else if (loss_mode == GAT_LOSS_BCE) std::printf("Val Loss: %f, Val Accuracy: %.2f%%\n", val_entries ? vl / val_entries : 0.0, val_entries ? 100.0f * (static_cast<float>(vc) / val_entries) : 0.0f);
+        else std::printf("Val Loss: %f\n", val_entries ? vl / val_entries : 0.0);
+    };
     const bool dropout = o.dropout > 0.f || o.attn_dropout > 0.f || o.drop_edge > 0.f;
     if (dropout) check(gat_set_dropout(ctx, o.dropout, o.attn_dropout, o.seed, 0), "gat_set_dropout");   // also seeds DropEdge
     if (o.drop_edge > 0.f) check(gat_set_dropedge(ctx, o.drop_edge, o.drop_edge_flags), "gat_set_dropedge");
@@ -632,11 +677,13 @@ int run(const Options& o, const RankEnv& env) {
         std::printf("\nEpoch %d\n", epoch);
         float loss_sum = 0.f; int32_t n_correct = 0;
         check(gat_forward(ctx, &loss_sum, &n_correct), "gatv2 forward");
-        std::printf("\nAvg Loss: %f, Accuracy: %.2f%%\n", loss_sum / n_train, 100.0f * (static_cast<float>(n_correct) / n_train));
+        if (loss_mode == GAT_LOSS_SOFTMAX_CE) std::printf("\nAvg Loss: %f, Accuracy: %.2f%%\n", loss_sum / n_train, 100.0f * (static_cast<float>(n_correct) / n_train));
+        else if (loss_mode == GAT_LOSS_BCE) std::printf("\nAvg Loss: %f, Accuracy: %.2f%%\n", loss_sum / train_entries, 100.0f * (static_cast<float>(n_correct) / train_entries));
+        else std::printf("\nAvg Loss: %f\n", loss_sum / train_entries);
         if (!val_m.empty() && !dropout) {
             double vl = 0.0; int32_t vc = 0, vn = 0;
             check(gat_eval_mask(ctx, val_m.data(), NH, &vl, &vc, &vn), "gat_eval_mask");
-            std::printf("Val Loss: %f, Val Accuracy: %.2f%%\n", vn ? vl / vn : 0.0, vn ? 100.0f * (static_cast<float>(vc) / vn) : 0.0f);
+            print_val(vl, vc, vn);
         }
         check(gat_backward(ctx), "gatv2 backward");
         if (o.clip) check(gat_clip(ctx, 5.0f), "clip_grad_norm");                   // E:1563
@@ -649,7 +696,7 @@ int run(const Options& o, const RankEnv& env) {
             check(gat_forward(ctx, nullptr, nullptr), "gatv2 forward");
             check(gat_eval_mask(ctx, val_m.data(), NH, &vl, &vc, &vn), "gat_eval_mask");
             check(gat_set_training(ctx, 1), "gat_set_training");
-            std::printf("Val Loss: %f, Val Accuracy: %.2f%%\n", vn ? vl / vn : 0.0, vn ? 100.0f * (static_cast<float>(vc) / vn) : 0.0f);
+            print_val(vl, vc, vn);
         }
         check(gat_sync(ctx), "gat_sync");
         const std::chrono::duration<double, std::milli> elapsed = std::chrono::high_resolution_clock::now() - start;
@@ -689,7 +736,7 @@ int main(int argc, char** argv) {
     }
     // --help, --edge-features with what it cannot be combined with, and graph flags without a graph to apply them to, end here: before
     // anything touches the GPU
-    bool graph_flag = false, edge_feat_flag = false, readout_flag = false;
+    bool graph_flag = false, edge_feat_flag = false, readout_flag = false, targets_flag = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--help") { std::cout << kUsage; return 0; }
@@ -700,6 +747,11 @@ int main(int argc, char** argv) {
         }
         if (a == "--add-self-loops" || a == "--undirected" || a == "--coalesce") graph_flag = true;
         if (a == "--edge-features") edge_feat_flag = true;
+        if (a == "--loss") {
+            const std::string v = i + 1 < argc ? argv[i + 1] : "";
+            if (v != "softmax" && v != "bce" && v != "mse") die("Error: --loss must be softmax, bce or mse\n");
+            targets_flag = v != "softmax";
+        }
     }
     if (edge_feat_flag && graph_flag)
         die("Error: --edge-features cannot be combined with --add-self-loops / --undirected / --coalesce: they rebuild the graph, and the rows of "
@@ -709,7 +761,7 @@ int main(int argc, char** argv) {
             "gat_set_edge_features on every shard's own CSR)\n");
     if (readout_flag && multi)
         die("Error: --readout needs --ranks 1: a graph of the batch may straddle two destination-range shards\n");
-    if (graph_flag || readout_flag) {
+    if (graph_flag || readout_flag || targets_flag) {
         std::string root = "./data", name = "pubmed";
         bool root_given = false;
         for (int i = 1; i + 1 < argc; ++i) {
@@ -722,6 +774,8 @@ int main(int argc, char** argv) {
         const std::string dir = root + name + "/";
         if (readout_flag && !file_exists(dir + "graph_ptr.txt"))
             die("Error: --readout needs graph_ptr.txt (G+1 integers: the first node of every graph, then the node count) in " + dir + "\n");
+        if (targets_flag && !file_exists(dir + "targets.txt"))
+            die("Error: --loss bce / mse needs targets.txt (one row of C floats per node, per graph with --readout; nan = missing) in " + dir + "\n");
         if (graph_flag && !file_exists(dir + "edges.txt") && !(file_exists(dir + "row_ptr.txt") && file_exists(dir + "col_idx.txt")))
             die("Error: --add-self-loops / --undirected / --coalesce need a graph: no edges.txt and no row_ptr.txt + col_idx.txt in " + dir + "\n");
     }
@@ -742,7 +796,12 @@ int main(int argc, char** argv) {
     const std::string dir = o.data_root + o.dataset + "/";
     if (edge_list_dataset(dir) || o.graph_flags) {
         std::vector<int32_t> src, dst, labels;
-        load_ints(dir + "labels.txt", labels);
+        if (o.loss == "softmax") load_ints(dir + "labels.txt", labels);
+        else {                                  // the node count from targets.txt: one row per node
+            std::vector<float> t; int64_t rows = 0; int tc = 0;
+            load_features(dir + "targets.txt", t, rows, tc);
+            labels.assign((size_t)rows, 0);
+        }
         const int64_t N = (int64_t)labels.size();
         if (N <= 0) die("Invalid labels length\n");
         if (edge_list_dataset(dir)) {

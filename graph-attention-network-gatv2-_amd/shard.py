@@ -104,6 +104,15 @@ def local_csr(plan: ShardPlan, row_ptr: np.ndarray, col_idx: np.ndarray):
     return rp, ci
 
 
+def local_targets(plan: ShardPlan, targets: np.ndarray) -> np.ndarray:
+    """Global float targets [N][C] of the BCE / MSE heads (gatv2_abi.h "loss modes of the output head") -> this shard's own rows
+    [row0, row0 + n_rows), a copy: sliced by destination range exactly as labels are.  The head is row-local: nothing is exchanged."""
+    t = np.asarray(targets)
+    if t.ndim != 2 or t.shape[0] != int(plan.bounds[-1]):
+        raise ValueError(f"targets must be [N][C] with N = {int(plan.bounds[-1])}, got shape {t.shape}")
+    return np.ascontiguousarray(t[plan.row0:plan.row0 + plan.n_rows], np.float32)
+
+
 def local_edge_features(plan: ShardPlan, row_ptr: np.ndarray, ea: np.ndarray) -> np.ndarray:
     """Global per-edge attributes [E][Fe] (rows in the order of the global CSR) -> the rows of this shard's own CSR, in its order:
     local_csr keeps the edges of rows [row0, row0 + n_rows) as one contiguous run, so the slice is that run (a copy).  Edge

@@ -190,6 +190,8 @@ def write_text_dataset(ds: dict, root: str, name: Optional[str] = None) -> str:
     np.savetxt(os.path.join(d, "row_ptr.txt"), ds["row_ptr"], fmt="%d")
     np.savetxt(os.path.join(d, "col_idx.txt"), ds["col_idx"], fmt="%d")
     np.savetxt(os.path.join(d, "labels.txt"), ds["labels"], fmt="%d")
+    if ds.get("targets") is not None:           # train_edge --loss bce|mse: rows of C floats, nan = missing
+        np.savetxt(os.path.join(d, "targets.txt"), np.asarray(ds["targets"]), fmt="%.9g")
     if ds.get("edge_features") is not None:
         np.savetxt(os.path.join(d, "edge_features.txt"), np.asarray(ds["edge_features"]).reshape(len(ds["col_idx"]), -1), fmt="%.9g")
     return d
@@ -202,6 +204,22 @@ def edge_features(seed: int, n_edges: int, fe: int) -> np.ndarray:
         raise ValueError(f"edge_features: bad sizes (n_edges={n_edges}, fe={fe})")
     rng = np.random.default_rng([int(seed) & (2 ** 63 - 1), 0xEA])
     return rng.standard_normal((int(n_edges), int(fe))).astype(np.float32)
+
+
+def targets(kind: str, n_rows: int, n_cols: int, seed: int = GRAPH_SEED + 3, missing: float = 0.0) -> np.ndarray:
+    """Float targets [n_rows][n_cols] for the BCE / MSE heads (gatv2_abi.h "loss modes of the output head"), hash-drawn per entry:
+    kind "multilabel": 0 / 1 with probability 1/2 each; "regression": U[-1,1).  A `missing` fraction of the entries (a second hash
+    stream, each entry independently) is NaN.  A function of the arguments alone."""
+    if kind not in ("multilabel", "regression"):
+        raise ValueError(f"targets: kind must be 'multilabel' or 'regression', got {kind!r}")
+    if n_rows < 0 or n_cols < 1 or not 0.0 <= missing <= 1.0:
+        raise ValueError(f"targets: bad arguments (n_rows={n_rows}, n_cols={n_cols}, missing={missing})")
+    idx = np.arange(int(n_rows) * int(n_cols), dtype=np.uint64)
+    u = _uniform01(seed, 13, idx)
+    t = (u < 0.5).astype(np.float32) if kind == "multilabel" else (u * 2.0 - 1.0).astype(np.float32)
+    if missing > 0.0:
+        t[_uniform01(seed, 17, idx) < missing] = np.nan
+    return t.reshape(int(n_rows), int(n_cols))
 
 
 def graph_batch(n_graphs: int, nodes_lo: int, nodes_hi: int, avg_degree: float, seed: int = GRAPH_SEED, f: int = 32, c: int = 4):

@@ -598,6 +598,68 @@ int gat_op_readout_forward(const float* d_x, int64_t x_stride, const int32_t* d_
 int gat_op_readout_backward(const float* d_gpooled, const int32_t* d_graph_ptr, int64_t n_graphs, int64_t n_rows, int32_t width,
                             int32_t mode, const int32_t* d_argmax, float* d_gh, int64_t gh_stride, void* stream);
 
+/* ---- loss modes of the output head (beyond the reference, whose head is one softmax + cross-entropy on an int32 label per row) ----------
+ * Multi-label classification (PPI, ogbn-proteins), regression (ZINC, QM9) and multi-task targets with missing entries (ogbg-molpcba)
+ * need a FLOAT target matrix T [rows][C], a per-entry loss, and entries that may be absent.  C = num_classes is the number of output
+ * columns; Wo keeps its shape [C][D_last]; a row r is a node — a graph on a readout context, exactly where labels were per graph.
+ *     z[r][c] = sum_j Wo[c][j] X[r][j]      fp32, ascending j, as in the softmax head (X = the head's input rows)
+ *     present(r,c) = !isnan(T[r][c])  (NaN marks a missing entry, the OGB convention);  trains(r) = no training mask, or mask[r]
+ *   Only entries that are present and in a training row contribute; every other entry has loss 0, count 0 and dz = 0.
+ *     GAT_LOSS_BCE  T in [0,1] (soft labels allowed) or NaN;  e = exp(-|z|);  y = z >= 0 ? 1/(1+e) : e/(1+e)  (= sigmoid(z), stable for
+ *                   both signs);  l = max(z,0) - t z + log1p(e);  dz = y - t;  the prediction is z > 0 and an entry is correct when
+ *                   (z > 0) == (t > 0.5);  GAT_TAP_Y returns y
+ *     GAT_LOSS_MSE  T finite or NaN;  y = z;  l = (z - t)^2;  dz = 2 (z - t)  (loss and gradient of torch.nn.MSELoss(reduction="sum"));
+ *                   n_correct is 0;  GAT_TAP_Y returns the predictions
+ *   loss_sum = sum of l over the contributing entries (fp32 terms, a double accumulator per thread, block and grid reductions in a fixed
+ *   order), n_correct = the correct contributing entries, gH = dz Wo, gradWo += dz^T X.  The loss is a SUM, like the reference's: callers
+ *   divide by gat_target_count.  Everything below the head is unchanged: the new head writes the gH the softmax head writes, and the
+ *   last layer's edge backward, the residual / norm kernels and the un-pool consume it as they do now.  No new parameter group (no bias
+ *   on the output head: a constant offset is reachable through the last layer's b / beta).
+ * gat_set_loss is allowed until the first gat_set_labels* / gat_set_targets* call (later: GAT_E_STATE); a mode outside 0..2:
+ *   GAT_E_INVALID.  Mode 0 (GAT_LOSS_SOFTMAX_CE) is the default and leaves the context exactly as it is: same buffers, same kernels,
+ *   same launch counts, bitwise the same results.  With mode != 0, gat_set_labels* returns GAT_E_STATE (its text names gat_set_targets);
+ *   with mode 0, gat_set_targets* returns GAT_E_STATE.
+ * gat_set_targets[_device] is called where labels are set today: after the graph (before: GAT_E_STATE), and after gat_set_readout on a
+ *   readout context.  n_cols must be C and n_rows the head's row count, else GAT_E_INVALID; n_rows * C >= 2^31: GAT_E_UNSUPPORTED
+ *   (n_correct is int32).  A BCE entry outside [0,1], or a +-inf entry in either mode: GAT_E_INVALID with a text naming the lowest
+ *   offending flat index; the device form finds it in one pass on the device before anything reads the array (as
+ *   gat_graph_check_device does).  The array is copied.  A later call with the same shape replaces the values IN THE SAME DEVICE
+ *   BUFFER: a captured gat_step_graph replay then reads the new targets without re-capture.  A step or phase call in mode != 0 without
+ *   targets returns GAT_E_STATE and says so.
+ * gat_set_train_mask is unchanged at the boundary; the new kernels read the mask byte of a row themselves (NULL = all rows) and
+ *   changing the mask re-arms a captured step, as it does now.  gat_eval_mask keeps its signature: in the new modes it returns the sum
+ *   of l and the correct count over the present entries of the mask's rows (it runs the head's forward kernel on the last forward's
+ *   input rows with that mask); n_nodes still counts rows, gat_target_count gives the entry denominator.
+ * Where it runs.  Two kernels in place of the softmax head's, both persistent over 128-row tiles (fewer rows per tile when C is large):
+ *   Wo, the tile's targets — one contiguous block, loaded coalesced, NaN test and mask byte applied there — and the tile's input rows in
+ *   LDS with odd row strides; the tile's entries are dealt to the 256 threads by flat index, so no thread owns a row and every C >= 1 and
+ *   D_last >= 1 takes the same path.  D_last in {4, 8, 16} with C <= 128 runs the register-blocked form of the same tile (a thread keeps
+ *   its input row in registers and walks half of the columns; then two waves own a row each for gH while the other two own (column, row
+ *   part) for gradWo); every z is the same fmaf chain in both forms, and a shape always takes the same form in both kernels.
+ *   exp / log / reciprocal are the hardware's (1 ulp; log1p(e) below 2^-10 by its series): absolute error of a loss term below 1e-6.
+ *   The forward kernel writes y and the loss / count partials (gat_head_forward, gat_forward, gat_step with
+ *   keep_taps); the gradient kernel recomputes z with the same expression in the same order, overwrites the targets in LDS with dz, and
+ *   writes gH rows and per-block gradWo partials (gat_head_backward; gat_step without keep_taps, where it forms the loss / count partials
+ *   too and y never reaches HBM).  Both run on the same grid: gat_step, gat_forward + gat_backward, the phase API and a graph replay
+ *   give bitwise the same loss and gradients.  No float atomics.  Timed under GAT_K_HEAD_FWD / GAT_K_HEAD_BWD.
+ * Shape limits: the gradient kernel needs C * D_last <= 2048, the forward kernel that one row of the tile fits in LDS beside Wo; beyond,
+ *   the call that would launch the kernel returns GAT_E_UNSUPPORTED with a text naming the output head.
+ * Works with every (H, D) family incl. both generic ones, bf16 storage (the head stays fp32), keep_taps, eval mode, all three
+ *   regularisers, residual, bias, norm, edge features and readout (targets and mask per graph), the phase API, gat_step, gat_step_graph,
+ *   and destination-range shards on any transport (the head is row-local, targets are the shard's own rows, nothing new is exchanged;
+ *   loss and count ride in the existing three-float tail, whose 12-bit split of the count stays exact because n_rows * C < 2^31).
+ * Refused with GAT_E_UNSUPPORTED (by gat_set_loss with mode != 0): flat_lrelu_index = 1 (the new head writes gH only, never a g); the
+ *   experiment library with GAT_DBG set.  GAT_FUSE_LAST=1 is not used by such a context: it runs the separate passes.
+ * gat_algorithmic_bytes (context form): unchanged in mode 0.  In the new modes GAT_K_HEAD_FWD and GAT_K_HEAD_BWD each price
+ *   4 * rows * C bytes of targets in place of 4 * rows of labels: + 4 * rows * (C - 1) per class, rows = n_graphs with readout on. */
+enum { GAT_LOSS_SOFTMAX_CE = 0, GAT_LOSS_BCE = 1, GAT_LOSS_MSE = 2 };
+int gat_set_loss(gat_ctx* ctx, int32_t mode);
+int gat_set_targets(gat_ctx* ctx, const float* t, int64_t n_rows, int32_t n_cols);            /* host  [n_rows][n_cols] */
+int gat_set_targets_device(gat_ctx* ctx, const float* d_t, int64_t n_rows, int32_t n_cols);   /* device, checked on the device */
+int gat_loss_info(gat_ctx* ctx, int32_t* mode, int32_t* n_cols);                              /* (0, num_classes) by default; pointers may be NULL */
+int gat_target_count(gat_ctx* ctx, const uint8_t* mask, int64_t n_rows, int64_t* n_entries);
+        /* present entries in the rows of `mask` (host, [n_rows]); mask NULL = the current training set */
+
 /* ---- op-level entry points, whole layers: caller-provided DEVICE pointers in the reference layouts
  *      (unit parity).  `stream` may be NULL (default stream).  One entry point per reference KERNEL: below. ---- */
 /* a1  csr_to_coo_kernel E:67-84 */

@@ -1,0 +1,179 @@
+"""Host-side checks of the BCE / MSE output heads (include/gatv2_abi.h "loss modes of the output head"): tests/loss_ref.py against
+torch's own losses, values and autograd gradients, on masked and NaN-holed inputs; the ABI boundary (symbols, constants, version,
+parameter groups); synth.targets; train_edge's dataset check; and the conditions tests/test_loss_modes.py relies on, for every whole-step
+and readout case: a parameter seed among the first 40 clear of the LeakyReLU kinks, few undecided BCE entries, gradients with a scale."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import feature_cases as FC
+import loss_ref as LR
+import readout_ref as RR
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "graph-attention-network-gatv2-_amd", "train_edge")
+
+
+def holed(rng, rows, C, mode):
+    T = (rng.random((rows, C)) if mode == LR.BCE else rng.standard_normal((rows, C))).astype(np.float32)
+    T[rng.random((rows, C)) < 0.25] = np.nan
+    T[3, :] = np.nan
+    T[:, 1] = np.nan
+    return T
+
+
+@pytest.mark.parametrize("mode", LR.MODES)
+@pytest.mark.parametrize("masked", [False, True])
+def test_losses_equal_torch(mode, masked):
+    """loss_ref.losses is binary_cross_entropy_with_logits / mse_loss with reduction="sum" over the contributing entries: the value and
+    the autograd gradient (exactly 0 on every other entry); loss_ref.head_ref gives the same numbers in plain numpy."""
+    import torch
+    import torch.nn.functional as F
+    rng = np.random.default_rng(4)
+    rows, C, DL = 37, 6, 5
+    T = holed(rng, rows, C, mode)
+    mask = LR.row_mask(rows) if masked else None
+    X = rng.standard_normal((rows, DL)) * 3
+    Wo = rng.standard_normal((C, DL)).astype(np.float32)
+    z = (torch.from_numpy(X) @ torch.from_numpy(Wo.astype(np.float64)).t()).requires_grad_(True)
+    loss, y = LR.losses(z, T, mask, mode)
+    loss.backward()
+    on = LR.contributes(T, mask)
+    z2 = z.detach().clone().requires_grad_(True)
+    sel = torch.from_numpy(on)
+    t = torch.from_numpy(np.nan_to_num(T.astype(np.float64)))
+    want = (F.binary_cross_entropy_with_logits(z2[sel], t[sel], reduction="sum") if mode == LR.BCE
+            else F.mse_loss(z2[sel], t[sel], reduction="sum"))
+    want.backward()
+    assert abs(loss.item() - want.item()) <= 1e-12 * max(1.0, abs(want.item()))
+    assert np.allclose(z.grad.numpy(), z2.grad.numpy(), rtol=1e-12, atol=1e-14)
+    assert not z.grad.numpy()[~on].any() and np.isfinite(z.grad.numpy()).all()
+    ref = LR.head_ref(X, Wo, T, mask, mode)
+    assert abs(ref.l.sum() - want.item()) <= 1e-12 * max(1.0, abs(want.item()))
+    assert np.allclose(ref.dz, z2.grad.numpy(), rtol=1e-12, atol=1e-14)
+    assert np.allclose(ref.y, y.detach().numpy(), rtol=1e-12, atol=1e-300)
+    assert np.allclose(ref.gH, ref.dz @ Wo.astype(np.float64)) and np.allclose(ref.gradWo, ref.dz.T @ X)
+    assert not ref.l[~on].any() and not ref.dz[~on].any()
+    if mode == LR.BCE:
+        assert np.array_equal(ref.correct, on & ((ref.z > 0) == (np.nan_to_num(T) > 0.5)))
+        sure, slack = LR.count_bounds(ref)
+        assert sure + slack >= int(ref.correct.sum()) >= sure
+    else:
+        assert not ref.correct.any() and not ref.undecided.any()
+
+
+def test_bce_is_stable_for_both_signs():
+    z = np.array([[-800.0, -90.0, 0.0, 90.0, 800.0]])
+    ref = LR.head_ref(z, np.eye(5, dtype=np.float32), np.array([[1.0, 0.0, 0.5, 1.0, 0.0]], np.float32), None, LR.BCE)
+    assert np.isfinite(ref.l).all() and np.isfinite(ref.y).all() and np.isfinite(ref.dz).all()
+    assert ref.l[0, 0] == 800.0 and ref.l[0, 4] == 800.0 and ref.y[0, 0] == 0.0 and ref.y[0, 4] == 1.0
+
+
+def test_symbols_constants_and_pins(pkg):
+    A = pkg.abi
+    lib = A.load_library()
+    names = A.declared_symbols()
+    for n in ("gat_set_loss", "gat_set_targets", "gat_set_targets_device", "gat_loss_info", "gat_target_count"):
+        assert n in names and hasattr(lib, n), n
+    hdr = open(A.HEADER_PATH).read()
+    m = re.search(r"enum \{ GAT_LOSS_SOFTMAX_CE = (\d+), GAT_LOSS_BCE = (\d+), GAT_LOSS_MSE = (\d+) \};", hdr)
+    assert m and tuple(map(int, m.groups())) == (A.LOSS_SOFTMAX_CE, A.LOSS_BCE, A.LOSS_MSE) == (0, 1, 2)
+    assert A.LOSS_MODES == {"softmax": 0, "bce": 1, "mse": 2}
+    assert A.loss_mode("bce") == 1 and A.loss_mode(2) == 2
+    with pytest.raises(ValueError):
+        A.loss_mode("huber")
+    assert lib.gat_abi_version() == 6 and "#define GAT_ABI_VERSION 6" in hdr
+    assert A.PARAM_GROUPS == tuple(range(8))
+
+
+def test_synth_targets(pkg):
+    S = pkg.synth
+    a = S.targets("multilabel", 500, 7, seed=3, missing=0.2)
+    assert a.dtype == np.float32 and a.shape == (500, 7)
+    assert np.array_equal(a, S.targets("multilabel", 500, 7, seed=3, missing=0.2), equal_nan=True)      # deterministic
+    assert not np.array_equal(a, S.targets("multilabel", 500, 7, seed=4, missing=0.2), equal_nan=True)
+    assert set(np.unique(a[~np.isnan(a)])) == {0.0, 1.0}
+    assert abs(np.isnan(a).mean() - 0.2) < 0.03 and abs(np.nanmean(a) - 0.5) < 0.05
+    full = S.targets("multilabel", 500, 7, seed=3)
+    assert not np.isnan(full).any() and np.array_equal(full[~np.isnan(a)], a[~np.isnan(a)])             # the holes are a second stream
+    r = S.targets("regression", 500, 7, seed=3, missing=0.5)
+    v = r[~np.isnan(r)]
+    assert v.min() >= -1.0 and v.max() < 1.0 and abs(v.mean()) < 0.05 and abs(np.isnan(r).mean() - 0.5) < 0.03
+    assert np.isnan(S.targets("regression", 4, 2, missing=1.0)).all()
+    with pytest.raises(ValueError):
+        S.targets("ranking", 4, 2)
+
+
+def test_train_edge_needs_targets_txt(tmp_path):
+    assert os.path.exists(BIN), "run __graft_entry__.build()"
+    d = tmp_path / "tiny"
+    d.mkdir()
+    for f in ("features.txt", "row_ptr.txt", "col_idx.txt", "labels.txt"):
+        (d / f).write_text("0\n")
+    env = dict(os.environ)
+    env.pop("DATA_ROOT", None)
+    base = [BIN, "--heads", "8,8", "--outdims", "8,8", "--dataset", "tiny", "--data-root", str(tmp_path)]
+    r = subprocess.run(base + ["--loss", "bce"], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 1 and "--loss bce / mse needs targets.txt" in r.stderr, r.stderr
+    (d / "targets.txt").write_text("0 1\n1 nan\n")                     # two rows for one node: the message names the targets
+    (d / "row_ptr.txt").write_text("0 0\n")
+    r = subprocess.run(base + ["--loss", "bce"], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 1 and "Invalid targets length" in r.stderr and "labels" not in r.stderr, r.stderr
+    r = subprocess.run(base + ["--loss", "huber"], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 1 and "--loss must be softmax, bce or mse" in r.stderr, r.stderr
+
+
+# -- the conditions the GPU cases rely on
+def check_conditions(ci):
+    assert 0 <= ci["seed"] < 40                                          # clear of the kinks (FC.pick_case / RR.pick found it)
+    ref = LR.model_of(ci)
+    assert RR.grads_min(ref) > RR.GRAD_MIN, RR.grads_min(ref)
+    if ci["mode"] == LR.BCE:
+        X = ref["X"].detach().numpy().astype(np.float32)                 # the rows as the head reads them
+        h = LR.head_ref(X, ci["P"][2], ci["T"], ci["mask"], LR.BCE)
+        n_on = int(h.on.sum())
+        assert n_on > 0
+        assert int(h.undecided.sum()) <= max(2, 0.001 * n_on), (int(h.undecided.sum()), n_on)
+
+
+STEP_CASES = LR.step_cases(FC)
+
+
+@pytest.mark.parametrize("case", STEP_CASES, ids=[LR.case_id(c) for c in STEP_CASES])
+def test_step_cases_meet_their_conditions(orc, case):
+    ci = LR.step_inputs(case)
+    if case[1] == "res_norm_reg":
+        assert FC.CLEAR_V(FC.run_model(ci["cfg"], ci["g"], ci["P"], **ci["inp"], **ci["model_kw"]))
+    else:
+        assert FC.CLEAR_HPRE(FC.run_model(ci["cfg"], ci["g"], ci["P"], **ci["model_kw"]))
+    check_conditions(ci)
+
+
+@pytest.mark.parametrize("case", LR.READOUT_CASES, ids=[LR.case_id(c) for c in LR.READOUT_CASES])
+def test_readout_cases_meet_their_conditions(orc, case):
+    check_conditions(LR.readout_inputs(case))
+
+
+def test_shard_case_has_missing_entries(pkg, orc):
+    g, P, T = LR.shard_setup(pkg, orc)
+    assert T.shape == (g["n"], g["c"]) and 0.1 < np.isnan(T).mean() < 0.3
+    S = pkg.shard
+    parts = []
+    for rank in range(2):                                                # sliced by destination range, as the labels are
+        plan = S.make_plan(g["row_ptr"], 2, rank)
+        parts.append(S.local_targets(plan, T))
+        assert parts[-1].shape == (plan.n_rows, g["c"]) and np.isnan(parts[-1]).any()
+    assert np.array_equal(np.concatenate(parts), T, equal_nan=True)
+    with pytest.raises(ValueError):
+        S.local_targets(plan, T[:-1])
+
+
+def test_write_text_dataset_writes_targets(pkg, tmp_path):
+    ds = pkg.synth.make_dataset("cora", scale=0.02)
+    ds["targets"] = pkg.synth.targets("regression", ds["n"], 3, seed=1, missing=0.3)
+    d = pkg.synth.write_text_dataset(ds, str(tmp_path), "tiny")
+    back = np.loadtxt(os.path.join(d, "targets.txt"), dtype=np.float32, ndmin=2)
+    assert np.array_equal(back, ds["targets"], equal_nan=True)
