@@ -489,7 +489,7 @@ static int ensure_buffers(gat_ctx* c) {
     const char* force = choice_env("GAT_BWD_ATOMICS");
     if ((msg_hd > 0 || stash_words > 0) && E > 0 && !(force && force[0] == '1')) {
         float* m = nullptr;
-        int32_t *src_ptr = nullptr, *cdst = nullptr, *csrc = nullptr;      // the SourceIndex's arrays while they are written
+        int32_t *src_ptr = nullptr, *cdst = nullptr, *cedge = nullptr, *csrc = nullptr;      // the SourceIndex's arrays while they are written
         // E + 1 rows / records: the last one takes the stores of the group-per-row kernels' padded lanes; kPullPad records of
         // padding behind the records and the destination list: the pull pass reads whole 16-slot chunks without clamping
         if (hipMalloc((void**)&m, std::max<size_t>((size_t)(E + kPullPad) * msg_hd * (size_t)st_bytes(c), (size_t)(E + kPullPad) * stash_words * sizeof(uint32_t))) == hipSuccess) {
@@ -502,6 +502,8 @@ static int ensure_buffers(gat_ctx* c) {
                 if (c->layers[L - 1].stash && c->gH != nullptr && c->gh_stride == 16) c->hbits = reinterpret_cast<uint8_t*>(c->gH) + 32;
                 GAT_TRY(dalloc(c, &cdst, E + kPullPad));
                 GAT_HIP(hipMemsetAsync(cdst + E, 0, (size_t)kPullPad * sizeof(int32_t), c->stream));      // padding: row 0 (any valid row)
+                // the CSR edge of every slot (4 B per slot): fp32 records may lie in edge order (records_take_edge_order)
+                if (!bf16(c)) GAT_TRY(dalloc(c, &cedge, E + kPullPad));
                 GAT_HIP(hipMemsetAsync(reinterpret_cast<uint32_t*>(m) + (size_t)E * stash_words, 0, (size_t)kPullPad * stash_words * sizeof(uint32_t), c->stream));
             }
             GAT_TRY(dalloc(c, &c->csc_pos, E));
@@ -512,9 +514,9 @@ static int ensure_buffers(gat_ctx* c) {
             const int32_t run = run_env >= 0 ? (run_env / 32) * 32 : 64;
             if (run > 0) GAT_TRY(dalloc(c, &csrc, E + kPullPad));
             GAT_TRY(build_csc(c->col_idx, E, T, c->csc_pos, src_ptr, csrc, c->stream));
-            if (cdst) GAT_TRY(build_csc_dst(c->row_ptr, c->csc_pos, cdst, N, E, c->stream));
+            if (cdst) GAT_TRY(build_csc_dst(c->row_ptr, c->csc_pos, cdst, N, E, c->stream, cedge));
             SourceIndex& ix = c->src_index;
-            ix.src_ptr = src_ptr; ix.cdst = cdst; ix.n_table = T; ix.n_slots = E; ix.slot_capacity = E + kPullPad;
+            ix.src_ptr = src_ptr; ix.cdst = cdst; ix.cedge = cedge; ix.n_table = T; ix.n_slots = E; ix.slot_capacity = E + kPullPad;
             HeavyList hl;
             GAT_TRY(build_heavy_list(src_ptr, T, E, &hl, c->stream, run));
             // device copy of one of the host lists (int4 entries as 4 int32), at least one entry allocated
@@ -1286,7 +1288,9 @@ int gat_head_backward(gat_ctx* c) {
 }
 
 // Arguments of layer l's edge backward (shared by gat_layer_backward_edges and the fused last layer of gat_step).
-struct BwdPlan { EdgeBwdArgs a; bool store, stash, last_g; DropArgs drop; };
+// edge_order: the layer's records lie in CSR edge order (records_take_edge_order), for the backward (a.edge_order) and the pull alike
+struct BwdPlan { EdgeBwdArgs a; bool store, stash, last_g, edge_order; DropArgs drop; };
+static bool fused_last(gat_ctx* c);
 static int plan_backward_edges(gat_ctx* c, int32_t l, BwdPlan* P) {
     Layer& y = c->layers[l];
     const bool store = c->msg != nullptr && edge_fast_path(y.H, y.D, c->n_table);
@@ -1313,6 +1317,11 @@ static int plan_backward_edges(gat_ctx* c, int32_t l, BwdPlan* P) {
     const bool last_g = stash && a.gh != nullptr && c->hbits != nullptr && !bf16(c) && !edge_feat_on(c) && (pull_last >= 0 ? pull_last == 1 : big_rows) &&
                         c->n_rows < ((int64_t)1 << 26);             // the pull pass addresses the 64-byte node records with 32-bit offsets
     a.hbits = last_g ? c->hbits : nullptr;
+    // the layout of the records: one answer for this layer's backward and pull.  The fused last layer writes its records itself, by slot
+    const bool fused = l == c->cfg.num_layers - 1 && fused_last(c);
+    const bool edge_order = stash && !y.ge && c->dbg == 0 && !fused &&
+                            records_take_edge_order(c->src_index, y.H, y.D, !bf16(c), last_g, !last_g || c->gh_stride == 16);
+    a.edge_order = edge_order ? 1 : 0;
     a.items = c->items; a.n_items = c->work.n_items; a.slot_info = c->slot_info; a.n_slots = c->work.n_slots; a.n_split = c->work.n_split;
     a.part_acc = c->part_acc;
     a.dbg = c->dbg;
@@ -1320,7 +1329,7 @@ static int plan_backward_edges(gat_ctx* c, int32_t l, BwdPlan* P) {
     a.slope = c->cfg.negative_slope;
     P->drop = drop_args(c, l);
     a.ga_blocks = edge_backward_blocks(a, &P->drop, y.PE != nullptr);
-    P->a = a; P->store = store; P->stash = stash; P->last_g = last_g;
+    P->a = a; P->store = store; P->stash = stash; P->last_g = last_g; P->edge_order = edge_order;
     return 0;
 }
 // The source-major pass of layer l (records -> gPL, or message rows -> gPL)
@@ -1330,7 +1339,7 @@ static int sum_backward_edges(gat_ctx* c, int32_t l, const BwdPlan& P) {
     Scope t(c, GAT_K_GPL_SUM);
     if (P.stash) {
         const PullArgs p{c->stash, c->gfull, bf16(c), P.last_g ? c->gH : nullptr, P.last_g ? c->hbits : nullptr, c->gh_stride, 64,
-                         a_of(c, l), c->cfg.negative_slope, gPL_of(c, l), y.H, y.D};
+                         a_of(c, l), c->cfg.negative_slope, gPL_of(c, l), y.H, y.D, P.edge_order};
         return launch_gpl_pull(c->src_index, p, c->stream);
     }
     return launch_gpl_sum(c->src_index, c->msg, bf16(c), gPL_of(c, l), y.HD, c->stream);

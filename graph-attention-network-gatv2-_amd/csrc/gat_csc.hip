@@ -386,9 +386,10 @@ __device__ __forceinline__ void stream_store(T* p, const T& v) {
 // LASTD > 0 (last layer, D = LASTD): g[dst][c] = gh[dst][c % D] * LReLU'(h_pre[dst][c]) / H  (E:598-603) is rebuilt from
 // gh [n_rows][D] and the per-lane decision byte hbits [n_rows][HD/N] — 48 B gathered per edge from two small tables
 // (98 MB + 39 MB at the Products shape: cache-resident) instead of a 256-B row of g.
-template <int HD, int N, bool BF, int LASTD>
+// EO: the records lie in CSR edge order — slot i's record is cedge[i], loaded beside cdst[i] (same chunk, one chunk ahead); else cedge is not read
+template <int HD, int N, bool BF, int LASTD, bool EO = false>
 __device__ __forceinline__ typename PullVec<N>::T pull_range(const uint32_t* __restrict__ stash,
-                                                             const int32_t* __restrict__ cdst,
+                                                             const int32_t* __restrict__ cdst, const int32_t* __restrict__ cedge,
                                                              const float* __restrict__ gfull, const uint8_t* __restrict__ hbits, int gh_stride, int hb_stride,
                                                              float slope, int b, int e, int lane,
                                                              typename PullVec<N>::T ac, typename PullVec<N>::T acs) {
@@ -404,16 +405,25 @@ __device__ __forceinline__ typename PullVec<N>::T pull_range(const uint32_t* __r
         const int j = i0 + (lane & (CH - 1));
         return cdst[j < e ? j : e - 1];
     };
+    [[maybe_unused]] auto load_edge = [&](int i0) {
+        const int j = i0 + (lane & (CH - 1));
+        return cedge[j < e ? j : e - 1];
+    };
     int dv = load_dst(b);                                   // callers pass b < e
+    [[maybe_unused]] int ev = 0;
+    if constexpr (EO) ev = load_edge(b);
     for (int i0 = b; i0 < e; i0 += CH) {
         const int dn = (i0 + CH < e) ? load_dst(i0 + CH) : 0;
+        [[maybe_unused]] int en = 0;
+        if constexpr (EO) en = (i0 + CH < e) ? load_edge(i0 + CH) : 0;
         uint32_t w[U];
         V g[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int i = i0 + u * G + gidx;
             const int ic = i < e ? i : e - 1;                   // clamped: loads need no predicate
-            w[u] = stash[(uint64_t)(uint32_t)ic * LPE + cp];
+            if constexpr (EO) w[u] = stash[(uint64_t)(uint32_t)__shfl(ev, u * G + gidx) * LPE + cp];      // lanes beyond the list hold its last slot's edge
+            else w[u] = stash[(uint64_t)(uint32_t)ic * LPE + cp];
             const uint32_t drow = (uint32_t)__shfl(dv, u * G + gidx);
             if constexpr (LASTD > 0) {                            // gfull = gh here
                 constexpr float inv_heads = 1.0f / (float)(HD / LASTD);
@@ -453,6 +463,7 @@ __device__ __forceinline__ typename PullVec<N>::T pull_range(const uint32_t* __r
             acc += (g[u] * al + asel * ge) * keep;
         }
         dv = dn;
+        if constexpr (EO) ev = en;
     }
 #pragma unroll
     for (int off = LPE; off < 64; off <<= 1)
@@ -501,9 +512,11 @@ __device__ __forceinline__ typename PullVec<N>::T select_bits(uint32_t bits, typ
     return r;
 }
 // TAB: multipliers from the LDS tables (T) — else from select_bits (no LDS, no per-block table set-up)
-template <int HD, int N, int LASTD, bool TAB>
+// EO: records in CSR edge order — the record of a slot is cedge[slot] (streamed beside cdst, unclamped: its padding names the spare
+// record), so the record address is per lane and per step instead of the wave-uniform base + loop-invariant offset
+template <int HD, int N, int LASTD, bool TAB, bool EO = false>
 __device__ __forceinline__ typename PullVec<N>::T pull_range2(const PullTabs<N>& T, const uint32_t* __restrict__ stash,
-                                                              const int32_t* __restrict__ cdst, const float* __restrict__ gfull,
+                                                              const int32_t* __restrict__ cdst, const int32_t* __restrict__ cedge, const float* __restrict__ gfull,
                                                               const uint8_t* __restrict__ hbits, int b, int e, int lane,
                                                               typename PullVec<N>::T ac, float slope) {
     using V = typename PullVec<N>::T;
@@ -525,8 +538,13 @@ __device__ __forceinline__ typename PullVec<N>::T pull_range2(const PullTabs<N>&
     const char* dp = reinterpret_cast<const char*>(cdst + b);
     const uint32_t doff = (uint32_t)(lane & (CH - 1)) * 4u;
     int dv = *reinterpret_cast<const int32_t*>(dp + doff);
+    [[maybe_unused]] const char* ep = reinterpret_cast<const char*>(cedge + (EO ? b : 0));
+    [[maybe_unused]] int ev = 0;
+    if constexpr (EO) ev = *reinterpret_cast<const int32_t*>(ep + doff);
     for (int rem = e - b; rem > 0; rem -= CH, sp += CH * LPE * 4, dp += CH * 4) {
         const int dn = *reinterpret_cast<const int32_t*>(dp + CH * 4 + doff);          // next chunk's destinations, unconditionally (padding)
+        [[maybe_unused]] int en = 0;
+        if constexpr (EO) { ep += CH * 4; en = *reinterpret_cast<const int32_t*>(ep + doff); }
         const int d0 = __builtin_amdgcn_readfirstlane(dv);                              // the chunk's first slot: always inside the list
         uint32_t w[U];
         V g[U];
@@ -536,7 +554,13 @@ __device__ __forceinline__ typename PullVec<N>::T pull_range2(const PullTabs<N>&
             // unclamped (the padding keeps it legal; a slot beyond the list reads the next source's record and is zeroed below).
             // Redirecting such lanes to the chunk's first record instead cost the last layer's launch +1.1 ms (1.71 -> 2.79):
             // the per-lane offset stops being loop-invariant
-            const uint32_t ww = *reinterpret_cast<const uint32_t*>(sp + (uint32_t)((u * G + gidx) * LPE + cp) * 4u);
+            uint32_t ww;
+            if constexpr (EO) {
+                // a slot beyond the list re-reads the chunk's first record (always inside the list): left alone it would fetch another
+                // list's record, a random line of its own (0.7 ms per launch on the last layer), where the scattered layout reads on in its stream
+                const int er = __shfl(ev, u * G + gidx);
+                ww = stash[(uint64_t)(uint32_t)(valid ? er : __builtin_amdgcn_readfirstlane(ev)) * LPE + cp];
+            } else ww = *reinterpret_cast<const uint32_t*>(sp + (uint32_t)((u * G + gidx) * LPE + cp) * 4u);
             int drow = __shfl(dv, u * G + gidx);
             drow = valid ? drow : d0;
             w[u] = valid ? ww : 0u;
@@ -560,6 +584,7 @@ __device__ __forceinline__ typename PullVec<N>::T pull_range2(const PullTabs<N>&
             else acc += select_bits<N>(w[u], ac, acs) * ge;
         }
         dv = dn;
+        if constexpr (EO) ev = en;
     }
 #pragma unroll
     for (int off = LPE; off < 64; off <<= 1)
@@ -568,33 +593,62 @@ __device__ __forceinline__ typename PullVec<N>::T pull_range2(const PullTabs<N>&
     return acc;
 }
 
+// The body of gpl_pull_kernel and of its edge-order twin gpl_pull_eo_kernel (EO_: records in edge order, through CEDGE_), as text: the
+// twin is a kernel of its own, so that the scattered kernel keeps its arguments and its machine code.  Likewise the chunk kernels'.
+#define GAT_PULL_LIST_BODY(BF_, EO_, CEDGE_) \
+    using V = typename PullVec<N>::T; \
+    constexpr int LPE = HD / N; \
+    __shared__ PullTabs<N> tabs; \
+    if constexpr (V2 == 1) pull_tabs_init<N>(tabs, slope, LASTD > 0 ? 1.0f / (float)(HD / (LASTD > 0 ? LASTD : 1)) : 1.0f); \
+    const int lane = threadIdx.x & 63; \
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); \
+    const int64_t s = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave; \
+    if (s >= n_table) return; \
+    const int b = __builtin_amdgcn_readfirstlane(src_ptr[s]), e = __builtin_amdgcn_readfirstlane(src_ptr[s + 1]); \
+    if (e - b > kHeavySlots) return;   /* long lists: gpl_pull_chunk_kernel + gpl_heavy_fix_kernel */ \
+    const int cp = lane % LPE; \
+    V acc; \
+    if (b < e) { \
+        const V ac = *reinterpret_cast<const V*>(a + cp * N); \
+        if constexpr (V2 != 0) acc = pull_range2<HD, N, LASTD, V2 == 1, EO_>(tabs, stash, cdst, CEDGE_, gfull, hbits, b, e, lane, ac, slope); \
+        else acc = pull_range<HD, N, BF_, LASTD, EO_>(stash, cdst, CEDGE_, gfull, hbits, gh_stride, hb_stride, slope, b, e, lane, ac, ac * slope); \
+    } else { \
+        _Pragma("unroll") \
+        for (int i = 0; i < N; ++i) acc[i] = 0.f; \
+    } \
+    if (lane < LPE) stream_store(reinterpret_cast<V*>(gPL + s * HD + cp * N), acc);
+#define GAT_PULL_CHUNK_BODY(BF_, EO_, CEDGE_) \
+    using V = typename PullVec<N>::T; \
+    constexpr int LPE = HD / N; \
+    __shared__ PullTabs<N> tabs; \
+    if constexpr (V2 == 1) pull_tabs_init<N>(tabs, slope, LASTD > 0 ? 1.0f / (float)(HD / (LASTD > 0 ? LASTD : 1)) : 1.0f); \
+    const int lane = threadIdx.x & 63; \
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); \
+    const int k = blockIdx.x * 4 + wave; \
+    if (k >= n_chunks) return; \
+    const int4 ch = chunks[k];   /* {first slot, end slot, partial row, -}, never empty */ \
+    const int cp = lane % LPE; \
+    const V ac = *reinterpret_cast<const V*>(a + cp * N); \
+    V acc; \
+    if constexpr (V2 != 0) acc = pull_range2<HD, N, LASTD, V2 == 1, EO_>(tabs, stash, cdst, CEDGE_, gfull, hbits, __builtin_amdgcn_readfirstlane(ch.x), __builtin_amdgcn_readfirstlane(ch.y), lane, ac, slope); \
+    else acc = pull_range<HD, N, BF_, LASTD, EO_>(stash, cdst, CEDGE_, gfull, hbits, gh_stride, hb_stride, slope, ch.x, ch.y, lane, ac, ac * slope); \
+    if (lane < LPE) *reinterpret_cast<V*>(part + (int64_t)ch.z * HD + cp * N) = acc;
+
 template <int HD, int N, bool BF, int LASTD, int V2 = 0>          // V2: 0 first form, 1 second form with LDS tables, 2 second form with bit selects
 __global__ __launch_bounds__(256) void gpl_pull_kernel(const int32_t* __restrict__ src_ptr, const uint32_t* __restrict__ stash,
                                                        const int32_t* __restrict__ cdst, const float* __restrict__ gfull,
                                                        const uint8_t* __restrict__ hbits, int gh_stride, int hb_stride,
                                                        const float* __restrict__ a, float slope, float* __restrict__ gPL,
                                                        int64_t n_table, int32_t kHeavySlots) {
-    using V = typename PullVec<N>::T;
-    constexpr int LPE = HD / N;
-    __shared__ PullTabs<N> tabs;
-    if constexpr (V2 == 1) pull_tabs_init<N>(tabs, slope, LASTD > 0 ? 1.0f / (float)(HD / (LASTD > 0 ? LASTD : 1)) : 1.0f);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t s = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
-    if (s >= n_table) return;
-    const int b = __builtin_amdgcn_readfirstlane(src_ptr[s]), e = __builtin_amdgcn_readfirstlane(src_ptr[s + 1]);
-    if (e - b > kHeavySlots) return;                    // long lists: gpl_pull_chunk_kernel + gpl_heavy_fix_kernel
-    const int cp = lane % LPE;
-    V acc;
-    if (b < e) {
-        const V ac = *reinterpret_cast<const V*>(a + cp * N);
-        if constexpr (V2 != 0) acc = pull_range2<HD, N, LASTD, V2 == 1>(tabs, stash, cdst, gfull, hbits, b, e, lane, ac, slope);
-        else acc = pull_range<HD, N, BF, LASTD>(stash, cdst, gfull, hbits, gh_stride, hb_stride, slope, b, e, lane, ac, ac * slope);
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; ++i) acc[i] = 0.f;
-    }
-    if (lane < LPE) stream_store(reinterpret_cast<V*>(gPL + s * HD + cp * N), acc);
+    GAT_PULL_LIST_BODY(BF, false, nullptr)
+}
+template <int HD, int N, int LASTD, int V2>                       // fp32 records in CSR edge order, fetched through cedge
+__global__ __launch_bounds__(256) void gpl_pull_eo_kernel(const int32_t* __restrict__ src_ptr, const uint32_t* __restrict__ stash,
+                                                          const int32_t* __restrict__ cdst, const float* __restrict__ gfull,
+                                                          const uint8_t* __restrict__ hbits, int gh_stride, int hb_stride,
+                                                          const float* __restrict__ a, float slope, float* __restrict__ gPL,
+                                                          int64_t n_table, int32_t kHeavySlots, const int32_t* __restrict__ cedge) {
+    GAT_PULL_LIST_BODY(false, true, cedge)
 }
 
 template <int HD, int N, bool BF, int LASTD, int V2 = 0>
@@ -603,22 +657,18 @@ __global__ __launch_bounds__(256) void gpl_pull_chunk_kernel(const int4* __restr
                                                              const float* __restrict__ gfull, const uint8_t* __restrict__ hbits,
                                                              int gh_stride, int hb_stride, const float* __restrict__ a,
                                                              float slope, float* __restrict__ part) {
-    using V = typename PullVec<N>::T;
-    constexpr int LPE = HD / N;
-    __shared__ PullTabs<N> tabs;
-    if constexpr (V2 == 1) pull_tabs_init<N>(tabs, slope, LASTD > 0 ? 1.0f / (float)(HD / (LASTD > 0 ? LASTD : 1)) : 1.0f);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int k = blockIdx.x * 4 + wave;
-    if (k >= n_chunks) return;
-    const int4 ch = chunks[k];                          // {first slot, end slot, partial row, -}, never empty
-    const int cp = lane % LPE;
-    const V ac = *reinterpret_cast<const V*>(a + cp * N);
-    V acc;
-    if constexpr (V2 != 0) acc = pull_range2<HD, N, LASTD, V2 == 1>(tabs, stash, cdst, gfull, hbits, __builtin_amdgcn_readfirstlane(ch.x), __builtin_amdgcn_readfirstlane(ch.y), lane, ac, slope);
-    else acc = pull_range<HD, N, BF, LASTD>(stash, cdst, gfull, hbits, gh_stride, hb_stride, slope, ch.x, ch.y, lane, ac, ac * slope);
-    if (lane < LPE) *reinterpret_cast<V*>(part + (int64_t)ch.z * HD + cp * N) = acc;
+    GAT_PULL_CHUNK_BODY(BF, false, nullptr)
 }
+template <int HD, int N, int LASTD, int V2>
+__global__ __launch_bounds__(256) void gpl_pull_chunk_eo_kernel(const int4* __restrict__ chunks, int32_t n_chunks,
+                                                                const uint32_t* __restrict__ stash, const int32_t* __restrict__ cdst,
+                                                                const float* __restrict__ gfull, const uint8_t* __restrict__ hbits,
+                                                                int gh_stride, int hb_stride, const float* __restrict__ a,
+                                                                float slope, float* __restrict__ part, const int32_t* __restrict__ cedge) {
+    GAT_PULL_CHUNK_BODY(false, true, cedge)
+}
+#undef GAT_PULL_LIST_BODY
+#undef GAT_PULL_CHUNK_BODY
 
 // Group-per-source form of the same pass (see edge_fwd3_kernel): a wave carries G = 64/(HD/N) source lists side by side,
 // one per lane group, from a length-sorted item list {source, first slot, end slot, partial row | -1} (lists longer than
@@ -967,8 +1017,9 @@ __global__ __launch_bounds__(256) void gpl_runs_fix_kernel(const int4* __restric
 }
 
 // cdst[pos[e]] = row of CSR edge e (binary search in row_ptr, as csr_to_coo_kernel)
+// cedge (or null): cedge[pos[e]] = e, the inverse of pos
 __global__ __launch_bounds__(256) void csc_dst_kernel(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ pos,
-                                                     int32_t* __restrict__ cdst, int64_t n_rows, int64_t n_edges) {
+                                                     int32_t* __restrict__ cdst, int64_t n_rows, int64_t n_edges, int32_t* __restrict__ cedge) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_edges; e += stride) {
         int64_t lo = 0, hi = n_rows;          // invariant: row_ptr[lo] <= e < row_ptr[hi]
@@ -976,16 +1027,24 @@ __global__ __launch_bounds__(256) void csc_dst_kernel(const int32_t* __restrict_
             const int64_t mid = (lo + hi) >> 1;
             if ((int64_t)row_ptr[mid] <= e) lo = mid; else hi = mid;
         }
-        cdst[pos[e]] = (int32_t)lo;
+        const int32_t p = pos[e];
+        cdst[p] = (int32_t)lo;
+        if (cedge != nullptr) cedge[p] = (int32_t)e;
     }
+}
+__global__ __launch_bounds__(64) void fill_kernel(int32_t* v, int32_t n, int32_t value) {
+    if ((int)threadIdx.x < n) v[threadIdx.x] = value;
 }
 
 }  // namespace
 
-int build_csc_dst(const int32_t* row_ptr, const int32_t* pos, int32_t* cdst, int64_t n_rows, int64_t n_edges, hipStream_t s) {
+int build_csc_dst(const int32_t* row_ptr, const int32_t* pos, int32_t* cdst, int64_t n_rows, int64_t n_edges, hipStream_t s, int32_t* cedge) {
+    static_assert(kPullPad <= 64, "one block fills the padding");
     if (n_edges <= 0) return 0;
+    if (cedge != nullptr)                                   // the padding names the spare record behind the last
+        hipLaunchKernelGGL(fill_kernel, dim3(1), dim3(64), 0, s, cedge + n_edges, (int32_t)kPullPad, (int32_t)n_edges);
     const int64_t blocks = std::min<int64_t>((n_edges + 255) / 256, 65536);
-    hipLaunchKernelGGL(csc_dst_kernel, dim3((unsigned)blocks), dim3(256), 0, s, row_ptr, pos, cdst, n_rows, n_edges);
+    hipLaunchKernelGGL(csc_dst_kernel, dim3((unsigned)blocks), dim3(256), 0, s, row_ptr, pos, cdst, n_rows, n_edges, cedge);
     GAT_HIP(hipGetLastError());
     return 0;
 }
@@ -1027,6 +1086,40 @@ static int gpl_bf16_group_env() {
     static const int v = [] { const char* e = choice_env("GAT_GPL_BF16_GROUP"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
     return v;
 }
+// GAT_STASH_ORDER=0|1: the layout of the fp32 records wherever the edge-ordered form exists (records_take_edge_order), A/B; h | l: edge
+// order on the layers whose pull gathers g rows (hidden) / node records (last) only, the measurement behind the defaults.
+// Bit 0: hidden kind, bit 1: last kind (-1: not set)
+static int stash_order_env() {
+    static const int v = [] { const char* e = choice_env("GAT_STASH_ORDER"); return e ? (e[0] == '0' ? 0 : e[0] == 'h' ? 1 : e[0] == 'l' ? 2 : 3) : -1; }();
+    return v;
+}
+
+// Which family of pull kernels runs (declared in gat_internal.h: pick_pull branches on it, the record-order rule asks it).
+// Slot-parallel form (gpl_pull_runs_kernel): default where the lists are short (a destination-range shard: the list-per-group
+// kernel pays three dependent latencies per ~4 slots); GAT_PULL_RUNS=0|1 forces.  The last layer's variant reads the
+// 64-byte node records (gh_stride 16, decision bytes at +32).
+// GAT_PULL_GROUPS=1: the group-per-source kernel.  Measured SLOWER on the Products shape (5.8 vs 5.36 ms per step), as was
+// everything else that shortened this pass's dependency chains or shrank its gathers: see DESIGN §4 (random-row rate)
+// default: groups only where the lists are short (a destination-range shard sees ~deg/P slots per source: one wave
+// per 3-slot list wastes 15 of its 16 gather slots) — the same rule the message-row sum used (n_slots < 8 n_table)
+// ... and only with enough lists to give every resident wave several (Pubmed shape, 19,717 lists: one wave per list 0.27 vs 0.30 ms per step)
+PullForm pull_form(const SourceIndex& ix, int32_t lpe, bool records64) {
+    const bool padded = ix.slot_capacity >= ix.n_slots + kPullPad;
+    const int runs_env = pull_runs_env(), groups_env = pull_groups_env();
+    const bool runs_ok = padded && ix.csrc != nullptr && ix.run % lpe == 0 && records64;
+    if (runs_ok && (runs_env >= 0 ? runs_env == 1 : (groups_env < 0 && short_lists_take_runs(ix.n_slots, ix.n_table)))) return kPullRuns;     // an explicit GAT_PULL_GROUPS selects among the list kernels
+    const bool groups = groups_env >= 0 ? groups_env == 1 : (ix.n_slots < 8 * ix.n_table && ix.n_items >= 32768);
+    return (ix.items != nullptr && groups) ? kPullItems : kPullLists;
+}
+// THE record-order rule (gat_internal.h).  Defaults per layer kind: DESIGN §4 "Record order"
+bool records_take_edge_order(const SourceIndex& ix, int32_t H, int32_t D, bool fp32, bool node_records, bool records64) {
+    const int words = edge_stash_words(H, D);
+    if (!fp32 || words == 0 || ix.cedge == nullptr || !edge_backward_groups(H, D)) return false;
+    if (pull_form(ix, words, records64) != kPullLists) return false;
+    const int env = stash_order_env();
+    if (env >= 0) return (env >> (node_records ? 1 : 0)) & 1;
+    return node_records ? kEdgeOrderLast : kEdgeOrderHidden;
+}
 
 namespace {
 // The kernel of one source-major pass and what its launch needs.  pick_pull / pick_sum below are the only places that name an
@@ -1059,13 +1152,11 @@ GplPick pick_pull(const SourceIndex& ix, const PullArgs& A, bool padded) {
     // one wave per block for the pull kernel (GAT_GPL_WAVES=1|2|4): 5.03 / 5.11 / 5.30 ms per step on the Products shape — a
     // 4-wave block lives as long as its longest list; the message-row sum (pick_sum) measured the other way round
     const int wpb = gpl_waves_env() ? gpl_waves_env() : 1;
-    // Slot-parallel form (gpl_pull_runs_kernel): default where the lists are short (a destination-range shard: the list-per-group
-    // kernel below pays three dependent latencies per ~4 slots); GAT_PULL_RUNS=0|1 forces.  The last layer's variant reads the
-    // 64-byte node records (gh_stride 16, decision bytes at +32).
-    const int runs_env = pull_runs_env(), groups_env = pull_groups_env();
     const bool records64 = LASTD == 0 || (A.gh_stride == 16 && A.hb_stride == 64);
-    const bool runs_ok = padded && ix.csrc != nullptr && ix.run % LPE == 0 && records64;
-    if (runs_ok && (runs_env >= 0 ? runs_env == 1 : (groups_env < 0 && short_lists_take_runs(ix.n_slots, ix.n_table)))) {     // an explicit GAT_PULL_GROUPS selects among the list kernels
+    const PullForm form = pull_form(ix, LPE, records64);
+    // records in edge order: only what the rule gives (the caller asked it: plan_backward_edges) has kernels
+    if (A.edge_order && !records_take_edge_order(ix, A.H, A.D, !BF, LASTD > 0, records64)) return {};
+    if (form == kPullRuns) {
         constexpr int U = LPE % 8 == 0 ? 8 : 4;
         const int u_env = pull_u_env();
         if constexpr (LPE == 16 && !BF) {
@@ -1074,13 +1165,7 @@ GplPick pick_pull(const SourceIndex& ix, const PullArgs& A, bool padded) {
         }
         return pick_runs(ix, GAT_K(gpl_pull_runs_kernel<HD, N, BF, LASTD, U>), G);
     }
-    // GAT_PULL_GROUPS=1: the group-per-source kernel.  Measured SLOWER on the Products shape (5.8 vs 5.36 ms per step), as was
-    // everything else that shortened this pass's dependency chains or shrank its gathers: see DESIGN §4 (random-row rate)
-    // default: groups only where the lists are short (a destination-range shard sees ~deg/P slots per source: one wave
-    // per 3-slot list wastes 15 of its 16 gather slots) — the same rule the message-row sum used (n_slots < 8 n_table)
-    // ... and only with enough lists to give every resident wave several (Pubmed shape, 19,717 lists: one wave per list 0.27 vs 0.30 ms per step)
-    const bool groups = groups_env >= 0 ? groups_env == 1 : (ix.n_slots < 8 * ix.n_table && ix.n_items >= 32768);
-    if (ix.items != nullptr && groups) {
+    if (form == kPullItems) {
         const int64_t quads = (ix.n_items + G - 1) / G;
         return {GAT_K(gpl_pull3_kernel<HD, N, BF, LASTD>), GplPick::kItems, nullptr, (unsigned)((quads + 3) / 4)};
     }
@@ -1097,6 +1182,11 @@ GplPick pick_pull(const SourceIndex& ix, const PullArgs& A, bool padded) {
     const int v2 = (padded && !BF && records64) ? v2_want : 0;
     const unsigned grid = (unsigned)((ix.n_table + wpb - 1) / wpb), block = 64u * wpb;
     if constexpr (!BF) {
+        if (A.edge_order) {                           // the same three forms of the walk, records fetched through cedge
+            if (v2 == 1) return {GAT_K(gpl_pull_eo_kernel<HD, N, LASTD, 1>), GplPick::kLists, GAT_K(gpl_pull_chunk_eo_kernel<HD, N, LASTD, 1>), grid, block};
+            if (v2 == 2) return {GAT_K(gpl_pull_eo_kernel<HD, N, LASTD, 2>), GplPick::kLists, GAT_K(gpl_pull_chunk_eo_kernel<HD, N, LASTD, 2>), grid, block};
+            return {GAT_K(gpl_pull_eo_kernel<HD, N, LASTD, 0>), GplPick::kLists, GAT_K(gpl_pull_chunk_eo_kernel<HD, N, LASTD, 0>), grid, block};
+        }
         if (v2 == 1) return {GAT_K(gpl_pull_kernel<HD, N, BF, LASTD, 1>), GplPick::kLists, GAT_K(gpl_pull_chunk_kernel<HD, N, BF, LASTD, 1>), grid, block};
         if (v2 == 2) return {GAT_K(gpl_pull_kernel<HD, N, BF, LASTD, 2>), GplPick::kLists, GAT_K(gpl_pull_chunk_kernel<HD, N, BF, LASTD, 2>), grid, block};
     }
@@ -1188,13 +1278,14 @@ int launch_gpl_pull(const SourceIndex& ix, const PullArgs& A, hipStream_t s) {
     const bool padded = ix.slot_capacity >= ix.n_slots + kPullPad;
     const bool last = A.gh != nullptr && A.hbits != nullptr;
     GplPick p = pick_pull_pass(ix, A, last, padded);
-    if (p.fn == nullptr) return fail(GAT_E_UNSUPPORTED, "gpl_pull: no stash path for this (H, D)");
+    if (p.fn == nullptr) return fail(GAT_E_UNSUPPORTED, A.edge_order ? "gpl_pull: records in edge order where the record-order rule gives the scattered layout" : "gpl_pull: no stash path for this (H, D)");
     SourceIndex x = ix;                                 // the kernels' arguments, by address
     PullArgs q = A;
     const float* g = last ? A.gh : A.gfull;
     int32_t hs = heavy_slots(ix.n_slots);
-    void* lists[] = {&x.src_ptr, &q.stash, &x.cdst, &g, &q.hbits, &q.gh_stride, &q.hb_stride, &q.a, &q.slope, &q.gPL, &x.n_table, &hs};
-    void* chunk[] = {&x.chunks, &x.n_chunks, &q.stash, &x.cdst, &g, &q.hbits, &q.gh_stride, &q.hb_stride, &q.a, &q.slope, &x.part};
+    // cedge, last: the edge-order kernels' extra argument (the scattered kernels' lists end before it)
+    void* lists[] = {&x.src_ptr, &q.stash, &x.cdst, &g, &q.hbits, &q.gh_stride, &q.hb_stride, &q.a, &q.slope, &q.gPL, &x.n_table, &hs, &x.cedge};
+    void* chunk[] = {&x.chunks, &x.n_chunks, &q.stash, &x.cdst, &g, &q.hbits, &q.gh_stride, &q.hb_stride, &q.a, &q.slope, &x.part, &x.cedge};
     void* items[] = {&x.items, &x.n_items, &q.stash, &x.cdst, &g, &q.hbits, &q.gh_stride, &q.hb_stride, &q.a, &q.slope, &q.gPL, &x.part};
     void* runs[] = {&q.stash, &x.cdst, &g, &q.hbits, &q.a, &q.slope, &q.gPL, &p.rd};
     return run_pick(ix, p, p.form == GplPick::kRuns ? runs : p.form == GplPick::kItems ? items : lists, chunk, A.gPL, A.H * A.D, s);

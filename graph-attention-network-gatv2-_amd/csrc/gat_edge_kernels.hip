@@ -689,6 +689,20 @@ __device__ __forceinline__ void stream_store(T* p, const T& v) {
     *p = v;
 #endif
 }
+// 4 x 4 transpose inside every lane quad: lane t of a quad (t = lane & 3) holds a[0..3] and ends with the a[t] of lanes 0..3 of its
+// quad, in lane order.  Two exchange stages (lane ^ 1, lane ^ 2) of DPP quad permutes, two words each.
+__device__ __forceinline__ void quad_transpose4(uint32_t (&a)[4], int t) {
+    const bool o1 = (t & 1) != 0, o2 = (t & 2) != 0;
+    auto swap = [](uint32_t& lo, uint32_t& hi, bool odd, auto ctrl) {          // even lanes give hi and take the partner's lo, odd lanes the reverse
+        const uint32_t x = odd ? lo : hi;
+        const uint32_t y = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, decltype(ctrl)::value, 0xF, 0xF, true);
+        if (odd) lo = y; else hi = y;
+    };
+    swap(a[0], a[1], o1, std::integral_constant<int, 0xB1>{});                  // quad_perm [1,0,3,2]
+    swap(a[2], a[3], o1, std::integral_constant<int, 0xB1>{});
+    swap(a[0], a[2], o2, std::integral_constant<int, 0x4E>{});                  // quad_perm [2,3,0,1]
+    swap(a[1], a[3], o2, std::integral_constant<int, 0x4E>{});
+}
 template <int HD, int N, bool BF>
 __device__ __forceinline__ void store_row_n(float* __restrict__ msg, int slot, int cp, vnf<N> v) {
     if constexpr (BF) {
@@ -1183,9 +1197,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 // PE (with DROP): s takes the edge term A.pe[j] in the score recomputation and in the LReLU / LReLU' terms alike, and gs is streamed to
 // A.gpe[j] for the edges inside the item (no spare row: padded lanes do not write).  The PE rows of a step are loaded next to its
 // gathers; gs goes out in the step that forms it.
-template <int HD, int D, int N, int DBG = 0, bool BF = false, bool MSG = false, bool DROP = false, bool PE = false>
+// EO (records only, gat_internal.h records_take_edge_order): the record of CSR edge j goes to record j, not to its source-major slot
+// pos[j] — a wave's stores follow its walk through the row instead of scattering one half line per edge, and pos is not read.
+// LINES (with EO): the step's four records leave as ONE 16-byte store per lane — after a 4 x 4 transpose inside every lane quad, lane
+// 4q + t of a group holds words 4q .. 4q+3 of the step's record t (a group's 16 lanes: four whole 64-byte records, each still
+// contiguous and in the same word order); the slot of a record is its edge index, so no slot words are kept or shuffled.
+template <int HD, int D, int N, int DBG = 0, bool BF = false, bool MSG = false, bool DROP = false, bool PE = false, bool EO = false, bool LINES = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DROP ? 3 : 4, 8))) void edge_bwd3_kernel(BwdArgsT<DROP> A) {
     static_assert(DROP || !PE, "the edge term travels in the extended argument struct");
+    static_assert(!EO || (!MSG && !BF && DBG == 0), "edge order: fp32 records");
     constexpr int LPE = HD / N, G = 64 / LPE, DL = D / N, H = HD / D;
     constexpr int U = 4;
     static_assert((MSG || DL == 2) && LPE >= U, "records: two lanes per head (one carries alpha, the other ge)");
@@ -1194,6 +1214,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DROP ? 3 : 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int cp = lane % LPE, gidx = lane / LPE;
     const int c = N * cp;
+    static_assert(!LINES || (EO && LPE % 4 == 0 && U == 4), "whole-line stores: edge order, quads of lanes inside a group");
+    // LINES: the records of step `stp` of the item (its edges b + stp * U ..), words pend_w; an edge outside [b, e) is the spare record
+    [[maybe_unused]] auto store_lines = [&](int b, int e, int stp, uint32_t (&pw)[U]) {
+        uint32_t o[4] = {pw[0], pw[1], pw[2], pw[3]};
+        quad_transpose4(o, cp & 3);
+        const int j = b + stp * U + (cp & 3);
+        const uint32_t rec = (j >= b && j < e) ? (uint32_t)j : A.stash_spare;
+        stream_store(reinterpret_cast<uint4*>(A.stash + ((uint64_t)rec * LPE + (cp & ~3))), make_uint4(o[0], o[1], o[2], o[3]));
+    };
     const vnf<N> ac = *reinterpret_cast<const vnf<N>*>(A.a + c);
     const vnf<N> acs = ac * A.slope;
     const vnf<N> ac2 = ac * kLog2e;
@@ -1216,7 +1245,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DROP ? 3 : 
             j = j < e ? j : e - 1;
             j = j > 0 ? j : 0;
             srcv = A.col_idx[j];
-            posv = (DBG == 2) ? j : A.pos[j];
+            posv = (DBG == 2 || EO) ? j : A.pos[j];
             // timing experiments (wrong results): K write FRONTS, each advancing sequentially with the CSR index — the store pattern of
             // records laid out by (source block, CSR index): front = slot mod K (a pseudo-random block), place = front * E/K + j / K
             if constexpr (DBG >= 15 && DBG <= 18) {
@@ -1334,6 +1363,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DROP ? 3 : 
                 const int j0 = b + (st > 0 ? st - 1 : 0) * U;
                 uint4 w4 = make_uint4(pend_w[0], pend_w[1], pend_w[2], pend_w[3]);
                 *reinterpret_cast<uint4*>(A.stash + (uint64_t)(uint32_t)(j0 < e ? j0 : 0) * LPE + cp * 4) = w4;
+            } else if constexpr (LINES) {
+                store_lines(b, e, st - 1, pend_w);
             } else if constexpr (DBG != 1) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) stream_store(&A.stash[(uint64_t)pend_s[u] * LPE + cp], pend_w[u]);
@@ -1394,6 +1425,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DROP ? 3 : 
 #pragma unroll
                 for (int u = 0; u < U; ++u) store_row_n<HD, N, BF>(A.msg, (int)pend_s[u], cp, pend_m[u]);          // the last step's rows
             }
+        } else if constexpr (LINES) {
+            store_lines(b, e, nst - 1, pend_w);
         } else if constexpr (DBG != 1 && DBG != 3) {
 #pragma unroll
             for (int u = 0; u < U; ++u) stream_store(&A.stash[(uint64_t)pend_s[u] * LPE + cp], pend_w[u]);      // the last step's records
@@ -2112,6 +2145,7 @@ static bool edge_shape_listed(int HD, int D) {
     return false;
 }
 // channels per lane of the two-lanes-per-head kernels (stash backward, group-per-row kernels) for this shape, 0 = none
+constexpr bool kStashLines = true;
 constexpr int stash_n(int HD, int D) { return (D == 8 && HD >= 32) ? 4 : (D == 4 ? 2 : 0); }
 template <int HD, int D> constexpr int stash_n() { return stash_n(HD, D); }
 
@@ -2121,6 +2155,11 @@ static bool row_groups() {
     return v;
 }
 // GAT_PACKED=0 keeps the one-channel-per-lane kernels on the training path too (A/B), forward and backward
+// GAT_STASH_LINES=0|1: edge-ordered records leave as one 16-byte store per lane and step (quad transpose) or as four dword stores (A/B)
+static bool stash_lines() {
+    static const bool v = [] { const char* e = choice_env("GAT_STASH_LINES"); return e ? e[0] != '0' : kStashLines; }();
+    return v;
+}
 static bool packed_layout() {
     static const bool v = [] { const char* e = choice_env("GAT_PACKED"); return !(e && e[0] == '0'); }();
     return v;
@@ -2209,14 +2248,26 @@ template <int HD, int D, bool BF>
 EdgePick pick_bwd(const EdgeBwdArgs& a, bool drop, int dbg, bool pe) {
     constexpr int N3 = stash_n<HD, D>(), N2 = (HD >= 32 && D % 4 == 0) ? 4 : 2;
     const bool store = a.pos != nullptr && a.msg != nullptr, taps = a.ge != nullptr, stash = a.stash != nullptr && !taps;
+    // records in CSR edge order (EdgeBwdArgs::edge_order, set under records_take_edge_order): the EO instantiation of the group-per-row
+    // record kernel, plain / DROP / PE; launch_edge_backward refuses the flag where that kernel is not the pick
+    [[maybe_unused]] const bool eo = a.edge_order != 0 && stash && store && !BF && N3 != 0 && row_groups() && dbg == 0;
+    [[maybe_unused]] const bool lines = eo && stash_lines();
     if (drop) {
         if (!store) return {};
         if (pe) {
             if (taps) return {GAT_K(edge_bwd_kernel<HD, D, true, true, 0, BF, true, true>)};
+            if constexpr (N3 != 0 && !BF) {
+                if (lines) return {GAT_K(edge_bwd3_kernel<HD, D, N3, 0, false, false, true, true, true, true>)};
+                if (eo) return {GAT_K(edge_bwd3_kernel<HD, D, N3, 0, false, false, true, true, true>)};
+            }
             if constexpr (N3 != 0) return {stash ? GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, false, true, true>) : GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, true, true, true>)};
             else return {GAT_K(edge_bwd2_kernel<HD, D, N2, 0, BF, false, true, true>)};
         }
         if (taps) return {GAT_K(edge_bwd_kernel<HD, D, true, true, 0, BF, true>)};
+        if constexpr (N3 != 0 && !BF) {
+            if (lines) return {GAT_K(edge_bwd3_kernel<HD, D, N3, 0, false, false, true, false, true, true>)};
+            if (eo) return {GAT_K(edge_bwd3_kernel<HD, D, N3, 0, false, false, true, false, true>)};
+        }
         if constexpr (N3 != 0) return {stash ? GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, false, true>) : GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, true, true>)};
         else return {GAT_K(edge_bwd2_kernel<HD, D, N2, 0, BF, false, true>)};
     }
@@ -2245,6 +2296,10 @@ EdgePick pick_bwd(const EdgeBwdArgs& a, bool drop, int dbg, bool pe) {
     }
 #endif
     if constexpr (N3 != 0) {
+        if constexpr (!BF) {
+            if (lines) return {GAT_K(edge_bwd3_kernel<HD, D, N3, 0, false, false, false, false, true, true>)};
+            if (eo) return {GAT_K(edge_bwd3_kernel<HD, D, N3, 0, false, false, false, false, true>)};
+        }
         // records; bf16 storage: always the group-per-row kernel (GAT_ROWGROUP=0 has no bf16 form)
         if (stash) return {(BF || row_groups()) ? GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF>) : GAT_K(edge_bwd2s_kernel<HD, D, N3>)};
         if (msg_rows && row_groups() && group_msg()) {                            // message rows from the group-per-row kernel
@@ -2327,6 +2382,7 @@ int edge_stash_words(int32_t H, int32_t D) {
     const int n = edge_shape_listed(H * D, D) ? stash_n(H * D, D) : 0;
     return n ? H * D / n : 0;
 }
+bool edge_backward_groups(int32_t H, int32_t D) { return edge_shape_listed(H * D, D) && stash_n(H * D, D) != 0 && row_groups(); }
 
 int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const EdgeFwdExtras* extras) {
     if (a.n_rows <= 0) return 0;
@@ -2384,6 +2440,8 @@ int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s, const DropArgs* dr
         if (a.stash != nullptr && a.ge == nullptr && (a.gfull == nullptr || a.pos == nullptr))
             return fail(GAT_E_INVALID, "edge_backward: stash path needs gfull and pos");
         if (ext && dr.step == nullptr) return fail(GAT_E_INVALID, "edge_backward: the extended kernels read the device counter (DropArgs::step)");
+        if (a.edge_order && !(a.stash != nullptr && a.ge == nullptr && !a.bf16 && a.dbg == 0 && edge_backward_groups(a.H, a.D)))
+            return fail(GAT_E_INVALID, "edge_backward: records in edge order need the fp32 group-per-row record kernel");
         const EdgePick p = pick_backward(a, ext, a.dbg, with_pe);
         if (p.fn == nullptr)
             return fail(GAT_E_UNSUPPORTED, "edge_backward: attention dropout / DropEdge / edge features need the store path (not with GAT_BWD_ATOMICS=1 or without the message scratch)");

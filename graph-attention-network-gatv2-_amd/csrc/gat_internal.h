@@ -209,6 +209,7 @@ struct EdgeBwdArgs {
     int32_t n_split;          // split rows: slot_info[n_slots + k].x = first slot of the k-th
     float* part_acc;          // [n_slots][HD]  per-segment gPR partials of split rows
     int32_t dbg;
+    int32_t edge_order;       // records in CSR edge order: record j = edge j (records_take_edge_order below), not stash[pos[j]]; fits the struct's tail padding
 };
 // drop: the attention dropout of the forward this backward follows (same masks)
 // pe / gpe (both or neither; gatv2_abi.h "edge features"): the forward's PE rows, and where gs = ge * a * LReLU'(s) of every CSR edge is
@@ -272,6 +273,7 @@ constexpr int64_t kPullPad = 32;
 struct SourceIndex {
     const int32_t* src_ptr = nullptr;   // [n_table + 1] first slot of every table row
     const int32_t* cdst = nullptr;      // [slot_capacity] destination row of every slot (record path), or null
+    const int32_t* cedge = nullptr;     // [slot_capacity] CSR edge of every slot (the inverse of pos), the padding at the spare record n_slots; or null
     // slot-parallel ("runs") form (gat_csc.hip gpl_pull_runs_kernel): the flat slot stream cut into runs of `run` slots, one per
     // lane group, segmented by a streamed source id per slot
     const int32_t* csrc = nullptr;      // [n_slots + kPullPad] table row of every slot, -1 behind the last; null = runs not built
@@ -294,15 +296,32 @@ constexpr int64_t kRunsMinSlots = 512 << 10;
 // THE short-list rule: lists this short (a destination-range shard, a sparse graph), and enough of them, take the slot-parallel
 // form.  Unforced: the callers apply their switches (GAT_PULL_RUNS, ...) and their own conditions around it.
 inline bool short_lists_take_runs(int64_t n_slots, int64_t n_table) { return n_slots < 8 * n_table && n_slots >= kRunsMinSlots; }
+// Which family of pull kernels a record pass over `ix` runs (gat_csc.hip pick_pull, switches GAT_PULL_RUNS / GAT_PULL_GROUPS included).
+// lpe = lanes per record, records64: hidden layer, or the last layer's 64-byte node records.
+enum PullForm : int32_t { kPullLists, kPullItems, kPullRuns };
+PullForm pull_form(const SourceIndex& ix, int32_t lpe, bool records64);
+// the fp32 record backward of this shape is the group-per-row kernel (gat_edge_kernels.hip; GAT_ROWGROUP=0: the chunked one)
+bool edge_backward_groups(int32_t H, int32_t D);
+// THE record-order rule.  A layer's records may lie in CSR edge order (record j = edge j: the backward streams them out instead of
+// scattering half lines, the pull pass fetches record cedge[slot]) only where the group-per-row backward writes fp32 records and the
+// wave-per-list pull (gpl_pull_kernel + gpl_pull_chunk_kernel) reads them: the only kernels with that form.  node_records: the pull
+// rebuilds g from the last layer's node records (else it gathers gfull rows, as on a hidden layer) — the default is per kind, from
+// the measurement in DESIGN §4 "Record order"; GAT_STASH_ORDER=0|1 forces it wherever the form exists.  plan_backward_edges asks
+// once per layer and hands the answer to both passes (EdgeBwdArgs::edge_order, PullArgs::edge_order); pick_pull refuses a layout
+// the rule does not give.
+constexpr bool kEdgeOrderHidden = true, kEdgeOrderLast = false;     // the unforced answer per layer kind
+bool records_take_edge_order(const SourceIndex& ix, int32_t H, int32_t D, bool fp32, bool node_records, bool records64);
 // message rows: gPL[s][:] = sum over the slots of s of msg[slot][:]   (rows of HD floats, or HD bf16 with msg_bf16)
 int launch_gpl_sum(const SourceIndex& ix, const float* msg, bool msg_bf16, float* gPL, int32_t HD, hipStream_t s);
 // cdst[pos[e]] = destination row of CSR edge e (the source-major twin of a1's dst array; built once per graph)
-int build_csc_dst(const int32_t* row_ptr, const int32_t* pos, int32_t* cdst, int64_t n_rows, int64_t n_edges, hipStream_t s);
+// cedge (or null): [n_edges + kPullPad], cedge[pos[e]] = e, the padding = n_edges (the spare record)
+int build_csc_dst(const int32_t* row_ptr, const int32_t* pos, int32_t* cdst, int64_t n_rows, int64_t n_edges, hipStream_t s, int32_t* cedge = nullptr);
 // Stash path: gPL[s][:] = sum over the slots of s of  g[cdst][:] * alpha + ge * a (.) LReLU'  rebuilt from the records
 // gh / hbits non-null (last layer): g rows are rebuilt from gh [n_rows][D] and the per-lane decision bytes instead of read from gfull
 struct PullArgs {
     const uint32_t* stash; const float* gfull; bool g_bf16; const float* gh; const uint8_t* hbits;
     int32_t gh_stride, hb_stride; const float* a; float slope; float* gPL; int32_t H, D;
+    bool edge_order = false;            // the records lie in CSR edge order (records_take_edge_order): read through SourceIndex::cedge
 };
 int launch_gpl_pull(const SourceIndex& ix, const PullArgs& p, hipStream_t s);
 
