@@ -1,0 +1,170 @@
+// gat_abi_features.hip — the optional features of a context, switched on before it is complete: residual / bias, layer
+// normalisation, edge features, graph-level readout, dropout / DropEdge / training mode.
+#include "gat_ctx.h"
+
+using namespace gat;
+extern "C" {
+
+// ---- residual / bias --------------------------------------------------------------------------------------------
+int gat_set_residual(gat_ctx* c, int32_t flags) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (flags & ~(GAT_RES_LINEAR | GAT_RES_BIAS)) return fail(GAT_E_INVALID, "gat_set_residual: unknown flag bits");
+    GAT_LAYOUT_OPEN(c, "gat_set_residual");
+    if (flags == c->res.flags) return 0;                 // (0 on a fresh context: nothing is touched)
+    GAT_REFUSE_DBG(c, flags != 0, "gat_set_residual", " (those kernels have no residual form)");
+    c->res.flags = flags;
+    return relayout(c);
+}
+// ---- layer normalisation ----------------------------------------------------------------------------------------
+int gat_set_norm(gat_ctx* c, int32_t flags, float eps) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (flags & ~(GAT_NORM_LAYER | GAT_NORM_SKIP_LAST)) return fail(GAT_E_INVALID, "gat_set_norm: unknown flag bits");
+    if ((flags & GAT_NORM_SKIP_LAST) && !(flags & GAT_NORM_LAYER)) return fail(GAT_E_INVALID, "gat_set_norm: GAT_NORM_SKIP_LAST needs GAT_NORM_LAYER");
+    if (flags != 0 && !(std::isfinite(eps) && eps > 0.f)) return fail(GAT_E_INVALID, "gat_set_norm: eps must be finite and > 0");
+    GAT_LAYOUT_OPEN(c, "gat_set_norm");
+    if (flags == 0 && c->res.norm_flags == 0) return 0;      // the default: nothing is touched
+    if (flags != 0 && c->cfg.flat_lrelu_index)
+        return fail(GAT_E_UNSUPPORTED, "gat_set_norm: not with flat_lrelu_index (the reference's flat index has no meaning on the normalised row)");
+    GAT_REFUSE_DBG(c, flags != 0, "gat_set_norm", " (those kernels have no normalised form)");
+    c->res.norm_flags = flags; c->res.norm_eps = flags != 0 ? eps : 0.f;
+    return relayout(c);
+}
+// ---- edge features ------------------------------------------------------------------------------------------------
+int gat_set_edge_dim(gat_ctx* c, int32_t edge_dim) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (edge_dim < 0 || edge_dim > GAT_EDGE_DIM_MAX) return fail(GAT_E_INVALID, "gat_set_edge_dim: edge_dim must be in [0, " + std::to_string(GAT_EDGE_DIM_MAX) + "]");
+    GAT_LAYOUT_OPEN(c, "gat_set_edge_dim");
+    if (edge_dim == c->ef.dim) return 0;               // (0 on a fresh context: nothing is touched)
+    GAT_REFUSE_DBG(c, edge_dim != 0, "gat_set_edge_dim", " (those kernels have no edge-feature form)");
+    c->ef.dim = edge_dim; c->ef.ld = (edge_dim + 3) / 4 * 4;
+    return relayout(c);
+}
+static int set_edge_features_common(gat_ctx* c, const float* ea, int64_t n_edges, int32_t edge_dim, hipMemcpyKind kind) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (!c->graph.have) return fail(GAT_E_STATE, "gat_set_edge_features: set the graph first (the rows are in the order of its CSR)");
+    if (edge_dim != c->ef.dim) return fail(GAT_E_INVALID, "gat_set_edge_features: edge_dim differs from the context's (gat_set_edge_dim)");
+    if (n_edges != c->graph.n_edges) return fail(GAT_E_INVALID, "gat_set_edge_features: row count differs from the graph's edge count");
+    if (edge_dim == 0) return 0;                         // a context without the feature: nothing to copy
+    if (!ea && n_edges > 0) return fail(GAT_E_INVALID, "gat_set_edge_features: null argument");
+    const int64_t Ea = std::max<int64_t>(n_edges, 1);
+    if (!c->ef.EA) {                                        // allocated once: a later call refills the same buffer (a captured step stays valid)
+        GAT_TRY(dalloc(c, &c->ef.EA, Ea * c->ef.ld));
+        GAT_HIP(hipMemsetAsync(c->ef.EA, 0, (size_t)(Ea * c->ef.ld) * sizeof(float), c->stream));
+    }
+    if (n_edges > 0)
+        GAT_HIP(hipMemcpy2DAsync(c->ef.EA, (size_t)c->ef.ld * sizeof(float), ea, (size_t)edge_dim * sizeof(float), (size_t)edge_dim * sizeof(float),
+                                 (size_t)n_edges, kind, c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    c->ef.have = true;
+    return 0;
+}
+int gat_set_edge_features(gat_ctx* c, const float* ea, int64_t n_edges, int32_t edge_dim) {
+    return set_edge_features_common(c, ea, n_edges, edge_dim, hipMemcpyHostToDevice);
+}
+int gat_set_edge_features_device(gat_ctx* c, const float* d_ea, int64_t n_edges, int32_t edge_dim) {
+    return set_edge_features_common(c, d_ea, n_edges, edge_dim, hipMemcpyDeviceToDevice);
+}
+// ---- graph-level readout ------------------------------------------------------------------------------------------
+static int set_readout_common(gat_ctx* c, int32_t mode, const int32_t* graph_ptr, int64_t n_graphs, bool on_host) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (mode < GAT_READOUT_NONE || mode > GAT_READOUT_MAX) return fail(GAT_E_INVALID, "gat_set_readout: mode must be 0 (none), 1 (mean), 2 (sum) or 3 (max)");
+    if (mode == GAT_READOUT_NONE) return 0;              // the default: nothing is touched
+    if (readout_on(c)) return fail(GAT_E_STATE, "gat_set_readout: readout already set (create a new context)");
+    if (!c->graph.have) return fail(GAT_E_STATE, "gat_set_readout: set the graph first");
+    if (c->sup.have) return fail(GAT_E_STATE, "gat_set_readout: call it before gat_set_labels (the label, mask and head buffers are sized by it)");
+    if (c->graph.n_table != c->graph.n_rows || c->xch.comm)
+        return fail(GAT_E_UNSUPPORTED, "gat_set_readout: not on a destination-range shard or with a transport (a graph may straddle shards)");
+    if (c->cfg.flat_lrelu_index)
+        return fail(GAT_E_UNSUPPORTED, "gat_set_readout: not with flat_lrelu_index = 1 (the head would write the last layer's g itself)");
+    GAT_REFUSE_DBG(c, true, "gat_set_readout", "");
+    if (!graph_ptr) return fail(GAT_E_INVALID, "gat_set_readout: null graph_ptr");
+    if (n_graphs < 1 || n_graphs >= 0x7fffffffLL) return fail(GAT_E_INVALID, "gat_set_readout: n_graphs must be >= 1 and fit int32");
+    const int64_t N = c->graph.n_rows, G = n_graphs;
+    int32_t problem = 0; int64_t where = -1;
+    std::vector<int32_t> fetched;
+    if (on_host) {
+        GAT_TRY(graph_ptr_check_host(graph_ptr, G, N, &problem, &where));
+    } else {                                             // the same rules on the caller's device array, before anything walks it
+        GAT_TRY(graph_ptr_check_device(graph_ptr, G, N, &problem, &where, c->stream));
+    }
+    if (problem) return fail(GAT_E_INVALID, "gat_set_readout: " + graph_ptr_problem_text(problem, where, N));
+    if (!on_host) {                                      // the work list is built on the host (as the edge passes' is)
+        fetched.resize((size_t)G + 1);
+        GAT_HIP(hipMemcpy(fetched.data(), graph_ptr, (size_t)(G + 1) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    const int32_t* gp = on_host ? graph_ptr : fetched.data();
+    ReadoutPlan plan;
+    build_readout_plan(gp, G, plan);
+    const int32_t DL = c->layers.back().D;
+    GAT_TRY(dalloc(c, &c->readout.graph_ptr, G + 1));
+    GAT_TRY(dalloc(c, &c->readout.node_graph, N));
+    GAT_HIP(hipMemcpyAsync(c->readout.graph_ptr, gp, (size_t)(G + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    GAT_TRY(upload_list(c, &c->readout.items, plan.items, 4));
+    GAT_TRY(upload_list(c, &c->readout.split, plan.split, 4));
+    GAT_TRY(dalloc(c, &c->readout.part, (int64_t)std::max<int32_t>(plan.n_parts, 1) * DL));
+    if (mode == GAT_READOUT_MAX) {
+        GAT_TRY(dalloc(c, &c->readout.part_arg, (int64_t)std::max<int32_t>(plan.n_parts, 1) * DL));
+        GAT_TRY(dalloc(c, &c->readout.argmax, G * DL));
+    }
+    GAT_TRY(dalloc(c, &c->readout.P, G * DL));
+    GAT_TRY(dalloc(c, &c->readout.gP, G * DL));
+    GAT_TRY(launch_node_graph(c->readout.graph_ptr, G, N, c->readout.node_graph, c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));            // (the host lists go out of scope)
+    c->readout.n_items = plan.n_items; c->readout.n_split = plan.n_split;
+    c->readout.mode = mode; c->readout.n_graphs = G;
+    c->head.y_valid = false;                                  // the head's outputs change shape: nothing of an earlier forward stays
+    graph_drop(c);
+    return 0;
+}
+int gat_set_readout(gat_ctx* c, int32_t mode, const int32_t* graph_ptr, int64_t n_graphs) {
+    return set_readout_common(c, mode, graph_ptr, n_graphs, true);
+}
+int gat_set_readout_device(gat_ctx* c, int32_t mode, const int32_t* d_graph_ptr, int64_t n_graphs) {
+    return set_readout_common(c, mode, d_graph_ptr, n_graphs, false);
+}
+int gat_readout_info(gat_ctx* c, int32_t* mode, int64_t* n_graphs) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (mode) *mode = c->readout.mode;
+    if (n_graphs) *n_graphs = c->readout.n_graphs;
+    return 0;
+}
+// ---- dropout ---------------------------------------------------------------------------------------------------
+int gat_set_dropout(gat_ctx* c, float feat_p, float attn_p, uint64_t seed, uint64_t first_step) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (!(feat_p >= 0.f && feat_p < 1.f)) return fail(GAT_E_INVALID, "gat_set_dropout: feat_p must be in [0, 1)");
+    if (!(attn_p >= 0.f && attn_p < 1.f)) return fail(GAT_E_INVALID, "gat_set_dropout: attn_p must be in [0, 1)");
+    GAT_REFUSE_DBG(c, feat_p > 0.f || attn_p > 0.f, "gat_set_dropout", " (those kernels have no dropout form)");
+    GAT_TRY(ensure_drop_step(c));
+    GAT_HIP(hipMemcpyAsync(c->drop.step, &first_step, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    graph_drop(c);                                       // a captured step holds the other kernel sequence
+    c->drop.pf = feat_p; c->drop.pa = attn_p; c->drop.seed = seed;
+    return ensure_drop_buffers(c);
+}
+int gat_set_dropedge(gat_ctx* c, float edge_p, int32_t flags) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (!(edge_p >= 0.f && edge_p < 1.f)) return fail(GAT_E_INVALID, "gat_set_dropedge: edge_p must be in [0, 1)");
+    if (flags & ~(GAT_DROPEDGE_KEEP_SELF | GAT_DROPEDGE_SHARED_LAYERS)) return fail(GAT_E_INVALID, "gat_set_dropedge: unknown flag bits");
+    GAT_REFUSE_DBG(c, edge_p > 0.f, "gat_set_dropedge", " (those kernels have no dropout form)");
+    GAT_TRY(ensure_drop_step(c));
+    graph_drop(c);                                       // a captured step holds the other kernel sequence
+    c->drop.edge_p = edge_p; c->drop.edge_flags = flags;
+    return 0;
+}
+int gat_set_training(gat_ctx* c, int32_t training) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (training != 0 && training != 1) return fail(GAT_E_INVALID, "gat_set_training: 0 (eval) or 1 (training)");
+    if (c->drop.training != (training == 1)) graph_drop(c);
+    c->drop.training = training == 1;
+    return 0;
+}
+int gat_dropout_step(gat_ctx* c, uint64_t* step) {
+    if (!c || !step) return fail(GAT_E_INVALID, "null argument");
+    *step = 0;
+    if (!c->drop.step) return 0;
+    GAT_HIP(hipMemcpyAsync(step, c->drop.step, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+}  // extern "C"

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "gatv2_abi.h"
@@ -217,6 +218,41 @@ struct EdgeBwdArgs {
 //   rule: without an active mask those run with T = Te = 0, scale = 1 (drop->step must still point at the device counter).
 int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s, const DropArgs* drop = nullptr, const float* pe = nullptr, float* gpe = nullptr);
 struct EdgeBwdDropArgs : EdgeBwdArgs { DropArgs drop; const float* pe = nullptr; float* gpe = nullptr; };
+// The work-list fields of EdgeFwdArgs / EdgeBwdArgs from a WorkList and its device copies (part_mz: the forward's only)
+template <class Args> void set_work_list(Args& a, const WorkList& w, const int4* items, const int4* slot_info, float* part_acc, float* part_mz = nullptr) {
+    a.items = items; a.n_items = w.n_items; a.slot_info = slot_info; a.n_slots = w.n_slots; a.n_split = w.n_split; a.part_acc = part_acc;
+    if constexpr (std::is_same<Args, EdgeFwdArgs>::value) a.part_mz = part_mz;
+}
+// Temporary device buffers of one call, freed at scope exit: declare it before the call's last synchronisation of its stream.
+struct Scratch {
+    std::vector<void*> bufs;
+    ~Scratch() { for (void* p : bufs) (void)hipFree(p); }
+    template <class T> int get(T** out, int64_t count) {
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, (size_t)(count > 0 ? count : 1) * sizeof(T));
+        if (e != hipSuccess) return fail(GAT_E_NOMEM, std::string("op scratch: ") + hipGetErrorString(e));
+        bufs.push_back(p); *out = (T*)p;
+        return 0;
+    }
+};
+// Device work list of a caller-provided CSR, its buffers in a Scratch (the op-level entry points have no context)
+struct ScratchWorkList {
+    WorkList w; int4* items = nullptr; int4* slot_info = nullptr; float* part_acc = nullptr; float* part_mz = nullptr;
+    int build(Scratch& t, const int32_t* d_row_ptr, int64_t n, int32_t hd, int32_t h, hipStream_t s) {
+        std::vector<int32_t> rp(n + 1);
+        GAT_HIP(hipMemcpyAsync(rp.data(), d_row_ptr, (n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        GAT_HIP(hipStreamSynchronize(s));
+        build_worklist(rp.data(), n, w);
+        GAT_TRY(t.get(&items, w.n_items));
+        GAT_TRY(t.get(&slot_info, w.n_slots + w.n_split));
+        GAT_TRY(t.get(&part_acc, (int64_t)(w.n_slots > 0 ? w.n_slots : 1) * hd));
+        GAT_TRY(t.get(&part_mz, (int64_t)(w.n_slots > 0 ? w.n_slots : 1) * 2 * h));
+        if (w.n_items) GAT_HIP(hipMemcpyAsync(items, w.items.data(), w.items.size() * 4, hipMemcpyHostToDevice, s));
+        if (w.n_slots) GAT_HIP(hipMemcpyAsync(slot_info, w.slot_info.data(), w.slot_info.size() * 4, hipMemcpyHostToDevice, s));
+        GAT_HIP(hipStreamSynchronize(s));
+        return 0;
+    }
+};
 // Last layer, fused per row (gat_step): forward edge pass + output head + backward edge pass of every WHOLE row in one kernel
 // (edge_last_fused_kernel); f / b as for the separate passes (f.items / f.n_items: the whole-row items only; b.ga_partial /
 // b.ga_blocks from edge_last_fused_blocks), gh_out = the [n_rows][gh_stride] node records the pull pass reads.
@@ -269,7 +305,7 @@ int build_heavy_list(const int32_t* d_src_ptr, int64_t n_table, int64_t n_edges,
 // the gathered tables are addressed with 32-bit byte offsets (n_table * H*D * 4 < 4 GiB: edge_fast_path; node records: n_rows < 2^26).
 constexpr int64_t kPullPad = 32;
 // The device-side source-major index of one graph, everything the second pass walks beside the records or rows themselves.  Built
-// once per graph by gat_abi.hip ensure_buffers (which owns the allocations) from build_csc / build_csc_dst / build_heavy_list.
+// once per graph by ensure_buffers in gat_abi.hip (which owns the allocations) from build_csc / build_csc_dst / build_heavy_list.
 struct SourceIndex {
     const int32_t* src_ptr = nullptr;   // [n_table + 1] first slot of every table row
     const int32_t* cdst = nullptr;      // [slot_capacity] destination row of every slot (record path), or null
@@ -372,7 +408,7 @@ int launch_pack_result(const float* loss, const int32_t* correct, float* dst3, h
 // Deferred slab reductions.  Between reduce_batch_begin() and reduce_batch_flush() (same host thread) launch_reduce_gradw /
 // launch_reduce_partials_add queue their job instead of launching it, and the flush runs all of them — plus the result
 // pack, if asked for — as ONE kernel: on Cora / Pubmed-size graphs every launch is ~5 us of a ~250 us step.  The slabs
-// of a queued job must stay untouched until the flush (per-layer scratch regions: gat_abi.hip).
+// of a queued job must stay untouched until the flush (per-layer scratch regions: ensure_buffers in gat_abi.hip).
 struct ReduceJob { const float* slabs; float* out; int64_t width; int32_t nslabs, HD, F, c_base, block0; };   // HD == 0: out[idx]
 struct ReduceBatch {
     ReduceJob jobs[8]; int32_t n, blocks;

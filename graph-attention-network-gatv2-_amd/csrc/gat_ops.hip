@@ -18,18 +18,6 @@
 namespace gat {
 namespace {
 
-struct Scratch {
-    std::vector<void*> p;
-    ~Scratch() { for (void* q : p) (void)hipFree(q); }
-    int get(float** out, int64_t n) {
-        void* q = nullptr;
-        const hipError_t e = hipMalloc(&q, (size_t)std::max<int64_t>(n, 1) * sizeof(float));
-        if (e != hipSuccess) return fail(GAT_E_NOMEM, std::string("op scratch: ") + hipGetErrorString(e));
-        p.push_back(q); *out = (float*)q;
-        return 0;
-    }
-};
-
 __device__ __forceinline__ float lrelu_f(float v, float s) { return v > 0.f ? v : v * s; }
 
 constexpr int kBlock = 256;
@@ -486,6 +474,140 @@ int gat_op_preact_gradient(int64_t n, float slope, int32_t in_dim, const float* 
     GAT_HIP(hipGetLastError());
     GAT_HIP(hipStreamSynchronize(s));
     return 0;
+}
+
+int gat_op_csr_to_coo(const int32_t* d_row_ptr, const int32_t* d_col_idx, int32_t* d_src, int32_t* d_dst,
+                      int64_t n_rows, int64_t n_edges, void* stream) {
+    if (!d_row_ptr || !d_src || !d_dst || (!d_col_idx && n_edges > 0)) return fail(GAT_E_INVALID, "null argument");
+    return launch_csr_to_coo(d_row_ptr, d_col_idx, d_src, d_dst, n_rows, n_edges, 0, (hipStream_t)stream);
+}
+
+int gat_op_layer_forward(const int32_t* d_row_ptr, const int32_t* d_col_idx, const float* d_x, const float* d_w,
+                         const float* d_a, float* d_attn_coeff, float* d_hpre, float* d_hout, int64_t n, int64_t e,
+                         int32_t f, int32_t h, int32_t d, int32_t is_last, float slope, void* stream) {
+    if (!d_row_ptr || !d_x || !d_w || !d_a || !d_attn_coeff || !d_hpre || !d_hout) return fail(GAT_E_INVALID, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int HD = h * d;
+    Scratch t; ScratchWorkList wl;
+    float *PL, *PR, *alpha, *ms, *zs;
+    GAT_TRY(t.get(&PL, n * HD)); GAT_TRY(t.get(&PR, n * HD)); GAT_TRY(t.get(&alpha, e * h));
+    GAT_TRY(t.get(&ms, n * h)); GAT_TRY(t.get(&zs, n * h));
+    GAT_TRY(launch_project(d_x, d_w, PL, PR, n, f, HD, kPartBoth, false, nullptr, 0, s));
+    EdgeFwdArgs a{};
+    a.row_ptr = d_row_ptr; a.col_idx = d_col_idx; a.PL = PL; a.PR = PR; a.a = d_a; a.alpha = alpha;
+    a.mstat = ms; a.zstat = zs;
+    a.hpre = d_hpre; a.hout = d_hout; a.n_rows = n; a.n_table = n; a.H = h; a.D = d; a.is_last = is_last; a.slope = slope;
+    GAT_TRY(wl.build(t, d_row_ptr, n, HD, h, s));
+    set_work_list(a, wl.w, wl.items, wl.slot_info, wl.part_acc, wl.part_mz);
+    GAT_TRY(launch_edge_forward(a, s));
+    GAT_TRY(launch_transpose_eh_to_he(alpha, d_attn_coeff, e, h, s));
+    GAT_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int gat_op_layer_backward(const int32_t* d_row_ptr, const int32_t* d_col_idx, const float* d_x, const float* d_w,
+                          const float* d_a, const float* d_attn_coeff, const float* d_hpre, const float* d_g,
+                          float* d_grad_w, float* d_grad_a, const float* d_hpre_prev, float* d_g_prev, int64_t n,
+                          int64_t e, int32_t f, int32_t h, int32_t d, float slope, void* stream) {
+    if (!d_row_ptr || !d_x || !d_w || !d_a || !d_attn_coeff || !d_hpre || !d_g || !d_grad_w || !d_grad_a)
+        return fail(GAT_E_INVALID, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int HD = h * d;
+    Scratch t; ScratchWorkList wl;
+    if (!d_col_idx) {                  // e == 0: the kernels still clamp their index prefetch to edge 0 — give them one to read
+        int32_t* dummy = nullptr;
+        GAT_TRY(t.get(&dummy, 1));
+        GAT_HIP(hipMemsetAsync(dummy, 0, sizeof(int32_t), s));
+        d_col_idx = dummy;
+    }
+    float *PL, *PR, *alpha, *gPL, *gPR, *gap, *scr;
+    GAT_TRY(t.get(&PL, n * HD)); GAT_TRY(t.get(&PR, n * HD)); GAT_TRY(t.get(&alpha, e * h));
+    GAT_TRY(t.get(&gPL, n * HD)); GAT_TRY(t.get(&gPR, n * HD)); GAT_TRY(t.get(&gap, (int64_t)kGaPartialRows * HD));    // capacity: >= any edge_backward_blocks()
+    GAT_TRY(t.get(&scr, grad_w_scratch_floats(n, f, HD)));
+    GAT_TRY(launch_project(d_x, d_w, PL, PR, n, f, HD, kPartBoth, false, nullptr, 0, s));
+    GAT_TRY(launch_transpose_he_to_eh(d_attn_coeff, alpha, e, h, s));
+    GAT_TRY(wl.build(t, d_row_ptr, n, HD, h, s));
+    // softmax stats of this layer (the fast-path backward recomputes alpha from them): one
+    // forward edge pass into scratch outputs
+    float *ms, *zs, *hp_tmp, *ho_tmp;
+    GAT_TRY(t.get(&ms, n * h)); GAT_TRY(t.get(&zs, n * h)); GAT_TRY(t.get(&hp_tmp, n * HD)); GAT_TRY(t.get(&ho_tmp, n * HD));
+    {
+        EdgeFwdArgs fa{};
+        fa.row_ptr = d_row_ptr; fa.col_idx = d_col_idx; fa.PL = PL; fa.PR = PR; fa.a = d_a;
+        fa.alpha = edge_fast_path(h, d, n) ? nullptr : alpha; fa.hpre = hp_tmp; fa.hout = ho_tmp; fa.mstat = ms; fa.zstat = zs;
+        fa.n_rows = n; fa.n_table = n; fa.H = h; fa.D = d; fa.is_last = 0; fa.slope = slope;
+        set_work_list(fa, wl.w, wl.items, wl.slot_info, wl.part_acc, wl.part_mz);
+        GAT_TRY(launch_edge_forward(fa, s));
+    }
+    GAT_HIP(hipMemsetAsync(gPL, 0, (size_t)n * HD * sizeof(float), s));
+    EdgeBwdArgs a{};
+    a.mstat = ms; a.zstat = zs;
+    a.row_ptr = d_row_ptr; a.col_idx = d_col_idx; a.PL = PL; a.PR = PR; a.a = d_a; a.alpha = alpha;
+    a.hpre = d_hpre; a.g = d_g; a.gPL = gPL; a.gPR = gPR; a.ge = nullptr; a.ga_partial = gap;
+    a.n_rows = n; a.n_table = n; a.H = h; a.D = d; a.slope = slope;
+    set_work_list(a, wl.w, wl.items, wl.slot_info, wl.part_acc, wl.part_mz);
+    a.ga_blocks = edge_backward_blocks(a);
+    GAT_TRY(launch_edge_backward(a, s));
+    GAT_TRY(launch_reduce_partials_add(gap, a.ga_blocks, HD, d_grad_a, s));
+    GAT_TRY(launch_grad_w(gPL, gPR, d_x, d_grad_w, scr, n, f, HD, kPartBoth, s));
+    if (d_hpre_prev && d_g_prev) GAT_TRY(launch_grad_x(gPL, gPR, d_w, d_hpre_prev, d_g_prev, n, f, HD, slope, s));
+    GAT_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+// The two kernels on caller-owned device pointers.  The graph_ptr is checked on the device before anything reads through it.
+static int op_readout_check(const char* who, const int32_t* d_graph_ptr, int64_t n_graphs, int64_t n_rows, int32_t width, int32_t mode, hipStream_t s) {
+    if (!d_graph_ptr) return fail(GAT_E_INVALID, std::string(who) + ": null argument");
+    if (mode < GAT_READOUT_MEAN || mode > GAT_READOUT_MAX) return fail(GAT_E_INVALID, std::string(who) + ": mode must be 1 (mean), 2 (sum) or 3 (max)");
+    if (n_graphs < 1 || n_graphs >= 0x7fffffffLL || n_rows < 0 || n_rows >= 0x7fffffffLL || width < 1) return fail(GAT_E_INVALID, std::string(who) + ": bad sizes");
+    int32_t problem = 0; int64_t where = -1;
+    GAT_TRY(graph_ptr_check_device(d_graph_ptr, n_graphs, n_rows, &problem, &where, s));
+    if (problem) return fail(GAT_E_INVALID, std::string(who) + ": " + graph_ptr_problem_text(problem, where, n_rows));
+    return 0;
+}
+int gat_op_readout_forward(const float* d_x, int64_t x_stride, const int32_t* d_graph_ptr, int64_t n_graphs, int64_t n_rows,
+                           int32_t width, int32_t mode, float* d_pooled, int32_t* d_argmax, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    GAT_TRY(op_readout_check("gat_op_readout_forward", d_graph_ptr, n_graphs, n_rows, width, mode, s));
+    if ((!d_x && n_rows > 0) || !d_pooled || (mode == GAT_READOUT_MAX && !d_argmax)) return fail(GAT_E_INVALID, "gat_op_readout_forward: null argument");
+    if (x_stride < width) return fail(GAT_E_INVALID, "gat_op_readout_forward: x_stride below width");
+    std::vector<int32_t> gp((size_t)n_graphs + 1);
+    GAT_HIP(hipMemcpy(gp.data(), d_graph_ptr, gp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    ReadoutPlan plan;
+    build_readout_plan(gp.data(), n_graphs, plan);
+    Scratch tmp;
+    int4 *items = nullptr, *split = nullptr; float* part = nullptr; int32_t* part_arg = nullptr;
+    GAT_TRY(tmp.get(&items, plan.n_items)); GAT_TRY(tmp.get(&split, plan.n_split));
+    GAT_TRY(tmp.get(&part, (int64_t)plan.n_parts * width)); GAT_TRY(tmp.get(&part_arg, (int64_t)plan.n_parts * width));
+    GAT_HIP(hipMemcpyAsync(items, plan.items.data(), plan.items.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (plan.n_split > 0) GAT_HIP(hipMemcpyAsync(split, plan.split.data(), plan.split.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    ReadoutFwdArgs a{};
+    a.x = d_x ? d_x : d_pooled; a.x_stride = x_stride; a.graph_ptr = d_graph_ptr;      // (n_rows == 0: no item has a row to load)
+    a.items = items; a.n_items = plan.n_items; a.split = split; a.n_split = plan.n_split;
+    a.pooled = d_pooled; a.argmax = d_argmax; a.part = part; a.part_arg = part_arg; a.width = width; a.mode = mode;
+    int rc = launch_readout_forward(a, s);
+    const hipError_t e = hipStreamSynchronize(s);        // before the scratch is freed
+    if (rc == 0 && e != hipSuccess) rc = fail((int)e, std::string("gat_op_readout_forward: ") + hipGetErrorString(e));
+    return rc;
+}
+int gat_op_readout_backward(const float* d_gpooled, const int32_t* d_graph_ptr, int64_t n_graphs, int64_t n_rows, int32_t width,
+                            int32_t mode, const int32_t* d_argmax, float* d_gh, int64_t gh_stride, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    GAT_TRY(op_readout_check("gat_op_readout_backward", d_graph_ptr, n_graphs, n_rows, width, mode, s));
+    if (!d_gpooled || (!d_gh && n_rows > 0) || (mode == GAT_READOUT_MAX && !d_argmax)) return fail(GAT_E_INVALID, "gat_op_readout_backward: null argument");
+    if (gh_stride < width) return fail(GAT_E_INVALID, "gat_op_readout_backward: gh_stride below width");
+    if (n_rows == 0) return 0;
+    Scratch tmp;
+    int32_t* node_graph = nullptr;
+    GAT_TRY(tmp.get(&node_graph, n_rows));
+    GAT_TRY(launch_node_graph(d_graph_ptr, n_graphs, n_rows, node_graph, s));
+    ReadoutBwdArgs a{};
+    a.gpooled = d_gpooled; a.argmax = d_argmax; a.graph_ptr = d_graph_ptr; a.node_graph = node_graph;
+    a.gh = d_gh; a.gh_stride = gh_stride; a.n_rows = n_rows; a.width = width; a.mode = mode;
+    int rc = launch_readout_backward(a, s);
+    const hipError_t e = hipStreamSynchronize(s);
+    if (rc == 0 && e != hipSuccess) rc = fail((int)e, std::string("gat_op_readout_backward: ") + hipGetErrorString(e));
+    return rc;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 """tests/test_edge_shapes.py without a GPU: which kernel instantiation each of its 112 cases reaches (COVERAGE, restated from pick_fwd /
-pick_bwd of csrc/gat_edge_kernels.hip and the record-path rule of csrc/gat_abi.hip — documentation that cannot silently shrink, it
+pick_bwd of csrc/gat_edge_kernels.hip and the record-path rule of csrc/gat_abi.hip (ensure_buffers) — documentation that cannot silently shrink, it
 inspects no binary), the `alpha` key of tests/step_ref.py, and — a condition, not a skip — a parameter seed clear of the
 LeakyReLU kinks among the first 40 for every case of the matrix."""
 import re

@@ -122,7 +122,7 @@ def test_table_of_4gib_says_it_left_the_fast_path(pkg):
 
 def test_replicated_input_shard_with_long_k_projects_both_halves(pkg):
     """n_rows = 500 takes the split-K kernel (N = H*D columns, K = 200), the 33,000-row table half does not: the scratch
-    must hold the former although it is the smaller launch (gat_abi.hip:348)."""
+    must hold the former although it is the smaller launch (ensure_buffers in gat_abi.hip)."""
     A = pkg.abi
     rng = np.random.default_rng(6)
     n_table, n, f, c = 33000, 500, 200, 4
