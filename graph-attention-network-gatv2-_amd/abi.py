@@ -222,6 +222,13 @@ def _declare(lib: C.CDLL) -> None:
         "gat_target_count": [vp, vp, i64, P(i64)],
         "gat_op_readout_forward": [vp, i64, vp, i64, i64, i32, i32, vp, vp, vp],
         "gat_op_readout_backward": [vp, vp, i64, i64, i32, i32, vp, vp, i64, vp],
+        "gat_op_dense_scratch_floats": [i32, i64, i32, i32, i32, P(i64)],
+        "gat_op_dense_project": [vp, i32, vp, i64, i32, i32, i32, i32, vp, vp, vp, i64, vp, C.c_char_p, i32],
+        "gat_op_dense_grad_x": [vp, vp, vp, vp, vp, i64, i32, i32, f32, vp, C.c_char_p, i32],
+        "gat_op_dense_grad_w": [vp, vp, vp, i32, vp, vp, i64, i64, i32, i32, i32, vp, C.c_char_p, i32],
+        "gat_op_dense_project_res": [vp, i32, vp, vp, i64, i32, i32, vp, C.c_char_p, i32],
+        "gat_op_dense_grad_wres": [vp, vp, i32, vp, vp, i64, i64, i32, i32, vp, C.c_char_p, i32],
+        "gat_op_dense_grad_x_res": [vp, vp, vp, i64, i32, i32, vp, C.c_char_p, i32],
         "gat_set_training": [vp, i32],
         "gat_dropout_step": [vp, P(C.c_uint64)],
         "gat_set_shard_bounds": [vp, i32, vp],
@@ -793,6 +800,57 @@ def op_readout_backward(d_gpooled: int, d_graph_ptr: int, n_graphs: int, n_rows:
     _chk(load_library().gat_op_readout_backward(C.c_void_p(d_gpooled or None), C.c_void_p(d_graph_ptr or None), n_graphs, n_rows, width,
                                                 readout_mode(mode), C.c_void_p(d_argmax or None), C.c_void_p(d_gh or None), gh_stride,
                                                 C.c_void_p(stream or None)))
+
+
+PART_BOTH, PART_LEFT, PART_RIGHT = 0, 1, 2       # the `part` of the dense seams
+DENSE_SCRATCH_PROJECT, DENSE_SCRATCH_GRAD_W = 0, 1
+
+
+def _p(ptr: int):
+    return C.c_void_p(ptr or None)
+
+
+def _dense(name: str, *args) -> str:
+    """One gat_op_dense_* call on device pointers; -> the template name of the kernel the launcher picked."""
+    buf = C.create_string_buffer(96)
+    _chk(getattr(load_library(), name)(*args, buf, 96))
+    return buf.value.decode()
+
+
+def op_dense_scratch_floats(kind: int, n_rows: int, F: int, HD: int, part: int = PART_BOTH) -> int:
+    out = C.c_int64()
+    _chk(load_library().gat_op_dense_scratch_floats(kind, n_rows, F, HD, part, C.byref(out)))
+    return out.value
+
+
+def op_dense_project(d_x: int, ldx: int, d_w: int, n_rows: int, F: int, HD: int, part: int, pl_bf16: bool, d_pl: int, d_pr: int,
+                     d_scratch: int = 0, scratch_floats: int = 0, stream: int = 0) -> str:
+    return _dense("gat_op_dense_project", _p(d_x), ldx, _p(d_w), n_rows, F, HD, part, int(pl_bf16), _p(d_pl), _p(d_pr), _p(d_scratch),
+                  scratch_floats, _p(stream))
+
+
+def op_dense_grad_x(d_gpl: int, d_gpr: int, d_w: int, d_hpre_prev: int, d_gprev: int, n_rows: int, F: int, HD: int, slope: float,
+                    stream: int = 0) -> str:
+    return _dense("gat_op_dense_grad_x", _p(d_gpl), _p(d_gpr), _p(d_w), _p(d_hpre_prev), _p(d_gprev), n_rows, F, HD, slope, _p(stream))
+
+
+def op_dense_grad_w(d_gpl: int, d_gpr: int, d_x: int, ldx: int, d_grad_w: int, d_scratch: int, scratch_floats: int, n_rows: int, F: int,
+                    HD: int, part: int, stream: int = 0) -> str:
+    return _dense("gat_op_dense_grad_w", _p(d_gpl), _p(d_gpr), _p(d_x), ldx, _p(d_grad_w), _p(d_scratch), scratch_floats, n_rows, F, HD,
+                  part, _p(stream))
+
+
+def op_dense_project_res(d_x: int, ldx: int, d_wres: int, d_r: int, n_rows: int, F: int, HD: int, stream: int = 0) -> str:
+    return _dense("gat_op_dense_project_res", _p(d_x), ldx, _p(d_wres), _p(d_r), n_rows, F, HD, _p(stream))
+
+
+def op_dense_grad_wres(d_g: int, d_x: int, ldx: int, d_grad_wres: int, d_scratch: int, scratch_floats: int, n_rows: int, F: int, HD: int,
+                       stream: int = 0) -> str:
+    return _dense("gat_op_dense_grad_wres", _p(d_g), _p(d_x), ldx, _p(d_grad_wres), _p(d_scratch), scratch_floats, n_rows, F, HD, _p(stream))
+
+
+def op_dense_grad_x_res(d_g: int, d_wres: int, d_gx: int, n_rows: int, F: int, HD: int, stream: int = 0) -> str:
+    return _dense("gat_op_dense_grad_x_res", _p(d_g), _p(d_wres), _p(d_gx), n_rows, F, HD, _p(stream))
 
 
 def _coo_sizes(n_in: int, n_rows: int, n_table: Optional[int], flags: int) -> int:

@@ -129,21 +129,34 @@ constexpr int kKC = 128;          // K chunk resident in LDS
 }  // namespace
 
 // blocks of a kernel (256 threads unless said otherwise) resident on the whole chip (occupancy API incl. dynamic LDS), cached
+// GAT_RESIDENT_CAP=<n> (tests): an upper bound on the answer, so that a graph of a few hundred rows walks several tiles per block and
+// cuts grad_w into few node chunks — the role GAT_SEG_EDGES=16 plays for the edge kernels.  Every caller sizes its grid AND its
+// partial buffers from this one function, so the bound can only make a launch smaller.  Unset: the occupancy figure as it is.
+static int64_t resident_capped(int64_t blocks) {
+    static const int64_t cap = [] { const char* e = choice_env("GAT_RESIDENT_CAP"); return e ? (int64_t)atoll(e) : (int64_t)0; }();
+    if (cap > 0 && blocks > cap) blocks = cap;
+    return blocks < 1 ? 1 : blocks;
+}
 int64_t resident_blocks(const void* fn, size_t dyn_lds, int threads) {
     static std::mutex mu;
     static std::map<std::pair<const void*, size_t>, int64_t> cache;
     std::lock_guard<std::mutex> lock(mu);
     const auto key = std::make_pair(fn, dyn_lds);
     auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
+    if (it != cache.end()) return resident_capped(it->second);
     int per_cu = 0, dev = 0, cus = 256;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, dyn_lds) != hipSuccess || per_cu < 1) per_cu = 1;
     if (per_cu > 8) per_cu = 8;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     (void)hipGetLastError();
-    return cache[key] = (int64_t)per_cu * (cus > 0 ? cus : 256);
+    return resident_capped(cache[key] = (int64_t)per_cu * (cus > 0 ? cus : 256));
 }
+
+// the template name of the row / tile kernel this host thread launched last (gat_op_dense_*: which branch a case reached)
+static thread_local const char* t_dense_kernel = "";
+const char* dense_last_kernel() { return t_dense_kernel; }
+void dense_last_kernel_clear() { t_dense_kernel = ""; }
 
 // dynamic LDS beyond 64 KiB must be allowed per kernel AND per device (a process may drive several); cheap after the first call
 static void allow_big_lds(const void* fn) {
@@ -713,6 +726,7 @@ int run_rowgemm(const AS& as, const BS& bs, const EP& ep, int64_t M, int32_t N, 
         if (res < 1) res = 1;                                                                                 \
         const dim3 grid((unsigned)(nt_ < res ? nt_ : res), (unsigned)ny);                                     \
         hipLaunchKernelGGL(kern, grid, dim3(W_ * 64), lds3, s, as, bs, ep, M, N, K);                           \
+        t_dense_kernel = "rowgemm_x3_kernel<" #NT_ ", " #W_ ", " #V_ ">";                                     \
     }
 #define GAT_ROWGEMM_X3_NT(W_, V_)                                                                             \
     { if (NT == 4) GAT_ROWGEMM_X3(4, W_, V_) else if (NT == 2) GAT_ROWGEMM_X3(2, W_, V_) else GAT_ROWGEMM_X3(1, W_, V_) }
@@ -738,6 +752,7 @@ int run_rowgemm(const AS& as, const BS& bs, const EP& ep, int64_t M, int32_t N, 
         const int64_t res = resident_blocks((const void*)kern, lds);                                          \
         const dim3 grid((unsigned)(ntiles < res ? ntiles : res), (unsigned)((N + NW - 1) / NW));              \
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, as, bs, ep, M, N, K);                                \
+        t_dense_kernel = "rowgemm_pipe_kernel<" #NT_ ">";                                                     \
     }
             if (NT == 2) GAT_ROWGEMM_PIPE(2) else GAT_ROWGEMM_PIPE(1)
 #undef GAT_ROWGEMM_PIPE
@@ -753,6 +768,7 @@ int run_rowgemm(const AS& as, const BS& bs, const EP& ep, int64_t M, int32_t N, 
         const int64_t res = resident_blocks((const void*)kern, lds);                                          \
         const dim3 grid((unsigned)(ntiles < res ? ntiles : res), (unsigned)((N + NW - 1) / NW));              \
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, as, bs, ep, M, N, K, kc_lds);                        \
+        t_dense_kernel = "rowgemm_kernel<" #NT_ ", " #V_ ">";                                                 \
     }
     if (vec4) { if (NT == 4) GAT_ROWGEMM(4, true) else if (NT == 2) GAT_ROWGEMM(2, true) else GAT_ROWGEMM(1, true) }
     else { if (NT == 4) GAT_ROWGEMM(4, false) else if (NT == 2) GAT_ROWGEMM(2, false) else GAT_ROWGEMM(1, false) }
@@ -1146,17 +1162,17 @@ int launch_project(const float* X, const float* W, float* PL_rows, float* PR, in
 #define GAT_ABLATE_ARG
 #endif
             if (nt == 4) {
-                if (vec4) hipLaunchKernelGGL((project_splitk_x3_kernel<true, 4>), grid3, dim3(256), lds, s, as, bs, scratch, n_rows, N, F GAT_ABLATE_ARG);
-                else hipLaunchKernelGGL((project_splitk_x3_kernel<false, 4>), grid3, dim3(256), lds, s, as, bs, scratch, n_rows, N, F GAT_ABLATE_ARG);
+                if (vec4) { hipLaunchKernelGGL((project_splitk_x3_kernel<true, 4>), grid3, dim3(256), lds, s, as, bs, scratch, n_rows, N, F GAT_ABLATE_ARG); t_dense_kernel = "project_splitk_x3_kernel<true, 4>"; }
+                else { hipLaunchKernelGGL((project_splitk_x3_kernel<false, 4>), grid3, dim3(256), lds, s, as, bs, scratch, n_rows, N, F GAT_ABLATE_ARG); t_dense_kernel = "project_splitk_x3_kernel<false, 4>"; }
             } else {
-                if (vec4) hipLaunchKernelGGL((project_splitk_x3_kernel<true, 2>), grid3, dim3(256), lds, s, as, bs, scratch, n_rows, N, F GAT_ABLATE_ARG);
-                else hipLaunchKernelGGL((project_splitk_x3_kernel<false, 2>), grid3, dim3(256), lds, s, as, bs, scratch, n_rows, N, F GAT_ABLATE_ARG);
+                if (vec4) { hipLaunchKernelGGL((project_splitk_x3_kernel<true, 2>), grid3, dim3(256), lds, s, as, bs, scratch, n_rows, N, F GAT_ABLATE_ARG); t_dense_kernel = "project_splitk_x3_kernel<true, 2>"; }
+                else { hipLaunchKernelGGL((project_splitk_x3_kernel<false, 2>), grid3, dim3(256), lds, s, as, bs, scratch, n_rows, N, F GAT_ABLATE_ARG); t_dense_kernel = "project_splitk_x3_kernel<false, 2>"; }
             }
 #undef GAT_ABLATE_ARG
         } else {
             const size_t lds = (size_t)(128 * 128) * sizeof(float);
-            if (vec4) hipLaunchKernelGGL(project_splitk_kernel<true>, grid, dim3(256), lds, s, as, bs, scratch, n_rows, N, F);
-            else hipLaunchKernelGGL(project_splitk_kernel<false>, grid, dim3(256), lds, s, as, bs, scratch, n_rows, N, F);
+            if (vec4) { hipLaunchKernelGGL(project_splitk_kernel<true>, grid, dim3(256), lds, s, as, bs, scratch, n_rows, N, F); t_dense_kernel = "project_splitk_kernel<true>"; }
+            else { hipLaunchKernelGGL(project_splitk_kernel<false>, grid, dim3(256), lds, s, as, bs, scratch, n_rows, N, F); t_dense_kernel = "project_splitk_kernel<false>"; }
         }
         const int64_t rb = std::min<int64_t>((n_rows * N + 255) / 256, 4096);
         if (pl_bf16) hipLaunchKernelGGL(project_reduce_kernel<EpiProject<true>>, dim3((unsigned)rb), dim3(256), 0, s, scratch, ksplit, n_rows, N, EpiProject<true>{PL_rows, PR, HD, j0});
@@ -1207,6 +1223,7 @@ static int grad_w_slabs(const float* gPL_rows, const float* gPR, const float* X,
     do {                                                                                                                    \
         if (grad_w_x3()) hipLaunchKernelGGL((gradw_x3_kernel<V_, WM_, BN_>), grid, dim3(256), 0, s, gPL_rows, gPR, X, scratch, n_rows, HD, F, kchunk, c_base, M, ldx); \
         else hipLaunchKernelGGL((gradw_kernel<V_, WM_, BN_>), grid, dim3(256), 0, s, gPL_rows, gPR, X, scratch, n_rows, HD, F, kchunk, c_base, M, ldx); \
+        t_dense_kernel = grad_w_x3() ? "gradw_x3_kernel<" #V_ ", " #WM_ ", " #BN_ ">" : "gradw_kernel<" #V_ ", " #WM_ ", " #BN_ ">";                     \
     } while (0)
     if (vec4) { if (bm == 128 && bn == 64) GAT_GRADW(true, 2, 64); else if (bm == 128) GAT_GRADW(true, 2, 128); else GAT_GRADW(true, 1, 128); }
     else { if (bm == 128 && bn == 64) GAT_GRADW(false, 2, 64); else if (bm == 128) GAT_GRADW(false, 2, 128); else GAT_GRADW(false, 1, 128); }

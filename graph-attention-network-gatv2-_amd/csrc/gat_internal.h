@@ -432,6 +432,10 @@ int launch_reduce_gradw(const float* slabs, int32_t ksplit, int32_t HD, int32_t 
 // dynamic LDS; cached).  Persistent kernels use exactly this grid: a larger one runs a second,
 // partly filled round of blocks.
 int64_t resident_blocks(const void* fn, size_t dyn_lds, int threads = 256);
+// The template name of the row / tile kernel the dense launchers below launched last on this host thread, e.g.
+// "rowgemm_x3_kernel<2, 8, true>" ("" after the clear: nothing launched) — the gat_op_dense_* seams report it.
+const char* dense_last_kernel();
+void dense_last_kernel_clear();
 
 // layout converters for taps / op-level entry points
 int launch_transpose_eh_to_he(const float* src_eh, float* dst_he, int64_t E, int32_t H, hipStream_t s);

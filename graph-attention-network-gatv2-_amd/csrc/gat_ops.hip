@@ -610,4 +610,107 @@ int gat_op_readout_backward(const float* d_gpooled, const int32_t* d_graph_ptr, 
     return rc;
 }
 
+// ---- the six dense launchers on caller-owned device pointers: one launcher per call, exactly the caller's arguments ----------------
+static int op_dense_sizes(const char* who, int64_t n_rows, int32_t F, int32_t HD) {
+    if (n_rows < 0 || n_rows >= 0x7fffffffLL || F < 1 || HD < 1) return fail(GAT_E_INVALID, std::string(who) + ": bad sizes (n_rows >= 0, F >= 1, HD >= 1)");
+    if ((int64_t)2 * HD * F >= 0x7fffffffLL) return fail(GAT_E_INVALID, std::string(who) + ": 2 * HD * F does not fit 32 bits");
+    return 0;
+}
+static int op_dense_part(const char* who, int32_t part) {
+    if (part != kPartBoth && part != kPartLeft && part != kPartRight) return fail(GAT_E_INVALID, std::string(who) + ": part must be 0 (both), 1 (left) or 2 (right)");
+    return 0;
+}
+static int op_dense_ldx(const char* who, int32_t ldx, int32_t F) {
+    if (ldx != 0 && ldx < F) return fail(GAT_E_INVALID, std::string(who) + ": ldx must be 0 or at least F");
+    return 0;
+}
+// synchronise, then hand the launcher's kernel name to the caller
+static int op_dense_finish(const char* who, int rc, hipStream_t s, char* picked, int32_t picked_cap) {
+    const hipError_t e = hipStreamSynchronize(s);
+    if (rc == 0 && e != hipSuccess) rc = fail((int)e, std::string(who) + ": " + hipGetErrorString(e));
+    if (picked != nullptr && picked_cap > 0) snprintf(picked, (size_t)picked_cap, "%s", dense_last_kernel());
+    return rc;
+}
+int gat_op_dense_scratch_floats(int32_t kind, int64_t n_rows, int32_t F, int32_t HD, int32_t part, int64_t* floats_out) {
+    if (!floats_out) return fail(GAT_E_INVALID, "gat_op_dense_scratch_floats: null argument");
+    if (kind != 0 && kind != 1) return fail(GAT_E_INVALID, "gat_op_dense_scratch_floats: kind must be 0 (project) or 1 (grad_w)");
+    GAT_TRY(op_dense_sizes("gat_op_dense_scratch_floats", n_rows, F, HD));
+    GAT_TRY(op_dense_part("gat_op_dense_scratch_floats", part));
+    *floats_out = kind == 0 ? project_scratch_floats(n_rows, F, HD, part) : grad_w_scratch_floats(n_rows, F, HD);
+    return 0;
+}
+int gat_op_dense_project(const float* d_x, int32_t ldx, const float* d_w, int64_t n_rows, int32_t F, int32_t HD, int32_t part, int32_t pl_bf16,
+                         void* d_pl, float* d_pr, float* d_scratch, int64_t scratch_floats, void* stream, char* picked, int32_t picked_cap) {
+    static const char* who = "gat_op_dense_project";
+    GAT_TRY(op_dense_sizes(who, n_rows, F, HD));
+    GAT_TRY(op_dense_part(who, part));
+    GAT_TRY(op_dense_ldx(who, ldx, F));
+    if (pl_bf16 != 0 && pl_bf16 != 1) return fail(GAT_E_INVALID, std::string(who) + ": pl_bf16 must be 0 or 1");
+    if (!d_x || !d_w || (part != kPartRight && !d_pl) || (part != kPartLeft && !d_pr)) return fail(GAT_E_INVALID, std::string(who) + ": null argument");
+    if (scratch_floats < 0 || (!d_scratch && scratch_floats != 0)) return fail(GAT_E_INVALID, std::string(who) + ": scratch_floats without a scratch");
+    hipStream_t s = (hipStream_t)stream;
+    dense_last_kernel_clear();
+    const int rc = launch_project(d_x, d_w, (float*)d_pl, d_pr, n_rows, F, HD, part, pl_bf16 != 0, d_scratch, scratch_floats, s, ldx);
+    return op_dense_finish(who, rc, s, picked, picked_cap);
+}
+int gat_op_dense_grad_x(const float* d_gpl, const float* d_gpr, const float* d_w, const float* d_hpre_prev, float* d_gprev, int64_t n_rows,
+                        int32_t F, int32_t HD, float slope, void* stream, char* picked, int32_t picked_cap) {
+    static const char* who = "gat_op_dense_grad_x";
+    GAT_TRY(op_dense_sizes(who, n_rows, F, HD));
+    if (!d_gpl || !d_gpr || !d_w || !d_gprev) return fail(GAT_E_INVALID, std::string(who) + ": null argument");
+    if (!(slope == slope)) return fail(GAT_E_INVALID, std::string(who) + ": slope is NaN");
+    hipStream_t s = (hipStream_t)stream;
+    dense_last_kernel_clear();
+    const int rc = launch_grad_x(d_gpl, d_gpr, d_w, d_hpre_prev, d_gprev, n_rows, F, HD, slope, s);
+    return op_dense_finish(who, rc, s, picked, picked_cap);
+}
+int gat_op_dense_grad_w(const float* d_gpl, const float* d_gpr, const float* d_x, int32_t ldx, float* d_grad_w, float* d_scratch,
+                        int64_t scratch_floats, int64_t n_rows, int32_t F, int32_t HD, int32_t part, void* stream, char* picked, int32_t picked_cap) {
+    static const char* who = "gat_op_dense_grad_w";
+    GAT_TRY(op_dense_sizes(who, n_rows, F, HD));
+    GAT_TRY(op_dense_part(who, part));
+    GAT_TRY(op_dense_ldx(who, ldx, F));
+    if ((part != kPartRight && !d_gpl) || (part != kPartLeft && !d_gpr) || !d_x || !d_grad_w || !d_scratch) return fail(GAT_E_INVALID, std::string(who) + ": null argument");
+    if (scratch_floats < grad_w_scratch_floats(n_rows, F, HD))
+        return fail(GAT_E_INVALID, std::string(who) + ": scratch below gat_op_dense_scratch_floats(1, ...) = " + std::to_string(grad_w_scratch_floats(n_rows, F, HD)) + " floats");
+    hipStream_t s = (hipStream_t)stream;
+    dense_last_kernel_clear();
+    const int rc = launch_grad_w(d_gpl, d_gpr, d_x, d_grad_w, d_scratch, n_rows, F, HD, part, s, ldx);
+    return op_dense_finish(who, rc, s, picked, picked_cap);
+}
+int gat_op_dense_project_res(const float* d_x, int32_t ldx, const float* d_wres, float* d_r, int64_t n_rows, int32_t F, int32_t HD, void* stream,
+                             char* picked, int32_t picked_cap) {
+    static const char* who = "gat_op_dense_project_res";
+    GAT_TRY(op_dense_sizes(who, n_rows, F, HD));
+    GAT_TRY(op_dense_ldx(who, ldx, F));
+    if (!d_x || !d_wres || !d_r) return fail(GAT_E_INVALID, std::string(who) + ": null argument");
+    hipStream_t s = (hipStream_t)stream;
+    dense_last_kernel_clear();
+    const int rc = launch_project_res(d_x, d_wres, d_r, n_rows, F, HD, s, ldx);
+    return op_dense_finish(who, rc, s, picked, picked_cap);
+}
+int gat_op_dense_grad_wres(const float* d_g, const float* d_x, int32_t ldx, float* d_grad_wres, float* d_scratch, int64_t scratch_floats,
+                           int64_t n_rows, int32_t F, int32_t HD, void* stream, char* picked, int32_t picked_cap) {
+    static const char* who = "gat_op_dense_grad_wres";
+    GAT_TRY(op_dense_sizes(who, n_rows, F, HD));
+    GAT_TRY(op_dense_ldx(who, ldx, F));
+    if (!d_g || !d_x || !d_grad_wres || !d_scratch) return fail(GAT_E_INVALID, std::string(who) + ": null argument");
+    if (scratch_floats < grad_w_scratch_floats(n_rows, F, HD))
+        return fail(GAT_E_INVALID, std::string(who) + ": scratch below gat_op_dense_scratch_floats(1, ...) = " + std::to_string(grad_w_scratch_floats(n_rows, F, HD)) + " floats");
+    hipStream_t s = (hipStream_t)stream;
+    dense_last_kernel_clear();
+    const int rc = launch_grad_wres(d_g, d_x, d_grad_wres, d_scratch, n_rows, F, HD, s, ldx);
+    return op_dense_finish(who, rc, s, picked, picked_cap);
+}
+int gat_op_dense_grad_x_res(const float* d_g, const float* d_wres, float* d_gx, int64_t n_rows, int32_t F, int32_t HD, void* stream,
+                            char* picked, int32_t picked_cap) {
+    static const char* who = "gat_op_dense_grad_x_res";
+    GAT_TRY(op_dense_sizes(who, n_rows, F, HD));
+    if (!d_g || !d_wres || !d_gx) return fail(GAT_E_INVALID, std::string(who) + ": null argument");
+    hipStream_t s = (hipStream_t)stream;
+    dense_last_kernel_clear();
+    const int rc = launch_grad_x_res(d_g, d_wres, d_gx, n_rows, F, HD, s);
+    return op_dense_finish(who, rc, s, picked, picked_cap);
+}
+
 }  // extern "C"

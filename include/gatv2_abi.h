@@ -598,6 +598,33 @@ int gat_op_readout_forward(const float* d_x, int64_t x_stride, const int32_t* d_
 int gat_op_readout_backward(const float* d_gpooled, const int32_t* d_graph_ptr, int64_t n_graphs, int64_t n_rows, int32_t width,
                             int32_t mode, const int32_t* d_argmax, float* d_gh, int64_t gh_stride, void* stream);
 
+/* The dense launchers (the W_l / W_r projections, their two backward products and the residual's three) as stateless seams on caller-owned
+ * DEVICE pointers (current device).  Each call runs exactly ONE launcher with exactly the caller's arguments and synchronises `stream`
+ * (may be NULL): parity seams, not the fast path.  W is the reference layout [HD][2F], Wres [HD][F]; part: 0 both halves, 1 the left
+ * (PL / gPL) half alone, 2 the right one — pointers of a half that is not asked for may be NULL and its cells are not written; ldx: floats
+ * between rows of X (0 = F; a multiple of 4 with ZEROS behind column F selects 16-byte loads); d_pl holds fp32 rows, or bf16 rows with
+ * pl_bf16 = 1; d_hpre_prev == NULL stores the plain sum; grad_w, grad_wres and grad_x_res ADD into their output.  Scratch sizes come from
+ * gat_op_dense_scratch_floats (kind 0: the projection's split-K slabs for (n_rows, F, HD, part), 0 when that launch never splits; kind 1:
+ * the slabs of grad_w / grad_wres, part is ignored).  The projection takes its split-K path only when scratch_floats covers it and the
+ * streaming kernel otherwise; grad_w / grad_wres refuse a scratch_floats below the stated size.  Every argument is checked before any
+ * launch: a NULL pointer the part needs, n_rows < 0, F < 1, HD < 1, ldx != 0 && ldx < F, a part or pl_bf16 outside its values give
+ * GAT_E_INVALID and a text, and nothing is written.  picked (may be NULL) receives, NUL-terminated and cut to picked_cap bytes, the template
+ * name of the row / tile kernel the launcher launched last, e.g. "rowgemm_x3_kernel<2, 8, true>" ("" when n_rows == 0 launched nothing):
+ * it is how tests/test_dense_seams.py proves that a case reached the dispatch branch it names. */
+int gat_op_dense_scratch_floats(int32_t kind, int64_t n_rows, int32_t F, int32_t HD, int32_t part, int64_t* floats_out);
+int gat_op_dense_project(const float* d_x, int32_t ldx, const float* d_w, int64_t n_rows, int32_t F, int32_t HD, int32_t part, int32_t pl_bf16,
+                         void* d_pl, float* d_pr, float* d_scratch, int64_t scratch_floats, void* stream, char* picked, int32_t picked_cap);
+int gat_op_dense_grad_x(const float* d_gpl, const float* d_gpr, const float* d_w, const float* d_hpre_prev, float* d_gprev, int64_t n_rows,
+                        int32_t F, int32_t HD, float slope, void* stream, char* picked, int32_t picked_cap);
+int gat_op_dense_grad_w(const float* d_gpl, const float* d_gpr, const float* d_x, int32_t ldx, float* d_grad_w, float* d_scratch,
+                        int64_t scratch_floats, int64_t n_rows, int32_t F, int32_t HD, int32_t part, void* stream, char* picked, int32_t picked_cap);
+int gat_op_dense_project_res(const float* d_x, int32_t ldx, const float* d_wres, float* d_r, int64_t n_rows, int32_t F, int32_t HD, void* stream,
+                             char* picked, int32_t picked_cap);
+int gat_op_dense_grad_wres(const float* d_g, const float* d_x, int32_t ldx, float* d_grad_wres, float* d_scratch, int64_t scratch_floats,
+                           int64_t n_rows, int32_t F, int32_t HD, void* stream, char* picked, int32_t picked_cap);
+int gat_op_dense_grad_x_res(const float* d_g, const float* d_wres, float* d_gx, int64_t n_rows, int32_t F, int32_t HD, void* stream,
+                            char* picked, int32_t picked_cap);
+
 /* ---- loss modes of the output head (beyond the reference, whose head is one softmax + cross-entropy on an int32 label per row) ----------
  * Multi-label classification (PPI, ogbn-proteins), regression (ZINC, QM9) and multi-task targets with missing entries (ogbg-molpcba)
  * need a FLOAT target matrix T [rows][C], a per-entry loss, and entries that may be absent.  C = num_classes is the number of output

@@ -19,23 +19,11 @@ import pytest
 
 import parity
 from conftest import small_graph
+from dense_ref import _chain_ratio, _ratio
 
 pytestmark = pytest.mark.gpu
 
 BOUND = 1e-6
-
-
-def _chain_ratio(a, b, exact, scale):
-    """a [M,K], b [N,K] fp32: the error ratio of acc = fma(a_k, b_k, acc), k ascending, in fp32 (product exact, one rounding per step)."""
-    a64, b64 = a.astype(np.float64), b.astype(np.float64)
-    acc = np.zeros((a.shape[0], b.shape[0]), np.float32)
-    for k in range(a.shape[1]):
-        acc = (acc.astype(np.float64) + a64[:, k:k + 1] * b64[:, k][None, :]).astype(np.float32)
-    return _ratio(acc, exact, scale)
-
-
-def _ratio(got, exact, scale):
-    return float(np.max(np.abs(got.astype(np.float64) - exact) / np.maximum(scale, 1e-300)))
 
 
 @pytest.mark.parametrize("n,f,heads,outdims,what", [

@@ -5,13 +5,9 @@ from the six piece products with (piece index of a) + (piece index of b) <= 2 di
 The kernels themselves are held to the same bound on the GPU (tests/test_dense_precision.py)."""
 import numpy as np
 
+from dense_ref import bf16_rne
+
 MASK = np.uint32(0xFFFF0000)
-
-
-def bf16_rne(x):
-    """fp32 -> nearest bf16 (ties to even), as v_cvt_pk_bf16_f32 does for finite values; returned as fp32."""
-    u = np.asarray(x, np.float32).view(np.uint32).astype(np.uint64)
-    return ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32).view(np.float32)
 
 
 def split3(x):
