@@ -63,7 +63,10 @@ TAP_ATTN_KEEP, TAP_FEAT_KEEP = 15, 16       # dropout factors (0 or 1/(1-p)) for
 TAP_EDGE_KEEP = 17                          # DropEdge: 1 = edge kept, 0 = dropped, [E], likewise
 TAP_POOLED = 18                             # readout: the pooled rows the head reads, [n_graphs][D_last] (last layer)
 DROPEDGE_KEEP_SELF, DROPEDGE_SHARED_LAYERS = 1, 2
+TAP_PAIRED = 19                             # pair head: the rows the head reads, [n_pairs][D_last] (last layer)
 READOUT_NONE, READOUT_MEAN, READOUT_SUM, READOUT_MAX = 0, 1, 2, 3      # graph-level readout (set_readout)
+PAIR_NONE, PAIR_MUL, PAIR_ADD = 0, 1, 2                                # pair head (set_pairs)
+PAIR_MODES = {"none": PAIR_NONE, "mul": PAIR_MUL, "add": PAIR_ADD}
 READOUT_MODES = {"none": READOUT_NONE, "mean": READOUT_MEAN, "sum": READOUT_SUM, "max": READOUT_MAX}
 LOSS_SOFTMAX_CE, LOSS_BCE, LOSS_MSE = 0, 1, 2                          # loss modes of the output head (set_loss)
 LOSS_MODES = {"softmax": LOSS_SOFTMAX_CE, "bce": LOSS_BCE, "mse": LOSS_MSE}
@@ -215,6 +218,11 @@ def _declare(lib: C.CDLL) -> None:
         "gat_set_readout": [vp, i32, vp, i64],
         "gat_set_readout_device": [vp, i32, vp, i64],
         "gat_readout_info": [vp, P(i32), P(i64)],
+        "gat_set_pairs": [vp, i32, vp, vp, i64],
+        "gat_set_pairs_device": [vp, i32, vp, vp, i64],
+        "gat_pairs_info": [vp, P(i32), P(i64)],
+        "gat_op_pair_forward": [vp, i64, vp, vp, i64, i64, i32, i32, vp, vp],
+        "gat_op_pair_backward": [vp, vp, i64, vp, vp, i64, i64, i32, i32, vp, i64, vp],
         "gat_set_loss": [vp, i32],
         "gat_set_targets": [vp, vp, i64, i32],
         "gat_set_targets_device": [vp, vp, i64, i32],
@@ -290,6 +298,7 @@ class GatContext:
         self.n_rows = self.n_edges = self.n_table = 0
         self.table_row0 = 0
         self.n_graphs = 0                               # > 0 on a readout context (set_readout)
+        self.n_pairs = 0                                # > 0 on a context with a pair head (set_pairs)
 
     # -- lifecycle
     def close(self):
@@ -313,6 +322,12 @@ class GatContext:
         _chk(self.lib.gat_sync(self._ctx))
 
     # -- shapes
+    @property
+    def head_rows(self) -> int:
+        """Rows of the output head — of labels, targets, masks and the y tap: the pairs of a pair head, the graphs of a readout
+        context, else the nodes."""
+        return self.n_pairs or self.n_graphs or self.n_rows
+
     @property
     def in_dims(self) -> List[int]:
         d = [self.in_dim]
@@ -389,7 +404,8 @@ class GatContext:
         _chk(self.lib.gat_set_labels(self._ctx, _np_ptr(lab), len(lab)))
 
     def set_train_mask(self, mask):
-        """mask: bool/uint8 [n_rows] — [n_graphs] on a readout context (None: every node / graph trains, the reference's behaviour)."""
+        """mask: bool/uint8 [head_rows] — nodes, graphs of a readout context or pairs of a pair head (None: every row trains, the
+        reference's behaviour)."""
         if mask is None:
             _chk(self.lib.gat_set_train_mask(self._ctx, None, 0))
             return
@@ -397,7 +413,8 @@ class GatContext:
         _chk(self.lib.gat_set_train_mask(self._ctx, _np_ptr(m), len(m)))
 
     def eval_mask(self, mask):
-        """-> (loss sum, #correct, #nodes) of the last forward over the nodes of `mask` (a readout context: over its graphs)."""
+        """-> (loss sum, #correct, #rows) of the last forward over the head rows of `mask`: nodes, the graphs of a readout context or
+        the pairs of a pair head."""
         m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
         l, c, n = C.c_double(), C.c_int32(), C.c_int32()
         _chk(self.lib.gat_eval_mask(self._ctx, _np_ptr(m), len(m), C.byref(l), C.byref(c), C.byref(n)))
@@ -505,6 +522,36 @@ class GatContext:
         _chk(self.lib.gat_readout_info(self._ctx, C.byref(m), C.byref(g)))
         return m.value, g.value
 
+    # -- pair head (gatv2_abi.h "pair head")
+    def set_pairs(self, mode, u=None, v=None):
+        """One label per PAIR of nodes: the head reads Q[p] = X[u_p] * X[v_p] ("mul") or X[u_p] + X[v_p] ("add", or the GAT_PAIR_*
+        integer) of the last layer's rows.  After set_graph*, before set_labels / set_targets; labels, targets and masks are then per
+        pair.  A later call with the same mode and length replaces the pairs.  Mode 0 / "none" leaves the context as it is."""
+        m = pair_mode(mode)
+        if m == PAIR_NONE:
+            _chk(self.lib.gat_set_pairs(self._ctx, m, None, None, 0))
+            return
+        if u is None or v is None:
+            raise ValueError("set_pairs: give u and v")
+        ua, va = np.ascontiguousarray(u, np.int32), np.ascontiguousarray(v, np.int32)
+        if ua.ndim != 1 or ua.shape != va.shape:
+            raise ValueError("u and v must be one-dimensional and of the same length")
+        _chk(self.lib.gat_set_pairs(self._ctx, m, _np_ptr(ua), _np_ptr(va), len(ua)))
+        self.n_pairs = len(ua)
+
+    def set_pairs_device(self, mode, d_u: int, d_v: int, n_pairs: int):
+        """set_pairs on device arrays [n_pairs] (checked on the device)."""
+        m = pair_mode(mode)
+        _chk(self.lib.gat_set_pairs_device(self._ctx, m, C.c_void_p(d_u or None), C.c_void_p(d_v or None), n_pairs))
+        if m != PAIR_NONE:
+            self.n_pairs = int(n_pairs)
+
+    def pairs_info(self):
+        """(mode, n_pairs); (0, 0) while the pair head is off."""
+        m, n = C.c_int32(), C.c_int64()
+        _chk(self.lib.gat_pairs_info(self._ctx, C.byref(m), C.byref(n)))
+        return m.value, n.value
+
     # -- loss modes of the output head (gatv2_abi.h "loss modes of the output head")
     def set_loss(self, mode):
         """"softmax" (the default: int32 labels, set_labels), "bce" or "mse" (float targets [rows][C] with NaN = missing, set_targets),
@@ -512,7 +559,7 @@ class GatContext:
         _chk(self.lib.gat_set_loss(self._ctx, loss_mode(mode)))
 
     def set_targets(self, t):
-        """Targets [n_rows][C] — [n_graphs][C] on a readout context — as floats; NaN marks a missing entry.  After set_graph* (and
+        """Targets [head_rows][C] — nodes, graphs of a readout context or pairs of a pair head — as floats; NaN marks a missing entry.  After set_graph* (and
         set_readout).  A later call with the same shape replaces the values in place (a captured step reads the new ones)."""
         a = np.ascontiguousarray(t, np.float32)
         if a.ndim != 2:
@@ -677,15 +724,16 @@ class GatContext:
         N, E = self.n_rows, self.n_edges
         H, D = self.heads[l], self.outdims[l]
         last = l == self.L - 1
-        G = self.n_graphs                               # readout: the head has one row per graph
+        G = self.n_graphs                               # readout: the pooled rows
         shapes = {
             TAP_SRC: ((E,), np.int32), TAP_DST: ((E,), np.int32),
             TAP_ALPHA: ((H, E), np.float32), TAP_GE: ((H, E), np.float32),
             TAP_MAX: ((H, N), np.float32), TAP_SUM: ((H, N), np.float32),
             TAP_HPRE: ((N, H, D), np.float32), TAP_G: ((N, H, D), np.float32),
             TAP_HOUT: ((N, D if last else H * D), np.float32),
-            TAP_Y: ((G or N, self.C), np.float32),
+            TAP_Y: ((self.head_rows, self.C), np.float32),
             TAP_POOLED: ((G, self.outdims[-1]), np.float32),
+            TAP_PAIRED: ((self.n_pairs, self.outdims[-1]), np.float32),
             TAP_PL: ((self.n_table, H * D), np.float32), TAP_PR: ((N, H * D), np.float32),
             TAP_SCORE: ((H, E), np.float32), TAP_GALPHA: ((H, E), np.float32),
             TAP_GX: ((N, self.heads[l - 1] * self.outdims[l - 1] if l > 0 else 0), np.float32),
@@ -761,6 +809,15 @@ def readout_mode(mode) -> int:
     return int(mode)
 
 
+def pair_mode(mode) -> int:
+    """"mul" / "add" / "none" or the GAT_PAIR_* integer -> the integer."""
+    if isinstance(mode, str):
+        if mode not in PAIR_MODES:
+            raise ValueError(f"pair mode must be one of {sorted(PAIR_MODES)}, got {mode!r}")
+        return PAIR_MODES[mode]
+    return int(mode)
+
+
 def loss_mode(mode) -> int:
     """"softmax" / "bce" / "mse" or the GAT_LOSS_* integer -> the integer."""
     if isinstance(mode, str):
@@ -800,6 +857,20 @@ def op_readout_backward(d_gpooled: int, d_graph_ptr: int, n_graphs: int, n_rows:
     _chk(load_library().gat_op_readout_backward(C.c_void_p(d_gpooled or None), C.c_void_p(d_graph_ptr or None), n_graphs, n_rows, width,
                                                 readout_mode(mode), C.c_void_p(d_argmax or None), C.c_void_p(d_gh or None), gh_stride,
                                                 C.c_void_p(stream or None)))
+
+
+def op_pair_forward(d_x: int, x_stride: int, d_u: int, d_v: int, n_pairs: int, n_rows: int, width: int, mode, d_q: int, stream: int = 0):
+    """gat_op_pair_forward on device pointers: q [n_pairs][width] = x[u] * x[v] ("mul") or x[u] + x[v] ("add")."""
+    _chk(load_library().gat_op_pair_forward(C.c_void_p(d_x or None), x_stride, C.c_void_p(d_u or None), C.c_void_p(d_v or None), n_pairs,
+                                            n_rows, width, pair_mode(mode), C.c_void_p(d_q or None), C.c_void_p(stream or None)))
+
+
+def op_pair_backward(d_gq: int, d_x: int, x_stride: int, d_u: int, d_v: int, n_pairs: int, n_rows: int, width: int, mode, d_gh: int,
+                     gh_stride: int, stream: int = 0):
+    """gat_op_pair_backward on device pointers: floats 0..width-1 of every gh row from the pair rows' gradient (d_x may be 0 for "add")."""
+    _chk(load_library().gat_op_pair_backward(C.c_void_p(d_gq or None), C.c_void_p(d_x or None), x_stride, C.c_void_p(d_u or None),
+                                             C.c_void_p(d_v or None), n_pairs, n_rows, width, pair_mode(mode), C.c_void_p(d_gh or None),
+                                             gh_stride, C.c_void_p(stream or None)))
 
 
 PART_BOTH, PART_LEFT, PART_RIGHT = 0, 1, 2       # the `part` of the dense seams

@@ -115,6 +115,17 @@ static int algorithmic_bytes_nodes(gat_ctx* c, double* bytes_step, double* per_k
     return 0;
 }
 static int algorithmic_bytes_softmax(gat_ctx* c, double* bytes_step, double* per_kernel) {
+    if (pairs_on(c)) {
+        // pair head (gatv2_abi.h "pair head"): the head classes priced with P rows; the gather reads the indices and two rows per pair and
+        // writes Q, the scatter reads an 8-byte entry and a gQ row (MUL: and an X row) per incidence and writes every gH row (under misc, fp32)
+        double k[GAT_K_COUNT] = {0};
+        GAT_TRY(algorithmic_bytes_nodes(c, nullptr, k));
+        const double N = (double)c->graph.n_rows, P = (double)c->pairs.n_pairs, DL = c->layers.back().D;
+        const double head = 2.0 * 4.0 * P * (DL + 2.0 * c->cfg.num_classes + 2.0);
+        k[GAT_K_HEAD_FWD] = head / 2; k[GAT_K_HEAD_BWD] = head / 2;
+        k[GAT_K_MISC] += 4.0 * (2 * P + 2 * P * DL + P * DL) + 4.0 * (4 * P + 2 * P * DL + (c->pairs.mode == GAT_PAIR_MUL ? 2 * P * DL : 0.0) + N * DL);
+        return report_bytes(k, bytes_step, per_kernel);
+    }
     if (!readout_on(c)) return algorithmic_bytes_nodes(c, bytes_step, per_kernel);
     // readout (gatv2_abi.h "graph-level readout"): the head classes priced with G rows; the pool reads N*DL and writes G*DL, the un-pool
     // reads G*DL and writes N*DL (under misc, fp32)

@@ -239,7 +239,7 @@ int gat_layer_exchange(gat_ctx* c, int32_t l, int32_t* needed) {
 static int set_labels_common(gat_ctx* c, const int32_t* labels, int64_t n_rows, hipMemcpyKind kind) {
     if (!c || !labels) return fail(GAT_E_INVALID, "gat_set_labels: null argument");
     if (c->sup.loss_mode != 0) return fail(GAT_E_STATE, "gat_set_labels: the context's loss mode takes float targets: call gat_set_targets");
-    if (c->graph.have && n_rows != head_rows(c)) return fail(GAT_E_INVALID, readout_on(c) ? "Invalid labels length (with readout: one label per graph)" : "Invalid labels length");
+    if (c->graph.have && n_rows != head_rows(c)) return fail(GAT_E_INVALID, pairs_on(c) ? "Invalid labels length (with a pair head: one per pair)" : readout_on(c) ? "Invalid labels length (with readout: one label per graph)" : "Invalid labels length");
     if (kind == hipMemcpyHostToDevice)
         for (int64_t i = 0; i < n_rows; ++i)
             if (labels[i] < 0 || labels[i] >= c->cfg.num_classes) return fail(GAT_E_INVALID, "label outside [0, num_classes)");
@@ -258,7 +258,7 @@ static int set_labels_common(gat_ctx* c, const int32_t* labels, int64_t n_rows, 
 static int upload_mask(gat_ctx* c, const uint8_t* mask, int64_t n_rows, uint8_t** dst) {
     if (!c->sup.have) return fail(GAT_E_STATE, "set the labels first");
     if (n_rows != c->sup.n_labels || (c->graph.have && n_rows != head_rows(c)))
-        return fail(GAT_E_INVALID, readout_on(c) ? "mask length differs from the graph count" : "mask length differs from the node count");
+        return fail(GAT_E_INVALID, std::string("mask length differs from the ") + head_row_name(c) + " count" + (pairs_on(c) ? " (with a pair head: one per pair)" : ""));
     if (!*dst) GAT_TRY(dalloc(c, dst, n_rows));
     GAT_HIP(hipMemcpyAsync(*dst, mask, (size_t)n_rows, hipMemcpyHostToDevice, c->stream));
     return 0;
@@ -366,7 +366,7 @@ static int set_targets_common(gat_ctx* c, const float* t, int64_t n_rows, int32_
     if (n_cols != C) return fail(GAT_E_INVALID, "gat_set_targets: n_cols differs from num_classes");
     if (n_rows < 0) return fail(GAT_E_INVALID, "gat_set_targets: negative n_rows");
     if (n_rows * (int64_t)C >= (1ll << 31)) return fail(GAT_E_UNSUPPORTED, "gat_set_targets: n_rows * n_cols >= 2^31 (n_correct is int32)");
-    if (n_rows != head_rows(c)) return fail(GAT_E_INVALID, readout_on(c) ? "gat_set_targets: n_rows differs from the graph count (with readout: one target row per graph)" : "gat_set_targets: n_rows differs from the node count");
+    if (n_rows != head_rows(c)) return fail(GAT_E_INVALID, pairs_on(c) ? "gat_set_targets: n_rows differs from the pair count (with a pair head: one per pair)" : readout_on(c) ? "gat_set_targets: n_rows differs from the graph count (with readout: one target row per graph)" : "gat_set_targets: n_rows differs from the node count");
     const int64_t n = n_rows * C;
     if (!c->sup.tgt_scratch) GAT_TRY(dalloc(c, &c->sup.tgt_scratch, 256));
     int64_t bad = -1;

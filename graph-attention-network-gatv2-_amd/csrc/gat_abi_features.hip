@@ -1,5 +1,5 @@
 // gat_abi_features.hip — the optional features of a context, switched on before it is complete: residual / bias, layer
-// normalisation, edge features, graph-level readout, dropout / DropEdge / training mode.
+// normalisation, edge features, graph-level readout, pair head, dropout / DropEdge / training mode.
 #include "gat_ctx.h"
 
 using namespace gat;
@@ -70,6 +70,7 @@ static int set_readout_common(gat_ctx* c, int32_t mode, const int32_t* graph_ptr
     if (mode < GAT_READOUT_NONE || mode > GAT_READOUT_MAX) return fail(GAT_E_INVALID, "gat_set_readout: mode must be 0 (none), 1 (mean), 2 (sum) or 3 (max)");
     if (mode == GAT_READOUT_NONE) return 0;              // the default: nothing is touched
     if (readout_on(c)) return fail(GAT_E_STATE, "gat_set_readout: readout already set (create a new context)");
+    if (pairs_on(c)) return fail(GAT_E_UNSUPPORTED, "gat_set_readout: not on a context with a pair head (gat_set_pairs)");
     if (!c->graph.have) return fail(GAT_E_STATE, "gat_set_readout: set the graph first");
     if (c->sup.have) return fail(GAT_E_STATE, "gat_set_readout: call it before gat_set_labels (the label, mask and head buffers are sized by it)");
     if (c->graph.n_table != c->graph.n_rows || c->xch.comm)
@@ -126,6 +127,83 @@ int gat_readout_info(gat_ctx* c, int32_t* mode, int64_t* n_graphs) {
     if (!c) return fail(GAT_E_INVALID, "null context");
     if (mode) *mode = c->readout.mode;
     if (n_graphs) *n_graphs = c->readout.n_graphs;
+    return 0;
+}
+// ---- pair head ----------------------------------------------------------------------------------------------------
+// The scatter's work list from the incidence row_ptr (fetched to the host, cut as the readout's graphs are), into the context's buffers
+static int pairs_plan(gat_ctx* c) {
+    const int64_t N = c->graph.n_rows;
+    std::vector<int32_t> ip((size_t)N + 1);
+    GAT_HIP(hipMemcpy(ip.data(), c->pairs.inc_ptr, ip.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    ReadoutPlan plan;
+    build_readout_plan(ip.data(), N, plan);
+    GAT_HIP(hipMemcpyAsync(c->pairs.items, plan.items.data(), plan.items.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (plan.n_split > 0) GAT_HIP(hipMemcpyAsync(c->pairs.split, plan.split.data(), plan.split.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));            // (the host lists go out of scope)
+    c->pairs.n_items = plan.n_items; c->pairs.n_split = plan.n_split;
+    return 0;
+}
+static int set_pairs_common(gat_ctx* c, int32_t mode, const int32_t* u, const int32_t* v, int64_t n_pairs, bool on_host) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (mode < GAT_PAIR_NONE || mode > GAT_PAIR_ADD) return fail(GAT_E_INVALID, "gat_set_pairs: mode must be 0 (none), 1 (mul) or 2 (add)");
+    if (mode == GAT_PAIR_NONE) return 0;                 // the default: nothing is touched
+    const bool first = !pairs_on(c);
+    if (!first && (mode != c->pairs.mode || n_pairs != c->pairs.n_pairs))
+        return fail(GAT_E_STATE, "gat_set_pairs: a later call replaces the pairs and keeps the mode and n_pairs (create a new context for others)");
+    if (first) {
+        if (readout_on(c)) return fail(GAT_E_UNSUPPORTED, "gat_set_pairs: not on a readout context (gat_set_readout)");
+        if (!c->graph.have) return fail(GAT_E_STATE, "gat_set_pairs: set the graph first");
+        if (c->sup.have) return fail(GAT_E_STATE, "gat_set_pairs: call it before gat_set_labels / gat_set_targets (the label, target, mask and head buffers are sized by it)");
+        if (c->graph.n_table != c->graph.n_rows || c->xch.comm)
+            return fail(GAT_E_UNSUPPORTED, "gat_set_pairs: not on a destination-range shard or with a transport (an endpoint may live on another shard)");
+        if (c->cfg.flat_lrelu_index)
+            return fail(GAT_E_UNSUPPORTED, "gat_set_pairs: not with flat_lrelu_index = 1 (the head would write the last layer's g itself)");
+        GAT_REFUSE_DBG(c, true, "gat_set_pairs", "");
+    }
+    if (!u || !v) return fail(GAT_E_INVALID, "gat_set_pairs: null argument");
+    if (n_pairs < 1) return fail(GAT_E_INVALID, "gat_set_pairs: n_pairs must be >= 1");
+    if (n_pairs >= (1ll << 30)) return fail(GAT_E_UNSUPPORTED, "gat_set_pairs: n_pairs must be below 2^30 (the incidence keys 2p + role go through the 32-bit graph builder)");
+    const int64_t N = c->graph.n_rows, P = n_pairs;
+    int64_t where = -1; int32_t value = 0;
+    if (on_host) {
+        where = pair_check_host(u, v, P, N);
+        if (where >= 0) value = (where & 1) ? v[where >> 1] : u[where >> 1];
+    } else {                                             // the same rule on the caller's device arrays, before anything reads through them
+        GAT_TRY(pair_check_device(u, v, P, N, &where, &value, c->stream));
+    }
+    if (where >= 0) return fail(GAT_E_INVALID, "gat_set_pairs: " + pair_problem_text(where, value, N));
+    if (first) {
+        const int32_t DL = c->layers.back().D;
+        // upper bounds of the work list over every pair list of this length: an item per node plus one per started segment of a long
+        // node; a long node has more than kPairSegEntries of the 2P incidences
+        const int64_t seg = 2 * P / kPairSegEntries + 1;
+        GAT_TRY(dalloc(c, &c->pairs.u, P)); GAT_TRY(dalloc(c, &c->pairs.v, P));
+        GAT_TRY(dalloc(c, &c->pairs.inc_ptr, N + 1)); GAT_TRY(dalloc(c, &c->pairs.inc, 2 * P));
+        GAT_TRY(dalloc(c, &c->pairs.items, N + 2 * seg)); GAT_TRY(dalloc(c, &c->pairs.split, seg));
+        GAT_TRY(dalloc(c, &c->pairs.part, 2 * seg * DL));
+        GAT_TRY(dalloc(c, &c->pairs.Q, P * DL)); GAT_TRY(dalloc(c, &c->pairs.gQ, P * DL));
+    }
+    const hipMemcpyKind kind = on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    GAT_HIP(hipStreamSynchronize(c->stream));            // a step in flight still reads the old pairs
+    GAT_HIP(hipMemcpyAsync(c->pairs.u, u, (size_t)P * sizeof(int32_t), kind, c->stream));
+    GAT_HIP(hipMemcpyAsync(c->pairs.v, v, (size_t)P * sizeof(int32_t), kind, c->stream));
+    GAT_TRY(pair_index_build(c->pairs.u, c->pairs.v, P, N, c->pairs.inc_ptr, c->pairs.inc, c->stream));
+    GAT_TRY(pairs_plan(c));
+    c->pairs.mode = mode; c->pairs.n_pairs = P;
+    c->head.y_valid = false;                                  // nothing of an earlier forward stays
+    graph_drop(c);                                            // the work list changed: no replay may survive
+    return 0;
+}
+int gat_set_pairs(gat_ctx* c, int32_t mode, const int32_t* u, const int32_t* v, int64_t n_pairs) {
+    return set_pairs_common(c, mode, u, v, n_pairs, true);
+}
+int gat_set_pairs_device(gat_ctx* c, int32_t mode, const int32_t* d_u, const int32_t* d_v, int64_t n_pairs) {
+    return set_pairs_common(c, mode, d_u, d_v, n_pairs, false);
+}
+int gat_pairs_info(gat_ctx* c, int32_t* mode, int64_t* n_pairs) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (mode) *mode = c->pairs.mode;
+    if (n_pairs) *n_pairs = c->pairs.n_pairs;
     return 0;
 }
 // ---- dropout ---------------------------------------------------------------------------------------------------

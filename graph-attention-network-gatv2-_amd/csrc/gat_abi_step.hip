@@ -30,6 +30,11 @@ static void head_args(gat_ctx* c, HeadArgs* f, HeadBwdArgs* b) {
         f->HL = b->HL = c->readout.P; f->n_rows = b->n_rows = c->readout.n_graphs;
         b->g = nullptr; b->hpre = nullptr; b->gh_out = c->readout.gP; b->gh_stride = y.D;
     }
+    if (pairs_on(c)) {
+        // the head on the pair rows Q: one row per pair, its gradient into gQ; the scatter fills c->bwd.gH afterwards, as the un-pool does
+        f->HL = b->HL = c->pairs.Q; f->n_rows = b->n_rows = c->pairs.n_pairs;
+        b->g = nullptr; b->hpre = nullptr; b->gh_out = c->pairs.gQ; b->gh_stride = y.D;
+    }
 }
 LossHeadArgs loss_head_args(gat_ctx* c) {
     HeadArgs f{}; HeadBwdArgs b{};
@@ -55,7 +60,7 @@ static bool fused_head(gat_ctx* c) {
 // a row's sources comes a few microseconds after the first.
 bool fused_last(gat_ctx* c) {
     if (c->sup.loss_mode != 0) return false;            // the BCE / MSE head runs the separate passes
-    if (!fused_head(c) || bf16(c) || c->xch.comm || c->graph.n_table != c->graph.n_rows || c->cfg.flat_lrelu_index || res_route(c) || edge_feat_on(c) || readout_on(c)) return false;   // no residual / norm / edge-feature / readout form
+    if (!fused_head(c) || bf16(c) || c->xch.comm || c->graph.n_table != c->graph.n_rows || c->cfg.flat_lrelu_index || res_route(c) || edge_feat_on(c) || readout_on(c) || pairs_on(c)) return false;   // no residual / norm / edge-feature / readout / pair form
     const Layer& y = c->layers.back();
     if (!edge_fast_path(y.H, y.D, c->graph.n_table) || !y.stash || c->bwd.stash == nullptr || c->bwd.gH == nullptr) return false;
     if (!edge_last_fused_supported(y.H, y.D, c->cfg.num_classes) || c->dbg != 0 || drop_on(c)) return false;   // no dropout form
@@ -148,11 +153,33 @@ static int readout_unpool(gat_ctx* c) {
     Scope t(c, GAT_K_HEAD_BWD);
     return launch_readout_backward(a, c->stream);
 }
+// Pair head: Q = gather(hout of the last layer) in front of the head, gH = scatter(gQ) behind it (both no-ops with the feature off).
+// Plain launches on the context's stream, like the readout's.
+static int pair_gather(gat_ctx* c) {
+    if (!pairs_on(c)) return 0;
+    const Layer& y = c->layers.back();
+    PairFwdArgs a{};
+    a.x = y.hout; a.x_stride = y.D; a.u = c->pairs.u; a.v = c->pairs.v; a.n_pairs = c->pairs.n_pairs;
+    a.q = c->pairs.Q; a.width = y.D; a.mode = c->pairs.mode;
+    Scope t(c, GAT_K_HEAD_FWD);
+    return launch_pair_forward(a, c->stream);
+}
+static int pair_scatter(gat_ctx* c) {
+    if (!pairs_on(c)) return 0;
+    const Layer& y = c->layers.back();
+    PairBwdArgs a{};
+    a.gq = c->pairs.gQ; a.x = y.hout; a.x_stride = y.D; a.inc = c->pairs.inc;
+    a.items = c->pairs.items; a.n_items = c->pairs.n_items; a.split = c->pairs.split; a.n_split = c->pairs.n_split; a.part = c->pairs.part;
+    a.gh = c->bwd.gH; a.gh_stride = c->bwd.gh_stride; a.width = y.D; a.mode = c->pairs.mode;
+    Scope t(c, GAT_K_HEAD_BWD);
+    return launch_pair_backward(a, c->stream);
+}
 int gat_head_forward(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
     GAT_TRY(check_layer(c, 0));
     HeadArgs a{}; HeadBwdArgs unused{};
     head_args(c, &a, &unused);
     GAT_TRY(readout_pool(c));
+    GAT_TRY(pair_gather(c));
     {
         Scope t(c, GAT_K_HEAD_FWD);
         if (c->sup.loss_mode != 0) GAT_TRY(launch_loss_head_forward(loss_head_args(c), c->stream));
@@ -179,7 +206,8 @@ int gat_head_backward(gat_ctx* c) {
         if (c->sup.loss_mode != 0) GAT_TRY(launch_loss_head_grad(loss_head_args(c), false, c->stream));
         else GAT_TRY(launch_head_backward(a, c->stream));
     }
-    return readout_unpool(c);
+    GAT_TRY(readout_unpool(c));
+    return pair_scatter(c);
 }
 
 // Arguments of layer l's edge backward (shared by gat_layer_backward_edges and the fused last layer of gat_step).
@@ -408,13 +436,15 @@ static int head_step(gat_ctx* c, bool with_gh = true) {
     head_args(c, &f, &b);
     if (!with_gh) b.gh_out = nullptr;               // loss, #correct and grad_Wo only (the fused last layer formed gH itself)
     GAT_TRY(readout_pool(c));
+    GAT_TRY(pair_gather(c));
     {
         Scope t(c, GAT_K_HEAD_BWD);
         c->head.y_valid = false;
         if (c->sup.loss_mode != 0) GAT_TRY(launch_loss_head_grad(loss_head_args(c), true, c->stream));
         else GAT_TRY(launch_head_step(f, b, c->stream));
     }
-    return readout_unpool(c);
+    GAT_TRY(readout_unpool(c));
+    return pair_scatter(c);
 }
 static int last_layer_fused(gat_ctx* c) {
     const int l = c->cfg.num_layers - 1;
@@ -693,6 +723,7 @@ static int check_comm_target(gat_ctx* c, int32_t world, int32_t rank) {
     if (c->xch.comm) return fail(GAT_E_STATE, "a transport is already attached");
     if (!c->graph.have) return fail(GAT_E_STATE, "gat_comm_init: set the graph first");
     if (readout_on(c)) return fail(GAT_E_UNSUPPORTED, "gat_comm_init: not on a readout context (a graph may straddle shards)");
+    if (pairs_on(c)) return fail(GAT_E_UNSUPPORTED, "gat_comm_init: not on a context with a pair head (an endpoint may live on another shard)");
     if (world < 1 || rank < 0 || rank >= world) return fail(GAT_E_INVALID, "gat_comm_init: bad world / rank");
     if (c->graph.n_table % world != 0 || c->graph.table_row0 != (int64_t)rank * (c->graph.n_table / world) || c->graph.n_rows > c->graph.n_table / world)
         return fail(GAT_E_INVALID, "gat_comm_init: the source table must be [world][max_rows] with this shard's rows at rank*max_rows");

@@ -54,7 +54,7 @@ int gat_tap(gat_ctx* c, int tensor, int32_t l, void* host, int64_t count) {
         case GAT_TAP_SUM: GAT_TRY(need(N * y.H)); return transposed(y.zstat, N, y.H, false);
         case GAT_TAP_HPRE: GAT_TRY(need(N * y.HD)); return d2h(c, host, y.hpre, N * y.HD * sizeof(float));
         case GAT_TAP_HOUT: { const int64_t n = N * (last ? y.D : y.HD); GAT_TRY(need(n)); return d2h(c, host, y.hout, n * sizeof(float)); }
-        case GAT_TAP_Y:                               // one row per graph with readout on
+        case GAT_TAP_Y:                               // one row per graph with readout on, per pair with a pair head
             GAT_TRY(need(head_rows(c) * c->cfg.num_classes));
             if (!c->head.y_valid) GAT_TRY(gat_head_forward(c, nullptr, nullptr));     // after a fused head step: y = f(H_L, Wo), both still there
             return d2h(c, host, c->head.y, head_rows(c) * c->cfg.num_classes * sizeof(float));
@@ -63,6 +63,11 @@ int gat_tap(gat_ctx* c, int tensor, int32_t l, void* host, int64_t count) {
             if (!last) return fail(GAT_E_INVALID, "gat_tap: GAT_TAP_POOLED exists for the last layer only");
             GAT_TRY(need(c->readout.n_graphs * y.D));
             return d2h(c, host, c->readout.P, c->readout.n_graphs * y.D * sizeof(float));
+        case GAT_TAP_PAIRED:                          // what the last head forward (or head step) gathered
+            if (!pairs_on(c)) return fail(GAT_E_STATE, "gat_tap: GAT_TAP_PAIRED needs gat_set_pairs");
+            if (!last) return fail(GAT_E_INVALID, "gat_tap: GAT_TAP_PAIRED exists for the last layer only");
+            GAT_TRY(need(c->pairs.n_pairs * y.D));
+            return d2h(c, host, c->pairs.Q, c->pairs.n_pairs * y.D * sizeof(float));
         case GAT_TAP_G: {
             GAT_TRY(need(N * y.HD));
             if (norm_layer(c, l)) {                     // dL/dh_pre through the normalisation: the backward kernel's row function again, on the

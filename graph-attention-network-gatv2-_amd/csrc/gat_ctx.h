@@ -121,6 +121,18 @@ struct gat_ctx {
         float* part = nullptr; int32_t* part_arg = nullptr;
         float* P = nullptr; float* gP = nullptr; int32_t* argmax = nullptr;       // [n_graphs][D_last]
     } readout;
+    // Pair head (gatv2_abi.h "pair head"): mode, the pairs, the incidence index over the nodes (inc_ptr [n_rows + 1], inc [2 n_pairs]
+    // entries {p, other}), the scatter's work list and partial rows (allocated once at their upper bounds: a replacement of the pairs
+    // refills them), the rows Q the head reads and its gradient gQ [n_pairs][D_last].
+    struct Pairs {
+        int32_t mode = 0; int64_t n_pairs = 0;
+        int32_t* u = nullptr; int32_t* v = nullptr;
+        int32_t* inc_ptr = nullptr; int2* inc = nullptr;
+        int4* items = nullptr; int64_t n_items = 0;
+        int4* split = nullptr; int32_t n_split = 0;
+        float* part = nullptr;
+        float* Q = nullptr; float* gQ = nullptr;
+    } pairs;
     // The output head: block partials, results, the class probabilities y (valid: y holds the last forward's, not after a fused head step).
     struct Head {
         float* hb_partial = nullptr; double* loss_partial = nullptr; int32_t* correct_partial = nullptr;
@@ -269,8 +281,12 @@ inline bool norm_layer(const gat_ctx* c, int l) {
 inline bool res_route(const gat_ctx* c) { return res_on(c) || norm_on(c); }
 inline bool edge_feat_on(const gat_ctx* c) { return c->ef.dim > 0; }
 inline bool readout_on(const gat_ctx* c) { return c->readout.mode != GAT_READOUT_NONE; }
-// rows of the output head, hence of the labels, the masks and y: the graphs with readout on, else the nodes
-inline int64_t head_rows(const gat_ctx* c) { return readout_on(c) ? c->readout.n_graphs : c->graph.n_rows; }
+inline bool pairs_on(const gat_ctx* c) { return c->pairs.mode != GAT_PAIR_NONE; }
+// rows of the output head, hence of the labels, the targets, the masks and y: the pairs of a pair head, the graphs with readout on, else
+// the nodes (the two features exclude each other)
+inline int64_t head_rows(const gat_ctx* c) { return pairs_on(c) ? c->pairs.n_pairs : readout_on(c) ? c->readout.n_graphs : c->graph.n_rows; }
+// what one of them is called in the length checks' texts
+inline const char* head_row_name(const gat_ctx* c) { return pairs_on(c) ? "pair" : readout_on(c) ? "graph" : "node"; }
 // a step / phase on a context with edge_dim > 0 needs the attribute rows
 inline int check_edge_features(gat_ctx* c) {
     if (edge_feat_on(c) && !c->ef.have)

@@ -618,6 +618,40 @@ struct ReadoutBwdArgs {
 };
 int launch_readout_backward(const ReadoutBwdArgs& a, hipStream_t s);
 
+// ---- pair head (gat_pair.hip; the contract is in gatv2_abi.h "pair head") ------------------------------------------------
+// The backward's work list is the readout's plan over the incidence counts of the nodes (build_readout_plan on the incidence
+// row_ptr): the same 256 — a node of at most kPairSegEntries incidences is one item, a longer one is cut into segments of that many.
+constexpr int kPairSegEntries = kReadoutSegRows;
+// the rules of gat_set_pairs on u / v: -1, or 2p + (0: u, 1: v) of the lowest pair p with an endpoint outside [0, n_rows), u before v.
+// The device form is one pass, synchronises s and fetches the offending value.
+int64_t pair_check_host(const int32_t* u, const int32_t* v, int64_t n_pairs, int64_t n_rows);
+int pair_check_device(const int32_t* d_u, const int32_t* d_v, int64_t n_pairs, int64_t n_rows, int64_t* where, int32_t* value, hipStream_t s);
+std::string pair_problem_text(int64_t where, int32_t value, int64_t n_rows);
+// The incidence index of checked device pairs: inc_ptr [n_rows + 1], inc [2 n_pairs] entries {p, other endpoint}, every node's in
+// ascending 2p + role.  Through coo_sort / coo_fill; allocates and frees its temporaries, synchronises s.
+int pair_index_build(const int32_t* d_u, const int32_t* d_v, int64_t n_pairs, int64_t n_rows, int32_t* d_inc_ptr, int2* d_inc, hipStream_t s);
+struct PairFwdArgs {
+    const float* x; int64_t x_stride;       // [n_rows] rows of x_stride floats, the first `width` used
+    const int32_t* u; const int32_t* v;     // [n_pairs], checked
+    int64_t n_pairs;
+    float* q;                               // [n_pairs][width]
+    int32_t width, mode;
+};
+int launch_pair_forward(const PairFwdArgs& a, hipStream_t s);
+// gh[n][0:width] = sum over the incidences {p, other} of n of gq[p] (ADD) / gq[p] * x[other] (MUL); floats behind column `width` of a
+// gh row are not touched
+struct PairBwdArgs {
+    const float* gq;                        // [n_pairs][width]
+    const float* x; int64_t x_stride;       // MUL only (ADD: may be null)
+    const int2* inc;                        // the incidence entries
+    const int4* items; int64_t n_items;     // ReadoutPlan::items over the incidence row_ptr
+    const int4* split; int32_t n_split;     // ReadoutPlan::split
+    float* part;                            // [n_parts][width] partial rows of the segments
+    float* gh; int64_t gh_stride;
+    int32_t width, mode;
+};
+int launch_pair_backward(const PairBwdArgs& a, hipStream_t s);
+
 // train / validation masks (README R:134 "later"): labels_eff = mask ? label : ~label — the head kernels skip negative
 // labels (no loss, no count, dz = 0); eval_mask: fixed-order block partials of loss / #correct / #nodes over a mask
 int launch_apply_mask(const int32_t* labels, const uint8_t* mask, int32_t* eff, int64_t n, hipStream_t s);

@@ -610,6 +610,58 @@ int gat_op_readout_backward(const float* d_gpooled, const int32_t* d_graph_ptr, 
     return rc;
 }
 
+// The pair head's two kernels on caller-owned device pointers.  u / v are checked on the device before anything reads through them.
+static int op_pair_check(const char* who, const int32_t* d_u, const int32_t* d_v, int64_t n_pairs, int64_t n_rows, int32_t width, int32_t mode, hipStream_t s) {
+    if (!d_u || !d_v) return fail(GAT_E_INVALID, std::string(who) + ": null argument");
+    if (mode < GAT_PAIR_MUL || mode > GAT_PAIR_ADD) return fail(GAT_E_INVALID, std::string(who) + ": mode must be 1 (mul) or 2 (add)");
+    if (n_pairs < 1 || n_rows < 1 || n_rows >= 0x7fffffffLL || width < 1) return fail(GAT_E_INVALID, std::string(who) + ": bad sizes");
+    if (n_pairs >= (1ll << 30)) return fail(GAT_E_UNSUPPORTED, std::string(who) + ": n_pairs must be below 2^30 (the incidence keys 2p + role go through the 32-bit graph builder)");
+    int64_t where = -1; int32_t value = 0;
+    GAT_TRY(pair_check_device(d_u, d_v, n_pairs, n_rows, &where, &value, s));
+    if (where >= 0) return fail(GAT_E_INVALID, std::string(who) + ": " + pair_problem_text(where, value, n_rows));
+    return 0;
+}
+int gat_op_pair_forward(const float* d_x, int64_t x_stride, const int32_t* d_u, const int32_t* d_v, int64_t n_pairs, int64_t n_rows,
+                        int32_t width, int32_t mode, float* d_q, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    GAT_TRY(op_pair_check("gat_op_pair_forward", d_u, d_v, n_pairs, n_rows, width, mode, s));
+    if (!d_x || !d_q) return fail(GAT_E_INVALID, "gat_op_pair_forward: null argument");
+    if (x_stride < width) return fail(GAT_E_INVALID, "gat_op_pair_forward: x_stride below width");
+    PairFwdArgs a{};
+    a.x = d_x; a.x_stride = x_stride; a.u = d_u; a.v = d_v; a.n_pairs = n_pairs; a.q = d_q; a.width = width; a.mode = mode;
+    int rc = launch_pair_forward(a, s);
+    const hipError_t e = hipStreamSynchronize(s);
+    if (rc == 0 && e != hipSuccess) rc = fail((int)e, std::string("gat_op_pair_forward: ") + hipGetErrorString(e));
+    return rc;
+}
+int gat_op_pair_backward(const float* d_gq, const float* d_x, int64_t x_stride, const int32_t* d_u, const int32_t* d_v, int64_t n_pairs,
+                         int64_t n_rows, int32_t width, int32_t mode, float* d_gh, int64_t gh_stride, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    GAT_TRY(op_pair_check("gat_op_pair_backward", d_u, d_v, n_pairs, n_rows, width, mode, s));
+    if (!d_gq || !d_gh || (mode == GAT_PAIR_MUL && !d_x)) return fail(GAT_E_INVALID, "gat_op_pair_backward: null argument");
+    if (gh_stride < width) return fail(GAT_E_INVALID, "gat_op_pair_backward: gh_stride below width");
+    if (mode == GAT_PAIR_MUL && x_stride < width) return fail(GAT_E_INVALID, "gat_op_pair_backward: x_stride below width");
+    Scratch tmp;
+    int32_t* inc_ptr = nullptr; int2* inc = nullptr;
+    GAT_TRY(tmp.get(&inc_ptr, n_rows + 1)); GAT_TRY(tmp.get(&inc, 2 * n_pairs));
+    GAT_TRY(pair_index_build(d_u, d_v, n_pairs, n_rows, inc_ptr, inc, s));
+    std::vector<int32_t> ip((size_t)n_rows + 1);
+    GAT_HIP(hipMemcpy(ip.data(), inc_ptr, ip.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    ReadoutPlan plan;
+    build_readout_plan(ip.data(), n_rows, plan);
+    int4 *items = nullptr, *split = nullptr; float* part = nullptr;
+    GAT_TRY(tmp.get(&items, plan.n_items)); GAT_TRY(tmp.get(&split, plan.n_split)); GAT_TRY(tmp.get(&part, (int64_t)plan.n_parts * width));
+    GAT_HIP(hipMemcpyAsync(items, plan.items.data(), plan.items.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (plan.n_split > 0) GAT_HIP(hipMemcpyAsync(split, plan.split.data(), plan.split.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    PairBwdArgs a{};
+    a.gq = d_gq; a.x = d_x; a.x_stride = x_stride; a.inc = inc; a.items = items; a.n_items = plan.n_items; a.split = split; a.n_split = plan.n_split;
+    a.part = part; a.gh = d_gh; a.gh_stride = gh_stride; a.width = width; a.mode = mode;
+    int rc = launch_pair_backward(a, s);
+    const hipError_t e = hipStreamSynchronize(s);        // before the scratch is freed
+    if (rc == 0 && e != hipSuccess) rc = fail((int)e, std::string("gat_op_pair_backward: ") + hipGetErrorString(e));
+    return rc;
+}
+
 // ---- the six dense launchers on caller-owned device pointers: one launcher per call, exactly the caller's arguments ----------------
 static int op_dense_sizes(const char* who, int64_t n_rows, int32_t F, int32_t HD) {
     if (n_rows < 0 || n_rows >= 0x7fffffffLL || F < 1 || HD < 1) return fail(GAT_E_INVALID, std::string(who) + ": bad sizes (n_rows >= 0, F >= 1, HD >= 1)");

@@ -39,6 +39,10 @@
 // into one CSR, graph_ptr.txt of the dataset folder holds G+1 integers (graph g owns nodes graph_ptr[g] .. graph_ptr[g+1]-1), and
 // labels.txt, --train-mask and --val-mask files hold G lines.  The last layer's rows are pooled per graph in front of the output head;
 // the epoch lines keep their format, loss and accuracy are over graphs.  One rank only (a graph may straddle shards); --cache is not used.
+// --pairs mul|add: link prediction / edge classification (gatv2_abi.h "pair head"): pairs.txt of the dataset folder holds one node pair
+// "u v" per line (not necessarily an edge), labels.txt / targets.txt, --train-mask and --val-mask files hold one line per pair.  The output
+// head reads X[u]*X[v] / X[u]+X[v] of the last layer's rows; the epoch lines keep their format, loss and accuracy are over pairs.  One rank
+// only (an endpoint may live on another shard), not with --readout; --cache is not used.
 // --add-self-loops / --undirected / --coalesce: the graph is rebuilt on the device before training (gat_graph_from_coo:
 // GAT_GRAPH_SELF_LOOPS / SYMMETRIZE / COALESCE, applied in that order); a CSR dataset is expanded to an edge list first.
 // Edge-list dataset: a folder with edges.txt (one "src dst" pair per line, a message flows src -> dst) instead of
@@ -99,6 +103,7 @@ struct Options {
     int graph_flags = 0;                  // GAT_GRAPH_*: --add-self-loops, --undirected, --coalesce
     std::string readout;                  // --readout mean|sum|max: graph_ptr.txt of the dataset folder, one label per graph
     bool edge_features = false;           // --edge-features: edge_features.txt of the dataset folder enters the attention score
+    std::string pairs;                    // --pairs mul|add: pairs.txt of the dataset folder ("u v" per line), one label per pair
     std::string loss = "softmax";         // --loss softmax|bce|mse: bce / mse read targets.txt (rows of C floats, nan allowed) in place of labels.txt
 };
 
@@ -129,6 +134,10 @@ const char* kUsage =
     "            --readout mean|sum|max   graph classification: graph_ptr.txt of the dataset folder holds G+1 integers (graph g owns nodes\n"
     "                          graph_ptr[g] .. graph_ptr[g+1]-1); labels.txt, --train-mask and --val-mask then hold G lines; the last\n"
     "                          layer's rows are pooled per graph before the output head; loss and accuracy are over graphs (--ranks 1)\n"
+    "            --pairs mul|add    link prediction / edge classification: pairs.txt of the dataset folder holds one node pair \"u v\" per\n"
+    "                          line (pairs need not be edges); the output head reads X[u]*X[v] (mul) or X[u]+X[v] (add) of the last\n"
+    "                          layer's rows; labels.txt / targets.txt, --train-mask and --val-mask then hold one line per pair; loss and\n"
+    "                          accuracy are over pairs (--ranks 1, not with --readout)\n"
     "            --loss softmax|bce|mse   the output head's loss (default softmax: labels.txt as always).  bce (multi-label) and mse\n"
     "                          (regression) read targets.txt in place of labels.txt: one row of C floats per node — per graph with\n"
     "                          --readout — where nan marks a missing entry; C is the row width.  The epoch line prints the loss sum over\n"
@@ -220,6 +229,7 @@ Options parse_args(int argc, char** argv) {
         else if (a == "--norm-eps" && has_val) o.norm_eps = std::strtof(argv[++i], nullptr);
         else if (a == "--edge-features") o.edge_features = true;
         else if (a == "--readout" && has_val) o.readout = argv[++i];
+        else if (a == "--pairs" && has_val) o.pairs = argv[++i];
         else if (a == "--loss" && has_val) o.loss = argv[++i];
         else if (a == "--transport" && has_val) {
             o.transport = argv[++i];
@@ -419,7 +429,8 @@ int run(const Options& o, const RankEnv& env) {
     const int readout = o.readout == "mean" ? GAT_READOUT_MEAN : o.readout == "sum" ? GAT_READOUT_SUM : o.readout == "max" ? GAT_READOUT_MAX : GAT_READOUT_NONE;
     const bool edge_list = edge_list_dataset(path);
     const int loss_mode = o.loss == "bce" ? GAT_LOSS_BCE : o.loss == "mse" ? GAT_LOSS_MSE : GAT_LOSS_SOFTMAX_CE;
-    const bool use_cache = o.cache && !readout && loss_mode == GAT_LOSS_SOFTMAX_CE;       // (the cache holds labels)
+    const int pair_mode = o.pairs == "mul" ? GAT_PAIR_MUL : o.pairs == "add" ? GAT_PAIR_ADD : GAT_PAIR_NONE;
+    const bool use_cache = o.cache && !readout && !pair_mode && loss_mode == GAT_LOSS_SOFTMAX_CE;       // (the cache holds labels)
     std::vector<float> targets;                 // --loss bce|mse: [rows][TC] in place of the labels
     int64_t t_rows = 0; int TC = 0;
     auto load_supervision = [&]() {
@@ -428,20 +439,20 @@ int run(const Options& o, const RankEnv& env) {
         labels.assign((size_t)t_rows, 0);       // (one entry per head row: the length checks below apply to the targets alike)
     };
     const char* bad_length = loss_mode == GAT_LOSS_SOFTMAX_CE ? "Invalid labels length\n"
-                                                              : "Invalid targets length: targets.txt must hold one row per node (per graph with --readout)\n";
+                                                              : "Invalid targets length: targets.txt must hold one row per node (per graph with --readout, per pair with --pairs)\n";
     std::vector<int32_t> e_src, e_dst;
     if (edge_list) {
         load_features(path + "features.txt", x, N, F0);
         if (!env.graph.row_ptr && !load_edges(path + "edges.txt", e_src, e_dst)) return 1;
         load_supervision();
-        if (!readout && (int64_t)labels.size() != N) { std::cerr << bad_length; return 1; }
+        if (!readout && !pair_mode && (int64_t)labels.size() != N) { std::cerr << bad_length; return 1; }
     } else if (!(use_cache && load_cache(cache, path, x, N, F0, row_ptr, col_idx, labels))) {
         load_features(path + "features.txt", x, N, F0);
         load_ints(path + "row_ptr.txt", row_ptr);
         if ((int64_t)row_ptr.size() != N + 1) { std::cerr << "Invalid row_ptr length\n"; return 1; }
         load_ints(path + "col_idx.txt", col_idx);
         load_supervision();
-        if (!readout && (int64_t)labels.size() != N) { std::cerr << bad_length; return 1; }
+        if (!readout && !pair_mode && (int64_t)labels.size() != N) { std::cerr << bad_length; return 1; }
         if (use_cache) save_cache(cache, x, N, F0, row_ptr, col_idx, labels);
     }
     if (loss_mode != GAT_LOSS_SOFTMAX_CE) {
@@ -458,7 +469,20 @@ int run(const Options& o, const RankEnv& env) {
         if (labels.size() + 1 != graph_ptr.size()) { std::cerr << bad_length; return 1; }
         std::cout << "Readout: " << o.readout << " over " << graph_ptr.size() - 1 << " graphs" << std::endl;
     }
-    const int64_t NH = readout ? (int64_t)graph_ptr.size() - 1 : N;        // rows of the output head: graphs with --readout, else nodes
+    // --pairs: the node pairs; labels.txt / targets.txt then hold one line per pair
+    std::vector<int32_t> pair_u, pair_v;
+    if (pair_mode) {
+        std::vector<int32_t> uv;
+        load_ints(path + "pairs.txt", uv);
+        bool ok = !uv.empty() && uv.size() % 2 == 0;
+        for (size_t i = 0; ok && i < uv.size(); ++i) ok = uv[i] >= 0 && (int64_t)uv[i] < N;
+        if (!ok) { std::cerr << "Invalid pairs.txt: expected lines \"u v\" of two node indices below the node count\n"; return 1; }
+        for (size_t i = 0; i < uv.size(); i += 2) { pair_u.push_back(uv[i]); pair_v.push_back(uv[i + 1]); }
+        if (labels.size() != pair_u.size()) { std::cerr << bad_length; return 1; }
+        std::cout << "Pairs: " << o.pairs << " over " << pair_u.size() << " pairs" << std::endl;
+    }
+    // rows of the output head: pairs with --pairs, graphs with --readout, else nodes
+    const int64_t NH = pair_mode ? (int64_t)pair_u.size() : readout ? (int64_t)graph_ptr.size() - 1 : N;
     if (env.graph.row_ptr) {                    // built before the ranks were forked
         if (env.graph.n != N) { std::cerr << "Invalid labels length\n"; return 1; }
         row_ptr.assign(env.graph.row_ptr, env.graph.row_ptr + N + 1);
@@ -554,6 +578,7 @@ int run(const Options& o, const RankEnv& env) {
         check(gat_set_graph(ctx, row_ptr.data(), col_idx.data(), N, E, N, 0), "csr_to_coo_kernel");
         check(gat_set_features(ctx, x.data(), N, F0), "gat_set_features");
         if (readout) check(gat_set_readout(ctx, readout, graph_ptr.data(), NH), "gat_set_readout");      // before the labels: they are per graph
+        if (pair_mode) check(gat_set_pairs(ctx, pair_mode, pair_u.data(), pair_v.data(), NH), "gat_set_pairs");      // likewise: per pair
         if (loss_mode != GAT_LOSS_SOFTMAX_CE) check(gat_set_targets(ctx, targets.data(), NH, C), "gat_set_targets");
         else check(gat_set_labels(ctx, labels.data(), NH), "gat_set_labels");
         if (o.edge_features) check(gat_set_edge_features(ctx, ea.data(), E, Fe), "gat_set_edge_features");
@@ -736,7 +761,7 @@ int main(int argc, char** argv) {
     }
     // --help, --edge-features with what it cannot be combined with, and graph flags without a graph to apply them to, end here: before
     // anything touches the GPU
-    bool graph_flag = false, edge_feat_flag = false, readout_flag = false, targets_flag = false;
+    bool graph_flag = false, edge_feat_flag = false, readout_flag = false, targets_flag = false, pairs_flag = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--help") { std::cout << kUsage; return 0; }
@@ -744,6 +769,11 @@ int main(int argc, char** argv) {
             const std::string v = i + 1 < argc ? argv[i + 1] : "";
             if (v != "mean" && v != "sum" && v != "max") die("Error: --readout must be mean, sum or max\n");
             readout_flag = true;
+        }
+        if (a == "--pairs") {
+            const std::string v = i + 1 < argc ? argv[i + 1] : "";
+            if (v != "mul" && v != "add") die("Error: --pairs must be mul or add\n");
+            pairs_flag = true;
         }
         if (a == "--add-self-loops" || a == "--undirected" || a == "--coalesce") graph_flag = true;
         if (a == "--edge-features") edge_feat_flag = true;
@@ -761,7 +791,11 @@ int main(int argc, char** argv) {
             "gat_set_edge_features on every shard's own CSR)\n");
     if (readout_flag && multi)
         die("Error: --readout needs --ranks 1: a graph of the batch may straddle two destination-range shards\n");
-    if (graph_flag || readout_flag || targets_flag) {
+    if (pairs_flag && multi)
+        die("Error: --pairs needs --ranks 1: an endpoint of a pair may live on another destination-range shard\n");
+    if (pairs_flag && readout_flag)
+        die("Error: --pairs cannot be combined with --readout: the output head has one kind of row\n");
+    if (graph_flag || readout_flag || targets_flag || pairs_flag) {
         std::string root = "./data", name = "pubmed";
         bool root_given = false;
         for (int i = 1; i + 1 < argc; ++i) {
@@ -774,8 +808,10 @@ int main(int argc, char** argv) {
         const std::string dir = root + name + "/";
         if (readout_flag && !file_exists(dir + "graph_ptr.txt"))
             die("Error: --readout needs graph_ptr.txt (G+1 integers: the first node of every graph, then the node count) in " + dir + "\n");
+        if (pairs_flag && !file_exists(dir + "pairs.txt"))
+            die("Error: --pairs needs pairs.txt (one line \"u v\" per pair: two node indices) in " + dir + "\n");
         if (targets_flag && !file_exists(dir + "targets.txt"))
-            die("Error: --loss bce / mse needs targets.txt (one row of C floats per node, per graph with --readout; nan = missing) in " + dir + "\n");
+            die("Error: --loss bce / mse needs targets.txt (one row of C floats per node, per graph with --readout, per pair with --pairs; nan = missing) in " + dir + "\n");
         if (graph_flag && !file_exists(dir + "edges.txt") && !(file_exists(dir + "row_ptr.txt") && file_exists(dir + "col_idx.txt")))
             die("Error: --add-self-loops / --undirected / --coalesce need a graph: no edges.txt and no row_ptr.txt + col_idx.txt in " + dir + "\n");
     }

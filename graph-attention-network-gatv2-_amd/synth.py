@@ -222,6 +222,26 @@ def targets(kind: str, n_rows: int, n_cols: int, seed: int = GRAPH_SEED + 3, mis
     return t.reshape(int(n_rows), int(n_cols))
 
 
+def link_pairs(row_ptr, col_idx, n_pos: int, n_neg: int, seed: int = GRAPH_SEED + 4):
+    """Node pairs for the pair head (gatv2_abi.h "pair head"): n_pos positives drawn (with replacement) from the graph's own edges —
+    pair (source, destination) of a hash-drawn CSR edge, t = 1 — then n_neg negatives, uniform node pairs with t = 0 (not filtered
+    against the edges: on a sparse graph a drawn pair is an edge with probability E / N^2).  Hash-drawn per pair with the generators'
+    counter hash: a function of the arguments alone.  -> (u [P] int32, v [P] int32, t [P] float32), P = n_pos + n_neg."""
+    rp, ci = np.asarray(row_ptr, np.int64), np.asarray(col_idx, np.int64)
+    n, e = len(rp) - 1, len(ci)
+    if n_pos < 0 or n_neg < 0 or n < 1 or (n_pos > 0 and e < 1):
+        raise ValueError(f"link_pairs: bad arguments (n_pos={n_pos}, n_neg={n_neg}, {n} nodes, {e} edges)")
+    pe = (_hash(seed, 19, np.arange(n_pos, dtype=np.uint64)) % _U64(max(e, 1))).astype(np.int64)
+    pos_v = np.searchsorted(rp, pe, side="right") - 1            # the destination row of edge pe
+    idx = np.arange(n_neg, dtype=np.uint64)
+    neg_u = (_hash(seed, 23, idx) % _U64(n)).astype(np.int64)
+    neg_v = (_hash(seed, 29, idx) % _U64(n)).astype(np.int64)
+    u = np.concatenate([ci[pe], neg_u]).astype(np.int32)
+    v = np.concatenate([pos_v, neg_v]).astype(np.int32)
+    t = np.concatenate([np.ones(n_pos, np.float32), np.zeros(n_neg, np.float32)])
+    return u, v, t
+
+
 def graph_batch(n_graphs: int, nodes_lo: int, nodes_hi: int, avg_degree: float, seed: int = GRAPH_SEED, f: int = 32, c: int = 4):
     """A batch of n_graphs small graphs (molecule-like) packed block-diagonally into one CSR, for the graph-level readout
     (gatv2_abi.h "graph-level readout"): graph g has a size drawn uniformly from [nodes_lo, nodes_hi] and owns the contiguous nodes

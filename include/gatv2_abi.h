@@ -313,8 +313,10 @@ enum {
                                                       holds, likewise (all 1 at edge_p = 0; needs gat_set_dropedge or gat_set_dropout).  Like the two
                                                       taps above it reports the mask of the SETTING, whatever the mode: in eval mode the passes drop
                                                       nothing, the tap still shows what a training forward at that counter value draws */
-    GAT_TAP_POOLED = 18     /* [n_graphs][D_last]    the pooled rows the head reads (last layer only; needs gat_set_readout, see
+    GAT_TAP_POOLED = 18,    /* [n_graphs][D_last]    the pooled rows the head reads (last layer only; needs gat_set_readout, see
                                                       "graph-level readout", where GAT_TAP_Y becomes [n_graphs][C]) */
+    GAT_TAP_PAIRED = 19     /* [n_pairs][D_last]     the rows the head reads (last layer only; needs gat_set_pairs, see "pair head",
+                                                      where GAT_TAP_Y becomes [n_pairs][C]) */
 };
 int gat_tap(gat_ctx* ctx, int tensor, int32_t layer, void* host_dst, int64_t count);
 
@@ -597,6 +599,61 @@ int gat_op_readout_forward(const float* d_x, int64_t x_stride, const int32_t* d_
                            int32_t width, int32_t mode, float* d_pooled, int32_t* d_argmax, void* stream);
 int gat_op_readout_backward(const float* d_gpooled, const int32_t* d_graph_ptr, int64_t n_graphs, int64_t n_rows, int32_t width,
                             int32_t mode, const int32_t* d_argmax, float* d_gh, int64_t gh_stride, void* stream);
+
+/* ---- pair head (beyond the reference, which has one label per node: link prediction, edge classification, edge regression) ----
+ * ONE label per pair of nodes.  A list of pairs (u_p, v_p), p = 0 .. P-1, both rows of the context; they need not be edges of the graph
+ * (negatives are not).  With X = the last layer's output ([n_rows][D_last], after the mean over heads) the head's input rows are
+ *     GAT_PAIR_MUL   Q[p][d] = X[u_p][d] * X[v_p][d]      dL/dX[n][d] = sum over incidences (p, role) of n:  gQ[p][d] * X[other(p, role)][d]
+ *     GAT_PAIR_ADD   Q[p][d] = X[u_p][d] + X[v_p][d]      dL/dX[n][d] = sum over incidences (p, role) of n:  gQ[p][d]
+ * An incidence of node n is a pair with u_p == n (role 0, other = v_p) or v_p == n (role 1, other = u_p).  A pair with u_p == v_p is two
+ * incidences of the same node (the gradient of x*x is 2 x gQ, no special case); duplicate pairs are legal and count separately.
+ * The output head runs unchanged on Q with P rows where it had n_rows: z = Q Wo^T, the context's loss mode, gradWo += dz^T Q, gQ = dz Wo.
+ * Wo keeps its shape [C][D_last]: no parameter group changes size.  With C = 1, BCE and Wo fixed at ones this is GAE's dot-product
+ * decoder; with C > 1 a DistMult-style relation scorer or an edge classifier; MSE gives edge regression.  Labels, targets, the training
+ * mask, gat_eval_mask, gat_target_count, GAT_TAP_Y, loss_sum and n_correct are all PER PAIR; the train / validation / test pair sets of a
+ * link-prediction run are one pair list with masks over it.  Everything from dL/dX downward is the code of a context without the feature.
+ * gat_set_pairs[_device]: the first call comes AFTER the graph is set and BEFORE the labels or targets (else GAT_E_STATE: the head buffers
+ *   are sized by P).  mode == 0 (GAT_PAIR_NONE) is the default and leaves the context exactly as it is: same buffers, same kernels, same
+ *   launch counts, bitwise the same results (the other arguments are not read).  mode outside 0..2: GAT_E_INVALID.
+ *   A later call with the same non-zero mode and the same n_pairs REPLACES the pairs (negatives resampled per epoch): the values go into
+ *   the same device buffers, the incidence index and the work list are rebuilt, and a captured gat_step_graph is re-armed as by
+ *   gat_bind_table (the work list changes: the next step runs eagerly, the one after captures again).  Another mode or n_pairs: GAT_E_STATE.
+ *   1 <= n_pairs < 2^30 (the incidence keys 2p + role go through the 32-bit graph builder), more: GAT_E_UNSUPPORTED; n_pairs < 1:
+ *   GAT_E_INVALID.  A u or v outside [0, n_rows): GAT_E_INVALID, "pair <p> has u|v <value> outside [0, n_rows)" for the lowest offending
+ *   pair (u before v).  The device form finds this in one pass on the device before any kernel reads through the arrays (as
+ *   gat_graph_check_device does); on failure the context keeps the pairs it had.  The arrays are copied.
+ * With a pair head, gat_set_labels[_device], gat_set_targets[_device], gat_set_train_mask, gat_eval_mask and gat_target_count take
+ *   n_pairs where they took n_rows (another length: GAT_E_INVALID, the text says "one per pair"); gat_eval_mask's n_nodes counts pairs.
+ * Where it runs.  Forward: a pair takes LPR lanes (float4 loads when D_last is a multiple of 4, scalar loads otherwise, any D_last >= 1),
+ *   a wave's other lane groups take the next pairs; two gathered rows in, one contiguous row of Q out, one fp32 operation per entry.
+ *   Backward: a node-major PULL over an incidence index — a CSR over the nodes with every node's entries {p, other} in ascending
+ *   2p + role, built on the device at gat_set_pairs* by the graph builder's sort — so that every row of the head's gradient buffer is
+ *   written exactly once by one wave (zeros included), with no float atomics: bitwise reproducible, a function of the pair list alone.  A
+ *   node of at most 256 incidences is one work item, a longer one is cut into 256-entry segments whose partial rows a second small kernel
+ *   adds in ascending order.  The launches are part of gat_head_forward (which gathers first) and gat_head_backward (which ends with the
+ *   scatter), of gat_forward / gat_backward, gat_step and a gat_step_graph replay (no host synchronisation), timed under GAT_K_HEAD_FWD /
+ *   GAT_K_HEAD_BWD.  GAT_TAP_PAIRED returns Q.
+ * Works with every (H, D) family incl. both generic ones, bf16 storage (X, Q, gQ and the head's gradient stay fp32), keep_taps, eval
+ *   mode, all three regularisers, residual, bias, norm, edge features and all three loss modes.
+ * Refused with GAT_E_UNSUPPORTED: a destination-range shard (n_table != n_rows) or a context with a transport (an endpoint may live on
+ *   another shard; gat_comm_init_* on a pair context is refused alike); flat_lrelu_index = 1; the experiment library with GAT_DBG set; a
+ *   pair head with a readout (whichever of the two is set second).  GAT_FUSE_LAST=1 is not used by a pair context.
+ * gat_algorithmic_bytes (context form): unchanged with the feature off.  On, the head classes are priced with P rows, and misc gains, at
+ *   4 bytes: forward 2P (indices) + 2 P D_last (gathered rows) + P D_last (Q); backward 4P (incidence entries) + 2 P D_last (gQ rows, once
+ *   per incidence) + 2 P D_last (X rows, MUL only) + N D_last (the head's gradient rows). */
+enum { GAT_PAIR_NONE = 0, GAT_PAIR_MUL = 1, GAT_PAIR_ADD = 2 };
+int gat_set_pairs(gat_ctx* ctx, int32_t mode, const int32_t* u, const int32_t* v, int64_t n_pairs);            /* host arrays [n_pairs] */
+int gat_set_pairs_device(gat_ctx* ctx, int32_t mode, const int32_t* d_u, const int32_t* d_v, int64_t n_pairs); /* checked on the device */
+int gat_pairs_info(gat_ctx* ctx, int32_t* mode, int64_t* n_pairs);                                             /* (0, 0) while off; pointers may be NULL */
+/* The two kernels as stateless seams on caller-owned DEVICE pointers (current device): d_x rows of x_stride >= width floats (may be NULL
+ * in the backward of GAT_PAIR_ADD), d_q / d_gq [n_pairs][width]; the backward writes floats 0..width-1 of every d_gh row (n_rows rows,
+ * gh_stride >= width floats apart) and nothing behind them.  Each call checks d_u / d_v with gat_set_pairs' rules (same codes and texts),
+ * the backward builds the incidence index and the work list, allocates and frees its scratch, and both synchronise `stream` (may be
+ * NULL): parity seams, not the fast path. */
+int gat_op_pair_forward(const float* d_x, int64_t x_stride, const int32_t* d_u, const int32_t* d_v, int64_t n_pairs, int64_t n_rows,
+                        int32_t width, int32_t mode, float* d_q, void* stream);
+int gat_op_pair_backward(const float* d_gq, const float* d_x, int64_t x_stride, const int32_t* d_u, const int32_t* d_v, int64_t n_pairs,
+                         int64_t n_rows, int32_t width, int32_t mode, float* d_gh, int64_t gh_stride, void* stream);
 
 /* The dense launchers (the W_l / W_r projections, their two backward products and the residual's three) as stateless seams on caller-owned
  * DEVICE pointers (current device).  Each call runs exactly ONE launcher with exactly the caller's arguments and synchronises `stream`

@@ -1,0 +1,487 @@
+"""The pair head on the GPU (include/gatv2_abi.h "pair head"): the two kernels through their stateless seams (the gather bitwise, the
+scatter within the rounding bound of its sums); the whole step of every dispatcher family against the fp64 model of tests/pair_ref.py at
+the project's bars (1e-4 of max-abs, 1e-2 with bf16 storage); the step paths against each other; replacing the pairs; eval_mask over
+pairs; the state and refusal matrix; off is the parent; the train_edge host.
+
+tests/test_pair_cpu.py proves on the host that every parity case has a parameter seed clear of the LeakyReLU kinks and of the loss clamp."""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+
+import feature_cases as FC
+import loss_ref as LR
+import pair_ref as PR
+import parity
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "graph-attention-network-gatv2-_amd", "train_edge")
+
+E_INVALID, E_STATE, E_UNSUPPORTED = 10001, 10002, 10004
+UNIT = 2.0 ** -24
+WIDTHS = [1, 4, 5, 8, 13, 16, 32, 64, 65]
+PAIR_COUNTS = [1, 2, 63, 64, 65, 1000]
+N_ROWS = 300
+INCIDENCES = [0, 1, 2, 255, 256, 257, 511, 512, 513, 700]       # of nodes 0 .. 9: the boundaries of the 256-entry segments
+SENTINEL = -12345.0
+
+
+@pytest.fixture(scope="module")
+def torch_dev():
+    import torch
+    assert torch.cuda.is_available(), "the seam tests need the GPU"
+    return torch, torch.device("cuda:0")
+
+
+# -- the seams
+@pytest.mark.parametrize("width", WIDTHS)
+def test_seam_forward_is_bitwise(pkg, torch_dev, width):
+    A = pkg.abi
+    torch, dev = torch_dev
+    rng = np.random.default_rng(200 + width)
+    x = rng.standard_normal((N_ROWS, width)).astype(np.float32)
+    for x_stride in (width, width + 3, width + 4):
+        xs = np.full((N_ROWS, x_stride), SENTINEL, np.float32)
+        xs[:, :width] = x
+        d_x = torch.from_numpy(xs).to(dev)
+        for n_pairs in PAIR_COUNTS:
+            u = rng.integers(0, N_ROWS, n_pairs).astype(np.int32); v = rng.integers(0, N_ROWS, n_pairs).astype(np.int32)
+            v[0] = u[0]                                                      # a u == v pair
+            if n_pairs > 1:
+                u[-1], v[-1] = u[0], v[0]                                    # a duplicate pair
+            d_u, d_v = torch.from_numpy(u).to(dev), torch.from_numpy(v).to(dev)
+            for mode in PR.MODES:
+                d_q = torch.full((n_pairs + 1, width), SENTINEL, device=dev)         # one row of padding behind
+                A.op_pair_forward(d_x.data_ptr(), x_stride, d_u.data_ptr(), d_v.data_ptr(), n_pairs, N_ROWS, width, mode, d_q.data_ptr())
+                q = d_q.cpu().numpy()
+                want = x[u] * x[v] if mode == "mul" else x[u] + x[v]         # np.float32: one rounding per entry
+                assert np.array_equal(q[:n_pairs], want), (mode, x_stride, n_pairs)
+                assert np.all(q[n_pairs] == SENTINEL), (mode, x_stride, n_pairs)
+        assert np.array_equal(d_x.cpu().numpy(), xs)                         # the input and its padding are untouched
+
+
+def backward_pairs(rng):
+    """Pairs on N_ROWS nodes in which node k < 10 has exactly INCIDENCES[k] incidences (as u and as v in turn, a u == v pair where the
+    count allows, a duplicate pair), nodes 10 .. 19 are in no pair, and the partners are spread over nodes 20 .. N_ROWS - 1."""
+    us, vs = [], []
+    for k, cnt in enumerate(INCIDENCES):
+        left = cnt
+        if cnt >= 2:
+            us.append(k); vs.append(k); left -= 2                            # u == v: two incidences of the node
+        partners = rng.integers(20, N_ROWS, left)
+        if left >= 2:
+            partners[1] = partners[0]                                        # (k, partner) twice — in both roles below: a duplicate when left >= 3
+        if left >= 3:
+            partners[2] = partners[0]
+        for j, o in enumerate(partners):
+            if j % 2 == 0:
+                us.append(k); vs.append(int(o))
+            else:
+                us.append(int(o)); vs.append(k)
+    order = rng.permutation(len(us))
+    return np.asarray(us, np.int32)[order], np.asarray(vs, np.int32)[order]
+
+
+@pytest.mark.parametrize("width", WIDTHS)
+def test_seam_backward_within_the_rounding_bound(pkg, torch_dev, width):
+    A = pkg.abi
+    torch, dev = torch_dev
+    rng = np.random.default_rng(300 + width)
+    u, v = backward_pairs(rng)
+    n_pairs = len(u)
+    cnt = np.bincount(u, minlength=N_ROWS) + np.bincount(v, minlength=N_ROWS)
+    assert cnt[:10].tolist() == INCIDENCES and np.all(cnt[10:20] == 0)
+    x = rng.standard_normal((N_ROWS, width)).astype(np.float32)
+    gq = rng.standard_normal((n_pairs, width)).astype(np.float32)
+    x64, gq64 = x.astype(np.float64), gq.astype(np.float64)
+    d_x, d_gq = torch.from_numpy(x).to(dev), torch.from_numpy(gq).to(dev)
+    d_u, d_v = torch.from_numpy(u).to(dev), torch.from_numpy(v).to(dev)
+    for mode in PR.MODES:
+        want = np.zeros((N_ROWS, width)); sabs = np.zeros((N_ROWS, width))
+        tu = gq64 * x64[v] if mode == "mul" else gq64                        # the term pair p sends to u_p
+        tv = gq64 * x64[u] if mode == "mul" else gq64
+        np.add.at(want, u, tu); np.add.at(want, v, tv)
+        np.add.at(sabs, u, np.abs(tu)); np.add.at(sabs, v, np.abs(tv))
+        # a cnt-term fp32 sum in any order, one rounding per product (MUL): (cnt + 2) 2^-24 sum|gQ X_other|; ADD: cnt 2^-24 sum|gQ|
+        bound = ((cnt + 2) if mode == "mul" else cnt)[:, None] * UNIT * sabs
+        for gh_stride in ([width, 16] if width <= 8 else [width]):
+            runs = []
+            for _ in range(2):
+                d_gh = torch.full((N_ROWS, gh_stride), SENTINEL, device=dev)
+                A.op_pair_backward(d_gq.data_ptr(), d_x.data_ptr() if mode == "mul" else 0, width, d_u.data_ptr(), d_v.data_ptr(), n_pairs,
+                                   N_ROWS, width, mode, d_gh.data_ptr(), gh_stride)
+                runs.append(d_gh.cpu().numpy())
+            gh = runs[0]
+            assert np.array_equal(runs[0], runs[1]), (mode, gh_stride, "not reproducible")
+            err = np.abs(gh[:, :width].astype(np.float64) - want)
+            assert np.all(err <= bound), (mode, gh_stride, float((err - bound).max()), int(np.argmax((err - bound).max(1))))
+            assert np.all(gh[cnt == 0, :width] == 0), (mode, gh_stride)      # rows without incidences: exactly 0, and written
+            assert np.all(gh[:, width:] == SENTINEL), (mode, gh_stride)      # the decision bytes' place stays
+            parity.record(f"seam bwd {mode} w{width} s{gh_stride} err/bound", float((err / np.maximum(bound, 1e-300))[cnt > 0].max()), 1.0)
+
+
+def test_seams_refuse_bad_pairs(pkg, torch_dev):
+    """An endpoint outside [0, n_rows): GAT_E_INVALID naming the lowest pair, u or v and the value, before any kernel reads through it."""
+    A = pkg.abi
+    torch, dev = torch_dev
+    n, w = 20, 4
+    d_x = torch.zeros((n, w), device=dev); d_q = torch.zeros((5, w), device=dev); d_gh = torch.zeros((n, w), device=dev)
+    for u, v, text in (([0, 1, 20, 3, 99], [0, 1, 2, 3, 4], "pair 2 has u 20 outside [0, 20)"),
+                       ([0, 1, 2, 3, 4], [0, -1, 2, 2000000000, 4], "pair 1 has v -1 outside [0, 20)"),
+                       ([0, 1, 2, 50, 4], [0, 1, 2, 60, 4], "pair 3 has u 50 outside [0, 20)"),
+                       ([0, 1, 2, 3, 4], [0, 1, 2, 3, 20], "pair 4 has v 20 outside [0, 20)")):
+        d_u = torch.tensor(u, dtype=torch.int32, device=dev); d_v = torch.tensor(v, dtype=torch.int32, device=dev)
+        for call in (lambda: A.op_pair_forward(d_x.data_ptr(), w, d_u.data_ptr(), d_v.data_ptr(), 5, n, w, "mul", d_q.data_ptr()),
+                     lambda: A.op_pair_backward(d_q.data_ptr(), d_x.data_ptr(), w, d_u.data_ptr(), d_v.data_ptr(), 5, n, w, "add", d_gh.data_ptr(), w)):
+            with pytest.raises(A.GatError) as ei:
+                call()
+            assert ei.value.code == E_INVALID and text in str(ei.value), str(ei.value)
+    d_u = torch.zeros(5, dtype=torch.int32, device=dev)
+    with pytest.raises(A.GatError) as ei:
+        A.op_pair_forward(d_x.data_ptr(), w, d_u.data_ptr(), d_u.data_ptr(), 5, n, w, 3, d_q.data_ptr())
+    assert ei.value.code == E_INVALID
+    torch.cuda.synchronize()
+
+
+# -- the whole step against the fp64 model
+TAPS = ["hout", "G"]
+
+
+def loss_rows(ci):
+    """What the loss is divided by: the pairs (softmax), the contributing target entries (BCE / MSE)."""
+    if ci["loss"] == PR.SOFTMAX:
+        return len(ci["u"])
+    return max(1, int(LR.contributes(ci["sup"], ci["mask"]).sum()))
+
+
+def compare_all(pkg, ctx, ci, ref, loss, tol):
+    """loss per pair, GAT_TAP_PAIRED, GAT_TAP_Y, hout and G of both layers, all eight gradient groups."""
+    A = pkg.abi
+    FC.compare(pkg, ctx, dict(ci["g"], n=loss_rows(ci)), ci["cfg"], ref, loss, tol, TAPS, FC.GROUPS)
+    parity.check_rel("paired", ctx.tap(A.TAP_PAIRED, ci["cfg"].L - 1), ref["paired"].detach().numpy(), tol)
+    parity.check_abs("y", ctx.tap(A.TAP_Y), ref["y"], tol)
+    got = ctx.grads_get(A.PARAM_WE)
+    if ref["We"] is None:
+        assert got.size == 0
+    else:
+        parity.check_rel("grad We", got, ref["We"].grad.numpy(), tol)
+
+
+CASES = PR.cases(FC)
+
+
+@pytest.mark.parametrize("case", CASES, ids=[PR.case_id(c) for c in CASES])
+def test_step_against_fp64(pkg, orc, case):
+    ci = PR.case_inputs(case)
+    ref = PR.model_of(ci)
+    tol = 1e-2 if ci["bf16"] else 1e-4
+    with PR.make_ctx(pkg, ci) as ctx:
+        assert ctx.pairs_info() == (pkg.abi.PAIR_MODES[ci["mode"]], len(ci["u"])) and ctx.head_rows == len(ci["u"])
+        loss, correct = ctx.step()
+        compare_all(pkg, ctx, ci, ref, loss, tol)
+        if ci["loss"] == PR.SOFTMAX and not ci["bf16"]:
+            keep = np.ones(len(ci["u"]), bool) if ci["mask"] is None else ci["mask"]
+            assert correct == int(((np.argmax(ref["y"], axis=1) == ci["sup"]) & keep).sum())
+
+
+# -- equal forms
+def all_grads(A, c):
+    return [c.grads_get(k) for k in A.PARAM_GROUPS]
+
+
+D8 = ("records_d8", [8, 8], [8, 8], {})
+
+
+@pytest.mark.parametrize("mode", PR.MODES)
+def test_paths_agree(pkg, orc, mode):
+    """gat_step, gat_forward + gat_backward and the phase API.  As in tests/test_readout.py, records_d8 takes the fused head step in
+    gat_step and the two-kernel head elsewhere: gradWo at 1e-5 there (another summation order of the same terms) and the loss at 1e-5,
+    everything else bitwise; a gat_step_graph replay is bitwise the eager step."""
+    A = pkg.abi
+    ci = PR.case_inputs((*D8, "plain", mode, PR.SOFTMAX))
+    with PR.make_ctx(pkg, ci) as s1, PR.make_ctx(pkg, ci) as fb, PR.make_ctx(pkg, ci) as ph, PR.make_ctx(pkg, ci) as gr:
+        l1 = s1.step(); g1 = all_grads(A, s1)
+        lf = fb.forward(); fb.backward(); gf = all_grads(A, fb)
+        for l in range(2):
+            ph.layer_project(l); ph.layer_forward_edges(l)
+        lp = ph.head_forward()
+        ph.head_backward()
+        for l in (1, 0):
+            ph.layer_backward_edges(l); ph.layer_backward_dense(l)
+        gp = all_grads(A, ph)
+        assert lf == lp and lf[1] == l1[1] and abs(lf[0] - l1[0]) <= 1e-5 * abs(l1[0])
+        for k in A.PARAM_GROUPS:
+            assert np.array_equal(gf[k], gp[k]), k                       # the same kernels in both
+            if k == A.PARAM_WO:
+                assert parity.rel_err(gf[k], g1[k]) <= 1e-5
+            else:
+                assert np.array_equal(gf[k], g1[k]), k
+        assert np.array_equal(fb.tap(A.TAP_PAIRED, 1), s1.tap(A.TAP_PAIRED, 1))
+        gr.step_graph(True)
+        outs = []
+        for _ in range(3):                                               # eager warm-up, capture + replay, replay
+            gr.zero_grad()
+            outs.append((gr.step(), all_grads(A, gr)))
+        for (lg, gg) in outs:
+            assert lg == l1
+            for k in A.PARAM_GROUPS:
+                assert np.array_equal(gg[k], g1[k]), k
+
+
+def test_replacing_the_pairs(pkg, orc, torch_dev):
+    """A later gat_set_pairs with the same mode and length — also after a captured replay, also in the device form — gives bitwise the
+    result of a fresh context with the new pairs; the model agrees; a bad replacement leaves the pairs in place."""
+    A = pkg.abi
+    torch, dev = torch_dev
+    ci = PR.case_inputs((*D8, "plain", "mul", PR.SOFTMAX))
+    n = ci["g"]["n"]
+    u2, v2 = PR.pair_list(n, seed=99, hub=12)                             # another long node, other partners
+    assert len(u2) == len(ci["u"])
+    with PR.make_ctx(pkg, ci, u=u2, v=v2) as fresh, PR.make_ctx(pkg, ci) as live, PR.make_ctx(pkg, ci) as cap, PR.make_ctx(pkg, ci) as devc:
+        want = fresh.step(); gw = all_grads(A, fresh)
+        first = live.step(); g_first = all_grads(A, live)
+        bad = u2.copy(); bad[5] = n
+        with pytest.raises(A.GatError) as ei:
+            live.set_pairs("mul", bad, v2)
+        assert ei.value.code == E_INVALID and f"pair 5 has u {n} outside [0, {n})" in str(ei.value)
+        d_bad = torch.from_numpy(bad).to(dev); d_v2 = torch.from_numpy(v2).to(dev); d_u2 = torch.from_numpy(u2).to(dev)
+        with pytest.raises(A.GatError) as ei:
+            live.set_pairs_device("mul", d_bad.data_ptr(), d_v2.data_ptr(), len(bad))
+        assert ei.value.code == E_INVALID and f"pair 5 has u {n} outside [0, {n})" in str(ei.value)
+        live.zero_grad()
+        assert live.step() == first                                      # the context kept the pairs it had
+        for k in A.PARAM_GROUPS:
+            assert np.array_equal(live.grads_get(k), g_first[k]), k
+        for c, dev_form in ((live, False), (devc, True)):
+            if dev_form:
+                c.set_pairs_device("mul", d_u2.data_ptr(), d_v2.data_ptr(), len(u2))
+            else:
+                c.set_pairs("mul", u2, v2)
+            c.zero_grad()
+            assert c.step() == want
+            for k in A.PARAM_GROUPS:
+                assert np.array_equal(c.grads_get(k), gw[k]), (k, dev_form)
+        cap.step_graph(True)
+        for _ in range(3):                                               # warm-up, capture + replay, replay: on the first pairs
+            cap.zero_grad()
+            assert cap.step() == first
+        cap.set_pairs("mul", u2, v2)                                     # re-arms: eager, capture + replay, replay on the new pairs
+        for _ in range(3):
+            cap.zero_grad()
+            assert cap.step() == want
+            for k in A.PARAM_GROUPS:
+                assert np.array_equal(cap.grads_get(k), gw[k]), k
+        ref = PR.model_of(ci, u2, v2)
+        assert abs(want[0] - ref["loss"].item()) / len(u2) < 1e-4
+        parity.check_rel("paired (replaced)", fresh.tap(A.TAP_PAIRED, 1), ref["paired"].detach().numpy(), 1e-4)
+
+
+def test_eval_mask_over_pairs(pkg, orc):
+    A = pkg.abi
+    ci = PR.case_inputs((*D8, "plain", "mul", PR.SOFTMAX))
+    ref = PR.model_of(ci)
+    n_pairs = len(ci["u"])
+    pred_ok = np.argmax(ref["y"], axis=1) == ci["sup"]
+    rng = np.random.default_rng(8)
+    with PR.make_ctx(pkg, ci) as ctx:
+        ctx.step()                                                       # the fused head step: eval_mask re-runs the head forward
+        for mask in (np.ones(n_pairs, bool), rng.random(n_pairs) > 0.8, np.arange(n_pairs) == 7):
+            loss, correct, count = ctx.eval_mask(mask)
+            assert count == int(mask.sum()) and correct == int((pred_ok & mask).sum())
+            assert abs(loss - ref["loss_per_pair"][mask].sum()) / mask.sum() < 1e-4
+        with pytest.raises(A.GatError) as ei:
+            ctx.eval_mask(np.ones(ci["g"]["n"], bool))                    # per node: the wrong length
+        assert ei.value.code == E_INVALID and "one per pair" in str(ei.value)
+    cb = PR.case_inputs((*D8, "plain", "mul", PR.BCE))                    # the BCE head: a validation mask of pairs, and the entry count
+    rb = PR.model_of(cb)
+    with PR.make_ctx(pkg, cb) as ctx:
+        ctx.step()
+        val = rng.random(n_pairs) > 0.7
+        want = LR.head_ref(rb["paired"].detach().numpy(), ctx.params_get(A.PARAM_WO), cb["sup"], val, PR.BCE)
+        loss, correct, count = ctx.eval_mask(val)
+        assert count == int(val.sum()) and ctx.target_count(val) == int(val.sum())
+        assert abs(loss - want.l.sum()) / val.sum() < 1e-4
+        sure, slack = LR.count_bounds(want)
+        assert sure <= correct <= sure + slack
+
+
+# -- states and refusals
+def test_state_and_refusal_matrix(pkg, orc, torch_dev):
+    A = pkg.abi
+    torch, dev = torch_dev
+    g = FC.parity_graph()
+    n = g["n"]
+    u, v = PR.pair_list(n)
+    P = len(u)
+    plab = PR.pair_labels(P, g["c"])
+
+    def fresh(**kw):
+        c = pkg.GatContext([8, 8], [8, 8], g["f"], g["c"], **kw)
+        c.set_graph(g["row_ptr"], g["col_idx"])
+        return c
+
+    def refused(code, fn, text=None):
+        with pytest.raises(A.GatError) as ei:
+            fn()
+        assert ei.value.code == code, str(ei.value)
+        if text is not None:
+            assert text in str(ei.value), str(ei.value)
+
+    with pkg.GatContext([8, 8], [8, 8], g["f"], g["c"]) as c:            # before the graph
+        refused(E_STATE, lambda: c.set_pairs("mul", u, v), "graph first")
+    with fresh() as c:                                                   # after the labels
+        c.set_labels(g["labels"])
+        refused(E_STATE, lambda: c.set_pairs("mul", u, v), "before gat_set_labels")
+        c.set_pairs(0)                                                   # mode 0 is always a no-op
+        assert c.pairs_info() == (0, 0)
+    with fresh() as c:
+        refused(E_INVALID, lambda: c.set_pairs(3, u, v))
+        refused(E_INVALID, lambda: c.set_pairs(-1, u, v))
+        refused(E_INVALID, lambda: c.set_pairs("mul", u[:0], v[:0]))      # n_pairs >= 1
+        refused(E_UNSUPPORTED, lambda: c.set_pairs_device("mul", 8, 8, 1 << 30), "2^30")       # (refused before the pointers are read)
+        for which, arr in (("u", u), ("v", v)):
+            bad = arr.copy(); bad[9] = -4; bad[200] = n + 3
+            args = (bad, v) if which == "u" else (u, bad)
+            refused(E_INVALID, lambda: c.set_pairs("add", *args), f"pair 9 has {which} -4 outside [0, {n})")
+            d_a, d_b = (torch.from_numpy(a).to(dev) for a in args)
+            refused(E_INVALID, lambda: c.set_pairs_device("add", d_a.data_ptr(), d_b.data_ptr(), P), f"pair 9 has {which} -4 outside [0, {n})")
+        torch.cuda.synchronize()                                         # the device form refused without a fault
+        assert c.pairs_info() == (0, 0)                                  # nothing stuck
+        d_u, d_v = torch.from_numpy(u).to(dev), torch.from_numpy(v).to(dev)
+        c.set_pairs_device("add", d_u.data_ptr(), d_v.data_ptr(), P)     # the device form
+        assert c.pairs_info() == (A.PAIR_ADD, P)
+        refused(E_STATE, lambda: c.set_pairs("mul", u, v))               # another mode
+        refused(E_STATE, lambda: c.set_pairs("add", u[:-1], v[:-1]))     # another length
+        c.set_pairs("none")
+        assert c.pairs_info() == (A.PAIR_ADD, P)
+        refused(E_UNSUPPORTED, lambda: c.set_readout("mean", graph_ptr=[0, n]), "pair head")       # the second of the two
+        c.set_features(g["x"])
+        refused(E_INVALID, lambda: c.set_labels(g["labels"]), "one per pair")          # one label per node: the wrong length
+        c.set_labels(plab)
+        refused(E_INVALID, lambda: c.set_train_mask(np.ones(n, bool)), "one per pair")
+        c.set_train_mask(np.ones(P, bool))
+        refused(E_UNSUPPORTED, lambda: c.comm_init_host(1, 0, "/gat_pairs_refused", 1 << 20), "pair head")
+        c.params_init(1)
+        loss, correct = c.step()
+        assert np.isfinite(loss) and 0 <= correct <= P
+        c.set_pairs("add", v, u)                                         # a replacement after the labels is allowed
+        assert np.isfinite(c.step()[0])
+    with pkg.GatContext([8, 8], [8, 8], g["f"], 1) as c:                 # targets: per pair too
+        c.set_loss("bce")
+        c.set_graph(g["row_ptr"], g["col_idx"])
+        c.set_pairs("mul", u, v)
+        refused(E_INVALID, lambda: c.set_targets(np.zeros((n, 1), np.float32)), "one per pair")
+        c.set_targets(np.zeros((P, 1), np.float32))
+    with fresh() as c:                                                   # a readout first: the pair head is the second of the two
+        c.set_readout("mean", graph_ptr=[0, n])
+        refused(E_UNSUPPORTED, lambda: c.set_pairs("mul", u, v), "readout")
+    with fresh(flat_lrelu_index=True) as c:
+        refused(E_UNSUPPORTED, lambda: c.set_pairs("mul", u, v), "flat_lrelu_index")
+    with pkg.GatContext([8, 8], [8, 8], g["f"], g["c"]) as c:            # a destination-range shard
+        c.set_graph(g["row_ptr"], g["col_idx"], n_table=2 * n, table_row0=0)
+        refused(E_UNSUPPORTED, lambda: c.set_pairs("mul", u, v), "shard")
+
+
+def test_experiment_library_refuses_gat_dbg():
+    """The experiment library with GAT_DBG set has no pair form: GAT_E_UNSUPPORTED (a child process: the switch is read at load)."""
+    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "import __graft_entry__ as e, feature_cases as FC, pair_ref as PR\n"
+            "pkg = e.load_package(); A = pkg.abi; g = FC.parity_graph(); u, v = PR.pair_list(g['n'])\n"
+            "c = pkg.GatContext([8, 8], [8, 8], g['f'], g['c']); c.set_graph(g['row_ptr'], g['col_idx'])\n"
+            "try:\n    c.set_pairs('mul', u, v)\nexcept A.GatError as ex:\n    print('CODE', ex.code, ex)\n" % (ROOT, os.path.join(ROOT, "tests")))
+    exp = os.path.join(ROOT, "graph-attention-network-gatv2-_amd", "libgatv2_hip_exp.so")
+    assert os.path.exists(exp), "build() makes the experiment library"
+    env = dict(os.environ, GATV2_LIB=exp, GAT_DBG="1")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0 and f"CODE {E_UNSUPPORTED}" in r.stdout and "GAT_DBG" in r.stdout, r.stdout + r.stderr
+
+
+# -- off is the parent
+def test_off_is_the_parent(pkg, orc):
+    A = pkg.abi
+    ci = PR.case_inputs((*D8, "plain", "mul", PR.SOFTMAX))
+    g = ci["g"]
+    with PR.make_ctx(pkg, ci, mode=False, collect_timing=True) as a, PR.make_ctx(pkg, ci, mode=0, collect_timing=True) as b:
+        for c in (a, b):
+            c.kernel_stats_reset()
+        assert a.step() == b.step()
+        for k in A.PARAM_GROUPS:
+            assert np.array_equal(a.grads_get(k), b.grads_get(k))
+        for tap in (A.TAP_HOUT, A.TAP_Y):
+            assert np.array_equal(a.tap(tap, 1), b.tap(tap, 1))
+        sa, sb = a.kernel_stats(), b.kernel_stats()
+        assert {k: v[0] for k, v in sa.items()} == {k: v[0] for k, v in sb.items()}      # the same launches, class by class
+        assert a.algorithmic_bytes() == b.algorithmic_bytes()
+        ta, pa = a.algorithmic_bytes()
+        # the parent's own numbers: the context's byte model without the feature is the shape form's
+        ts, ps = A.algorithmic_bytes_shape(ci["heads"], ci["outdims"], g["f"], g["c"], g["n"], len(g["col_idx"]))
+        assert ta == ts and pa == ps
+    for mode in PR.MODES:                                                # on: the documented terms
+        with PR.make_ctx(pkg, dict(ci, mode=mode)) as r:
+            tr, pr = r.algorithmic_bytes()
+            N, P, DL, Cn = g["n"], len(ci["u"]), 8, g["c"]
+            fwd = 2 * P + 2 * P * DL + P * DL
+            bwd = 4 * P + 2 * P * DL + (2 * P * DL if mode == "mul" else 0) + N * DL
+            assert pr["misc"] - pa["misc"] == 4.0 * (fwd + bwd)
+            for k in ("head_forward", "head_backward"):
+                assert pr[k] == 4.0 * P * (DL + 2.0 * Cn + 2.0) and pa[k] == 4.0 * N * (DL + 2.0 * Cn + 2.0)
+            assert all(pr[k] == pa[k] for k in pa if k not in ("misc", "head_forward", "head_backward"))
+
+
+def test_launches_are_timed_under_the_head_classes(pkg, orc):
+    ci = PR.case_inputs((*D8, "plain", "mul", PR.SOFTMAX))
+    with PR.make_ctx(pkg, ci, mode=False, collect_timing=True) as a, PR.make_ctx(pkg, ci, collect_timing=True) as b:
+        for c in (a, b):
+            c.kernel_stats_reset()
+            c.forward(); c.backward()
+        sa, sb = a.kernel_stats(), b.kernel_stats()
+        assert sb["head_forward"][0] == sa["head_forward"][0] + 1 and sb["head_backward"][0] == sa["head_backward"][0] + 1
+        assert all(sa[k][0] == sb[k][0] for k in sa if k not in ("head_forward", "head_backward"))
+
+
+# -- the host program
+def test_train_edge_pairs(pkg, orc):
+    """train_edge --pairs mul --loss bce on a dataset folder written here: the epochs match a GatContext driven the same way."""
+    assert os.path.exists(BIN), "build() makes the host binary"
+    A = pkg.abi
+    g = FC.host_graph(3)
+    u, v, t = pkg.synth.link_pairs(g["row_ptr"], g["col_idx"], 60, 60, seed=2)
+    P = len(u)
+    with tempfile.TemporaryDirectory() as root:
+        d = os.path.join(root, "tiny")
+        os.makedirs(d)
+        np.savetxt(os.path.join(d, "row_ptr.txt"), g["row_ptr"], fmt="%d")
+        np.savetxt(os.path.join(d, "col_idx.txt"), g["col_idx"], fmt="%d")
+        np.savetxt(os.path.join(d, "features.txt"), g["x"], fmt="%.9g")
+        np.savetxt(os.path.join(d, "targets.txt"), t, fmt="%.9g")
+        np.savetxt(os.path.join(d, "pairs.txt"), np.stack([u, v], 1), fmt="%d")
+        x = np.loadtxt(os.path.join(d, "features.txt"), dtype=np.float32, ndmin=2)      # exactly what the binary reads
+        env = dict(os.environ)
+        env.pop("DATA_ROOT", None)
+        r = subprocess.run([BIN, "--dataset", "tiny", "--data-root", root, "--epochs", "3", "--optimizer", "adam", "--lr", "0.01", "--clip",
+                            "--num-layers", "2", "--heads", "8,8", "--outdims", "8,8", "--seed", "7", "--pairs", "mul", "--loss", "bce"],
+                           capture_output=True, text=True, env=env, timeout=300)
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert f"Pairs: mul over {P} pairs\n" in r.stdout
+        got = re.findall(r"Avg Loss: ([0-9.]+), Accuracy: ([0-9.]+)%", r.stdout)
+        assert len(got) == 3, r.stdout
+    with pkg.GatContext([8, 8], [8, 8], g["f"], 1) as ctx:
+        ctx.set_loss("bce")
+        ctx.set_graph(g["row_ptr"], g["col_idx"]); ctx.set_features(x)
+        ctx.set_pairs("mul", u, v)
+        ctx.set_targets(t.reshape(P, 1))
+        ctx.params_init(7)
+        ctx.zero_grad()
+        for e, (loss_txt, acc_txt) in enumerate(got, 1):                 # the host's epoch: forward, backward, clip, adam, zero_grad
+            loss, correct = ctx.forward()
+            ctx.backward()
+            ctx.clip(5.0)
+            ctx.step_adam(0.01, 0.9, 0.999, 1e-8, e)
+            ctx.zero_grad()
+            assert loss_txt == "%f" % (np.float32(loss) / P), (e, loss_txt, loss / P)
+            assert acc_txt == "%.2f" % (100.0 * np.float32(np.float32(correct) / P)), (e, acc_txt, correct)
