@@ -172,6 +172,25 @@ def make_ctx(pkg, g, heads, outdims, P, fe, ea=None, We=None, Wres=None, b=None,
     return ctx
 
 
+# -- a context against the model (tests/test_edge_features.py, tests/pick_profiles.py)
+TAPS = ["hpre", "hout", "G"]
+
+
+def check_we(pkg, ctx, ref, tol):
+    import parity
+    want = ref["We"].grad.numpy()
+    got = ctx.grads_get(pkg.abi.PARAM_WE)
+    assert got.shape == want.shape and np.abs(want).max() > 0
+    parity.check_rel("grad We", got, want, tol)
+
+
+def compare_all(pkg, ctx, g, cfg, ref, loss, tol):
+    """loss, the three taps of every layer and all eight gradient groups (a group the model does not have is empty on the device)."""
+    import feature_cases as FC
+    FC.compare(pkg, ctx, g, cfg, ref, loss, tol, TAPS, FC.GROUPS)
+    check_we(pkg, ctx, ref, tol)
+
+
 SHARD_FE = 3
 
 

@@ -25,21 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "graph-attention-network-gatv2-_amd", "train_edge")
 
 TOL = {"fp32": 1e-4, "bf16": 1e-2}
-TAPS = ["hpre", "hout", "G"]
-
-
-def check_we(pkg, ctx, ref, tol):
-    want = ref["We"].grad.numpy()
-    got = ctx.grads_get(pkg.abi.PARAM_WE)
-    assert got.shape == want.shape and np.abs(want).max() > 0
-    parity.check_rel("grad We", got, want, tol)
-
-
-def compare_all(pkg, ctx, g, cfg, ref, loss, tol):
-    """loss, the three taps of every layer and all eight gradient groups (a group the model does not have is empty on the device)."""
-    FC.compare(pkg, ctx, g, cfg, ref, loss, tol, TAPS, FC.GROUPS)
-    check_we(pkg, ctx, ref, tol)
-
+compare_all = EF.compare_all                      # with check_we: shared with tests/pick_profiles.py
 
 # -- 1. families
 @pytest.mark.parametrize("reg", [None, REG], ids=["plain", "regularised"])
