@@ -67,6 +67,10 @@ TAP_PAIRED = 19                             # pair head: the rows the head reads
 READOUT_NONE, READOUT_MEAN, READOUT_SUM, READOUT_MAX = 0, 1, 2, 3      # graph-level readout (set_readout)
 PAIR_NONE, PAIR_MUL, PAIR_ADD = 0, 1, 2                                # pair head (set_pairs)
 PAIR_MODES = {"none": PAIR_NONE, "mul": PAIR_MUL, "add": PAIR_ADD}
+NEG_NONE, NEG_UNIFORM, NEG_CORRUPT = 0, 1, 2                           # negative sampling (set_negative_sampling)
+NEG_MODES = {"none": NEG_NONE, "uniform": NEG_UNIFORM, "corrupt": NEG_CORRUPT}
+NEG_BOTH_DIRECTIONS, NEG_ALLOW_SELF = 1, 2
+NEG_TRIES = 16
 READOUT_MODES = {"none": READOUT_NONE, "mean": READOUT_MEAN, "sum": READOUT_SUM, "max": READOUT_MAX}
 LOSS_SOFTMAX_CE, LOSS_BCE, LOSS_MSE = 0, 1, 2                          # loss modes of the output head (set_loss)
 LOSS_MODES = {"softmax": LOSS_SOFTMAX_CE, "bce": LOSS_BCE, "mse": LOSS_MSE}
@@ -223,6 +227,11 @@ def _declare(lib: C.CDLL) -> None:
         "gat_pairs_info": [vp, P(i32), P(i64)],
         "gat_op_pair_forward": [vp, i64, vp, vp, i64, i64, i32, i32, vp, vp],
         "gat_op_pair_backward": [vp, vp, i64, vp, vp, i64, i64, i32, i32, vp, i64, vp],
+        "gat_set_negative_sampling": [vp, i32, i64, i64, i32, C.c_uint64],
+        "gat_resample_negatives": [vp, C.c_uint64],
+        "gat_negatives_info": [vp, P(i32), P(i64), P(i64), P(C.c_uint64), P(i64)],
+        "gat_pairs_get": [vp, vp, vp, i64],
+        "gat_op_negative_sample": [vp, vp, i64, i64, i32, i32, C.c_uint64, C.c_uint64, vp, vp, i64, vp, vp, i64, P(i64), vp],
         "gat_set_loss": [vp, i32],
         "gat_set_targets": [vp, vp, i64, i32],
         "gat_set_targets_device": [vp, vp, i64, i32],
@@ -552,6 +561,33 @@ class GatContext:
         _chk(self.lib.gat_pairs_info(self._ctx, C.byref(m), C.byref(n)))
         return m.value, n.value
 
+    def pairs(self):
+        """The current pair lists (u [n_pairs] int32, v [n_pairs] int32), copied from the device: what a resample drew."""
+        _, n = self.pairs_info()
+        u, v = np.empty(n, np.int32), np.empty(n, np.int32)
+        _chk(self.lib.gat_pairs_get(self._ctx, _np_ptr(u), _np_ptr(v), n))
+        return u, v
+
+    # -- negative sampling (gatv2_abi.h "negative sampling")
+    def set_negative_sampling(self, mode, first=0, count=0, both_directions=False, allow_self=False, seed=0):
+        """Pairs [first, first + count) of the pair list become the slots resample_negatives redraws: "uniform" node pairs or
+        "corrupt" (one endpoint of source pair j % first, of pairs [0, first), replaced), never an edge of the context's graph — in
+        either direction with both_directions — nor a self pair unless allow_self.  Labels, targets and masks over the slots stay the
+        caller's.  Mode 0 / "none" switches it off.  Draws nothing itself."""
+        flags = (NEG_BOTH_DIRECTIONS if both_directions else 0) | (NEG_ALLOW_SELF if allow_self else 0)
+        _chk(self.lib.gat_set_negative_sampling(self._ctx, neg_mode(mode), int(first), int(count), flags, int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def resample_negatives(self, round):
+        """Draw round `round` into the negative slots (the law of synth.negative_pairs, bit for bit), rebuild the pair index and the
+        work list on the device; a captured step_graph re-arms as after a replacing set_pairs."""
+        _chk(self.lib.gat_resample_negatives(self._ctx, int(round) & 0xFFFFFFFFFFFFFFFF))
+
+    def negatives_info(self):
+        """(mode, first, count, last round drawn, its unfiltered count); zeros while off."""
+        m, f, n, r, uf = C.c_int32(), C.c_int64(), C.c_int64(), C.c_uint64(), C.c_int64()
+        _chk(self.lib.gat_negatives_info(self._ctx, C.byref(m), C.byref(f), C.byref(n), C.byref(r), C.byref(uf)))
+        return m.value, f.value, n.value, r.value, uf.value
+
     # -- loss modes of the output head (gatv2_abi.h "loss modes of the output head")
     def set_loss(self, mode):
         """"softmax" (the default: int32 labels, set_labels), "bce" or "mse" (float targets [rows][C] with NaN = missing, set_targets),
@@ -818,6 +854,15 @@ def pair_mode(mode) -> int:
     return int(mode)
 
 
+def neg_mode(mode) -> int:
+    """"uniform" / "corrupt" / "none" or the GAT_NEG_* integer -> the integer."""
+    if isinstance(mode, str):
+        if mode not in NEG_MODES:
+            raise ValueError(f"negative sampling mode must be one of {sorted(NEG_MODES)}, got {mode!r}")
+        return NEG_MODES[mode]
+    return int(mode)
+
+
 def loss_mode(mode) -> int:
     """"softmax" / "bce" / "mse" or the GAT_LOSS_* integer -> the integer."""
     if isinstance(mode, str):
@@ -871,6 +916,18 @@ def op_pair_backward(d_gq: int, d_x: int, x_stride: int, d_u: int, d_v: int, n_p
     _chk(load_library().gat_op_pair_backward(C.c_void_p(d_gq or None), C.c_void_p(d_x or None), x_stride, C.c_void_p(d_u or None),
                                              C.c_void_p(d_v or None), n_pairs, n_rows, width, pair_mode(mode), C.c_void_p(d_gh or None),
                                              gh_stride, C.c_void_p(stream or None)))
+
+
+def op_negative_sample(d_row_ptr: int, d_col_idx: int, n_rows: int, n_edges: int, mode, flags: int, seed: int, round: int, d_u: int, d_v: int,
+                       count: int, d_src_u: int = 0, d_src_v: int = 0, n_src: int = 0, stream: int = 0) -> int:
+    """gat_op_negative_sample on device pointers: d_u / d_v [count] int32 receive round `round` of the sampling law on the CSR (rows =
+    destinations); d_src_u / d_src_v [n_src] are the source pairs of "corrupt".  -> the unfiltered count."""
+    uf = C.c_int64()
+    _chk(load_library().gat_op_negative_sample(C.c_void_p(d_row_ptr or None), C.c_void_p(d_col_idx or None), n_rows, n_edges, neg_mode(mode),
+                                               int(flags), int(seed) & 0xFFFFFFFFFFFFFFFF, int(round) & 0xFFFFFFFFFFFFFFFF,
+                                               C.c_void_p(d_src_u or None), C.c_void_p(d_src_v or None), n_src, C.c_void_p(d_u or None),
+                                               C.c_void_p(d_v or None), count, C.byref(uf), C.c_void_p(stream or None)))
+    return uf.value
 
 
 PART_BOTH, PART_LEFT, PART_RIGHT = 0, 1, 2       # the `part` of the dense seams

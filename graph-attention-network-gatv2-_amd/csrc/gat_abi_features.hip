@@ -206,6 +206,77 @@ int gat_pairs_info(gat_ctx* c, int32_t* mode, int64_t* n_pairs) {
     if (n_pairs) *n_pairs = c->pairs.n_pairs;
     return 0;
 }
+int gat_pairs_get(gat_ctx* c, int32_t* u_host, int32_t* v_host, int64_t n_pairs) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (!pairs_on(c)) return fail(GAT_E_STATE, "gat_pairs_get: no pair head (gat_set_pairs)");
+    if (n_pairs != c->pairs.n_pairs) return fail(GAT_E_INVALID, "gat_pairs_get: n_pairs differs from the context's pair count");
+    if (!u_host || !v_host) return fail(GAT_E_INVALID, "gat_pairs_get: null argument");
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    GAT_HIP(hipMemcpy(u_host, c->pairs.u, (size_t)n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost));
+    GAT_HIP(hipMemcpy(v_host, c->pairs.v, (size_t)n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+// ---- negative sampling ------------------------------------------------------------------------------------------
+int gat_set_negative_sampling(gat_ctx* c, int32_t mode, int64_t first, int64_t count, int32_t flags, uint64_t seed) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (mode < GAT_NEG_NONE || mode > GAT_NEG_CORRUPT) return fail(GAT_E_INVALID, "gat_set_negative_sampling: mode must be 0 (none), 1 (uniform) or 2 (corrupt)");
+    if (mode == GAT_NEG_NONE) {                          // off: the pairs, the index and every buffer stay what they are
+        auto& g = c->neg;
+        g.mode = 0; g.flags = 0; g.first = g.count = 0; g.seed = 0; g.last_round = 0; g.unfiltered = 0;
+        return 0;
+    }
+    if (!pairs_on(c)) return fail(GAT_E_STATE, "gat_set_negative_sampling: needs a pair head (gat_set_pairs comes first)");
+    if (flags & ~(GAT_NEG_BOTH_DIRECTIONS | GAT_NEG_ALLOW_SELF)) return fail(GAT_E_INVALID, "gat_set_negative_sampling: unknown flag bits");
+    if (count < 1 || first < 0 || first > c->pairs.n_pairs || count > c->pairs.n_pairs - first)
+        return fail(GAT_E_INVALID, "gat_set_negative_sampling: the slots [first, first + count) must be at least one pair inside the pair list");
+    if (mode == GAT_NEG_CORRUPT && first < 1) return fail(GAT_E_INVALID, "gat_set_negative_sampling: GAT_NEG_CORRUPT takes pairs [0, first) as its sources: first must be >= 1");
+    const int64_t N = c->graph.n_rows;
+    if (!c->neg.ascending_known) {
+        GAT_TRY(csr_rows_ascending(c->graph.row_ptr, c->graph.col_idx, N, &c->neg.ascending, c->stream));
+        c->neg.ascending_known = true;
+    }
+    if (!c->neg.counter) {
+        GAT_TRY(dalloc(c, &c->neg.counter, 1));
+        GAT_TRY(dalloc(c, &c->neg.plan_key, N + 1)); GAT_TRY(dalloc(c, &c->neg.plan_off, N + 1));
+        GAT_TRY(pair_plan_temp_bytes(N, &c->neg.plan_temp_bytes));
+        GAT_TRY(dmalloc(c, &c->neg.plan_temp, c->neg.plan_temp_bytes));
+    }
+    c->neg.mode = mode; c->neg.flags = flags; c->neg.first = first; c->neg.count = count; c->neg.seed = seed;
+    c->neg.last_round = 0; c->neg.unfiltered = 0;
+    return 0;
+}
+int gat_resample_negatives(gat_ctx* c, uint64_t round) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (c->neg.mode == GAT_NEG_NONE) return fail(GAT_E_STATE, "gat_resample_negatives: gat_set_negative_sampling comes first");
+    auto& g = c->neg; auto& p = c->pairs;
+    const int64_t N = c->graph.n_rows;
+    GAT_HIP(hipStreamSynchronize(c->stream));            // a step in flight still reads the old pairs
+    GAT_HIP(hipMemsetAsync(g.counter, 0, sizeof(unsigned long long), c->stream));
+    NegSampleArgs a{};
+    a.row_ptr = c->graph.row_ptr; a.col_idx = c->graph.col_idx; a.n_rows = N; a.ascending = g.ascending;
+    a.mode = g.mode; a.flags = g.flags; a.seed = g.seed; a.round = round;
+    a.src_u = p.u; a.src_v = p.v; a.n_src = g.first;     // (disjoint from the slots written below)
+    a.u = p.u + g.first; a.v = p.v + g.first; a.count = g.count; a.unfiltered = g.counter;
+    GAT_TRY(launch_negative_sample(a, c->stream));
+    GAT_TRY(pair_index_build(p.u, p.v, p.n_pairs, N, p.inc_ptr, p.inc, c->stream));       // synchronises
+    unsigned long long unfiltered = 0;
+    GAT_HIP(hipMemcpy(&unfiltered, g.counter, sizeof(unfiltered), hipMemcpyDeviceToHost));
+    int32_t n_parts = 0;
+    GAT_TRY(pair_plan_device(p.inc_ptr, N, g.plan_key, g.plan_off, g.plan_temp, g.plan_temp_bytes, p.items, p.split, &p.n_items, &p.n_split, &n_parts, c->stream));
+    g.last_round = round; g.unfiltered = (int64_t)unfiltered;
+    c->head.y_valid = false;                                  // nothing of an earlier forward stays
+    graph_drop(c);                                            // the work list changed: no replay may survive
+    return 0;
+}
+int gat_negatives_info(gat_ctx* c, int32_t* mode, int64_t* first, int64_t* count, uint64_t* last_round, int64_t* unfiltered) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (mode) *mode = c->neg.mode;
+    if (first) *first = c->neg.first;
+    if (count) *count = c->neg.count;
+    if (last_round) *last_round = c->neg.last_round;
+    if (unfiltered) *unfiltered = c->neg.unfiltered;
+    return 0;
+}
 // ---- dropout ---------------------------------------------------------------------------------------------------
 int gat_set_dropout(gat_ctx* c, float feat_p, float attn_p, uint64_t seed, uint64_t first_step) {
     if (!c) return fail(GAT_E_INVALID, "null context");

@@ -133,6 +133,17 @@ struct gat_ctx {
         float* part = nullptr;
         float* Q = nullptr; float* gQ = nullptr;
     } pairs;
+    // Negative sampling (gatv2_abi.h "negative sampling"): pairs [first, first + count) are the slots gat_resample_negatives redraws;
+    // ascending: every row of the graph is (checked once, when the feature is first switched on: the sampler then searches a row
+    // instead of scanning it); counter [1]: the kernel's unfiltered count; plan_key / plan_off [n_rows + 1] and plan_temp: the device
+    // plan's scratch (pair_plan_device), allocated once; last_round / unfiltered: of the last resample.
+    struct Negatives {
+        int32_t mode = 0, flags = 0; int64_t first = 0, count = 0; uint64_t seed = 0;
+        bool ascending_known = false, ascending = false;
+        unsigned long long* counter = nullptr;
+        unsigned long long* plan_key = nullptr; unsigned long long* plan_off = nullptr; void* plan_temp = nullptr; size_t plan_temp_bytes = 0;
+        uint64_t last_round = 0; int64_t unfiltered = 0;
+    } neg;
     // The output head: block partials, results, the class probabilities y (valid: y holds the last forward's, not after a fused head step).
     struct Head {
         float* hb_partial = nullptr; double* loss_partial = nullptr; int32_t* correct_partial = nullptr;

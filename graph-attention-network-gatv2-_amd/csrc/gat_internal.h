@@ -33,6 +33,18 @@ const char* choice_env(const char* name);
         if (rc__ != 0) return rc__;   \
     } while (0)
 
+// ---- the generators' counter hash (synth._hash): gat_synth.hip draws the datasets with it, gat_negsample.hip the negatives -----------
+constexpr uint64_t kGold = 0x9E3779B97F4A7C15ull;
+__host__ __device__ inline uint64_t mix64(uint64_t x) {          // synth._mix (splitmix64 finaliser)
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+// H(seed, stream, idx) = hash_at(hash_base(seed, stream), idx): the base is formed once on the host
+inline uint64_t hash_base(uint64_t seed, uint64_t stream) { return mix64(seed ^ (stream * 0xD1342543DE82EF95ull)); }
+__device__ inline uint64_t hash_at(uint64_t base, uint64_t idx) { return mix64(idx * kGold + base); }
+
 // ---- dropout masks (gat_dropout.hip; the contract is in gatv2_abi.h "dropout") -------------------------
 // Stateless, counter-based: every keep decision is a hash of (seed, step, layer, kind, node, position), so a shard, a replay and
 // the backward draw the same masks as the forward without storing them.  `step` lives on the device (advanced by the layer-0
@@ -651,6 +663,29 @@ struct PairBwdArgs {
     int32_t width, mode;
 };
 int launch_pair_backward(const PairBwdArgs& a, hipStream_t s);
+// build_readout_plan over a DEVICE incidence row_ptr, without the n_rows-sized round trip: d_items / d_split receive word for word the
+// host plan's lists (order, the -1 slot, partial-row numbering), only the three totals come back.  One packed count per node {split
+// nodes << 32 | partial rows} in d_key [n_rows + 1], its exclusive sum in d_off [n_rows + 1] — a node's first item is
+// n + partial rows before it - split nodes before it — then one fill kernel.  d_temp: pair_plan_temp_bytes(n_rows) bytes.  The lists
+// must hold the upper bounds of gat_set_pairs (n_rows + 2 seg items, seg split entries).  Synchronises s.
+int pair_plan_temp_bytes(int64_t n_rows, size_t* bytes);
+int pair_plan_device(const int32_t* d_inc_ptr, int64_t n_rows, unsigned long long* d_key, unsigned long long* d_off, void* d_temp,
+                     size_t temp_bytes, int4* d_items, int4* d_split, int64_t* n_items, int32_t* n_split, int32_t* n_parts, hipStream_t s);
+
+// ---- negative sampling (gat_negsample.hip; the contract — the sampling law — is in gatv2_abi.h "negative sampling") ---------------
+// *ascending = every row of the CSR has its sources in non-decreasing order (one pass, synchronises s): the sampler's membership test
+// is then a binary search, else a linear scan of the row — the drawn pairs are the same either way.
+int csr_rows_ascending(const int32_t* d_row_ptr, const int32_t* d_col_idx, int64_t n_rows, bool* ascending, hipStream_t s);
+struct NegSampleArgs {
+    const int32_t* row_ptr; const int32_t* col_idx; int64_t n_rows;     // rows = destinations, columns = sources (a checked CSR)
+    bool ascending;                                                     // csr_rows_ascending
+    int32_t mode, flags;                                                // GAT_NEG_UNIFORM | GAT_NEG_CORRUPT, GAT_NEG_* flag bits
+    uint64_t seed, round;
+    const int32_t* src_u; const int32_t* src_v; int64_t n_src;          // GAT_NEG_CORRUPT: the source pairs
+    int32_t* u; int32_t* v; int64_t count;                              // out
+    unsigned long long* unfiltered;                                     // [1] device word, ADDED to: negatives whose 16 attempts all failed
+};
+int launch_negative_sample(const NegSampleArgs& a, hipStream_t s);
 
 // train / validation masks (README R:134 "later"): labels_eff = mask ? label : ~label — the head kernels skip negative
 // labels (no loss, no count, dz = 0); eval_mask: fixed-order block partials of loss / #correct / #nodes over a mask

@@ -662,6 +662,46 @@ int gat_op_pair_backward(const float* d_gq, const float* d_x, int64_t x_stride, 
     return rc;
 }
 
+// The negative sampler on caller-owned device pointers.  The CSR and the source pairs are checked on the device before anything walks them.
+int gat_op_negative_sample(const int32_t* d_row_ptr, const int32_t* d_col_idx, int64_t n_rows, int64_t n_edges, int32_t mode, int32_t flags,
+                           uint64_t seed, uint64_t round, const int32_t* d_src_u, const int32_t* d_src_v, int64_t n_src, int32_t* d_u,
+                           int32_t* d_v, int64_t count, int64_t* unfiltered, void* stream) {
+    static const char* who = "gat_op_negative_sample";
+    hipStream_t s = (hipStream_t)stream;
+    if (mode != GAT_NEG_UNIFORM && mode != GAT_NEG_CORRUPT) return fail(GAT_E_INVALID, std::string(who) + ": mode must be 1 (uniform) or 2 (corrupt)");
+    if (flags & ~(GAT_NEG_BOTH_DIRECTIONS | GAT_NEG_ALLOW_SELF)) return fail(GAT_E_INVALID, std::string(who) + ": unknown flag bits");
+    if (n_rows < 1 || n_rows >= 0x7fffffffLL || n_edges < 0 || n_edges > 0x7fffffffLL || count < 1) return fail(GAT_E_INVALID, std::string(who) + ": bad sizes");
+    if (!d_row_ptr || (!d_col_idx && n_edges > 0) || !d_u || !d_v || !unfiltered) return fail(GAT_E_INVALID, std::string(who) + ": null argument");
+    const bool corrupt = mode == GAT_NEG_CORRUPT;
+    if (corrupt && (n_src < 1 || !d_src_u || !d_src_v)) return fail(GAT_E_INVALID, std::string(who) + ": GAT_NEG_CORRUPT needs at least one source pair");
+    int32_t problem = 0; int64_t where = -1;
+    GAT_TRY(csr_check_device(d_row_ptr, d_col_idx, n_rows, n_edges, n_rows, &problem, &where, s));
+    if (problem) return fail(GAT_E_INVALID, std::string(who) + ": " + csr_problem_text(problem));
+    if (corrupt) {
+        int32_t value = 0;
+        GAT_TRY(pair_check_device(d_src_u, d_src_v, n_src, n_rows, &where, &value, s));
+        if (where >= 0) return fail(GAT_E_INVALID, std::string(who) + ": source " + pair_problem_text(where, value, n_rows));
+    }
+    Scratch tmp;
+    unsigned long long* d_cnt = nullptr;
+    int32_t* d_none = nullptr;                           // a graph without edges: the rows are never dereferenced
+    GAT_TRY(tmp.get(&d_cnt, 1)); GAT_TRY(tmp.get(&d_none, 1));
+    GAT_HIP(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), s));
+    NegSampleArgs a{};
+    a.row_ptr = d_row_ptr; a.col_idx = d_col_idx ? d_col_idx : d_none; a.n_rows = n_rows;
+    GAT_TRY(csr_rows_ascending(a.row_ptr, a.col_idx, n_rows, &a.ascending, s));
+    a.mode = mode; a.flags = flags; a.seed = seed; a.round = round;
+    a.src_u = d_src_u; a.src_v = d_src_v; a.n_src = corrupt ? n_src : 0;
+    a.u = d_u; a.v = d_v; a.count = count; a.unfiltered = d_cnt;
+    int rc = launch_negative_sample(a, s);
+    unsigned long long cnt = 0;
+    hipError_t e = hipMemcpyAsync(&cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);    // before the scratch is freed
+    if (rc == 0 && e != hipSuccess) rc = fail((int)e, std::string(who) + ": " + hipGetErrorString(e));
+    if (rc == 0) *unfiltered = (int64_t)cnt;
+    return rc;
+}
+
 // ---- the six dense launchers on caller-owned device pointers: one launcher per call, exactly the caller's arguments ----------------
 static int op_dense_sizes(const char* who, int64_t n_rows, int32_t F, int32_t HD) {
     if (n_rows < 0 || n_rows >= 0x7fffffffLL || F < 1 || HD < 1) return fail(GAT_E_INVALID, std::string(who) + ": bad sizes (n_rows >= 0, F >= 1, HD >= 1)");

@@ -10,9 +10,13 @@
 // partial rows a second small kernel adds in ascending order.  ONE WAVE runs an item: LPR lanes per row, the other lane groups are entry
 // slots that walk their entries in ascending order and are combined by a fixed-order xor butterfly.  No float atomics anywhere: the
 // result is a function of the pair list alone, bitwise reproducible.
+// pair_plan_device builds the same work list from a DEVICE incidence row_ptr (one packed count per node, one exclusive sum, one fill
+// kernel; only the totals return to the host): what gat_resample_negatives uses in place of the host plan.
 #include <algorithm>
 
 #include "gat_internal.h"
+
+#include <hipcub/hipcub.hpp>
 
 namespace gat {
 
@@ -153,6 +157,41 @@ __global__ __launch_bounds__(256) void pair_combine_kernel(PairBwdArgs A) {
     }
 }
 
+// ---- the work list on the device (pair_plan_device): build_readout_plan's lists from a device inc_ptr ----
+// key[n] = split << 32 | partial rows of node n (0 for a node of at most kPairSegEntries incidences), key[n_rows] = 0: the exclusive sum's
+// last entry then holds the totals
+__global__ __launch_bounds__(256) void pair_plan_keys_kernel(const int32_t* __restrict__ inc_ptr, int64_t n_rows, unsigned long long* __restrict__ key) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n <= n_rows; n += stride) {
+        unsigned long long k = 0;
+        if (n < n_rows) {
+            const int32_t cnt = inc_ptr[n + 1] - inc_ptr[n];
+            if (cnt > kPairSegEntries) k = 1ull << 32 | (unsigned long long)((cnt + kPairSegEntries - 1) / kPairSegEntries);
+        }
+        key[n] = k;
+    }
+}
+// off[n] = {split nodes, partial rows} before node n.  Items are in node order, one per short node and one per segment of a long one:
+// node n's first item is n + (partial rows before) - (split nodes before).
+__global__ __launch_bounds__(256) void pair_plan_fill_kernel(const int32_t* __restrict__ inc_ptr, int64_t n_rows, const unsigned long long* __restrict__ off,
+                                                             int4* __restrict__ items, int4* __restrict__ split) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < n_rows; n += stride) {
+        const int32_t beg = inc_ptr[n], end = inc_ptr[n + 1], cnt = end - beg;
+        const unsigned long long o = off[n];
+        const int32_t parts0 = (int32_t)(o & 0xffffffffull), split0 = (int32_t)(o >> 32);
+        const int64_t item0 = n + parts0 - split0;
+        if (cnt <= kPairSegEntries) {
+            items[item0] = make_int4((int32_t)n, beg, end, -1);
+            continue;
+        }
+        const int32_t nseg = (cnt + kPairSegEntries - 1) / kPairSegEntries;
+        split[split0] = make_int4((int32_t)n, parts0, nseg, 0);
+        for (int32_t k = 0; k < nseg; ++k)
+            items[item0 + k] = make_int4((int32_t)n, beg + k * kPairSegEntries, min(end, beg + (k + 1) * kPairSegEntries), parts0 + k);
+    }
+}
+
 bool pair_mode_ok(int32_t mode) { return mode == GAT_PAIR_MUL || mode == GAT_PAIR_ADD; }
 int32_t lanes_per_row(int groups) {
     int32_t LPR = 1;
@@ -208,6 +247,27 @@ int pair_index_build(const int32_t* d_u, const int32_t* d_v, int64_t n_pairs, in
     hipLaunchKernelGGL(pair_entries_kernel, dim3(grid_for(n_inc)), dim3(256), 0, s, keys, d_u, d_v, n_inc, d_inc);
     GAT_HIP(hipGetLastError());
     GAT_HIP(hipStreamSynchronize(s));                    // before the scratch is freed
+    return 0;
+}
+
+int pair_plan_temp_bytes(int64_t n_rows, size_t* bytes) {
+    *bytes = 0;
+    GAT_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)(n_rows + 1)));
+    return 0;
+}
+int pair_plan_device(const int32_t* d_inc_ptr, int64_t n_rows, unsigned long long* d_key, unsigned long long* d_off, void* d_temp,
+                     size_t temp_bytes, int4* d_items, int4* d_split, int64_t* n_items, int32_t* n_split, int32_t* n_parts, hipStream_t s) {
+    hipLaunchKernelGGL(pair_plan_keys_kernel, dim3(grid_for(n_rows + 1)), dim3(256), 0, s, d_inc_ptr, n_rows, d_key);
+    GAT_HIP(hipGetLastError());
+    GAT_HIP(hipcub::DeviceScan::ExclusiveSum(d_temp, temp_bytes, d_key, d_off, (int)(n_rows + 1), s));
+    hipLaunchKernelGGL(pair_plan_fill_kernel, dim3(grid_for(n_rows)), dim3(256), 0, s, d_inc_ptr, n_rows, d_off, d_items, d_split);
+    GAT_HIP(hipGetLastError());
+    unsigned long long total = 0;                        // off[n_rows]: the only words that return to the host
+    GAT_HIP(hipMemcpyAsync(&total, d_off + n_rows, sizeof(total), hipMemcpyDeviceToHost, s));
+    GAT_HIP(hipStreamSynchronize(s));
+    *n_parts = (int32_t)(total & 0xffffffffull);
+    *n_split = (int32_t)(total >> 32);
+    *n_items = n_rows + *n_parts - *n_split;
     return 0;
 }
 

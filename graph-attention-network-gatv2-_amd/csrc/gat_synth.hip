@@ -15,16 +15,7 @@
 namespace gat {
 namespace {
 
-constexpr uint64_t kGold = 0x9E3779B97F4A7C15ull;
-
-__host__ __device__ inline uint64_t mix64(uint64_t x) {          // synth._mix (splitmix64 finaliser)
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
-inline uint64_t hash_base(uint64_t seed, uint64_t stream) { return mix64(seed ^ (stream * 0xD1342543DE82EF95ull)); }   // synth._hash
-__device__ inline uint64_t hash_at(uint64_t base, uint64_t idx) { return mix64(idx * kGold + base); }
+// mix64 / hash_base / hash_at (synth._mix / synth._hash) live in gat_internal.h
 __device__ inline double uniform01(uint64_t h) { return (double)(h >> 11) * (1.0 / 9007199254740992.0); }          // synth._uniform01
 
 // key[e] = dst(e) * n + node_of_rank[ upper_bound(cdf, u_e) ]      (synth.powerlaw_graph: searchsorted side="right")

@@ -104,6 +104,8 @@ struct Options {
     std::string readout;                  // --readout mean|sum|max: graph_ptr.txt of the dataset folder, one label per graph
     bool edge_features = false;           // --edge-features: edge_features.txt of the dataset folder enters the attention score
     std::string pairs;                    // --pairs mul|add: pairs.txt of the dataset folder ("u v" per line), one label per pair
+    std::string neg_sampling;             // --neg-sampling uniform|corrupt: lines --neg-first .. of pairs.txt are redrawn before every epoch
+    long long neg_first = -1; uint64_t neg_seed = 0; int neg_flags = 0;      // --neg-first K, --neg-seed S, GAT_NEG_*: --neg-both-directions, --neg-allow-self
     std::string loss = "softmax";         // --loss softmax|bce|mse: bce / mse read targets.txt (rows of C floats, nan allowed) in place of labels.txt
 };
 
@@ -138,6 +140,10 @@ const char* kUsage =
     "                          line (pairs need not be edges); the output head reads X[u]*X[v] (mul) or X[u]+X[v] (add) of the last\n"
     "                          layer's rows; labels.txt / targets.txt, --train-mask and --val-mask then hold one line per pair; loss and\n"
     "                          accuracy are over pairs (--ranks 1, not with --readout)\n"
+    "            --neg-sampling uniform|corrupt --neg-first K [--neg-seed S] [--neg-both-directions] [--neg-allow-self]   with --pairs:\n"
+    "                          lines K.. of pairs.txt are negative slots, redrawn on the device before every epoch (round = epoch index)\n"
+    "                          as node pairs that are not edges of the graph — uniform, or one endpoint of a pair of lines 0..K-1\n"
+    "                          replaced (corrupt); not an edge in either direction / self pairs allowed with the two flags\n"
     "            --loss softmax|bce|mse   the output head's loss (default softmax: labels.txt as always).  bce (multi-label) and mse\n"
     "                          (regression) read targets.txt in place of labels.txt: one row of C floats per node — per graph with\n"
     "                          --readout — where nan marks a missing entry; C is the row width.  The epoch line prints the loss sum over\n"
@@ -230,6 +236,11 @@ Options parse_args(int argc, char** argv) {
         else if (a == "--edge-features") o.edge_features = true;
         else if (a == "--readout" && has_val) o.readout = argv[++i];
         else if (a == "--pairs" && has_val) o.pairs = argv[++i];
+        else if (a == "--neg-sampling" && has_val) o.neg_sampling = argv[++i];
+        else if (a == "--neg-first" && has_val) o.neg_first = std::strtoll(argv[++i], nullptr, 0);
+        else if (a == "--neg-seed" && has_val) o.neg_seed = std::strtoull(argv[++i], nullptr, 0);
+        else if (a == "--neg-both-directions") o.neg_flags |= GAT_NEG_BOTH_DIRECTIONS;
+        else if (a == "--neg-allow-self") o.neg_flags |= GAT_NEG_ALLOW_SELF;
         else if (a == "--loss" && has_val) o.loss = argv[++i];
         else if (a == "--transport" && has_val) {
             o.transport = argv[++i];
@@ -696,10 +707,23 @@ int run(const Options& o, const RankEnv& env) {
     std::printf("  Approx. GPU memory allocated by this program: %.2f MB\n",
                 (double)(free_before - free_after) / (1024.0 * 1024.0));
 
+    // --neg-sampling: lines neg_first .. of pairs.txt are the negative slots (their labels / targets stay those of the files)
+    const int neg_mode = o.neg_sampling == "uniform" ? GAT_NEG_UNIFORM : o.neg_sampling == "corrupt" ? GAT_NEG_CORRUPT : GAT_NEG_NONE;
+    if (neg_mode) {
+        check(gat_set_negative_sampling(ctx, neg_mode, o.neg_first, NH - o.neg_first, o.neg_flags, o.neg_seed), "gat_set_negative_sampling");
+        std::printf("Negative sampling: %s, pairs %lld .. %lld redrawn before every epoch\n", o.neg_sampling.c_str(), o.neg_first, (long long)NH - 1);
+    }
+
     check(gat_zero_grad(ctx), "gat_zero_grad");
     for (int epoch = 1; epoch <= o.epochs; ++epoch) {
         const auto start = std::chrono::high_resolution_clock::now();
         std::printf("\nEpoch %d\n", epoch);
+        if (neg_mode) {                           // fresh non-edges for this epoch, the first included
+            check(gat_resample_negatives(ctx, (uint64_t)epoch), "gat_resample_negatives");
+            int64_t unfiltered = 0;
+            check(gat_negatives_info(ctx, nullptr, nullptr, nullptr, nullptr, &unfiltered), "gat_negatives_info");
+            if (unfiltered) fprintf(stderr, "Warning: epoch %d: %lld negative(s) found no non-edge in %d attempts and are unfiltered\n", epoch, (long long)unfiltered, GAT_NEG_TRIES);
+        }
         float loss_sum = 0.f; int32_t n_correct = 0;
         check(gat_forward(ctx, &loss_sum, &n_correct), "gatv2 forward");
         if (loss_mode == GAT_LOSS_SOFTMAX_CE) std::printf("\nAvg Loss: %f, Accuracy: %.2f%%\n", loss_sum / n_train, 100.0f * (static_cast<float>(n_correct) / n_train));
@@ -762,6 +786,7 @@ int main(int argc, char** argv) {
     // --help, --edge-features with what it cannot be combined with, and graph flags without a graph to apply them to, end here: before
     // anything touches the GPU
     bool graph_flag = false, edge_feat_flag = false, readout_flag = false, targets_flag = false, pairs_flag = false;
+    bool neg_flag = false, neg_corrupt = false; long long neg_first = -1;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--help") { std::cout << kUsage; return 0; }
@@ -774,6 +799,16 @@ int main(int argc, char** argv) {
             const std::string v = i + 1 < argc ? argv[i + 1] : "";
             if (v != "mul" && v != "add") die("Error: --pairs must be mul or add\n");
             pairs_flag = true;
+        }
+        if (a == "--neg-sampling") {
+            const std::string v = i + 1 < argc ? argv[i + 1] : "";
+            if (v != "uniform" && v != "corrupt") die("Error: --neg-sampling must be uniform or corrupt\n");
+            neg_flag = true; neg_corrupt = v == "corrupt";
+        }
+        if (a == "--neg-first" && i + 1 < argc) {
+            char* end = nullptr;
+            neg_first = std::strtoll(argv[i + 1], &end, 0);
+            if (end == argv[i + 1] || *end != '\0' || neg_first < 0) die("Error: --neg-first must be a line index of pairs.txt (>= 0)\n");
         }
         if (a == "--add-self-loops" || a == "--undirected" || a == "--coalesce") graph_flag = true;
         if (a == "--edge-features") edge_feat_flag = true;
@@ -795,6 +830,9 @@ int main(int argc, char** argv) {
         die("Error: --pairs needs --ranks 1: an endpoint of a pair may live on another destination-range shard\n");
     if (pairs_flag && readout_flag)
         die("Error: --pairs cannot be combined with --readout: the output head has one kind of row\n");
+    if (neg_flag && !pairs_flag) die("Error: --neg-sampling needs --pairs: the negatives are lines of pairs.txt\n");
+    if (neg_flag && neg_first < 0) die("Error: --neg-sampling needs --neg-first K: lines K.. of pairs.txt are the negative slots\n");
+    if (neg_flag && neg_corrupt && neg_first < 1) die("Error: --neg-sampling corrupt needs --neg-first >= 1: lines 0..K-1 of pairs.txt are its source pairs\n");
     if (graph_flag || readout_flag || targets_flag || pairs_flag) {
         std::string root = "./data", name = "pubmed";
         bool root_given = false;

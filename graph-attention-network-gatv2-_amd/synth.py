@@ -242,6 +242,61 @@ def link_pairs(row_ptr, col_idx, n_pos: int, n_neg: int, seed: int = GRAPH_SEED 
     return u, v, t
 
 
+NEG_UNIFORM, NEG_CORRUPT = 1, 2                      # gatv2_abi.h GAT_NEG_*
+NEG_BOTH_DIRECTIONS, NEG_ALLOW_SELF = 1, 2
+NEG_TRIES = 16
+
+
+def negative_pairs(row_ptr, col_idx, mode: int, count: int, seed: int, round: int, flags: int = 0, src_u=None, src_v=None):
+    """The sampling law of gatv2_abi.h "negative sampling" in numpy — what gat_resample_negatives / gat_op_negative_sample draw, bit
+    for bit.  Negative j in [0, count), attempt a in [0, 16): counter k = (round * count + j) * 16 + a (wrapping uint64).
+    NEG_UNIFORM: u = H(seed, 37, k) % N, v = H(seed, 41, k) % N.  NEG_CORRUPT: source pair p = j % n_src, role = H(seed, 43,
+    round * count + j) & 1 once per negative, w = H(seed, 37, k) % N; role 0: (w, v_p), role 1: (u_p, w).  Accepted: u != v (unless
+    NEG_ALLOW_SELF), (u, v) not an edge — u not among the sources of row v — nor, with NEG_BOTH_DIRECTIONS, (v, u).  The first accepted
+    attempt wins; a negative without one keeps attempt 15's candidate and counts as unfiltered.
+    -> (u [count] int32, v [count] int32, unfiltered)."""
+    rp, ci = np.asarray(row_ptr, np.int64), np.asarray(col_idx, np.int64)
+    n = len(rp) - 1
+    if mode not in (NEG_UNIFORM, NEG_CORRUPT) or flags & ~(NEG_BOTH_DIRECTIONS | NEG_ALLOW_SELF) or count < 1 or n < 1:
+        raise ValueError(f"negative_pairs: bad arguments (mode={mode}, flags={flags}, count={count}, {n} nodes)")
+    corrupt = mode == NEG_CORRUPT
+    if corrupt:
+        if src_u is None or src_v is None or len(src_u) < 1 or len(src_u) != len(src_v):
+            raise ValueError("negative_pairs: NEG_CORRUPT needs at least one source pair")
+        su, sv = np.asarray(src_u, np.int64), np.asarray(src_v, np.int64)
+    edges = np.unique(np.repeat(np.arange(n, dtype=np.int64), np.diff(rp)) * n + ci)      # sorted keys dst * N + src
+
+    def is_edge(a, b):                                   # (a, b) is an edge: a among the sources of row b
+        key = b * n + a
+        pos = np.searchsorted(edges, key)
+        return (pos < len(edges)) & (edges[np.minimum(pos, max(len(edges) - 1, 0))] == key) if len(edges) else np.zeros(len(a), bool)
+
+    nn = _U64(n)
+    with np.errstate(over="ignore"):
+        c = _U64(int(round) & 0xFFFFFFFFFFFFFFFF) * _U64(count) + np.arange(count, dtype=np.uint64)
+    if corrupt:
+        p = np.arange(count, dtype=np.int64) % len(su)
+        role = (_hash(seed, 43, c) & _U64(1)).astype(np.int64)
+    u, v = np.zeros(count, np.int64), np.zeros(count, np.int64)
+    done = np.zeros(count, bool)
+    for a in range(NEG_TRIES):
+        with np.errstate(over="ignore"):
+            k = c * _U64(NEG_TRIES) + _U64(a)
+        if corrupt:
+            w = (_hash(seed, 37, k) % nn).astype(np.int64)
+            cu, cv = np.where(role == 0, w, su[p]), np.where(role == 0, sv[p], w)
+        else:
+            cu, cv = (_hash(seed, 37, k) % nn).astype(np.int64), (_hash(seed, 41, k) % nn).astype(np.int64)
+        ok = ~is_edge(cu, cv)
+        if not flags & NEG_ALLOW_SELF:
+            ok &= cu != cv
+        if flags & NEG_BOTH_DIRECTIONS:
+            ok &= ~is_edge(cv, cu)
+        u[~done], v[~done] = cu[~done], cv[~done]          # the candidate of the first accepted attempt, else of the last
+        done |= ok
+    return u.astype(np.int32), v.astype(np.int32), int((~done).sum())
+
+
 def graph_batch(n_graphs: int, nodes_lo: int, nodes_hi: int, avg_degree: float, seed: int = GRAPH_SEED, f: int = 32, c: int = 4):
     """A batch of n_graphs small graphs (molecule-like) packed block-diagonally into one CSR, for the graph-level readout
     (gatv2_abi.h "graph-level readout"): graph g has a size drawn uniformly from [nodes_lo, nodes_hi] and owns the contiguous nodes

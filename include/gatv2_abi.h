@@ -655,6 +655,51 @@ int gat_op_pair_forward(const float* d_x, int64_t x_stride, const int32_t* d_u, 
 int gat_op_pair_backward(const float* d_gq, const float* d_x, int64_t x_stride, const int32_t* d_u, const int32_t* d_v, int64_t n_pairs,
                          int64_t n_rows, int32_t width, int32_t mode, float* d_gh, int64_t gh_stride, void* stream);
 
+/* ---- negative sampling (for the pair head: link prediction draws fresh non-edges every epoch, PyG's negative_sampling /
+ * structured_negative_sampling; here one full-batch step is one epoch) ----
+ * A deterministic, edge-filtered sampler on the device and a call that rewrites the negative part of the context's pair list in place.
+ * THE SAMPLING LAW — one function of (graph, mode, flags, seed, round, count[, source pairs]); synth.negative_pairs states it in numpy and
+ * the kernel agrees with it to the bit.  H(seed, stream, idx) is the generators' counter hash (synth._hash).  For negative j in
+ * [0, count) and attempt a in [0, GAT_NEG_TRIES) the counter is k = (round * count + j) * 16 + a, in wrapping uint64 arithmetic.
+ *     GAT_NEG_UNIFORM   u = H(seed, 37, k) % N,  v = H(seed, 41, k) % N
+ *     GAT_NEG_CORRUPT   structured: one endpoint of a real pair is kept.  Source pair p = j % n_src; role = H(seed, 43, round * count + j) & 1,
+ *                       drawn once per negative, not per attempt; w = H(seed, 37, k) % N; role 0: (u, v) = (w, v_p), role 1: (u, v) = (u_p, w)
+ *   A candidate is accepted when u != v (unless GAT_NEG_ALLOW_SELF), (u, v) is not an edge and, with GAT_NEG_BOTH_DIRECTIONS, (v, u) is not
+ *   one either.  "(u, v) is an edge": u occurs in col_idx[row_ptr[v] .. row_ptr[v+1]) — rows are destinations, columns sources; rows whose
+ *   sources are not ascending and rows with duplicate edges are tested correctly (a binary search when every row of the graph is
+ *   ascending, checked in one pass at set-up; a linear scan of the row otherwise — the result does not depend on which).  The first
+ *   accepted attempt wins.  When none of the 16 is accepted the negative keeps attempt 15's candidate and counts as one UNFILTERED
+ *   negative (the list length is fixed); the count is reported.
+ * gat_set_negative_sampling declares pairs [first, first + count) of the context's pair list as the negative slots.  Labels, targets and
+ *   masks over those slots are the caller's and are never touched.  Needs a pair head (else GAT_E_STATE); count >= 1, 0 <= first,
+ *   first + count <= n_pairs, a mode and flags inside the enums, else GAT_E_INVALID; GAT_NEG_CORRUPT takes pairs [0, first) as its sources
+ *   and needs first >= 1 (GAT_E_INVALID).  mode == 0 (GAT_NEG_NONE) switches the feature off and leaves the context exactly as it was (the
+ *   pairs stay what they are; the other arguments are not read).  It draws nothing itself.
+ * gat_resample_negatives waits for the context's stream, draws round `round` from the context's own graph into u / v [first, first + count),
+ *   rebuilds the incidence index and — on the device, without an n_rows-sized round trip — the scatter's work list (word for word the
+ *   lists gat_set_pairs builds for the same pairs, so results are bitwise those of gat_set_pairs with the same lists), invalidates y and
+ *   re-arms a captured gat_step_graph exactly as a replacing gat_set_pairs does.  Before gat_set_negative_sampling: GAT_E_STATE.  Not part
+ *   of a step: not captured, and gat_algorithmic_bytes is unchanged.
+ *   Only the graph's edges are rejected: a candidate equal to a held-out positive of the pair list is NOT (PyG's behaviour when it is
+ *   given the training edges).
+ * gat_negatives_info: (mode, first, count, the last round drawn, its unfiltered count); all 0 while off; pointers may be NULL.
+ * gat_pairs_get copies the current pair lists to the host ([n_pairs] each; a wrong n_pairs: GAT_E_INVALID; no pair head: GAT_E_STATE).
+ * gat_op_negative_sample is the sampler as a stateless seam on caller-owned DEVICE pointers (current device): a CSR of n_rows rows and
+ *   n_edges edges over n_rows sources (checked on the device with gat_graph_check_device's rules before anything walks it), d_src_u /
+ *   d_src_v [n_src] for GAT_NEG_CORRUPT (checked like gat_set_pairs' arrays; may be NULL for GAT_NEG_UNIFORM), d_u / d_v [count] out,
+ *   *unfiltered (host) the count.  Same codes as the context form; mode 0 is GAT_E_INVALID here.  Synchronises `stream` (may be NULL). */
+enum { GAT_NEG_NONE = 0, GAT_NEG_UNIFORM = 1, GAT_NEG_CORRUPT = 2 };
+enum { GAT_NEG_BOTH_DIRECTIONS = 1, GAT_NEG_ALLOW_SELF = 2 };
+#define GAT_NEG_TRIES 16
+int gat_set_negative_sampling(gat_ctx* ctx, int32_t mode, int64_t first, int64_t count, int32_t flags, uint64_t seed);
+int gat_resample_negatives(gat_ctx* ctx, uint64_t round);
+int gat_negatives_info(gat_ctx* ctx, int32_t* mode, int64_t* first, int64_t* count, uint64_t* last_round, int64_t* unfiltered);
+int gat_pairs_get(gat_ctx* ctx, int32_t* u_host, int32_t* v_host, int64_t n_pairs);
+int gat_op_negative_sample(const int32_t* d_row_ptr, const int32_t* d_col_idx, int64_t n_rows, int64_t n_edges,
+                           int32_t mode, int32_t flags, uint64_t seed, uint64_t round,
+                           const int32_t* d_src_u, const int32_t* d_src_v, int64_t n_src,
+                           int32_t* d_u, int32_t* d_v, int64_t count, int64_t* unfiltered, void* stream);
+
 /* The dense launchers (the W_l / W_r projections, their two backward products and the residual's three) as stateless seams on caller-owned
  * DEVICE pointers (current device).  Each call runs exactly ONE launcher with exactly the caller's arguments and synchronises `stream`
  * (may be NULL): parity seams, not the fast path.  W is the reference layout [HD][2F], Wres [HD][F]; part: 0 both halves, 1 the left
