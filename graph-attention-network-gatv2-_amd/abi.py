@@ -170,6 +170,7 @@ def _declare(lib: C.CDLL) -> None:
         "gat_comm_halo_info": [vp, P(i32), P(i64), P(i64), P(C.c_double)],
         "gat_step": [vp, P(f32), P(i32)],
         "gat_step_graph": [vp, i32],
+        "gat_step_graph_state": [vp, P(i32)],
         "gat_forward": [vp, P(f32), P(i32)],
         "gat_backward": [vp],
         "gat_zero_grad": [vp],
@@ -237,6 +238,8 @@ def _declare(lib: C.CDLL) -> None:
         "gat_set_targets_device": [vp, vp, i64, i32],
         "gat_loss_info": [vp, P(i32), P(i32)],
         "gat_target_count": [vp, vp, i64, P(i64)],
+        "gat_eval_rank": [vp, vp, i64, vp, i32, vp],
+        "gat_op_rank_stats": [vp, i64, vp, vp, vp, i64, i32, vp, i32, vp, vp],
         "gat_op_readout_forward": [vp, i64, vp, i64, i64, i32, i32, vp, vp, vp],
         "gat_op_readout_backward": [vp, vp, i64, i64, i32, i32, vp, vp, i64, vp],
         "gat_op_dense_scratch_floats": [i32, i64, i32, i32, i32, P(i64)],
@@ -428,6 +431,16 @@ class GatContext:
         l, c, n = C.c_double(), C.c_int32(), C.c_int32()
         _chk(self.lib.gat_eval_mask(self._ctx, _np_ptr(m), len(m), C.byref(l), C.byref(c), C.byref(n)))
         return l.value, c.value, n.value
+
+    def eval_rank(self, mask, ks=()):
+        """Ranking metrics of the last forward over the head rows of `mask` (gat_eval_rank): a dict of arrays with one entry per output
+        column — n_pos, n_neg, n_nan, auc_num, ap, mrr, hits [C][len(ks)] — plus the derived auc (NaN where n_pos * n_neg == 0) and
+        hits_at (hits / n_pos; 1.0 where the column has fewer than K negatives, NaN where it has no positive)."""
+        m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        k = np.ascontiguousarray(ks, np.int32).reshape(-1)
+        out = np.zeros(self.C, RANK_STATS_DTYPE)
+        _chk(self.lib.gat_eval_rank(self._ctx, _np_ptr(m), len(m), _np_ptr(k) if len(k) else None, len(k), _np_ptr(out)))
+        return rank_stats_dict(out, len(k))
 
     def set_labels_device(self, d_labels: int, n_rows: int):
         _chk(self.lib.gat_set_labels_device(self._ctx, C.c_void_p(d_labels), n_rows))
@@ -672,6 +685,12 @@ class GatContext:
     def step_graph(self, enable: bool = True):
         """step() as one replayed hipGraph launch (small, launch-bound graphs)."""
         _chk(self.lib.gat_step_graph(self._ctx, int(enable)))
+
+    def step_graph_state(self) -> int:
+        """0 off, 1 armed (the next step runs eagerly or captures), 2 captured (the next step is a replay)."""
+        s = C.c_int32()
+        _chk(self.lib.gat_step_graph_state(self._ctx, C.byref(s)))
+        return s.value
 
     @staticmethod
     def comm_unique_id() -> bytes:
@@ -928,6 +947,37 @@ def op_negative_sample(d_row_ptr: int, d_col_idx: int, n_rows: int, n_edges: int
                                                C.c_void_p(d_src_u or None), C.c_void_p(d_src_v or None), n_src, C.c_void_p(d_u or None),
                                                C.c_void_p(d_v or None), count, C.byref(uf), C.c_void_p(stream or None)))
     return uf.value
+
+
+RANK_MAX_KS = 8
+# gat_rank_stats, field for field (no padding: every member is 8 bytes wide)
+RANK_STATS_DTYPE = np.dtype([("n_pos", np.int64), ("n_neg", np.int64), ("n_nan", np.int64), ("auc_num", np.uint64), ("ap", np.float64),
+                             ("mrr", np.float64), ("hits", np.int64, (RANK_MAX_KS,))])
+
+
+def rank_stats_dict(out: np.ndarray, n_ks: int) -> dict:
+    """A gat_rank_stats array as a dict of per-column arrays, with the two ratios callers divide out themselves: auc = auc_num /
+    (2 n_pos n_neg), NaN where a class is missing; hits_at = hits / n_pos (NaN without positives)."""
+    d = {f: out[f].copy() for f in ("n_pos", "n_neg", "n_nan", "auc_num", "ap", "mrr")}
+    d["hits"] = out["hits"][:, :n_ks].copy()
+    pn = d["n_pos"].astype(np.float64) * d["n_neg"].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d["auc"] = np.where(pn > 0, d["auc_num"].astype(np.float64) / (2.0 * pn), np.nan)
+        d["hits_at"] = np.where(d["n_pos"][:, None] > 0, d["hits"].astype(np.float64) / d["n_pos"][:, None].astype(np.float64), np.nan)
+    return d
+
+
+def op_rank_stats(d_scores: int, score_stride: int, n_rows: int, n_cols: int, d_labels: int = 0, d_targets: int = 0, d_mask: int = 0,
+                  ks=(), stream: int = 0) -> dict:
+    """gat_op_rank_stats on device pointers: the ranking statistics per column of scores [n_rows][n_cols] (rows score_stride floats
+    apart) against int32 labels [n_rows] or float targets [n_rows][n_cols] (exactly one), over the rows of the uint8 mask (0: all).
+    -> the dict of GatContext.eval_rank."""
+    k = np.ascontiguousarray(ks, np.int32).reshape(-1)
+    out = np.zeros(max(int(n_cols), 0), RANK_STATS_DTYPE)
+    _chk(load_library().gat_op_rank_stats(C.c_void_p(d_scores or None), score_stride, C.c_void_p(d_labels or None), C.c_void_p(d_targets or None),
+                                          C.c_void_p(d_mask or None), n_rows, n_cols, _np_ptr(k) if len(k) else None, len(k),
+                                          _np_ptr(out) if len(out) else None, C.c_void_p(stream or None)))
+    return rank_stats_dict(out, len(k))
 
 
 PART_BOTH, PART_LEFT, PART_RIGHT = 0, 1, 2       # the `part` of the dense seams

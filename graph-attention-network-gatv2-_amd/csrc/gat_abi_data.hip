@@ -333,6 +333,41 @@ int gat_eval_mask(gat_ctx* c, const uint8_t* mask, int64_t n_rows, double* loss_
     if (n_nodes) *n_nodes = (int32_t)nn;
     return 0;
 }
+// Ranking metrics of the last forward over a split (gatv2_abi.h "ranking metrics"): y as gat_eval_mask takes it, the mask in mask_tmp, the
+// call's buffers allocated once.  Reads y, the labels / targets and the mask; writes only its own buffers: a later step sees nothing of it.
+int gat_eval_rank(gat_ctx* c, const uint8_t* mask, int64_t n_rows, const int32_t* ks, int32_t n_ks, gat_rank_stats* out) {
+    GAT_TRY(check_layer(c, 0));
+    if (c->sup.loss_mode == GAT_LOSS_MSE) return fail(GAT_E_UNSUPPORTED, "gat_eval_rank: not with GAT_LOSS_MSE (a regression target has no binary relevance)");
+    if (c->graph.n_table != c->graph.n_rows || c->graph.table_row0 != 0 || c->xch.comm)
+        return fail(GAT_E_UNSUPPORTED, "gat_eval_rank: not on a destination-range shard or a context with a transport (a ranking is global: it cannot be summed over shards)");
+    const int32_t C = c->cfg.num_classes;
+    GAT_TRY(rank_check("gat_eval_rank", head_rows(c), C, ks, n_ks));
+    if (!mask || !out) return fail(GAT_E_INVALID, "gat_eval_rank: null argument");
+    if (!c->head.ran) return fail(GAT_E_STATE, "gat_eval_rank: no forward yet (call it after gat_forward or gat_step)");
+    GAT_TRY(upload_mask(c, mask, n_rows, &c->sup.mask_tmp));
+    if (!c->head.y_valid) GAT_TRY(gat_head_forward(c, nullptr, nullptr));     // after a fused head step: y = f(H_L, Wo), both still there
+    RankSizes z;
+    GAT_TRY(rank_sizes(n_rows, C, &z));
+    if (!c->rank.have || z.slots != c->rank.sizes.slots || z.temp_bytes != c->rank.sizes.temp_bytes || z.partial_doubles != c->rank.sizes.partial_doubles) {
+        RankBuffers& b = c->rank.buf;                   // first use (the head's rows and C are fixed for the context's life; a change: again)
+        for (void* p : {(void*)b.keys0, (void*)b.keys1, (void*)b.incl, b.temp, (void*)b.seg, (void*)b.stats, (void*)b.partial, (void*)b.ks}) dfree(c, p);
+        b = RankBuffers{};
+        c->rank.have = false;
+        GAT_TRY(rank_buffers_get(&b, z, C, [c](void** p, size_t bytes) { return dmalloc(c, p, bytes); }));
+        c->rank.sizes = z; c->rank.have = true;
+    }
+    RankArgs a{};
+    a.scores = c->head.y; a.score_stride = C;
+    a.labels = c->sup.loss_mode == 0 ? c->sup.labels : nullptr; a.targets = c->sup.loss_mode == 0 ? nullptr : c->sup.targets;
+    a.mask = c->sup.mask_tmp; a.n_rows = n_rows; a.n_cols = C; a.ks = ks; a.n_ks = n_ks;
+    {
+        Scope t(c, GAT_K_MISC);
+        GAT_TRY(launch_rank_stats(a, c->rank.buf, c->stream));
+    }
+    GAT_HIP(hipMemcpyAsync(out, c->rank.buf.stats, (size_t)C * sizeof(gat_rank_stats), hipMemcpyDeviceToHost, c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
 int gat_set_labels(gat_ctx* c, const int32_t* labels, int64_t n_rows) {
     return set_labels_common(c, labels, n_rows, hipMemcpyHostToDevice);
 }

@@ -185,7 +185,7 @@ int gat_head_forward(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
         if (c->sup.loss_mode != 0) GAT_TRY(launch_loss_head_forward(loss_head_args(c), c->stream));
         else GAT_TRY(launch_head_forward(a, c->stream));
     }
-    c->head.y_valid = true;
+    c->head.y_valid = true; c->head.ran = true;
     if (loss_sum || n_correct) {
         float hl = 0.f; int32_t hc = 0;
         GAT_HIP(hipMemcpyAsync(&hl, c->head.loss_out, sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -439,7 +439,7 @@ static int head_step(gat_ctx* c, bool with_gh = true) {
     GAT_TRY(pair_gather(c));
     {
         Scope t(c, GAT_K_HEAD_BWD);
-        c->head.y_valid = false;
+        c->head.y_valid = false; c->head.ran = true;
         if (c->sup.loss_mode != 0) GAT_TRY(launch_loss_head_grad(loss_head_args(c), true, c->stream));
         else GAT_TRY(launch_head_step(f, b, c->stream));
     }
@@ -690,8 +690,10 @@ static int step_graph(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
         c->replay.graph = g;
         GAT_HIP(hipGraphInstantiate(&c->replay.exec, c->replay.graph, nullptr, nullptr, 0));
         c->replay.state = 2;
+        c->replay.y_after = c->head.y_valid;
     }
     GAT_HIP(hipGraphLaunch(c->replay.exec, c->stream));
+    c->head.y_valid = c->replay.y_after;              // y of an earlier forward (gat_eval_mask, gat_eval_rank, gat_tap between replays) is stale now
     if (!loss_sum && !n_correct) return 0;
     GAT_HIP(hipStreamSynchronize(c->stream));
     if (loss_sum) *loss_sum = c->replay.pinned_tail[0];
@@ -704,6 +706,11 @@ int gat_step_graph(gat_ctx* c, int32_t enable) {
     if (enable && c->cfg.collect_timing) return fail(GAT_E_UNSUPPORTED, "gat_step_graph: not with collect_timing (event pairs cannot be read back from a replay)");
     graph_drop(c);
     c->replay.state = enable ? 1 : 0;
+    return 0;
+}
+int gat_step_graph_state(gat_ctx* c, int32_t* state) {
+    if (!c || !state) return fail(GAT_E_INVALID, "gat_step_graph_state: null argument");
+    *state = c->replay.state;
     return 0;
 }
 

@@ -144,12 +144,18 @@ struct gat_ctx {
         unsigned long long* plan_key = nullptr; unsigned long long* plan_off = nullptr; void* plan_temp = nullptr; size_t plan_temp_bytes = 0;
         uint64_t last_round = 0; int64_t unfiltered = 0;
     } neg;
-    // The output head: block partials, results, the class probabilities y (valid: y holds the last forward's, not after a fused head step).
+    // The output head: block partials, results, the class probabilities y (valid: y holds the last forward's, not after a fused head step;
+    // ran: the head has run at least once, so its input rows are those of a forward).
     struct Head {
         float* hb_partial = nullptr; double* loss_partial = nullptr; int32_t* correct_partial = nullptr;
         float* loss_out = nullptr; int32_t* correct_out = nullptr;
-        float* y = nullptr; bool y_valid = false;
+        float* y = nullptr; bool y_valid = false, ran = false;
     } head;
+    // Ranking metrics (gatv2_abi.h "ranking metrics"): the buffers of gat_eval_rank, allocated at its first call for head rows x C slots
+    // and kept (sizes: what they were allocated for).
+    struct Rank {
+        gat::RankBuffers buf; gat::RankSizes sizes; bool have = false;
+    } rank;
     // Backward scratch.  gPL [n_table][HDmax] (may be caller-bound), gPR [n_rows][HDmax]; gH [n_rows][gh_stride] the head-independent output
     // gradient (gh_stride: D_last, or 16 = 64-B records {gH row | the row's LReLU'(h_pre) decision bytes at +32}, hbits); the per-edge
     // scatter: csc_pos [E] slot of each CSR edge in source-major order, src_index everything else the source-major pass walks (src_ptr null
@@ -183,9 +189,10 @@ struct gat_ctx {
         std::vector<hipEvent_t> fork, join;
     } ov;
     // gat_step as a replayed hipGraph (gat_step_graph).  state: 0 off, 1 armed (next step runs eagerly, then captures), 2 ready;
-    // pinned_tail [4]: host-pinned landing zone of {loss, correct lo, correct hi}.
+    // pinned_tail [4]: host-pinned landing zone of {loss, correct lo, correct hi}; y_after: what head.y_valid is after the captured body
+    // (a replay runs none of the host code that keeps the flag: false when the body's head is the fused one, which writes no y).
     struct Replay {
-        int state = 0, warm = 0;
+        int state = 0, warm = 0; bool y_after = false;
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
         float* pinned_tail = nullptr;
     } replay;

@@ -2,6 +2,7 @@
 // gfx950 (MI355X) only: wave64, fp32 MFMA, no portability layer.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -686,6 +687,45 @@ struct NegSampleArgs {
     unsigned long long* unfiltered;                                     // [1] device word, ADDED to: negatives whose 16 attempts all failed
 };
 int launch_negative_sample(const NegSampleArgs& a, hipStream_t s);
+
+// ---- ranking metrics (gat_rank.hip; the contract — the law — is in gatv2_abi.h "ranking metrics") -----------------------------------
+// Per column of scores [n_rows][n_cols] (rows score_stride floats apart) the rank statistics of gat_rank_stats.  Exactly one of labels
+// [n_rows] / targets [n_rows][n_cols] is set; mask [n_rows] may be null (every row); ks: host values, checked by rank_check.
+struct RankArgs {
+    const float* scores; int64_t score_stride;
+    const int32_t* labels; const float* targets; const uint8_t* mask;
+    int64_t n_rows; int32_t n_cols;
+    const int32_t* ks; int32_t n_ks;
+};
+// What a call of that shape needs: slots = n_rows * n_cols keys per key buffer and prefix counts, temp_bytes for the sort and the scan,
+// partial_doubles of block partials (blocks_per_col blocks of the rank kernel per column, a function of the shape alone).
+struct RankSizes { int64_t slots = 0; size_t temp_bytes = 0; int32_t blocks_per_col = 0; int64_t partial_doubles = 0; };
+// The call's device buffers (20 B per slot + temp + O(n_cols)): the context keeps one set for its life, the seam a Scratch.
+// stats [n_cols] is where the kernels leave the result.
+struct RankBuffers {
+    unsigned long long* keys0 = nullptr; unsigned long long* keys1 = nullptr; uint32_t* incl = nullptr;
+    void* temp = nullptr; size_t temp_bytes = 0;
+    uint4* seg = nullptr; gat_rank_stats* stats = nullptr; double* partial = nullptr; int32_t* ks = nullptr;
+};
+// get(void** p, size_t bytes) -> int allocates one buffer
+template <class Get> int rank_buffers_get(RankBuffers* b, const RankSizes& z, int32_t n_cols, Get&& get) {
+    const size_t slots = (size_t)std::max<int64_t>(z.slots, 1);
+    GAT_TRY(get((void**)&b->keys0, slots * sizeof(unsigned long long)));
+    GAT_TRY(get((void**)&b->keys1, slots * sizeof(unsigned long long)));
+    GAT_TRY(get((void**)&b->incl, slots * sizeof(uint32_t)));
+    GAT_TRY(get(&b->temp, z.temp_bytes));
+    b->temp_bytes = z.temp_bytes;
+    GAT_TRY(get((void**)&b->seg, (size_t)n_cols * sizeof(uint4)));
+    GAT_TRY(get((void**)&b->stats, (size_t)n_cols * sizeof(gat_rank_stats)));
+    GAT_TRY(get((void**)&b->partial, (size_t)std::max<int64_t>(z.partial_doubles, 2) * sizeof(double)));
+    GAT_TRY(get((void**)&b->ks, GAT_RANK_MAX_KS * sizeof(int32_t)));
+    return 0;
+}
+// argument rules shared by gat_eval_rank and gat_op_rank_stats (codes of gatv2_abi.h); who: the caller's name for the text
+int rank_check(const char* who, int64_t n_rows, int32_t n_cols, const int32_t* ks, int32_t n_ks);
+int rank_sizes(int64_t n_rows, int32_t n_cols, RankSizes* out);
+// all launches on s, no synchronisation; afterwards b.stats holds the result
+int launch_rank_stats(const RankArgs& a, const RankBuffers& b, hipStream_t s);
 
 // train / validation masks (README R:134 "later"): labels_eff = mask ? label : ~label — the head kernels skip negative
 // labels (no loss, no count, dz = 0); eval_mask: fixed-order block partials of loss / #correct / #nodes over a mask

@@ -805,4 +805,28 @@ int gat_op_dense_grad_x_res(const float* d_g, const float* d_wres, float* d_gx, 
     return op_dense_finish(who, rc, s, picked, picked_cap);
 }
 
+// ---- ranking metrics (gatv2_abi.h "ranking metrics"): the kernels of gat_eval_rank on caller-owned device pointers -------------------
+int gat_op_rank_stats(const float* d_scores, int64_t score_stride, const int32_t* d_labels, const float* d_targets, const uint8_t* d_mask,
+                      int64_t n_rows, int32_t n_cols, const int32_t* ks, int32_t n_ks, gat_rank_stats* out, void* stream) {
+    static const char* who = "gat_op_rank_stats";
+    GAT_TRY(rank_check(who, n_rows, n_cols, ks, n_ks));
+    if (!d_scores || !out) return fail(GAT_E_INVALID, std::string(who) + ": null argument");
+    if ((d_labels != nullptr) == (d_targets != nullptr)) return fail(GAT_E_INVALID, std::string(who) + ": exactly one of d_labels / d_targets must be given");
+    if (score_stride < n_cols) return fail(GAT_E_INVALID, std::string(who) + ": score_stride below n_cols");
+    hipStream_t s = (hipStream_t)stream;
+    Scratch tmp;
+    RankSizes z; RankBuffers b;
+    GAT_TRY(rank_sizes(n_rows, n_cols, &z));
+    GAT_TRY(rank_buffers_get(&b, z, n_cols, [&tmp](void** p, size_t bytes) { return tmp.get((char**)p, (int64_t)bytes); }));
+    RankArgs a{};
+    a.scores = d_scores; a.score_stride = score_stride; a.labels = d_labels; a.targets = d_targets; a.mask = d_mask;
+    a.n_rows = n_rows; a.n_cols = n_cols; a.ks = ks; a.n_ks = n_ks;
+    int rc = launch_rank_stats(a, b, s);
+    if (rc == 0 && hipMemcpyAsync(out, b.stats, (size_t)n_cols * sizeof(gat_rank_stats), hipMemcpyDeviceToHost, s) != hipSuccess)
+        rc = fail(GAT_E_STATE, std::string(who) + ": copy of the result failed");
+    const hipError_t e = hipStreamSynchronize(s);
+    if (rc == 0 && e != hipSuccess) rc = fail((int)e, std::string(who) + ": " + hipGetErrorString(e));
+    return rc;
+}
+
 }  // extern "C"

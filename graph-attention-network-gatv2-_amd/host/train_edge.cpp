@@ -43,6 +43,9 @@
 // "u v" per line (not necessarily an edge), labels.txt / targets.txt, --train-mask and --val-mask files hold one line per pair.  The output
 // head reads X[u]*X[v] / X[u]+X[v] of the last layer's rows; the epoch lines keep their format, loss and accuracy are over pairs.  One rank
 // only (an endpoint may live on another shard), not with --readout; --cache is not used.
+// --rank-metrics K1,K2,... (with --val-mask, --ranks 1, not --loss mse): one more line behind every validation line — ROC-AUC, average
+// precision, MRR and Hits@K of the validation rows (gatv2_abi.h "ranking metrics"), macro-averaged over the output columns that have both
+// classes, then the count of those columns.  Every other line is printed as without the flag.
 // --add-self-loops / --undirected / --coalesce: the graph is rebuilt on the device before training (gat_graph_from_coo:
 // GAT_GRAPH_SELF_LOOPS / SYMMETRIZE / COALESCE, applied in that order); a CSR dataset is expanded to an edge list first.
 // Edge-list dataset: a folder with edges.txt (one "src dst" pair per line, a message flows src -> dst) instead of
@@ -107,6 +110,7 @@ struct Options {
     std::string neg_sampling;             // --neg-sampling uniform|corrupt: lines --neg-first .. of pairs.txt are redrawn before every epoch
     long long neg_first = -1; uint64_t neg_seed = 0; int neg_flags = 0;      // --neg-first K, --neg-seed S, GAT_NEG_*: --neg-both-directions, --neg-allow-self
     std::string loss = "softmax";         // --loss softmax|bce|mse: bce / mse read targets.txt (rows of C floats, nan allowed) in place of labels.txt
+    std::vector<int32_t> rank_ks; bool rank_metrics = false;      // --rank-metrics K1,K2,...: a ranking line behind every validation line
 };
 
 // A CSR built before the ranks were forked (main): row_ptr [n + 1] then col_idx [e] in shared memory.
@@ -148,6 +152,10 @@ const char* kUsage =
     "                          (regression) read targets.txt in place of labels.txt: one row of C floats per node — per graph with\n"
     "                          --readout — where nan marks a missing entry; C is the row width.  The epoch line prints the loss sum over\n"
     "                          the present entries of the training rows, and for bce the accuracy over those entries\n"
+    "            --rank-metrics K1,K2,...   with --val-mask: behind every validation line one line \"Val AUC: .., AP: .., MRR: .., Hits@K1: ..\n"
+    "                          (n columns)\" — ROC-AUC, average precision, MRR (every positive against all negatives) and Hits@K of the\n"
+    "                          validation rows, ranked on the device, macro-averaged over the n output columns that have both classes\n"
+    "                          (up to 8 K >= 1; --ranks 1; not with --loss mse)\n"
     "            --ranks P [--transport rccl|host] [--halo 0|1|2]\n";
 
 struct RankEnv {                      // one forked process per GPU
@@ -242,6 +250,16 @@ Options parse_args(int argc, char** argv) {
         else if (a == "--neg-both-directions") o.neg_flags |= GAT_NEG_BOTH_DIRECTIONS;
         else if (a == "--neg-allow-self") o.neg_flags |= GAT_NEG_ALLOW_SELF;
         else if (a == "--loss" && has_val) o.loss = argv[++i];
+        else if (a == "--rank-metrics" && has_val) {          // (checked in main, before anything touches the GPU)
+            o.rank_metrics = true;
+            for (const char* p = argv[++i]; *p;) {
+                char* end = nullptr;
+                const long k = std::strtol(p, &end, 10);
+                if (end == p) break;
+                o.rank_ks.push_back((int32_t)k);
+                p = *end == ',' ? end + 1 : end;
+            }
+        }
         else if (a == "--transport" && has_val) {
             o.transport = argv[++i];
             if (o.transport != "rccl" && o.transport != "host") die("Invalid transport choice. Use 'rccl' or 'host'\n");
@@ -682,6 +700,26 @@ int run(const Options& o, const RankEnv& env) {
         else if (loss_mode == GAT_LOSS_BCE) std::printf("Val Loss: %f, Val Accuracy: %.2f%%\n", val_entries ? vl / val_entries : 0.0, val_entries ? 100.0f * (static_cast<float>(vc) / val_entries) : 0.0f);
         else std::printf("Val Loss: %f\n", val_entries ? vl / val_entries : 0.0);
     };
+    // --rank-metrics: the ranking line behind a validation line (gat_eval_rank over the validation rows of the forward the validation
+    // line came from): macro averages over the output columns that have both classes, and how many those are
+    auto print_rank = [&]() {
+        if (!o.rank_metrics) return;
+        std::vector<gat_rank_stats> rs((size_t)C);
+        check(gat_eval_rank(ctx, val_m.data(), NH, o.rank_ks.data(), (int32_t)o.rank_ks.size(), rs.data()), "gat_eval_rank");
+        double auc = 0.0, ap = 0.0, mrr = 0.0;
+        std::vector<double> hits(o.rank_ks.size(), 0.0);
+        int n = 0;
+        for (const gat_rank_stats& s : rs) {
+            if (s.n_pos == 0 || s.n_neg == 0) continue;
+            ++n;
+            auc += (double)s.auc_num / (2.0 * (double)s.n_pos * (double)s.n_neg); ap += s.ap; mrr += s.mrr;
+            for (size_t k = 0; k < hits.size(); ++k) hits[k] += (double)s.hits[k] / (double)s.n_pos;
+        }
+        const double d = n ? (double)n : 1.0;
+        std::printf("Val AUC: %.6f, AP: %.6f, MRR: %.6f", auc / d, ap / d, mrr / d);
+        for (size_t k = 0; k < hits.size(); ++k) std::printf(", Hits@%d: %.6f", (int)o.rank_ks[k], hits[k] / d);
+        std::printf(" (%d column%s)\n", n, n == 1 ? "" : "s");
+    };
     const bool dropout = o.dropout > 0.f || o.attn_dropout > 0.f || o.drop_edge > 0.f;
     if (dropout) check(gat_set_dropout(ctx, o.dropout, o.attn_dropout, o.seed, 0), "gat_set_dropout");   // also seeds DropEdge
     if (o.drop_edge > 0.f) check(gat_set_dropedge(ctx, o.drop_edge, o.drop_edge_flags), "gat_set_dropedge");
@@ -733,6 +771,7 @@ int run(const Options& o, const RankEnv& env) {
             double vl = 0.0; int32_t vc = 0, vn = 0;
             check(gat_eval_mask(ctx, val_m.data(), NH, &vl, &vc, &vn), "gat_eval_mask");
             print_val(vl, vc, vn);
+            print_rank();
         }
         check(gat_backward(ctx), "gatv2 backward");
         if (o.clip) check(gat_clip(ctx, 5.0f), "clip_grad_norm");                   // E:1563
@@ -746,6 +785,7 @@ int run(const Options& o, const RankEnv& env) {
             check(gat_eval_mask(ctx, val_m.data(), NH, &vl, &vc, &vn), "gat_eval_mask");
             check(gat_set_training(ctx, 1), "gat_set_training");
             print_val(vl, vc, vn);
+            print_rank();
         }
         check(gat_sync(ctx), "gat_sync");
         const std::chrono::duration<double, std::milli> elapsed = std::chrono::high_resolution_clock::now() - start;
@@ -787,9 +827,24 @@ int main(int argc, char** argv) {
     // anything touches the GPU
     bool graph_flag = false, edge_feat_flag = false, readout_flag = false, targets_flag = false, pairs_flag = false;
     bool neg_flag = false, neg_corrupt = false; long long neg_first = -1;
+    bool rank_flag = false, val_flag = false, mse_flag = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--help") { std::cout << kUsage; return 0; }
+        if (a == "--val-mask" && i + 1 < argc) val_flag = true;
+        if (a == "--rank-metrics") {                       // 1 .. GAT_RANK_MAX_KS integers >= 1, comma separated, nothing else
+            const std::string v = i + 1 < argc ? argv[i + 1] : "";
+            int n = 0;
+            bool ok = !v.empty();
+            for (const char* p = v.c_str(); ok && *p;) {
+                char* end = nullptr;
+                const long k = std::strtol(p, &end, 10);
+                ok = end != p && *p >= '0' && *p <= '9' && k >= 1 && k <= 2147483647L && (*end == '\0' || (*end == ',' && end[1] != '\0')) && ++n <= GAT_RANK_MAX_KS;
+                p = *end == ',' ? end + 1 : end;
+            }
+            if (!ok) die("Error: --rank-metrics takes 1 to " + std::to_string(GAT_RANK_MAX_KS) + " comma-separated integers K >= 1\n");
+            rank_flag = true;
+        }
         if (a == "--readout") {
             const std::string v = i + 1 < argc ? argv[i + 1] : "";
             if (v != "mean" && v != "sum" && v != "max") die("Error: --readout must be mean, sum or max\n");
@@ -816,8 +871,12 @@ int main(int argc, char** argv) {
             const std::string v = i + 1 < argc ? argv[i + 1] : "";
             if (v != "softmax" && v != "bce" && v != "mse") die("Error: --loss must be softmax, bce or mse\n");
             targets_flag = v != "softmax";
+            mse_flag = v == "mse";
         }
     }
+    if (rank_flag && !val_flag) die("Error: --rank-metrics needs --val-mask: the ranking is over the validation rows\n");
+    if (rank_flag && multi) die("Error: --rank-metrics needs --ranks 1: a ranking is global and cannot be summed over shards\n");
+    if (rank_flag && mse_flag) die("Error: --rank-metrics cannot be combined with --loss mse: a regression target has no binary relevance\n");
     if (edge_feat_flag && graph_flag)
         die("Error: --edge-features cannot be combined with --add-self-loops / --undirected / --coalesce: they rebuild the graph, and the rows of "
             "edge_features.txt (one per CSR edge of the dataset) would no longer match its edges\n");

@@ -273,6 +273,9 @@ int gat_step(gat_ctx* ctx, float* loss_sum, int32_t* n_correct);
  * one launch per step instead of ~25; for graphs small enough to be launch-bound.  Single shard, no
  * transport, collect_timing = 0.  Results are those of the eager step, bit for bit. */
 int gat_step_graph(gat_ctx* ctx, int32_t enable);
+/* *state = 0 off, 1 armed (the next gat_step runs eagerly or captures), 2 captured (the next gat_step is a replay).  A call that re-arms a
+ * captured step (gat_bind_table, a changed mask, replaced pairs, ...) takes 2 back to 1; gat_eval_mask, gat_eval_rank and gat_tap do not. */
+int gat_step_graph_state(gat_ctx* ctx, int32_t* state);
 
 /* Exchange buffers.  GAT_TABLE_PL: projected source features, [n_table][H_l*D_l] f32, the
  * context writes rows [table_row0, +n_rows) in gat_layer_project and reads all rows in the edge
@@ -788,6 +791,67 @@ int gat_set_targets_device(gat_ctx* ctx, const float* d_t, int64_t n_rows, int32
 int gat_loss_info(gat_ctx* ctx, int32_t* mode, int32_t* n_cols);                              /* (0, num_classes) by default; pointers may be NULL */
 int gat_target_count(gat_ctx* ctx, const uint8_t* mask, int64_t n_rows, int64_t* n_entries);
         /* present entries in the rows of `mask` (host, [n_rows]); mask NULL = the current training set */
+
+/* ---- ranking metrics (beyond the reference, which reports a loss and an accuracy: ROC-AUC of ogbn-proteins / ogbg-molhiv, average
+ * precision of ogbg-molpcba, MRR of ogbl-citation2, Hits@K of ogbl-collab / -ppa / -ddi) ----
+ * The integer rank statistics behind those metrics, per output column, formed on the device from ONE sort of the scores it already holds.
+ * THE LAW — tests/rank_ref.py states it in numpy.  Inputs: the head's rows r of the LAST forward (nodes; the graphs of a readout context; the
+ * pairs of a pair head) and a host mask over those rows, as gat_eval_mask takes it.  The score of entry (r, c) is the value GAT_TAP_Y
+ * returns for it: the softmax probability of class c in the default loss mode (one-vs-rest), sigmoid(z) under GAT_LOSS_BCE.
+ *   Saturation: fp32 sigmoid(z) is exactly 1.0 above z ~ 17 (and the softmax probability of a dominant class likewise), so very confident
+ *   entries TIE.  Ties are handled exactly (below); ranking on the logits z is out of scope.
+ * An entry TAKES PART when its row is in the mask, its target is present (BCE: !isnan(t); softmax mode: always) and its score is not NaN.
+ *   An entry with a NaN score that passes the first two tests is counted in n_nan and otherwise ignored.
+ * An entry is POSITIVE when label[r] == c (softmax mode) or t > 0.5 (BCE: the rule n_correct uses), else NEGATIVE.
+ * Two scores TIE when they compare equal as floats: -0.0 and +0.0 tie, +-inf are ordinary values.
+ * Per column c, over its participating entries, with P positives and N negatives:
+ *   n_pos, n_neg, n_nan   the counts
+ *   auc_num  = sum over the positives of  2 * #{negatives strictly lower} + #{negatives equal}      (twice the Mann-Whitney U, ties at 1/2)
+ *              AUC = auc_num / (2 P N) is the caller's division: sklearn.metrics.roc_auc_score; undefined when P * N == 0
+ *   ap       = (1/P) sum over the positives of  TP(>= s) / (TP(>= s) + FP(>= s)),  s the positive's score, the counts over all participating
+ *              entries of the column: sklearn.metrics.average_precision_score (one threshold per distinct score); 0 when P == 0
+ *   mrr      = (1/P) sum over the positives of  1 / (1 + #{negatives higher} + 0.5 * #{negatives equal}): every positive ranked against ALL the
+ *              column's negatives, OGB's tie rule (mean of the optimistic and the pessimistic rank); 0 when P == 0
+ *   hits[k]  = for each of the n_ks <= GAT_RANK_MAX_KS caller-given K >= 1: the positives with a score STRICTLY above the K-th highest negative
+ *              score (duplicates count, as torch.topk does): OGB's Hits@K numerator; with N < K it is P (OGB returns 1.0 there).  hits[n_ks ..] = 0
+ *   All integers are exact.  Each fp64 term is one division of exact integers (mrr: of 1 by an exact half-integer); the two sums are formed
+ *   in an order fixed by the shape — per-thread, per-block and per-column in ascending order, no float atomics — so they are bitwise
+ *   reproducible from run to run and lie within (P + 2) * 2^-52 relative of the exact sum.  Integer atomics are used.
+ * Grouped ranking (each positive against its OWN negatives, ogbl-citation2's evaluator), micro-averages and F1 are out of scope.
+ * Where it runs (csrc/gat_rank.hip).  One pass writes a 64-bit key per (row, column) slot — column in the high bits, then the order-preserving
+ *   unsigned image of the score (sign-flipped float bits, -0.0 folded onto +0.0), the positive bit lowest; the all-ones key for a slot that does
+ *   not take part — and counts the NaN scores.  One radix sort over the 33 + bit_width(C) bits in use.  An inclusive prefix count of negatives
+ *   over the sorted keys.  The C column segments by binary search.  The rank kernel: one lane per sorted slot; a positive finds its tie group
+ *   by a galloping and a binary search on key >> 1 inside its column's segment (never a walk: a saturated column is one group of millions),
+ *   reads negatives below / equal / above and TP, FP from the prefix counts, and leaves its terms to fixed-order block partials that a last
+ *   kernel adds per column.  Hits@K: per (column, K) one search on the prefix counts and one for the end of the tie group, no pass over the data.
+ *   Temporary device memory: 20 bytes per slot (two key buffers and the prefix counts; slots = rows * C) plus the sort's scratch (a few
+ *   MB) and O(C) words — 80 MB for 4 M pairs at C = 1, 2.3 GB for 2.45 M rows at C = 47.  The context allocates it at the first
+ *   gat_eval_rank and keeps it; the seam allocates and frees per call.  rows * C >= 2^31 slots: GAT_E_UNSUPPORTED, never truncated.
+ * gat_eval_rank(ctx, mask, n_rows, ks, n_ks, out): out is a HOST array of num_classes entries.  The mask follows gat_eval_mask's rules (non-NULL,
+ *   length = the head's rows, else GAT_E_INVALID), and so does y: after a fused head step (gat_step) the head's forward kernel is re-run
+ *   on the last forward's rows, as gat_eval_mask and gat_tap(GAT_TAP_Y) do.  The call changes nothing a later step reads: it does not re-arm
+ *   a captured gat_step_graph (gat_step_graph_state stays 2) and advances no counter; the steps after it are bitwise those of a run
+ *   without it.  Between replayed steps it ranks the last replay's forward: a replay leaves y stale when its head is the fused one.
+ *   It synchronises.
+ *   n_ks outside 0..GAT_RANK_MAX_KS, or a K < 1: GAT_E_INVALID.  GAT_LOSS_MSE: GAT_E_UNSUPPORTED (no binary relevance).  A destination-range
+ *   shard (n_table != n_rows) or a context with a transport: GAT_E_UNSUPPORTED (a ranking is global and cannot be summed over shards).  Before
+ *   labels / targets, or before any forward: GAT_E_STATE.  Timed under GAT_K_MISC; gat_algorithmic_bytes is unchanged (not part of a step).
+ * gat_op_rank_stats is the same computation as a stateless seam on caller-owned DEVICE pointers (current device): d_scores rows of
+ *   score_stride >= n_cols floats; exactly one of d_labels [n_rows] / d_targets [n_rows][n_cols] non-NULL (else GAT_E_INVALID); d_mask
+ *   [n_rows] may be NULL (every row); ks and out are HOST arrays.  Every argument is checked before any launch (n_rows < 0, n_cols < 1,
+ *   score_stride < n_cols: GAT_E_INVALID; the K and slot rules above); it allocates and frees its scratch and synchronises `stream` (may
+ *   be NULL).  Nothing is written to device memory the caller owns. */
+#define GAT_RANK_MAX_KS 8
+typedef struct gat_rank_stats {
+    int64_t n_pos, n_neg, n_nan;
+    uint64_t auc_num;
+    double ap, mrr;
+    int64_t hits[GAT_RANK_MAX_KS];
+} gat_rank_stats;
+int gat_eval_rank(gat_ctx* ctx, const uint8_t* mask, int64_t n_rows, const int32_t* ks, int32_t n_ks, gat_rank_stats* out /* [num_classes] */);
+int gat_op_rank_stats(const float* d_scores, int64_t score_stride, const int32_t* d_labels, const float* d_targets, const uint8_t* d_mask,
+                      int64_t n_rows, int32_t n_cols, const int32_t* ks, int32_t n_ks, gat_rank_stats* out /* host, [n_cols] */, void* stream);
 
 /* ---- op-level entry points, whole layers: caller-provided DEVICE pointers in the reference layouts
  *      (unit parity).  `stream` may be NULL (default stream).  One entry point per reference KERNEL: below. ---- */
