@@ -50,6 +50,10 @@ PARAM_W, PARAM_A, PARAM_WO, PARAM_WRES, PARAM_B = 0, 1, 2, 3, 4
 PARAM_LN_G, PARAM_LN_B = 5, 6
 PARAM_WE = 7                                # edge features (set_edge_dim): flat [l][H_l*D_l][Fe], behind the others
 PARAM_GROUPS = (PARAM_W, PARAM_A, PARAM_WO, PARAM_WRES, PARAM_B, PARAM_LN_G, PARAM_LN_B, PARAM_WE)      # the packed order
+PARAM_HEAD_W, PARAM_HEAD_B = 8, 9           # hidden layer in front of the head (set_head_hidden): W1 [Dh][D_last], b1 [Dh], behind PARAM_WE
+PARAM_GROUPS_ALL = PARAM_GROUPS + (PARAM_HEAD_W, PARAM_HEAD_B)         # the packed order of a context with a hidden head layer
+HEAD_ACT_LRELU = 1
+HEAD_ACTS = {"relu": 0, "lrelu": HEAD_ACT_LRELU}
 EDGE_DIM_MAX = 64
 RES_LINEAR, RES_BIAS = 1, 2
 NORM_LAYER, NORM_SKIP_LAST = 1, 2
@@ -64,6 +68,7 @@ TAP_EDGE_KEEP = 17                          # DropEdge: 1 = edge kept, 0 = dropp
 TAP_POOLED = 18                             # readout: the pooled rows the head reads, [n_graphs][D_last] (last layer)
 DROPEDGE_KEEP_SELF, DROPEDGE_SHARED_LAYERS = 1, 2
 TAP_PAIRED = 19                             # pair head: the rows the head reads, [n_pairs][D_last] (last layer)
+TAP_HEAD_HIDDEN = 20                        # hidden head layer: Z1 of the last forward, [head_rows][Dh] (last layer)
 READOUT_NONE, READOUT_MEAN, READOUT_SUM, READOUT_MAX = 0, 1, 2, 3      # graph-level readout (set_readout)
 PAIR_NONE, PAIR_MUL, PAIR_ADD = 0, 1, 2                                # pair head (set_pairs)
 PAIR_MODES = {"none": PAIR_NONE, "mul": PAIR_MUL, "add": PAIR_ADD}
@@ -228,6 +233,10 @@ def _declare(lib: C.CDLL) -> None:
         "gat_pairs_info": [vp, P(i32), P(i64)],
         "gat_op_pair_forward": [vp, i64, vp, vp, i64, i64, i32, i32, vp, vp],
         "gat_op_pair_backward": [vp, vp, i64, vp, vp, i64, i64, i32, i32, vp, i64, vp],
+        "gat_set_head_hidden": [vp, i32, i32],
+        "gat_head_hidden_info": [vp, P(i32), P(i32)],
+        "gat_op_head_hidden_forward": [vp, vp, i64, i32, f32, vp],
+        "gat_op_head_hidden_backward": [vp, vp, i64, i32, f32, vp, vp],
         "gat_set_negative_sampling": [vp, i32, i64, i64, i32, C.c_uint64],
         "gat_resample_negatives": [vp, C.c_uint64],
         "gat_negatives_info": [vp, P(i32), P(i64), P(i64), P(C.c_uint64), P(i64)],
@@ -311,6 +320,7 @@ class GatContext:
         self.table_row0 = 0
         self.n_graphs = 0                               # > 0 on a readout context (set_readout)
         self.n_pairs = 0                                # > 0 on a context with a pair head (set_pairs)
+        self.head_hidden = 0                            # > 0 on a context with a hidden head layer (set_head_hidden)
 
     # -- lifecycle
     def close(self):
@@ -484,7 +494,7 @@ class GatContext:
 
     @property
     def n_params(self) -> int:
-        return sum(self.param_count(g) for g in PARAM_GROUPS)
+        return sum(self.param_count(g) for g in PARAM_GROUPS_ALL)
 
     # -- residual / bias (gatv2_abi.h "residual")
     def set_residual(self, linear: bool = False, bias: bool = False, flags: int = 0):
@@ -514,6 +524,20 @@ class GatContext:
 
     def set_edge_features_device(self, d_ea: int, n_edges: int, edge_dim: int):
         _chk(self.lib.gat_set_edge_features_device(self._ctx, C.c_void_p(d_ea or None), n_edges, edge_dim))
+
+    # -- hidden layer in front of the output head (gatv2_abi.h "hidden layer")
+    def set_head_hidden(self, width: int, act="relu"):
+        """One hidden layer of ``width`` units in front of the output head, for every head kind: Z1 = act(Xin W1^T + b1) with the
+        parameter groups PARAM_HEAD_W [width][D_last] / PARAM_HEAD_B [width]; PARAM_WO becomes [C][width].  act: "relu", "lrelu" (the
+        context's negative_slope) or the raw GAT_HEAD_ACT_* flags.  Only before the first params_* / grads_* / set_graph* call; 0 = off."""
+        _chk(self.lib.gat_set_head_hidden(self._ctx, int(width), head_act(act)))
+        self.head_hidden = int(width)
+
+    def head_hidden_info(self):
+        """(width, flags); (0, 0) while off."""
+        w, f = C.c_int32(), C.c_int32()
+        _chk(self.lib.gat_head_hidden_info(self._ctx, C.byref(w), C.byref(f)))
+        return w.value, f.value
 
     # -- graph-level readout (gatv2_abi.h "graph-level readout")
     def set_readout(self, mode, graph_ptr=None, batch=None):
@@ -789,6 +813,7 @@ class GatContext:
             TAP_Y: ((self.head_rows, self.C), np.float32),
             TAP_POOLED: ((G, self.outdims[-1]), np.float32),
             TAP_PAIRED: ((self.n_pairs, self.outdims[-1]), np.float32),
+            TAP_HEAD_HIDDEN: ((self.head_rows, self.head_hidden), np.float32),
             TAP_PL: ((self.n_table, H * D), np.float32), TAP_PR: ((N, H * D), np.float32),
             TAP_SCORE: ((H, E), np.float32), TAP_GALPHA: ((H, E), np.float32),
             TAP_GX: ((N, self.heads[l - 1] * self.outdims[l - 1] if l > 0 else 0), np.float32),
@@ -891,6 +916,15 @@ def loss_mode(mode) -> int:
     return int(mode)
 
 
+def head_act(act) -> int:
+    """"relu" / "lrelu" or the GAT_HEAD_ACT_* flags -> the flags."""
+    if isinstance(act, str):
+        if act not in HEAD_ACTS:
+            raise ValueError(f"head activation must be one of {sorted(HEAD_ACTS)}, got {act!r}")
+        return HEAD_ACTS[act]
+    return int(act)
+
+
 def batch_to_graph_ptr(batch) -> np.ndarray:
     """A sorted graph id per row (PyG's Batch.batch) -> graph_ptr [n_graphs + 1] int32, n_graphs = batch[-1] + 1 (ids that do not
     occur are empty graphs).  ValueError for an unsorted, negative or empty vector."""
@@ -935,6 +969,18 @@ def op_pair_backward(d_gq: int, d_x: int, x_stride: int, d_u: int, d_v: int, n_p
     _chk(load_library().gat_op_pair_backward(C.c_void_p(d_gq or None), C.c_void_p(d_x or None), x_stride, C.c_void_p(d_u or None),
                                              C.c_void_p(d_v or None), n_pairs, n_rows, width, pair_mode(mode), C.c_void_p(d_gh or None),
                                              gh_stride, C.c_void_p(stream or None)))
+
+
+def op_head_hidden_forward(d_a: int, d_b1: int, rows: int, width: int, slope: float = 0.0, stream: int = 0):
+    """gat_op_head_hidden_forward on device pointers: a [rows][width] becomes act(a + b1) in place (slope 0 = ReLU)."""
+    _chk(load_library().gat_op_head_hidden_forward(C.c_void_p(d_a or None), C.c_void_p(d_b1 or None), rows, width, slope, C.c_void_p(stream or None)))
+
+
+def op_head_hidden_backward(d_gz: int, d_z1: int, rows: int, width: int, slope: float = 0.0, d_grad_b1: int = 0, stream: int = 0):
+    """gat_op_head_hidden_backward on device pointers: gz [rows][width] becomes gz * (z1 > 0 ? 1 : slope) in place; its column sums are
+    added into grad_b1 [width] (0: not formed)."""
+    _chk(load_library().gat_op_head_hidden_backward(C.c_void_p(d_gz or None), C.c_void_p(d_z1 or None), rows, width, slope,
+                                                    C.c_void_p(d_grad_b1 or None), C.c_void_p(stream or None)))
 
 
 def op_negative_sample(d_row_ptr: int, d_col_idx: int, n_rows: int, n_edges: int, mode, flags: int, seed: int, round: int, d_u: int, d_v: int,

@@ -36,8 +36,8 @@ static std::string choices_text() {
     return t;
 }
 
-// The packed layout [W | a | Wo | Wres | b | gamma | beta | We]: every layer's offset inside the groups, the groups' sizes and where they
-// start.  Called whenever the set of groups changes: by relayout (gat_create, gat_set_residual, gat_set_norm, gat_set_edge_dim).
+// The packed layout [W | a | Wo | Wres | b | gamma | beta | We | W1 | b1]: every layer's offset inside the groups, the groups' sizes and where they
+// start.  Called whenever the set of groups changes: by relayout (gat_create, gat_set_residual, gat_set_norm, gat_set_edge_dim, gat_set_head_hidden).
 static void layout_params(gat_ctx* c) {
     int64_t* n = c->packed.group_cnt;
     std::fill(n, n + kParamGroups, (int64_t)0);
@@ -50,7 +50,8 @@ static void layout_params(gat_ctx* c) {
         if (c->res.norm_flags != 0) n[GAT_PARAM_LN_G] += y.HD;               // all L layers; with GAT_NORM_SKIP_LAST the last one's entries are never read
         n[GAT_PARAM_WE] += (int64_t)y.HD * c->ef.dim;
     }
-    n[GAT_PARAM_WO] = (int64_t)c->cfg.num_classes * c->layers.back().D;
+    n[GAT_PARAM_WO] = (int64_t)c->cfg.num_classes * head_width(c);      // [C][Dh] behind a hidden layer
+    if (hidden_on(c)) { n[GAT_PARAM_HEAD_W] = (int64_t)c->hid.width * c->layers.back().D; n[GAT_PARAM_HEAD_B] = c->hid.width; }
     n[GAT_PARAM_LN_B] = n[GAT_PARAM_LN_G];
     for (int k = 0; k < kParamGroups; ++k) c->packed.group_off[k] = k ? c->packed.group_off[k - 1] + n[k - 1] : 0;
 }
@@ -86,6 +87,7 @@ int ensure_drop_buffers(gat_ctx* c) {
 int ensure_buffers(gat_ctx* c) {
     if (c->buffers_ready) return 0;
     if (!(c->graph.have && c->in.have && c->sup.have)) return 0;
+    GAT_TRY(head_hidden_check(c));                   // the head's limits at the hidden width, now that the loss mode is fixed
     const int L = c->cfg.num_layers;
     const int64_t N = c->graph.n_rows, E = c->graph.n_edges, T = c->graph.n_table;
     for (int l = 0; l < L; ++l) {
@@ -117,7 +119,8 @@ int ensure_buffers(gat_ctx* c) {
         // L1 misses in flight, not by bytes: DESIGN §4)
         const Layer& yl = c->layers[L - 1];
         const int w = edge_stash_words(yl.H, yl.D);
-        c->bwd.gh_stride = (w > 0 && w <= 32 && yl.D <= 8 && !bf16(c) && !c->cfg.keep_taps) ? 16 : yl.D;
+        // (a hidden layer's gXin = gA W1 is written by a dense launcher: plain rows of D_last floats)
+        c->bwd.gh_stride = (w > 0 && w <= 32 && yl.D <= 8 && !bf16(c) && !c->cfg.keep_taps && !hidden_on(c)) ? 16 : yl.D;
         GAT_TRY(dalloc(c, &c->bwd.gH, N * c->bwd.gh_stride));
     }
     // work items (rows / hub-row segments) of the wave-per-item kernels
@@ -224,8 +227,15 @@ int ensure_buffers(gat_ctx* c) {
     }
     GAT_TRY(dalloc(c, &c->bwd.gw_scratch, gw));
     c->bwd.gw_scratch_floats = gw;
-    const int C = c->cfg.num_classes, DL = c->layers[L - 1].D;
+    const int C = c->cfg.num_classes, DL = head_width(c);      // the rows the head reads: Dh floats behind a hidden layer
     const int64_t NH = head_rows(c);                 // graphs with readout on
+    if (hidden_on(c)) {                              // gatv2_abi.h "hidden layer": Z1 and gZ1 [R][Dh], the column-sum partials, the slabs of gradW1
+        const int32_t Dh = c->hid.width;
+        GAT_TRY(dalloc(c, &c->hid.Z1, NH * Dh));
+        GAT_TRY(dalloc(c, &c->hid.gZ1, NH * Dh));
+        GAT_TRY(dalloc(c, &c->hid.partial, (int64_t)kHiddenPartialRows * Dh));
+        GAT_TRY(dalloc(c, &c->hid.gw_scratch, std::max<int64_t>(grad_w_scratch_floats(NH, c->layers[L - 1].D, Dh), 1)));
+    }
     GAT_TRY(dalloc(c, &c->head.hb_partial, (int64_t)head_bwd_blocks(NH, C, DL) * C * DL));
     GAT_TRY(dalloc(c, &c->head.loss_partial, head_blocks(NH)));
     GAT_TRY(dalloc(c, &c->head.correct_partial, head_blocks(NH)));
@@ -338,7 +348,7 @@ int gat_create(const gat_config* cfg, gat_ctx** out) {
     if (cfg->stream) { c->stream = (hipStream_t)cfg->stream; c->own_stream = false; }
     else { GAT_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
     GAT_TRY(relayout(c.get()));
-    GAT_TRY(dalloc(c.get(), &c->packed.clip_scratch, 8));
+    GAT_TRY(dalloc(c.get(), &c->packed.clip_scratch, kParamGroups));
     *out = c.release();
     return 0;
 }
@@ -449,7 +459,7 @@ int gat_params_init(gat_ctx* c, uint64_t seed) {
         GAT_TRY(launch_xavier_init(a_of(c, l), y.HD, s0, draw, lim, c->stream));
         draw += (uint64_t)y.HD;
     }
-    const float limo = sqrtf(6.0f / (float)(c->cfg.num_classes + c->layers.back().D));
+    const float limo = sqrtf(6.0f / (float)(c->cfg.num_classes + head_width(c)));        // Wo [C][Dh] behind a hidden layer: the draws behind it shift
     GAT_TRY(launch_xavier_init(Wo_of(c), c->packed.group_cnt[GAT_PARAM_WO], s0, draw, limo, c->stream));
     draw += (uint64_t)c->packed.group_cnt[GAT_PARAM_WO];
     if (c->packed.group_cnt[GAT_PARAM_WRES]) {                                  // after every existing draw: W, a and Wo of a seed do not depend on the flag
@@ -467,6 +477,12 @@ int gat_params_init(gat_ctx* c, uint64_t seed) {
             GAT_TRY(launch_xavier_init(We_of(c, l), ne, s0, draw, sqrtf(6.0f / (float)(c->ef.dim + y.HD)), c->stream));
             draw += (uint64_t)ne;
         }
+    }
+    if (hidden_on(c)) {                                                  // after every other draw; b1 = 0
+        const int64_t n1 = c->packed.group_cnt[GAT_PARAM_HEAD_W];
+        GAT_TRY(launch_xavier_init(W1_of(c), n1, s0, draw, sqrtf(6.0f / (float)(c->layers.back().D + c->hid.width)), c->stream));
+        draw += (uint64_t)n1;
+        GAT_HIP(hipMemsetAsync(b1_of(c), 0, (size_t)c->hid.width * sizeof(float), c->stream));
     }
     if (b_of(c, 0)) GAT_HIP(hipMemsetAsync(b_of(c, 0), 0, (size_t)c->packed.group_cnt[GAT_PARAM_B] * sizeof(float), c->stream));
     const std::vector<float> ones((size_t)c->packed.group_cnt[GAT_PARAM_LN_G], 1.0f);      // layer normalisation: gamma = 1, beta = 0, no draws

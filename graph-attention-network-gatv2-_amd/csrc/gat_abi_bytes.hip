@@ -137,8 +137,20 @@ static int algorithmic_bytes_softmax(gat_ctx* c, double* bytes_step, double* per
     k[GAT_K_MISC] += 4.0 * (N * DL + G * DL) + 4.0 * (G * DL + N * DL);
     return report_bytes(k, bytes_step, per_kernel);
 }
+static int algorithmic_bytes_modes(gat_ctx* c, double* bytes_step, double* per_kernel);
 int gat_algorithmic_bytes(gat_ctx* c, double* bytes_step, double* per_kernel) {
     if (!c || !c->graph.have) return fail(GAT_E_STATE, "graph not set");
+    if (!hidden_on(c)) return algorithmic_bytes_modes(c, bytes_step, per_kernel);
+    // hidden layer (gatv2_abi.h "hidden layer"): the head classes read rows of Dh floats where they read D_last; the stage adds, fp32:
+    // forward Xin, W1, A written, A read and Z1 written; backward gZ1 and Z1 read and gA written, then gA, Xin and gradW1, then gA, W1 and gXin
+    double k[GAT_K_COUNT] = {0};
+    GAT_TRY(algorithmic_bytes_modes(c, nullptr, k));
+    const double R = (double)head_rows(c), DL = c->layers.back().D, Dh = c->hid.width;
+    k[GAT_K_HEAD_FWD] += 4.0 * R * (Dh - DL) + 4.0 * (R * DL + Dh * DL + 3 * R * Dh);
+    k[GAT_K_HEAD_BWD] += 4.0 * R * (Dh - DL) + 4.0 * (3 * R * Dh + (R * Dh + R * DL + Dh * DL) + (R * Dh + Dh * DL + R * DL));
+    return report_bytes(k, bytes_step, per_kernel);
+}
+static int algorithmic_bytes_modes(gat_ctx* c, double* bytes_step, double* per_kernel) {
     if (c->sup.loss_mode == 0) return algorithmic_bytes_softmax(c, bytes_step, per_kernel);
     // loss modes (gatv2_abi.h "loss modes of the output head"): each head class reads 4*rows*C bytes of targets where the softmax head
     // reads 4*rows of labels

@@ -64,6 +64,46 @@ int gat_set_edge_features(gat_ctx* c, const float* ea, int64_t n_edges, int32_t 
 int gat_set_edge_features_device(gat_ctx* c, const float* d_ea, int64_t n_edges, int32_t edge_dim) {
     return set_edge_features_common(c, d_ea, n_edges, edge_dim, hipMemcpyDeviceToDevice);
 }
+// ---- hidden layer in front of the output head -----------------------------------------------------------------------
+}  // extern "C"
+namespace gat {
+// The head's own limits with Dh in D_last's place.  mode_known: the loss mode is fixed (the context is being completed); before that
+// only what holds for every mode is refused: C * Dh <= 2048.
+static int hidden_width_check(gat_ctx* c, int32_t width, bool mode_known) {
+    const int32_t C = c->cfg.num_classes;
+    std::string limit;
+    int rc = (int64_t)C * width > 2048 ? GAT_E_UNSUPPORTED : 0;
+    if (rc) limit = "num_classes * width <= 2048";
+    else if (mode_known) rc = head_shape_check(C, width, c->sup.loss_mode, &limit);
+    if (rc) return fail(rc, "gat_set_head_hidden: width " + std::to_string(width) + " with num_classes " + std::to_string(C) + " is outside the output head's limit: " + limit);
+    return 0;
+}
+int head_hidden_check(gat_ctx* c) {
+    if (!hidden_on(c)) return 0;
+    GAT_TRY(hidden_refuse_shard(c, c->graph.n_rows, c->graph.n_table));
+    return hidden_width_check(c, c->hid.width, true);
+}
+}  // namespace gat
+extern "C" {
+int gat_set_head_hidden(gat_ctx* c, int32_t width, int32_t flags) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (width < 0) return fail(GAT_E_INVALID, "gat_set_head_hidden: width must be >= 0 (0 = no hidden layer)");
+    if (flags & ~GAT_HEAD_ACT_LRELU) return fail(GAT_E_INVALID, "gat_set_head_hidden: unknown flag bits");
+    if (width == 0 && c->hid.width == 0) return 0;       // the default: nothing is touched
+    GAT_LAYOUT_OPEN(c, "gat_set_head_hidden");
+    if (width > 0 && c->cfg.flat_lrelu_index)
+        return fail(GAT_E_UNSUPPORTED, "gat_set_head_hidden: not with flat_lrelu_index = 1 (the head would write the last layer's g itself)");
+    GAT_REFUSE_DBG(c, width > 0, "gat_set_head_hidden", "");
+    if (width > 0) GAT_TRY(hidden_width_check(c, width, false));
+    c->hid.width = width; c->hid.flags = width > 0 ? flags : 0;
+    return relayout(c);
+}
+int gat_head_hidden_info(gat_ctx* c, int32_t* width, int32_t* flags) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (width) *width = c->hid.width;
+    if (flags) *flags = c->hid.flags;
+    return 0;
+}
 // ---- graph-level readout ------------------------------------------------------------------------------------------
 static int set_readout_common(gat_ctx* c, int32_t mode, const int32_t* graph_ptr, int64_t n_graphs, bool on_host) {
     if (!c) return fail(GAT_E_INVALID, "null context");

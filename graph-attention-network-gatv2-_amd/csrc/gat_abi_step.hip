@@ -35,6 +35,12 @@ static void head_args(gat_ctx* c, HeadArgs* f, HeadBwdArgs* b) {
         f->HL = b->HL = c->pairs.Q; f->n_rows = b->n_rows = c->pairs.n_pairs;
         b->g = nullptr; b->hpre = nullptr; b->gh_out = c->pairs.gQ; b->gh_stride = y.D;
     }
+    if (hidden_on(c)) {
+        // the head on Z1 = act(Xin W1^T + b1), rows of Dh floats (Wo is [C][Dh]), its gradient into gZ1; the hidden stage's backward
+        // fills the buffer the head's gradient went to before (gH, gP or gQ), so the head never writes a g of its own here either
+        f->HL = b->HL = c->hid.Z1; f->DL = b->DL = c->hid.width;
+        b->g = nullptr; b->hpre = nullptr; b->gh_out = c->hid.gZ1; b->gh_stride = c->hid.width;
+    }
 }
 LossHeadArgs loss_head_args(gat_ctx* c) {
     HeadArgs f{}; HeadBwdArgs b{};
@@ -60,7 +66,7 @@ static bool fused_head(gat_ctx* c) {
 // a row's sources comes a few microseconds after the first.
 bool fused_last(gat_ctx* c) {
     if (c->sup.loss_mode != 0) return false;            // the BCE / MSE head runs the separate passes
-    if (!fused_head(c) || bf16(c) || c->xch.comm || c->graph.n_table != c->graph.n_rows || c->cfg.flat_lrelu_index || res_route(c) || edge_feat_on(c) || readout_on(c) || pairs_on(c)) return false;   // no residual / norm / edge-feature / readout / pair form
+    if (!fused_head(c) || bf16(c) || c->xch.comm || c->graph.n_table != c->graph.n_rows || c->cfg.flat_lrelu_index || res_route(c) || edge_feat_on(c) || readout_on(c) || pairs_on(c) || hidden_on(c)) return false;   // no residual / norm / edge-feature / readout / pair / hidden-head form
     const Layer& y = c->layers.back();
     if (!edge_fast_path(y.H, y.D, c->graph.n_table) || !y.stash || c->bwd.stash == nullptr || c->bwd.gH == nullptr) return false;
     if (!edge_last_fused_supported(y.H, y.D, c->cfg.num_classes) || c->dbg != 0 || drop_on(c)) return false;   // no dropout form
@@ -174,12 +180,36 @@ static int pair_scatter(gat_ctx* c) {
     Scope t(c, GAT_K_HEAD_BWD);
     return launch_pair_backward(a, c->stream);
 }
+// Hidden layer (gatv2_abi.h "hidden layer"): Z1 = act(Xin W1^T + b1) in front of the head, and behind it gA from gZ1 in place, gradb1,
+// gradW1 and gXin = gA W1 into the buffer the head's gradient goes to without the feature (both no-ops with it off).  Xin: the rows the
+// head reads without it.  Plain launches on the context's stream: capturable, no host synchronisation.
+static const float* hidden_input(gat_ctx* c) { return pairs_on(c) ? c->pairs.Q : readout_on(c) ? c->readout.P : c->layers.back().hout; }
+static int hidden_forward(gat_ctx* c) {
+    if (!hidden_on(c)) return 0;
+    const int32_t DL = c->layers.back().D, Dh = c->hid.width;
+    Scope t(c, GAT_K_HEAD_FWD);
+    GAT_TRY(launch_project_res(hidden_input(c), W1_of(c), c->hid.Z1, head_rows(c), DL, Dh, c->stream, DL));
+    return launch_head_hidden_forward(c->hid.Z1, b1_of(c), head_rows(c), Dh, hidden_slope(c), c->stream);
+}
+static int hidden_backward(gat_ctx* c) {
+    if (!hidden_on(c)) return 0;
+    const int32_t DL = c->layers.back().D, Dh = c->hid.width;
+    const int64_t R = head_rows(c);
+    float* gxin = pairs_on(c) ? c->pairs.gQ : readout_on(c) ? c->readout.gP : c->bwd.gH;      // (a node head's gH: rows of D_last floats here)
+    Scope t(c, GAT_K_HEAD_BWD);
+    GAT_TRY(launch_head_hidden_backward(c->hid.gZ1, c->hid.Z1, c->hid.partial, R, Dh, hidden_slope(c), c->stream));
+    GAT_TRY(launch_reduce_partials_add(c->hid.partial, head_hidden_blocks(R, Dh), Dh, gb1_of(c), c->stream));
+    GAT_TRY(launch_grad_wres(c->hid.gZ1, hidden_input(c), gW1_of(c), c->hid.gw_scratch, R, DL, Dh, c->stream, DL));
+    GAT_HIP(hipMemsetAsync(gxin, 0, (size_t)R * DL * sizeof(float), c->stream));          // the launcher below adds into its output
+    return launch_grad_x_res(c->hid.gZ1, W1_of(c), gxin, R, DL, Dh, c->stream);
+}
 int gat_head_forward(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
     GAT_TRY(check_layer(c, 0));
     HeadArgs a{}; HeadBwdArgs unused{};
     head_args(c, &a, &unused);
     GAT_TRY(readout_pool(c));
     GAT_TRY(pair_gather(c));
+    GAT_TRY(hidden_forward(c));
     {
         Scope t(c, GAT_K_HEAD_FWD);
         if (c->sup.loss_mode != 0) GAT_TRY(launch_loss_head_forward(loss_head_args(c), c->stream));
@@ -206,6 +236,7 @@ int gat_head_backward(gat_ctx* c) {
         if (c->sup.loss_mode != 0) GAT_TRY(launch_loss_head_grad(loss_head_args(c), false, c->stream));
         else GAT_TRY(launch_head_backward(a, c->stream));
     }
+    GAT_TRY(hidden_backward(c));
     GAT_TRY(readout_unpool(c));
     return pair_scatter(c);
 }
@@ -437,12 +468,14 @@ static int head_step(gat_ctx* c, bool with_gh = true) {
     if (!with_gh) b.gh_out = nullptr;               // loss, #correct and grad_Wo only (the fused last layer formed gH itself)
     GAT_TRY(readout_pool(c));
     GAT_TRY(pair_gather(c));
+    GAT_TRY(hidden_forward(c));
     {
         Scope t(c, GAT_K_HEAD_BWD);
         c->head.y_valid = false; c->head.ran = true;
         if (c->sup.loss_mode != 0) GAT_TRY(launch_loss_head_grad(loss_head_args(c), true, c->stream));
         else GAT_TRY(launch_head_step(f, b, c->stream));
     }
+    GAT_TRY(hidden_backward(c));
     GAT_TRY(readout_unpool(c));
     return pair_scatter(c);
 }
@@ -731,6 +764,7 @@ static int check_comm_target(gat_ctx* c, int32_t world, int32_t rank) {
     if (!c->graph.have) return fail(GAT_E_STATE, "gat_comm_init: set the graph first");
     if (readout_on(c)) return fail(GAT_E_UNSUPPORTED, "gat_comm_init: not on a readout context (a graph may straddle shards)");
     if (pairs_on(c)) return fail(GAT_E_UNSUPPORTED, "gat_comm_init: not on a context with a pair head (an endpoint may live on another shard)");
+    if (hidden_on(c)) return fail(GAT_E_UNSUPPORTED, "gat_comm_init: not on a context with a hidden head layer (gat_set_head_hidden has no sharded form)");
     if (world < 1 || rank < 0 || rank >= world) return fail(GAT_E_INVALID, "gat_comm_init: bad world / rank");
     if (c->graph.n_table % world != 0 || c->graph.table_row0 != (int64_t)rank * (c->graph.n_table / world) || c->graph.n_rows > c->graph.n_table / world)
         return fail(GAT_E_INVALID, "gat_comm_init: the source table must be [world][max_rows] with this shard's rows at rank*max_rows");

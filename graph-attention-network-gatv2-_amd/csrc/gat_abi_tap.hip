@@ -68,6 +68,11 @@ int gat_tap(gat_ctx* c, int tensor, int32_t l, void* host, int64_t count) {
             if (!last) return fail(GAT_E_INVALID, "gat_tap: GAT_TAP_PAIRED exists for the last layer only");
             GAT_TRY(need(c->pairs.n_pairs * y.D));
             return d2h(c, host, c->pairs.Q, c->pairs.n_pairs * y.D * sizeof(float));
+        case GAT_TAP_HEAD_HIDDEN:                     // Z1 of the last head forward (or head step): what the head reads
+            if (!hidden_on(c)) return fail(GAT_E_STATE, "gat_tap: GAT_TAP_HEAD_HIDDEN needs gat_set_head_hidden");
+            if (!last) return fail(GAT_E_INVALID, "gat_tap: GAT_TAP_HEAD_HIDDEN exists for the last layer only");
+            GAT_TRY(need(head_rows(c) * c->hid.width));
+            return d2h(c, host, c->hid.Z1, head_rows(c) * c->hid.width * sizeof(float));
         case GAT_TAP_G: {
             GAT_TRY(need(N * y.HD));
             if (norm_layer(c, l)) {                     // dL/dh_pre through the normalisation: the backward kernel's row function again, on the

@@ -36,7 +36,7 @@ struct Pending { int k; hipEvent_t e0, e1; };
 
 }  // namespace gat
 
-constexpr int kParamGroups = GAT_PARAM_WE + 1;   // GAT_PARAM_* are 0 .. 7, in packed order
+constexpr int kParamGroups = GAT_PARAM_HEAD_B + 1;   // GAT_PARAM_* are 0 .. 9, in packed order
 struct gat_ctx {
     gat_config cfg{};
     std::vector<int32_t> heads, outdims;
@@ -77,9 +77,9 @@ struct gat_ctx {
         float* targets = nullptr; unsigned long long* tgt_scratch = nullptr;
         double* eval_loss = nullptr; int32_t* eval_cnt = nullptr;      // block partials of gat_eval_mask
     } sup;
-    // The packed parameters [W | a | Wo | Wres | b | gamma | beta | We] and their gradients (+ 4 floats of tail: [loss, correct lo,
+    // The packed parameters [W | a | Wo | Wres | b | gamma | beta | We | W1 | b1] and their gradients (+ 4 floats of tail: [loss, correct lo,
     // correct hi, -]).  group_cnt / group_off by GAT_PARAM_* (layout_params): floats in each group — Wres / b are empty unless
-    // gat_set_residual, gamma / beta unless gat_set_norm, We unless gat_set_edge_dim switched them on — and the group's first float.
+    // gat_set_residual, gamma / beta unless gat_set_norm, We unless gat_set_edge_dim, W1 / b1 unless gat_set_head_hidden switched them on — and the group's first float.
     // touched: a gat_params_* / gat_grads_* / gat_set_graph* call was made, the buffers keep their size.
     struct Packed {
         int64_t group_cnt[kParamGroups] = {0}, group_off[kParamGroups] = {0};
@@ -151,6 +151,13 @@ struct gat_ctx {
         float* loss_out = nullptr; int32_t* correct_out = nullptr;
         float* y = nullptr; bool y_valid = false, ran = false;
     } head;
+    // Hidden layer in front of the head (gatv2_abi.h "hidden layer"): width Dh (0: off) and the activation flags; Z1 [R][Dh] = act(Xin W1^T
+    // + b1), what the head reads; gZ1 [R][Dh] the head's input gradient, turned into gA in place; partial [head_hidden_blocks][Dh] block
+    // column sums of gA (gradb1); gw_scratch the slabs of gradW1.  Allocated by ensure_buffers for R = head_rows.
+    struct HeadHidden {
+        int32_t width = 0, flags = 0;
+        float* Z1 = nullptr; float* gZ1 = nullptr; float* partial = nullptr; float* gw_scratch = nullptr;
+    } hid;
     // Ranking metrics (gatv2_abi.h "ranking metrics"): the buffers of gat_eval_rank, allocated at its first call for head rows x C slots
     // and kept (sizes: what they were allocated for).
     struct Rank {
@@ -300,6 +307,21 @@ inline bool res_route(const gat_ctx* c) { return res_on(c) || norm_on(c); }
 inline bool edge_feat_on(const gat_ctx* c) { return c->ef.dim > 0; }
 inline bool readout_on(const gat_ctx* c) { return c->readout.mode != GAT_READOUT_NONE; }
 inline bool pairs_on(const gat_ctx* c) { return c->pairs.mode != GAT_PAIR_NONE; }
+inline bool hidden_on(const gat_ctx* c) { return c->hid.width > 0; }
+// width of the rows the output head reads (columns of Wo): Dh with a hidden layer in front of it, else D_last
+inline int32_t head_width(const gat_ctx* c) { return hidden_on(c) ? c->hid.width : c->layers.back().D; }
+// the hidden stage's activation as a slope: 0 = ReLU
+inline float hidden_slope(const gat_ctx* c) { return (c->hid.flags & GAT_HEAD_ACT_LRELU) ? c->cfg.negative_slope : 0.f; }
+// a hidden-head context takes no destination-range shard (asked by the calls that set the graph: the feature is switched on before them)
+inline int hidden_refuse_shard(const gat_ctx* c, int64_t n_rows, int64_t n_table) {
+    if (hidden_on(c) && n_table != n_rows)
+        return fail(GAT_E_UNSUPPORTED, "gat_set_head_hidden: not on a destination-range shard (n_table != n_rows) or with a transport (the head's rows may straddle shards)");
+    return 0;
+}
+inline float* W1_of(gat_ctx* c) { return c->packed.params + c->packed.group_off[GAT_PARAM_HEAD_W]; }
+inline float* b1_of(gat_ctx* c) { return c->packed.params + c->packed.group_off[GAT_PARAM_HEAD_B]; }
+inline float* gW1_of(gat_ctx* c) { return c->packed.grads + c->packed.group_off[GAT_PARAM_HEAD_W]; }
+inline float* gb1_of(gat_ctx* c) { return c->packed.grads + c->packed.group_off[GAT_PARAM_HEAD_B]; }
 // rows of the output head, hence of the labels, the targets, the masks and y: the pairs of a pair head, the graphs with readout on, else
 // the nodes (the two features exclude each other)
 inline int64_t head_rows(const gat_ctx* c) { return pairs_on(c) ? c->pairs.n_pairs : readout_on(c) ? c->readout.n_graphs : c->graph.n_rows; }
@@ -356,7 +378,7 @@ inline float* gPR_of(gat_ctx* c, int l) { return (c->ov.active && (l & 1)) ? c->
 #else
 #define GAT_REFUSE_DBG(c, applies, who, tail) do {} while (0)
 #endif
-// The setters that change the packed layout (gat_set_residual / gat_set_norm / gat_set_edge_dim) open with this refusal, make their own
+// The setters that change the packed layout (gat_set_residual / gat_set_norm / gat_set_edge_dim / gat_set_head_hidden) open with this refusal, make their own
 // checks, set their fields and end with relayout().
 #define GAT_LAYOUT_OPEN(c, who)                                                                                                  \
     do { if ((c)->packed.touched) return ::gat::fail(GAT_E_STATE, who ": call it before the first gat_params_*, gat_grads_* or " \
@@ -369,6 +391,7 @@ int ensure_drop_buffers(gat_ctx* c);      // gat_abi.hip: feature-dropout copies
 int ensure_buffers(gat_ctx* c);           // gat_abi.hip: everything sized by the graph, once graph, features and labels / targets are all set
 void graph_drop(gat_ctx* c);              // gat_abi_step.hip: forgets a captured step (it holds pointers and a kernel sequence); the next one runs eagerly
 LossHeadArgs loss_head_args(gat_ctx* c);  // gat_abi_step.hip: the BCE / MSE head's arguments: rows, outputs and partial buffers of the softmax head's
+int head_hidden_check(gat_ctx* c);        // gat_abi_features.hip: the head's shape limits at the hidden width and the shard refusal, once the graph (and the loss mode) are known
 bool fused_last(gat_ctx* c);              // gat_abi_step.hip: gat_step runs the last layer's edge passes and the head's gradient as one kernel (GAT_FUSE_LAST=1)
 
 }  // namespace gat

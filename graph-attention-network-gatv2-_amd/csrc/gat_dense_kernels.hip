@@ -1453,6 +1453,21 @@ int launch_loss_head_grad(const LossHeadArgs& a, bool fused, hipStream_t s) {
 #undef GAT_LOSS_FWD
 #undef GAT_LOSS_LAUNCH
 
+// The limits the head's launchers above apply to (C, DL), asked without a launch (the hidden layer's width is checked with it)
+int head_shape_check(int32_t C, int32_t DL, int32_t mode, std::string* limit) {
+    if ((int64_t)C * DL > 2048) { *limit = "num_classes * width <= 2048"; return GAT_E_UNSUPPORTED; }
+    int32_t NB, ldz, ldx, ws, dlt;
+    bool fits;
+    if (mode != 0) fits = loss_head_tile(C, DL, &NB, &ldz, &ldx, &ws, &dlt);
+    else {
+        const int dlp = DL <= 8 ? 8 : (DL <= 16 ? 16 : (DL <= 32 ? 32 : (DL <= 64 ? 64 : DL)));
+        const bool blocked = C <= 64 && (DL == 4 || DL == 8 || DL == 16);
+        fits = head_tile(C, dlp, 0, &NB, &ldz) == 0 && (blocked || head_tile(C, DL, 2 * DL, &NB, &ldz) == 0);
+    }
+    if (!fits) { *limit = "the head's LDS tile (Wo and its row tile in 60 KiB)"; return GAT_E_UNSUPPORTED; }
+    return 0;
+}
+
 int64_t targets_check_host(const float* t, int64_t n, int32_t mode) {
     for (int64_t i = 0; i < n; ++i) {
         const float v = t[i];

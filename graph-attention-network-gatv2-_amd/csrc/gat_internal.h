@@ -673,6 +673,21 @@ int pair_plan_temp_bytes(int64_t n_rows, size_t* bytes);
 int pair_plan_device(const int32_t* d_inc_ptr, int64_t n_rows, unsigned long long* d_key, unsigned long long* d_off, void* d_temp,
                      size_t temp_bytes, int4* d_items, int4* d_split, int64_t* n_items, int32_t* n_split, int32_t* n_parts, hipStream_t s);
 
+// ---- hidden layer in front of the output head (gat_head_hidden.hip; the contract is in gatv2_abi.h "hidden layer") ------------------
+// The two row-streaming kernels around the stage's three products (which run on launch_project_res / launch_grad_wres /
+// launch_grad_x_res with rows = R, F = D_last, HD = Dh).  slope = 0: ReLU.
+// a[r][j] = act(a[r][j] + b1[j]) in place, act(t) = t > 0 ? t : slope * t
+int launch_head_hidden_forward(float* a, const float* b1, int64_t rows, int32_t width, float slope, hipStream_t s);
+// gz[r][j] *= z1[r][j] > 0 ? 1 : slope in place; partial [blocks][width] (or null: not formed) receives the column sums of the rows each
+// block walked, rows in ascending order — blocks = head_hidden_blocks(rows, width) <= kHiddenPartialRows, a function of the shape alone;
+// finished by launch_reduce_partials_add
+constexpr int kHiddenPartialRows = 1024;
+int head_hidden_blocks(int64_t rows, int32_t width);
+int launch_head_hidden_backward(float* gz, const float* z1, float* partial, int64_t rows, int32_t width, float slope, hipStream_t s);
+// The output head's own shape limits for rows of DL floats and C columns under loss mode `mode` (the checks its launchers make, without
+// a launch): 0, or GAT_E_UNSUPPORTED with *limit naming the limit that is broken
+int head_shape_check(int32_t C, int32_t DL, int32_t mode, std::string* limit);
+
 // ---- negative sampling (gat_negsample.hip; the contract — the sampling law — is in gatv2_abi.h "negative sampling") ---------------
 // *ascending = every row of the CSR has its sources in non-decreasing order (one pass, synchronises s): the sampler's membership test
 // is then a binary search, else a linear scan of the row — the drawn pairs are the same either way.

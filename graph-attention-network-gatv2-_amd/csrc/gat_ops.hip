@@ -829,4 +829,38 @@ int gat_op_rank_stats(const float* d_scores, int64_t score_stride, const int32_t
     return rc;
 }
 
+// ---- hidden layer in front of the head (gatv2_abi.h "hidden layer"): the two row-streaming kernels on caller-owned device pointers -----
+static int op_hidden_check(const char* who, int64_t rows, int32_t width, float slope) {
+    if (rows < 0 || width < 1) return fail(GAT_E_INVALID, std::string(who) + ": bad sizes (rows >= 0, width >= 1)");
+    if (!(slope >= 0.f && slope <= 1.f)) return fail(GAT_E_INVALID, std::string(who) + ": slope must be in [0, 1] (0 = ReLU)");
+    return 0;
+}
+int gat_op_head_hidden_forward(float* d_a, const float* d_b1, int64_t rows, int32_t width, float slope, void* stream) {
+    static const char* who = "gat_op_head_hidden_forward";
+    GAT_TRY(op_hidden_check(who, rows, width, slope));
+    if (rows == 0) return 0;
+    if (!d_a || !d_b1) return fail(GAT_E_INVALID, std::string(who) + ": null argument");
+    hipStream_t s = (hipStream_t)stream;
+    int rc = launch_head_hidden_forward(d_a, d_b1, rows, width, slope, s);
+    const hipError_t e = hipStreamSynchronize(s);
+    if (rc == 0 && e != hipSuccess) rc = fail((int)e, std::string(who) + ": " + hipGetErrorString(e));
+    return rc;
+}
+int gat_op_head_hidden_backward(float* d_gz, const float* d_z1, int64_t rows, int32_t width, float slope, float* d_grad_b1, void* stream) {
+    static const char* who = "gat_op_head_hidden_backward";
+    GAT_TRY(op_hidden_check(who, rows, width, slope));
+    if (rows == 0) return 0;
+    if (!d_gz || !d_z1) return fail(GAT_E_INVALID, std::string(who) + ": null argument");
+    hipStream_t s = (hipStream_t)stream;
+    Scratch tmp;
+    float* partial = nullptr;
+    const int blocks = head_hidden_blocks(rows, width);
+    if (d_grad_b1) GAT_TRY(tmp.get(&partial, (int64_t)blocks * width));
+    int rc = launch_head_hidden_backward(d_gz, d_z1, partial, rows, width, slope, s);
+    if (rc == 0 && d_grad_b1) rc = launch_reduce_partials_add(partial, blocks, width, d_grad_b1, s);
+    const hipError_t e = hipStreamSynchronize(s);        // before the scratch is freed
+    if (rc == 0 && e != hipSuccess) rc = fail((int)e, std::string(who) + ": " + hipGetErrorString(e));
+    return rc;
+}
+
 }  // extern "C"

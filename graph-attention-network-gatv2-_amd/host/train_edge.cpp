@@ -43,6 +43,10 @@
 // "u v" per line (not necessarily an edge), labels.txt / targets.txt, --train-mask and --val-mask files hold one line per pair.  The output
 // head reads X[u]*X[v] / X[u]+X[v] of the last layer's rows; the epoch lines keep their format, loss and accuracy are over pairs.  One rank
 // only (an endpoint may live on another shard), not with --readout; --cache is not used.
+// --head-hidden K [--head-act relu|lrelu]: one hidden layer of K units in front of the output head (gatv2_abi.h "hidden layer"), for every
+// head kind: Z1 = act(Xin W1^T + b1), the head reads Z1 and Wo becomes [C][K]; act is ReLU, or LeakyReLU with the model's slope.  W1 is
+// Xavier-initialised from --seed after every other parameter, b1 starts at 0, and --dump-params / --load-params carry W1 and b1 behind We,
+// only with the flag (files written without it keep their format).  One rank only: refused with --ranks > 1 before any GPU call.
 // --rank-metrics K1,K2,... (with --val-mask, --ranks 1, not --loss mse): one more line behind every validation line — ROC-AUC, average
 // precision, MRR and Hits@K of the validation rows (gatv2_abi.h "ranking metrics"), macro-averaged over the output columns that have both
 // classes, then the count of those columns.  Every other line is printed as without the flag.
@@ -110,6 +114,7 @@ struct Options {
     std::string neg_sampling;             // --neg-sampling uniform|corrupt: lines --neg-first .. of pairs.txt are redrawn before every epoch
     long long neg_first = -1; uint64_t neg_seed = 0; int neg_flags = 0;      // --neg-first K, --neg-seed S, GAT_NEG_*: --neg-both-directions, --neg-allow-self
     std::string loss = "softmax";         // --loss softmax|bce|mse: bce / mse read targets.txt (rows of C floats, nan allowed) in place of labels.txt
+    int head_hidden = 0; int head_act = 0;   // --head-hidden K, --head-act relu|lrelu (GAT_HEAD_ACT_*): a hidden layer in front of the output head
     std::vector<int32_t> rank_ks; bool rank_metrics = false;      // --rank-metrics K1,K2,...: a ranking line behind every validation line
 };
 
@@ -152,6 +157,9 @@ const char* kUsage =
     "                          (regression) read targets.txt in place of labels.txt: one row of C floats per node — per graph with\n"
     "                          --readout — where nan marks a missing entry; C is the row width.  The epoch line prints the loss sum over\n"
     "                          the present entries of the training rows, and for bce the accuracy over those entries\n"
+    "            --head-hidden K [--head-act relu|lrelu]   one hidden layer of K units in front of the output head (an MLP predictor, for\n"
+    "                          node, --readout and --pairs heads alike): Z1 = act(Xin W1^T + b1), act = ReLU (default) or LeakyReLU with the\n"
+    "                          model's slope; W1 and b1 follow We in --dump-params / --load-params, only with the flag (--ranks 1)\n"
     "            --rank-metrics K1,K2,...   with --val-mask: behind every validation line one line \"Val AUC: .., AP: .., MRR: .., Hits@K1: ..\n"
     "                          (n columns)\" — ROC-AUC, average precision, MRR (every positive against all negatives) and Hits@K of the\n"
     "                          validation rows, ranked on the device, macro-averaged over the n output columns that have both classes\n"
@@ -250,6 +258,8 @@ Options parse_args(int argc, char** argv) {
         else if (a == "--neg-both-directions") o.neg_flags |= GAT_NEG_BOTH_DIRECTIONS;
         else if (a == "--neg-allow-self") o.neg_flags |= GAT_NEG_ALLOW_SELF;
         else if (a == "--loss" && has_val) o.loss = argv[++i];
+        else if (a == "--head-hidden" && has_val) o.head_hidden = std::atoi(argv[++i]);       // (checked in main, before anything touches the GPU)
+        else if (a == "--head-act" && has_val) o.head_act = std::string(argv[++i]) == "lrelu" ? GAT_HEAD_ACT_LRELU : 0;
         else if (a == "--rank-metrics" && has_val) {          // (checked in main, before anything touches the GPU)
             o.rank_metrics = true;
             for (const char* p = argv[++i]; *p;) {
@@ -598,7 +608,9 @@ int run(const Options& o, const RankEnv& env) {
     if (o.norm_flags) check(gat_set_norm(ctx, o.norm_flags, o.norm_eps), "gat_set_norm");
     if (o.edge_features) check(gat_set_edge_dim(ctx, Fe), "gat_set_edge_dim");
     if (loss_mode != GAT_LOSS_SOFTMAX_CE) check(gat_set_loss(ctx, loss_mode), "gat_set_loss");
-    int64_t nW = 0, nA = 0, nWo = 0, nWres = 0, nB = 0, nLnG = 0, nLnB = 0, nWe = 0;
+    if (o.head_hidden > 0) check(gat_set_head_hidden(ctx, o.head_hidden, o.head_act), "gat_set_head_hidden");
+    int64_t nW = 0, nA = 0, nWo = 0, nWres = 0, nB = 0, nLnG = 0, nLnB = 0, nWe = 0, nW1 = 0, nB1 = 0;
+    gat_param_count(ctx, GAT_PARAM_HEAD_W, &nW1); gat_param_count(ctx, GAT_PARAM_HEAD_B, &nB1);   // 0 without --head-hidden
     gat_param_count(ctx, GAT_PARAM_WE, &nWe);                                                 // 0 without --edge-features
     gat_param_count(ctx, GAT_PARAM_W, &nW); gat_param_count(ctx, GAT_PARAM_A, &nA); gat_param_count(ctx, GAT_PARAM_WO, &nWo);
     gat_param_count(ctx, GAT_PARAM_WRES, &nWres); gat_param_count(ctx, GAT_PARAM_B, &nB);     // 0 without the flags
@@ -640,7 +652,7 @@ int run(const Options& o, const RankEnv& env) {
         } else {
             int64_t hd_max = 0;
             for (int l = 0; l < L; ++l) hd_max = std::max<int64_t>(hd_max, (int64_t)o.heads[l] * o.outdims[l]);
-            const int64_t bytes = std::max<int64_t>(plan.n_table() * hd_max + 64, nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe + 3) * (int64_t)sizeof(float);   // (+ 64: block offsets of a halo exchange)
+            const int64_t bytes = std::max<int64_t>(plan.n_table() * hd_max + 64, nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe + nW1 + nB1 + 3) * (int64_t)sizeof(float);   // (+ 64: block offsets of a halo exchange)
             check(gat_comm_init_host(ctx, env.world, env.rank, env.shm_name.c_str(), bytes), "gat_comm_init_host");
         }
         if (o.halo != 0) check(gat_comm_option(ctx, GAT_COMM_HALO, o.halo), "gat_comm_option(GAT_COMM_HALO)");      // collective: every rank
@@ -725,7 +737,7 @@ int run(const Options& o, const RankEnv& env) {
     if (o.drop_edge > 0.f) check(gat_set_dropedge(ctx, o.drop_edge, o.drop_edge_flags), "gat_set_dropedge");
     check(gat_params_init(ctx, o.seed), "xavier_init_kernel");
     if (!o.load_params.empty()) {
-        std::vector<float> p(nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe);    // the residual, norm and edge-feature groups follow the others, only with their flags
+        std::vector<float> p(nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe + nW1 + nB1);    // the residual, norm, edge-feature and hidden-head groups follow the others, only with their flags
         std::ifstream f(o.load_params, std::ios::binary);
         if (!f.read(reinterpret_cast<char*>(p.data()), p.size() * sizeof(float))) die("Error: cannot read --load-params file\n");
         check(gat_params_set(ctx, GAT_PARAM_W, p.data(), nW), "gat_params_set");
@@ -736,6 +748,8 @@ int run(const Options& o, const RankEnv& env) {
         if (nLnG) check(gat_params_set(ctx, GAT_PARAM_LN_G, p.data() + nW + nA + nWo + nWres + nB, nLnG), "gat_params_set");
         if (nLnB) check(gat_params_set(ctx, GAT_PARAM_LN_B, p.data() + nW + nA + nWo + nWres + nB + nLnG, nLnB), "gat_params_set");
         if (nWe) check(gat_params_set(ctx, GAT_PARAM_WE, p.data() + nW + nA + nWo + nWres + nB + nLnG + nLnB, nWe), "gat_params_set");
+        if (nW1) check(gat_params_set(ctx, GAT_PARAM_HEAD_W, p.data() + nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe, nW1), "gat_params_set");
+        if (nB1) check(gat_params_set(ctx, GAT_PARAM_HEAD_B, p.data() + nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe + nW1, nB1), "gat_params_set");
     }
 
     size_t free_after = 0;
@@ -793,7 +807,7 @@ int run(const Options& o, const RankEnv& env) {
     }
 
     if (!o.dump_params.empty() && env.rank == 0) {
-        std::vector<float> p(nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe);    // without --residual / --bias / --layer-norm / --edge-features: the format of always
+        std::vector<float> p(nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe + nW1 + nB1);    // without --residual / --bias / --layer-norm / --edge-features / --head-hidden: the format of always
         check(gat_params_get(ctx, GAT_PARAM_W, p.data(), nW), "gat_params_get");
         check(gat_params_get(ctx, GAT_PARAM_A, p.data() + nW, nA), "gat_params_get");
         check(gat_params_get(ctx, GAT_PARAM_WO, p.data() + nW + nA, nWo), "gat_params_get");
@@ -802,6 +816,8 @@ int run(const Options& o, const RankEnv& env) {
         if (nLnG) check(gat_params_get(ctx, GAT_PARAM_LN_G, p.data() + nW + nA + nWo + nWres + nB, nLnG), "gat_params_get");
         if (nLnB) check(gat_params_get(ctx, GAT_PARAM_LN_B, p.data() + nW + nA + nWo + nWres + nB + nLnG, nLnB), "gat_params_get");
         if (nWe) check(gat_params_get(ctx, GAT_PARAM_WE, p.data() + nW + nA + nWo + nWres + nB + nLnG + nLnB, nWe), "gat_params_get");
+        if (nW1) check(gat_params_get(ctx, GAT_PARAM_HEAD_W, p.data() + nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe, nW1), "gat_params_get");
+        if (nB1) check(gat_params_get(ctx, GAT_PARAM_HEAD_B, p.data() + nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe + nW1, nB1), "gat_params_get");
         std::ofstream f(o.dump_params, std::ios::binary);
         f.write(reinterpret_cast<const char*>(p.data()), p.size() * sizeof(float));
     }
@@ -827,7 +843,7 @@ int main(int argc, char** argv) {
     // anything touches the GPU
     bool graph_flag = false, edge_feat_flag = false, readout_flag = false, targets_flag = false, pairs_flag = false;
     bool neg_flag = false, neg_corrupt = false; long long neg_first = -1;
-    bool rank_flag = false, val_flag = false, mse_flag = false;
+    bool rank_flag = false, val_flag = false, mse_flag = false, hidden_flag = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--help") { std::cout << kUsage; return 0; }
@@ -867,6 +883,17 @@ int main(int argc, char** argv) {
         }
         if (a == "--add-self-loops" || a == "--undirected" || a == "--coalesce") graph_flag = true;
         if (a == "--edge-features") edge_feat_flag = true;
+        if (a == "--head-hidden") {                        // a positive integer, nothing else
+            const char* v = i + 1 < argc ? argv[i + 1] : "";
+            char* end = nullptr;
+            const long k = std::strtol(v, &end, 10);
+            if (end == v || *end != '\0' || k < 1 || k > 2147483647L) die("Error: --head-hidden must be an integer K >= 1 (the hidden layer's width)\n");
+            hidden_flag = true;
+        }
+        if (a == "--head-act") {
+            const std::string v = i + 1 < argc ? argv[i + 1] : "";
+            if (v != "relu" && v != "lrelu") die("Error: --head-act must be relu or lrelu\n");
+        }
         if (a == "--loss") {
             const std::string v = i + 1 < argc ? argv[i + 1] : "";
             if (v != "softmax" && v != "bce" && v != "mse") die("Error: --loss must be softmax, bce or mse\n");
@@ -887,6 +914,8 @@ int main(int argc, char** argv) {
         die("Error: --readout needs --ranks 1: a graph of the batch may straddle two destination-range shards\n");
     if (pairs_flag && multi)
         die("Error: --pairs needs --ranks 1: an endpoint of a pair may live on another destination-range shard\n");
+    if (hidden_flag && multi)
+        die("Error: --head-hidden needs --ranks 1: the hidden layer in front of the output head has no sharded form\n");
     if (pairs_flag && readout_flag)
         die("Error: --pairs cannot be combined with --readout: the output head has one kind of row\n");
     if (neg_flag && !pairs_flag) die("Error: --neg-sampling needs --pairs: the negatives are lines of pairs.txt\n");

@@ -190,14 +190,16 @@ int gat_param_count(gat_ctx* ctx, int group, int64_t* count);
 /* U(-lim,lim], lim as E:208, 236.  With GAT_RES_LINEAR: Wres_l Xavier-uniform with lim = sqrt(6 / (F_l + H_l*D_l)), drawn from the same
  * counter stream AFTER all existing draws (layer by layer), so W, a and Wo of a seed are those of a context without it; b = 0.
  * With gat_set_norm: gamma = 1, beta = 0, no draws.  With gat_set_edge_dim: We_l Xavier-uniform with lim = sqrt(6 / (Fe + H_l*D_l)), drawn
- * after every other draw (after Wres), so all other groups of a seed are unchanged. */
+ * after every other draw (after Wres), so all other groups of a seed are unchanged.
+ * With gat_set_head_hidden(width > 0): Wo is drawn at its own place with its new shape [C][Dh], so the draws BEHIND it (Wres, We) shift on
+ * such a context — W and a of a seed stay what they are; W1 is drawn after every other draw, b1 = 0 (see "hidden layer" below). */
 int gat_params_init(gat_ctx* ctx, uint64_t seed);
 int gat_params_set(gat_ctx* ctx, int group, const float* host, int64_t count);
 int gat_params_get(gat_ctx* ctx, int group, float* host, int64_t count);
 int gat_grads_get(gat_ctx* ctx, int group, float* host, int64_t count);
 int gat_grads_set(gat_ctx* ctx, int group, const float* host, int64_t count);
 /* Device address of the packed gradient buffer [gradW | grada | gradWo | gradWres | gradb | gradgamma | gradbeta | gradWe] (for the all-reduce;
- * groups 3 and 4 only with gat_set_residual, 5 and 6 only with gat_set_norm, 7 only with gat_set_edge_dim).  count = n_params, the sum of the eight group counts; the three-float result tail of
+ * groups 3 and 4 only with gat_set_residual, 5 and 6 only with gat_set_norm, 7 only with gat_set_edge_dim).  count = n_params, the sum of the eight group counts (ten with gat_set_head_hidden: gradW1 | gradb1 behind gradWe); the three-float result tail of
  * gat_result_export sits behind it, and the host transport's bytes_per_rank rule stays (n_params + 3) * 4. */
 int gat_grads_device(gat_ctx* ctx, void** d_ptr, int64_t* count);
 /* Async D2D copies of the packed gradients on the context's stream, to / from a caller-owned
@@ -852,6 +854,65 @@ typedef struct gat_rank_stats {
 int gat_eval_rank(gat_ctx* ctx, const uint8_t* mask, int64_t n_rows, const int32_t* ks, int32_t n_ks, gat_rank_stats* out /* [num_classes] */);
 int gat_op_rank_stats(const float* d_scores, int64_t score_stride, const int32_t* d_labels, const float* d_targets, const uint8_t* d_mask,
                       int64_t n_rows, int32_t n_cols, const int32_t* ks, int32_t n_ks, gat_rank_stats* out /* host, [n_cols] */, void* stream);
+
+/* ---- hidden layer in front of the output head (beyond the reference, whose head is one linear map: the MLP predictor of the OGB link
+ * baselines and of PyG's MLP after global_*_pool) ----
+ * An optional hidden stage for every head kind.  With R the head's rows (n_rows, n_graphs or n_pairs) and Xin [R][D_last] the rows the head
+ * reads without it (the last layer's output, the pooled rows P, the pair rows Q):
+ *     A  = Xin W1^T              W1 [Dh][D_last], the three-bf16-piece product of the other dense terms (fp32-accurate)
+ *     Z1 = act(A + b1)           b1 [Dh];  act = ReLU, or with GAT_HEAD_ACT_LRELU LeakyReLU with the context's negative_slope
+ *     z  = Z1 Wo^T               the existing head, unchanged, with Dh where it had D_last: Wo becomes [C][Dh]
+ * Backward: gZ1 = the head's input gradient ([R][Dh]);  gA = gZ1 (.) (Z1 > 0 ? 1 : slope), slope = 0 for ReLU, Z1 == 0 takes the slope
+ * branch (torch's convention);  gradb1 += column sums of gA,  gradW1 += gA^T Xin,  gXin = gA W1.  gXin goes where the head's gradient
+ * went: the [n_rows][D_last] output gradient of a node head (the head then writes no g of its own, as with a readout), gP with a readout,
+ * gQ with a pair head; everything from there downward is the code of a context without the feature.  The sign of A is that of Z1 for both
+ * activations, so A is not kept.
+ * gat_set_head_hidden(ctx, width, flags): width == 0 is the default and leaves the context exactly as it is: same buffers, same kernels,
+ *   same launch counts, bitwise the same results (the flags are still checked).  width > 0 follows gat_set_residual's state rule: only
+ *   before the first gat_params_*, gat_grads_* or gat_set_graph* call, else GAT_E_STATE (the packed buffers and Wo change size).
+ *   width < 0 or unknown flag bits: GAT_E_INVALID.
+ * Parameters: GAT_PARAM_HEAD_W flat [Dh][D_last] and GAT_PARAM_HEAD_B flat [Dh], behind GAT_PARAM_WE in the packed parameter, gradient and
+ *   Adam buffers; their counts are 0 while the feature is off.  gat_zero_grad, gat_clip (one more norm per group), gat_step_sgd,
+ *   gat_step_adam and gat_grads_device / export / import cover them; count of gat_grads_device = the sum of the ten group counts.
+ *   gat_params_init: W and a of a seed are those of a context without the feature; Wo is drawn at its own place in the stream with its new
+ *   shape [C][Dh] and lim = sqrt(6 / (C + Dh)), so the draws behind it (Wres, We) SHIFT on a context with the feature; W1 is Xavier-uniform
+ *   with lim = sqrt(6 / (D_last + Dh)), drawn after every other draw; b1 = 0.
+ * Shape limits: the head's, with Dh in D_last's place — C * Dh <= 2048 and the LDS tile of the head's kernels.  A width outside them is
+ *   refused with GAT_E_UNSUPPORTED and a text naming the width and the limit, by gat_set_head_hidden itself where the limit does not depend
+ *   on the loss mode, else by the call that completes the context.  Dh in {4, 8, 16} selects the head's register-blocked / fused forms as
+ *   D_last does; every other width the any-shape forms.
+ * Where it runs.  The three products run on the dense launchers of the residual term with rows = R, F = D_last, HD = Dh; gXin's launcher adds
+ *   into its output, which is zeroed first (a memset node in a captured step).  Around them two row-streaming kernels: the forward writes
+ *   Z1 = act(A + b1) in place (float4 accesses when Dh is a multiple of 4, scalar otherwise, b1 in registers, a persistent grid); the
+ *   backward turns gZ1 into gA in place and leaves per-block column sums of gA in a fixed order, which the slab reduction adds into gradb1.
+ *   No float atomics: the result is a function of (R, Dh) and the data alone, bitwise the same in gat_step, gat_forward + gat_backward,
+ *   the phase API and a gat_step_graph replay.  The launches are part of gat_head_forward (after the pool or gather, before the head) and
+ *   gat_head_backward (after the head, before the un-pool or scatter): no host synchronisation, fixed addresses; timed under
+ *   GAT_K_HEAD_FWD / GAT_K_HEAD_BWD.  A replacing gat_set_pairs / gat_resample_negatives keeps every buffer.
+ * gat_eval_mask, gat_eval_rank and gat_tap(GAT_TAP_Y) run the head on Z1 of the last forward; GAT_TAP_HEAD_HIDDEN returns Z1 ([R][Dh], last
+ *   layer only, GAT_E_STATE without the feature).
+ * Works with every head kind, all three loss modes, every (H, D) family, bf16 storage (the stage stays fp32), keep_taps, the regularisers,
+ *   residual, bias, norm and edge features.
+ * Refused with GAT_E_UNSUPPORTED, as the readout and the pair head refuse them: a destination-range shard (n_table != n_rows) or a context
+ *   with a transport (at the call that sets such a graph; gat_comm_init_* on a hidden-head context alike); flat_lrelu_index = 1; the
+ *   experiment library with GAT_DBG set.  GAT_FUSE_LAST=1 is not used by such a context.
+ * Not there: more than one hidden layer, dropout on Z1, a bias on the output layer (a hidden unit with a zero W1 row and a positive b1
+ *   supplies the offset), shards.
+ * gat_algorithmic_bytes (context form): unchanged with the feature off.  On, the head classes are priced with Dh for D_last, and at 4 bytes
+ *   GAT_K_HEAD_FWD gains R D_last + Dh D_last + 3 R Dh (Xin, W1, A written, A read and Z1 written) and GAT_K_HEAD_BWD gains 3 R Dh (the
+ *   activation backward) + R Dh + R D_last + Dh D_last (gradW1) + R Dh + Dh D_last + R D_last (gXin). */
+enum { GAT_HEAD_ACT_LRELU = 1 };                       /* flags; 0 = ReLU */
+enum { GAT_PARAM_HEAD_W = 8, GAT_PARAM_HEAD_B = 9 };   /* [Dh][D_last], [Dh]: behind GAT_PARAM_WE; count 0 while off */
+enum { GAT_TAP_HEAD_HIDDEN = 20 };                     /* [R][Dh]  Z1 of the last forward */
+int gat_set_head_hidden(gat_ctx* ctx, int32_t width, int32_t flags);
+int gat_head_hidden_info(gat_ctx* ctx, int32_t* width, int32_t* flags);   /* (0, 0) while off; pointers may be NULL */
+/* The two row-streaming kernels as stateless seams on caller-owned DEVICE pointers (current device).  Forward: d_a [rows][width] becomes
+ * Z1 = act(d_a + d_b1) in place, slope = 0 for ReLU.  Backward: d_gz [rows][width] becomes gA = d_gz (.) (d_z1 > 0 ? 1 : slope) in place
+ * and the column sums of gA are ADDED into d_grad_b1 [width] (may be NULL: not formed).  rows == 0 launches nothing and succeeds.  rows < 0,
+ * width < 1, a slope outside [0, 1] or not finite, or a null pointer with rows > 0: GAT_E_INVALID, nothing is written.  The backward
+ * allocates and frees its block partials; both synchronise `stream` (may be NULL). */
+int gat_op_head_hidden_forward(float* d_a, const float* d_b1, int64_t rows, int32_t width, float slope, void* stream);
+int gat_op_head_hidden_backward(float* d_gz, const float* d_z1, int64_t rows, int32_t width, float slope, float* d_grad_b1, void* stream);
 
 /* ---- op-level entry points, whole layers: caller-provided DEVICE pointers in the reference layouts
  *      (unit parity).  `stream` may be NULL (default stream).  One entry point per reference KERNEL: below. ---- */
