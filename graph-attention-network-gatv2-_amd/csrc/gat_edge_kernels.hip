@@ -2302,7 +2302,9 @@ EdgePick pick_bwd(const EdgeBwdArgs& a, bool drop, int dbg, bool pe) {
         }
         // records; bf16 storage: always the group-per-row kernel (GAT_ROWGROUP=0 has no bf16 form)
         if (stash) return {(BF || row_groups()) ? GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF>) : GAT_K(edge_bwd2s_kernel<HD, D, N3>)};
-        if (msg_rows && row_groups() && group_msg()) {                            // message rows from the group-per-row kernel
+        // message rows from the group-per-row kernel.  Both switches are read, GAT_GROUP_MSG first: a process that sets both reports
+        // both in gat_switches() (either one at 0 gives the wave-per-row kernel)
+        if (const bool gm = group_msg(); msg_rows && row_groups() && gm) {
 #ifdef GAT_EXPERIMENTS      // GAT_DBG=1 on a message-row layer (BASELINE config 5): the walk without its message-row stores — WRONG RESULTS, timing / PMC
             if constexpr (HD == 32 && D == 8 && BF) {     // attribution only (DESIGN §4 "Round 4": how much of the backward's reads is fill for its 64-byte row writes)
                 if (dbg == 1) return {GAT_K(edge_bwd3_kernel<HD, D, N3, 1, true, true>)};
@@ -2336,21 +2338,23 @@ static EdgePick pick_backward(const EdgeBwdArgs& a, bool drop, int dbg, bool pe 
 
 // Blocks of `fn` (`block` threads, no dynamic LDS) that are resident on the whole chip at once, from the
 // occupancy API (cached per kernel).  The backward grid is exactly this size: its items are dealt
-// statically, so a second, partially filled round of blocks would be pure tail.
+// statically, so a second, partially filled round of blocks would be pure tail.  GAT_RESIDENT_CAP (resident_capped,
+// gat_internal.h) bounds the answer as it bounds the dense kernels': the cache holds the occupancy figure, the bound is applied
+// on the way out, so a wave of a small graph walks several items.  ga_blocks sizes the grid AND the ga_partial rows.
 static int resident_blocks(const void* fn, unsigned block) {
     static std::mutex mu;
     static std::map<std::pair<const void*, unsigned>, int> cache;
     std::lock_guard<std::mutex> lock(mu);
     const auto key = std::make_pair(fn, block);
     auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
+    if (it != cache.end()) return (int)resident_capped(it->second);
     int per_cu = 0, dev = 0, cus = 256;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, (int)block, 0) != hipSuccess || per_cu < 1) per_cu = 4;
     if (per_cu > 8) per_cu = 8;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     (void)hipGetLastError();
-    return cache[key] = per_cu * (cus > 0 ? cus : 256);
+    return (int)resident_capped(cache[key] = per_cu * (cus > 0 ? cus : 256));
 }
 
 // the split rows' partial sums -> their rows (after either forward kernel; the plain fix-up kernel reads the EdgeFwdArgs part of `a`)

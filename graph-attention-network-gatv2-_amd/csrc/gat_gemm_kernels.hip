@@ -132,7 +132,8 @@ constexpr int kKC = 128;          // K chunk resident in LDS
 // GAT_RESIDENT_CAP=<n> (tests): an upper bound on the answer, so that a graph of a few hundred rows walks several tiles per block and
 // cuts grad_w into few node chunks — the role GAT_SEG_EDGES=16 plays for the edge kernels.  Every caller sizes its grid AND its
 // partial buffers from this one function, so the bound can only make a launch smaller.  Unset: the occupancy figure as it is.
-static int64_t resident_capped(int64_t blocks) {
+// The persistent edge backward kernels (gat_edge_kernels.hip: edge_backward_blocks, edge_last_fused_blocks) take the same bound.
+int64_t resident_capped(int64_t blocks) {
     static const int64_t cap = [] { const char* e = choice_env("GAT_RESIDENT_CAP"); return e ? (int64_t)atoll(e) : (int64_t)0; }();
     if (cap > 0 && blocks > cap) blocks = cap;
     return blocks < 1 ? 1 : blocks;

@@ -445,6 +445,9 @@ int launch_reduce_gradw(const float* slabs, int32_t ksplit, int32_t HD, int32_t 
 // dynamic LDS; cached).  Persistent kernels use exactly this grid: a larger one runs a second,
 // partly filled round of blocks.
 int64_t resident_blocks(const void* fn, size_t dyn_lds, int threads = 256);
+// GAT_RESIDENT_CAP=<n> (tests) applied to a resident count: min(blocks, n), at least 1; unset: blocks.  Every persistent grid —
+// resident_blocks() above and the edge kernels' own count (gat_edge_kernels.hip) — answers through it.
+int64_t resident_capped(int64_t blocks);
 // The template name of the row / tile kernel the dense launchers below launched last on this host thread, e.g.
 // "rowgemm_x3_kernel<2, 8, true>" ("" after the clear: nothing launched) — the gat_op_dense_* seams report it.
 const char* dense_last_kernel();

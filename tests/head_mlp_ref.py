@@ -154,7 +154,7 @@ def case_id(case):
 
 
 @functools.lru_cache(maxsize=None)
-def _case_inputs(fam, variant, kind, loss, dh, act_name):
+def _case_inputs(fam, variant, kind, loss, dh, act_name, n_rand=None):
     import __graft_entry__ as entry
     import feature_cases as FC
     pkg, orc = entry.load_package(), entry.load_oracle()
@@ -165,7 +165,7 @@ def _case_inputs(fam, variant, kind, loss, dh, act_name):
     cfg = orc.Config(heads, outdims, g["f"], g["c"])
     bf16 = kw.get("dtype") == "bf16"
     graph_ptr = GRAPH_PTR if kind == "readout" else None
-    u, v = PR.pair_list(g["n"]) if kind.startswith("pair") else (None, None)
+    u, v = (PR.pair_list(g["n"]) if n_rand is None else PR.pair_list(g["n"], n_rand=n_rand)) if kind.startswith("pair") else (None, None)
     R = len(u) if u is not None else len(graph_ptr) - 1 if graph_ptr is not None else g["n"]
     if loss == SOFTMAX:
         sup = g["labels"] if kind == "node" else PR.pair_labels(R, g["c"])
@@ -196,9 +196,10 @@ def _case_inputs(fam, variant, kind, loss, dh, act_name):
                 dh=dh, act=act_name, W1=W1, b1=b1, Wo=Wo, graph_ptr=graph_ptr, u=u, v=v, rows=R, reg=reg, bf16=bf16, model_kw=model_kw)
 
 
-def case_inputs(case):
-    """Everything a case runs on (cached: the seed search runs once per process).  A case without a clear seed among the 40 FAILS."""
-    return dict(_case_inputs(*case))
+def case_inputs(case, n_rand=None):
+    """Everything a case runs on (cached: the seed search runs once per process).  A case without a clear seed among the 40 FAILS.
+    n_rand: the random pairs of pair_ref.pair_list (None: its own count), for a longer pair list (tests/trip_cases.py)."""
+    return dict(_case_inputs(*case) if n_rand is None else _case_inputs(*case, n_rand))
 
 
 def model_of(ci, u=None, v=None):

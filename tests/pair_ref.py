@@ -155,7 +155,7 @@ def pick(FC, orc, cfg, g, u, v, mode, loss, labels, mask=None, variant="plain", 
 
 
 @functools.lru_cache(maxsize=None)
-def _case_inputs(family, variant, mode, loss):
+def _case_inputs(family, variant, mode, loss, n_rand=None):
     import __graft_entry__ as entry
     import feature_cases as FC
     pkg, orc = entry.load_package(), entry.load_oracle()
@@ -165,7 +165,7 @@ def _case_inputs(family, variant, mode, loss):
     _, heads, outdims, kw = next(f for f in families(FC) if f[0] == family)
     cfg = orc.Config(heads, outdims, g["f"], g["c"])
     bf16 = kw.get("dtype") == "bf16"
-    u, v = pair_list(g["n"])
+    u, v = pair_list(g["n"]) if n_rand is None else pair_list(g["n"], n_rand=n_rand)
     n_pairs = len(u)
     labels = pair_labels(n_pairs, g["c"])
     if loss == SOFTMAX:
@@ -182,9 +182,11 @@ def _case_inputs(family, variant, mode, loss):
                 reg=reg, bf16=bf16, model_kw=dict(eps=FC.EPS, keeps=keeps, attn=attn, feat=feat, bf16_pl=bf16))
 
 
-def case_inputs(case):
-    """Everything a case runs on (cached: the seed search runs once per process).  case: an entry of cases()."""
-    return dict(_case_inputs(case[0], case[4], case[5], case[6]), mode=case[5])
+def case_inputs(case, n_rand=None):
+    """Everything a case runs on (cached: the seed search runs once per process).  case: an entry of cases(); n_rand: the random pairs of
+    pair_list (None: its own count), for a longer pair list (tests/trip_cases.py)."""
+    key = (case[0], case[4], case[5], case[6])
+    return dict(_case_inputs(*key) if n_rand is None else _case_inputs(*key, n_rand), mode=case[5])
 
 
 def model_of(ci, u=None, v=None):

@@ -121,22 +121,23 @@ def case_id(case):
     return f"{name}-{dt}-{form}" + (f"-fe{fe}" if fe else "")
 
 
-def case_config(orc, case):
-    g = long_rows_graph()
+def case_config(orc, case, graph=None):
+    """graph: (name, graph dict) instead of long_rows_graph (tests/trip_cases.py)."""
+    g = long_rows_graph() if graph is None else graph[1]
     return g, orc.Config(case[1], case[2], g["f"], g["c"])
 
 
 _REFS = {}
 
 
-def reference(orc, case):
-    """(W, a, Wo), the other inputs, the fp64 model after its backward: once per model (the keep_taps form shares res_norm_reg's).
+def reference(orc, case, graph=None):
+    """(W, a, Wo), the other inputs, the fp64 model after its backward: once per model and graph (the keep_taps form shares res_norm_reg's).
     The seed search and its bounds are the ones of the parent tests (FC.pick_shape, EF.pick)."""
     name, heads, outdims, dt, form, fe = case
     norm, reg, _ = PLAIN_FORMS[form]
-    key = (name, dt, norm, reg, fe)
+    key = (name, dt, norm, reg, fe, None if graph is None else graph[0])
     if key not in _REFS:
-        g, cfg = case_config(orc, case)
+        g, cfg = case_config(orc, case, graph)
         if fe:
             out = EF.pick(FC, orc, cfg, g, fe, REG if reg else None, res_norm=norm, bf16=dt == "bf16")
         else:
@@ -146,13 +147,13 @@ def reference(orc, case):
     return _REFS[key]
 
 
-def run_case(pkg, orc, case):
-    """One context and one step of a case against its model, at the bar of the storage mode."""
+def run_case(pkg, orc, case, graph=None):
+    """One context and one step of a case against its model, at the bar of the storage mode (graph: see case_config)."""
     name, heads, outdims, dt, form, fe = case
     norm, reg, taps = PLAIN_FORMS[form]
     A = pkg.abi
-    g, cfg = case_config(orc, case)
-    P, inp, ref = reference(orc, case)
+    g, cfg = case_config(orc, case, graph)
+    P, inp, ref = reference(orc, case, graph)
     kw = {}
     if dt == "bf16":
         kw["dtype"] = "bf16"
