@@ -57,6 +57,9 @@ HEAD_ACTS = {"relu": 0, "lrelu": HEAD_ACT_LRELU}
 EDGE_DIM_MAX = 64
 RES_LINEAR, RES_BIAS = 1, 2
 NORM_LAYER, NORM_SKIP_LAST = 1, 2
+PARAM_NORM_G, PARAM_NORM_B = PARAM_LN_G, PARAM_LN_B       # the same two groups, as a batch-norm context reads them (set_batch_norm)
+BN_ON, BN_SKIP_LAST = 1, 2
+BN_RUNNING_MEAN, BN_RUNNING_VAR, BN_BATCH_MEAN, BN_BATCH_RSTD = 0, 1, 2, 3
 TABLE_PL, TABLE_GPL = 0, 1
 COMM_GPL_BF16 = 1
 COMM_PIPELINE = 2
@@ -222,6 +225,12 @@ def _declare(lib: C.CDLL) -> None:
         "gat_set_dropedge": [vp, f32, i32],
         "gat_set_residual": [vp, i32],
         "gat_set_norm": [vp, i32, f32],
+        "gat_set_batch_norm": [vp, i32, f32, f32],
+        "gat_batch_norm_info": [vp, P(i32), P(f32), P(f32)],
+        "gat_batch_norm_stats_get": [vp, i32, vp, i64],
+        "gat_batch_norm_stats_set": [vp, i32, vp, i64],
+        "gat_op_batch_norm_forward": [vp, i64, i32, i32, i32, vp, vp, f32, f32, f32, vp, vp, i32, vp, vp, vp],
+        "gat_op_batch_norm_backward": [vp, vp, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
         "gat_set_edge_dim": [vp, i32],
         "gat_set_edge_features": [vp, vp, i64, i32],
         "gat_set_edge_features_device": [vp, vp, i64, i32],
@@ -508,6 +517,34 @@ class GatContext:
         but the last), with the parameter groups PARAM_LN_G / PARAM_LN_B.  Only before the first params_* / grads_* / set_graph*
         call on the context.  ``flags``: extra raw GAT_NORM_* bits (or-ed in)."""
         _chk(self.lib.gat_set_norm(self._ctx, int(flags) | (NORM_LAYER if layer else 0) | (NORM_SKIP_LAST if skip_last else 0), float(eps)))
+
+    # -- batch normalisation (gatv2_abi.h "batch normalisation")
+    def set_batch_norm(self, skip_last: bool = False, eps: float = 1e-5, momentum: float = 0.1, flags: int = BN_ON):
+        """BatchNorm over the columns of each layer's [n_rows][H*D] aggregate between the aggregation and the LeakyReLU, in every layer
+        (``skip_last``: every layer but the last), with gamma / beta in PARAM_NORM_G / PARAM_NORM_B and running statistics that
+        advance once per training forward and are what eval mode (set_training(False)) normalises with.  Only before the first
+        params_* / grads_* / set_graph* call on the context.  ``flags``: the raw GAT_BN_* bits (0: the call changes nothing)."""
+        _chk(self.lib.gat_set_batch_norm(self._ctx, int(flags) | (BN_SKIP_LAST if skip_last else 0), float(eps), float(momentum)))
+
+    def batch_norm_info(self):
+        """(flags, eps, momentum) of the context's batch normalisation; flags 0 = off."""
+        f, e, m = C.c_int32(0), C.c_float(0), C.c_float(0)
+        _chk(self.lib.gat_batch_norm_info(self._ctx, C.byref(f), C.byref(e), C.byref(m)))
+        return f.value, e.value, m.value
+
+    def _bn_count(self) -> int:
+        return sum(h * d for h, d in zip(self.heads, self.outdims))
+
+    def batch_norm_stats(self, which: int) -> np.ndarray:
+        """One of the BN_* statistics vectors, flat [l][H_l*D_l] over all layers."""
+        out = np.empty(self._bn_count(), np.float32)
+        _chk(self.lib.gat_batch_norm_stats_get(self._ctx, int(which), _np_ptr(out), out.size))
+        return out
+
+    def set_batch_norm_stats(self, which: int, arr):
+        """Replaces BN_RUNNING_MEAN or BN_RUNNING_VAR (flat [l][H_l*D_l]); a captured step graph stays valid."""
+        a = np.ascontiguousarray(arr, np.float32).ravel()
+        _chk(self.lib.gat_batch_norm_stats_set(self._ctx, int(which), _np_ptr(a), a.size))
 
     # -- edge features (gatv2_abi.h "edge features")
     def set_edge_dim(self, edge_dim: int):
@@ -955,6 +992,27 @@ def op_readout_backward(d_gpooled: int, d_graph_ptr: int, n_graphs: int, n_rows:
     _chk(load_library().gat_op_readout_backward(C.c_void_p(d_gpooled or None), C.c_void_p(d_graph_ptr or None), n_graphs, n_rows, width,
                                                 readout_mode(mode), C.c_void_p(d_argmax or None), C.c_void_p(d_gh or None), gh_stride,
                                                 C.c_void_p(stream or None)))
+
+
+def op_batch_norm_forward(d_u: int, n_rows: int, H: int, D: int, is_last: bool, d_gamma: int, d_beta: int, eps: float, slope: float,
+                          momentum: float, d_running_mean: int, d_running_var: int, training: bool, d_mean_rstd: int, d_hout: int,
+                          stream: int = 0):
+    """gat_op_batch_norm_forward on device pointers: hout of u [n_rows][H*D]; training: {mu, rstd} into d_mean_rstd [2][H*D] and the
+    running pair (0: none) advanced; eval: the running pair is what is normalised with."""
+    p = lambda x: C.c_void_p(x or None)
+    _chk(load_library().gat_op_batch_norm_forward(p(d_u), n_rows, H, D, int(bool(is_last)), p(d_gamma), p(d_beta), eps, slope, momentum,
+                                                  p(d_running_mean), p(d_running_var), int(bool(training)), p(d_mean_rstd), p(d_hout), p(stream)))
+
+
+def op_batch_norm_backward(d_u: int, d_g: int, d_gh: int, gh_stride: int, n_rows: int, H: int, D: int, d_gamma: int, d_beta: int,
+                           d_mean_rstd: int, d_running_mean: int, d_running_var: int, eps: float, slope: float, training: bool, d_res: int,
+                           d_bias: int, d_G: int, d_agg: int, d_grad_gamma: int, d_grad_beta: int, d_grad_b: int, stream: int = 0):
+    """gat_op_batch_norm_backward on device pointers: G and agg [n_rows][H*D] from dL/dhout (d_g, or d_gh for the last layer); the
+    three gradient vectors [H*D] are added into (0: not formed)."""
+    p = lambda x: C.c_void_p(x or None)
+    _chk(load_library().gat_op_batch_norm_backward(p(d_u), p(d_g), p(d_gh), gh_stride, n_rows, H, D, p(d_gamma), p(d_beta), p(d_mean_rstd),
+                                                   p(d_running_mean), p(d_running_var), eps, slope, int(bool(training)), p(d_res), p(d_bias),
+                                                   p(d_G), p(d_agg), p(d_grad_gamma), p(d_grad_beta), p(d_grad_b), p(stream)))
 
 
 def op_pair_forward(d_x: int, x_stride: int, d_u: int, d_v: int, n_pairs: int, n_rows: int, width: int, mode, d_q: int, stream: int = 0):

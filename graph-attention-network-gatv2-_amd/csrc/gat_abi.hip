@@ -47,7 +47,7 @@ static void layout_params(gat_ctx* c) {
         n[GAT_PARAM_A] += y.HD;
         if (c->res.flags & GAT_RES_LINEAR) n[GAT_PARAM_WRES] += (int64_t)y.HD * y.F;
         if (c->res.flags & GAT_RES_BIAS) n[GAT_PARAM_B] += y.HD;
-        if (c->res.norm_flags != 0) n[GAT_PARAM_LN_G] += y.HD;               // all L layers; with GAT_NORM_SKIP_LAST the last one's entries are never read
+        if (c->res.norm_flags != 0 || c->res.bn_flags != 0) n[GAT_PARAM_LN_G] += y.HD;   // all L layers; with GAT_NORM_SKIP_LAST / GAT_BN_SKIP_LAST the last one's entries are never read
         n[GAT_PARAM_WE] += (int64_t)y.HD * c->ef.dim;
     }
     n[GAT_PARAM_WO] = (int64_t)c->cfg.num_classes * head_width(c);      // [C][Dh] behind a hidden layer
@@ -244,6 +244,10 @@ int ensure_buffers(gat_ctx* c) {
     GAT_TRY(dalloc(c, &c->head.y, NH * C));
     if (res_route(c)) {                              // gatv2_abi.h "residual" / "layer normalisation"
         if (norm_on(c)) GAT_TRY(dalloc(c, &c->res.norm_partial, (int64_t)L * 2 * kResPartialRows * c->HDmax));
+        if (bn_on(c)) {                              // gatv2_abi.h "batch normalisation" (the statistics themselves: gat_set_batch_norm)
+            GAT_TRY(dalloc(c, &c->res.bn_partial, (int64_t)2 * kResPartialRows * c->HDmax));
+            GAT_TRY(dalloc(c, &c->res.bn_sums, (int64_t)2 * c->HDmax));
+        }
         GAT_TRY(dalloc(c, &c->res.G, N * c->HDmax));
         GAT_TRY(dalloc(c, &c->res.agg, N * c->HDmax));
         GAT_TRY(dalloc(c, &c->res.partial, (int64_t)L * kResPartialRows * c->HDmax));

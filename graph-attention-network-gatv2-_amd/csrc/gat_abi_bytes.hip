@@ -93,6 +93,9 @@ static int algorithmic_bytes_nodes(gat_ctx* c, double* bytes_step, double* per_k
             // adds gamma and beta, read by the forward epilogue and by the backward kernel: 2*HD floats per pass
             k[GAT_K_MISC] += 4.0 * N * HD * (lin ? 5 : 4);
             if (norm_layer(c, l)) k[GAT_K_MISC] += 4.0 * 2 * HD * 2;       // (both passes priced under misc)
+            // a batch-normalised layer (gatv2_abi.h "batch normalisation"): forward u read twice and hout written; backward u and g read
+            // twice, G and agg written, in place of the route's four tensors (R, with GAT_RES_LINEAR, is read once as before)
+            if (bn_layer(c, l)) k[GAT_K_MISC] += 4.0 * N * HD * (3 + 2);
             if (!lin) continue;
             k[GAT_K_PROJECT] += 4.0 * (N * HD + HD * F + N * F);
             k[GAT_K_EDGE_FWD] += 4.0 * N * HD;

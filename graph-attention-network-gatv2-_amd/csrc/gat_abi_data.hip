@@ -95,6 +95,7 @@ static int set_graph_common(gat_ctx* c, const int32_t* row_ptr, const int32_t* c
         return fail(GAT_E_UNSUPPORTED, "gat_set_graph: int32 CSR limits (E:1045-1046) exceeded");
     if (table_row0 < 0 || table_row0 + n_rows > n_table) return fail(GAT_E_INVALID, "gat_set_graph: shard rows outside the table");
     GAT_TRY(hidden_refuse_shard(c, n_rows, n_table));
+    GAT_TRY(bn_refuse_shard(c, n_rows, n_table, table_row0));
     if (kind == hipMemcpyHostToDevice) {
         if (row_ptr[0] != 0 || (int64_t)row_ptr[n_rows] != n_edges)
             return fail(GAT_E_INVALID, "Invalid row_ptr: must start at 0 and end at the edge count");
@@ -132,6 +133,7 @@ static int set_graph_coo_common(gat_ctx* c, const int32_t* src, const int32_t* d
     c->packed.touched = true;                        // from here on gat_set_residual is refused
     if (n_in < 0 || n_in > 0x7fffffffLL) return fail(n_in < 0 ? GAT_E_INVALID : GAT_E_UNSUPPORTED, "gat_set_graph_coo: edge count outside the 32-bit count of the sort");
     GAT_TRY(hidden_refuse_shard(c, n_rows, n_table));
+    GAT_TRY(bn_refuse_shard(c, n_rows, n_table, table_row0));
     int32_t *d_src = nullptr, *d_dst = nullptr;
     if (on_host && n_in > 0) {
         GAT_TRY(dalloc(c, &d_src, n_in));

@@ -25,9 +25,63 @@ int gat_set_norm(gat_ctx* c, int32_t flags, float eps) {
     if (flags == 0 && c->res.norm_flags == 0) return 0;      // the default: nothing is touched
     if (flags != 0 && c->cfg.flat_lrelu_index)
         return fail(GAT_E_UNSUPPORTED, "gat_set_norm: not with flat_lrelu_index (the reference's flat index has no meaning on the normalised row)");
+    if (flags != 0 && bn_on(c)) return fail(GAT_E_UNSUPPORTED, "gat_set_norm: not on a context with batch normalisation (gat_set_batch_norm): one normaliser per context");
     GAT_REFUSE_DBG(c, flags != 0, "gat_set_norm", " (those kernels have no normalised form)");
     c->res.norm_flags = flags; c->res.norm_eps = flags != 0 ? eps : 0.f;
     return relayout(c);
+}
+// ---- batch normalisation ----------------------------------------------------------------------------------------
+int gat_set_batch_norm(gat_ctx* c, int32_t flags, float eps, float momentum) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (flags & ~(GAT_BN_ON | GAT_BN_SKIP_LAST)) return fail(GAT_E_INVALID, "gat_set_batch_norm: unknown flag bits");
+    if ((flags & GAT_BN_SKIP_LAST) && !(flags & GAT_BN_ON)) return fail(GAT_E_INVALID, "gat_set_batch_norm: GAT_BN_SKIP_LAST needs GAT_BN_ON");
+    if (flags != 0 && !(std::isfinite(eps) && eps > 0.f)) return fail(GAT_E_INVALID, "gat_set_batch_norm: eps must be finite and > 0");
+    if (flags != 0 && !(std::isfinite(momentum) && momentum >= 0.f && momentum <= 1.f)) return fail(GAT_E_INVALID, "gat_set_batch_norm: momentum must be in [0, 1]");
+    GAT_LAYOUT_OPEN(c, "gat_set_batch_norm");
+    if (flags == 0 && c->res.bn_flags == 0) return 0;        // the default: nothing is touched
+    if (flags != 0 && norm_on(c)) return fail(GAT_E_UNSUPPORTED, "gat_set_batch_norm: not on a context with layer normalisation (gat_set_norm): one normaliser per context");
+    if (flags != 0 && c->cfg.flat_lrelu_index)
+        return fail(GAT_E_UNSUPPORTED, "gat_set_batch_norm: not with flat_lrelu_index (the reference's flat index has no meaning on the normalised row)");
+    GAT_REFUSE_DBG(c, flags != 0, "gat_set_batch_norm", " (those kernels have no normalised form)");
+    c->res.bn_flags = flags; c->res.bn_eps = flags != 0 ? eps : 0.f; c->res.bn_momentum = flags != 0 ? momentum : 0.f;
+    GAT_TRY(relayout(c));
+    if (flags != 0 && !c->res.bn_stats) {                    // the statistics: allocated once and never moved (a captured step keeps its pointers)
+        int64_t total = 0;
+        for (const Layer& y : c->layers) total += y.HD;
+        c->res.bn_total = total;
+        GAT_TRY(dalloc(c, &c->res.bn_stats, 4 * total));
+        std::vector<float> init((size_t)(4 * total), 0.f);
+        std::fill(init.begin() + total, init.begin() + 2 * total, 1.0f);      // running mean 0, running var 1
+        GAT_HIP(hipMemcpy(c->res.bn_stats, init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+int gat_batch_norm_info(gat_ctx* c, int32_t* flags, float* eps, float* momentum) {
+    if (!c) return fail(GAT_E_INVALID, "null context");
+    if (flags) *flags = c->res.bn_flags;
+    if (eps) *eps = c->res.bn_eps;
+    if (momentum) *momentum = c->res.bn_momentum;
+    return 0;
+}
+static int bn_stats_access(gat_ctx* c, const char* who, int32_t which, const void* host, int64_t count, int32_t max_which) {
+    if (!c || !host) return fail(GAT_E_INVALID, std::string(who) + ": null argument");
+    if (!bn_on(c) || !c->res.bn_stats) return fail(GAT_E_STATE, std::string(who) + ": the context has no batch normalisation (gat_set_batch_norm)");
+    if (which < 0 || which > max_which)
+        return fail(GAT_E_INVALID, std::string(who) + (max_which == GAT_BN_RUNNING_VAR ? ": only GAT_BN_RUNNING_MEAN and GAT_BN_RUNNING_VAR can be set" : ": unknown statistic"));
+    if (count != c->res.bn_total) return fail(GAT_E_INVALID, std::string(who) + ": count mismatch (sum over the layers of H*D)");
+    return 0;
+}
+int gat_batch_norm_stats_get(gat_ctx* c, int32_t which, float* host, int64_t count) {
+    GAT_TRY(bn_stats_access(c, "gat_batch_norm_stats_get", which, host, count, GAT_BN_BATCH_RSTD));
+    GAT_HIP(hipMemcpyAsync(host, c->res.bn_stats + (int64_t)which * c->res.bn_total, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+int gat_batch_norm_stats_set(gat_ctx* c, int32_t which, const float* host, int64_t count) {
+    GAT_TRY(bn_stats_access(c, "gat_batch_norm_stats_set", which, host, count, GAT_BN_RUNNING_VAR));
+    GAT_HIP(hipMemcpyAsync(c->res.bn_stats + (int64_t)which * c->res.bn_total, host, (size_t)count * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    GAT_HIP(hipStreamSynchronize(c->stream));               // (the same buffer: a captured step graph reads the new values)
+    return 0;
 }
 // ---- edge features ------------------------------------------------------------------------------------------------
 int gat_set_edge_dim(gat_ctx* c, int32_t edge_dim) {

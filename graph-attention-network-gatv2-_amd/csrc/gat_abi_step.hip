@@ -127,14 +127,31 @@ static EdgeFwdArgs plan_forward_edges(gat_ctx* c, int32_t l) {
     set_work_list(a, c->graph.work, c->graph.items, c->graph.slot_info, c->graph.part_acc, c->graph.part_mz);
     return a;
 }
+// Batch-normalised layer, behind its edge forward (gatv2_abi.h "batch normalisation"): in training mode the column statistics of u = h_pre
+// and their finish (mu, rstd, the running update), then hout = LReLU(v) over the LReLU(u) the edge forward left; eval mode: the apply
+// launch alone, on the running statistics.  Plain launches on the context's stream: capturable, no host synchronisation.
+static int bn_forward_layer(gat_ctx* c, int32_t l) {
+    if (!bn_layer(c, l)) return 0;
+    const Layer& y = c->layers[l];
+    Scope t(c, GAT_K_MISC);
+    if (c->drop.training)
+        GAT_TRY(launch_batch_norm_stats(y.hpre, c->graph.n_rows, y.HD, c->res.bn_partial, c->res.bn_partial + (int64_t)kResPartialRows * c->HDmax,
+                                        c->res.bn_eps, c->res.bn_momentum, bn_stat_of(c, GAT_BN_BATCH_MEAN, l), bn_stat_of(c, GAT_BN_BATCH_RSTD, l),
+                                        bn_stat_of(c, GAT_BN_RUNNING_MEAN, l), bn_stat_of(c, GAT_BN_RUNNING_VAR, l), c->stream));
+    return launch_batch_norm_apply(y.hpre, bn_stats_now(c, l), lng_of(c, l), lnb_of(c, l), c->cfg.negative_slope, y.hout, c->graph.n_rows, y.H, y.D,
+                                   l == c->cfg.num_layers - 1, c->stream);
+}
 int gat_layer_forward_edges(gat_ctx* c, int32_t l) {
     GAT_TRY(check_layer(c, l));
     GAT_TRY(check_edge_features(c));
     const EdgeFwdArgs a = plan_forward_edges(c, l);
     EdgeFwdExtras x;                                 // masks, residual, bias, norm, edge term: whatever of them is on (launch_edge_forward: none = the plain kernels)
     x.drop = drop_args(c, l); x.res = c->layers[l].R; x.bias = b_of(c, l); x.ln = ln_args(c, l); x.pe = c->layers[l].PE;
-    Scope t(c, GAT_K_EDGE_FWD);
-    return launch_edge_forward(a, c->stream, &x);
+    {
+        Scope t(c, GAT_K_EDGE_FWD);
+        GAT_TRY(launch_edge_forward(a, c->stream, &x));
+    }
+    return bn_forward_layer(c, l);
 }
 
 // Readout: P = pool(hout of the last layer) in front of the head, gH = un-pool(gP) behind it (both no-ops with readout off).  Plain
@@ -318,6 +335,15 @@ static int res_backward_layer(gat_ctx* c, int32_t l) {
         GAT_TRY(launch_norm_backward(n, c->stream));
         GAT_TRY(launch_reduce_partials_add(n.part_gamma, r.blocks, y.HD, glng_of(c, l), c->stream));
         GAT_TRY(launch_reduce_partials_add(n.part_beta, r.blocks, y.HD, glnb_of(c, l), c->stream));
+    } else if (bn_layer(c, l)) {                     // batch-normalised layer: column sums of dv and dv * xhat, then G through the normalisation
+        BnBwdArgs n{};
+        n.u = y.hpre; n.g = r.g; n.gh = r.gh; n.res = r.res; n.bias = r.bias; n.gamma = lng_of(c, l); n.beta = lnb_of(c, l);
+        n.stats = bn_stats_now(c, l);
+        n.G = r.G; n.agg = r.agg; n.part_G = r.partial;
+        n.part_s1 = c->res.bn_partial; n.part_s2 = c->res.bn_partial + (int64_t)kResPartialRows * c->HDmax; n.sums = c->res.bn_sums;
+        n.n_rows = r.n_rows; n.gh_stride = r.gh_stride; n.H = y.H; n.D = y.D; n.training = c->drop.training ? 1 : 0; n.slope = r.slope;
+        n.blocks = r.blocks = batch_norm_blocks(c->graph.n_rows, y.HD);
+        GAT_TRY(launch_batch_norm_backward(n, glng_of(c, l), glnb_of(c, l), c->stream));
     } else {
         r.blocks = res_backward_blocks(c->graph.n_rows, y.HD);
         GAT_TRY(launch_res_backward(r, c->stream));
@@ -765,6 +791,7 @@ static int check_comm_target(gat_ctx* c, int32_t world, int32_t rank) {
     if (readout_on(c)) return fail(GAT_E_UNSUPPORTED, "gat_comm_init: not on a readout context (a graph may straddle shards)");
     if (pairs_on(c)) return fail(GAT_E_UNSUPPORTED, "gat_comm_init: not on a context with a pair head (an endpoint may live on another shard)");
     if (hidden_on(c)) return fail(GAT_E_UNSUPPORTED, "gat_comm_init: not on a context with a hidden head layer (gat_set_head_hidden has no sharded form)");
+    if (bn_on(c)) return fail(GAT_E_UNSUPPORTED, "gat_comm_init: not on a context with batch normalisation (the column statistics of a shard would need an exchange)");
     if (world < 1 || rank < 0 || rank >= world) return fail(GAT_E_INVALID, "gat_comm_init: bad world / rank");
     if (c->graph.n_table % world != 0 || c->graph.table_row0 != (int64_t)rank * (c->graph.n_table / world) || c->graph.n_rows > c->graph.n_table / world)
         return fail(GAT_E_INVALID, "gat_comm_init: the source table must be [world][max_rows] with this shard's rows at rank*max_rows");

@@ -87,6 +87,19 @@ int gat_tap(gat_ctx* c, int tensor, int32_t l, void* host, int64_t count) {
                 GAT_TRY(launch_norm_backward(n, c->stream));
                 return d2h(c, host, tmp, (size_t)(N * y.HD) * sizeof(float));
             }
+            if (bn_layer(c, l)) {                       // through the batch normalisation: the two backward launches again, into scratch (no
+                BnBwdArgs n{};                          // gradient is added to, no aggregate, no column sums of G)
+                n.u = y.hpre; n.g = y.g; n.gh = (last && c->bwd.gH != nullptr) ? c->bwd.gH : nullptr; n.gamma = lng_of(c, l); n.beta = lnb_of(c, l);
+                n.stats = bn_stats_now(c, l);
+                n.n_rows = N; n.gh_stride = c->bwd.gh_stride; n.H = y.H; n.D = y.D; n.training = c->drop.training ? 1 : 0; n.slope = c->cfg.negative_slope;
+                n.blocks = batch_norm_blocks(N, y.HD);
+                float* tmp = nullptr;
+                GAT_TRY(tmps.get(&tmp, N * y.HD));
+                GAT_TRY(tmps.get(&n.part_s1, (int64_t)n.blocks * y.HD)); GAT_TRY(tmps.get(&n.part_s2, (int64_t)n.blocks * y.HD)); GAT_TRY(tmps.get(&n.sums, 2 * y.HD));
+                n.G = tmp;
+                GAT_TRY(launch_batch_norm_backward(n, nullptr, nullptr, c->stream));
+                return d2h(c, host, tmp, (size_t)(N * y.HD) * sizeof(float));
+            }
             if (last && c->bwd.gH) {                        // formed on the fly by the kernels: same expression, same order
                 std::vector<float> hp((size_t)(N * y.HD)), gh((size_t)(N * c->bwd.gh_stride));
                 GAT_TRY(d2h(c, hp.data(), y.hpre, hp.size() * sizeof(float)));

@@ -89,8 +89,14 @@ struct gat_ctx {
     // Residual / bias (GAT_RES_* flags) and layer normalisation (GAT_NORM_* flags): G and agg [n_rows][HDmax] are dL/dh_pre and
     // h_pre - (R + b) of the layer whose backward runs; partial [L][kResPartialRows][HDmax] block column sums of G (grad_b) and
     // norm_partial [L][2][kResPartialRows][HDmax] (grad_gamma / grad_beta), one region per layer; the slabs of gradWres likewise.
+    // Batch normalisation (GAT_BN_* flags, gatv2_abi.h "batch normalisation"): bn_stats [4][bn_total] = running mean | running var |
+    // batch mean | batch rstd, each flat [l][H_l*D_l] at the layers' ln_off (not parameters: outside the packed buffers, allocated by
+    // the setter and never moved); bn_partial [2][kResPartialRows][HDmax] the block partials of whichever launch runs (consumed by its
+    // finish launch at once, so the layers share it) and bn_sums [2][HDmax] this step's s1 / s2.
     struct Residual {
         int32_t flags = 0, norm_flags = 0; float norm_eps = 0.f;
+        int32_t bn_flags = 0; float bn_eps = 0.f, bn_momentum = 0.f;
+        float* bn_stats = nullptr; int64_t bn_total = 0; float* bn_partial = nullptr; float* bn_sums = nullptr;
         float* G = nullptr; float* agg = nullptr; float* partial = nullptr; float* norm_partial = nullptr;
         float* gw_scratch = nullptr; std::vector<int64_t> gw_off;
     } res;
@@ -302,8 +308,24 @@ inline bool norm_on(const gat_ctx* c) { return c->res.norm_flags != 0; }
 inline bool norm_layer(const gat_ctx* c, int l) {
     return norm_on(c) && !((c->res.norm_flags & GAT_NORM_SKIP_LAST) && l == c->cfg.num_layers - 1);
 }
+inline bool bn_on(const gat_ctx* c) { return c->res.bn_flags != 0; }
+// layer l is batch-normalised (gatv2_abi.h "batch normalisation")
+inline bool bn_layer(const gat_ctx* c, int l) {
+    return bn_on(c) && !((c->res.bn_flags & GAT_BN_SKIP_LAST) && l == c->cfg.num_layers - 1);
+}
+// one of the four statistics vectors (GAT_BN_*) of layer l
+inline float* bn_stat_of(gat_ctx* c, int which, int l) { return c->res.bn_stats + (int64_t)which * c->res.bn_total + c->layers[l].ln_off; }
+// what layer l normalises with now: the batch's statistics in training mode, the running ones in eval mode (training: of the dropout block,
+// the one mode switch of the context)
+inline BnStats bn_stats_now(gat_ctx* c, int l);
+// a batch-norm context takes no destination-range shard (asked by the calls that set the graph: the feature is switched on before them)
+inline int bn_refuse_shard(const gat_ctx* c, int64_t n_rows, int64_t n_table, int64_t table_row0) {
+    if (bn_on(c) && (n_table != n_rows || table_row0 != 0))
+        return fail(GAT_E_UNSUPPORTED, "gat_set_batch_norm: not on a destination-range shard (n_table != n_rows or table_row0 != 0): the column statistics of a shard would need an exchange");
+    return 0;
+}
 // the context runs the residual route: the forward takes EdgeFwdExtras, the backward the N-sized kernel, G and agg in the edge backward
-inline bool res_route(const gat_ctx* c) { return res_on(c) || norm_on(c); }
+inline bool res_route(const gat_ctx* c) { return res_on(c) || norm_on(c) || bn_on(c); }
 inline bool edge_feat_on(const gat_ctx* c) { return c->ef.dim > 0; }
 inline bool readout_on(const gat_ctx* c) { return c->readout.mode != GAT_READOUT_NONE; }
 inline bool pairs_on(const gat_ctx* c) { return c->pairs.mode != GAT_PAIR_NONE; }
@@ -337,6 +359,13 @@ inline LnArgs ln_args(gat_ctx* c, int l) {
     LnArgs a;
     if (norm_layer(c, l)) { a.gamma = lng_of(c, l); a.beta = lnb_of(c, l); a.eps = c->res.norm_eps; }
     return a;
+}
+inline BnStats bn_stats_now(gat_ctx* c, int l) {
+    BnStats s{};
+    s.eps = c->res.bn_eps; s.from_var = c->drop.training ? 0 : 1;
+    s.mean = bn_stat_of(c, c->drop.training ? GAT_BN_BATCH_MEAN : GAT_BN_RUNNING_MEAN, l);
+    s.scale = bn_stat_of(c, c->drop.training ? GAT_BN_BATCH_RSTD : GAT_BN_RUNNING_VAR, l);
+    return s;
 }
 inline bool feat_drop_on(const gat_ctx* c) { return c->drop.training && c->drop.pf > 0.f; }
 inline bool attn_drop_on(const gat_ctx* c) { return c->drop.training && c->drop.pa > 0.f; }
@@ -378,7 +407,7 @@ inline float* gPR_of(gat_ctx* c, int l) { return (c->ov.active && (l & 1)) ? c->
 #else
 #define GAT_REFUSE_DBG(c, applies, who, tail) do {} while (0)
 #endif
-// The setters that change the packed layout (gat_set_residual / gat_set_norm / gat_set_edge_dim / gat_set_head_hidden) open with this refusal, make their own
+// The setters that change the packed layout (gat_set_residual / gat_set_norm / gat_set_batch_norm / gat_set_edge_dim / gat_set_head_hidden) open with this refusal, make their own
 // checks, set their fields and end with relayout().
 #define GAT_LAYOUT_OPEN(c, who)                                                                                                  \
     do { if ((c)->packed.touched) return ::gat::fail(GAT_E_STATE, who ": call it before the first gat_params_*, gat_grads_* or " \

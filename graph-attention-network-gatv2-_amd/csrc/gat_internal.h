@@ -527,6 +527,36 @@ struct NormBwdArgs {
 int norm_backward_blocks(int64_t n_rows, int32_t HD);
 int launch_norm_backward(const NormBwdArgs& a, hipStream_t s);
 
+// ---- batch normalisation (gatv2_abi.h "batch normalisation"; gat_batchnorm.hip) ----------------------------------
+// The statistics a kernel normalises with, per channel [HD]: the batch's (mean, rstd) of a training forward, or — from_var — the
+// running (mean, var) of eval mode, turned into 1 / sqrt(var + eps) as they are read.
+struct BnStats { const float* mean; const float* scale; float eps; int32_t from_var; };
+// Blocks of the kernels that write per-block column partials (each region [blocks][HD], blocks <= kResPartialRows).
+int batch_norm_blocks(int64_t n_rows, int32_t HD);
+// Training forward, launches 1 and 2: Welford / Chan column statistics of u [n_rows][HD] through part_mean / part_m2 [blocks][HD]
+// into mean / rstd [HD]; run_mean / run_var (both or neither) advance by `momentum` with the unbiased variance.
+int launch_batch_norm_stats(const float* u, int64_t n_rows, int32_t HD, float* part_mean, float* part_m2, float eps, float momentum, float* mean,
+                            float* rstd, float* run_mean, float* run_var, hipStream_t s);
+// Launch 3 (eval mode: the only one): hout = LReLU(gamma * (u - mean) * rstd + beta), [n_rows][HD], or with is_last the mean over heads
+// [n_rows][D] (h ascending).
+int launch_batch_norm_apply(const float* u, const BnStats& st, const float* gamma, const float* beta, float slope, float* hout, int64_t n_rows,
+                            int32_t H, int32_t D, bool is_last, hipStream_t s);
+// Backward of a normalised layer, in res_backward's place: dv = dL/dhout * LReLU'(v) with dL/dhout = g (hidden) or gh / H (last layer),
+//   sums [2][HD] = {s1 = sum_n dv, s2 = sum_n dv * xhat} of THIS call (through part_s1 / part_s2 [blocks][HD]), added to grad_beta / grad_gamma,
+//   G   = gamma * rstd * (dv - s1 / N - xhat * s2 / N)   (training)      gamma * rstd * dv   (training == 0: the statistics are constants)
+//   agg = u - (res + bias)   (null: not written),  part_G [blocks][HD]: block column sums of G (null: not formed; finished by
+//   launch_reduce_partials_add).  blocks = batch_norm_blocks(n_rows, H * D).
+struct BnBwdArgs {
+    const float* u; const float* g; const float* gh; const float* res; const float* bias;
+    const float* gamma; const float* beta;
+    BnStats stats;
+    float* G; float* agg; float* part_G; float* part_s1; float* part_s2; float* sums;
+    int64_t n_rows, gh_stride;
+    int32_t H, D, blocks, training;
+    float slope;
+};
+int launch_batch_norm_backward(const BnBwdArgs& a, float* grad_gamma, float* grad_beta, hipStream_t s);
+
 struct HeadArgs {
     const float* Wo;          // [C][DL]
     const float* HL;          // [n_rows][DL]  post-activation last layer output

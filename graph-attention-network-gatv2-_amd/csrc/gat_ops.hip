@@ -863,4 +863,67 @@ int gat_op_head_hidden_backward(float* d_gz, const float* d_z1, int64_t rows, in
     return rc;
 }
 
+// The batch-normalisation kernels on caller-owned device pointers (gatv2_abi.h "batch normalisation").
+int gat_op_batch_norm_forward(const float* d_u, int64_t n_rows, int32_t H, int32_t D, int32_t is_last, const float* d_gamma, const float* d_beta,
+                              float eps, float slope, float momentum, float* d_running_mean, float* d_running_var, int32_t training,
+                              float* d_mean_rstd, float* d_hout, void* stream) {
+    const char* who = "gat_op_batch_norm_forward";
+    if (n_rows < 1 || n_rows >= 0x7fffffffLL || H < 1 || D < 1 || (int64_t)H * D >= (1 << 24)) return fail(GAT_E_INVALID, std::string(who) + ": bad sizes");
+    if (!d_u || !d_gamma || !d_beta || !d_hout) return fail(GAT_E_INVALID, std::string(who) + ": null argument");
+    if (!(std::isfinite(eps) && eps > 0.f) || !(std::isfinite(momentum) && momentum >= 0.f && momentum <= 1.f)) return fail(GAT_E_INVALID, std::string(who) + ": bad eps or momentum");
+    if ((d_running_mean == nullptr) != (d_running_var == nullptr)) return fail(GAT_E_INVALID, std::string(who) + ": one running statistic without the other");
+    if (training == 0 && !d_running_mean) return fail(GAT_E_INVALID, std::string(who) + ": eval mode needs the running statistics");
+    if (training != 0 && !d_mean_rstd) return fail(GAT_E_INVALID, std::string(who) + ": training mode needs d_mean_rstd");
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t HD = H * D;
+    Scratch tmp;
+    int rc = 0;
+    BnStats st{};
+    st.eps = eps;
+    if (training != 0) {
+        float* part = nullptr;
+        const int blocks = batch_norm_blocks(n_rows, HD);
+        GAT_TRY(tmp.get(&part, (int64_t)2 * blocks * HD));
+        rc = launch_batch_norm_stats(d_u, n_rows, HD, part, part + (int64_t)blocks * HD, eps, momentum, d_mean_rstd, d_mean_rstd + HD, d_running_mean,
+                                     d_running_var, s);
+        st.mean = d_mean_rstd; st.scale = d_mean_rstd + HD; st.from_var = 0;
+    } else {
+        st.mean = d_running_mean; st.scale = d_running_var; st.from_var = 1;
+    }
+    if (rc == 0) rc = launch_batch_norm_apply(d_u, st, d_gamma, d_beta, slope, d_hout, n_rows, H, D, is_last != 0, s);
+    const hipError_t e = hipStreamSynchronize(s);        // before the scratch is freed
+    if (rc == 0 && e != hipSuccess) rc = fail((int)e, std::string(who) + ": " + hipGetErrorString(e));
+    return rc;
+}
+int gat_op_batch_norm_backward(const float* d_u, const float* d_g, const float* d_gh, int64_t gh_stride, int64_t n_rows, int32_t H, int32_t D,
+                               const float* d_gamma, const float* d_beta, const float* d_mean_rstd, const float* d_running_mean,
+                               const float* d_running_var, float eps, float slope, int32_t training, const float* d_res, const float* d_bias,
+                               float* d_G, float* d_agg, float* d_grad_gamma, float* d_grad_beta, float* d_grad_b, void* stream) {
+    const char* who = "gat_op_batch_norm_backward";
+    if (n_rows < 1 || n_rows >= 0x7fffffffLL || H < 1 || D < 1 || (int64_t)H * D >= (1 << 24)) return fail(GAT_E_INVALID, std::string(who) + ": bad sizes");
+    if (!d_u || !d_gamma || !d_beta || !d_G) return fail(GAT_E_INVALID, std::string(who) + ": null argument");
+    if ((d_g == nullptr) == (d_gh == nullptr)) return fail(GAT_E_INVALID, std::string(who) + ": exactly one of d_g and d_gh");
+    if (d_gh && gh_stride < D) return fail(GAT_E_INVALID, std::string(who) + ": gh_stride below D");
+    if (training != 0 ? !d_mean_rstd : (!d_running_mean || !d_running_var)) return fail(GAT_E_INVALID, std::string(who) + ": the statistics of this mode are null");
+    if (training == 0 && !(std::isfinite(eps) && eps > 0.f)) return fail(GAT_E_INVALID, std::string(who) + ": bad eps");
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t HD = H * D;
+    BnBwdArgs a{};
+    a.u = d_u; a.g = d_g; a.gh = d_gh; a.res = d_res; a.bias = d_bias; a.gamma = d_gamma; a.beta = d_beta;
+    a.stats.eps = eps; a.stats.from_var = training != 0 ? 0 : 1;
+    a.stats.mean = training != 0 ? d_mean_rstd : d_running_mean; a.stats.scale = training != 0 ? d_mean_rstd + HD : d_running_var;
+    a.G = d_G; a.agg = d_agg; a.n_rows = n_rows; a.gh_stride = gh_stride; a.H = H; a.D = D; a.training = training != 0 ? 1 : 0; a.slope = slope;
+    a.blocks = batch_norm_blocks(n_rows, HD);
+    Scratch tmp;
+    float* part = nullptr;
+    GAT_TRY(tmp.get(&part, ((int64_t)3 * a.blocks + 2) * HD));
+    a.part_s1 = part; a.part_s2 = part + (int64_t)a.blocks * HD; a.sums = part + (int64_t)3 * a.blocks * HD;
+    a.part_G = d_grad_b ? part + (int64_t)2 * a.blocks * HD : nullptr;
+    int rc = launch_batch_norm_backward(a, d_grad_gamma, d_grad_beta, s);
+    if (rc == 0 && d_grad_b) rc = launch_reduce_partials_add(a.part_G, a.blocks, HD, d_grad_b, s);
+    const hipError_t e = hipStreamSynchronize(s);        // before the scratch is freed
+    if (rc == 0 && e != hipSuccess) rc = fail((int)e, std::string(who) + ": " + hipGetErrorString(e));
+    return rc;
+}
+
 }  // extern "C"

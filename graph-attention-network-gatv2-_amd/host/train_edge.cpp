@@ -30,6 +30,10 @@
 // --layer-norm [--norm-eps X] [--norm-skip-last]: LayerNorm over each row's H*D channels between the aggregation and the LeakyReLU
 // (gatv2_abi.h "layer normalisation"; eps default 1e-5; --norm-skip-last leaves the last layer un-normalised); gamma starts at 1, beta
 // at 0, and --dump-params / --load-params carry gamma and beta behind the residual groups, only with the flag.
+// --batch-norm [--bn-momentum M] [--norm-eps X] [--norm-skip-last]: BatchNorm over the columns of each layer's [N][H*D] aggregate between the
+// aggregation and the LeakyReLU (gatv2_abi.h "batch normalisation"; momentum default 0.1; not together with --layer-norm; one rank).
+// Validation (--val-mask) then comes from an eval-mode forward, on the running statistics.  gamma and beta travel in --dump-params /
+// --load-params as with --layer-norm, and — only with this flag — running_mean then running_var follow the last group.
 // --edge-features: per-edge attributes in the attention score (gatv2_abi.h "edge features"): edge_features.txt of the dataset folder holds
 // E lines of Fe values, line j for CSR edge j (Fe is derived from the count); We is Xavier-initialised from --seed after every other
 // parameter, and --dump-params / --load-params carry We behind beta, only with the flag.  CSR datasets as they are, one rank: the flag
@@ -107,6 +111,7 @@ struct Options {
     float drop_edge = 0.f; int drop_edge_flags = 0;   // GAT_DROPEDGE_*: --drop-edge-keep-self, --drop-edge-shared
     int residual_flags = 0;                           // GAT_RES_*: --residual, --bias
     int norm_flags = 0; float norm_eps = 1e-5f;       // GAT_NORM_*: --layer-norm, --norm-skip-last; --norm-eps
+    bool batch_norm = false; float bn_momentum = 0.1f; // --batch-norm, --bn-momentum (eps and skip-last: the two norm flags above)
     int graph_flags = 0;                  // GAT_GRAPH_*: --add-self-loops, --undirected, --coalesce
     std::string readout;                  // --readout mean|sum|max: graph_ptr.txt of the dataset folder, one label per graph
     bool edge_features = false;           // --edge-features: edge_features.txt of the dataset folder enters the attention score
@@ -138,6 +143,7 @@ const char* kUsage =
     "            --bias             every layer adds a learned bias b to h_pre\n"
     "                          (--dump-params / --load-params then append Wres and b behind W, a and Wo)\n"
     "            --layer-norm [--norm-eps X] [--norm-skip-last]   LayerNorm over each row's H*D channels before the LeakyReLU\n"
+    "            --batch-norm [--bn-momentum M] [--norm-eps X] [--norm-skip-last]   BatchNorm over each layer's columns (all nodes) before the LeakyReLU\n"
     "                          (eps X, default 1e-5 / not in the last layer; gamma and beta follow b in --dump-params / --load-params)\n"
     "            --edge-features    per-edge attributes enter the attention score: edge_features.txt of the dataset folder, E lines of Fe\n"
     "                          values in CSR order (CSR datasets only, not with the graph flags, --ranks 1; We follows beta in\n"
@@ -247,6 +253,8 @@ Options parse_args(int argc, char** argv) {
         else if (a == "--residual") o.residual_flags |= GAT_RES_LINEAR;
         else if (a == "--bias") o.residual_flags |= GAT_RES_BIAS;
         else if (a == "--layer-norm") o.norm_flags |= GAT_NORM_LAYER;
+        else if (a == "--batch-norm") o.batch_norm = true;
+        else if (a == "--bn-momentum" && has_val) o.bn_momentum = std::strtof(argv[++i], nullptr);
         else if (a == "--norm-skip-last") o.norm_flags |= GAT_NORM_SKIP_LAST;
         else if (a == "--norm-eps" && has_val) o.norm_eps = std::strtof(argv[++i], nullptr);
         else if (a == "--edge-features") o.edge_features = true;
@@ -281,6 +289,8 @@ Options parse_args(int argc, char** argv) {
     } else if (o.beta1_given || o.beta2_given) {
         std::cerr << "Warning: beta1/beta2 specified but ignored for SGD optimizer.\n";
     }
+    if (o.batch_norm && (o.norm_flags & GAT_NORM_LAYER)) die("Error: --batch-norm and --layer-norm exclude each other (one normaliser per model).\n");
+    if (o.batch_norm && o.ranks > 1) die("Error: --batch-norm runs on one rank (the column statistics of a shard would need an exchange).\n");
     // The reference leaves head[]/out_dim[] uninitialised without these flags.
     if (!o.heads_given) die("Error: --heads must have " + std::to_string(o.layers) + " values.\n");
     if (!o.outdims_given) die("Error: --ooutdims must have " + std::to_string(o.layers) + " values.\n");
@@ -605,7 +615,8 @@ int run(const Options& o, const RankEnv& env) {
     check(gat_create(&cfg, &ctx), "gat_create");
     // residual / bias: before anything sizes the packed buffers; every rank of --ranks runs this with the same options
     if (o.residual_flags) check(gat_set_residual(ctx, o.residual_flags), "gat_set_residual");
-    if (o.norm_flags) check(gat_set_norm(ctx, o.norm_flags, o.norm_eps), "gat_set_norm");
+    if (o.batch_norm) check(gat_set_batch_norm(ctx, GAT_BN_ON | ((o.norm_flags & GAT_NORM_SKIP_LAST) ? GAT_BN_SKIP_LAST : 0), o.norm_eps, o.bn_momentum), "gat_set_batch_norm");
+    else if (o.norm_flags) check(gat_set_norm(ctx, o.norm_flags, o.norm_eps), "gat_set_norm");
     if (o.edge_features) check(gat_set_edge_dim(ctx, Fe), "gat_set_edge_dim");
     if (loss_mode != GAT_LOSS_SOFTMAX_CE) check(gat_set_loss(ctx, loss_mode), "gat_set_loss");
     if (o.head_hidden > 0) check(gat_set_head_hidden(ctx, o.head_hidden, o.head_act), "gat_set_head_hidden");
@@ -615,6 +626,7 @@ int run(const Options& o, const RankEnv& env) {
     gat_param_count(ctx, GAT_PARAM_W, &nW); gat_param_count(ctx, GAT_PARAM_A, &nA); gat_param_count(ctx, GAT_PARAM_WO, &nWo);
     gat_param_count(ctx, GAT_PARAM_WRES, &nWres); gat_param_count(ctx, GAT_PARAM_B, &nB);     // 0 without the flags
     gat_param_count(ctx, GAT_PARAM_LN_G, &nLnG); gat_param_count(ctx, GAT_PARAM_LN_B, &nLnB);
+    const int64_t nBn = o.batch_norm ? nLnG : 0;      // floats of running_mean, and of running_var: behind the last group of a parameter file
     if (env.world == 1) {
         check(gat_set_graph(ctx, row_ptr.data(), col_idx.data(), N, E, N, 0), "csr_to_coo_kernel");
         check(gat_set_features(ctx, x.data(), N, F0), "gat_set_features");
@@ -733,11 +745,12 @@ int run(const Options& o, const RankEnv& env) {
         std::printf(" (%d column%s)\n", n, n == 1 ? "" : "s");
     };
     const bool dropout = o.dropout > 0.f || o.attn_dropout > 0.f || o.drop_edge > 0.f;
+    const bool eval_pass = dropout || o.batch_norm;   // validation needs a forward of its own in eval mode
     if (dropout) check(gat_set_dropout(ctx, o.dropout, o.attn_dropout, o.seed, 0), "gat_set_dropout");   // also seeds DropEdge
     if (o.drop_edge > 0.f) check(gat_set_dropedge(ctx, o.drop_edge, o.drop_edge_flags), "gat_set_dropedge");
     check(gat_params_init(ctx, o.seed), "xavier_init_kernel");
     if (!o.load_params.empty()) {
-        std::vector<float> p(nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe + nW1 + nB1);    // the residual, norm, edge-feature and hidden-head groups follow the others, only with their flags
+        std::vector<float> p(nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe + nW1 + nB1 + 2 * nBn);    // the residual, norm, edge-feature and hidden-head groups follow the others, only with their flags
         std::ifstream f(o.load_params, std::ios::binary);
         if (!f.read(reinterpret_cast<char*>(p.data()), p.size() * sizeof(float))) die("Error: cannot read --load-params file\n");
         check(gat_params_set(ctx, GAT_PARAM_W, p.data(), nW), "gat_params_set");
@@ -750,6 +763,11 @@ int run(const Options& o, const RankEnv& env) {
         if (nWe) check(gat_params_set(ctx, GAT_PARAM_WE, p.data() + nW + nA + nWo + nWres + nB + nLnG + nLnB, nWe), "gat_params_set");
         if (nW1) check(gat_params_set(ctx, GAT_PARAM_HEAD_W, p.data() + nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe, nW1), "gat_params_set");
         if (nB1) check(gat_params_set(ctx, GAT_PARAM_HEAD_B, p.data() + nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe + nW1, nB1), "gat_params_set");
+        if (nBn) {
+            const float* stats = p.data() + (p.size() - 2 * nBn);
+            check(gat_batch_norm_stats_set(ctx, GAT_BN_RUNNING_MEAN, stats, nBn), "gat_batch_norm_stats_set");
+            check(gat_batch_norm_stats_set(ctx, GAT_BN_RUNNING_VAR, stats + nBn, nBn), "gat_batch_norm_stats_set");
+        }
     }
 
     size_t free_after = 0;
@@ -781,7 +799,7 @@ int run(const Options& o, const RankEnv& env) {
         if (loss_mode == GAT_LOSS_SOFTMAX_CE) std::printf("\nAvg Loss: %f, Accuracy: %.2f%%\n", loss_sum / n_train, 100.0f * (static_cast<float>(n_correct) / n_train));
         else if (loss_mode == GAT_LOSS_BCE) std::printf("\nAvg Loss: %f, Accuracy: %.2f%%\n", loss_sum / train_entries, 100.0f * (static_cast<float>(n_correct) / train_entries));
         else std::printf("\nAvg Loss: %f\n", loss_sum / train_entries);
-        if (!val_m.empty() && !dropout) {
+        if (!val_m.empty() && !eval_pass) {
             double vl = 0.0; int32_t vc = 0, vn = 0;
             check(gat_eval_mask(ctx, val_m.data(), NH, &vl, &vc, &vn), "gat_eval_mask");
             print_val(vl, vc, vn);
@@ -792,7 +810,7 @@ int run(const Options& o, const RankEnv& env) {
         if (o.optimizer == "adam") check(gat_step_adam(ctx, o.lr, o.beta1, o.beta2, 1e-8f, epoch), "adam_update_kernel");
         else check(gat_step_sgd(ctx, o.lr), "sgd_update_kernel");
         check(gat_zero_grad(ctx), "gat_zero_grad");
-        if (!val_m.empty() && dropout) {          // validation of the updated model, without dropout
+        if (!val_m.empty() && eval_pass) {        // validation of the updated model, without dropout, on the running statistics
             double vl = 0.0; int32_t vc = 0, vn = 0;
             check(gat_set_training(ctx, 0), "gat_set_training");
             check(gat_forward(ctx, nullptr, nullptr), "gatv2 forward");
@@ -807,7 +825,7 @@ int run(const Options& o, const RankEnv& env) {
     }
 
     if (!o.dump_params.empty() && env.rank == 0) {
-        std::vector<float> p(nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe + nW1 + nB1);    // without --residual / --bias / --layer-norm / --edge-features / --head-hidden: the format of always
+        std::vector<float> p(nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe + nW1 + nB1 + 2 * nBn);    // without --residual / --bias / --layer-norm / --batch-norm / --edge-features / --head-hidden: the format of always
         check(gat_params_get(ctx, GAT_PARAM_W, p.data(), nW), "gat_params_get");
         check(gat_params_get(ctx, GAT_PARAM_A, p.data() + nW, nA), "gat_params_get");
         check(gat_params_get(ctx, GAT_PARAM_WO, p.data() + nW + nA, nWo), "gat_params_get");
@@ -818,6 +836,11 @@ int run(const Options& o, const RankEnv& env) {
         if (nWe) check(gat_params_get(ctx, GAT_PARAM_WE, p.data() + nW + nA + nWo + nWres + nB + nLnG + nLnB, nWe), "gat_params_get");
         if (nW1) check(gat_params_get(ctx, GAT_PARAM_HEAD_W, p.data() + nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe, nW1), "gat_params_get");
         if (nB1) check(gat_params_get(ctx, GAT_PARAM_HEAD_B, p.data() + nW + nA + nWo + nWres + nB + nLnG + nLnB + nWe + nW1, nB1), "gat_params_get");
+        if (nBn) {
+            float* stats = p.data() + (p.size() - 2 * nBn);
+            check(gat_batch_norm_stats_get(ctx, GAT_BN_RUNNING_MEAN, stats, nBn), "gat_batch_norm_stats_get");
+            check(gat_batch_norm_stats_get(ctx, GAT_BN_RUNNING_VAR, stats + nBn, nBn), "gat_batch_norm_stats_get");
+        }
         std::ofstream f(o.dump_params, std::ios::binary);
         f.write(reinterpret_cast<const char*>(p.data()), p.size() * sizeof(float));
     }

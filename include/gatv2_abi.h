@@ -186,6 +186,8 @@ int gat_graph_check_device(const int32_t* d_row_ptr, const int32_t* d_col_idx, i
  * GAT_PARAM_WE flat [l][H_l*D_l][Fe] exists on a context with gat_set_edge_dim(Fe > 0) (see "edge features" below) and sits behind
  * the other six; with edge_dim == 0 its count is 0. */
 enum { GAT_PARAM_W = 0, GAT_PARAM_A = 1, GAT_PARAM_WO = 2, GAT_PARAM_WRES = 3, GAT_PARAM_B = 4, GAT_PARAM_LN_G = 5, GAT_PARAM_LN_B = 6, GAT_PARAM_WE = 7 };
+/* the two norm groups under the name a batch-norm context reads them by (gat_set_batch_norm: the same groups, not new ones) */
+enum { GAT_PARAM_NORM_G = GAT_PARAM_LN_G, GAT_PARAM_NORM_B = GAT_PARAM_LN_B };
 int gat_param_count(gat_ctx* ctx, int group, int64_t* count);
 /* U(-lim,lim], lim as E:208, 236.  With GAT_RES_LINEAR: Wres_l Xavier-uniform with lim = sqrt(6 / (F_l + H_l*D_l)), drawn from the same
  * counter stream AFTER all existing draws (layer by layer), so W, a and Wo of a seed are those of a context without it; b = 0.
@@ -502,6 +504,78 @@ int gat_set_residual(gat_ctx* ctx, int32_t flags);
  *   normalised layer adds 2*HD floats of parameters per pass to misc.  gat_algorithmic_bytes_shape prices the model without it. */
 enum { GAT_NORM_LAYER = 1, GAT_NORM_SKIP_LAST = 2 };
 int gat_set_norm(gat_ctx* ctx, int32_t flags, float eps);
+
+/* ---- batch normalisation between the aggregation and the activation (beyond the reference; DGL's OGB GAT baselines put
+ *      BatchNorm1d(H*D) behind every hidden GATConv, the usual graph-classification stack normalises over all nodes of the batch) ----
+ * With GAT_BN_ON every layer l — with GAT_BN_SKIP_LAST every layer but the last — computes, with u[n,c] = h_pre exactly as without
+ * the feature (attention dropout, DropEdge, Wres x' and b included), c = h*D + d, and N = ALL n_rows rows of the context (whatever the
+ * training mask says; the nodes of all graphs of a readout context; rows without in-edges included), in TRAINING mode
+ *     mu[c]   = (1/N) sum_n u[n,c]
+ *     var[c]  = (1/N) sum_n (u[n,c] - mu[c])^2        biased; formed by Welford / Chan merges, never as E[u^2] - mu^2
+ *     rstd[c] = 1 / sqrt(var[c] + eps)
+ *     xhat    = (u - mu) * rstd
+ *     v       = gamma_l[c] * xhat + beta_l[c]
+ *     hout    = LReLU(v)      hidden layers: concatenated; last layer: mean over heads (h ascending) of LReLU(v)
+ *     running_mean_l = (1 - m) * running_mean_l + m * mu
+ *     running_var_l  = (1 - m) * running_var_l  + m * var * N/(N-1)        (N == 1: var itself)
+ * The running statistics start at 0 and 1 and advance once per training forward: gat_forward, gat_step, a replay of a captured step
+ * graph (the update is one of its kernels), or gat_layer_forward_edges of the phase API.  They never advance in eval mode.
+ * EVAL mode (gat_set_training(ctx, 0)): mu and rstd are replaced by running_mean and 1 / sqrt(running_var + eps); no statistics pass
+ * runs and nothing advances.
+ * Backward, with dv = dL/dhout (.) LReLU'(v) and dL/dhout what the layer-norm backward takes (g of a hidden layer, gH / H of the last):
+ *     grad_beta_l[c]  += s1[c],  s1 = sum_n dv[n,c]
+ *     grad_gamma_l[c] += s2[c],  s2 = sum_n dv[n,c] * xhat[n,c]
+ *     G[n,c] = gamma_l[c] * rstd[c] * (dv[n,c] - s1[c]/N - xhat[n,c] * s2[c]/N)        training mode
+ *     G[n,c] = gamma_l[c] * rstd[c] * dv[n,c]                                          eval mode (the statistics are constants)
+ * G and agg = u - (R + b) then play the role they play on the residual route (edge backward, gradWres = G^T x', grad_b = sum_n G,
+ * grad_x += G Wres).  Upstream of u nothing changes: score, softmax statistics, alpha, and GAT_TAP_HPRE, which keeps returning u.
+ * Parameters: gamma and beta live in the two existing norm groups, GAT_PARAM_NORM_G / GAT_PARAM_NORM_B (= GAT_PARAM_LN_G / _LN_B), flat
+ *   [l][H_l*D_l] over ALL layers, gamma = 1, beta = 0, no draws; with GAT_BN_SKIP_LAST the last layer's entries exist, are never read
+ *   and their gradients are exactly 0.  The running statistics are NOT parameters: two device buffers [l][H_l*D_l] outside the packed
+ *   buffers, which SGD, Adam, clip and zero_grad never touch.
+ * Kernels: forward = statistics (one read of u: per-lane Welford, the block's row lanes and then the blocks merged in ascending order
+ *   with Chan's formula) + a one-block finish (mu, rstd, the running update) + apply (hout; it overwrites the LReLU(u) the edge forward
+ *   wrote); eval mode is the apply launch alone.  Backward = column sums of dv and dv * xhat + a one-block finish + apply (G, agg, the
+ *   block partials of grad_b).  No float atomics; every sum runs in an order fixed by (N, H*D, grid): bitwise reproducible.  Plain
+ *   launches on the context's stream, capturable, timed under GAT_K_MISC.
+ * Taps: GAT_TAP_HOUT returns the normalised output; GAT_TAP_G returns G of any layer, recomputed through the two backward launches.
+ * gat_set_batch_norm follows gat_set_norm's state rules: only BEFORE the first gat_params_*, gat_grads_*, gat_set_graph* call (later:
+ *   GAT_E_STATE).  flags == 0 is the default: it ignores eps and momentum and leaves the context exactly as it is.  Unknown bits,
+ *   GAT_BN_SKIP_LAST without GAT_BN_ON, an eps that is not finite and > 0, a momentum outside [0, 1] or not finite: GAT_E_INVALID.
+ *   GAT_E_UNSUPPORTED: together with gat_set_norm(flags != 0) on the same context, in either order (the second call is refused);
+ *   flat_lrelu_index = 1; the experiment library with GAT_DBG set; a destination-range shard (n_table != n_rows or table_row0 != 0:
+ *   refused by the call that sets the graph) and gat_comm_init_* — the column statistics of a shard would need an exchange that is
+ *   not built.
+ * Works with every (H, D) family incl. both generic ones, bf16 storage (the arithmetic, G and agg stay fp32), keep_taps, the residual
+ *   flags, the three regularisers, edge features, readout, pair head, hidden head, all three loss modes, training masks, the phase
+ *   API, gat_step and its graph replay.
+ * gat_algorithmic_bytes (context form): unchanged with the feature off.  On, every layer is priced on the residual route and each
+ *   normalised layer adds to misc 3 * N*HD floats forward (u read twice, hout written) and 6 * N*HD backward (u and g read twice, G and
+ *   agg written; R once more with GAT_RES_LINEAR) in place of the residual route's 4.  gat_algorithmic_bytes_shape prices the model
+ *   without it. */
+enum { GAT_BN_ON = 1, GAT_BN_SKIP_LAST = 2 };
+int gat_set_batch_norm(gat_ctx* ctx, int32_t flags, float eps, float momentum);
+int gat_batch_norm_info(gat_ctx* ctx, int32_t* flags, float* eps, float* momentum);
+/* The statistics, flat [l][H_l*D_l] over all layers, count = sum_l H_l*D_l (a layer GAT_BN_SKIP_LAST leaves out keeps 0 / 1 / 0 / 0).
+ * BATCH_MEAN / BATCH_RSTD: of the last training forward.  set: the two running vectors only (others: GAT_E_INVALID); it writes into
+ * the same buffers, so a captured step graph stays valid.  Both on a context without batch norm: GAT_E_STATE. */
+enum { GAT_BN_RUNNING_MEAN = 0, GAT_BN_RUNNING_VAR = 1, GAT_BN_BATCH_MEAN = 2, GAT_BN_BATCH_RSTD = 3 };
+int gat_batch_norm_stats_get(gat_ctx* ctx, int32_t which, float* host, int64_t count);
+int gat_batch_norm_stats_set(gat_ctx* ctx, int32_t which, const float* host, int64_t count);
+/* The kernels on caller-owned device pointers (stateless; synchronises `stream` before it returns).
+ * forward: u [n_rows][H*D].  training != 0: the statistics of u go to d_mean_rstd [2][H*D] = {mu, rstd} and, unless both are null,
+ *   d_running_mean / d_running_var advance.  training == 0: d_running_mean / d_running_var are what is normalised with (null:
+ *   GAT_E_INVALID), d_mean_rstd is not touched.  d_hout [n_rows][H*D], with is_last [n_rows][D].
+ * backward: d_g [n_rows][H*D] or d_gh [n_rows][gh_stride] (first D floats of a row: the gradient of the mean over heads) is dL/dhout;
+ *   training != 0 reads d_mean_rstd, training == 0 the running pair.  d_res / d_bias: R and b (null: none).  d_G, d_agg [n_rows][H*D]
+ *   (d_agg null: not written); d_grad_gamma / d_grad_beta / d_grad_b [H*D] are ADDED into (null: not formed). */
+int gat_op_batch_norm_forward(const float* d_u, int64_t n_rows, int32_t H, int32_t D, int32_t is_last, const float* d_gamma,
+                              const float* d_beta, float eps, float slope, float momentum, float* d_running_mean, float* d_running_var,
+                              int32_t training, float* d_mean_rstd, float* d_hout, void* stream);
+int gat_op_batch_norm_backward(const float* d_u, const float* d_g, const float* d_gh, int64_t gh_stride, int64_t n_rows, int32_t H, int32_t D,
+                               const float* d_gamma, const float* d_beta, const float* d_mean_rstd, const float* d_running_mean,
+                               const float* d_running_var, float eps, float slope, int32_t training, const float* d_res, const float* d_bias,
+                               float* d_G, float* d_agg, float* d_grad_gamma, float* d_grad_beta, float* d_grad_b, void* stream);
 
 /* ---- edge features in the attention score (beyond the reference; the `edge_dim` argument of PyG's GATv2Conv) ----------------------
  * With edge_dim = Fe > 0 every layer l has a parameter We_l, flat [H_l*D_l][Fe], and every CSR edge j of the context's graph an
