@@ -1,18 +1,19 @@
 """What the batch-normalisation tests share (tests/test_batchnorm.py, test_batchnorm_kernels.py, test_batchnorm_cpu.py): the context
 builder (feature_cases.make_ctx with gat_set_batch_norm in gat_set_norm's place), the seed search against the fp64 model of
-tests/batchnorm_ref.py, the comparison of the four statistics vectors, and the table of the kernel tests with its fp64 numpy model.  A
+tests/step_ref.py (bn=True), the comparison of the four statistics vectors, and the table of the kernel tests with its fp64 numpy model.  A
 plain module: the test modules import it, never each other."""
 import numpy as np
 
 import batchnorm_ref as BR
 import feature_cases as FC
+import head_model as HD
 import parity
 import step_ref as SR
 
 EPS = FC.EPS
 MOMENTUM = 0.1
 MODES = [("bn", False, False), ("bn_res", True, True)]          # (name, GAT_RES_LINEAR, GAT_RES_BIAS)
-GROUPS = FC.GROUPS
+GROUPS = FC.GROUPS[:7]
 TAPS = ["hpre", "hout", "G"]
 STATS = ("running_mean", "running_var", "batch_mean", "batch_rstd")     # GAT_BN_RUNNING_MEAN .. GAT_BN_BATCH_RSTD
 
@@ -42,8 +43,8 @@ def setters(mode, skip_last=False):
     return dict(residual=mode[1:] if mode[1] or mode[2] else None, bn=dict(skip_last=skip_last))
 
 
-def run_model(cfg, g, P, **kw):
-    return BR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, **kw)
+def run_model(cfg, g, P, bn=True, **kw):
+    return SR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, bn=bn, **kw)
 
 
 SEEDS = 400
@@ -64,7 +65,7 @@ def pick_params(orc, cfg, model, clear):
 def pick_case(orc, cfg, g, mode, reg=None, clear=None, **kw):
     """feature_cases.pick_case against the batch-norm model: Wres / b of xavier_wres(ps) where the mode has them, gamma / beta of
     ln_params(ps); seeds keep every non-zero |s| above 1e-5 and |v| above 1e-4 (FC.CLEAR_V, the layer norm's bound).  **kw goes to
-    batchnorm_ref.forward.  -> (W, a, Wo), dict(Wres, b, gamma, beta), outputs."""
+    step_ref.forward.  -> (W, a, Wo), dict(Wres, b, gamma, beta), outputs."""
     _, lin, bias = mode
     keeps, attn, feat = FC.masks(cfg, g, cfg.heads, reg)
 
@@ -266,7 +267,7 @@ def run_kernel_profile(pkg, outdir=None):
     return len(KERNEL_CASES), failures
 
 
-# -- one case per head kind (tests/test_batchnorm.py), against batchnorm_ref.forward with batchnorm_ref.head_of
+# -- one case per head kind (tests/test_batchnorm.py), against step_ref.forward(bn=True) with head_model.head
 FE = 3
 HEAD_CASES = {                                   # name -> (kind, loss, training mask, hidden width, edge features)
     "readout_mean": ("readout", "softmax", False, 0, False),
@@ -309,8 +310,9 @@ def head_case(pkg, orc, name):
         gamma, beta = SR.ln_params(cfg, ps)
         inp = dict(Wres=Wres, b=b, gamma=gamma, beta=beta)
         if fe:
-            inp.update(ea=ea, We=EF.xavier_we(cfg, FE, ps))
-        head = BR.head_of(kind, loss, sup, Wo_h if dh else P[2], mask=mask, graph_ptr=graph_ptr, u=u, v=v, W1=W1, b1=b1)
+            inp.update(ea=ea, We=SR.xavier_we(cfg, FE, ps))
+        head = HD.head(kind, loss, sup, mask, graph_ptr=graph_ptr, u=u, v=v, Wo=Wo_h if dh else P[2], W1=W1, b1=b1, detach_max=False,
+                       smooth_bce=True)
         return inp, run_model(cfg, g, P, **inp, eps=EPS, momentum=MOMENTUM, head=head, **kw)
 
     def clear(r):

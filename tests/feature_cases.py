@@ -16,7 +16,7 @@ from conftest import small_graph
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-GROUPS = "W a Wo Wres b gamma beta".split()          # GAT_PARAM_W .. GAT_PARAM_LN_B, in the ABI's order
+GROUPS = SR.GROUPS                               # the ten parameter groups in the ABI's order; the call sites slice it
 EPS = 1e-5
 
 FAMILIES = [
@@ -158,7 +158,8 @@ def setters(mode, norm=False, skip_last=False):
 def grads(pkg, ctx, groups):
     """The gradient groups named in groups (names of GROUPS)."""
     A = pkg.abi
-    ids = dict(zip(GROUPS, (A.PARAM_W, A.PARAM_A, A.PARAM_WO, A.PARAM_WRES, A.PARAM_B, A.PARAM_LN_G, A.PARAM_LN_B)))
+    ids = dict(zip(GROUPS, (A.PARAM_W, A.PARAM_A, A.PARAM_WO, A.PARAM_WRES, A.PARAM_B, A.PARAM_LN_G, A.PARAM_LN_B, A.PARAM_WE, A.PARAM_HEAD_W,
+                             A.PARAM_HEAD_B)))
     return [ctx.grads_get(ids[k]) for k in groups]
 
 

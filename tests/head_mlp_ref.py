@@ -1,6 +1,6 @@
-"""The fp64 autograd model of a training step with a hidden layer in front of the output head (include/gatv2_abi.h "hidden layer"), on
-top of tests/step_ref.py, tests/readout_ref.py and tests/pair_ref.py the way pair_ref sits on step_ref: those models run with a dummy
-output layer and leave the rows the head reads — hout of the last layer, the pooled rows, the pair rows — attached to the autograd graph;
+"""The fp64 autograd model of a training step with a hidden layer in front of the output head (include/gatv2_abi.h "hidden layer"):
+tests/step_ref.py::forward with the head of tests/head_model.py on the rows the head reads — hout of the last layer, the pooled rows, the
+pair rows — and its hidden layer:
     A = Xin W1^T,   Z1 = act(A + b1),   z = Z1 Wo^T  (Wo [C][Dh])
 and the loss of the case run on top.  Also what tests/test_head_mlp.py and tests/test_head_mlp_cpu.py share: the cases, the test values
 of W1 / b1 / Wo, the seed search, the context builder."""
@@ -9,15 +9,15 @@ import functools
 import numpy as np
 
 import edge_feat_ref as EF
+import head_model as HD
 import loss_ref as LR
 import pair_ref as PR
 import readout_ref as RR
 import step_ref as SR
 
-KINDS = ("node", "readout", "pair_mul", "pair_add")
+KINDS = HD.KINDS
 SOFTMAX, BCE, MSE = PR.SOFTMAX, PR.BCE, PR.MSE
 ACTS = ("relu", "lrelu")
-SLOPE = 0.01                      # GatContext's default negative_slope (the lrelu activation's)
 Y_MIN = RR.Y_MIN                  # a softmax case needs y[label] > Y_MIN for every row that trains (readout_ref: the model's loss clamp)
 A_MIN = 1e-5                      # every |A + b1| entry above this: the bound CLEAR_HPRE puts on h_pre, so that no kink correction is ever
                                   # applied.  The bound sits on the activation's ARGUMENT A + b1, where the kink of act(A + b1) is — not
@@ -28,13 +28,6 @@ FE = RR.FE
 D5_FAMILY = RR.D5_FAMILY
 GRAPH_PTR = RR.GRAPH_PTR
 VARIANTS = ("res_norm_reg", "fe3", "mask", "keep_taps", "bf16")
-GROUPS = ("W", "a", "Wo", "Wres", "b", "gamma", "beta", "We", "W1", "b1")       # GAT_PARAM_W .. GAT_PARAM_HEAD_B, in the ABI's order
-
-
-def act(t, name):
-    """torch: ReLU, or LeakyReLU with SLOPE; at exactly 0 the derivative is the slope branch's (torch's convention for both)."""
-    import torch
-    return torch.relu(t) if name == "relu" else torch.nn.functional.leaky_relu(t, SLOPE)
 
 
 def head_values(d_last, dh, c, seed=0):
@@ -48,65 +41,14 @@ def head_values(d_last, dh, c, seed=0):
     return W1, b1, Wo
 
 
-def head_input(out, kind, graph_ptr=None, u=None, v=None):
-    """The rows the head reads without the hidden layer, attached to the node model's autograd graph."""
-    X = out["hout"][-1]
-    if kind == "node":
-        return X
-    if kind == "readout":
-        return RR.pool(X, graph_ptr, "mean")[0]
-    return PR.gather(X, u, v, "mul" if kind == "pair_mul" else "add")
-
-
-def head_loss(z, loss, sup, mask):
-    """The loss of the case on the logits z [R][C] (torch fp64) -> (loss sum, y numpy, per-row loss numpy or None): softmax +
-    cross-entropy of step_ref.forward, BCE in pair_ref.forward's smooth form, MSE of loss_ref.losses."""
-    import torch
-    R = z.shape[0]
-    keep = np.ones(R, bool) if mask is None else np.asarray(mask, bool)
-    if loss == SOFTMAX:
-        # the row maximum stays attached: with the 1e-8 guard below y depends on it (by 1e-8 of itself), and a detached maximum leaves
-        # autograd that far from the function's derivative — nothing at the 1e-4 bars, but visible to central differences at 1e-8
-        ez = torch.exp(z - z.max(dim=1, keepdim=True).values)
-        y = ez / (ez.sum(1, keepdim=True) + 1e-8)
-        lab = torch.from_numpy(np.asarray(sup)).long()
-        per = -torch.log(torch.clamp(y[torch.arange(R), lab], min=1e-12))
-        return (per * torch.from_numpy(keep.astype(np.float64))).sum(), y.detach().numpy(), per.detach().numpy()
-    if loss == BCE:
-        on = LR.contributes(sup, mask)
-        t = torch.from_numpy(np.where(on, np.nan_to_num(np.asarray(sup, np.float64)), 0.0))
-        per = torch.nn.functional.binary_cross_entropy_with_logits(z, t, reduction="none")
-        return (per * torch.from_numpy(on.astype(np.float64))).sum(), torch.sigmoid(z).detach().numpy(), None
-    total, y = LR.losses(z, sup, mask, loss)
-    return total, y.detach().numpy(), None
-
-
-def forward(cfg, g, kind, loss, sup, P2, W1, b1, Wo, act_name="relu", mask=None, graph_ptr=None, u=None, v=None, ea=None, We=None, **kw):
+def forward(cfg, g, kind, loss, sup, P2, W1, b1, Wo, act_name="relu", mask=None, graph_ptr=None, u=None, v=None, **kw):
     """fp64 step with the hidden layer.  g: the graph dict of tests/feature_cases.py; kind: one of KINDS (readout: mean over graph_ptr;
-    pairs: u, v); loss / sup / mask as in pair_ref.forward, over the head's rows; P2 = (W, a); W1 [Dh][D_last], b1 [Dh], Wo [C][Dh];
-    ea / We: edge features; **kw: step_ref.forward's keywords.  -> the node model's dict with Wo, W1, b1 (leaves), xin (grad retained), A
-    (numpy), z1 (grad retained), loss, y, loss_per_row."""
-    import torch
-    dummy = np.zeros(g["n"], np.int64)
-    P = (P2[0], P2[1], np.zeros(cfg.num_classes * cfg.outdims[-1], np.float32))       # the node model's own output layer is not used
-    if ea is not None:
-        out = EF.forward(cfg, g["row_ptr"], g["col_idx"], dummy, g["x"], *P, ea=ea, We=We, **kw)
-    else:
-        out = SR.forward(cfg, g["row_ptr"], g["col_idx"], dummy, g["x"], *P, **kw)
-        out["We"] = None
-    xin = head_input(out, kind, graph_ptr, u, v)
-    if xin.requires_grad:
-        xin.retain_grad()
-    leaf = lambda a: torch.from_numpy(np.asarray(a, np.float32).astype(np.float64).reshape(-1)).requires_grad_(True)      # flat, as the ABI's groups
-    W1t, b1t, Wot = leaf(W1), leaf(b1), leaf(Wo)
-    dh = b1t.shape[0]
-    A = xin @ W1t.view(dh, -1).t()
-    z1 = act(A + b1t, act_name)
-    z1.retain_grad()
-    z = z1 @ Wot.view(-1, dh).t()
-    out["loss"], out["y"], out["loss_per_row"] = head_loss(z, loss, sup, mask)
-    out.update(Wo=Wot, W1=W1t, b1=b1t, xin=xin, A=A.detach().numpy(), pre=(A + b1t).detach().numpy(), z1=z1)
-    return out
+    pairs: u, v); loss / sup / mask as in pair_ref.forward, over the head's rows, the softmax's row maximum attached (head_model.loss
+    says why); P2 = (W, a); W1 [Dh][D_last], b1 [Dh], Wo [C][Dh]; **kw: step_ref.forward's keywords.  -> the model's dict with Wo, W1,
+    b1 (leaves), xin (grad retained), A and pre (numpy), z1 (grad retained), loss, y, loss_per_row."""
+    head = HD.head(kind, loss, sup, mask, graph_ptr=graph_ptr, u=u, v=v, Wo=Wo, W1=W1, b1=b1, act_name=act_name, detach_max=False,
+                   smooth_bce=True)
+    return SR.forward(cfg, g["row_ptr"], g["col_idx"], None, g["x"], P2[0], P2[1], None, head=head, **kw)
 
 
 def nonzero_min(a):
@@ -183,7 +125,7 @@ def _case_inputs(fam, variant, kind, loss, dh, act_name, n_rand=None):
     def model(ps, P):
         inp = {}
         if variant == "fe3":
-            inp = dict(ea=ea, We=EF.xavier_we(cfg, FE, ps))
+            inp = dict(ea=ea, We=SR.xavier_we(cfg, FE, ps))
         elif variant == "res_norm_reg":
             Wres, b = SR.xavier_wres(cfg, ps)
             gamma, beta = SR.ln_params(cfg, ps)

@@ -1,8 +1,7 @@
 """The references of the BCE / MSE output heads (include/gatv2_abi.h "loss modes of the output head"; TEST INFRASTRUCTURE).
 
-1. The fp64 autograd model of a whole step, on top of tests/step_ref.py the way tests/readout_ref.py is: the node model runs with dummy
-   labels (through readout_ref.forward's pooling when a readout is on), the head's input rows X — still attached to the autograd graph —
-   go through z = X Woᵀ and one of the two losses, with the NaN entries and the rows outside the mask removed from the sum.
+1. The fp64 autograd model of a whole step: tests/step_ref.py::forward with the head of tests/head_model.py on the node rows or the
+   pooled rows X, z = X Woᵀ and one of the two losses (max-form BCE), the NaN entries and the rows outside the mask removed from the sum.
 2. A plain numpy fp64 reference of the head alone, in the style of tests/head_ref.py: y, l, dz, gH, gradWo from the head's own inputs,
    and `undecided`: the BCE entries whose |z| is below the fp32 rounding bound of that logit (their prediction z > 0 may come out
    either way in fp32) — except where the bound itself is 0: all products are exactly 0 there and z = 0 on any path.
@@ -15,56 +14,21 @@ from typing import NamedTuple
 
 import numpy as np
 
-import edge_feat_ref as EF
+import head_model as HD
 import readout_ref as RR
 import step_ref as SR
-
-BCE, MSE = "bce", "mse"
+from head_model import BCE, MSE, contributes
 MODES = (BCE, MSE)
 MISSING = 0.2
 
 
-def contributes(T, mask=None):
-    """[R][C] bool: the entry is present (not NaN) and its row trains."""
-    T = np.asarray(T)
-    rows = np.ones(T.shape[0], bool) if mask is None else np.asarray(mask) != 0
-    return ~np.isnan(T) & rows[:, None]
-
-
-def losses(z, T, mask, mode):
-    """z [R][C] torch fp64 -> (loss sum over the contributing entries (autograd through z), y)."""
-    import torch
-    on = contributes(T, mask)
-    t = torch.from_numpy(np.where(on, np.nan_to_num(np.asarray(T, np.float64)), 0.0))
-    w = torch.from_numpy(on.astype(np.float64))
-    if mode == BCE:
-        per = torch.clamp(z, min=0) - t * z + torch.log1p(torch.exp(-z.abs()))
-        y = torch.sigmoid(z)
-    else:
-        per = (z - t) ** 2
-        y = z
-    return (per * w).sum(), y
-
-
-def forward(cfg, g, T, mode, P, mask=None, graph_ptr=None, readout=None, ea=None, We=None, **kw):
+def forward(cfg, g, T, mode, P, mask=None, graph_ptr=None, readout=None, **kw):
     """fp64 step in loss mode `mode`.  g: the graph dict of tests/feature_cases.py (its labels are not used); T [rows][C] float with NaN
-    = missing, mask [rows] or None — rows are nodes, or the graphs of graph_ptr when readout is "mean" / "sum" / "max"; ea / We: edge
-    features; **kw: step_ref.forward's keywords.  -> the node model's dict with loss, y (numpy), z (numpy), X (the head's input rows)."""
-    if readout is not None:
-        G = len(graph_ptr) - 1
-        out = RR.forward(cfg, g, graph_ptr, readout, np.zeros(G, np.int64), P, ea=ea, We=We, **kw)
-        X = out["pooled"]
-    else:
-        dummy = np.zeros(g["n"], np.int64)
-        if ea is not None:
-            out = EF.forward(cfg, g["row_ptr"], g["col_idx"], dummy, g["x"], *P, ea=ea, We=We, **kw)
-        else:
-            out = SR.forward(cfg, g["row_ptr"], g["col_idx"], dummy, g["x"], *P, **kw)
-            out["We"] = None
-        X = out["hout"][-1]
-    z = X @ out["Wo"].view(cfg.num_classes, cfg.outdims[-1]).t()
-    out["loss"], y = losses(z, T, mask, mode)
-    out["y"], out["z"], out["X"] = y.detach().numpy(), z.detach().numpy(), X
+    = missing, mask [rows] or None — rows are nodes, or the graphs of graph_ptr when readout is "mean" / "sum" / "max"; **kw:
+    step_ref.forward's keywords.  -> the model's dict with loss, y (numpy), z (numpy), X (the head's input rows)."""
+    head = HD.head("node" if readout is None else "readout", mode, T, mask, graph_ptr=graph_ptr, pool_mode=readout)
+    out = SR.forward(cfg, g["row_ptr"], g["col_idx"], None, g["x"], *P, head=head, **kw)
+    out["X"] = out["xin"]
     return out
 
 
@@ -282,9 +246,6 @@ def shard_worker(rank, world, outdir, shm):
     grads = np.concatenate([ctx.grads_get(k) for k in range(3)])
     np.savez(os.path.join(outdir, f"r{rank}.npz"), loss=loss, correct=correct, grads=grads)
     ctx.close()
-
-
-GROUP_NAMES = ("W", "a", "Wo", "Wres", "b", "gamma", "beta", "We")
 
 
 def grads_min(ref):

@@ -1,20 +1,20 @@
-"""The fp64 autograd model of a training step with a pair head (include/gatv2_abi.h "pair head"), on top of tests/step_ref.py
-(tests/edge_feat_ref.py with edge features) the way tests/readout_ref.py is: the node model runs with dummy node labels, its last hout X
-— still attached to the autograd graph — is gathered into the pair rows
+"""The fp64 autograd model of a training step with a pair head (include/gatv2_abi.h "pair head"): tests/step_ref.py::forward with the
+pair head of tests/head_model.py — the last hout X, still attached to the autograd graph, is gathered into the pair rows
     mul:  Q[p] = X[u_p] * X[v_p]        add:  Q[p] = X[u_p] + X[v_p]
-and the head of the chosen loss mode (softmax + cross-entropy of step_ref.forward, MSE of loss_ref.losses, BCE in a smooth form) runs on the P rows.
+and the head of the chosen loss mode (softmax + cross-entropy, MSE, BCE in its smooth form) runs on the P rows.
 Also what tests/test_pair_head.py and tests/test_pair_cpu.py share: the pair list, the cases, the seed search, the context builder."""
 import functools
 
 import numpy as np
 
 import edge_feat_ref as EF
+import head_model as HD
 import loss_ref as LR
 import readout_ref as RR
 import step_ref as SR
 
 MODES = ("mul", "add")
-SOFTMAX, BCE, MSE = "softmax", LR.BCE, LR.MSE
+SOFTMAX, BCE, MSE = HD.SOFTMAX, HD.BCE, HD.MSE
 Y_MIN = RR.Y_MIN          # a softmax case needs y[label] > Y_MIN for every pair that trains (readout_ref: the model's loss clamp)
 FE = RR.FE
 D5_FAMILY = RR.D5_FAMILY  # D_last = 5: the scalar-load path of the gather and the scatter
@@ -42,46 +42,18 @@ def pair_list(n, seed=17, hub=HUB, n_hub=262, n_rand=136):
     return u.astype(np.int32), v.astype(np.int32)
 
 
-def forward(cfg, g, u, v, mode, loss, sup, P, mask=None, ea=None, We=None, **kw):
+def forward(cfg, g, u, v, mode, loss, sup, P, mask=None, **kw):
     """fp64 step with a pair head.  g: the graph dict of tests/feature_cases.py (its node labels are not used); u, v [P]; loss: SOFTMAX
-    (sup = labels [P]), BCE or MSE (sup = targets [P][C], NaN = missing); mask [P] bool or None (pairs outside it: no loss); ea / We: edge
-    features; **kw: step_ref.forward's keywords.  -> the node model's dict with loss (over the pairs), loss_per_pair, y [P][C], paired (Q,
-    grad retained)."""
-    import torch
-    dummy = np.zeros(g["n"], np.int64)
-    if ea is not None:
-        out = EF.forward(cfg, g["row_ptr"], g["col_idx"], dummy, g["x"], *P, ea=ea, We=We, **kw)
-    else:
-        out = SR.forward(cfg, g["row_ptr"], g["col_idx"], dummy, g["x"], *P, **kw)
-        out["We"] = None
-    Q = gather(out["hout"][-1], u, v, mode)
-    if Q.requires_grad:
-        Q.retain_grad()
-    n_pairs = Q.shape[0]
-    z = Q @ out["Wo"].view(cfg.num_classes, cfg.outdims[-1]).t()
-    keep = np.ones(n_pairs, bool) if mask is None else np.asarray(mask, bool)
+    (sup = labels [P]), BCE (smooth form: head_model.loss says why) or MSE (sup = targets [P][C], NaN = missing); mask [P] bool or None
+    (pairs outside it: no loss); **kw: step_ref.forward's keywords.  -> the model's dict with loss (over the pairs), y [P][C], paired
+    (Q, grad retained) and, for SOFTMAX, loss_per_pair and y_label_min."""
+    out = SR.forward(cfg, g["row_ptr"], g["col_idx"], None, g["x"], *P, **kw,
+                     head=HD.head("pair_" + mode, loss, sup, mask, u=u, v=v, smooth_bce=True))
+    out["paired"] = out["xin"]
     if loss == SOFTMAX:
-        ez = torch.exp(z - z.max(dim=1, keepdim=True).values.detach())
-        y = ez / (ez.sum(1, keepdim=True) + 1e-8)
-        lab = torch.from_numpy(np.asarray(sup)).long()
-        per = -torch.log(torch.clamp(y[torch.arange(n_pairs), lab], min=1e-12))
-        out["loss_per_pair"] = per.detach().numpy()
-        out["loss"] = (per * torch.from_numpy(keep.astype(np.float64))).sum()
-        out["y"] = y.detach().numpy()
-        out["y_label_min"] = float(out["y"][np.arange(n_pairs), np.asarray(sup)][keep].min())
-    elif loss == BCE:
-        # not loss_ref.losses: its max(z,0) - t z + log1p(exp(-|z|)) has the autograd subgradient 1 - t at z == 0 exactly, where the
-        # derivative is sigmoid(0) - t = 0.5 - t (the header's dz = y - t).  A pair row of exact zeros — MUL with an endpoint whose row is
-        # 0, as the graph's empty row is — has z == 0, and its gQ reaches the G taps compared here.  The same loss, smooth form:
-        on = LR.contributes(sup, mask)
-        t = torch.from_numpy(np.where(on, np.nan_to_num(np.asarray(sup, np.float64)), 0.0))
-        per = torch.nn.functional.binary_cross_entropy_with_logits(z, t, reduction="none")
-        out["loss"] = (per * torch.from_numpy(on.astype(np.float64))).sum()
-        out["y"] = torch.sigmoid(z).detach().numpy()
-    else:
-        out["loss"], y = LR.losses(z, sup, mask, loss)
-        out["y"] = y.detach().numpy()
-    out["paired"] = Q
+        keep = np.ones(len(out["y"]), bool) if mask is None else np.asarray(mask, bool)
+        out["loss_per_pair"] = out["loss_per_row"]
+        out["y_label_min"] = float(out["y"][np.arange(len(keep)), np.asarray(sup)][keep].min())
     return out
 
 
@@ -142,8 +114,8 @@ def pick(FC, orc, cfg, g, u, v, mode, loss, labels, mask=None, variant="plain", 
         ea = EF.edge_attrs(g, FE)
 
         def model(ps, P):
-            inp = dict(ea=ea, We=EF.xavier_we(cfg, FE, ps))
-            return inp, EF.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, **inp, bf16_pl=bf16)
+            inp = dict(ea=ea, We=SR.xavier_we(cfg, FE, ps))
+            return inp, SR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, **inp, bf16_pl=bf16)
         P, inp, ref = FC.pick_params(orc, cfg, model, with_clamp(FC.CLEAR_HPRE, u, v, mode, loss, labels, mask))
         return P, inp, ref["seed"]
     if variant == "res_norm_reg":

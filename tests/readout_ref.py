@@ -1,14 +1,15 @@
-"""The fp64 autograd model of a training step with a graph-level readout (include/gatv2_abi.h "graph-level readout"), on top of
-tests/step_ref.py (tests/edge_feat_ref.py with edge features): the node model runs with dummy node labels, its last hout — still
-attached to the autograd graph — is pooled per graph,
+"""The fp64 autograd model of a training step with a graph-level readout (include/gatv2_abi.h "graph-level readout"):
+tests/step_ref.py::forward with the readout head of tests/head_model.py — the last hout, still attached to the autograd graph, is
+pooled per graph,
     sum:  P[g] = sum_n X[n]        mean: P[g] = (sum_n X[n]) / cnt_g        max: P[g][d] = max_n X[n][d], the FIRST row attaining it
-(an empty graph: P[g] = 0, no gradient), and the head of step_ref.forward runs on the G pooled rows with the graph labels.
+(an empty graph: P[g] = 0, no gradient), and the softmax + cross-entropy runs on the G pooled rows with the graph labels.
 Also what tests/test_readout.py and tests/test_readout_cpu.py share: the cases, the seed search, the context builder."""
 import functools
 
 import numpy as np
 
 import edge_feat_ref as EF
+import head_model as HD
 import step_ref as SR
 
 MODES = ("mean", "sum", "max")
@@ -71,35 +72,19 @@ def pool_gap(X, graph_ptr, mode):
     return gap
 
 
-def forward(cfg, g, graph_ptr, mode, glabels, P, gmask=None, ea=None, We=None, **kw):
+def forward(cfg, g, graph_ptr, mode, glabels, P, gmask=None, **kw):
     """fp64 step with readout.  g: the graph dict of tests/feature_cases.py (its node labels are not used), glabels [G], gmask [G] bool
-    or None (graphs outside it: no loss), ea / We: edge features (edge_feat_ref.forward), **kw: step_ref.forward's keywords.
-    -> the node model's dict with loss (over the graphs), y [G][C], pooled (grad retained), argmax, pool_gap, x_max = max|X|."""
-    import torch
-    dummy = np.zeros(g["n"], np.int64)
-    if ea is not None:
-        out = EF.forward(cfg, g["row_ptr"], g["col_idx"], dummy, g["x"], *P, ea=ea, We=We, **kw)
-    else:
-        out = SR.forward(cfg, g["row_ptr"], g["col_idx"], dummy, g["x"], *P, **kw)
-        out["We"] = None
-    X = out["hout"][-1]
-    pooled, arg = pool(X, graph_ptr, mode)
-    if pooled.requires_grad:
-        pooled.retain_grad()
-    G = pooled.shape[0]
-    z = pooled @ out["Wo"].view(cfg.num_classes, cfg.outdims[-1]).t()
-    ez = torch.exp(z - z.max(dim=1, keepdim=True).values.detach())
-    y = ez / (ez.sum(1, keepdim=True) + 1e-8)
-    lab = torch.from_numpy(np.asarray(glabels)).long()
-    per = -torch.log(torch.clamp(y[torch.arange(G), lab], min=1e-12))
+    or None (graphs outside it: no loss), **kw: step_ref.forward's keywords.
+    -> the model's dict with loss (over the graphs), y [G][C], pooled (grad retained), argmax, pool_gap, x_max = max|X|."""
+    out = SR.forward(cfg, g["row_ptr"], g["col_idx"], None, g["x"], *P, **kw,
+                     head=HD.head("readout", HD.SOFTMAX, glabels, gmask, graph_ptr=graph_ptr, pool_mode=mode))
+    X = out["hout"][-1].detach()
+    G = len(graph_ptr) - 1
     keep = np.ones(G, bool) if gmask is None else np.asarray(gmask, bool)
-    out["loss_per_graph"] = per.detach().numpy()
-    out["loss"] = (per * torch.from_numpy(keep.astype(np.float64))).sum()
-    out["y"] = y.detach().numpy()
+    out["pooled"], out["loss_per_graph"], out["argmax"] = out["xin"], out["loss_per_row"], pool(X, graph_ptr, mode)[1]
     out["y_label_min"] = float(out["y"][np.arange(G), np.asarray(glabels)][keep].min())
-    out["pooled"], out["argmax"] = pooled, arg
-    out["pool_gap"] = pool_gap(X.detach().numpy(), graph_ptr, mode)
-    out["x_max"] = float(X.detach().abs().max())
+    out["pool_gap"] = pool_gap(X.numpy(), graph_ptr, mode)
+    out["x_max"] = float(X.abs().max())
     return out
 
 
@@ -175,7 +160,7 @@ BOUNDARY_SEEDS = (584, 5897)
 
 def grads_min(ref):
     """Smallest max-abs over the model's parameter gradients (after loss.backward())."""
-    return min(float(ref[k].grad.abs().max()) for k in ("W", "a", "Wo", "Wres", "b", "gamma", "beta", "We") if ref.get(k) is not None)
+    return min(float(ref[k].grad.abs().max()) for k in SR.GROUPS[:8] if ref.get(k) is not None)
 
 
 def pick_boundary(FC, orc, cfg, g, graph_ptr, mode, glabels):
@@ -196,13 +181,13 @@ def pick(FC, orc, cfg, g, graph_ptr, mode, glabels, gmask=None, variant="plain",
     """The parameter seed of a case: the first of 40 whose node model is clear of the LeakyReLU kinks at the bounds of the feature's own
     tests AND, for MAX, has a clear winner in every (graph, column), AND keeps every trained graph off the loss clamp.  The kink and MAX
     conditions do not depend on the labels, so the search runs on the node model (FC.pick_case; edge features: FC.pick_params on
-    edge_feat_ref.forward).  -> (W, a, Wo), dict of the other inputs, seed."""
+    step_ref.forward).  -> (W, a, Wo), dict of the other inputs, seed."""
     if variant == "fe3":
         ea = EF.edge_attrs(g, FE)
 
         def model(ps, P):
-            inp = dict(ea=ea, We=EF.xavier_we(cfg, FE, ps))
-            return inp, EF.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, **inp, bf16_pl=bf16)
+            inp = dict(ea=ea, We=SR.xavier_we(cfg, FE, ps))
+            return inp, SR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, **inp, bf16_pl=bf16)
         P, inp, ref = FC.pick_params(orc, cfg, model, with_gap(FC.CLEAR_HPRE, graph_ptr, mode, glabels, gmask))
         return P, inp, ref["seed"]
     if variant == "res_norm_reg":

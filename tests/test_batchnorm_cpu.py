@@ -1,6 +1,6 @@
 """Batch normalisation without a GPU (include/gatv2_abi.h "batch normalisation"): the new ABI symbols, the fp64 model of
-tests/batchnorm_ref.py pinned to torch.nn.BatchNorm1d (normalisation, gradients, running statistics; training and eval; a momentum other
-than 0.1; N = 1 and 2) and to tests/step_ref.py with the feature off, the Welford / Chan merge the kernels use against the two-pass
+tests/step_ref.py (bn=True) pinned to torch.nn.BatchNorm1d (normalisation, gradients, running statistics; training and eval; a momentum other
+than 0.1; N = 1 and 2) and to tests/torch_ref.py with nothing normalised, the Welford / Chan merge the kernels use against the two-pass
 variance, the kernel tests' numpy model against the same module, and — a condition, not a skip — a parameter seed clear of the LeakyReLU
 kinks for the cases tests/test_batchnorm.py runs."""
 import ctypes
@@ -118,22 +118,23 @@ def test_two_rows_and_one_row(orc):
     assert np.abs(ref["batch_rstd"] - 1 / np.sqrt(1e-5)).max() <= 1e-9
 
 
-def test_off_is_step_ref(orc):
-    """bn=False (layer norm) and no norm at all: the model is step_ref.forward, value for value; skip_last leaves the last layer alone."""
+def test_off_is_the_plain_model_and_skip_last_leaves_the_last_layer_alone(orc):
+    """bn=True without gamma / beta normalises nothing: the model is tests/torch_ref.py's.  (With them it is held to the recorded forms
+    bn_* of tests/test_step_ref_cpu.py, the layer norm behind bn=False to the forms norm_*.)  skip_last leaves the last layer alone."""
+    import torch_ref
     g = _graph(2)
     cfg = orc.Config([4, 2], [4, 8], g["f"], g["c"])
     P = orc.xavier_params(cfg, 2)
-    Wres, b = SR.xavier_wres(cfg, 2)
     gamma, beta = SR.ln_params(cfg, 2)
-    for kw in (dict(), dict(Wres=Wres, b=b), dict(gamma=gamma, beta=beta, Wres=Wres, b=b), dict(gamma=gamma, beta=beta, skip_last=True)):
-        a = FC.run_model(cfg, g, P, **kw)
-        c = BC.run_model(cfg, g, P, bn=False, **kw)
-        a["loss"].backward(); c["loss"].backward()
-        assert a["loss"].item() == c["loss"].item()
-        for l in range(2):
-            assert (a["hout"][l] == c["hout"][l]).all() and (a["hpre"][l].grad == c["hpre"][l].grad).all()
-        for k in ("W", "a", "Wo"):
-            assert (a[k].grad == c[k].grad).all()
+    a = torch_ref.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P)
+    c = BC.run_model(cfg, g, P)
+    a["loss"].backward(); c["loss"].backward()
+    assert abs(a["loss"].item() - c["loss"].item()) <= 1e-12 * abs(a["loss"].item())
+    for l in range(2):
+        assert (a["hpre"][l] - c["hpre"][l]).abs().max().item() <= 1e-12
+    for k in ("W", "a", "Wo"):
+        assert (a[k].grad - c[k].grad).abs().max().item() <= 1e-12 * max(1.0, a[k].grad.abs().max().item())
+    assert (c["batch_mean"] == 0).all() and (c["running_var"] == 1).all()
     s = BC.run_model(cfg, g, P, gamma=gamma, beta=beta, skip_last=True)
     s["loss"].backward()
     o = SR.ln_offsets(cfg)

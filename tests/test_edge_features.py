@@ -1,5 +1,5 @@
 """Edge features in the attention score on the GPU (include/gatv2_abi.h "edge features"): parity of every dispatcher family and every
-fast-path shape against the fp64 model of tests/edge_feat_ref.py, DropEdge rows, off is off, We = 0, the step paths against each other,
+fast-path shape against the fp64 model of tests/step_ref.py, DropEdge rows, off is off, We = 0, the step paths against each other,
 the optimizer, shards, error codes.
 
 Each parity case is one context and one step on parity_graph of tests/feature_cases.py (150 nodes, 700 edges + a hub row of 300
@@ -18,6 +18,7 @@ import dropedge_ref as E
 import edge_feat_ref as EF
 import feature_cases as FC
 import parity
+import step_ref as SR
 from feature_cases import FAMILIES, REG
 
 pytestmark = pytest.mark.gpu
@@ -40,7 +41,7 @@ def test_families_against_fp64(pkg, orc, name, heads, outdims, kw, fe, reg):
     P, inp, ref = EF.pick(FC, orc, cfg, g, fe, reg, bf16=bf16)
     ref["loss"].backward()
     with EF.make_ctx(pkg, g, heads, outdims, P, fe, **inp, reg=reg, **kw) as ctx:
-        assert ctx.param_count(A.PARAM_WE) == EF.we_offsets(cfg, fe)[-1]
+        assert ctx.param_count(A.PARAM_WE) == SR.we_offsets(cfg, fe)[-1]
         loss, _ = ctx.step()
         compare_all(pkg, ctx, g, cfg, ref, loss, tol)
         if kw.get("keep_taps"):
@@ -94,8 +95,8 @@ def test_dropedge_rows_and_dropped_edges(pkg, orc):
     gr = dict(g, row_ptr=rp, col_idx=ci)
     ea = inp["ea"]
     P, inp, ref = FC.pick_params(orc, cfg, lambda ps, PP: (
-        dict(We=EF.xavier_we(cfg, fe, ps)),
-        EF.forward(cfg, rp, ci, g["labels"], g["x"], *PP, ea=ea[keep], We=EF.xavier_we(cfg, fe, ps))), FC.CLEAR_HPRE)
+        dict(We=SR.xavier_we(cfg, fe, ps)),
+        SR.forward(cfg, rp, ci, g["labels"], g["x"], *PP, ea=ea[keep], We=SR.xavier_we(cfg, fe, ps))), FC.CLEAR_HPRE)
     ref["loss"].backward()
     with EF.make_ctx(pkg, g, heads, outdims, P, fe, ea=ea, **inp) as ctx:      # the FULL graph and the FULL attribute rows
         ctx.set_dropout(0.0, 0.0, seed=FC.ROWS_SEED)
@@ -149,7 +150,7 @@ def test_zero_we_is_the_context_without_the_feature(pkg, orc, kw):
     cfg = orc.Config(heads, outdims, g["f"], g["c"])
     P = orc.xavier_params(cfg, 3)
     with EF.make_ctx(pkg, g, heads, outdims, P, 0, touch=False, **kw) as a, \
-            EF.make_ctx(pkg, g, heads, outdims, P, fe, ea=EF.edge_attrs(g, fe), We=np.zeros(EF.we_offsets(cfg, fe)[-1], np.float32), **kw) as b:
+            EF.make_ctx(pkg, g, heads, outdims, P, fe, ea=EF.edge_attrs(g, fe), We=np.zeros(SR.we_offsets(cfg, fe)[-1], np.float32), **kw) as b:
         ra, rb = a.step(), b.step()
         assert ra == rb
         for l in range(2):
@@ -166,7 +167,7 @@ def test_paths_agree(pkg, orc):
     heads, outdims, fe = [8, 8], [8, 8], 3
     cfg = orc.Config(heads, outdims, g["f"], g["c"])
     P = orc.xavier_params(cfg, 3)
-    ea, We = EF.edge_attrs(g, fe), EF.xavier_we(cfg, fe, 3)
+    ea, We = EF.edge_attrs(g, fe), SR.xavier_we(cfg, fe, 3)
 
     def new():
         return EF.make_ctx(pkg, g, heads, outdims, P, fe, ea=ea, We=We)
@@ -184,7 +185,7 @@ def test_paths_agree(pkg, orc):
         assert np.abs(g1[A.PARAM_WE]).max() > 0
         lf = fb.forward(); fb.backward()
         gf = grads(fb)
-        for name, x, y in zip(FC.GROUPS + ["We"], g1, gf):
+        for name, x, y in zip(FC.GROUPS[:8], g1, gf):
             if y.size:
                 parity.record(f"step vs forward+backward: {name}", parity.rel_err(x, y), 0.0)
         assert lf == l1 and same(g1, gf)
@@ -346,13 +347,13 @@ SNIPPET = """
 import sys, numpy as np
 sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
 import __graft_entry__ as entry
-import edge_feat_ref as EF, feature_cases as FC
+import edge_feat_ref as EF, feature_cases as FC, step_ref as SR
 pkg = entry.load_package(); orc = entry.load_oracle(); A = pkg.abi
 g = FC.make_graph(2)
 cfg = orc.Config([8, 8], [8, 8], g["f"], g["c"])
 P = orc.xavier_params(cfg, 3)
 try:
-    with EF.make_ctx(pkg, g, [8, 8], [8, 8], P, 3, ea=EF.edge_attrs(g, 3), We=EF.xavier_we(cfg, 3, 3)) as ctx:
+    with EF.make_ctx(pkg, g, [8, 8], [8, 8], P, 3, ea=EF.edge_attrs(g, 3), We=SR.xavier_we(cfg, 3, 3)) as ctx:
         loss = ctx.forward()
         ctx.backward()
         np.save({out!r}, np.concatenate([ctx.grads_get(k) for k in A.PARAM_GROUPS]))

@@ -1,5 +1,5 @@
-"""Edge features without a GPU (include/gatv2_abi.h "edge features"): the fp64 model of tests/edge_feat_ref.py pinned to
-tests/step_ref.py where the feature is absent, gradWe against central finite differences, the new ABI constants and symbols, the shard
+"""Edge features without a GPU (include/gatv2_abi.h "edge features"): the edge term of the fp64 model of tests/step_ref.py: zero
+weights against the model without them (and tests/torch_ref.py), gradWe against central finite differences, the new ABI constants and symbols, the shard
 and synth helpers, and — a condition, not a skip — a parameter seed clear of the LeakyReLU kinks among the first 40 for every parity
 case tests/test_edge_features.py runs."""
 import ctypes
@@ -12,6 +12,7 @@ import pytest
 import edge_feat_ref as EF
 import feature_cases as FC
 import step_ref as SR
+import torch_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "graph-attention-network-gatv2-_amd", "train_edge")
@@ -31,27 +32,35 @@ def _inputs(orc, g, cfg, reg, res_norm, ps=3):
 
 
 @pytest.mark.parametrize("name,reg,res_norm", FORMS, ids=[f[0] for f in FORMS])
-def test_absent_feature_is_step_ref_exactly(orc, name, reg, res_norm):
+def test_zero_edge_weights_are_the_model_without_the_term(orc, name, reg, res_norm):
+    """ea with We = 0 is the model without the arguments, value for value, and in its plain form that model is tests/torch_ref.py's.
+    (With a non-zero We the model is held to the recorded forms edge_* of tests/test_step_ref_cpu.py.)"""
     g = FC.host_graph(1)
     cfg = orc.Config([4, 2], [4, 8], g["f"], g["c"])
     P, kw = _inputs(orc, g, cfg, reg, res_norm)
     want = FC.run_model(cfg, g, P, **kw)
     want["loss"].backward()
     fe = 3
-    ea = EF.edge_attrs(g, fe)
-    groups = [k for k in FC.GROUPS if want[k] is not None]
-    assert len(groups) == (7 if res_norm else 3)
-    for e, We in ((None, None), (ea, np.zeros(EF.we_offsets(cfg, fe)[-1], np.float32))):
-        got = EF.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, ea=e, We=We, **kw)
-        assert got["loss"].item() == want["loss"].item()
-        assert got["s_min"] == want["s_min"] and got["hpre_min"] == want["hpre_min"] and got["v_min"] == want["v_min"]
-        got["loss"].backward()
+    groups = [k for k in FC.GROUPS[:7] if want[k] is not None]
+    assert len(groups) == (7 if res_norm else 3) and want["We"] is None
+    got = FC.run_model(cfg, g, P, ea=EF.edge_attrs(g, fe), We=np.zeros(SR.we_offsets(cfg, fe)[-1], np.float32), **kw)
+    assert got["loss"].item() == want["loss"].item()
+    assert got["s_min"] == want["s_min"] and got["hpre_min"] == want["hpre_min"] and got["v_min"] == want["v_min"]
+    got["loss"].backward()
+    for k in groups:
+        assert np.array_equal(got[k].grad.numpy(), want[k].grad.numpy()), k
+    for l in range(cfg.L):
+        assert np.array_equal(got["hpre"][l].detach().numpy(), want["hpre"][l].detach().numpy())
+        assert np.array_equal(got["alpha"][l], want["alpha"][l])
+    assert got["We"] is not None
+    if name == "plain":
+        ref = torch_ref.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P)
+        ref["loss"].backward()
+        assert abs(got["loss"].item() - ref["loss"].item()) <= 1e-12 * abs(ref["loss"].item())
+        for x, y in zip(got["hpre"], ref["hpre"]):
+            assert (x - y).abs().max().item() <= 1e-12
         for k in groups:
-            assert np.array_equal(got[k].grad.numpy(), want[k].grad.numpy()), k
-        for l in range(cfg.L):
-            assert np.array_equal(got["hpre"][l].detach().numpy(), want["hpre"][l].detach().numpy())
-            assert np.array_equal(got["alpha"][l], want["alpha"][l])
-        assert (got["We"] is None) == (e is None)
+            assert (got[k].grad - ref[k].grad).abs().max().item() <= 1e-12 * max(1.0, ref[k].grad.abs().max().item())
 
 
 def test_the_edge_term_is_in_the_score_only(orc):
@@ -60,8 +69,8 @@ def test_the_edge_term_is_in_the_score_only(orc):
     cfg = orc.Config([4, 2], [4, 8], g["f"], g["c"])
     P = orc.xavier_params(cfg, 1)
     fe = 3
-    ea, We = EF.edge_attrs(g, fe), EF.xavier_we(cfg, fe, 1)
-    ref = EF.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, ea=ea, We=We)
+    ea, We = EF.edge_attrs(g, fe), SR.xavier_we(cfg, fe, 1)
+    ref = SR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, ea=ea, We=We)
     base = FC.run_model(cfg, g, P)
     assert abs(ref["loss"].item() - base["loss"].item()) > 1e-3
     W, a = P[0].astype(np.float64), P[1].astype(np.float64)
@@ -81,17 +90,17 @@ def test_grad_we_matches_central_differences(orc):
     P = orc.xavier_params(cfg, 2)
     fe = 3
     ea = EF.edge_attrs(g, fe)
-    We = EF.xavier_we(cfg, fe, 2).astype(np.float64)
+    We = SR.xavier_we(cfg, fe, 2).astype(np.float64)
     keeps, attn, feat = FC.masks(cfg, g, cfg.heads, FC.REG)
 
     def run(w):
-        return EF.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, ea=ea, We=w, keeps=keeps, attn=attn, feat=feat)
+        return SR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, ea=ea, We=w, keeps=keeps, attn=attn, feat=feat)
     ref = run(We)
     assert ref["s_min"] > 1e-4 and ref["hpre_min"] > 1e-4      # the probes below stay on one side of every kink
     ref["loss"].backward()
     grad = ref["We"].grad.numpy()
     assert grad.shape == We.shape and np.abs(grad).max() > 0
-    o = EF.we_offsets(cfg, fe)
+    o = SR.we_offsets(cfg, fe)
     assert all(np.abs(grad[o[l]:o[l + 1]]).max() > 0 for l in range(cfg.L))
     rng = np.random.default_rng(0)
     h = 1e-6
@@ -109,11 +118,11 @@ def test_dropped_edges_get_no_gradient(orc):
     cfg = orc.Config([4, 2], [4, 8], g["f"], g["c"])
     P = orc.xavier_params(cfg, 1)
     fe = 2
-    ea, We = EF.edge_attrs(g, fe), EF.xavier_we(cfg, fe, 1)
+    ea, We = EF.edge_attrs(g, fe), SR.xavier_we(cfg, fe, 1)
     keep = np.random.default_rng(5).random(len(g["col_idx"])) > 0.5
-    full = EF.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, ea=ea, We=We, keeps=[keep, keep])
+    full = SR.forward(cfg, g["row_ptr"], g["col_idx"], g["labels"], g["x"], *P, ea=ea, We=We, keeps=[keep, keep])
     rp, ci = E.reduce_graph(g["row_ptr"], g["col_idx"], keep)
-    red = EF.forward(cfg, rp, ci, g["labels"], g["x"], *P, ea=ea[keep], We=We)
+    red = SR.forward(cfg, rp, ci, g["labels"], g["x"], *P, ea=ea[keep], We=We)
     full["loss"].backward(); red["loss"].backward()
     assert np.abs(full["We"].grad.numpy() - red["We"].grad.numpy()).max() <= 1e-12 * np.abs(red["We"].grad.numpy()).max()
 
@@ -199,8 +208,8 @@ def test_rows_case_finds_a_clear_seed(orc):
     assert 0 < keep.sum() < keep.size
     rp, ci = E.reduce_graph(g["row_ptr"], g["col_idx"], keep)
     assert (np.diff(rp)[np.diff(g["row_ptr"]) > 0] == 0).any()          # rows go empty
-    FC.pick_params(orc, cfg, lambda ps, PP: (None, EF.forward(cfg, rp, ci, g["labels"], g["x"], *PP, ea=inp["ea"][keep],
-                                                              We=EF.xavier_we(cfg, fe, ps))), FC.CLEAR_HPRE)
+    FC.pick_params(orc, cfg, lambda ps, PP: (None, SR.forward(cfg, rp, ci, g["labels"], g["x"], *PP, ea=inp["ea"][keep],
+                                                              We=SR.xavier_we(cfg, fe, ps))), FC.CLEAR_HPRE)
 
 
 def test_train_edge_flag_and_its_refusals(tmp_path):

@@ -54,7 +54,7 @@ def test_form_against_fp64(pkg, orc, case):
     setters = FC.setters(NORM_RES, norm=True) if norm else {}
     with FC.make_ctx(pkg, g, heads, outdims, P, **inp, **setters, reg=REG if reg else None, **kw) as ctx:
         loss, _ = ctx.step()
-        FC.compare(pkg, ctx, g, cfg, ref, loss, tol, taps=["hpre", "hout", "G"], groups=FC.GROUPS)
+        FC.compare(pkg, ctx, g, cfg, ref, loss, tol, taps=["hpre", "hout", "G"], groups=FC.GROUPS[:7])
         if taps:
             for l in range(cfg.L):
                 want = ref["alpha"][l]

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import feature_cases as FC
+import head_model as HD
 import loss_ref as LR
 import readout_ref as RR
 
@@ -28,7 +29,7 @@ def holed(rng, rows, C, mode):
 @pytest.mark.parametrize("mode", LR.MODES)
 @pytest.mark.parametrize("masked", [False, True])
 def test_losses_equal_torch(mode, masked):
-    """loss_ref.losses is binary_cross_entropy_with_logits / mse_loss with reduction="sum" over the contributing entries: the value and
+    """head_model.loss (max-form BCE, MSE) is binary_cross_entropy_with_logits / mse_loss with reduction="sum" over the contributing entries: the value and
     the autograd gradient (exactly 0 on every other entry); loss_ref.head_ref gives the same numbers in plain numpy."""
     import torch
     import torch.nn.functional as F
@@ -39,7 +40,7 @@ def test_losses_equal_torch(mode, masked):
     X = rng.standard_normal((rows, DL)) * 3
     Wo = rng.standard_normal((C, DL)).astype(np.float32)
     z = (torch.from_numpy(X) @ torch.from_numpy(Wo.astype(np.float64)).t()).requires_grad_(True)
-    loss, y = LR.losses(z, T, mask, mode)
+    loss, y, _ = HD.loss(z, mode, T, mask)
     loss.backward()
     on = LR.contributes(T, mask)
     z2 = z.detach().clone().requires_grad_(True)
