@@ -83,20 +83,25 @@ using namespace gat;
 extern "C" {
 
 // ---- phases --------------------------------------------------------------------------------------------------
+// What a layer's projection phase runs in front of PL / PR, whole (gat_layer_project) or in chunks (forward_exchange_pipelined).
 // Training forward with dropout: layer 0 advances the step counter first (one lane, captured like any other kernel), then every
 // layer with p_f > 0 writes its masked input x' = x (.) kappa s_f, which the projection and grad_W read instead of x.
-static int drop_prepare_input(gat_ctx* c, int32_t l) {
-    if (!drop_on(c)) return 0;
-    if (l == 0) GAT_TRY(launch_drop_advance(c->drop.step, c->stream));
-    if (!feat_drop_on(c)) return 0;
-    if (c->drop.x.empty() || (c->in.Xtab && !c->drop.x_tab)) GAT_TRY(ensure_drop_buffers(c));
+static int project_side_terms(gat_ctx* c, int32_t l) {
     const Layer& y = c->layers[l];
-    DropArgs d = drop_args(c, l, kDropFeat);
-    GAT_TRY(launch_feat_drop_fwd(Xin_raw(c, l), c->drop.x[(size_t)l], c->graph.n_rows, y.F, ldX_of(c, l), d, c->stream));
-    if (l == 0 && c->in.Xtab) {      // the replicated table: its rows are table rows, the same node ids
-        d.row0 = 0;
-        GAT_TRY(launch_feat_drop_fwd(c->in.Xtab, c->drop.x_tab, c->graph.n_table, y.F, c->in.ld0, d, c->stream));
+    if (drop_on(c) && l == 0) GAT_TRY(launch_drop_advance(c->drop.step, c->stream));
+    if (feat_drop_on(c)) {
+        if (c->drop.x.empty() || (c->in.Xtab && !c->drop.x_tab)) GAT_TRY(ensure_drop_buffers(c));
+        DropArgs d = drop_args(c, l, kDropFeat);
+        GAT_TRY(launch_feat_drop_fwd(Xin_raw(c, l), c->drop.x[(size_t)l], c->graph.n_rows, y.F, ldX_of(c, l), d, c->stream));
+        if (l == 0 && c->in.Xtab) {      // the replicated table: its rows are table rows, the same node ids
+            d.row0 = 0;
+            GAT_TRY(launch_feat_drop_fwd(c->in.Xtab, c->drop.x_tab, c->graph.n_table, y.F, c->in.ld0, d, c->stream));
+        }
     }
+    // edge features: PE = EA We^T over the E edges of the shard's own CSR — the residual term's product with rows = E, K = Fe
+    if (y.PE != nullptr && c->graph.n_edges > 0) GAT_TRY(launch_project_res(c->ef.EA, We_of(c, l), y.PE, c->graph.n_edges, c->ef.dim, y.HD, c->stream, c->ef.ld));
+    // residual: R = x' Wres^T over the shard's own rows (with replicated input: its own rows of the table) — the third projection
+    if (y.R != nullptr) GAT_TRY(launch_project_res(Xin_of(c, l), Wres_of(c, l), y.R, c->graph.n_rows, y.F, y.HD, c->stream, ldX_of(c, l)));
     return 0;
 }
 int gat_layer_project(gat_ctx* c, int32_t l) {
@@ -104,11 +109,7 @@ int gat_layer_project(gat_ctx* c, int32_t l) {
     GAT_TRY(check_edge_features(c));
     Layer& y = c->layers[l];
     Scope t(c, GAT_K_PROJECT);
-    GAT_TRY(drop_prepare_input(c, l));
-    // edge features: PE = EA We^T over the E edges of the shard's own CSR — the residual term's product with rows = E, K = Fe
-    if (y.PE != nullptr && c->graph.n_edges > 0) GAT_TRY(launch_project_res(c->ef.EA, We_of(c, l), y.PE, c->graph.n_edges, c->ef.dim, y.HD, c->stream, c->ef.ld));
-    // residual: R = x' Wres^T over the shard's own rows (with replicated input: its own rows of the table) — the third projection
-    if (y.R != nullptr) GAT_TRY(launch_project_res(Xin_of(c, l), Wres_of(c, l), y.R, c->graph.n_rows, y.F, y.HD, c->stream, ldX_of(c, l)));
+    GAT_TRY(project_side_terms(c, l));
     if (l == 0 && c->in.Xtab) {      // replicated input: whole PL table from the table rows, PR from the shard's rows
         GAT_TRY(launch_project(Xtab_of(c), W_of(c, l), y.PL, nullptr, c->graph.n_table, y.F, y.HD, kPartLeft, bf16(c), c->bwd.gw_scratch, c->bwd.gw_scratch_floats, c->stream, c->in.ld0));
         return launch_project(Xin_of(c, 0), W_of(c, l), nullptr, y.PR, c->graph.n_rows, y.F, y.HD, kPartRight, bf16(c), c->bwd.gw_scratch, c->bwd.gw_scratch_floats, c->stream, c->in.ld0);
@@ -258,9 +259,10 @@ int gat_head_backward(gat_ctx* c) {
     return pair_scatter(c);
 }
 
-// Arguments of layer l's edge backward (shared by gat_layer_backward_edges and the fused last layer of gat_step).
+// Arguments of layer l's edge backward (shared by gat_layer_backward_edges and the fused last layer of gat_step), and x: what it takes
+// beyond them (the forward's masks, the edge term) — filled here and nowhere else, handed as it is to the grid sizing and the launch.
 // edge_order: the layer's records lie in CSR edge order (records_take_edge_order), for the backward (a.edge_order) and the pull alike
-struct BwdPlan { EdgeBwdArgs a; bool store, stash, last_g, edge_order; DropArgs drop; };
+struct BwdPlan { EdgeBwdArgs a; bool store, stash, last_g, edge_order; EdgeBwdExtras x; };
 static int plan_backward_edges(gat_ctx* c, int32_t l, BwdPlan* P) {
     Layer& y = c->layers[l];
     const bool store = c->bwd.msg != nullptr && edge_fast_path(y.H, y.D, c->graph.n_table);
@@ -293,11 +295,14 @@ static int plan_backward_edges(gat_ctx* c, int32_t l, BwdPlan* P) {
                             records_take_edge_order(c->bwd.src_index, y.H, y.D, !bf16(c), last_g, !last_g || c->bwd.gh_stride == 16);
     a.edge_order = edge_order ? 1 : 0;
     set_work_list(a, c->graph.work, c->graph.items, c->graph.slot_info, c->graph.part_acc);
-    a.dbg = c->dbg;
     a.ga_partial = c->bwd.ga_partial + (int64_t)l * kGaPartialRows * c->HDmax; a.n_rows = c->graph.n_rows; a.n_table = c->graph.n_table; a.bf16 = bf16(c); a.H = y.H; a.D = y.D;
     a.slope = c->cfg.negative_slope;
-    P->drop = drop_args(c, l);
-    a.ga_blocks = edge_backward_blocks(a, &P->drop, y.PE != nullptr);
+    a.dbg = c->dbg;
+    P->x.drop = drop_args(c, l);
+    // edge features: the PE instantiations; gs of every edge goes to the shared gPE buffer (rows of this layer's HD floats)
+    P->x.pe = y.PE;
+    P->x.gpe = y.PE != nullptr ? c->ef.gPE : nullptr;
+    a.ga_blocks = edge_backward_blocks(a, &P->x);
     P->a = a; P->store = store; P->stash = stash; P->last_g = last_g; P->edge_order = edge_order;
     return 0;
 }
@@ -307,8 +312,13 @@ static int sum_backward_edges(gat_ctx* c, int32_t l, const BwdPlan& P) {
     if (!P.stash && !P.store) return 0;
     Scope t(c, GAT_K_GPL_SUM);
     if (P.stash) {
-        const PullArgs p{c->bwd.stash, c->bwd.gfull, bf16(c), P.last_g ? c->bwd.gH : nullptr, P.last_g ? c->bwd.hbits : nullptr, c->bwd.gh_stride, 64,
-                         a_of(c, l), c->cfg.negative_slope, gPL_of(c, l), y.H, y.D, P.edge_order};
+        PullArgs p{};
+        p.stash = c->bwd.stash; p.edge_order = P.edge_order;                  // the records and their layout
+        p.gfull = c->bwd.gfull; p.g_bf16 = bf16(c);                           // g rows, gathered ...
+        if (P.last_g) { p.gh = c->bwd.gH; p.hbits = c->bwd.hbits; }           // ... or rebuilt from the node records (last layer)
+        p.gh_stride = c->bwd.gh_stride; p.hb_stride = 64;
+        p.a = a_of(c, l); p.slope = c->cfg.negative_slope;
+        p.gPL = gPL_of(c, l); p.H = y.H; p.D = y.D;
         return launch_gpl_pull(c->bwd.src_index, p, c->stream);
     }
     return launch_gpl_sum(c->bwd.src_index, c->bwd.msg, bf16(c), gPL_of(c, l), y.HD, c->stream);
@@ -364,8 +374,7 @@ int gat_layer_backward_edges(gat_ctx* c, int32_t l) {
     }
     {
         Scope t(c, GAT_K_EDGE_BWD);
-        // edge features: the PE instantiations; gs of every edge goes to the shared gPE buffer (rows of this layer's HD floats)
-        GAT_TRY(launch_edge_backward(P.a, c->stream, &P.drop, y.PE, y.PE != nullptr ? c->ef.gPE : nullptr));
+        GAT_TRY(launch_edge_backward(P.a, c->stream, &P.x));
     }
     GAT_TRY(sum_backward_edges(c, l, P));
     Scope t(c, GAT_K_MISC);
@@ -446,9 +455,7 @@ static int forward_exchange_pipelined(gat_ctx* c, int l) {
     const int64_t rowf = y.HD * st_bytes(c) / 4;                           // floats per PL row (bf16 rows: half)
     char* own_rows = reinterpret_cast<char*>(y.PL) + c->graph.table_row0 * y.HD * st_bytes(c);
     Scope t(c, GAT_K_EXCHANGE);                                            // timed as a whole: projection chunks + their exchanges
-    GAT_TRY(drop_prepare_input(c, l));
-    if (y.PE != nullptr && c->graph.n_edges > 0) GAT_TRY(launch_project_res(c->ef.EA, We_of(c, l), y.PE, c->graph.n_edges, c->ef.dim, y.HD, c->stream, c->ef.ld));
-    if (y.R != nullptr) GAT_TRY(launch_project_res(Xin_of(c, l), Wres_of(c, l), y.R, c->graph.n_rows, y.F, y.HD, c->stream, ldX_of(c, l)));
+    GAT_TRY(project_side_terms(c, l));
     for (int k = 0; k < K; ++k) {
         const int64_t r0 = (int64_t)k * rpc, r1s = std::min<int64_t>(r0 + rpc, max_rows), r1 = std::min<int64_t>(r1s, c->graph.n_rows);
         if (r0 >= max_rows) break;
@@ -529,6 +536,7 @@ static int last_layer_fused(gat_ctx* c) {
         EdgeBwdArgs bs = P.a;
         bs.n_items = n_seg;
         bs.ga_partial = ga_a;
+        // without P.x on purpose, grid and launch alike: fused_last() excludes dropout and edge features, so the plan's extras are inert here
         bs.ga_blocks = blocks_a = std::min(kGaPartialRows / 2, edge_backward_blocks(bs));
         Scope t(c, GAT_K_EDGE_BWD);
         GAT_TRY(launch_edge_backward(bs, c->stream));

@@ -56,7 +56,7 @@ __device__ __forceinline__ void row_keys(const DropArgs& d, int64_t row, const i
 // (callers clamp j the way they clamp the edge index, so the load needs no predicate); gPE[j] is written once and never read back here.
 __device__ __forceinline__ float pe_load(const float* __restrict__ pe, int j, int HD, int c) { return pe[(int64_t)j * HD + c]; }
 // kernel argument: the forward's EXT instantiations take the plain struct + EdgeFwdExtras (masks and / or residual, bias, norm), the
-// backward's DROP instantiations the plain struct + the mask parameters; the default ones keep the plain struct
+// backward's DROP instantiations the plain struct + EdgeBwdExtras (masks, edge term); the default ones keep the plain struct
 template <bool EXT> struct FwdArgsOf { typedef EdgeFwdArgs T; };
 template <> struct FwdArgsOf<true> { typedef EdgeFwdExtArgs T; };
 template <bool DROP> struct BwdArgsOf { typedef EdgeBwdArgs T; };
@@ -2183,50 +2183,49 @@ static bool group_msg() {
 
 // The kernel of one edge pass and what its launch needs.  pick_fwd / pick_bwd below are the only places that name an
 // instantiation: the launchers run what they return, and edge_backward_blocks() sizes the persistent backward grid from
-// the same answer, so the two cannot disagree.
+// the same answer to the same (arguments, extras), so the two cannot disagree.
 struct EdgePick {
     const void* fn = nullptr;       // null: no kernel for this selection
     unsigned block = 256;           // threads per block
     int per_block = 4;              // forward: work items per block (the backward grid is edge_backward_blocks())
     const void* fix = nullptr;      // forward: the fix-up kernel of the split rows
     int grid_div = 1;               // backward: blocks this many times the size of the product kernel's (experiments)
+    bool edge_order = false;        // backward: the kernel writes its records in CSR edge order, i.e. honours EdgeBwdArgs::edge_order
 };
 #define GAT_K(...) ((const void*)(__VA_ARGS__))
+static EdgePick in_edge_order(const void* fn) { EdgePick p{fn}; p.edge_order = true; return p; }
 
-// Forward.  ext (EdgeFwdExtras were passed: masks and / or residual, bias, norm): the EXT instantiation of the kernel the default
-// settings pick, one wave per block — the parity-tap form with alpha, else the group-per-row kernel where the shape has one, else the
-// packed wave-per-row kernel.  The A/B switches of the default path (GAT_ROWGROUP, GAT_PACKED, GAT_CPL, GAT_FWD_WAVES) do not apply to
-// it: only these instantiations exist.
-// res (residual, bias or norm, always with ext): the fix-up kernel is the EXT form too — the masks alone leave it the plain one.
-// pe (edge features, always with ext): the PE instantiation of the same kernel; the fix-up kernels never see the edge term.
-template <int HD, int D, bool BF>
-EdgePick pick_fwd(const EdgeFwdArgs& a, bool ext, bool res, bool pe) {
+// Forward, one ladder: the parity-tap form with alpha, else the group-per-row kernel where the shape has one, else the packed
+// wave-per-row kernel.  The variant is compile-time: plain, EXT (EdgeFwdExtras were passed: masks and / or residual, bias, norm) or
+// EXT + PE (edge features: the PE instantiation of the same kernel).  The A/B switches (GAT_PACKED, GAT_ROWGROUP, GAT_CPL,
+// GAT_FWD_WAVES) apply to the plain variant only: the EXT instantiations exist for the kernel the default settings pick, one wave per
+// block, and for no other.
+// res (residual, bias or norm, always with EXT): the fix-up kernel is the EXT form too — the masks alone leave it the plain one, and it
+// never sees the edge term.
+template <int HD, int D, bool BF, bool EXT, bool PE>
+EdgePick fwd_ladder(const EdgeFwdArgs& a, bool res) {
     static_assert(D % 2 == 0, "every fast-path shape has an even D");
     constexpr int N3 = stash_n<HD, D>(), N2 = (HD >= 32 && D % 4 == 0) ? 4 : 2;
     constexpr int G3 = N3 != 0 ? 64 / (HD / (N3 != 0 ? N3 : 1)) : 1;             // rows per wave of the group-per-row kernel
-    if (a.alpha != nullptr) {                                                     // parity-tap form: alpha (and scores) materialised
-        const void* fix = res ? GAT_K(edge_fwd_fix_kernel<HD, D, true, true>) : GAT_K(edge_fwd_fix_kernel<HD, D, true>);
-        if (pe) return {GAT_K(edge_fwd_kernel<HD, D, true, BF, true, true>), 256, 4, fix};
-        return {ext ? GAT_K(edge_fwd_kernel<HD, D, true, BF, true>) : GAT_K(edge_fwd_kernel<HD, D, true, BF>), 256, 4, fix};
+    constexpr bool AB = !EXT;                                                     // the variant the A/B switches steer
+    const bool tap = a.alpha != nullptr;                                          // parity-tap form: alpha (and scores) materialised
+    const void* fix = tap ? (res ? GAT_K(edge_fwd_fix_kernel<HD, D, true, true>) : GAT_K(edge_fwd_fix_kernel<HD, D, true>))
+                          : (res ? GAT_K(edge_fwd_fix_kernel<HD, D, false, true>) : GAT_K(edge_fwd_fix_kernel<HD, D, false>));
+    if (tap) return {GAT_K(edge_fwd_kernel<HD, D, true, BF, EXT, PE>), 256, 4, fix};
+    if constexpr (AB) if (!packed_layout()) return {GAT_K(edge_fwd_kernel<HD, D, false, BF>), 256, 4, fix};
+    const int wpb = AB ? fwd_waves() : 1;                                         // waves per block of the packed kernels: two or four channels per lane
+    // group-per-row kernel (GAT_ROWGROUP=0: the chunked one, A/B)
+    if constexpr (N3 != 0) if (EXT || row_groups()) return {GAT_K(edge_fwd3_kernel<HD, D, N3, BF, EXT, PE>), 64u * wpb, G3 * wpb, fix};
+    if constexpr (AB || N3 == 0) {
+        if constexpr (N2 == 4) if (EXT || lane_channels() == 4) return {GAT_K(edge_fwd2_kernel<HD, D, 4, BF, EXT, PE>), 64u * wpb, wpb, fix};
+        if constexpr (AB || N2 == 2) return {GAT_K(edge_fwd2_kernel<HD, D, 2, BF, EXT, PE>), 64u * wpb, wpb, fix};
     }
-    const void* fix = res ? GAT_K(edge_fwd_fix_kernel<HD, D, false, true>) : GAT_K(edge_fwd_fix_kernel<HD, D, false>);
-    if (pe) {
-        if constexpr (N3 != 0) return {GAT_K(edge_fwd3_kernel<HD, D, N3, BF, true, true>), 64, G3, fix};
-        else return {GAT_K(edge_fwd2_kernel<HD, D, N2, BF, true, true>), 64, 1, fix};
-    }
-    if (ext) {
-        if constexpr (N3 != 0) return {GAT_K(edge_fwd3_kernel<HD, D, N3, BF, true>), 64, G3, fix};
-        else return {GAT_K(edge_fwd2_kernel<HD, D, N2, BF, true>), 64, 1, fix};
-    }
-    if (!packed_layout()) return {GAT_K(edge_fwd_kernel<HD, D, false, BF>), 256, 4, fix};
-    const int wpb = fwd_waves();                                                  // two or four channels per lane (see edge_fwd2_kernel)
-    if constexpr (N3 != 0) {                                                      // group-per-row kernel (GAT_ROWGROUP=0: the chunked one, A/B)
-        if (row_groups()) return {GAT_K(edge_fwd3_kernel<HD, D, N3, BF>), 64u * wpb, G3 * wpb, fix};
-    }
-    if constexpr (N2 == 4) {
-        if (lane_channels() == 4) return {GAT_K(edge_fwd2_kernel<HD, D, 4, BF>), 64u * wpb, wpb, fix};
-    }
-    return {GAT_K(edge_fwd2_kernel<HD, D, 2, BF>), 64u * wpb, wpb, fix};
+    return {};                                                                    // (not reached: every variant returned above)
+}
+template <int HD, int D, bool BF>
+EdgePick pick_fwd(const EdgeFwdArgs& a, bool ext, bool res, bool pe) {
+    if (pe) return fwd_ladder<HD, D, BF, true, true>(a, res);
+    return ext ? fwd_ladder<HD, D, BF, true, false>(a, res) : fwd_ladder<HD, D, BF, false, false>(a, res);
 }
 
 #ifdef GAT_EXPERIMENTS
@@ -2239,41 +2238,22 @@ const void* bwd3_dbg(int dbg) {
 }
 #endif
 
-// Backward.  store: message rows or records by CSC slot (else atomics into gPL); taps: the parity form that also writes ge / galpha;
-// stash: per-edge records + pull pass instead of message rows.  Attention dropout / DropEdge (drop) exist for the store path only,
-// as the DROP instantiation of the kernel the default settings pick; the A/B switches do not apply to them.
-// dbg (experiment library only, GAT_DBG): timing variants, most with WRONG results; 0 = the product kernel of the selection.
-// pe (edge features, always with drop): the PE instantiation of the same DROP kernel.
-template <int HD, int D, bool BF>
-EdgePick pick_bwd(const EdgeBwdArgs& a, bool drop, int dbg, bool pe) {
+// Backward, one ladder: records in edge order / records by slot / message rows from the group-per-row kernel / from the packed wave-per-row
+// kernel / the one-channel-per-lane kernel (parity taps, atomics, GAT_PACKED=0).  store: message rows or records by CSC slot (else atomics
+// into gPL); taps: the parity form that also writes ge / galpha; stash: per-edge records + pull pass instead of message rows.
+// The variant is compile-time: plain, DROP (attention dropout / DropEdge) or DROP + PE (edge features: the PE instantiation of the same
+// DROP kernel).  The DROP instantiations exist for the store path only, and for the kernel the default settings pick: the A/B switches
+// (GAT_ROWGROUP, GAT_GROUP_MSG, GAT_PACKED, GAT_CPL) and the GAT_DBG entries (experiment library; timing variants, most with WRONG results;
+// 0 = the product kernel of the selection) belong to the plain variant — but for GAT_ROWGROUP=0, which leaves every variant's records by slot.
+template <int HD, int D, bool BF, bool DROP, bool PE>
+EdgePick bwd_ladder(const EdgeBwdArgs& a, [[maybe_unused]] int dbg) {
     constexpr int N3 = stash_n<HD, D>(), N2 = (HD >= 32 && D % 4 == 0) ? 4 : 2;
+    constexpr bool AB = !DROP;                                                    // the variant the A/B switches and GAT_DBG steer
     const bool store = a.pos != nullptr && a.msg != nullptr, taps = a.ge != nullptr, stash = a.stash != nullptr && !taps;
-    // records in CSR edge order (EdgeBwdArgs::edge_order, set under records_take_edge_order): the EO instantiation of the group-per-row
-    // record kernel, plain / DROP / PE; launch_edge_backward refuses the flag where that kernel is not the pick
-    [[maybe_unused]] const bool eo = a.edge_order != 0 && stash && store && !BF && N3 != 0 && row_groups() && dbg == 0;
-    [[maybe_unused]] const bool lines = eo && stash_lines();
-    if (drop) {
-        if (!store) return {};
-        if (pe) {
-            if (taps) return {GAT_K(edge_bwd_kernel<HD, D, true, true, 0, BF, true, true>)};
-            if constexpr (N3 != 0 && !BF) {
-                if (lines) return {GAT_K(edge_bwd3_kernel<HD, D, N3, 0, false, false, true, true, true, true>)};
-                if (eo) return {GAT_K(edge_bwd3_kernel<HD, D, N3, 0, false, false, true, true, true>)};
-            }
-            if constexpr (N3 != 0) return {stash ? GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, false, true, true>) : GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, true, true, true>)};
-            else return {GAT_K(edge_bwd2_kernel<HD, D, N2, 0, BF, false, true, true>)};
-        }
-        if (taps) return {GAT_K(edge_bwd_kernel<HD, D, true, true, 0, BF, true>)};
-        if constexpr (N3 != 0 && !BF) {
-            if (lines) return {GAT_K(edge_bwd3_kernel<HD, D, N3, 0, false, false, true, false, true, true>)};
-            if (eo) return {GAT_K(edge_bwd3_kernel<HD, D, N3, 0, false, false, true, false, true>)};
-        }
-        if constexpr (N3 != 0) return {stash ? GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, false, true>) : GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, true, true>)};
-        else return {GAT_K(edge_bwd2_kernel<HD, D, N2, 0, BF, false, true>)};
-    }
-    const bool msg_rows = store && !taps && packed_layout();                      // packed message-row kernels
+    if (DROP && !store) return {};
+    const bool msg_rows = store && !taps && (DROP || packed_layout());            // packed message-row kernels
 #ifdef GAT_EXPERIMENTS
-    if constexpr (HD == 64 && D == 8) {
+    if constexpr (AB && HD == 64 && D == 8) {
         if (store && !taps && !stash) {                                           // GAT_DBG=1: no message store, 2: sequential slots
             if (dbg == 1) return {GAT_K(edge_bwd_kernel<HD, D, true, false, 1>)};
             if (dbg == 2) return {GAT_K(edge_bwd_kernel<HD, D, true, false, 2>)};
@@ -2296,31 +2276,38 @@ EdgePick pick_bwd(const EdgeBwdArgs& a, bool drop, int dbg, bool pe) {
     }
 #endif
     if constexpr (N3 != 0) {
-        if constexpr (!BF) {
-            if (lines) return {GAT_K(edge_bwd3_kernel<HD, D, N3, 0, false, false, false, false, true, true>)};
-            if (eo) return {GAT_K(edge_bwd3_kernel<HD, D, N3, 0, false, false, false, false, true>)};
+        // records in CSR edge order (EdgeBwdArgs::edge_order, set under records_take_edge_order): the EO instantiation of the fp32
+        // group-per-row record kernel, its stores whole lines (GAT_STASH_LINES).  This rung is the one statement of where the flag is
+        // honoured: launch_edge_backward refuses it on any other pick
+        if constexpr (!BF) if (a.edge_order != 0 && stash && store && row_groups() && dbg == 0)
+            return in_edge_order(stash_lines() ? GAT_K(edge_bwd3_kernel<HD, D, N3, 0, false, false, DROP, PE, true, true>)
+                                               : GAT_K(edge_bwd3_kernel<HD, D, N3, 0, false, false, DROP, PE, true>));
+        if (stash) {                                                              // records by slot; GAT_ROWGROUP=0 has no bf16 form
+            if constexpr (AB && !BF) if (!row_groups()) return {GAT_K(edge_bwd2s_kernel<HD, D, N3>)};
+            return {GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, false, DROP, PE>)};
         }
-        // records; bf16 storage: always the group-per-row kernel (GAT_ROWGROUP=0 has no bf16 form)
-        if (stash) return {(BF || row_groups()) ? GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF>) : GAT_K(edge_bwd2s_kernel<HD, D, N3>)};
         // message rows from the group-per-row kernel.  Both switches are read, GAT_GROUP_MSG first: a process that sets both reports
         // both in gat_switches() (either one at 0 gives the wave-per-row kernel)
-        if (const bool gm = group_msg(); msg_rows && row_groups() && gm) {
+        if (const bool gm = DROP || group_msg(); msg_rows && (DROP || row_groups()) && gm) {
 #ifdef GAT_EXPERIMENTS      // GAT_DBG=1 on a message-row layer (BASELINE config 5): the walk without its message-row stores — WRONG RESULTS, timing / PMC
-            if constexpr (HD == 32 && D == 8 && BF) {     // attribution only (DESIGN §4 "Round 4": how much of the backward's reads is fill for its 64-byte row writes)
-                if (dbg == 1) return {GAT_K(edge_bwd3_kernel<HD, D, N3, 1, true, true>)};
-            }
+            // attribution only (DESIGN §4 "Round 4": how much of the backward's reads is fill for its 64-byte row writes)
+            if constexpr (AB && HD == 32 && D == 8 && BF) if (dbg == 1) return {GAT_K(edge_bwd3_kernel<HD, D, N3, 1, true, true>)};
 #endif
-            return {GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, true>)};
+            return {GAT_K(edge_bwd3_kernel<HD, D, N3, 0, BF, true, DROP, PE>)};
         }
     }
-    if (msg_rows) {
-        if constexpr (N2 == 4) {
-            if (lane_channels() == 4) return {GAT_K(edge_bwd2_kernel<HD, D, 4, 0, BF>)};
-        }
-        return {GAT_K(edge_bwd2_kernel<HD, D, 2, 0, BF>)};
+    if constexpr (AB || N3 == 0) if (msg_rows) {
+        if constexpr (N2 == 4) if (DROP || lane_channels() == 4) return {GAT_K(edge_bwd2_kernel<HD, D, 4, 0, BF, false, DROP, PE>)};
+        if constexpr (AB || N2 == 2) return {GAT_K(edge_bwd2_kernel<HD, D, 2, 0, BF, false, DROP, PE>)};
     }
-    return {store ? (taps ? GAT_K(edge_bwd_kernel<HD, D, true, true, 0, BF>) : GAT_K(edge_bwd_kernel<HD, D, true, false, 0, BF>))
-                  : (taps ? GAT_K(edge_bwd_kernel<HD, D, false, true, 0, BF>) : GAT_K(edge_bwd_kernel<HD, D, false, false, 0, BF>))};
+    if constexpr (DROP) return {taps ? GAT_K(edge_bwd_kernel<HD, D, true, true, 0, BF, true, PE>) : nullptr};    // (without taps: returned above)
+    else return {store ? (taps ? GAT_K(edge_bwd_kernel<HD, D, true, true, 0, BF>) : GAT_K(edge_bwd_kernel<HD, D, true, false, 0, BF>))
+                       : (taps ? GAT_K(edge_bwd_kernel<HD, D, false, true, 0, BF>) : GAT_K(edge_bwd_kernel<HD, D, false, false, 0, BF>))};
+}
+template <int HD, int D, bool BF>
+EdgePick pick_bwd(const EdgeBwdArgs& a, bool drop, int dbg, bool pe) {
+    if (drop && pe) return bwd_ladder<HD, D, BF, true, true>(a, dbg);
+    return drop ? bwd_ladder<HD, D, BF, true, false>(a, dbg) : bwd_ladder<HD, D, BF, false, false>(a, dbg);
 }
 
 // the templates' entry: FN<H*D, D, bf16 storage>(...) for a listed shape (returns from the enclosing function), nothing otherwise
@@ -2331,9 +2318,20 @@ static EdgePick pick_forward(const EdgeFwdArgs& a, bool ext, bool res, bool pe) 
     GAT_DISPATCH_HD_D(a.H * a.D, a.D, pick_fwd, a.bf16 != 0, a, ext, res, pe)
     return {};
 }
-static EdgePick pick_backward(const EdgeBwdArgs& a, bool drop, int dbg, bool pe = false) {
+static EdgePick pick_backward(const EdgeBwdArgs& a, bool drop, int dbg, bool pe) {
     GAT_DISPATCH_HD_D(a.H * a.D, a.D, pick_bwd, a.bf16 != 0, a, drop, dbg, pe)
     return {};
+}
+// the variant of (a, x): an active mask or the edge term — which runs the DROP instantiations, masks or not
+static EdgePick pick_backward(const EdgeBwdArgs& a, const EdgeBwdExtras* x, int dbg) {
+    const bool pe = x != nullptr && x->pe != nullptr;
+    return pick_backward(a, pe || (x != nullptr && x->drop.on != 0), dbg, pe);
+}
+// The pick the persistent backward grid is sized for: the product kernel (dbg 0; the experiment kernels run on its grid) of what
+// launch_edge_backward(a, s, x) will run.  Extras without a kernel there — the launcher refuses them — size like the plain selection.
+static EdgePick grid_pick(const EdgeBwdArgs& a, const EdgeBwdExtras* x) {
+    const EdgePick p = pick_backward(a, x, 0);
+    return p.fn != nullptr ? p : pick_backward(a, nullptr, 0);
 }
 
 // Blocks of `fn` (`block` threads, no dynamic LDS) that are resident on the whole chip at once, from the
@@ -2397,8 +2395,7 @@ int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const EdgeFwdExtras
     if (x.ln.gamma == nullptr) x.ln = LnArgs{};
     else if (x.ln.beta == nullptr) return fail(GAT_E_INVALID, "edge_forward: layer normalisation without beta");
     const bool with_res = x.res != nullptr || x.bias != nullptr || x.ln.gamma != nullptr;    // residual, bias, norm
-    // THE RULE (gat_internal.h EdgeFwdExtras): extras without an active mask — every draw keeps, nothing is scaled
-    if (!x.drop.on) { x.drop.T = 0; x.drop.Te = 0; x.drop.scale = 1.f; x.drop.eflags = 0; }
+    neutral_mask(x.drop);
     if (edge_fast_path(a.H, a.D, a.n_table)) {
         if (a.items == nullptr) return fail(GAT_E_INVALID, "edge_forward: work-item list missing");
         if (a.mstat == nullptr || a.zstat == nullptr) return fail(GAT_E_INVALID, "edge_forward: stats buffers missing");
@@ -2417,41 +2414,36 @@ int launch_edge_forward(const EdgeFwdArgs& a, hipStream_t s, const EdgeFwdExtras
     return 0;
 }
 
-int edge_backward_blocks(const EdgeBwdArgs& a, const DropArgs* drop, bool pe) {
+int edge_backward_blocks(const EdgeBwdArgs& a, const EdgeBwdExtras* x) {
     if (!edge_fast_path(a.H, a.D, a.n_table))            // generic path: one wave per block, a row at a time
         return (int)std::min<int64_t>(std::max<int64_t>(a.n_rows, 1), kGaPartialRows);
-    const bool on = (drop != nullptr && drop->on != 0) || pe;     // edge features: the DROP instantiations, masks or not
-    // the experiment kernels (dbg) run on the grid of the product kernel of their selection
-    EdgePick p = pick_backward(a, on, 0, pe);
-    if (p.fn == nullptr) p = pick_backward(a, false, 0);  // no dropout form: launch_edge_backward reports it
+    const EdgePick p = grid_pick(a, x);
     int64_t cap = resident_blocks(p.fn, p.block);
 #ifdef GAT_EXPERIMENTS
-    cap /= pick_backward(a, on, a.dbg).grid_div;
+    cap /= pick_backward(a, x, a.dbg).grid_div;
 #endif
     return (int)std::min({std::max<int64_t>((a.n_items + 3) / 4, 1), cap, (int64_t)kGaPartialRows});
 }
 
-int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s, const DropArgs* drop, const float* pe, float* gpe) {
+int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s, const EdgeBwdExtras* extras) {
     if (a.ga_blocks < 1) return fail(GAT_E_INVALID, "edge_backward: ga_blocks must come from edge_backward_blocks()");
-    DropArgs dr = drop != nullptr ? *drop : DropArgs{};
-    const bool with_pe = pe != nullptr;
-    if (with_pe != (gpe != nullptr)) return fail(GAT_E_INVALID, "edge_backward: the edge term needs both PE and gPE");
-    // THE RULE of launch_edge_forward: the extended instantiations without an active mask — every draw keeps, nothing is scaled
-    if (with_pe && !dr.on) { dr.T = 0; dr.Te = 0; dr.scale = 1.f; dr.eflags = 0; }
-    const bool ext = dr.on != 0 || with_pe;
+    EdgeBwdDropArgs ad;                                  // the extended argument struct; the plain kernels read its EdgeBwdArgs part
+    static_cast<EdgeBwdArgs&>(ad) = a;
+    if (extras != nullptr) static_cast<EdgeBwdExtras&>(ad) = *extras;
+    EdgeBwdExtras& x = ad;
+    if ((x.pe != nullptr) != (x.gpe != nullptr)) return fail(GAT_E_INVALID, "edge_backward: the edge term needs both PE and gPE");
+    neutral_mask(x.drop);
     if (edge_fast_path(a.H, a.D, a.n_table)) {
         if (a.items == nullptr) return fail(GAT_E_INVALID, "edge_backward: work-item list missing");
         if (a.stash != nullptr && a.ge == nullptr && (a.gfull == nullptr || a.pos == nullptr))
             return fail(GAT_E_INVALID, "edge_backward: stash path needs gfull and pos");
-        if (ext && dr.step == nullptr) return fail(GAT_E_INVALID, "edge_backward: the extended kernels read the device counter (DropArgs::step)");
-        if (a.edge_order && !(a.stash != nullptr && a.ge == nullptr && !a.bf16 && a.dbg == 0 && edge_backward_groups(a.H, a.D)))
-            return fail(GAT_E_INVALID, "edge_backward: records in edge order need the fp32 group-per-row record kernel");
-        const EdgePick p = pick_backward(a, ext, a.dbg, with_pe);
+        if ((x.drop.on != 0 || x.pe != nullptr) && x.drop.step == nullptr)
+            return fail(GAT_E_INVALID, "edge_backward: the extended kernels read the device counter (DropArgs::step)");
+        const EdgePick p = pick_backward(a, &x, a.dbg);
+        if (a.edge_order && !p.edge_order) return fail(GAT_E_INVALID, "edge_backward: records in edge order need the fp32 group-per-row record kernel");
         if (p.fn == nullptr)
             return fail(GAT_E_UNSUPPORTED, "edge_backward: attention dropout / DropEdge / edge features need the store path (not with GAT_BWD_ATOMICS=1 or without the message scratch)");
-        EdgeBwdDropArgs ad;
-        if (ext) { static_cast<EdgeBwdArgs&>(ad) = a; ad.drop = dr; ad.pe = pe; ad.gpe = gpe; }
-        void* args[] = {ext ? (void*)&ad : (void*)const_cast<EdgeBwdArgs*>(&a)};
+        void* args[] = {&ad};
         GAT_HIP(hipLaunchKernel(p.fn, dim3((unsigned)a.ga_blocks), dim3(p.block), args, 0, s));
         return launch_bwd_fix(a, s);
     }
@@ -2459,8 +2451,8 @@ int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s, const DropArgs* dr
     const int HD = a.H * a.D;
     const size_t lds = (size_t)(3 * a.H + 2 * HD) * sizeof(float);
     if (lds > 64 * 1024) return fail(GAT_E_UNSUPPORTED, "edge_backward: H*D too large for the generic path");
-    if (with_pe) hipLaunchKernelGGL(edge_bwd_generic_pe, dim3((unsigned)a.ga_blocks), dim3(64), lds, s, a, dr, pe, gpe);
-    else hipLaunchKernelGGL(edge_bwd_generic, dim3((unsigned)a.ga_blocks), dim3(64), lds, s, a, dr);
+    if (x.pe != nullptr) hipLaunchKernelGGL(edge_bwd_generic_pe, dim3((unsigned)a.ga_blocks), dim3(64), lds, s, a, x.drop, x.pe, x.gpe);
+    else hipLaunchKernelGGL(edge_bwd_generic, dim3((unsigned)a.ga_blocks), dim3(64), lds, s, a, x.drop);
     GAT_HIP(hipGetLastError());
     return 0;
 }

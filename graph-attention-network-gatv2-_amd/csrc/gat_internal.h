@@ -161,7 +161,7 @@ struct LnArgs {
 // whose argument struct is EdgeFwdExtArgs below; without extras the kernels keep the plain struct and the machine code they have
 // without these features.
 // drop: attention dropout / DropEdge (drop.on: a mask is active).  drop.step must point at a device counter whenever extras are
-//   passed: the extended instantiations hash every edge.  THE RULE, applied in launch_edge_forward and nowhere else: extras without
+//   passed: the extended instantiations hash every edge.  THE RULE (neutral_mask below, called by the two launchers): extras without
 //   an active mask run the extended instantiation with T = Te = 0, scale = 1 — every draw keeps, nothing is scaled.  (The generic
 //   kernels get the same struct and read drop.on at run time: off, they do not hash at all.  The template kernels never read it.)
 // res / bias (either may be null, gatv2_abi.h "residual"): h_pre[row][c] += res[row][c] + bias[c] in the row epilogue, before h_pre
@@ -225,12 +225,33 @@ struct EdgeBwdArgs {
     int32_t dbg;
     int32_t edge_order;       // records in CSR edge order: record j = edge j (records_take_edge_order below), not stash[pos[j]]; fits the struct's tail padding
 };
-// drop: the attention dropout of the forward this backward follows (same masks)
+// What a backward may take beyond EdgeBwdArgs, the counterpart of EdgeFwdExtras.  An active mask or the edge term selects the DROP
+// instantiations of the kernels, whose argument struct is EdgeBwdDropArgs below.  The grid and the launch are handed the SAME object:
+// edge_backward_blocks(a, &x) sizes the grid — and the ga_partial rows — for the kernel launch_edge_backward(a, s, &x) runs.
+// drop: the attention dropout / DropEdge of the forward this backward follows (same masks)
 // pe / gpe (both or neither; gatv2_abi.h "edge features"): the forward's PE rows, and where gs = ge * a * LReLU'(s) of every CSR edge is
 //   written ([n_edges][HD] fp32, zeros at dropped edges).  They select the PE instantiations of the DROP kernels, under the forward's
-//   rule: without an active mask those run with T = Te = 0, scale = 1 (drop->step must still point at the device counter).
-int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s, const DropArgs* drop = nullptr, const float* pe = nullptr, float* gpe = nullptr);
-struct EdgeBwdDropArgs : EdgeBwdArgs { DropArgs drop; const float* pe = nullptr; float* gpe = nullptr; };
+//   rule (neutral_mask): without an active mask those run with T = Te = 0, scale = 1 (drop.step must still point at the device counter).
+struct EdgeBwdExtras {
+    DropArgs drop;
+    const float* pe = nullptr;    // [n_edges][HD] fp32 in CSR order, or null
+    float* gpe = nullptr;         // [n_edges][HD] fp32, written
+};
+int launch_edge_backward(const EdgeBwdArgs& a, hipStream_t s, const EdgeBwdExtras* x = nullptr);
+// the DROP kernels' argument: the plain struct, then drop, pe, gpe — the layout those kernels were compiled against
+struct EdgeBwdDropArgs : EdgeBwdArgs, EdgeBwdExtras {};
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+static_assert(offsetof(EdgeBwdDropArgs, drop) == sizeof(EdgeBwdArgs) && offsetof(EdgeBwdDropArgs, pe) == sizeof(EdgeBwdArgs) + sizeof(DropArgs) &&
+                  offsetof(EdgeBwdDropArgs, gpe) == offsetof(EdgeBwdDropArgs, pe) + sizeof(float*) &&
+                  sizeof(EdgeBwdDropArgs) == sizeof(EdgeBwdArgs) + sizeof(EdgeBwdExtras) && sizeof(EdgeBwdArgs) % alignof(DropArgs) == 0,
+              "EdgeBwdDropArgs: EdgeBwdArgs, then drop, pe, gpe");
+#pragma clang diagnostic pop
+// THE RULE of the extended instantiations, forward and backward (they hash every edge): without an active mask every draw keeps and
+// nothing is scaled.  The launchers apply it to their copy of the extras; nothing else does.
+inline void neutral_mask(DropArgs& d) {
+    if (!d.on) { d.T = 0; d.Te = 0; d.scale = 1.f; d.eflags = 0; }
+}
 // The work-list fields of EdgeFwdArgs / EdgeBwdArgs from a WorkList and its device copies (part_mz: the forward's only)
 template <class Args> void set_work_list(Args& a, const WorkList& w, const int4* items, const int4* slot_info, float* part_acc, float* part_mz = nullptr) {
     a.items = items; a.n_items = w.n_items; a.slot_info = slot_info; a.n_slots = w.n_slots; a.n_split = w.n_split; a.part_acc = part_acc;
@@ -288,9 +309,9 @@ int launch_head_rows(const int4* slot_info, int32_t n_slots, int32_t n_split, co
 int edge_stash_words(int32_t H, int32_t D);
 // Rows of ga_partial a layer's backward may write: the cap of every grid that writes one row per block
 constexpr int kGaPartialRows = 2048;
-// Grid size (== rows of ga_partial, <= kGaPartialRows) for the backward launch_edge_backward(a, s, drop) will run: sized for the
-// kernel those arguments select (a.ga_blocks is not read); pe: the backward will be given PE rows
-int edge_backward_blocks(const EdgeBwdArgs& a, const DropArgs* drop = nullptr, bool pe = false);
+// Grid size (== rows of ga_partial, <= kGaPartialRows) for the backward launch_edge_backward(a, s, x) will run: sized for the
+// kernel those arguments select (a.ga_blocks is not read)
+int edge_backward_blocks(const EdgeBwdArgs& a, const EdgeBwdExtras* x = nullptr);
 // wave-per-row templates cover this (H, D), and the gathered table is < 4 GiB (they address it as
 // uniform base + 32-bit byte offset); anything else runs the generic kernels
 bool edge_fast_path(int32_t H, int32_t D, int64_t n_table);

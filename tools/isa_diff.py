@@ -3,7 +3,8 @@
 
 Per kernel: the .amdhsa figures tools/isa_stats.py prints must be equal, and the instruction lines must be equal once comments,
 register numbers and local labels are masked ("registers renamed").  "Byte-identical" is the kernel's text as it stands, but for
-the number of the function inside its local labels (.LBB<function>_<block>), which moves when another kernel is emitted before it.  Kernels whose mangled name exists on one side only are paired
+the number of the function inside its local labels (.LBB<function>_<block>) and the column padding behind such a label, which move when
+another kernel is emitted before it.  Kernels whose mangled name exists on one side only are paired
 by the longest common prefix of their names (a renamed parameter type changes the tail only) and listed; --pairs FILE pairs by hand
 first ("OLD_NAME NEW_NAME" per line: kernels folded into one template, whose names differ in the middle).
 Prints one summary line; exit status 1 if any kernel has other differences or stays unpaired."""
@@ -38,8 +39,9 @@ def masked(body):
 
 def unnumbered(body):
     """Local labels, and the comments that cite them, carry the number of their function in the file (.LBB<function>_<block>):
-    where a kernel is emitted is not its code."""
-    return re.sub(r"(BB|JTI)\d+_(?=\d)", r"\1_", body)
+    where a kernel is emitted is not its code.  Nor is the padding between such a label and its comment, which shrinks by a column
+    when the function's number gains a digit."""
+    return re.sub(r"(?m)^(\.L\w+:)[ \t]+;", r"\1 ;", re.sub(r"(BB|JTI)\d+_(?=\d)", r"\1_", body))
 
 
 def prefix_len(a, b):
