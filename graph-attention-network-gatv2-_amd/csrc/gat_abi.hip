@@ -236,7 +236,7 @@ int ensure_buffers(gat_ctx* c) {
         GAT_TRY(dalloc(c, &c->hid.partial, (int64_t)kHiddenPartialRows * Dh));
         GAT_TRY(dalloc(c, &c->hid.gw_scratch, std::max<int64_t>(grad_w_scratch_floats(NH, c->layers[L - 1].D, Dh), 1)));
     }
-    GAT_TRY(dalloc(c, &c->head.hb_partial, (int64_t)head_bwd_blocks(NH, C, DL) * C * DL));
+    GAT_TRY(dalloc(c, &c->head.hb_partial, (int64_t)head_bwd_blocks(NH) * C * DL));
     GAT_TRY(dalloc(c, &c->head.loss_partial, head_blocks(NH)));
     GAT_TRY(dalloc(c, &c->head.correct_partial, head_blocks(NH)));
     GAT_TRY(dalloc(c, &c->head.loss_out, 1));

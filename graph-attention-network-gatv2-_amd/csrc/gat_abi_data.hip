@@ -295,14 +295,14 @@ int gat_set_train_mask(gat_ctx* c, const uint8_t* mask, int64_t n_rows) {
 // terms and the correct count over the present entries of the mask's rows, from the head's input rows of the last forward
 static int eval_mask_targets(gat_ctx* c, const uint8_t* mask, int64_t n_rows, double* loss_sum, int32_t* n_correct, int32_t* n_nodes) {
     GAT_TRY(upload_mask(c, mask, n_rows, &c->sup.mask_tmp));
-    LossHeadArgs a = loss_head_args(c);
+    HeadArgs a = head_args(c);
     const int blocks = loss_head_blocks(a.n_rows, a.C, a.DL, a.mode);
     if (blocks < 0) return fail(GAT_E_UNSUPPORTED, "output head: num_classes*D_last too large for the LDS tile");
     if (!c->sup.eval_loss) { GAT_TRY(dalloc(c, &c->sup.eval_loss, head_blocks(a.n_rows))); GAT_TRY(dalloc(c, &c->sup.eval_cnt, head_blocks(a.n_rows))); }
     a.mask = c->sup.mask_tmp; a.loss_partial = c->sup.eval_loss; a.correct_partial = c->sup.eval_cnt; a.loss_out = nullptr; a.correct_out = nullptr;
     {
         Scope t(c, GAT_K_HEAD_FWD);
-        GAT_TRY(launch_loss_head_forward(a, c->stream));
+        GAT_TRY(launch_head_forward(a, c->stream));
     }
     c->head.y_valid = true;                              // (y does not depend on the mask)
     std::vector<double> hl((size_t)blocks); std::vector<int32_t> hc((size_t)blocks);

@@ -15,51 +15,38 @@ void graph_drop(gat_ctx* c) {
     if (c->replay.state == 2) c->replay.state = 1;
     c->replay.warm = 0;
 }
-static void head_args(gat_ctx* c, HeadArgs* f, HeadBwdArgs* b) {
+HeadArgs head_args(gat_ctx* c) {
     const Layer& y = c->layers.back();
-    f->Wo = Wo_of(c); f->HL = y.hout; f->labels = c->sup.labels_eff ? c->sup.labels_eff : c->sup.labels; f->y = c->head.y;
-    f->loss_partial = c->head.loss_partial; f->correct_partial = c->head.correct_partial;
-    f->loss_out = c->head.loss_out; f->correct_out = c->head.correct_out;
-    f->n_rows = c->graph.n_rows; f->C = c->cfg.num_classes; f->DL = y.D;
-    b->Wo = Wo_of(c); b->HL = y.hout; b->y = c->head.y; b->labels = c->sup.labels_eff ? c->sup.labels_eff : c->sup.labels; b->hpre = y.hpre; b->g = y.g; b->gh_out = c->bwd.gH; b->gh_stride = c->bwd.gh_stride;
-    b->gradWo = gWo_of(c); b->partial = c->head.hb_partial; b->n_rows = c->graph.n_rows; b->C = c->cfg.num_classes;
-    b->DL = y.D; b->H = y.H; b->slope = c->cfg.negative_slope; b->flat_index = c->cfg.flat_lrelu_index;
+    HeadArgs a{};
+    a.mode = c->sup.loss_mode; a.Wo = Wo_of(c); a.X = y.hout; a.y = c->head.y;
+    a.labels = c->sup.labels_eff ? c->sup.labels_eff : c->sup.labels;
+    a.T = c->sup.targets; a.mask = c->sup.mask_on ? c->sup.train_mask : nullptr;
+    a.hpre = y.hpre; a.g = y.g; a.gh_out = c->bwd.gH; a.gh_stride = c->bwd.gh_stride; a.gradWo = gWo_of(c); a.partial = c->head.hb_partial;
+    a.loss_partial = c->head.loss_partial; a.correct_partial = c->head.correct_partial;
+    a.loss_out = c->head.loss_out; a.correct_out = c->head.correct_out;
+    a.n_rows = c->graph.n_rows; a.C = c->cfg.num_classes; a.DL = y.D; a.H = y.H;
+    a.slope = c->cfg.negative_slope; a.flat_index = c->cfg.flat_lrelu_index;
     if (readout_on(c)) {
         // the head on the pooled rows: one row per graph, its gradient into gP (rows of D_last floats); the un-pool fills c->bwd.gH
         // afterwards and the last layer's edge backward expands that as always, so the head never writes a g of its own
-        f->HL = b->HL = c->readout.P; f->n_rows = b->n_rows = c->readout.n_graphs;
-        b->g = nullptr; b->hpre = nullptr; b->gh_out = c->readout.gP; b->gh_stride = y.D;
+        a.X = c->readout.P; a.n_rows = c->readout.n_graphs;
+        a.g = nullptr; a.hpre = nullptr; a.gh_out = c->readout.gP; a.gh_stride = y.D;
     }
     if (pairs_on(c)) {
         // the head on the pair rows Q: one row per pair, its gradient into gQ; the scatter fills c->bwd.gH afterwards, as the un-pool does
-        f->HL = b->HL = c->pairs.Q; f->n_rows = b->n_rows = c->pairs.n_pairs;
-        b->g = nullptr; b->hpre = nullptr; b->gh_out = c->pairs.gQ; b->gh_stride = y.D;
+        a.X = c->pairs.Q; a.n_rows = c->pairs.n_pairs;
+        a.g = nullptr; a.hpre = nullptr; a.gh_out = c->pairs.gQ; a.gh_stride = y.D;
     }
     if (hidden_on(c)) {
         // the head on Z1 = act(Xin W1^T + b1), rows of Dh floats (Wo is [C][Dh]), its gradient into gZ1; the hidden stage's backward
         // fills the buffer the head's gradient went to before (gH, gP or gQ), so the head never writes a g of its own here either
-        f->HL = b->HL = c->hid.Z1; f->DL = b->DL = c->hid.width;
-        b->g = nullptr; b->hpre = nullptr; b->gh_out = c->hid.gZ1; b->gh_stride = c->hid.width;
+        a.X = c->hid.Z1; a.DL = c->hid.width;
+        a.g = nullptr; a.hpre = nullptr; a.gh_out = c->hid.gZ1; a.gh_stride = c->hid.width;
     }
-}
-LossHeadArgs loss_head_args(gat_ctx* c) {
-    HeadArgs f{}; HeadBwdArgs b{};
-    head_args(c, &f, &b);
-    LossHeadArgs a{};
-    a.Wo = f.Wo; a.X = f.HL; a.T = c->sup.targets; a.mask = c->sup.mask_on ? c->sup.train_mask : nullptr; a.y = f.y;
-    a.gh_out = b.gh_out; a.gh_stride = b.gh_stride; a.gradWo = b.gradWo; a.partial = b.partial;
-    a.loss_partial = f.loss_partial; a.correct_partial = f.correct_partial; a.loss_out = f.loss_out; a.correct_out = f.correct_out;
-    a.n_rows = f.n_rows; a.C = f.C; a.DL = f.DL; a.mode = c->sup.loss_mode;
     return a;
 }
 // gat_step: the head's forward and backward as ONE kernel when nothing needs the class probabilities in HBM
-static bool fused_head(gat_ctx* c) {
-    if (c->cfg.keep_taps) return false;
-    if (c->sup.loss_mode != 0) return true;             // the gradient kernel's FUSED form has no shape restriction of its own
-    HeadArgs f{}; HeadBwdArgs b{};
-    head_args(c, &f, &b);
-    return head_step_supported(b);
-}
+static bool fused_head(gat_ctx* c) { return !c->cfg.keep_taps && head_step_supported(head_args(c)); }
 // gat_step: the last layer's forward edge pass, the output head and its backward edge pass fused per destination row
 // (edge_last_fused_kernel) — single shard, fp32, H*D = 64 / D = 8 record path.  The idea: the separate backward finds nothing
 // of the forward's rows left in the caches when a pass's gathers exceed the Infinity Cache; fused per row, the second walk of
@@ -223,15 +210,12 @@ static int hidden_backward(gat_ctx* c) {
 }
 int gat_head_forward(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
     GAT_TRY(check_layer(c, 0));
-    HeadArgs a{}; HeadBwdArgs unused{};
-    head_args(c, &a, &unused);
     GAT_TRY(readout_pool(c));
     GAT_TRY(pair_gather(c));
     GAT_TRY(hidden_forward(c));
     {
         Scope t(c, GAT_K_HEAD_FWD);
-        if (c->sup.loss_mode != 0) GAT_TRY(launch_loss_head_forward(loss_head_args(c), c->stream));
-        else GAT_TRY(launch_head_forward(a, c->stream));
+        GAT_TRY(launch_head_forward(head_args(c), c->stream));
     }
     c->head.y_valid = true; c->head.ran = true;
     if (loss_sum || n_correct) {
@@ -247,12 +231,9 @@ int gat_head_forward(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
 
 int gat_head_backward(gat_ctx* c) {
     GAT_TRY(check_layer(c, 0));
-    HeadArgs unused{}; HeadBwdArgs a{};
-    head_args(c, &unused, &a);
     {
         Scope t(c, GAT_K_HEAD_BWD);
-        if (c->sup.loss_mode != 0) GAT_TRY(launch_loss_head_grad(loss_head_args(c), false, c->stream));
-        else GAT_TRY(launch_head_backward(a, c->stream));
+        GAT_TRY(launch_head_backward(head_args(c), c->stream));
     }
     GAT_TRY(hidden_backward(c));
     GAT_TRY(readout_unpool(c));
@@ -496,17 +477,15 @@ static int forward_phases(gat_ctx* c, int l_end = -1, bool last_edges = true) {
     return 0;
 }
 static int head_step(gat_ctx* c, bool with_gh = true) {
-    HeadArgs f{}; HeadBwdArgs b{};
-    head_args(c, &f, &b);
-    if (!with_gh) b.gh_out = nullptr;               // loss, #correct and grad_Wo only (the fused last layer formed gH itself)
+    HeadArgs a = head_args(c);
+    if (!with_gh) a.gh_out = nullptr;               // loss, #correct and grad_Wo only (the fused last layer formed gH itself)
     GAT_TRY(readout_pool(c));
     GAT_TRY(pair_gather(c));
     GAT_TRY(hidden_forward(c));
     {
         Scope t(c, GAT_K_HEAD_BWD);
         c->head.y_valid = false; c->head.ran = true;
-        if (c->sup.loss_mode != 0) GAT_TRY(launch_loss_head_grad(loss_head_args(c), true, c->stream));
-        else GAT_TRY(launch_head_step(f, b, c->stream));
+        GAT_TRY(launch_head_step(a, c->stream));
     }
     GAT_TRY(hidden_backward(c));
     GAT_TRY(readout_unpool(c));

@@ -419,7 +419,7 @@ int ensure_drop_step(gat_ctx* c);         // gat_abi.hip: the dropout step count
 int ensure_drop_buffers(gat_ctx* c);      // gat_abi.hip: feature-dropout copies of the layer inputs (only once p_f > 0 was set on a complete context)
 int ensure_buffers(gat_ctx* c);           // gat_abi.hip: everything sized by the graph, once graph, features and labels / targets are all set
 void graph_drop(gat_ctx* c);              // gat_abi_step.hip: forgets a captured step (it holds pointers and a kernel sequence); the next one runs eagerly
-LossHeadArgs loss_head_args(gat_ctx* c);  // gat_abi_step.hip: the BCE / MSE head's arguments: rows, outputs and partial buffers of the softmax head's
+HeadArgs head_args(gat_ctx* c);           // gat_abi_step.hip: the output head's arguments in the context's loss mode: the rows it reads (readout / pair / hidden overrides), outputs, partial buffers
 int head_hidden_check(gat_ctx* c);        // gat_abi_features.hip: the head's shape limits at the hidden width and the shard refusal, once the graph (and the loss mode) are known
 bool fused_last(gat_ctx* c);              // gat_abi_step.hip: gat_step runs the last layer's edge passes and the head's gradient as one kernel (GAT_FUSE_LAST=1)
 

@@ -438,7 +438,6 @@ int comm_unique_id(void* id_out);
 int comm_create_rccl(int world, int rank, const void* id_bytes, Comm** out);
 int comm_create_host(int world, int rank, const char* shm_name, int64_t bytes_per_rank, Comm** out);
 
-int launch_pack_result(const float* loss, const int32_t* correct, float* dst3, hipStream_t s);
 // Deferred slab reductions.  Between reduce_batch_begin() and reduce_batch_flush() (same host thread) launch_reduce_gradw /
 // launch_reduce_partials_add queue their job instead of launching it, and the flush runs all of them — plus the result
 // pack, if asked for — as ONE kernel: on Cora / Pubmed-size graphs every launch is ~5 us of a ~250 us step.  The slabs
@@ -578,75 +577,62 @@ struct BnBwdArgs {
 };
 int launch_batch_norm_backward(const BnBwdArgs& a, float* grad_gamma, float* grad_beta, hipStream_t s);
 
-struct HeadArgs {
+// ---- output head (gat_head.hip) --------------------------------------------------------------------------------------
+// One argument struct for the three loss modes and the three entry points.  mode 0: softmax + cross-entropy on integer labels (a
+// negative label: the row is outside the training mask).  GAT_LOSS_BCE / GAT_LOSS_MSE (gatv2_abi.h "loss modes of the output head"): a
+// float target matrix; an entry contributes when its row trains (mask null, or mask[r] != 0) and its target is not NaN, every other
+// entry has loss 0, count 0 and dz 0.  In each mode every kernel forms z with the same expression in the same order, and the forward
+// and the fused step run on grids that pair up, so their loss and count are bitwise equal.
+struct HeadArgs {             // (what every forward reads comes first, together: a kernel fetches its fields with scalar loads)
     const float* Wo;          // [C][DL]
-    const float* HL;          // [n_rows][DL]  post-activation last layer output
-    const int32_t* labels;    // [n_rows]
-    float* y;                 // [n_rows][C]
-    double* loss_partial;     // [blocks]
-    int32_t* correct_partial; // [blocks]
-    float* loss_out;          // [1] device
+    const float* X;           // [n_rows][DL] the head's input rows: H_L, the pooled rows, the pair rows or the hidden layer's Z1
+    const int32_t* labels;    // mode 0: [n_rows]
+    float* y;                 // [n_rows][C] softmax / sigmoid(z) (BCE) / z (MSE): the forward writes it, the mode-0 backward reads it
+    double* loss_partial;     // [head_blocks]
+    int32_t* correct_partial; // [head_blocks]
+    float* loss_out;          // [1] device, or null (loss-mode forward): the block partials are left for the caller (gat_eval_mask)
     int32_t* correct_out;     // [1] device
     int64_t n_rows;
     int32_t C, DL;
-};
-int head_blocks(int64_t n_rows);
-int launch_head_forward(const HeadArgs& a, hipStream_t s);
-
-struct HeadBwdArgs {
-    const float* Wo;          // [C][DL]
-    const float* HL;          // [n_rows][DL]
-    const float* y;           // [n_rows][C]
-    const int32_t* labels;
-    const float* hpre;        // last layer pre-activation [n_rows][H][DL]
-    float* g;                 // [n_rows][H][DL], or null: only gh_out is written and the edge backward of the last
+    int32_t mode;             // 0, GAT_LOSS_BCE or GAT_LOSS_MSE
+    const float* T;           // loss modes: [n_rows][C] targets, NaN = missing
+    const uint8_t* mask;      // loss modes: [n_rows] or null: every row
+    const float* hpre;        // mode 0 with g: last layer pre-activation [n_rows][H][DL]
+    float* g;                 // mode 0: [n_rows][H][DL], or null: only gh_out is written and the edge backward of the last
                               // layer expands it (EdgeBwdArgs::gh) — saves writing 4*N*H*D and reading h_pre here
-    float* gh_out;            // [n_rows][DL]  Wo^T dz  (the head-independent part of g), or null
+    float* gh_out;            // rows of Wo^T dz (the head-independent part of g); null: mode 0 with g, or a step without gH
     int32_t gh_stride;        // floats between consecutive rows of gh_out (0 = DL)
     float* gradWo;            // [C][DL] added into
     float* partial;           // [head_bwd_blocks][C*DL]
-    int64_t n_rows;
-    int32_t C, DL, H;
+    int32_t H;
     float slope;
     int32_t flat_index;
 };
-int head_bwd_blocks(int64_t n_rows, int32_t C, int32_t DL);
-int launch_head_backward(const HeadBwdArgs& a, hipStream_t s);
-// forward + backward of the output head in one kernel (gat_step; y is not stored)
-bool head_step_supported(const HeadBwdArgs& b);
-int launch_head_step(const HeadArgs& f, const HeadBwdArgs& b, hipStream_t s);
-
-// ---- loss modes of the output head (gat_dense_kernels.hip; the contract is in gatv2_abi.h "loss modes of the output head") ----
-// BCE / MSE on a float target matrix.  An entry contributes when its row trains (mask null, or mask[r] != 0) and its target is not NaN;
-// every other entry has loss 0, count 0 and dz 0.  Both kernels form z with the same expression in the same order and run on the
-// same grid, so the loss of the forward kernel and of the fused gradient kernel are bitwise equal.
-struct LossHeadArgs {
-    const float* Wo;          // [C][DL]
-    const float* X;           // [n_rows][DL] the head's input rows (H_L, or the pooled rows of a readout context)
-    const float* T;           // [n_rows][C] targets, NaN = missing
-    const uint8_t* mask;      // [n_rows] or null: every row
-    float* y;                 // forward: [n_rows][C] sigmoid(z) (BCE) / z (MSE)
-    float* gh_out;            // gradient: rows of dz·Wo, gh_stride floats apart (0 = DL)
-    int32_t gh_stride;
-    float* gradWo;            // gradient: [C][DL] added into
-    float* partial;           // gradient: [blocks][C*DL]
-    double* loss_partial;     // [blocks]
-    int32_t* correct_partial; // [blocks]
-    float* loss_out;          // [1] device, or null: the block partials are left for the caller (gat_eval_mask)
-    int32_t* correct_out;
-    int64_t n_rows;
-    int32_t C, DL, mode;      // mode: GAT_LOSS_BCE or GAT_LOSS_MSE
-};
-// blocks either launch uses (<= head_bwd_blocks(n_rows, C, DL) <= head_blocks(n_rows)); < 0: the shape does not fit the LDS tile
+// sizes of the partial buffers: upper bounds of every head grid, functions of the row count alone
+int head_blocks(int64_t n_rows);
+int head_bwd_blocks(int64_t n_rows);
+// blocks every launch of a loss mode uses (<= head_bwd_blocks <= head_blocks); < 0: the shape does not fit the LDS tile
 int loss_head_blocks(int64_t n_rows, int32_t C, int32_t DL, int32_t mode);
-int launch_loss_head_forward(const LossHeadArgs& a, hipStream_t s);
-// fused: also the loss / count partials and their finalize (gat_step without keep_taps)
-int launch_loss_head_grad(const LossHeadArgs& a, bool fused, hipStream_t s);
+// forward: y, loss, count.  backward: gH (or g) and gradWo from y (mode 0) or from z formed again (loss modes).  step: forward and
+// backward in one kernel, y is not stored (gat_step without keep_taps) — where head_step_supported(a); gh_out may be null in mode 0.
+int launch_head_forward(const HeadArgs& a, hipStream_t s);
+int launch_head_backward(const HeadArgs& a, hipStream_t s);
+bool head_step_supported(const HeadArgs& a);
+int launch_head_step(const HeadArgs& a, hipStream_t s);
+// The head's own shape limits for rows of DL floats and C columns under loss mode `mode` (the checks its launchers make, without
+// a launch): 0, or GAT_E_UNSUPPORTED with *limit naming the limit that is broken
+int head_shape_check(int32_t C, int32_t DL, int32_t mode, std::string* limit);
+int launch_pack_result(const float* loss, const int32_t* correct, float* dst3, hipStream_t s);
 // lowest flat index of an entry that is +-inf, or (BCE) outside [0, 1]; -1: none.  Device form: one pass, synchronises s.
 int64_t targets_check_host(const float* t, int64_t n, int32_t mode);
 int targets_check_device(const float* d_t, int64_t n, int32_t mode, unsigned long long* d_scratch, int64_t* where, hipStream_t s);
 // part[b] = present entries in the rows of mask (null: all rows) seen by block b, blocks = 256
 int launch_target_count(const float* T, const uint8_t* mask, int64_t n_rows, int32_t C, unsigned long long* part, hipStream_t s);
+// train / validation masks (README R:134 "later"): labels_eff = mask ? label : ~label — the head kernels skip negative
+// labels (no loss, no count, dz = 0); eval_mask: fixed-order block partials of loss / #correct / #nodes over a mask
+int launch_apply_mask(const int32_t* labels, const uint8_t* mask, int32_t* eff, int64_t n, hipStream_t s);
+int launch_eval_mask(const float* y, const int32_t* labels, const uint8_t* mask, int64_t n, int32_t C, double* part_loss,
+                     int32_t* part_cnt, int32_t blocks, hipStream_t s);
 
 // ---- graph-level readout (gat_readout.hip; the contract is in gatv2_abi.h "graph-level readout") ----------------------
 // Work decomposition of the pooling: a graph of at most kReadoutSegRows rows is one item (an empty graph too), a longer one is cut into
@@ -738,9 +724,6 @@ int launch_head_hidden_forward(float* a, const float* b1, int64_t rows, int32_t 
 constexpr int kHiddenPartialRows = 1024;
 int head_hidden_blocks(int64_t rows, int32_t width);
 int launch_head_hidden_backward(float* gz, const float* z1, float* partial, int64_t rows, int32_t width, float slope, hipStream_t s);
-// The output head's own shape limits for rows of DL floats and C columns under loss mode `mode` (the checks its launchers make, without
-// a launch): 0, or GAT_E_UNSUPPORTED with *limit naming the limit that is broken
-int head_shape_check(int32_t C, int32_t DL, int32_t mode, std::string* limit);
 
 // ---- negative sampling (gat_negsample.hip; the contract — the sampling law — is in gatv2_abi.h "negative sampling") ---------------
 // *ascending = every row of the CSR has its sources in non-decreasing order (one pass, synchronises s): the sampler's membership test
@@ -796,11 +779,6 @@ int rank_sizes(int64_t n_rows, int32_t n_cols, RankSizes* out);
 // all launches on s, no synchronisation; afterwards b.stats holds the result
 int launch_rank_stats(const RankArgs& a, const RankBuffers& b, hipStream_t s);
 
-// train / validation masks (README R:134 "later"): labels_eff = mask ? label : ~label — the head kernels skip negative
-// labels (no loss, no count, dz = 0); eval_mask: fixed-order block partials of loss / #correct / #nodes over a mask
-int launch_apply_mask(const int32_t* labels, const uint8_t* mask, int32_t* eff, int64_t n, hipStream_t s);
-int launch_eval_mask(const float* y, const int32_t* labels, const uint8_t* mask, int64_t n, int32_t C, double* part_loss,
-                     int32_t* part_cnt, int32_t blocks, hipStream_t s);
 // p[i] = the (draw0+i)-th draw of the seeded counter stream mapped to (-lim, lim]  (Xavier-uniform, E:186-248)
 int launch_xavier_init(float* p, int64_t n, uint64_t s0, uint64_t draw0, float lim, hipStream_t s);
 int launch_sgd(float* p, const float* g, float lr, int64_t n, hipStream_t s);

@@ -456,7 +456,7 @@ def check_forward(tag, out, one, L, keep_taps):
     """Every forward tap of a rank's own rows is a row-local function of bit-identical inputs (the edge kernels pick per row, the projection
     per row tile, F <= 128 keeps both sides off the split-K projection): bitwise the one-GPU rows, and the same #correct.
     The one relaxation: the LOSS.  head_forward sums the rows' losses per 128-node block of the context's OWN rows, adds the block
-    partials in fp64 and rounds to fp32 (gat_dense_kernels.hip head_finalize_kernel); P shards give P rounded fp32 partial sums that the
+    partials in fp64 and rounds to fp32 (gat_head.hip head_finalize_kernel); P shards give P rounded fp32 partial sums that the
     exchange adds in fp32 — a sum ordered by a size the shard changes.  Nothing is downstream of it (the backward starts from y), so only
     the loss itself is held to 1e-5; y is bitwise."""
     st, ost = stitched(out, L, keep_taps), stitched(one, L, keep_taps)

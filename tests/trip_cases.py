@@ -35,7 +35,7 @@ TIMEOUT = {"cap1": 240, "cap3": 240, "cap1_fused": 120, "cap1_wave_rows": 120}
 SEG = 16                # build_worklist (gat_abi_data.hip:14): the segment length of a graph below 512 Ki edges
 MAX_N = 4               # gat_edge_kernels.hip:1209  LPE = HD / N, G = 64 / LPE with N <= 4 channels per lane (stash_n, :2149)
 WAVES = 4               # waves of a backward block: q = blockIdx.x * 4 + wave (:1236), nwaves = gridDim.x * 4
-HEAD_TILE = 128         # head_blocks / head_bwd_blocks (gat_dense_kernels.hip:832, :895): 128-row tiles
+HEAD_TILE = 128         # head_blocks / head_bwd_blocks (gat_head.hip:667, :673): 128-row tiles
 K_U = 4                 # gat_head_hidden.hip: kU rows per lane and trip
 
 
@@ -66,7 +66,7 @@ def edge_trips(n_items, hd, cap):
 
 
 def row_shape(hd, norm):
-    """(lanes per row, rows per block) of res_backward_shape / norm_backward_shape (gat_dense_kernels.hip:718, :742) and hidden_shape
+    """(lanes per row, rows per block) of res_backward_shape / norm_backward_shape (gat_dense_kernels.hip:346, :370) and hidden_shape
     (gat_head_hidden.hip:134, the res_backward rule)."""
     groups = hd // 4 if hd % 4 == 0 else hd
     if norm:
