@@ -45,6 +45,16 @@ class _Config(C.Structure):
     ]
 
 
+class _OptimizerConfig(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32), ("flags", C.c_int32),
+        ("lr", C.c_float), ("momentum", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+        ("weight_decay", C.c_float),
+        ("decay_groups", C.c_uint32),
+        ("clip_mode", C.c_int32), ("clip_threshold", C.c_float),
+    ]
+
+
 # enums of the header
 PARAM_W, PARAM_A, PARAM_WO, PARAM_WRES, PARAM_B = 0, 1, 2, 3, 4
 PARAM_LN_G, PARAM_LN_B = 5, 6
@@ -88,6 +98,14 @@ COMM_ID_BYTES = 128
 PATH_GENERIC_SHAPE, PATH_FAST, PATH_GENERIC_SIZE = 0, 1, 2
 GRAPH_SELF_LOOPS, GRAPH_SYMMETRIZE, GRAPH_COALESCE = 1, 2, 4      # flags of the graph builder (graph_from_coo, set_graph_coo)
 CSR_OK, CSR_BAD_START, CSR_BAD_END, CSR_NOT_MONOTONE, CSR_COL_RANGE = range(5)   # graph_check_device
+
+OPT_SGD, OPT_ADAM, OPT_ADAMW = 1, 2, 3                                 # optimizer on the device (set_optimizer)
+OPT_KINDS = {"sgd": OPT_SGD, "adam": OPT_ADAM, "adamw": OPT_ADAMW}
+OPT_NESTEROV = 1
+CLIP_NONE, CLIP_PER_GROUP, CLIP_GLOBAL = 0, 1, 2
+CLIP_MODES = {"none": CLIP_NONE, "group": CLIP_PER_GROUP, "global": CLIP_GLOBAL}
+OPT_STATE_M, OPT_STATE_V, OPT_STATE_MOMENTUM = 0, 1, 2
+DECAY_ALL_GROUPS = 0xFFFFFFFF
 
 _lib: Optional[C.CDLL] = None
 
@@ -185,6 +203,14 @@ def _declare(lib: C.CDLL) -> None:
         "gat_clip": [vp, f32],
         "gat_step_sgd": [vp, f32],
         "gat_step_adam": [vp, f32, f32, f32, f32, i32],
+        "gat_set_optimizer": [vp, P(_OptimizerConfig)],
+        "gat_optimizer_step": [vp],
+        "gat_set_lr": [vp, f32],
+        "gat_optimizer_info": [vp, P(_OptimizerConfig), P(i64), P(f32), P(f32), vp],
+        "gat_optimizer_state_get": [vp, C.c_int, C.c_int, vp, i64],
+        "gat_optimizer_state_set": [vp, C.c_int, C.c_int, vp, i64],
+        "gat_optimizer_step_count_set": [vp, i64],
+        "gat_train_step": [vp, P(f32), P(i32)],
         "gat_layer_project": [vp, i32],
         "gat_layer_forward_edges": [vp, i32],
         "gat_head_forward": [vp, P(f32), P(i32)],
@@ -787,6 +813,71 @@ class GatContext:
 
     def step_adam(self, lr: float, beta1: float, beta2: float, eps: float, t: int):
         _chk(self.lib.gat_step_adam(self._ctx, lr, beta1, beta2, eps, t))
+
+    # -- optimizer on the device (gatv2_abi.h "optimizer")
+    def set_optimizer(self, kind, lr: float, *, momentum: float = 0.0, nesterov: bool = False, betas=(0.9, 0.999), eps: float = 1e-8,
+                      weight_decay: float = 0.0, decay_groups=None, clip=None, flags: int = 0):
+        """Configure the optimizer whose step runs on the device: ``kind`` "sgd" | "adam" | "adamw" (or an OPT_* value); ``decay_groups``
+        None = every group (torch's behaviour), a bit mask, or an iterable of PARAM_* groups that take the weight decay; ``clip`` None,
+        ("group", thr) = every group by its own norm (clip()'s law) or ("global", thr) = clip_grad_norm_ over all parameters.  Counts
+        as a first params_* call (the packed sizes are final) and drops a captured step graph.  ``flags``: raw OPT_* bits (or-ed in)."""
+        q = _OptimizerConfig()
+        q.kind = OPT_KINDS[kind] if isinstance(kind, str) else int(kind)
+        q.flags = int(flags) | (OPT_NESTEROV if nesterov else 0)
+        q.lr, q.momentum, q.beta1, q.beta2, q.eps, q.weight_decay = float(lr), float(momentum), float(betas[0]), float(betas[1]), float(eps), float(weight_decay)
+        if decay_groups is None:
+            q.decay_groups = DECAY_ALL_GROUPS
+        elif isinstance(decay_groups, (int, np.integer)):
+            q.decay_groups = int(decay_groups)
+        else:
+            q.decay_groups = sum(1 << int(g) for g in set(decay_groups))
+        if clip is None:
+            q.clip_mode, q.clip_threshold = CLIP_NONE, 0.0
+        else:
+            mode, thr = clip
+            q.clip_mode = CLIP_MODES[mode] if isinstance(mode, str) else int(mode)
+            q.clip_threshold = float(thr)
+        _chk(self.lib.gat_set_optimizer(self._ctx, C.byref(q)))
+
+    def optimizer_step(self):
+        """Clip and update in two launches, from the packed gradients as they are (they are only read)."""
+        _chk(self.lib.gat_optimizer_step(self._ctx))
+
+    def set_lr(self, lr: float):
+        """Write the device learning rate on the context's stream; a captured step graph stays valid."""
+        _chk(self.lib.gat_set_lr(self._ctx, float(lr)))
+
+    def optimizer_info(self) -> dict:
+        """The configuration, the device step count ``t`` and ``lr``, and the norms of the last step: ``group_norms`` [10], ``global_norm``."""
+        q, t, lr, gn = _OptimizerConfig(), C.c_int64(), C.c_float(), C.c_float()
+        norms = np.zeros(len(PARAM_GROUPS_ALL), np.float32)
+        _chk(self.lib.gat_optimizer_info(self._ctx, C.byref(q), C.byref(t), C.byref(lr), C.byref(gn), _np_ptr(norms)))
+        out = {name: getattr(q, name) for name, _ in _OptimizerConfig._fields_}
+        out.update(t=t.value, lr=lr.value, global_norm=gn.value, group_norms=norms)
+        return out
+
+    def optimizer_state(self, which: int, group: int) -> np.ndarray:
+        """One group of an optimizer state buffer (OPT_STATE_M / _V / _MOMENTUM), flat like params_get."""
+        a = np.empty(self.param_count(group), np.float32)
+        _chk(self.lib.gat_optimizer_state_get(self._ctx, int(which), int(group), _np_ptr(a), a.size))
+        return a
+
+    def set_optimizer_state(self, which: int, group: int, arr):
+        a = np.ascontiguousarray(arr, np.float32).reshape(-1)
+        _chk(self.lib.gat_optimizer_state_set(self._ctx, int(which), int(group), _np_ptr(a), a.size))
+
+    def set_optimizer_step_count(self, t: int):
+        _chk(self.lib.gat_optimizer_step_count_set(self._ctx, int(t)))
+
+    def train_step(self, want_loss: bool = True):
+        """zero_grad + step + optimizer_step as one call (with step_graph(True): one replayed launch).  Returns (loss sum, #correct) of the
+        forward before the update."""
+        if not want_loss:
+            _chk(self.lib.gat_train_step(self._ctx, None, None))
+            return None
+        loss, corr = C.c_float(), C.c_int32()
+        _chk(self.lib.gat_train_step(self._ctx, C.byref(loss), C.byref(corr)))
+        return loss.value, corr.value
 
     # -- phases
     def layer_project(self, l: int):

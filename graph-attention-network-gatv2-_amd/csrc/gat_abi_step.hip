@@ -710,10 +710,26 @@ static int step_body(gat_ctx* c, float* host_tail = nullptr, bool* host_done = n
     }
     return batch.finish(c, true, host_tail, host_done);
 }
-static int step_graph(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
+// What the replay slot holds: the body of gat_step (entry 0), or of gat_train_step (entry 1) — the packed gradients zeroed in front of
+// it, the optimizer's two launches behind it (the result tail sits behind the gradients and is packed by the body: the update does not
+// touch it).
+static int entry_body(gat_ctx* c, int entry, float* host_tail = nullptr, bool* host_done = nullptr) {
+    if (entry == 0) return step_body(c, host_tail, host_done);
+    {
+        Scope t(c, GAT_K_MISC);
+        GAT_HIP(hipMemsetAsync(c->packed.grads, 0, (size_t)n_params(c) * sizeof(float), c->stream));
+    }
+    GAT_TRY(step_body(c, host_tail, host_done));
+    return optimizer_launch(c);
+}
+static int step_graph(gat_ctx* c, int entry, float* loss_sum, int32_t* n_correct) {
     const int64_t np = n_params(c);
+    if (c->replay.entry != entry) {                               // the slot holds (or was warmed by) the other entry point: start over
+        graph_drop(c);
+        c->replay.entry = entry;
+    }
     if (c->replay.state == 1 && c->replay.warm == 0) {            // eager warm-up
-        GAT_TRY(step_body(c));
+        GAT_TRY(entry_body(c, entry));
         c->replay.warm = 1;
         return (loss_sum || n_correct) ? read_result_tail(c, loss_sum, n_correct) : 0;
     }
@@ -722,7 +738,7 @@ static int step_graph(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
         GAT_HIP(hipStreamSynchronize(c->stream));
         GAT_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         bool host_done = false;                             // the batch kernel's pack block wrote the pinned copy itself
-        int rc = step_body(c, c->replay.pinned_tail, &host_done);
+        int rc = entry_body(c, entry, c->replay.pinned_tail, &host_done);
         if (rc == 0 && !host_done && hipMemcpyAsync(c->replay.pinned_tail, c->packed.grads + np, 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
             rc = fail(GAT_E_STATE, "gat_step_graph: capture of the result copy failed");
         hipGraph_t g = nullptr;
@@ -762,10 +778,24 @@ int gat_step_graph_state(gat_ctx* c, int32_t* state) {
 
 int gat_step(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
     GAT_TRY(check_step(c, "gat_step"));
-    if (c->replay.state != 0) return step_graph(c, loss_sum, n_correct);
+    if (c->replay.state != 0) return step_graph(c, 0, loss_sum, n_correct);
     GAT_TRY(reduce_begin(c));
     GAT_TRY(step_body(c));                              // ends with the packed {loss, correct} behind the gradients
     GAT_TRY(reduce_end(c, n_params(c) + 3));
+    if (!loss_sum && !n_correct) return 0;
+    return read_result_tail(c, loss_sum, n_correct);
+}
+// gatv2_abi.h "optimizer": zero the gradients, the step, the update — eagerly here (with a transport: the update reads the gradients the
+// all-reduce has summed), or as the replay slot's entry 1
+int gat_train_step(gat_ctx* c, float* loss_sum, int32_t* n_correct) {
+    GAT_TRY(check_step(c, "gat_train_step"));
+    if (!c->opt.have) return fail(GAT_E_STATE, "gat_train_step: call gat_set_optimizer first");
+    if (c->replay.state != 0) return step_graph(c, 1, loss_sum, n_correct);
+    GAT_TRY(gat_zero_grad(c));
+    GAT_TRY(reduce_begin(c));
+    GAT_TRY(step_body(c));
+    GAT_TRY(reduce_end(c, n_params(c) + 3));
+    GAT_TRY(optimizer_launch(c));
     if (!loss_sum && !n_correct) return 0;
     return read_result_tail(c, loss_sum, n_correct);
 }

@@ -86,6 +86,16 @@ struct gat_ctx {
         float* params = nullptr; float* grads = nullptr; bool touched = false;
         float* adam_m = nullptr; float* adam_v = nullptr; float* clip_scratch = nullptr;
     } packed;
+    // The optimizer on the device (gatv2_abi.h "optimizer"; gat_abi_optimizer.hip): the configuration, the state of its kind over the packed
+    // layout (m, v: the Adam kinds; buf: SGD with momentum > 0; all apart from adam_m / adam_v above, which stay gat_step_adam's), the
+    // device scalars t and lr, the record of norms [kOptGroups + 1], the block table with its partials.  have: gat_set_optimizer was called.
+    struct Optimizer {
+        bool have = false; gat_optimizer_config cfg{};
+        float* m = nullptr; float* v = nullptr; float* buf = nullptr;
+        unsigned long long* t = nullptr; float* lr = nullptr; float* norms = nullptr;
+        gat::OptBlock* table = nullptr; float* partial = nullptr; int32_t n_blocks = 0;
+        int32_t group_block0[gat::kOptGroups + 1] = {0};
+    } opt;
     // Residual / bias (GAT_RES_* flags) and layer normalisation (GAT_NORM_* flags): G and agg [n_rows][HDmax] are dL/dh_pre and
     // h_pre - (R + b) of the layer whose backward runs; partial [L][kResPartialRows][HDmax] block column sums of G (grad_b) and
     // norm_partial [L][2][kResPartialRows][HDmax] (grad_gamma / grad_beta), one region per layer; the slabs of gradWres likewise.
@@ -204,8 +214,9 @@ struct gat_ctx {
     // gat_step as a replayed hipGraph (gat_step_graph).  state: 0 off, 1 armed (next step runs eagerly, then captures), 2 ready;
     // pinned_tail [4]: host-pinned landing zone of {loss, correct lo, correct hi}; y_after: what head.y_valid is after the captured body
     // (a replay runs none of the host code that keeps the flag: false when the body's head is the fused one, which writes no y).
+    // entry: which entry point the slot holds or is warming up for (0 gat_step, 1 gat_train_step).
     struct Replay {
-        int state = 0, warm = 0; bool y_after = false;
+        int state = 0, warm = 0, entry = 0; bool y_after = false;
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
         float* pinned_tail = nullptr;
     } replay;
@@ -421,6 +432,7 @@ int ensure_buffers(gat_ctx* c);           // gat_abi.hip: everything sized by th
 void graph_drop(gat_ctx* c);              // gat_abi_step.hip: forgets a captured step (it holds pointers and a kernel sequence); the next one runs eagerly
 HeadArgs head_args(gat_ctx* c);           // gat_abi_step.hip: the output head's arguments in the context's loss mode: the rows it reads (readout / pair / hidden overrides), outputs, partial buffers
 int head_hidden_check(gat_ctx* c);        // gat_abi_features.hip: the head's shape limits at the hidden width and the shard refusal, once the graph (and the loss mode) are known
+int optimizer_launch(gat_ctx* c);         // gat_abi_optimizer.hip: the two launches of an optimizer step on the context's stream (gat_set_optimizer was called)
 bool fused_last(gat_ctx* c);              // gat_abi_step.hip: gat_step runs the last layer's edge passes and the head's gradient as one kernel (GAT_FUSE_LAST=1)
 
 }  // namespace gat

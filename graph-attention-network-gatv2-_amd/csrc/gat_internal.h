@@ -787,6 +787,34 @@ int launch_adam(float* p, const float* g, float* m, float* v, float lr, int64_t 
 // per-group clip (E:250-278) with the norm kept on the device; scratch >= 1 float
 int launch_clip(float* g, int64_t n, float thresh, float* scratch, hipStream_t s);
 
+// ---- optimizer step on the device (gat_optimizer.hip; the law is in gatv2_abi.h "optimizer") ---------------------------------------
+// The block table: row b = the entries [first, first + count) of the packed buffers, all of parameter group `group`; count is at most
+// kOptBlockEntries, a group of 0 entries has no row, a short group is one partial row.  group_block0 [kOptGroups + 1]: the rows of group
+// k are [group_block0[k], group_block0[k + 1]) — the partials a clip norm adds, in that order.
+constexpr int kOptGroups = 10;                       // GAT_PARAM_* 0 .. 9
+constexpr int kOptThreads = 256;
+constexpr int kOptBlockEntries = 1024;
+struct OptBlock { int64_t first; int32_t count; int32_t group; };
+struct OptArgs {
+    float* p = nullptr; const float* g = nullptr;    // packed parameters (updated) and gradients (read only)
+    float* s0 = nullptr; float* s1 = nullptr;        // state: Adam kinds m, v; SGD the momentum buffer (null: momentum = 0), -
+    const OptBlock* table = nullptr; int32_t n_blocks = 0;
+    int32_t group_block0[kOptGroups + 1] = {0};
+    float* partial = nullptr;                        // [n_blocks] block sums of squares of g
+    unsigned long long* t = nullptr;                 // step counter: opt_prepare advances it, opt_apply reads it
+    const float* lr = nullptr;                       // the learning rate (gat_set_lr)
+    float* norms = nullptr;                          // [kOptGroups + 1] the record of gat_optimizer_info: n_k, then the global n
+    int32_t kind = 0, flags = 0, clip_mode = 0;
+    float momentum = 0.f, beta1 = 0.f, beta2 = 0.f, eps = 0.f, weight_decay = 0.f, clip_threshold = 0.f;
+    uint32_t decay_groups = 0;
+};
+void opt_build_table(const int64_t* group_off, const int64_t* group_cnt, std::vector<OptBlock>* table, int32_t* group_block0);
+// opt_prepare + opt_apply on s: two launches, no synchronisation, capturable
+int launch_opt_step(const OptArgs& a, hipStream_t s);
+// one-lane stream-ordered writes of the device scalars
+int launch_opt_set_lr(float* lr, float v, hipStream_t s);
+int launch_opt_set_count(unsigned long long* t, uint64_t v, hipStream_t s);
+
 // ---- graph construction (gat_graph.hip; the contract is in gatv2_abi.h "graph construction") ---------------------------
 // coo_sort: range check + packing + sort (+ unique) of the edge keys; afterwards b->m is the edge count of the result and
 // coo_fill writes row_ptr [n_rows+1] / col_idx [m].  coo_free releases the temporaries (also after a failure).

@@ -54,6 +54,12 @@
 // --rank-metrics K1,K2,... (with --val-mask, --ranks 1, not --loss mse): one more line behind every validation line — ROC-AUC, average
 // precision, MRR and Hits@K of the validation rows (gatv2_abi.h "ranking metrics"), macro-averaged over the output columns that have both
 // classes, then the count of those columns.  Every other line is printed as without the flag.
+// --weight-decay X, --optimizer adamw, --momentum M [--nesterov], --clip-global T, --no-decay-bias-norm, --fused-step: the update runs on
+// the device-side optimizer (gatv2_abi.h "optimizer step on the device": gat_set_optimizer once, then gat_optimizer_step in place of
+// gat_clip + gat_step_*; --clip becomes its per-group clip at 5, --clip-global its global-norm clip; --no-decay-bias-norm clears the decay
+// bits of b, gamma, beta and b1).  --fused-step makes the epoch body the one call gat_train_step (on one rank a replayed graph) and moves
+// the validation line behind the update, from a forward of its own.  Bad values are refused with the usage text before any GPU call.
+// With none of these flags the program makes the reference's calls and prints the reference's text.
 // --add-self-loops / --undirected / --coalesce: the graph is rebuilt on the device before training (gat_graph_from_coo:
 // GAT_GRAPH_SELF_LOOPS / SYMMETRIZE / COALESCE, applied in that order); a CSR dataset is expanded to an edge list first.
 // Edge-list dataset: a folder with edges.txt (one "src dst" pair per line, a message flows src -> dst) instead of
@@ -121,6 +127,10 @@ struct Options {
     std::string loss = "softmax";         // --loss softmax|bce|mse: bce / mse read targets.txt (rows of C floats, nan allowed) in place of labels.txt
     int head_hidden = 0; int head_act = 0;   // --head-hidden K, --head-act relu|lrelu (GAT_HEAD_ACT_*): a hidden layer in front of the output head
     std::vector<int32_t> rank_ks; bool rank_metrics = false;      // --rank-metrics K1,K2,...: a ranking line behind every validation line
+    // the optimizer on the device (gatv2_abi.h "optimizer"): any of these flags moves the update from gat_clip / gat_step_* to gat_set_optimizer
+    float weight_decay = 0.f, momentum = 0.f, clip_global = 0.f;  // --weight-decay X, --momentum M, --clip-global T
+    bool nesterov = false, no_decay_bias_norm = false, fused_step = false;   // --nesterov, --no-decay-bias-norm, --fused-step
+    bool device_optimizer() const { return weight_decay > 0.f || momentum > 0.f || clip_global > 0.f || nesterov || no_decay_bias_norm || fused_step || optimizer == "adamw"; }
 };
 
 // A CSR built before the ranks were forked (main): row_ptr [n + 1] then col_idx [e] in shared memory.
@@ -170,6 +180,15 @@ const char* kUsage =
     "                          (n columns)\" — ROC-AUC, average precision, MRR (every positive against all negatives) and Hits@K of the\n"
     "                          validation rows, ranked on the device, macro-averaged over the n output columns that have both classes\n"
     "                          (up to 8 K >= 1; --ranks 1; not with --loss mse)\n"
+    "            --weight-decay X   weight decay: L2 (added to the gradient) with --optimizer sgd | adam, decoupled with --optimizer adamw\n"
+    "            --optimizer adamw  AdamW (beside sgd and adam)\n"
+    "            --momentum M [--nesterov]   SGD momentum, 0 <= M < 1 (--optimizer sgd)\n"
+    "            --clip-global T    clip the gradient by its norm over ALL parameters (torch's clip_grad_norm_), T > 0; --clip alone stays the\n"
+    "                          per-group clip at 5\n"
+    "            --no-decay-bias-norm   no weight decay on the biases and the norm parameters (b, gamma, beta, b1)\n"
+    "            --fused-step       the epoch body is ONE call (gat_train_step: zero, forward, backward, clip, update), replayed as one launch\n"
+    "                          on one rank; validation then comes from a forward of its own after the update\n"
+    "                          (any of these flags runs the update on the device-side optimizer, gatv2_abi.h \"optimizer\": t and lr live there)\n"
     "            --ranks P [--transport rccl|host] [--halo 0|1|2]\n";
 
 struct RankEnv {                      // one forked process per GPU
@@ -220,7 +239,7 @@ Options parse_args(int argc, char** argv) {
         } else if (a == "--clip") o.clip = true;
         else if (a == "--optimizer" && has_val) {
             o.optimizer = argv[++i];
-            if (o.optimizer != "sgd" && o.optimizer != "adam") die("Invalid optimizer choice. Use 'sgd' or 'adam'\n");
+            if (o.optimizer != "sgd" && o.optimizer != "adam" && o.optimizer != "adamw") die("Invalid optimizer choice. Use 'sgd' or 'adam'\n");
         } else if (a == "--beta1" && has_val) { o.beta1 = std::stof(argv[++i]); o.beta1_given = true; }
         else if (a == "--beta2" && has_val) { o.beta2 = std::stof(argv[++i]); o.beta2_given = true; }
         else if (a == "--lr" && has_val) o.lr = std::stof(argv[++i]);
@@ -266,6 +285,12 @@ Options parse_args(int argc, char** argv) {
         else if (a == "--neg-both-directions") o.neg_flags |= GAT_NEG_BOTH_DIRECTIONS;
         else if (a == "--neg-allow-self") o.neg_flags |= GAT_NEG_ALLOW_SELF;
         else if (a == "--loss" && has_val) o.loss = argv[++i];
+        else if (a == "--weight-decay" && has_val) o.weight_decay = std::strtof(argv[++i], nullptr);       // (the four values are checked in main)
+        else if (a == "--momentum" && has_val) o.momentum = std::strtof(argv[++i], nullptr);
+        else if (a == "--clip-global" && has_val) o.clip_global = std::strtof(argv[++i], nullptr);
+        else if (a == "--nesterov") o.nesterov = true;
+        else if (a == "--no-decay-bias-norm") o.no_decay_bias_norm = true;
+        else if (a == "--fused-step") o.fused_step = true;
         else if (a == "--head-hidden" && has_val) o.head_hidden = std::atoi(argv[++i]);       // (checked in main, before anything touches the GPU)
         else if (a == "--head-act" && has_val) o.head_act = std::string(argv[++i]) == "lrelu" ? GAT_HEAD_ACT_LRELU : 0;
         else if (a == "--rank-metrics" && has_val) {          // (checked in main, before anything touches the GPU)
@@ -283,7 +308,7 @@ Options parse_args(int argc, char** argv) {
             if (o.transport != "rccl" && o.transport != "host") die("Invalid transport choice. Use 'rccl' or 'host'\n");
         }
     }
-    if (o.optimizer == "adam") {
+    if (o.optimizer == "adam" || o.optimizer == "adamw") {
         if (o.beta1 <= 0.0f || o.beta1 >= 1.0f || o.beta2 <= 0.0f || o.beta2 >= 1.0f)
             die("Error: For Adam optimizer, beta1 and beta2 must be in (0,1).\n");
     } else if (o.beta1_given || o.beta2_given) {
@@ -745,7 +770,7 @@ int run(const Options& o, const RankEnv& env) {
         std::printf(" (%d column%s)\n", n, n == 1 ? "" : "s");
     };
     const bool dropout = o.dropout > 0.f || o.attn_dropout > 0.f || o.drop_edge > 0.f;
-    const bool eval_pass = dropout || o.batch_norm;   // validation needs a forward of its own in eval mode
+    const bool eval_pass = dropout || o.batch_norm || o.fused_step;   // validation needs a forward of its own in eval mode (--fused-step: the step leaves no forward to read)
     if (dropout) check(gat_set_dropout(ctx, o.dropout, o.attn_dropout, o.seed, 0), "gat_set_dropout");   // also seeds DropEdge
     if (o.drop_edge > 0.f) check(gat_set_dropedge(ctx, o.drop_edge, o.drop_edge_flags), "gat_set_dropedge");
     check(gat_params_init(ctx, o.seed), "xavier_init_kernel");
@@ -784,6 +809,21 @@ int run(const Options& o, const RankEnv& env) {
         std::printf("Negative sampling: %s, pairs %lld .. %lld redrawn before every epoch\n", o.neg_sampling.c_str(), o.neg_first, (long long)NH - 1);
     }
 
+    // any optimizer flag beyond the reference's: the update runs on the device-side optimizer (clip, decay and update in two launches)
+    const bool dev_opt = o.device_optimizer();
+    if (dev_opt) {
+        gat_optimizer_config oc{};
+        oc.kind = o.optimizer == "adamw" ? GAT_OPT_ADAMW : o.optimizer == "adam" ? GAT_OPT_ADAM : GAT_OPT_SGD;
+        oc.flags = o.nesterov ? GAT_OPT_NESTEROV : 0;
+        oc.lr = o.lr; oc.momentum = o.momentum; oc.beta1 = o.beta1; oc.beta2 = o.beta2; oc.eps = 1e-8f; oc.weight_decay = o.weight_decay;
+        oc.decay_groups = 0xFFFFFFFFu;
+        if (o.no_decay_bias_norm)
+            oc.decay_groups = ((1u << (GAT_PARAM_HEAD_B + 1)) - 1u) & ~((1u << GAT_PARAM_B) | (1u << GAT_PARAM_NORM_G) | (1u << GAT_PARAM_NORM_B) | (1u << GAT_PARAM_HEAD_B));
+        oc.clip_mode = o.clip_global > 0.f ? GAT_CLIP_GLOBAL : o.clip ? GAT_CLIP_PER_GROUP : GAT_CLIP_NONE;
+        oc.clip_threshold = o.clip_global > 0.f ? o.clip_global : 5.0f;
+        check(gat_set_optimizer(ctx, &oc), "gat_set_optimizer");
+        if (o.fused_step && env.world == 1) check(gat_step_graph(ctx, 1), "gat_step_graph");
+    }
     check(gat_zero_grad(ctx), "gat_zero_grad");
     for (int epoch = 1; epoch <= o.epochs; ++epoch) {
         const auto start = std::chrono::high_resolution_clock::now();
@@ -795,7 +835,8 @@ int run(const Options& o, const RankEnv& env) {
             if (unfiltered) fprintf(stderr, "Warning: epoch %d: %lld negative(s) found no non-edge in %d attempts and are unfiltered\n", epoch, (long long)unfiltered, GAT_NEG_TRIES);
         }
         float loss_sum = 0.f; int32_t n_correct = 0;
-        check(gat_forward(ctx, &loss_sum, &n_correct), "gatv2 forward");
+        if (o.fused_step) check(gat_train_step(ctx, &loss_sum, &n_correct), "gat_train_step");
+        else check(gat_forward(ctx, &loss_sum, &n_correct), "gatv2 forward");
         if (loss_mode == GAT_LOSS_SOFTMAX_CE) std::printf("\nAvg Loss: %f, Accuracy: %.2f%%\n", loss_sum / n_train, 100.0f * (static_cast<float>(n_correct) / n_train));
         else if (loss_mode == GAT_LOSS_BCE) std::printf("\nAvg Loss: %f, Accuracy: %.2f%%\n", loss_sum / train_entries, 100.0f * (static_cast<float>(n_correct) / train_entries));
         else std::printf("\nAvg Loss: %f\n", loss_sum / train_entries);
@@ -805,11 +846,16 @@ int run(const Options& o, const RankEnv& env) {
             print_val(vl, vc, vn);
             print_rank();
         }
-        check(gat_backward(ctx), "gatv2 backward");
-        if (o.clip) check(gat_clip(ctx, 5.0f), "clip_grad_norm");                   // E:1563
-        if (o.optimizer == "adam") check(gat_step_adam(ctx, o.lr, o.beta1, o.beta2, 1e-8f, epoch), "adam_update_kernel");
-        else check(gat_step_sgd(ctx, o.lr), "sgd_update_kernel");
-        check(gat_zero_grad(ctx), "gat_zero_grad");
+        if (!o.fused_step) {                      // (--fused-step: zero, forward, backward, clip and update were the one call above)
+            check(gat_backward(ctx), "gatv2 backward");
+            if (dev_opt) check(gat_optimizer_step(ctx), "gat_optimizer_step");      // clip, decay and update in two launches
+            else {
+                if (o.clip) check(gat_clip(ctx, 5.0f), "clip_grad_norm");           // E:1563
+                if (o.optimizer == "adam") check(gat_step_adam(ctx, o.lr, o.beta1, o.beta2, 1e-8f, epoch), "adam_update_kernel");
+                else check(gat_step_sgd(ctx, o.lr), "sgd_update_kernel");
+            }
+            check(gat_zero_grad(ctx), "gat_zero_grad");
+        }
         if (!val_m.empty() && eval_pass) {        // validation of the updated model, without dropout, on the running statistics
             double vl = 0.0; int32_t vc = 0, vn = 0;
             check(gat_set_training(ctx, 0), "gat_set_training");
@@ -867,6 +913,7 @@ int main(int argc, char** argv) {
     bool graph_flag = false, edge_feat_flag = false, readout_flag = false, targets_flag = false, pairs_flag = false;
     bool neg_flag = false, neg_corrupt = false; long long neg_first = -1;
     bool rank_flag = false, val_flag = false, mse_flag = false, hidden_flag = false;
+    bool momentum_flag = false, momentum_pos = false, nesterov_flag = false; std::string optimizer_name = "sgd";
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--help") { std::cout << kUsage; return 0; }
@@ -917,6 +964,18 @@ int main(int argc, char** argv) {
             const std::string v = i + 1 < argc ? argv[i + 1] : "";
             if (v != "relu" && v != "lrelu") die("Error: --head-act must be relu or lrelu\n");
         }
+        if (a == "--weight-decay" || a == "--momentum" || a == "--clip-global") {      // one finite number in the flag's range, nothing else
+            const char* v = i + 1 < argc ? argv[i + 1] : "";
+            char* end = nullptr;
+            const float x = std::strtof(v, &end);
+            const bool parsed = end != v && *end == '\0' && std::isfinite(x);
+            if (a == "--weight-decay" && !(parsed && x >= 0.f)) die(std::string("Error: --weight-decay must be a finite number >= 0\n") + kUsage);
+            if (a == "--momentum" && !(parsed && x >= 0.f && x < 1.f)) die(std::string("Error: --momentum must be in [0, 1)\n") + kUsage);
+            if (a == "--clip-global" && !(parsed && x > 0.f)) die(std::string("Error: --clip-global must be a finite number > 0\n") + kUsage);
+            if (a == "--momentum") { momentum_flag = true; momentum_pos = x > 0.f; }
+        }
+        if (a == "--nesterov") nesterov_flag = true;
+        if (a == "--optimizer" && i + 1 < argc) optimizer_name = argv[i + 1];
         if (a == "--loss") {
             const std::string v = i + 1 < argc ? argv[i + 1] : "";
             if (v != "softmax" && v != "bce" && v != "mse") die("Error: --loss must be softmax, bce or mse\n");
@@ -924,6 +983,8 @@ int main(int argc, char** argv) {
             mse_flag = v == "mse";
         }
     }
+    if (momentum_flag && momentum_pos && optimizer_name != "sgd") die(std::string("Error: --momentum needs --optimizer sgd\n") + kUsage);
+    if (nesterov_flag && !(momentum_pos && optimizer_name == "sgd")) die(std::string("Error: --nesterov needs --optimizer sgd and --momentum M > 0\n") + kUsage);
     if (rank_flag && !val_flag) die("Error: --rank-metrics needs --val-mask: the ranking is over the validation rows\n");
     if (rank_flag && multi) die("Error: --rank-metrics needs --ranks 1: a ranking is global and cannot be summed over shards\n");
     if (rank_flag && mse_flag) die("Error: --rank-metrics cannot be combined with --loss mse: a regression target has no binary relevance\n");

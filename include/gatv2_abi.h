@@ -988,6 +988,75 @@ int gat_head_hidden_info(gat_ctx* ctx, int32_t* width, int32_t* flags);   /* (0,
 int gat_op_head_hidden_forward(float* d_a, const float* d_b1, int64_t rows, int32_t width, float slope, void* stream);
 int gat_op_head_hidden_backward(float* d_gz, const float* d_z1, int64_t rows, int32_t width, float slope, float* d_grad_b1, void* stream);
 
+/* ---- optimizer step on the device (beyond the reference, whose three kernels stay behind gat_clip / gat_step_sgd / gat_step_adam): weight
+ *      decay, SGD with momentum, Adam with L2, AdamW, per-group and global-norm clipping, one captured launch per epoch -------------------
+ * The law.  p, g and the state are entries of the packed buffers, k is the parameter group (GAT_PARAM_*) of an entry, fp32 throughout.
+ *   Clip factor, with s_k the sum of squares of group k's gradient:
+ *     GAT_CLIP_NONE       c_k = 1
+ *     GAT_CLIP_PER_GROUP  n_k = sqrt(s_k);  c_k = thr / (n_k + 1e-9f) if n_k > thr, else 1                       (gat_clip's law)
+ *     GAT_CLIP_GLOBAL     n = sqrt(sum_k s_k), groups added in ascending order;  c = min(1, thr / (n + 1e-6f))   (clip_grad_norm_'s law)
+ *   g^ = c_k * g.  The gradient buffer is only read: after the call it still holds the unclipped g.  A non-finite norm propagates as the
+ *   formulas give it (a NaN norm gives c = NaN, as torch's clamp does; no special case).
+ *   Update, with lambda = weight_decay where bit k of decay_groups is set and 0 elsewhere:
+ *     GAT_OPT_SGD    d = g^ + lambda p;  buf = mu buf + d (buf starts at 0: the first step gives buf = d, torch's dampening = 0);
+ *                    d = d + mu buf with GAT_OPT_NESTEROV, else d = buf;  p -= lr d.  With mu = 0 no buf exists and d is used as it is.
+ *     GAT_OPT_ADAM   d = g^ + lambda p (L2, torch.optim.Adam(weight_decay=));  m = b1 m + (1 - b1) d;  v = b2 v + (1 - b2) d d;
+ *                    m^ = m / (1 - b1^t);  v^ = v / (1 - b2^t);  p -= lr m^ / (sqrt(v^) + eps)   — the operations of gat_step_adam's kernel
+ *     GAT_OPT_ADAMW  p *= 1 - lr lambda first, then the Adam update with d = g^ (torch.optim.AdamW)
+ *   The two bias corrections 1 - b^t are formed once per block (powf on (float)t).  An entry with g = 0, lambda = 0 and zero state comes
+ *   back bit for bit.
+ * t and lr live on the device.  t is a 64-bit counter that starts at 0 and is advanced by one BEFORE use (the first step uses t = 1), by
+ * one lane of the first launch; the second launch reads it.  gat_set_lr writes the device scalar on the context's stream (a one-lane
+ * launch, no synchronisation): it does not re-arm a captured graph, so a learning-rate schedule costs nothing.
+ * Kernels (csrc/gat_optimizer.hip): an optimizer step is TWO launches whatever the number of groups.  Both run over a block table built on
+ * the host at gat_set_optimizer — rows {group, first, count} of at most 1024 entries, never straddling two groups.  opt_prepare writes each
+ * block's sum of squares (lane-strided, wave butterfly, waves ascending) and advances t (GAT_CLIP_NONE: one block that only advances t);
+ * opt_apply adds the partials it needs in ascending block order (its group's, or all of them with the groups ascending), forms c_k, reads t
+ * and lr and updates its entries; block 0 leaves the norms for gat_optimizer_info.  No float atomics, no fences, no cooperative launch: the
+ * result is a function of the packed sizes alone, bitwise reproducible, the same in a replay.  Timed under GAT_K_MISC;
+ * gat_algorithmic_bytes* are unchanged (the optimizer never was priced).
+ * State rules.  gat_set_optimizer counts as a first gat_params_* call: the packed sizes are final after it (a later gat_set_residual or
+ * any other size-changing setter gives GAT_E_STATE).  It allocates and zeroes the state of the kind: m and v for the Adam kinds, buf for SGD
+ * with momentum > 0.  A second call with the same kind keeps state and t and replaces the hyper-parameters (lr included); another kind
+ * frees the old state, zeroes the new one and sets t = 0.  Either way a captured step graph is dropped (the hyper-parameters other than lr
+ * are kernel arguments).  The state is the optimizer's own: gat_step_adam keeps its own moments, and gat_clip / gat_step_sgd /
+ * gat_step_adam / gat_zero_grad neither read nor write anything of this section.
+ * GAT_E_INVALID, with a text: a null config; a kind, flag or clip mode outside the enums; GAT_OPT_NESTEROV without momentum > 0 or on an
+ * Adam kind; a beta outside (0, 1) (Adam kinds); eps, lr, weight_decay or momentum negative or not finite; momentum >= 1; a clip mode other
+ * than NONE with a threshold that is not finite and > 0; a bit of decay_groups at or above group 10 unless the mask is exactly 0xFFFFFFFF.
+ * Works with every context gat_step works on (all features, bf16 storage, shards with a transport: the update then reads the gradients the
+ * all-reduce has summed, every rank takes the same step).  Refused: gat_optimizer_step, gat_train_step and the state calls before
+ * gat_set_optimizer (GAT_E_STATE); capturing gat_train_step with a transport (gat_step_graph's own refusal). */
+enum { GAT_OPT_SGD = 1, GAT_OPT_ADAM = 2, GAT_OPT_ADAMW = 3 };
+enum { GAT_OPT_NESTEROV = 1 };
+enum { GAT_CLIP_NONE = 0, GAT_CLIP_PER_GROUP = 1, GAT_CLIP_GLOBAL = 2 };
+typedef struct gat_optimizer_config {
+    int32_t kind, flags; float lr, momentum, beta1, beta2, eps, weight_decay;
+    uint32_t decay_groups;          /* bit k = GAT_PARAM_* group k; 0xFFFFFFFF = all (torch's behaviour) */
+    int32_t clip_mode; float clip_threshold;
+} gat_optimizer_config;
+int gat_set_optimizer(gat_ctx* ctx, const gat_optimizer_config* cfg);
+int gat_optimizer_step(gat_ctx* ctx);                       /* prepare + apply; GAT_E_STATE before gat_set_optimizer */
+int gat_set_lr(gat_ctx* ctx, float lr);                     /* negative or not finite: GAT_E_INVALID */
+/* Synchronises.  Any pointer may be NULL.  *t: steps taken; *lr: the device scalar; group_norms [10]: n_k of the last step (0 for an empty
+ * group), *global_norm: n of the last step under GAT_CLIP_GLOBAL, else 0.  With GAT_CLIP_NONE no norm is formed: all stay what they were (0
+ * at first). */
+int gat_optimizer_info(gat_ctx* ctx, gat_optimizer_config* cfg, int64_t* t, float* lr, float* global_norm, float* group_norms /* [10] or NULL */);
+/* One group of one state buffer, to / from the host (checkpoints).  `which` must be a state the current configuration has (M, V: the Adam
+ * kinds; MOMENTUM: SGD with momentum > 0), else GAT_E_INVALID; the size rules are gat_params_get's (a group that is off has count 0 and the
+ * call is a no-op).  set writes into the same buffers, so a captured graph stays valid; gat_optimizer_step_count_set (t >= 0) likewise. */
+enum { GAT_OPT_STATE_M = 0, GAT_OPT_STATE_V = 1, GAT_OPT_STATE_MOMENTUM = 2 };
+int gat_optimizer_state_get(gat_ctx* ctx, int which, int group, float* host, int64_t count);
+int gat_optimizer_state_set(gat_ctx* ctx, int which, int group, const float* host, int64_t count);
+int gat_optimizer_step_count_set(gat_ctx* ctx, int64_t t);
+/* One epoch body: zero the packed gradients (gat_zero_grad's memset), the body of gat_step, gat_optimizer_step — on the context's stream,
+ * in that order.  Returns the loss sum and #correct of the forward BEFORE the update, as gat_step does.  With gat_step_graph(ctx, 1) the
+ * whole sequence is captured into the one replay slot after one eager call, like gat_step; the slot remembers which of the two entry
+ * points it holds, and calling the other one on a captured (or warmed) slot drops it: that call runs eagerly, the next one captures.
+ * Everything that re-arms gat_step re-arms it too, and gat_step_graph_state keeps its meaning.  The batch-norm running update and the
+ * dropout counter advance once per call, replay included.  With a transport it runs eagerly. */
+int gat_train_step(gat_ctx* ctx, float* loss_sum, int32_t* n_correct);
+
 /* ---- op-level entry points, whole layers: caller-provided DEVICE pointers in the reference layouts
  *      (unit parity).  `stream` may be NULL (default stream).  One entry point per reference KERNEL: below. ---- */
 /* a1  csr_to_coo_kernel E:67-84 */
